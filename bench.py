@@ -14,19 +14,24 @@ phase_timed, phase_replica_check, rank0_report, composed by run_bench().  main()
 tests/test_distributed_gloo.py makes gloo / cpu Jobs around the emulator build of the product sources and runs the same
 functions at world sizes 2 and 3, so the N > 1 control flow has executed before an 8-GPU lease runs it.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run does what the headline needs: synthetic data, the GPU build, the smallest ef_search
+of the ladder that reaches the recall target, W warm-up steps, EXACTLY K timed steps, the line (`value`, `ms_per_step`, `config`,
+`build`, `roofline` without `traffic`).  `--dump-outputs DIR` writes the last timed step's answers (dump_outputs()).
+Extra objects:
   roofline     HBM bound: the bytes one launch requests by the kernel's own counters — f32 rows of the pushed candidates the
                reject filter did not turn down + compact rows of the candidates it examined + adjacency rows +
                results; = SURVEY 8(d)'s B_q = n_dist*4*D + n_exp0*256 + n_expU*128 + 8*ef when nothing is filtered, and that
                figure is kept beside it as `survey_8d` — / average kernel duration measured with HIP events on the launch
-               stream; `traffic` = fabric bytes per launch from two child passes of this command under rocprofv3 --pmc,
+               stream; `traffic` (--full) = fabric bytes per launch from two child passes of this command under rocprofv3 --pmc,
                calibrated in the same pass on both request patterns (N = 1).
+  replica_check (N > 1, and under torch.distributed.run at N = 1) every rank's answers for a common sample against rank 0's
+               (digest), rank 0's against the oracle (--full).
+Everything below runs with --full only (full_report()), as do the in-process RCCL child at N > 1 and the build's cpu_baseline:
+  single_query, pcie_inclusive  one query per call, T host threads of scalar calls, host-pointer batches.
   cpu_baseline the CPU oracle (restated reference, NOT the Rust crate) searching the SAME graph
                on the host cores for a bounded query sample (rank 0 at N = 1 only).
   parity       (N = 1) the oracle's answers for a query sample at ef_search 100 / 200 / the timed one compared with
                the GPU's: ids, order, counts, distance bits, work counters.
-  replica_check (N > 1, and under torch.distributed.run at N = 1) every rank's answers for a common sample against rank 0's
-               (digest), rank 0's against the oracle.
   checks       (--check) size-independent properties of the results and of the built graph; tests/ assert on them.
 """
 import argparse
@@ -290,7 +295,15 @@ def parse_args(argv=None):
     ap.add_argument("--rccl-child", type=int, default=0, help=argparse.SUPPRESS)        # internal: devices of the in-process replication child
     ap.add_argument("--launch-timeout", type=float, default=3000.0, help="--gpus N > 1 started without a launcher: seconds the N ranks get")
     ap.add_argument("--collective-timeout", type=float, default=900.0, help="bound of every torch.distributed wait (C5 broadcasts 33.8 GB)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true", help="also the measurements and checks beyond the headline: roofline traffic, scalar "
+                    "calls, host-pointer rates, CPU baselines, oracle parity, --check, the in-process RCCL child")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the last timed step's answers (rank 0) as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.check and not args.full:
+        ap.error("--check needs --full (its graph checks run against the CPU oracle)")
+    return args
 
 
 class Job:
@@ -480,6 +493,31 @@ def phase_timed(job, r, outs, warmup, steps):
     return elapsed
 
 
+def dump_outputs(dirname, outs, budget=64 << 20):
+    """--dump-outputs: the answers of the last timed step as a caller of Hnsw::search receives them, one DIR/<name>.npy each —
+    pid [nq, ef] (past `count`: INVALID, as the host-pointer call pads), distance [nq, ef] (past `count`: +inf), count [nq],
+    counters [nq, 3] {n_dist, n_exp0, n_expU}.  Integers as float64 (exact), distances float32.  A batch above `budget` bytes
+    keeps a fixed sample of query rows (seed 0, in order), the same for the same arguments."""
+    from instant_distance_amd import INVALID
+
+    pid = outs[0].cpu().numpy().view(np.uint32).copy()
+    dist = outs[1].cpu().numpy().copy()
+    cnt = outs[2].cpu().numpy().view(np.uint32)
+    ctr = outs[3].cpu().numpy().view(np.uint32)
+    pad = np.arange(pid.shape[1])[None, :] >= cnt[:, None]
+    pid[pad] = INVALID
+    dist[pad] = np.inf
+    arrays = {"pid": pid.astype(np.float64), "distance": dist, "count": cnt.astype(np.float64), "counters": ctr.astype(np.float64)}
+    row_bytes = sum(a[:1].nbytes for a in arrays.values())
+    nq = pid.shape[0]
+    if nq * row_bytes > budget:
+        rows = np.sort(np.random.default_rng(0).choice(nq, budget // row_bytes, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def answers_digest(arrays):
     """63 bits over ids + distance bits + counts + work counters (fits a signed int64 tensor)"""
     import hashlib
@@ -589,6 +627,8 @@ def run_bench(job, args):
 
     # ---- timed region ----
     elapsed = phase_timed(job, r, outs, args.warmup, args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs)              # before anything else writes into `outs`
 
     replica_check, d_sample, sample_np = None, None, None
     if job.multi:
@@ -604,12 +644,11 @@ def run_bench(job, args):
 
 
 def rank0_report(job, args, cfgd, ida, r, outs, hnsw, d_pts, build, m):
-    """Rank 0 after the timed region: the JSON line's objects (roofline from the kernel's own counters and HIP events, the
-    reference's scalar call pattern, the host-pointer rate, and the CPU oracle as checker / baseline)."""
+    """Rank 0 after the timed region: the JSON line (roofline from the kernel's own counters and HIP events; with --full also
+    the measured traffic and full_report()'s objects)."""
     torch, world = job.torch, job.world
     n, dim, k, nq, nq_total, chosen = m["n"], m["dim"], m["k"], m["nq"], m["nq_total"], m["chosen"]
-    search, d_q, run, alloc_out = r.search, r.d_q, r.run, r.alloc_out
-    sample_out, replica_check = m["sample_out"], m["replica_check"]
+    search, replica_check = r.search, m["replica_check"]
     elapsed = m["elapsed"]
     ms_per_step = elapsed / args.steps * 1e3
     value = nq_total / (elapsed / args.steps)
@@ -643,8 +682,8 @@ def rank0_report(job, args, cfgd, ida, r, outs, hnsw, d_pts, build, m):
             break
         except Exception:  # noqa: BLE001
             continue
-    traffic, traffic_why = (None, "skipped (--no-traffic, N > 1, or a 10M-point configuration)")
-    if not args.no_traffic and world == 1 and job.cuda and n * dim <= 2_000_000_000:
+    traffic, traffic_why = (None, "skipped (no --full, --no-traffic, N > 1, or a 10M-point configuration)")
+    if args.full and not args.no_traffic and world == 1 and job.cuda and n * dim <= 2_000_000_000:
         compact_b = examined * compact_row
         traffic, traffic_why = measure_traffic(args, n, dim, nq, chosen, mix={"rows": launch_bytes - compact_b, "compact": compact_b})
     roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
@@ -669,7 +708,50 @@ def rank0_report(job, args, cfgd, ida, r, outs, hnsw, d_pts, build, m):
                                       "went below those bytes, not that HBM ran faster"},
                 "n_dist_per_query": round(float(ctr[:, 0].mean()), 1) if nq else 0.0, "n_exp0_per_query": round(float(ctr[:, 1].mean()), 1) if nq else 0.0,
                 "n_expU_per_query": round(float(ctr[:, 2].mean()), 1) if nq else 0.0}
+    extra = full_report(job, args, cfgd, ida, r, outs, hnsw, d_pts, build, m) if args.full else {}
 
+    recall = m["recall"]
+    out = {"commit": source_stamp(),
+           "metric": f"queries/sec @ recall@10>=0.95, {'1M' if n == 1_000_000 else n}x{dim}-d f32; index build points/sec",
+           "value": round(value, 1), "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+           "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "strong" if m["split"] else "weak",
+           "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+           "config": {"workload": f"{cfgd['what']} — {n}x{dim}-d f32 fastText-shape synthetic (32-d latent, L2-normalised), "
+                                  f"Builder::build on GPU + {nq}-query Hnsw::search batch per GPU, k={k}",
+                      "name": args.config, "n": n, "dim": dim, "queries_per_gpu": nq, "k": k, "ef_search": chosen,
+                      "recall_at_10": round(recall, 4), "recall_target": args.recall_target,
+                      "recall_target_met": bool(recall >= args.recall_target), "recall_queries": m["gtq"],
+                      "ef_sweep_recall": m["sweep"], "parallelism": f"query-shard x{world}, index replicated",
+                      "replication": m["replication"], "replicate_seconds": round(m["t_rep"], 3), **m["rep"]},
+           "build": build, "roofline": roofline}
+    if args.full:
+        out.update({"cpu_baseline": extra["cpu"], "parity": extra["parity"], "single_query": extra["single"], "pcie_inclusive": extra["pcie"]})
+    try:                                                     # rank 0's footprint (C5: 30.7 GB of points + the index + the oracle's leg)
+        import resource
+        free_b, total_b = torch.cuda.mem_get_info() if job.cuda else (0, 0)
+        out["memory"] = {"host_rss_peak_gb": round(resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1048576.0, 2),
+                         "hbm_in_use_at_end_gb": round((total_b - free_b) / 1e9, 2), "hbm_total_gb": round(total_b / 1e9, 1)}
+    except Exception:  # noqa: BLE001
+        pass
+    if replica_check is not None:
+        out["replica_check"] = replica_check
+    if extra.get("checks") is not None:
+        out["checks"] = extra["checks"]
+    if extra.get("cpu"):
+        out["gpu_over_cpu"] = round(value / extra["cpu"]["value"], 2)
+    return out
+
+
+def full_report(job, args, cfgd, ida, r, outs, hnsw, d_pts, build, m):
+    """--full, rank 0 after the timed region: the reference's scalar call pattern, the host-pointer rate, --check, and the CPU
+    oracle as checker / baseline (writes the build's cpu_baseline into `build` and the oracle's verdict into `replica_check`).
+    -> {single, pcie, checks, cpu, parity}"""
+    import glob
+
+    torch, world = job.torch, job.world
+    n, dim, nq, chosen = m["n"], m["dim"], m["nq"], m["chosen"]
+    search, d_q, run, alloc_out = r.search, r.d_q, r.run, r.alloc_out
+    sample_out, replica_check = m["sample_out"], m["replica_check"]
     # the reference's own call pattern: one query per call (`Hnsw::search`).  Outside the timed region.
     lat_n = min(32, nq)
     for i in range(lat_n):
@@ -809,36 +891,7 @@ def rank0_report(job, args, cfgd, ida, r, outs, hnsw, d_pts, build, m):
                          "(C oracle = restated reference, not the Rust crate)",
                "seconds": round(tc, 2), "ids_identical_to_gpu": same,
                "ids_distance_bits_counts_and_work_counters_identical_to_gpu": same_all}
-
-    recall = m["recall"]
-    out = {"commit": source_stamp(),
-           "metric": f"queries/sec @ recall@10>=0.95, {'1M' if n == 1_000_000 else n}x{dim}-d f32; index build points/sec",
-           "value": round(value, 1), "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-           "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "strong" if m["split"] else "weak",
-           "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-           "config": {"workload": f"{cfgd['what']} — {n}x{dim}-d f32 fastText-shape synthetic (32-d latent, L2-normalised), "
-                                  f"Builder::build on GPU + {nq}-query Hnsw::search batch per GPU, k={k}",
-                      "name": args.config, "n": n, "dim": dim, "queries_per_gpu": nq, "k": k, "ef_search": chosen,
-                      "recall_at_10": round(recall, 4), "recall_target": args.recall_target,
-                      "recall_target_met": bool(recall >= args.recall_target), "recall_queries": m["gtq"],
-                      "ef_sweep_recall": m["sweep"], "parallelism": f"query-shard x{world}, index replicated",
-                      "replication": m["replication"], "replicate_seconds": round(m["t_rep"], 3), **m["rep"]},
-           "build": build, "roofline": roofline, "cpu_baseline": cpu, "parity": parity, "single_query": single,
-           "pcie_inclusive": pcie}
-    try:                                                     # rank 0's footprint (C5: 30.7 GB of points + the index + the oracle's leg)
-        import resource
-        free_b, total_b = torch.cuda.mem_get_info() if job.cuda else (0, 0)
-        out["memory"] = {"host_rss_peak_gb": round(resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1048576.0, 2),
-                         "hbm_in_use_at_end_gb": round((total_b - free_b) / 1e9, 2), "hbm_total_gb": round(total_b / 1e9, 1)}
-    except Exception:  # noqa: BLE001
-        pass
-    if replica_check is not None:
-        out["replica_check"] = replica_check
-    if checks is not None:
-        out["checks"] = checks
-    if cpu:
-        out["gpu_over_cpu"] = round(value / cpu["value"], 2)
-    return out
+    return {"single": single, "pcie": pcie, "checks": checks, "cpu": cpu, "parity": parity}
 
 
 def inproc_rccl_child(args, world, n, dim, chosen):
@@ -938,7 +991,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        if job.multi and not args.no_inproc_rccl:
+        if job.multi and args.full and not args.no_inproc_rccl:
             try:
                 gone, waited = wait_for_peers(pids)
                 child = inproc_rccl_child(args, world, out["config"]["n"], out["config"]["dim"], out["config"]["ef_search"])

@@ -1,12 +1,16 @@
 """`python bench.py --gpus N` must start itself: the driver's N = 1 command shape (`python bench.py --gpus 1 ...`) repeated at N = 8
 has no launcher around it.  These run without a GPU: the command that would be started, the fail-fast line on a node with too few
-devices, and the pass-through of rank 0's line (Hnsw::search takes &self, core/lib.rs:352-356)."""
+devices, and the pass-through of rank 0's line (Hnsw::search takes &self, core/lib.rs:352-356); and what a plain run
+(no --full) does and writes with --dump-outputs."""
 import json
 import os
 import subprocess
 import sys
 import time
 import types
+
+import numpy as np
+import pytest
 
 import bench
 
@@ -56,3 +60,57 @@ def test_self_launch_passes_rank0_line_through(monkeypatch, capsys):
     assert bench.self_launch(args, ["--gpus", "4"]) == 1
     line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
     assert line["value"] is None and "no result line" in line["error"]
+
+
+def test_plain_run_is_the_headline_and_dumps_the_last_step(engine_loader, tmp_path):
+    """`bench.py --steps K --warmup W` without --full: exactly K timed steps, the headline fields, none of the --full objects;
+    --dump-outputs writes the last timed step's answers, identical for identical arguments (emulated kernels, toy size)."""
+    import torch
+
+    engine_loader("emu")
+    job = bench.Job(torch, dev=torch.device("cpu"))
+    toy = ["--n", "300", "--dim", "12", "--nq", "9", "--steps", "3", "--warmup", "1", "--max-batch", "1", "--gt-queries", "0"]
+    outs, dumps = [], []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        outs.append(bench.run_bench(job, bench.parse_args(toy + ["--dump-outputs", str(d)])))
+        dumps.append({f.name: np.load(f) for f in d.iterdir()})
+    out = outs[0]
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["unit"] == "queries/s" and out["dtype"] == "f32"
+    assert abs(out["value"] - 9 / (out["ms_per_step"] * 1e-3)) <= 1e-3 * out["value"]
+    assert out["higher_is_better"] is True and out["metric"].startswith("queries/sec @ recall@10>=0.95")
+    assert not {"cpu_baseline", "parity", "single_query", "pcie_inclusive", "checks", "gpu_over_cpu"} & set(out)
+    assert out["roofline"]["traffic"] is None and "cpu_baseline" not in out["build"]
+    ef = out["config"]["ef_search"]
+    a, b = dumps
+    assert set(a) == {"pid.npy", "distance.npy", "count.npy", "counters.npy"}
+    assert a["pid.npy"].shape == (9, ef) and a["distance.npy"].shape == (9, ef) and a["counters.npy"].shape == (9, 3)
+    assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+    assert np.all(a["count.npy"] == min(ef, 300)) and np.all(a["pid.npy"] < 300) and np.all(a["counters.npy"][:, 0] > 0)
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--check"])                 # the oracle's checks belong to --full
+
+
+def test_dump_outputs_pads_like_the_host_call_and_samples_within_budget(tmp_path):
+    import torch
+
+    nq, ef = 50, 4
+    pid = torch.arange(nq * ef, dtype=torch.int32).reshape(nq, ef)
+    dist = torch.rand(nq, ef)
+    cnt = torch.full((nq,), ef, dtype=torch.int32)
+    cnt[7] = 2
+    ctr = torch.randint(0, 1000, (nq, 3), dtype=torch.int32)
+    bench.dump_outputs(str(tmp_path / "all"), (pid, dist, cnt, ctr))
+    got = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in ("pid", "distance", "count", "counters")}
+    assert got["pid"].dtype == np.float64 and got["distance"].dtype == np.float32
+    assert np.all(got["pid"][7, 2:] == 0xFFFFFFFF) and np.all(np.isinf(got["distance"][7, 2:]))
+    assert np.array_equal(got["pid"][8], pid[8].numpy()) and np.array_equal(got["counters"], ctr.numpy())
+    # above the byte budget: a fixed, ordered sample of whole query rows
+    row = ef * 8 + ef * 4 + 8 + 3 * 8
+    bench.dump_outputs(str(tmp_path / "s1"), (pid, dist, cnt, ctr), budget=10 * row)
+    bench.dump_outputs(str(tmp_path / "s2"), (pid, dist, cnt, ctr), budget=10 * row)
+    s1, s2 = (np.load(tmp_path / s / "pid.npy") for s in ("s1", "s2"))
+    assert s1.shape == (10, ef) and np.array_equal(s1, s2)
+    rows = (s1[:, 0] // ef).astype(int)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(s1, got["pid"][rows])

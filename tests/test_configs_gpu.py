@@ -1,5 +1,5 @@
 """BASELINE.json configurations C4 (1M x 768-d, 65,536 batched queries) and C5 (10M x 768-d, one GPU's replica) at FULL
-size on the MI355X, through the same code that prints their bench lines (`bench.py --config C4|C5 --check`):
+size on the MI355X, through the same code that prints their bench lines (`bench.py --config C4|C5 --full --check`):
 
   * the index is built on the GPU from device-resident points (Builder::build, core/lib.rs:209-345);
   * the CPU oracle searches the SAME exported graph (the graph is an input of Hnsw::search, core/lib.rs:352-383) for a
@@ -24,7 +24,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def run_config(name, extra=()):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", name, "--check", "--steps", "3", "--warmup", "1",
-           "--threads", "", "--cpu-sample", "512", "--cpu-build-sample", "0", "--no-traffic", *extra]
+           "--threads", "", "--cpu-sample", "512", "--cpu-build-sample", "0", "--no-traffic", "--full", *extra]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -80,7 +80,7 @@ def test_bench_under_torchrun_one_rank_gpu():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "C2", "--points", "50000", "--nq", "2000",
-           "--steps", "3", "--warmup", "1", "--threads", "", "--cpu-sample", "512", "--cpu-build-sample", "0", "--no-traffic", "--check"]
+           "--steps", "3", "--warmup", "1", "--threads", "", "--cpu-sample", "512", "--cpu-build-sample", "0", "--no-traffic", "--full", "--check"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -199,7 +199,7 @@ def _run_world(world, scenario, argv, timeout=400):
 
 
 TOY = ["--n", "300", "--dim", "12", "--steps", "2", "--warmup", "1", "--threads", "", "--no-traffic", "--max-batch", "1",
-       "--gt-queries", "0", "--parity-queries", "8"]
+       "--gt-queries", "0", "--parity-queries", "8", "--full"]
 
 
 @pytest.mark.timeout(900)
