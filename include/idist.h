@@ -294,6 +294,65 @@ idist_status idist_search_batch_sharded(const idist_index* const* replicas, idis
                                         uint32_t* out_pid, float* out_dist, uint32_t* out_count,
                                         uint32_t* out_counters);
 
+/* ---- partitioned index: several indexes searched as one ------------------------ */
+/* The reference has one `Hnsw` per set of points.  A partitioned index is an ordered list of 1..64 ordinary indexes
+ * ("parts") with the same dim, metric and ef_search, on any devices: an index larger than one GPU's memory, built on several
+ * GPUs side by side.  ("Partitioned", not "sharded": sharded above means QUERIES split over replicas of one index.)
+ *   global id of a point = base[p] + its PointId inside part p, base[p] = points in parts 0..p-1;
+ *   search of one query  = Hnsw::search (core/lib.rs:352-383) on every part, ids made global, the lists merged by the
+ *                          reference's `Candidate` order (core/types.rs:229-234: distance, then id), the first ef_search kept;
+ *                          count = min(ef_search, sum of the parts' counts); counters = the parts' counters summed.
+ * One part is the identity: the arrays idist_search_batch returns for that part.  Empty parts contribute nothing.
+ *
+ * idist_merge_topk_device is that merge on its own: n_lists (1..64) sorted lists per query, d_pid / d_dist
+ * [n_lists][nq][width], d_count [n_lists][nq], d_counters [n_lists][nq][3] (may be NULL), all in the memory of `device`;
+ * list l's ids are offset by base[l] (HOST array of n_lists entries, read before the call returns).  Output as
+ * idist_search_batch_device writes it with ef_search = out_width: d_out_pid / d_out_dist [nq][out_width] padded with
+ * IDIST_INVALID / +inf, d_out_count [nq], d_out_counters [nq][3] (may be NULL).  width, out_width: 1..IDIST_MAX_EF.  Only the
+ * first min(count, width) entries of a list are read as results — whatever lies behind them is ignored.  Distances must be
+ * what the engine produces (non-negative, one NaN pattern): they are ordered by their bit patterns.  Enqueued on
+ * `hip_stream` (a hipStream_t, may be NULL) without synchronising. */
+idist_status idist_merge_topk_device(const void* d_pid, const void* d_dist, const void* d_count,
+                                     const void* d_counters, uint32_t n_lists, uint32_t nq, uint32_t width,
+                                     const uint32_t* base, uint32_t out_width, void* d_out_pid, void* d_out_dist,
+                                     void* d_out_count, void* d_out_counters, int32_t device, void* hip_stream);
+
+typedef struct idist_partitioned idist_partitioned;
+typedef struct idist_partitioned_info {
+    uint32_t n_parts, dim, ef_search;
+    int32_t metric;
+    int32_t merge_device;       /* the device of part 0: the parts' lists meet and are merged there */
+    uint64_t n;                 /* points in all parts */
+    uint32_t base[65];          /* base[p] = first global id of part p; base[n_parts] = n */
+} idist_partitioned_info;
+/* The parts are BORROWED: the caller keeps every index alive until idist_partitioned_free and frees it afterwards.  The
+ * object is one `&mut Search` over all parts (core/lib.rs:352-356): it owns a search context and a stream per part and
+ * the staging memory of the merge, and is used by one thread at a time.  IDIST_ERR_INVALID_ARG (naming the part) when
+ * n_parts is 0 or above 64, a part is NULL, dim / metric / ef_search differ, or the points together do not fit a PointId. */
+idist_status idist_partitioned_new(const idist_index* const* parts, uint32_t n_parts, idist_partitioned** out);
+void idist_partitioned_free(idist_partitioned* p);
+idist_status idist_partitioned_get_info(const idist_partitioned* p, idist_partitioned_info* out);
+/* Hnsw::search over all parts for nq host queries; shapes and padding exactly as idist_search_batch, ids global.  The queries
+ * are uploaded once per distinct device, every part is searched on its own stream (idist_search_batch_device) straight into
+ * its slice of the staging memory on the merge device (parts elsewhere: into memory of their own device, then one peer copy),
+ * one merge kernel, results to the host.  Blocks until done.  Strict ties: a part whose tie region overflowed is searched
+ * again with the larger region, as idist_search_batch does — IDIST_ERR_TIE_OVERFLOW never reaches the caller.  The parts'
+ * dim / metric / ef_search are compared again at every call (idist_index_set_ef_search may have changed one). */
+idist_status idist_partitioned_search_batch(idist_partitioned* p, const float* queries, uint32_t nq,
+                                            uint32_t* out_pid, float* out_dist, uint32_t* out_count,
+                                            uint32_t* out_counters);
+/* Exact k nearest neighbours over all parts: the same merge, width k, over every part's idist_bruteforce (part p contributes
+ * min(k, n_p) items) — the brute-force check of tests/all.rs:60-67 on the points concatenated in global-id order, ties
+ * (distance, then id) included.  out_pid / out_dist: nq*k, padded with IDIST_INVALID / +inf when fewer than k points exist. */
+idist_status idist_partitioned_bruteforce(idist_partitioned* p, const float* queries, uint32_t nq, uint32_t k,
+                                          uint32_t* out_pid, float* out_dist);
+/* HIP-event duration of the last merge kernel launched through p, milliseconds. */
+idist_status idist_partitioned_last_merge_ms(idist_partitioned* p, float* ms);
+/* ms[i] = HIP-event duration of part i's last search kernel (idist_search_ctx_last_kernel_ms of the context p owns for it),
+ * milliseconds; 0 for an empty part, -1 where no launch was timed.  *n_out = entries written (<= cap): what the merge's
+ * own time is set against. */
+idist_status idist_partitioned_last_search_kernel_ms(idist_partitioned* p, float* ms, uint32_t cap, uint32_t* n_out);
+
 /* Point::distance for id lists (core/lib.rs:780-782 as used at :709-710): out[q][i] =
  * distance(queries[q], points[ids[q][i]]) for i < n_ids; IDIST_INVALID ids give +inf.
  * Host pointers. The batched gather-L2 kernel on its own. */

@@ -11,6 +11,7 @@ The directory name is fixed by the repo contract; import it as
 # it imports torch).
 from ._capi import (INVALID, M, M2, METRIC_L2, METRIC_L2SQ, MAX_EF, TIES_DROP, TIES_STRICT, IdistError, LIB_PATH)
 from .api import (BatchResult, Builder, Heuristic, Hnsw, HnswMap, Item, MapItem, PointId, Search)
+from .partition import PartitionedHnsw
 
-__all__ = ["Builder", "Heuristic", "Hnsw", "HnswMap", "Search", "Item", "MapItem", "PointId", "BatchResult",
+__all__ = ["Builder", "Heuristic", "Hnsw", "HnswMap", "PartitionedHnsw", "Search", "Item", "MapItem", "PointId", "BatchResult",
            "IdistError", "INVALID", "M", "M2", "METRIC_L2", "METRIC_L2SQ", "MAX_EF", "TIES_DROP", "TIES_STRICT", "LIB_PATH"]

@@ -76,6 +76,13 @@ class BuildStats(C.Structure):
     ]
 
 
+class PartitionedInfo(C.Structure):
+    _fields_ = [
+        ("n_parts", C.c_uint32), ("dim", C.c_uint32), ("ef_search", C.c_uint32), ("metric", C.c_int32),
+        ("merge_device", C.c_int32), ("n", C.c_uint64), ("base", C.c_uint32 * 65),
+    ]
+
+
 # every symbol include/idist.h declares: name -> (restype, argtypes)
 _f32p = C.POINTER(C.c_float)
 _u32p = C.POINTER(C.c_uint32)
@@ -116,6 +123,15 @@ SYMBOLS = {
     "idist_replicate_rccl": (C.c_int32, [_vp, C.POINTER(C.c_int32), C.c_uint32, C.POINTER(_vp), C.POINTER(C.c_double)]),
     "idist_search_batch_sharded": (C.c_int32, [C.POINTER(_vp), C.POINTER(_vp), C.c_uint32, _f32p, C.c_uint32, _u32p, _f32p,
                                                _u32p, _u32p]),
+    "idist_merge_topk_device": (C.c_int32, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, _vp, _vp, _vp,
+                                            _vp, C.c_int32, _vp]),
+    "idist_partitioned_new": (C.c_int32, [C.POINTER(_vp), C.c_uint32, C.POINTER(_vp)]),
+    "idist_partitioned_free": (None, [_vp]),
+    "idist_partitioned_get_info": (C.c_int32, [_vp, C.POINTER(PartitionedInfo)]),
+    "idist_partitioned_search_batch": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p, _f32p, _u32p, _u32p]),
+    "idist_partitioned_bruteforce": (C.c_int32, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),
+    "idist_partitioned_last_merge_ms": (C.c_int32, [_vp, C.POINTER(C.c_float)]),
+    "idist_partitioned_last_search_kernel_ms": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p]),
     "idist_distance_batch": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, _f32p]),
     "idist_filter_bound_batch": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, _f32p]),
     "idist_bruteforce": (C.c_int32, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),

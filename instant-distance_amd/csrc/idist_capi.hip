@@ -5,6 +5,7 @@
 #include "idist_kernels.hpp"
 #include "idist_mfma.hpp"
 #include "idist_combine.hpp"
+#include "idist_merge.hpp"
 
 #ifndef IDIST_EMU
 #include <hip/hip_runtime.h>
@@ -329,6 +330,38 @@ struct idist_search_ctx {
     // copies of what idist_search_ctx_status needs, so that it never reads through `idx`
     int32_t tie_policy = IDIST_TIES_STRICT;
     uint32_t base_tie_cap = kTieCap, stride = 0, last_ef = 0;
+};
+
+// A partitioned index (include/idist.h): borrowed parts + everything one caller needs to search them as one — the role of one
+// `&mut Search` over all parts.  Staging memory only grows.
+struct idist_partitioned {
+    struct Part {
+        const idist_index* idx = nullptr;
+        uint64_t uid = 0;
+        idist_search_ctx* ctx = nullptr;     // nullptr: empty part (nothing to search); its stream is the part's stream
+        int dev_slot = 0;                    // index into `devs`
+        // parts away from the merge device write here first, then one peer copy per array
+        uint32_t *r_pid = nullptr, *r_cnt = nullptr, *r_ctr = nullptr;
+        float* r_dist = nullptr;
+        size_t r_cap_out = 0, r_cap_nq = 0;
+    };
+    struct Dev {
+        int32_t device = 0;
+        float* d_q = nullptr;                // the batch's queries, uploaded once per distinct device
+        size_t cap_q = 0;
+    };
+    std::vector<Part> parts;
+    std::vector<Dev> devs;
+    uint32_t base[kMergeMaxLists + 1] = {0};
+    uint32_t dim = 0;
+    int32_t metric = 0, merge_device = 0;
+    // on the merge device: the parts' lists [P][nq][width] and the merged result [nq][out_width]
+    uint32_t *s_pid = nullptr, *s_cnt = nullptr, *s_ctr = nullptr, *o_pid = nullptr, *o_cnt = nullptr, *o_ctr = nullptr;
+    float *s_dist = nullptr, *o_dist = nullptr;
+    size_t cap_slab = 0, cap_nq = 0, cap_o = 0;   // elements: P*nq*width, nq, nq*out_width
+    hipStream_t stream = nullptr;            // the merge and the copies of its result
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool timed = false;
 };
 
 namespace {
@@ -2244,6 +2277,326 @@ idist_status idist_search_batch_sharded(const idist_index* const* replicas, idis
     return IDIST_OK;
 }
 
+// ---- partitioned index: several indexes searched as one, merged on the device ----
+static idist_status launch_merge(MergeArgs a, hipStream_t stream) {
+    const size_t keys = (size_t)a.n_lists * a.width * 8;
+    const bool lds = keys + kMergeHeadBytes <= kMergeLdsBudget;
+    a.vec4 = (a.width % 4u == 0u && ((uintptr_t)a.pid % 16u) == 0 && ((uintptr_t)a.dist % 16u) == 0) ? 1u : 0u;
+    const uint32_t grid = std::min<uint32_t>(a.nq, 16384u);          // one wave per query; the kernel strides over the rest
+    if (lds) {
+        auto kM = merge_topk_kernel<true>;
+        IDIST_LAUNCH(kM, grid, 64, kMergeHeadBytes + keys, stream, a);
+    } else {
+        auto kM = merge_topk_kernel<false>;
+        IDIST_LAUNCH(kM, grid, 64, (size_t)kMergeHeadBytes, stream, a);
+    }
+    HIPCHK(hipGetLastError());
+    return IDIST_OK;
+}
+
+idist_status idist_merge_topk_device(const void* d_pid, const void* d_dist, const void* d_count, const void* d_counters,
+                                     uint32_t n_lists, uint32_t nq, uint32_t width, const uint32_t* base, uint32_t out_width,
+                                     void* d_out_pid, void* d_out_dist, void* d_out_count, void* d_out_counters,
+                                     int32_t device, void* hip_stream) {
+    const uint32_t max_w = IDIST_MAX_EF;
+    if (n_lists == 0 || n_lists > kMergeMaxLists) return fail(IDIST_ERR_INVALID_ARG, "n_lists %u out of [1,%u]", n_lists, kMergeMaxLists);
+    if (width == 0 || width > max_w || out_width == 0 || out_width > max_w)
+        return fail(IDIST_ERR_INVALID_ARG, "width %u / out_width %u out of [1,%u]", width, out_width, max_w);
+    if (!base) return fail(IDIST_ERR_INVALID_ARG, "base is null");
+    if (nq == 0) return IDIST_OK;
+    if (!d_pid || !d_dist || !d_count || !d_out_pid || !d_out_dist || !d_out_count) return fail(IDIST_ERR_INVALID_ARG, "null device pointer");
+    int cnt = 0;
+    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return fail(IDIST_ERR_NO_DEVICE, "no HIP device visible; libidist has no CPU path");
+    if (device < 0 || device >= cnt) return fail(IDIST_ERR_INVALID_ARG, "device %d out of range [0,%d)", device, cnt);
+    HIPCHK(hipSetDevice(device));
+    MergeArgs a{};
+    a.pid = (const uint32_t*)d_pid; a.dist = (const uint32_t*)d_dist; a.count = (const uint32_t*)d_count;
+    a.counters = (const uint32_t*)d_counters;
+    a.n_lists = n_lists; a.nq = nq; a.width = width; a.out_width = out_width;
+    a.out_pid = (uint32_t*)d_out_pid; a.out_dist = (uint32_t*)d_out_dist; a.out_count = (uint32_t*)d_out_count;
+    a.out_counters = d_counters ? (uint32_t*)d_out_counters : nullptr;
+    for (uint32_t l = 0; l < n_lists; l++) a.base[l] = base[l];
+    return launch_merge(a, (hipStream_t)hip_stream);
+}
+
+// dim / metric / ef_search of every part against part 0, and the id space; fills base[] (idist_index_set_ef_search can change a
+// part at any time, so this runs at every call)
+static idist_status partitioned_check(idist_partitioned* p, uint32_t* ef_out) {
+    const idist_index* first = p->parts[0].idx;
+    uint64_t n = 0;
+    for (size_t i = 0; i < p->parts.size(); i++) {
+        const idist_index* ix = p->parts[i].idx;
+        if (ix->uid != p->parts[i].uid) return fail(IDIST_ERR_INVALID_ARG, "part %zu is not the index this object was made for", i);
+        if (ix->dim != first->dim) return fail(IDIST_ERR_INVALID_ARG, "part %zu: dim %u differs from part 0's %u", i, ix->dim, first->dim);
+        if (ix->cfg.metric != first->cfg.metric) return fail(IDIST_ERR_INVALID_ARG, "part %zu: metric %d differs from part 0's %d", i, ix->cfg.metric, first->cfg.metric);
+        if (ix->cfg.ef_search != first->cfg.ef_search)
+            return fail(IDIST_ERR_INVALID_ARG, "part %zu: ef_search %u differs from part 0's %u", i, ix->cfg.ef_search, first->cfg.ef_search);
+        p->base[i] = (uint32_t)n;
+        n += ix->n;
+        if (n >= (uint64_t)kInvalid) return fail(IDIST_ERR_INVALID_ARG, "part %zu: %llu points together do not fit a PointId", i, (unsigned long long)n);
+    }
+    p->base[p->parts.size()] = (uint32_t)n;
+    if (ef_out) *ef_out = first->cfg.ef_search;
+    return IDIST_OK;
+}
+
+idist_status idist_partitioned_new(const idist_index* const* parts, uint32_t n_parts, idist_partitioned** out) {
+    if (!out) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (n_parts == 0 || n_parts > kMergeMaxLists) return fail(IDIST_ERR_INVALID_ARG, "n_parts %u out of [1,%u]", n_parts, kMergeMaxLists);
+    if (!parts) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    for (uint32_t i = 0; i < n_parts; i++)
+        if (!parts[i]) return fail(IDIST_ERR_INVALID_ARG, "part %u is null", i);
+    idist_partitioned* p = new idist_partitioned();
+    auto bail = [&](idist_status s) {
+        const std::string keep = g_err;
+        idist_partitioned_free(p);
+        g_err = keep;
+        return s;
+    };
+    p->parts.resize(n_parts);
+    for (uint32_t i = 0; i < n_parts; i++) { p->parts[i].idx = parts[i]; p->parts[i].uid = parts[i]->uid; }
+    p->dim = parts[0]->dim;
+    p->metric = parts[0]->cfg.metric;
+    p->merge_device = parts[0]->device;
+    idist_status s = partitioned_check(p, nullptr);
+    if (s != IDIST_OK) return bail(s);
+    for (uint32_t i = 0; i < n_parts; i++) {
+        idist_partitioned::Part& pt = p->parts[i];
+        int slot = -1;
+        for (size_t d = 0; d < p->devs.size(); d++) if (p->devs[d].device == parts[i]->device) slot = (int)d;
+        if (slot < 0) {
+            idist_partitioned::Dev dv;
+            dv.device = parts[i]->device;
+            p->devs.push_back(dv);
+            slot = (int)p->devs.size() - 1;
+        }
+        pt.dev_slot = slot;
+        if (parts[i]->n && (s = idist_search_ctx_new(parts[i], 0, &pt.ctx)) != IDIST_OK) return bail(s);
+    }
+    hipError_t e;
+    if ((e = hipSetDevice(p->merge_device)) != hipSuccess || (e = hipStreamCreate(&p->stream)) != hipSuccess ||
+        (e = hipEventCreate(&p->ev0)) != hipSuccess || (e = hipEventCreate(&p->ev1)) != hipSuccess)
+        return bail(fail(IDIST_ERR_HIP, "partitioned index set-up failed: %s", hipGetErrorString(e)));
+    *out = p;
+    return IDIST_OK;
+}
+
+void idist_partitioned_free(idist_partitioned* p) {
+    if (!p) return;
+    // (the parts are borrowed and may already be gone: nothing of them is touched here)
+    for (auto& pt : p->parts) {
+        idist_search_ctx_free(pt.ctx);
+        hipFree(pt.r_pid); hipFree(pt.r_dist); hipFree(pt.r_cnt); hipFree(pt.r_ctr);
+    }
+    for (auto& dv : p->devs) hipFree(dv.d_q);
+    hipFree(p->s_pid); hipFree(p->s_dist); hipFree(p->s_cnt); hipFree(p->s_ctr);
+    hipFree(p->o_pid); hipFree(p->o_dist); hipFree(p->o_cnt); hipFree(p->o_ctr);
+    if (p->ev0) hipEventDestroy(p->ev0);
+    if (p->ev1) hipEventDestroy(p->ev1);
+    if (p->stream) hipStreamDestroy(p->stream);
+    delete p;
+}
+
+idist_status idist_partitioned_get_info(const idist_partitioned* p, idist_partitioned_info* out) {
+    if (!p || !out) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    memset(out, 0, sizeof(*out));
+    uint32_t ef = 0;
+    CHK(partitioned_check(const_cast<idist_partitioned*>(p), &ef));
+    out->n_parts = (uint32_t)p->parts.size();
+    out->dim = p->dim;
+    out->ef_search = ef;
+    out->metric = p->metric;
+    out->merge_device = p->merge_device;
+    out->n = p->base[p->parts.size()];
+    for (size_t i = 0; i <= p->parts.size(); i++) out->base[i] = p->base[i];
+    return IDIST_OK;
+}
+
+// staging on the merge device for P lists of `width` per query and a result of `out_width` (the merge device is current)
+static idist_status partitioned_reserve(idist_partitioned* p, uint32_t nq, uint32_t width, uint32_t out_width) {
+    const size_t P = p->parts.size(), slab = P * nq * width, o = (size_t)nq * out_width;
+    if (slab > p->cap_slab) {
+        hipFree(p->s_pid); hipFree(p->s_dist); p->s_pid = nullptr; p->s_dist = nullptr; p->cap_slab = 0;
+        HIPCHK(hipMalloc((void**)&p->s_pid, slab * 4));
+        HIPCHK(hipMalloc((void**)&p->s_dist, slab * 4));
+        p->cap_slab = slab;
+    }
+    if (nq > p->cap_nq) {
+        hipFree(p->s_cnt); hipFree(p->s_ctr); hipFree(p->o_cnt); hipFree(p->o_ctr);
+        p->s_cnt = p->s_ctr = p->o_cnt = p->o_ctr = nullptr; p->cap_nq = 0;
+        HIPCHK(hipMalloc((void**)&p->s_cnt, P * nq * 4));
+        HIPCHK(hipMalloc((void**)&p->s_ctr, P * nq * 12));
+        HIPCHK(hipMalloc((void**)&p->o_cnt, (size_t)nq * 4));
+        HIPCHK(hipMalloc((void**)&p->o_ctr, (size_t)nq * 12));
+        p->cap_nq = nq;
+    }
+    if (o > p->cap_o) {
+        hipFree(p->o_pid); hipFree(p->o_dist); p->o_pid = nullptr; p->o_dist = nullptr; p->cap_o = 0;
+        HIPCHK(hipMalloc((void**)&p->o_pid, o * 4));
+        HIPCHK(hipMalloc((void**)&p->o_dist, o * 4));
+        p->cap_o = o;
+    }
+    return IDIST_OK;
+}
+
+// the merge kernel between two events + its result to the host; every part's list is complete in the staging memory
+static idist_status partitioned_merge(idist_partitioned* p, uint32_t nq, uint32_t width, uint32_t out_width, bool counters,
+                                      uint32_t* out_pid, float* out_dist, uint32_t* out_count, uint32_t* out_counters) {
+    MergeArgs a{};
+    a.pid = p->s_pid; a.dist = (const uint32_t*)p->s_dist; a.count = p->s_cnt; a.counters = counters ? p->s_ctr : nullptr;
+    a.n_lists = (uint32_t)p->parts.size(); a.nq = nq; a.width = width; a.out_width = out_width;
+    a.out_pid = p->o_pid; a.out_dist = (uint32_t*)p->o_dist; a.out_count = p->o_cnt; a.out_counters = counters ? p->o_ctr : nullptr;
+    for (uint32_t l = 0; l < a.n_lists; l++) a.base[l] = p->base[l];
+    HIPCHK(hipEventRecord(p->ev0, p->stream));
+    CHK(launch_merge(a, p->stream));
+    HIPCHK(hipEventRecord(p->ev1, p->stream));
+    p->timed = true;
+    const size_t ob = (size_t)nq * out_width * 4;
+    HIPCHK(hipMemcpyAsync(out_pid, p->o_pid, ob, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipMemcpyAsync(out_dist, p->o_dist, ob, hipMemcpyDeviceToHost, p->stream));
+    if (out_count) HIPCHK(hipMemcpyAsync(out_count, p->o_cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, p->stream));
+    if (counters) HIPCHK(hipMemcpyAsync(out_counters, p->o_ctr, (size_t)nq * 12, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    return IDIST_OK;
+}
+
+idist_status idist_partitioned_search_batch(idist_partitioned* p, const float* queries, uint32_t nq, uint32_t* out_pid,
+                                            float* out_dist, uint32_t* out_count, uint32_t* out_counters) {
+    if (!p) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    uint32_t ef = 0;
+    CHK(partitioned_check(p, &ef));
+    if (nq == 0) return IDIST_OK;
+    if (!queries || !out_count) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    const size_t P = p->parts.size();
+    if (p->base[P] == 0 || ef == 0) {                    // core/lib.rs:359-361
+        memset(out_count, 0, (size_t)nq * 4);
+        if (out_counters) memset(out_counters, 0, (size_t)nq * 12);
+        return IDIST_OK;
+    }
+    if (!out_pid || !out_dist) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    const bool counters = out_counters != nullptr;
+    const size_t qb = (size_t)nq * p->dim * 4, row = (size_t)nq * ef;
+    HIPCHK(hipSetDevice(p->merge_device));
+    CHK(partitioned_reserve(p, nq, ef, ef));
+    // 1. the queries, once per distinct device that has something to search
+    for (size_t d = 0; d < p->devs.size(); d++) {
+        idist_partitioned::Dev& dv = p->devs[d];
+        bool used = false;
+        for (auto& pt : p->parts) used |= pt.ctx && pt.dev_slot == (int)d;
+        if (!used) continue;
+        HIPCHK(hipSetDevice(dv.device));
+        if (qb > dv.cap_q) { hipFree(dv.d_q); dv.d_q = nullptr; dv.cap_q = 0; HIPCHK(hipMalloc((void**)&dv.d_q, qb)); dv.cap_q = qb; }
+        HIPCHK(hipMemcpy(dv.d_q, queries, qb, hipMemcpyHostToDevice));
+    }
+    // 2. every part on its own stream: on the merge device straight into its slice of the staging memory, elsewhere into memory of
+    //    its own device followed by one peer copy per array
+    auto enqueue = [&](size_t i) -> idist_status {
+        idist_partitioned::Part& pt = p->parts[i];
+        const int32_t dev = p->devs[pt.dev_slot].device;
+        uint32_t *s_pid = p->s_pid + i * row, *s_cnt = p->s_cnt + i * nq, *s_ctr = p->s_ctr + i * nq * 3;
+        float* s_dist = p->s_dist + i * row;
+        HIPCHK(hipSetDevice(dev));
+        if (dev == p->merge_device)
+            return idist_search_batch_device(pt.idx, pt.ctx, p->devs[pt.dev_slot].d_q, nq, s_pid, s_dist, s_cnt, counters ? s_ctr : nullptr, pt.ctx->stream);
+        if (row > pt.r_cap_out) {
+            hipFree(pt.r_pid); hipFree(pt.r_dist); pt.r_pid = nullptr; pt.r_dist = nullptr; pt.r_cap_out = 0;
+            HIPCHK(hipMalloc((void**)&pt.r_pid, row * 4));
+            HIPCHK(hipMalloc((void**)&pt.r_dist, row * 4));
+            pt.r_cap_out = row;
+        }
+        if (nq > pt.r_cap_nq) {
+            hipFree(pt.r_cnt); hipFree(pt.r_ctr); pt.r_cnt = nullptr; pt.r_ctr = nullptr; pt.r_cap_nq = 0;
+            HIPCHK(hipMalloc((void**)&pt.r_cnt, (size_t)nq * 4));
+            HIPCHK(hipMalloc((void**)&pt.r_ctr, (size_t)nq * 12));
+            pt.r_cap_nq = nq;
+        }
+        CHK(idist_search_batch_device(pt.idx, pt.ctx, p->devs[pt.dev_slot].d_q, nq, pt.r_pid, pt.r_dist, pt.r_cnt, counters ? pt.r_ctr : nullptr, pt.ctx->stream));
+        HIPCHK(hipMemcpyPeerAsync(s_pid, p->merge_device, pt.r_pid, dev, row * 4, pt.ctx->stream));
+        HIPCHK(hipMemcpyPeerAsync(s_dist, p->merge_device, pt.r_dist, dev, row * 4, pt.ctx->stream));
+        HIPCHK(hipMemcpyPeerAsync(s_cnt, p->merge_device, pt.r_cnt, dev, (size_t)nq * 4, pt.ctx->stream));
+        if (counters) HIPCHK(hipMemcpyPeerAsync(s_ctr, p->merge_device, pt.r_ctr, dev, (size_t)nq * 12, pt.ctx->stream));
+        return IDIST_OK;
+    };
+    for (size_t i = 0; i < P; i++) {
+        if (p->parts[i].ctx) { CHK(enqueue(i)); continue; }
+        HIPCHK(hipSetDevice(p->merge_device));           // an empty part: lists of length 0, no work done
+        HIPCHK(hipMemsetAsync(p->s_cnt + i * nq, 0, (size_t)nq * 4, p->stream));
+        if (counters) HIPCHK(hipMemsetAsync(p->s_ctr + i * nq * 3, 0, (size_t)nq * 12, p->stream));
+    }
+    // 3. wait for every part and read its device-side status.  Strict ties: a part whose tie region overflowed now has the larger
+    //    region (or the HBM bags) and is searched again — for as long as the escalation makes progress, the bound idist_search_batch
+    //    puts on its own loop; the merge never sees a list from an overflowed launch
+    for (size_t i = 0; i < P; i++) {
+        idist_partitioned::Part& pt = p->parts[i];
+        if (!pt.ctx) continue;
+        for (;;) {
+            HIPCHK(hipSetDevice(p->devs[pt.dev_slot].device));
+            HIPCHK(hipStreamSynchronize(pt.ctx->stream));
+            const uint32_t cap_before = std::max(tie_capacity(pt.idx->cfg), pt.ctx->tie_cap);
+            const bool spill_before = pt.ctx->tie_spill;
+            const idist_status s = idist_search_ctx_status(pt.ctx);
+            if (s == IDIST_OK) break;
+            if (s == IDIST_ERR_TIE_OVERFLOW && (std::max(tie_capacity(pt.idx->cfg), pt.ctx->tie_cap) > cap_before || pt.ctx->tie_spill != spill_before)) {
+                CHK(enqueue(i));
+                continue;
+            }
+            const std::string msg = g_err;
+            return fail(s, "part %zu (device %d): %s", i, p->devs[pt.dev_slot].device, msg.c_str());
+        }
+    }
+    // 4. the union
+    HIPCHK(hipSetDevice(p->merge_device));
+    return partitioned_merge(p, nq, ef, ef, counters, out_pid, out_dist, out_count, out_counters);
+}
+
+idist_status idist_partitioned_bruteforce(idist_partitioned* p, const float* queries, uint32_t nq, uint32_t k,
+                                          uint32_t* out_pid, float* out_dist) {
+    if (!p) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    CHK(partitioned_check(p, nullptr));
+    if (nq == 0) return IDIST_OK;
+    if (k == 0 || k > IDIST_MAX_EF) return fail(IDIST_ERR_INVALID_ARG, "k %u out of [1,%u]", k, IDIST_MAX_EF);
+    if (!queries || !out_pid || !out_dist) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    const size_t P = p->parts.size(), row = (size_t)nq * k;
+    HIPCHK(hipSetDevice(p->merge_device));
+    CHK(partitioned_reserve(p, nq, k, k));
+    std::vector<uint32_t> h_pid(row), h_cnt(nq);
+    std::vector<float> h_dist(row);
+    for (size_t i = 0; i < P; i++) {
+        const idist_index* ix = p->parts[i].idx;
+        const uint32_t kp = std::min(k, ix->n);                   // what this part contributes per query
+        if (kp) {
+            const idist_status s = idist_bruteforce(ix, queries, nq, kp, h_pid.data(), h_dist.data());
+            if (s != IDIST_OK) { const std::string msg = g_err; return fail(s, "part %zu (device %d): %s", i, ix->device, msg.c_str()); }
+            HIPCHK(hipSetDevice(p->merge_device));
+            HIPCHK(hipMemcpy2D(p->s_pid + i * row, (size_t)k * 4, h_pid.data(), (size_t)kp * 4, (size_t)kp * 4, nq, hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy2D(p->s_dist + i * row, (size_t)k * 4, h_dist.data(), (size_t)kp * 4, (size_t)kp * 4, nq, hipMemcpyHostToDevice));
+        }
+        std::fill(h_cnt.begin(), h_cnt.end(), kp);
+        HIPCHK(hipMemcpy(p->s_cnt + i * nq, h_cnt.data(), (size_t)nq * 4, hipMemcpyHostToDevice));
+    }
+    return partitioned_merge(p, nq, k, k, false, out_pid, out_dist, nullptr, nullptr);
+}
+
+idist_status idist_partitioned_last_search_kernel_ms(idist_partitioned* p, float* ms, uint32_t cap, uint32_t* n_out) {
+    if (!p || !ms || !n_out) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    const uint32_t take = (uint32_t)std::min<size_t>(p->parts.size(), cap);
+    for (uint32_t i = 0; i < take; i++) {
+        idist_search_ctx* c = p->parts[i].ctx;
+        ms[i] = c ? -1.0f : 0.0f;                                    // empty part: no kernel; no timed launch (yet): -1
+        if (c && c->n_rec) CHK(resolve_time(c, c->recs[(c->n_rec - 1) % IDIST_EVENT_RING], &ms[i]));
+    }
+    *n_out = take;
+    return IDIST_OK;
+}
+
+idist_status idist_partitioned_last_merge_ms(idist_partitioned* p, float* ms) {
+    if (!p || !ms) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    if (!p->timed) return fail(IDIST_ERR_INVALID_ARG, "no merge kernel has run through this object yet");
+    HIPCHK(hipEventSynchronize(p->ev1));
+    HIPCHK(hipEventElapsedTime(ms, p->ev0, p->ev1));
+    return IDIST_OK;
+}
 
 idist_status idist_distance_batch(const idist_index* idx, const float* queries, uint32_t nq, const uint32_t* ids,
                                   uint32_t n_ids, float* out_dist) {

@@ -1,0 +1,170 @@
+"""Partitioned index: several `Hnsw` parts searched as one (include/idist.h).
+
+The reference has one `Hnsw` per set of points; across GPUs this package could so far only copy ONE index everywhere and
+split the queries (`Hnsw.replicate`, dist.py).  A `PartitionedHnsw` cuts the POINTS instead: P ordinary indexes, on any
+devices, each built and searched exactly as before; a query is answered by searching every part and keeping the best
+`ef_search` of the union, merged on the GPU by the reference's `Candidate` order (distance, then id).
+
+    global id of a point = base[p] + its PointId inside part p        (base[p] = points in parts 0..p-1)
+
+"Partitioned", not "sharded": in this package sharded means queries split over replicas.
+"""
+from __future__ import annotations
+
+import copy
+import ctypes as C
+import threading
+from typing import Sequence
+
+import numpy as np
+
+from . import _capi
+from ._capi import INVALID
+from .api import BatchResult, Builder, Hnsw, Item, _as_points
+from .dist import shard_range
+
+
+def _lib():
+    return _capi.lib()
+
+
+class PartitionedHnsw:
+    """An ordered list of `Hnsw` parts with the same dim, metric and ef_search behind one search call."""
+
+    def __init__(self, handle, hnsws: Sequence[Hnsw]):
+        self._h = handle
+        self.parts = list(hnsws)      # kept alive for as long as the C handle exists (it borrows them)
+        info = self.info()
+        self._base = np.array(info.base[: info.n_parts + 1], dtype=np.int64)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) is not None:
+                _lib().idist_partitioned_free(self._h)   # before the parts: their own __del__ frees the indexes
+                self._h = None
+        except Exception:
+            pass
+
+    # -- construction --
+    @classmethod
+    def from_hnsws(cls, hnsws: Sequence[Hnsw]) -> "PartitionedHnsw":
+        """Adopt existing indexes as parts 0..P-1 (1 <= P <= 64)."""
+        hnsws = list(hnsws)
+        k = len(hnsws)
+        hs = (C.c_void_p * max(k, 1))(*[h._h for h in hnsws])
+        out = C.c_void_p()
+        L = _lib()
+        L.check(L.idist_partitioned_new(hs, k, C.byref(out)))
+        return cls(out, hnsws)
+
+    @classmethod
+    def build(cls, points, builder: Builder | None = None, parts: int = 2,
+              devices: Sequence[int] | None = None) -> tuple["PartitionedHnsw", list[int]]:
+        """Cut `points` into `parts` contiguous ranges (dist.shard_range), build an ordinary `Hnsw` of each with `builder`
+        (its seed drives every part's own shuffle) on devices[p % len(devices)] (default: all on the builder's device).
+        Parts on different devices build side by side, one host thread per distinct device; parts that share a device
+        one after the other.  Returns (index, caller's row index -> global id), as `Builder.build_hnsw` does for PointIds."""
+        builder = builder or Builder()
+        pts = _as_points(points)
+        n = pts.shape[0]
+        P = int(parts)
+        devs = [int(d) for d in devices] if devices else [builder._device]
+        hnsws: list = [None] * P
+        local: list = [None] * P
+        errors: list = []
+
+        def work(device: int, mine: list[int]):
+            try:
+                b = copy.copy(builder)
+                b._device = device
+                for p in mine:
+                    lo, hi = shard_range(n, p, P)
+                    hnsws[p], local[p] = Hnsw._new(pts[lo:hi], b)
+            except BaseException as e:  # noqa: BLE001 - handed to the calling thread
+                errors.append(e)
+
+        by_dev: dict[int, list[int]] = {}
+        for p in range(P):
+            by_dev.setdefault(devs[p % len(devs)], []).append(p)
+        groups = list(by_dev.items())
+        threads = [threading.Thread(target=work, args=g) for g in groups[1:]]
+        for t in threads:
+            t.start()
+        if groups:
+            work(*groups[0])
+        for t in threads:
+            t.join()
+        if errors:
+            raise errors[0]
+        self = cls.from_hnsws(hnsws)
+        ids = np.zeros(n, dtype=np.int64)
+        for p in range(P):
+            lo, hi = shard_range(n, p, P)
+            ids[lo:hi] = self._base[p] + np.asarray(local[p], dtype=np.int64)
+        return self, [int(x) for x in ids]
+
+    # -- introspection --
+    def info(self) -> _capi.PartitionedInfo:
+        info = _capi.PartitionedInfo()
+        _lib().check(_lib().idist_partitioned_get_info(self._h, C.byref(info)))
+        return info
+
+    def last_merge_ms(self) -> float:
+        """HIP-event duration of the last merge kernel, milliseconds."""
+        ms = C.c_float(0.0)
+        _lib().check(_lib().idist_partitioned_last_merge_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def last_search_kernel_ms(self) -> np.ndarray:
+        """Per part, the HIP-event duration of its last search kernel (0: empty part, -1: nothing timed), milliseconds."""
+        out = np.zeros(64, dtype=np.float32)
+        n = C.c_uint32(0)
+        _lib().check(_lib().idist_partitioned_last_search_kernel_ms(self._h, _capi.f32p(out), 64, C.byref(n)))
+        return out[: n.value]
+
+    def part_of(self, gid: int) -> tuple[int, int]:
+        """(part, PointId inside it) of a global id."""
+        gid = int(gid)
+        if not 0 <= gid < int(self._base[-1]):
+            raise IndexError(f"global id {gid} out of range [0, {int(self._base[-1])})")
+        p = int(np.searchsorted(self._base, gid, side="right")) - 1
+        return p, gid - int(self._base[p])
+
+    def __len__(self):
+        return int(self._base[-1])
+
+    def __getitem__(self, gid: int) -> np.ndarray:
+        p, pid = self.part_of(gid)
+        return self.parts[p].points[pid]
+
+    # -- search --
+    def search_batch(self, queries, counters: bool = False) -> BatchResult:
+        """Hnsw::search on every part, merged: <= ef_search (global id, distance) pairs per query, nearest first."""
+        q = _as_points(queries)
+        info = self.info()
+        if q.shape[0] and len(self) and q.shape[1] != info.dim:
+            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
+        nq, ef = q.shape[0], int(info.ef_search)
+        pid = np.full((nq, ef), INVALID, dtype=np.uint32)
+        dist = np.full((nq, ef), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
+        if nq:
+            L = _lib()
+            L.check(L.idist_partitioned_search_batch(self._h, _capi.f32p(q), nq, _capi.u32p(pid), _capi.f32p(dist),
+                                                     _capi.u32p(cnt), _capi.u32p(ctr) if counters else None))
+        return BatchResult(pid, dist, cnt, ctr)
+
+    def search(self, point) -> list[Item]:
+        """One query: the merged items, nearest first; `Item.pid` is the global id."""
+        r = self.search_batch(np.asarray(point, dtype=np.float32).reshape(1, -1))
+        return [Item(float(r.distance[0, i]), int(r.pid[0, i]), self[int(r.pid[0, i])]) for i in range(int(r.count[0]))]
+
+    def bruteforce(self, queries, k: int) -> tuple[np.ndarray, np.ndarray]:
+        """Exact k-NN over all parts (global ids, ties by id): every part's exhaustive scan, merged."""
+        q = _as_points(queries)
+        pid = np.full((q.shape[0], k), INVALID, dtype=np.uint32)
+        dist = np.full((q.shape[0], k), np.inf, dtype=np.float32)
+        L = _lib()
+        L.check(L.idist_partitioned_bruteforce(self._h, _capi.f32p(q), q.shape[0], k, _capi.u32p(pid), _capi.f32p(dist)))
+        return pid, dist
