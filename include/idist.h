@@ -65,7 +65,15 @@ enum { IDIST_TIES_STRICT = 0, IDIST_TIES_DROP = 1 };
 
 enum {
     IDIST_METRIC_L2SQ = 0, /* FloatArray::distance, instant-distance-py/src/lib.rs:378-421 */
-    IDIST_METRIC_L2 = 1    /* sqrt of it: tests/all.rs:93-97, examples/colors.rs:21-25 */
+    IDIST_METRIC_L2 = 1,   /* sqrt of it: tests/all.rs:93-97, examples/colors.rs:21-25 */
+    IDIST_METRIC_COSINE = 2 /* cosine distance 1 - cos (no counterpart in the reference), DEFINED through L2SQ: with s(x) = the canonical
+                              L2SQ distance of x to the origin, r = sqrtf(s) and x^ = x / r coordinate by coordinate (f32, correctly
+                              rounded; x^ = x when r is not a positive finite number: zero rows, NaN / inf, s overflowed or underflowed),
+                              an index with this metric over rows X IS the L2SQ index over X^ — same graph, same ids, order, counts and
+                              counters for a query q as the L2SQ search of q^ — and every distance it reports is 0.5f * d, one f32
+                              multiply of the canonical L2SQ distance d (|q^ - x^|^2 / 2 = 1 - cos).  Rows are normalised where they become
+                              the index's device copy (build, build_device, import), queries per call; the caller's buffers are never
+                              written.  idist_index_device_buffers / idist_replicate* hand on rows that already are x^. */
 };
 
 /* Builder fields, core/lib.rs:23-31 (defaults :101-128). */
@@ -372,6 +380,12 @@ idist_status idist_filter_bound_batch(const idist_index* idx, const float* queri
  * brute-force check of tests/all.rs:60-67); host pointers. */
 idist_status idist_bruteforce(const idist_index* idx, const float* queries, uint32_t nq,
                               uint32_t k, uint32_t* out_pid, float* out_dist);
+
+/* The normalisation of IDIST_METRIC_COSINE on its own: out_rows[i] = x^ of rows[i] (n x dim, row-major; may be `rows` itself),
+ * out_norm2[i] (may be NULL) = s(rows[i]), the canonical L2SQ distance of the row to the origin.  Host pointers.  What a caller
+ * needs to reproduce a cosine index with an L2SQ one, bit for bit. */
+idist_status idist_normalize_batch(const float* rows, uint32_t n, uint32_t dim, float* out_rows, float* out_norm2,
+                                   int32_t device);
 
 #ifdef __cplusplus
 }

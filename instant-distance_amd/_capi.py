@@ -21,6 +21,7 @@ MAX_LAYERS = 64
 MAX_EF = 4096
 METRIC_L2SQ = 0
 METRIC_L2 = 1
+METRIC_COSINE = 2
 TIES_STRICT = 0
 TIES_DROP = 1
 
@@ -135,6 +136,7 @@ SYMBOLS = {
     "idist_distance_batch": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, _f32p]),
     "idist_filter_bound_batch": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, _f32p]),
     "idist_bruteforce": (C.c_int32, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),
+    "idist_normalize_batch": (C.c_int32, [_f32p, C.c_uint32, C.c_uint32, _f32p, _f32p, C.c_int32]),
 }
 
 

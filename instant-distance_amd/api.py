@@ -12,7 +12,8 @@ Same names, argument meaning and error behaviour as the reference
 `Point::distance` (core/lib.rs:780-782) is arbitrary user code in the reference and
 cannot run on a GPU; here a point is an f32 vector and the distance is one of the two
 the reference itself ships: squared L2 (FloatArray, the default) or L2 with sqrt
-(the Point of tests/all.rs and examples/colors.rs) — `Builder.metric()`.
+(the Point of tests/all.rs and examples/colors.rs) — `Builder.metric()`.  METRIC_COSINE (not in the reference) is
+squared L2 over rows and queries the engine normalises itself, reported as 1 - cos; the host copies stay the caller's rows.
 
 All compute goes through the C ABI (include/idist.h); there is no CPU path.
 """
@@ -26,7 +27,7 @@ from typing import Any, Iterator, Sequence
 import numpy as np
 
 from . import _capi
-from ._capi import INVALID, M, M2, METRIC_L2, METRIC_L2SQ, TIES_DROP, TIES_STRICT
+from ._capi import INVALID, M, M2, METRIC_COSINE, METRIC_L2, METRIC_L2SQ, TIES_DROP, TIES_STRICT
 
 PointId = int
 
@@ -94,7 +95,11 @@ class Builder:
 
     # -- additions of this engine --
     def metric(self, metric: int) -> "Builder":
-        """METRIC_L2SQ (FloatArray, py/lib.rs:378-421) or METRIC_L2 (tests/all.rs:93-97)."""
+        """METRIC_L2SQ (FloatArray, py/lib.rs:378-421), METRIC_L2 (tests/all.rs:93-97) or METRIC_COSINE: the cosine distance
+        1 - cos, defined as the METRIC_L2SQ index over the rows normalised by `normalize()`'s arithmetic (the engine does it where
+        the rows reach the device, and to every query), with distances reported as half the squared L2 distance of the
+        normalised vectors.  `points`, `Item.point` and `__getitem__` keep the caller's rows; rows without a positive finite norm
+        (zero, NaN, inf) take part unchanged."""
         self._metric = int(metric)
         return self
 
@@ -299,6 +304,20 @@ class BatchResult:
     distance: np.ndarray  # [nq, ef_search] float32, +inf padded
     count: np.ndarray     # [nq]
     counters: np.ndarray | None  # [nq, 3] {n_dist, n_exp0, n_expU}
+
+
+def normalize(points, device: int = 0, return_norm2: bool = False):
+    """x / sqrt(s(x)) per row, s = the canonical squared-L2 distance of the row to the origin (idist_normalize_batch): the rows a
+    METRIC_COSINE index holds for `points`, bit for bit — an METRIC_L2SQ index over `normalize(points)` searched with
+    `normalize(queries)` returns the same ids and twice the distances.  Rows whose sqrt(s) is not a positive finite number come
+    back unchanged.  `return_norm2`: also s per row."""
+    pts = _as_points(points)
+    out = np.empty_like(pts)
+    s = np.empty(pts.shape[0], dtype=np.float32) if return_norm2 else None
+    L = _lib()
+    L.check(L.idist_normalize_batch(_capi.f32p(pts), pts.shape[0], max(pts.shape[1], 1), _capi.f32p(out),
+                                    _capi.f32p(s) if return_norm2 else None, int(device)))
+    return (out, s) if return_norm2 else out
 
 
 def _as_points(points) -> np.ndarray:

@@ -6,6 +6,7 @@
 #include "idist_mfma.hpp"
 #include "idist_combine.hpp"
 #include "idist_merge.hpp"
+#include "idist_normalize.hpp"
 
 #ifndef IDIST_EMU
 #include <hip/hip_runtime.h>
@@ -155,7 +156,7 @@ idist_status check_device(int32_t device) {
 idist_status validate_config(const idist_config* cfg, bool for_build) {
     if (!cfg) return fail(IDIST_ERR_INVALID_ARG, "config is null");
     if (cfg->ef_search > IDIST_MAX_EF) return fail(IDIST_ERR_INVALID_ARG, "ef_search %u > %u", cfg->ef_search, IDIST_MAX_EF);
-    if (cfg->metric != IDIST_METRIC_L2SQ && cfg->metric != IDIST_METRIC_L2)
+    if (cfg->metric != IDIST_METRIC_L2SQ && cfg->metric != IDIST_METRIC_L2 && cfg->metric != IDIST_METRIC_COSINE)
         return fail(IDIST_ERR_INVALID_ARG, "unknown metric %d", cfg->metric);
     if (cfg->tie_policy != IDIST_TIES_STRICT && cfg->tie_policy != IDIST_TIES_DROP)
         return fail(IDIST_ERR_INVALID_ARG, "unknown tie_policy %d", cfg->tie_policy);
@@ -166,6 +167,12 @@ idist_status validate_config(const idist_config* cfg, bool for_build) {
     }
     return IDIST_OK;
 }
+
+// IDIST_METRIC_COSINE is the squared-L2 index over normalised rows (idist_normalize.hpp): rows are normalised where they become the
+// index's device copy, queries per launch, reported distances are halved — and every kernel and every policy that asks for the
+// metric (IndexView.metric, the MFMA paths) sees squared L2.
+inline bool is_cosine(const idist_config& cfg) { return cfg.metric == IDIST_METRIC_COSINE; }
+inline int32_t kernel_metric(const idist_config& cfg) { return is_cosine(cfg) ? (int32_t)IDIST_METRIC_L2SQ : cfg.metric; }
 
 }  // namespace
 
@@ -226,7 +233,7 @@ struct idist_index {
         v.rs = L.rs;
         v.tail = L.tail;
         v.n_upper = n_upper;
-        v.metric = (uint32_t)cfg.metric;
+        v.metric = (uint32_t)kernel_metric(cfg);
         if (filt_state.load(std::memory_order_acquire) == 1) v.f = filt;
         return v;
     }
@@ -320,6 +327,8 @@ struct idist_search_ctx {
     uint32_t* d_cnt = nullptr;
     uint32_t* d_ctr = nullptr;
     size_t cap_q = 0, cap_out = 0, cap_nq = 0;
+    float* d_qn = nullptr;         // cosine indexes: the launch's queries, normalised (launch_search); grown like the staging above
+    size_t cap_qn = 0;
     bool tie_overflowed = false;
     uint32_t tie_cap = 0;          // tie capacity this context escalated to (0 = the index's)
     // strict ties, last resort: one bag of n keys per slot in HBM (the reference's candidate heap is unbounded, core/lib.rs:564)
@@ -469,13 +478,37 @@ idist_status index_alloc(uint32_t n, uint32_t dim, const idist_config* cfg, cons
     return IDIST_OK;
 }
 
-// natural row-major device points -> blocked rows of the index
+// x -> x^ for n rows of `dim` coordinates, `ld` floats apart, in the layout (nb blocks, natural remainder); natural rows: ld = dim,
+// nb = 0.  out may be in.  Enqueued on `stream`.
+idist_status launch_normalize(const float* in, float* out, uint32_t n, uint32_t dim, uint32_t ld, uint32_t nb, float* out_norm2,
+                              int n_cu, hipStream_t stream) {
+    if (n == 0) return IDIST_OK;
+    const uint32_t vec = (ld % 4u) == 0u && (((uintptr_t)in | (uintptr_t)out) & 15u) == 0u ? 1u : 0u;
+    const uint32_t grid = std::min<uint32_t>((n + 7u) / 8u, (uint32_t)std::max(n_cu, 1) * 32u);
+    IDIST_LAUNCH(normalize_rows_kernel, grid, 64, 0, stream, in, out, n, dim, ld, nb, vec, out_norm2);
+    HIPCHK(hipGetLastError());
+    return IDIST_OK;
+}
+// the factor 0.5 on `total` reported distances of a cosine index, on `stream`
+idist_status launch_scale_half(float* d, size_t total, int n_cu, hipStream_t stream) {
+    if (total == 0) return IDIST_OK;
+    const uint32_t vec = ((uintptr_t)d & 15u) == 0u ? 1u : 0u;
+    const uint32_t grid = (uint32_t)std::min<size_t>((total / 4u + 255u) / 256u + 1u, (size_t)std::max(n_cu, 1) * 8u);
+    IDIST_LAUNCH(scale_half_kernel, grid, 256, 0, stream, d, total, vec);
+    HIPCHK(hipGetLastError());
+    return IDIST_OK;
+}
+
+// natural row-major device points -> blocked rows of the index (cosine: normalised there, the caller's rows are only read).
+// The ONLY place rows are normalised: replicas and broadcast targets copy device rows that already are x^.
 idist_status load_points_device(idist_index* ix, const float* d_nat) {
     if (ix->n == 0) return IDIST_OK;
     const size_t total = (size_t)ix->n * ix->L.stride;
     const int grid = (int)std::min<size_t>((total + 255) / 256, 65536);
     IDIST_LAUNCH(permute_rows_kernel, grid, 256, 0, (hipStream_t) nullptr, d_nat, ix->d_points, ix->n, ix->dim, ix->L.stride, ix->L.nb);
     HIPCHK(hipGetLastError());
+    if (is_cosine(ix->cfg))
+        CHK(launch_normalize(ix->d_points, ix->d_points, ix->n, ix->dim, ix->L.stride, ix->L.nb, nullptr, ix->n_cu, nullptr));
     HIPCHK(hipDeviceSynchronize());
     return IDIST_OK;
 }
@@ -625,7 +658,7 @@ idist_status run_build(idist_index* ix, idist_progress* prog, bool tie_spill) {
     const size_t smemX = smem_bytes_extend(ix->L.stride, wcap, 1u << tab_log2, vg.dirty_words);
     if (ext && smemX > 64 * 1024) return fail(IDIST_ERR_INVALID_ARG, "dim/ef_construction need %zu B of LDS per wave with extend_candidates (> 64 KiB)", smemX);
     // step A2 on the matrix cores (Gram matrix of the candidates as a filter, idist_mfma.hpp) where it applies
-    const bool a2_mfma = cfg.has_heuristic && cfg.metric == IDIST_METRIC_L2SQ && cfg.ef_construction <= 128 &&
+    const bool a2_mfma = cfg.has_heuristic && kernel_metric(cfg) == IDIST_METRIC_L2SQ && cfg.ef_construction <= 128 &&
                          !(test_env("IDIST_BUILD_A2") && test_env("IDIST_BUILD_A2")[0] == 't');
     const size_t smemA2m = smem_bytes_select_mfma(ix->L.stride);
     uint32_t* d_vis = nullptr;
@@ -1263,9 +1296,26 @@ idist_status filter_ensure(const idist_index* ix) {
 
 idist_status launch_search(const idist_index* ix, idist_search_ctx* ctx, const float* d_q, uint32_t nq,
                            uint32_t* d_pid, float* d_dist, uint32_t* d_cnt, uint32_t* d_ctr, hipStream_t stream,
-                           uint32_t* status_host = nullptr, uint32_t* grid_out = nullptr, uint32_t* done_host = nullptr, uint32_t done_seq = 0) {
+                           uint32_t* status_host = nullptr, uint32_t* grid_out = nullptr, uint32_t* done_host = nullptr, uint32_t done_seq = 0,
+                           bool prepared = false) {
     const uint32_t ef = ix->cfg.ef_search;
     CHK(variants_check(ctx->knobs.classic));
+    // Cosine: the walk reads a normalised copy of the queries that this context owns, and the distances it wrote are halved behind
+    // it — both on the launch's stream, outside the events that time the search kernel.  `prepared`: the caller normalised the
+    // queries itself and halves the distances later (the partitioned search: after its merge).
+    const bool cosine = is_cosine(ix->cfg) && !prepared;
+    if (cosine) {
+        const size_t qb = (size_t)nq * ix->dim * 4;
+        if (qb > ctx->cap_qn) {                                   // grows like the staging buffers; hipFree waits for the device
+            size_t cap = std::max<size_t>(ctx->cap_qn, 4096);
+            while (cap < qb) cap <<= 1;
+            hipFree(ctx->d_qn); ctx->d_qn = nullptr; ctx->cap_qn = 0;
+            HIPCHK(hipMalloc((void**)&ctx->d_qn, cap));
+            ctx->cap_qn = cap;
+        }
+        CHK(launch_normalize(d_q, ctx->d_qn, nq, ix->dim, ix->dim, 0u, nullptr, ix->n_cu, stream));
+        d_q = ctx->d_qn;
+    }
     SearchArgs a{};
     a.queries = d_q;
     a.nq = nq;
@@ -1491,6 +1541,7 @@ idist_status launch_search(const idist_index* ix, idist_search_ctx* ctx, const f
         ctx->n_launch++;
         ctx->recs[ctx->n_rec++ % IDIST_EVENT_RING] = {(int32_t)slot, 0.0f};
     }
+    if (cosine) CHK(launch_scale_half(d_dist, (size_t)nq * ef, ix->n_cu, stream));
     return IDIST_OK;
 }
 
@@ -1780,6 +1831,7 @@ void idist_search_ctx_free(idist_search_ctx* c) {
     hipFree(c->d_next);
     if (c->h_io) hipHostFree(c->h_io);
     hipFree(c->d_q);
+    hipFree(c->d_qn);
     hipFree(c->d_pid);
     hipFree(c->d_dist);
     hipFree(c->d_cnt);
@@ -1803,9 +1855,10 @@ idist_status idist_search_ctx_reserve(idist_search_ctx* ctx, uint32_t slots) {
     return IDIST_OK;
 }
 
-idist_status idist_search_batch_device(const idist_index* idx, idist_search_ctx* ctx, const void* d_queries,
-                                       uint32_t nq, void* d_out_pid, void* d_out_dist, void* d_out_count,
-                                       void* d_out_counters, void* hip_stream) {
+// prepared: see launch_search (the partitioned search hands in normalised queries and halves the distances after its merge)
+static idist_status search_batch_device_impl(const idist_index* idx, idist_search_ctx* ctx, const void* d_queries,
+                                             uint32_t nq, void* d_out_pid, void* d_out_dist, void* d_out_count,
+                                             void* d_out_counters, void* hip_stream, bool prepared) {
     CHK(check_ctx(idx, ctx));
     if (nq == 0) return IDIST_OK;
     if (!d_queries || !d_out_count) return fail(IDIST_ERR_INVALID_ARG, "null device pointer");
@@ -1817,7 +1870,13 @@ idist_status idist_search_batch_device(const idist_index* idx, idist_search_ctx*
     }
     if (!d_out_pid || !d_out_dist) return fail(IDIST_ERR_INVALID_ARG, "null device pointer");
     return launch_search(idx, ctx, (const float*)d_queries, nq, (uint32_t*)d_out_pid, (float*)d_out_dist,
-                         (uint32_t*)d_out_count, (uint32_t*)d_out_counters, stream);
+                         (uint32_t*)d_out_count, (uint32_t*)d_out_counters, stream, nullptr, nullptr, nullptr, 0, prepared);
+}
+
+idist_status idist_search_batch_device(const idist_index* idx, idist_search_ctx* ctx, const void* d_queries,
+                                       uint32_t nq, void* d_out_pid, void* d_out_dist, void* d_out_count,
+                                       void* d_out_counters, void* hip_stream) {
+    return search_batch_device_impl(idx, ctx, d_queries, nq, d_out_pid, d_out_dist, d_out_count, d_out_counters, hip_stream, false);
 }
 
 idist_status idist_search_ctx_status(idist_search_ctx* ctx) {
@@ -1953,7 +2012,8 @@ static idist_status search_batch_impl(const idist_index* idx, idist_search_ctx* 
     // pinned, device-mapped buffer that the kernel reads and writes itself; the call is a host memcpy, one launch, one
     // stream sync, a host memcpy.  (The general path below costs six copy / memset calls of ~10 us each around the kernel.)
     const size_t io_need = qb + 2 * ob + (size_t)nq * 16 + idist_search_ctx::kIoHeadBytes;
-    if (io_need <= idist_search_ctx::kIoMaxBytes && !ctx->knobs.no_zero_copy) {
+    // (not for cosine indexes: the completion word the kernel writes would run ahead of the pass that halves the distances)
+    if (io_need <= idist_search_ctx::kIoMaxBytes && !ctx->knobs.no_zero_copy && !is_cosine(idx->cfg)) {
         if (io_need > ctx->io_cap) {
             size_t cap = idist_search_ctx::kIoMinBytes;
             while (cap < io_need) cap <<= 1;
@@ -2440,7 +2500,12 @@ static idist_status partitioned_reserve(idist_partitioned* p, uint32_t nq, uint3
     return IDIST_OK;
 }
 
-// the merge kernel between two events + its result to the host; every part's list is complete in the staging memory
+static idist_status bruteforce_impl(const idist_index* idx, const float* queries, uint32_t nq, uint32_t k, uint32_t* out_pid,
+                                    float* out_dist, bool raw);
+
+// the merge kernel between two events + its result to the host; every part's list is complete in the staging memory.  Cosine
+// parts hand in squared-L2 distances of normalised vectors: they are halved HERE, after the merge — the merge relies on every
+// list being strictly ordered by (distance bits, id), which halving can break for denormal distances.
 static idist_status partitioned_merge(idist_partitioned* p, uint32_t nq, uint32_t width, uint32_t out_width, bool counters,
                                       uint32_t* out_pid, float* out_dist, uint32_t* out_count, uint32_t* out_counters) {
     MergeArgs a{};
@@ -2452,6 +2517,7 @@ static idist_status partitioned_merge(idist_partitioned* p, uint32_t nq, uint32_
     CHK(launch_merge(a, p->stream));
     HIPCHK(hipEventRecord(p->ev1, p->stream));
     p->timed = true;
+    if (p->metric == IDIST_METRIC_COSINE) CHK(launch_scale_half(p->o_dist, (size_t)nq * out_width, p->parts[0].idx->n_cu, p->stream));
     const size_t ob = (size_t)nq * out_width * 4;
     HIPCHK(hipMemcpyAsync(out_pid, p->o_pid, ob, hipMemcpyDeviceToHost, p->stream));
     HIPCHK(hipMemcpyAsync(out_dist, p->o_dist, ob, hipMemcpyDeviceToHost, p->stream));
@@ -2488,6 +2554,10 @@ idist_status idist_partitioned_search_batch(idist_partitioned* p, const float* q
         HIPCHK(hipSetDevice(dv.device));
         if (qb > dv.cap_q) { hipFree(dv.d_q); dv.d_q = nullptr; dv.cap_q = 0; HIPCHK(hipMalloc((void**)&dv.d_q, qb)); dv.cap_q = qb; }
         HIPCHK(hipMemcpy(dv.d_q, queries, qb, hipMemcpyHostToDevice));
+        if (p->metric == IDIST_METRIC_COSINE) {          // normalised once per device; the parts' launches take them as they are
+            CHK(launch_normalize(dv.d_q, dv.d_q, nq, p->dim, p->dim, 0u, nullptr, p->parts[0].idx->n_cu, nullptr));
+            HIPCHK(hipStreamSynchronize(nullptr));
+        }
     }
     // 2. every part on its own stream: on the merge device straight into its slice of the staging memory, elsewhere into memory of
     //    its own device followed by one peer copy per array
@@ -2498,7 +2568,7 @@ idist_status idist_partitioned_search_batch(idist_partitioned* p, const float* q
         float* s_dist = p->s_dist + i * row;
         HIPCHK(hipSetDevice(dev));
         if (dev == p->merge_device)
-            return idist_search_batch_device(pt.idx, pt.ctx, p->devs[pt.dev_slot].d_q, nq, s_pid, s_dist, s_cnt, counters ? s_ctr : nullptr, pt.ctx->stream);
+            return search_batch_device_impl(pt.idx, pt.ctx, p->devs[pt.dev_slot].d_q, nq, s_pid, s_dist, s_cnt, counters ? s_ctr : nullptr, pt.ctx->stream, true);
         if (row > pt.r_cap_out) {
             hipFree(pt.r_pid); hipFree(pt.r_dist); pt.r_pid = nullptr; pt.r_dist = nullptr; pt.r_cap_out = 0;
             HIPCHK(hipMalloc((void**)&pt.r_pid, row * 4));
@@ -2511,7 +2581,7 @@ idist_status idist_partitioned_search_batch(idist_partitioned* p, const float* q
             HIPCHK(hipMalloc((void**)&pt.r_ctr, (size_t)nq * 12));
             pt.r_cap_nq = nq;
         }
-        CHK(idist_search_batch_device(pt.idx, pt.ctx, p->devs[pt.dev_slot].d_q, nq, pt.r_pid, pt.r_dist, pt.r_cnt, counters ? pt.r_ctr : nullptr, pt.ctx->stream));
+        CHK(search_batch_device_impl(pt.idx, pt.ctx, p->devs[pt.dev_slot].d_q, nq, pt.r_pid, pt.r_dist, pt.r_cnt, counters ? pt.r_ctr : nullptr, pt.ctx->stream, true));
         HIPCHK(hipMemcpyPeerAsync(s_pid, p->merge_device, pt.r_pid, dev, row * 4, pt.ctx->stream));
         HIPCHK(hipMemcpyPeerAsync(s_dist, p->merge_device, pt.r_dist, dev, row * 4, pt.ctx->stream));
         HIPCHK(hipMemcpyPeerAsync(s_cnt, p->merge_device, pt.r_cnt, dev, (size_t)nq * 4, pt.ctx->stream));
@@ -2566,7 +2636,7 @@ idist_status idist_partitioned_bruteforce(idist_partitioned* p, const float* que
         const idist_index* ix = p->parts[i].idx;
         const uint32_t kp = std::min(k, ix->n);                   // what this part contributes per query
         if (kp) {
-            const idist_status s = idist_bruteforce(ix, queries, nq, kp, h_pid.data(), h_dist.data());
+            const idist_status s = bruteforce_impl(ix, queries, nq, kp, h_pid.data(), h_dist.data(), true);
             if (s != IDIST_OK) { const std::string msg = g_err; return fail(s, "part %zu (device %d): %s", i, ix->device, msg.c_str()); }
             HIPCHK(hipSetDevice(p->merge_device));
             HIPCHK(hipMemcpy2D(p->s_pid + i * row, (size_t)k * 4, h_pid.data(), (size_t)kp * 4, (size_t)kp * 4, nq, hipMemcpyHostToDevice));
@@ -2616,6 +2686,8 @@ idist_status idist_distance_batch(const idist_index* idx, const float* queries, 
         release();
         return fail(IDIST_ERR_HIP, "distance_batch staging: %s", hipGetErrorString(e));
     }
+    const bool cosine = is_cosine(idx->cfg);
+    if (cosine && launch_normalize(d_q, d_q, nq, idx->dim, idx->dim, 0u, nullptr, idx->n_cu, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
     const uint32_t chunks = (n_ids + 63u) / 64u;
     const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)nq * chunks, 1u << 20);
     const size_t smem = smem_bytes(idx->L.stride, 0, false);
@@ -2627,6 +2699,7 @@ idist_status idist_distance_batch(const idist_index* idx, const float* queries, 
     }
     IDIST_DISPATCH(idx->L, LAUNCH_DIST);
 #undef LAUNCH_DIST
+    if (cosine && launch_scale_half(d_out, (size_t)nq * n_ids, idx->n_cu, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
     if ((e = hipGetLastError()) != hipSuccess || (e = hipMemcpy(out_dist, d_out, ib, hipMemcpyDeviceToHost)) != hipSuccess) {
         release();
         return fail(IDIST_ERR_HIP, "distance_batch: %s", hipGetErrorString(e));
@@ -2658,6 +2731,8 @@ idist_status idist_filter_bound_batch(const idist_index* idx, const float* queri
         release();
         return fail(IDIST_ERR_HIP, "filter_bound_batch staging: %s", hipGetErrorString(e));
     }
+    const bool cosine = is_cosine(idx->cfg);                             // (half a lower bound is a lower bound of half)
+    if (cosine && launch_normalize(d_q, d_q, nq, idx->dim, idx->dim, 0u, nullptr, idx->n_cu, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
     const uint32_t chunks = (n_ids + 63u) / 64u;
     const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)nq * chunks, 1u << 20);
     const size_t smem = smem_bytes(idx->L.stride, 0, false);
@@ -2669,6 +2744,7 @@ idist_status idist_filter_bound_batch(const idist_index* idx, const float* queri
     }
     IDIST_DISPATCH(idx->L, LAUNCH_FB);
 #undef LAUNCH_FB
+    if (cosine && launch_scale_half(d_out, (size_t)nq * n_ids, idx->n_cu, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
     if ((e = hipGetLastError()) != hipSuccess || (e = hipMemcpy(out_bound, d_out, ib, hipMemcpyDeviceToHost)) != hipSuccess) {
         release();
         return fail(IDIST_ERR_HIP, "filter_bound_batch: %s", hipGetErrorString(e));
@@ -2677,8 +2753,10 @@ idist_status idist_filter_bound_batch(const idist_index* idx, const float* queri
     return IDIST_OK;
 }
 
+// raw (both brute-force paths): the squared-L2 distances of a cosine index are left as they are — the partitioned brute force
+// halves them after its merge (the queries are normalised either way)
 static idist_status bruteforce_scan(const idist_index* idx, const float* queries, uint32_t nq, uint32_t k,
-                                    uint32_t* out_pid, float* out_dist) {
+                                    uint32_t* out_pid, float* out_dist, bool raw) {
     if (!idx) return fail(IDIST_ERR_INVALID_ARG, "idx is null");
     if (nq == 0) return IDIST_OK;
     if (k == 0 || k > IDIST_MAX_EF) return fail(IDIST_ERR_INVALID_ARG, "k %u out of [1,%u]", k, IDIST_MAX_EF);
@@ -2696,6 +2774,8 @@ static idist_status bruteforce_scan(const idist_index* idx, const float* queries
         release();
         return fail(IDIST_ERR_HIP, "bruteforce staging: %s", hipGetErrorString(e));
     }
+    const bool cosine = is_cosine(idx->cfg);
+    if (cosine && launch_normalize(d_q, d_q, nq, idx->dim, idx->dim, 0u, nullptr, idx->n_cu, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
     const uint32_t wcap = k + 64 + 8;
     const size_t smem = smem_bytes(idx->L.stride, wcap, false);
     const uint32_t grid = std::min<uint32_t>(nq, (uint32_t)idx->n_cu * 16);
@@ -2707,6 +2787,7 @@ static idist_status bruteforce_scan(const idist_index* idx, const float* queries
     }
     IDIST_DISPATCH(idx->L, LAUNCH_BF);
 #undef LAUNCH_BF
+    if (cosine && !raw && launch_scale_half(d_dist, (size_t)nq * k, idx->n_cu, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
     if ((e = hipGetLastError()) != hipSuccess || (e = hipMemcpy(out_pid, d_pid, ob, hipMemcpyDeviceToHost)) != hipSuccess ||
         (e = hipMemcpy(out_dist, d_dist, ob, hipMemcpyDeviceToHost)) != hipSuccess) {
         release();
@@ -2720,8 +2801,9 @@ static idist_status bruteforce_scan(const idist_index* idx, const float* queries
 // Wide-batch exact k-NN: f32-MFMA -2QP^T filter + canonical re-rank (idist_mfma.hpp).  Returns
 // IDIST_ERR_INTERNAL with *fell_back = 1 if a candidate list overflowed (caller rescans).
 static idist_status bruteforce_mfma(const idist_index* idx, const float* queries, uint32_t nq, uint32_t k,
-                                    uint32_t* out_pid, float* out_dist, int* fell_back) {
+                                    uint32_t* out_pid, float* out_dist, int* fell_back, bool raw) {
     *fell_back = 0;
+    const bool cosine = is_cosine(idx->cfg);
     const uint32_t n = idx->n, stride = idx->L.stride;
     uint32_t S = 32768;
     if (const char* e = test_env("IDIST_BF_SAMPLE")) S = (uint32_t)atoi(e);
@@ -2769,6 +2851,7 @@ static idist_status bruteforce_mfma(const idist_index* idx, const float* queries
         const uint32_t qc = std::min(QC, nq - qb);
         const uint32_t qpad = (qc + kTM - 1) / kTM * kTM;
         MCHK(hipMemcpy(d_qnat, queries + (size_t)qb * idx->dim, (size_t)qc * idx->dim * 4, hipMemcpyHostToDevice));
+        if (cosine && launch_normalize(d_qnat, d_qnat, qc, idx->dim, idx->dim, 0u, nullptr, idx->n_cu, st) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
         MCHK(hipMemset(d_qb, 0, (size_t)qpad * stride * 4));
         {
             const size_t total = (size_t)qc * stride;
@@ -2802,6 +2885,7 @@ static idist_status bruteforce_mfma(const idist_index* idx, const float* queries
         IDIST_DISPATCH(idx->L, LAUNCH_RR);
 #undef LAUNCH_RR
         MCHK(hipGetLastError());
+        if (cosine && !raw && launch_scale_half(d_dist, (size_t)qc * k, idx->n_cu, st) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
         MCHK(hipMemcpy(out_pid + (size_t)qb * k, d_pid, (size_t)qc * k * 4, hipMemcpyDeviceToHost));
         MCHK(hipMemcpy(out_dist + (size_t)qb * k, d_dist, (size_t)qc * k * 4, hipMemcpyDeviceToHost));
     }
@@ -2813,8 +2897,8 @@ static idist_status bruteforce_mfma(const idist_index* idx, const float* queries
     return IDIST_OK;
 }
 
-idist_status idist_bruteforce(const idist_index* idx, const float* queries, uint32_t nq, uint32_t k,
-                              uint32_t* out_pid, float* out_dist) {
+static idist_status bruteforce_impl(const idist_index* idx, const float* queries, uint32_t nq, uint32_t k,
+                                    uint32_t* out_pid, float* out_dist, bool raw) {
     if (!idx) return fail(IDIST_ERR_INVALID_ARG, "idx is null");
     if (nq == 0) return IDIST_OK;
     if (k == 0 || k > IDIST_MAX_EF) return fail(IDIST_ERR_INVALID_ARG, "k %u out of [1,%u]", k, IDIST_MAX_EF);
@@ -2825,10 +2909,41 @@ idist_status idist_bruteforce(const idist_index* idx, const float* queries, uint
     if (mfma && idx->n >= k && idx->n >= 128) {
         HIPCHK(hipSetDevice(idx->device));
         int fell_back = 0;
-        idist_status s = bruteforce_mfma(idx, queries, nq, k, out_pid, out_dist, &fell_back);
+        idist_status s = bruteforce_mfma(idx, queries, nq, k, out_pid, out_dist, &fell_back, raw);
         if (s == IDIST_OK || !fell_back) return s;
     }
-    return bruteforce_scan(idx, queries, nq, k, out_pid, out_dist);
+    return bruteforce_scan(idx, queries, nq, k, out_pid, out_dist, raw);
+}
+
+idist_status idist_bruteforce(const idist_index* idx, const float* queries, uint32_t nq, uint32_t k,
+                              uint32_t* out_pid, float* out_dist) {
+    return bruteforce_impl(idx, queries, nq, k, out_pid, out_dist, false);
+}
+
+idist_status idist_normalize_batch(const float* rows, uint32_t n, uint32_t dim, float* out_rows, float* out_norm2, int32_t device) {
+    if (dim == 0 || dim > 65536) return fail(IDIST_ERR_INVALID_ARG, "dim %u out of [1,65536]", dim);
+    if (n == 0) return IDIST_OK;
+    if (!rows || !out_rows) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    CHK(check_device(device));
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    float *d_x = nullptr, *d_s = nullptr;
+    const size_t xb = (size_t)n * dim * 4;
+    auto release = [&]() { hipFree(d_x); hipFree(d_s); };
+    hipError_t e;
+    if ((e = hipMalloc((void**)&d_x, xb)) != hipSuccess || (out_norm2 && (e = hipMalloc((void**)&d_s, (size_t)n * 4)) != hipSuccess) ||
+        (e = hipMemcpy(d_x, rows, xb, hipMemcpyHostToDevice)) != hipSuccess) {
+        release();
+        return fail(IDIST_ERR_HIP, "normalize_batch staging: %s", hipGetErrorString(e));
+    }
+    if (launch_normalize(d_x, d_x, n, dim, dim, 0u, d_s, prop.multiProcessorCount, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
+    if ((e = hipMemcpy(out_rows, d_x, xb, hipMemcpyDeviceToHost)) != hipSuccess ||
+        (out_norm2 && (e = hipMemcpy(out_norm2, d_s, (size_t)n * 4, hipMemcpyDeviceToHost)) != hipSuccess)) {
+        release();
+        return fail(IDIST_ERR_HIP, "normalize_batch: %s", hipGetErrorString(e));
+    }
+    release();
+    return IDIST_OK;
 }
 
 }  // extern "C"

@@ -10,9 +10,12 @@
 //
 // `trait Point { fn distance(&self, &Self) -> f32 }` is arbitrary user code in the reference and
 // cannot be shipped to a GPU.  Here a Point type exposes its coordinates as f32 and names one of
-// the two distances the reference itself ships:
+// the two distances the reference itself ships, or the cosine distance the engine adds:
 //     static constexpr int METRIC = IDIST_METRIC_L2SQ;   // FloatArray, py/lib.rs:378-421
 //     static constexpr int METRIC = IDIST_METRIC_L2;     // tests/all.rs:93-97, examples/colors.rs
+//     static constexpr int METRIC = IDIST_METRIC_COSINE; // 1 - cos: the L2SQ index over rows and queries the ENGINE normalises
+//                                                        // (include/idist.h); write_f32 hands over the point as it is, and the
+//                                                        // points this header keeps (Item::point, iter()) stay the caller's
 //     size_t dim() const;  void write_f32(float* out) const;
 // A Point without that interface is a compile-time error — there is no CPU fallback.
 // Errors: the reference API is infallible (it panics at core/lib.rs:256 and :148); every non-OK

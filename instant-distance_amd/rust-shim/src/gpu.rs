@@ -90,13 +90,16 @@ fn expect(status: i32) {
     }
 }
 
-/// Which of the two distances the reference ships a point type computes (`Point::METRIC`).
+/// Which distance a point type computes (`Point::METRIC`): one of the two the reference ships, or the engine's cosine distance.
 #[derive(Clone, Copy, Debug, Eq, PartialEq)]
 pub enum Metric {
     /// `FloatArray::distance`, instant-distance-py/src/lib.rs:378-421 (squared L2, eight FMA chains)
     L2Sq = 0,
     /// the sqrt of it: `tests/all.rs:93-97`, `examples/colors.rs:21-25`
     L2 = 1,
+    /// cosine distance `1 - cos`: the `L2Sq` index over rows and queries the engine normalises itself (`IDIST_METRIC_COSINE`,
+    /// include/idist.h); the crate's own `points` stay the caller's vectors
+    Cosine = 2,
 }
 
 /// Hardware queues: every `Search` owns a HIP stream, and the runtime multiplexes a process's streams onto
