@@ -66,7 +66,7 @@ enum { IDIST_TIES_STRICT = 0, IDIST_TIES_DROP = 1 };
 enum {
     IDIST_METRIC_L2SQ = 0, /* FloatArray::distance, instant-distance-py/src/lib.rs:378-421 */
     IDIST_METRIC_L2 = 1,   /* sqrt of it: tests/all.rs:93-97, examples/colors.rs:21-25 */
-    IDIST_METRIC_COSINE = 2 /* cosine distance 1 - cos (no counterpart in the reference), DEFINED through L2SQ: with s(x) = the canonical
+    IDIST_METRIC_COSINE = 2, /* cosine distance 1 - cos (no counterpart in the reference), DEFINED through L2SQ: with s(x) = the canonical
                               L2SQ distance of x to the origin, r = sqrtf(s) and x^ = x / r coordinate by coordinate (f32, correctly
                               rounded; x^ = x when r is not a positive finite number: zero rows, NaN / inf, s overflowed or underflowed),
                               an index with this metric over rows X IS the L2SQ index over X^ — same graph, same ids, order, counts and
@@ -74,6 +74,30 @@ enum {
                               multiply of the canonical L2SQ distance d (|q^ - x^|^2 / 2 = 1 - cos).  Rows are normalised where they become
                               the index's device copy (build, build_device, import), queries per call; the caller's buffers are never
                               written.  idist_index_device_buffers / idist_replicate* hand on rows that already are x^. */
+    /* (3 is not assigned and is refused) */
+    IDIST_METRIC_DOT = 4    /* inner product, nearest = LARGEST q.x (no counterpart in the reference), DEFINED through L2SQ over one more
+                              coordinate.  dim is the caller's dimension everywhere in this ABI, kdim = dim + 1 what the index stores.
+                              1. s(x) = the canonical L2SQ distance of x to the origin over its dim coordinates (what
+                                 idist_normalize_batch returns as out_norm2; NOT taken over kdim coordinates).  A row is finite when
+                                 s(x) is neither NaN nor inf.
+                              2. S = idist_config.dot_bound if that is > 0, else the maximum of s(x) over the finite rows (0 when there
+                                 is none).  A given bound must be finite and >= every finite s(x): IDIST_ERR_INVALID_ARG otherwise,
+                                 naming a row.
+                              3. e(x) = sqrtf(S - s(x)) for finite rows (one f32 subtraction, a correctly rounded square root), else 0.
+                              4. x~ = (x, e(x)), q~ = (q, 0), both of length kdim: |q~ - x~|^2 = |q|^2 + S - 2 q.x.
+                              5. An index with this metric over rows X IS the L2SQ index over X~ - same graph, same ids, order, counts
+                                 and counters for a query q as the L2SQ search of q~.
+                              6. With d the canonical L2SQ distance and t = s(q) + S (one f32 add), every reported distance is
+                                 0.5f * (d - t) in IEEE f32, approximately -q.x; a d that is +inf (the padding) or NaN is reported
+                                 unchanged.  It is non-decreasing in d (nearest first still holds, possibly with ties).  Its absolute
+                                 error is of the order eps * (|q|^2 + S), NOT eps * |q.x|: one giant-norm outlier row coarsens every
+                                 other distance.  idist_filter_bound_batch: the transformed bound is a lower bound of the reported
+                                 value; "no bound" (raw 0) becomes the trivial bound -t / 2.
+                              Rows are augmented where they become the index's device copy (build, build_device, import), queries per
+                              call; the caller's buffers are never written.  idist_index_device_buffers / idist_replicate* hand on rows
+                              that already are x~ (row_stride is that of kdim), and a replication target needs the same S:
+                              idist_index_alloc takes it from idist_config.dot_bound (0 there is refused).  Every part of a partitioned
+                              index must hold the same S bit for bit.  dim <= 65535. */
 };
 
 /* Builder fields, core/lib.rs:23-31 (defaults :101-128). */
@@ -109,6 +133,8 @@ typedef struct idist_config {
                                    next to `nearest` (8 B per entry): a larger one spares such data the repeated launch at
                                    the price of fewer resident waves per CU.  (HBM bags: n keys per query slot, as many
                                    slots as fit 1 GiB.) */
+    float dot_bound;            /* IDIST_METRIC_DOT only (ignored otherwise): the bound S on the rows' squared norms, 0 (the default) =
+                                   derive it from the rows.  idist_index_get_info reports the S in use. */
 } idist_config;
 
 typedef struct idist_index idist_index;
@@ -123,6 +149,7 @@ typedef struct idist_index_info {
     int32_t device;
     uint32_t layer_len[IDIST_MAX_LAYERS]; /* layer_len[l-1] = rows of layers[l-1], l = 1..n_upper */
     uint32_t tie_capacity;      /* the tie region the build ended up using (see idist_config.tie_capacity) */
+    float dot_bound;            /* IDIST_METRIC_DOT: the bound S in use (given or derived); 0 for every other metric */
 } idist_index_info;
 
 /* Raw device views (for RCCL replication by the host: torch.distributed / ncclBroadcast). */
@@ -386,6 +413,14 @@ idist_status idist_bruteforce(const idist_index* idx, const float* queries, uint
  * needs to reproduce a cosine index with an L2SQ one, bit for bit. */
 idist_status idist_normalize_batch(const float* rows, uint32_t n, uint32_t dim, float* out_rows, float* out_norm2,
                                    int32_t device);
+
+/* The augmentation of IDIST_METRIC_DOT on its own (steps 1-4 of its definition).  rows: n x dim, row-major.  bound_in: 0 = derive S
+ * from the rows, else the S to use (finite, > 0, >= every finite s(x): IDIST_ERR_INVALID_ARG otherwise, naming a row).
+ * out_rows (n x (dim + 1), may be NULL when only the norms and the bound are wanted) = x~; out_norm2 (n, may be NULL) = s(x);
+ * out_bound (may be NULL) = S.  Queries are augmented by appending a 0.  Host pointers; `rows` is only read.  What a caller needs
+ * to reproduce a DOT index with an L2SQ one bit for bit, and to find the common bound of the parts of a partitioned index. */
+idist_status idist_dot_augment_batch(const float* rows, uint32_t n, uint32_t dim, float bound_in, float* out_rows,
+                                     float* out_norm2, float* out_bound, int32_t device);
 
 #ifdef __cplusplus
 }

@@ -22,6 +22,7 @@ MAX_EF = 4096
 METRIC_L2SQ = 0
 METRIC_L2 = 1
 METRIC_COSINE = 2
+METRIC_DOT = 4   # (3 is unassigned and refused)
 TIES_STRICT = 0
 TIES_DROP = 1
 
@@ -47,6 +48,7 @@ class Config(C.Structure):
         ("max_batch", C.c_uint32),
         ("tie_policy", C.c_int32),
         ("tie_capacity", C.c_uint32),
+        ("dot_bound", C.c_float),
     ]
 
 
@@ -56,6 +58,7 @@ class IndexInfo(C.Structure):
         ("ef_search", C.c_uint32), ("metric", C.c_int32), ("device", C.c_int32),
         ("layer_len", C.c_uint32 * MAX_LAYERS),
         ("tie_capacity", C.c_uint32),
+        ("dot_bound", C.c_float),
     ]
 
 
@@ -137,6 +140,7 @@ SYMBOLS = {
     "idist_filter_bound_batch": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, _f32p]),
     "idist_bruteforce": (C.c_int32, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),
     "idist_normalize_batch": (C.c_int32, [_f32p, C.c_uint32, C.c_uint32, _f32p, _f32p, C.c_int32]),
+    "idist_dot_augment_batch": (C.c_int32, [_f32p, C.c_uint32, C.c_uint32, C.c_float, _f32p, _f32p, _f32p, C.c_int32]),
 }
 
 

@@ -13,7 +13,8 @@ Same names, argument meaning and error behaviour as the reference
 cannot run on a GPU; here a point is an f32 vector and the distance is one of the two
 the reference itself ships: squared L2 (FloatArray, the default) or L2 with sqrt
 (the Point of tests/all.rs and examples/colors.rs) — `Builder.metric()`.  METRIC_COSINE (not in the reference) is
-squared L2 over rows and queries the engine normalises itself, reported as 1 - cos; the host copies stay the caller's rows.
+squared L2 over rows and queries the engine normalises itself, reported as 1 - cos; METRIC_DOT (not in the reference either) is
+squared L2 over rows the engine gives one more coordinate, reported as -q.x; the host copies stay the caller's rows.
 
 All compute goes through the C ABI (include/idist.h); there is no CPU path.
 """
@@ -27,7 +28,7 @@ from typing import Any, Iterator, Sequence
 import numpy as np
 
 from . import _capi
-from ._capi import INVALID, M, M2, METRIC_COSINE, METRIC_L2, METRIC_L2SQ, TIES_DROP, TIES_STRICT
+from ._capi import INVALID, M, M2, METRIC_COSINE, METRIC_DOT, METRIC_L2, METRIC_L2SQ, TIES_DROP, TIES_STRICT
 
 PointId = int
 
@@ -59,6 +60,7 @@ class Builder:
         self._progress = None
         self._tie_policy = TIES_STRICT
         self._tie_capacity = 0
+        self._dot_bound = 0.0
 
     @classmethod
     def default(cls) -> "Builder":
@@ -99,8 +101,21 @@ class Builder:
         1 - cos, defined as the METRIC_L2SQ index over the rows normalised by `normalize()`'s arithmetic (the engine does it where
         the rows reach the device, and to every query), with distances reported as half the squared L2 distance of the
         normalised vectors.  `points`, `Item.point` and `__getitem__` keep the caller's rows; rows without a positive finite norm
-        (zero, NaN, inf) take part unchanged."""
+        (zero, NaN, inf) take part unchanged.
+        METRIC_DOT: the inner product, nearest = largest q.x, defined as the METRIC_L2SQ index over the rows `augment_dot()`
+        returns — every row gets the extra coordinate sqrt(S - |x|^2), S the bound `dot_bound()` sets or the largest squared norm
+        of the rows, every query a trailing 0 — with distances reported as 0.5 * (d - (|q|^2 + S)), approximately -q.x.  The
+        error of a reported distance is of the order eps * (|q|^2 + S), not eps * |q.x|: one row with a giant norm coarsens all
+        the others.  `points`, `Item.point` and `__getitem__` keep the caller's dim-wide rows; rows with a NaN / inf squared
+        norm get the extra coordinate 0."""
         self._metric = int(metric)
+        return self
+
+    def dot_bound(self, bound: float) -> "Builder":
+        """METRIC_DOT only: the bound S on the squared norms of the rows (finite, >= every finite row's; 0 = the default, derive it
+        from the rows).  Indexes that are searched as one (PartitionedHnsw) or compared with each other need the same S;
+        `Hnsw.info().dot_bound` reports the one in use."""
+        self._dot_bound = float(np.float32(bound))
         return self
 
     def tie_policy(self, policy: int) -> "Builder":
@@ -143,6 +158,7 @@ class Builder:
         c.max_batch = self._max_batch
         c.tie_policy = self._tie_policy
         c.tie_capacity = self._tie_capacity
+        c.dot_bound = self._dot_bound
         return c
 
     def build(self, points, values: Sequence[Any]) -> "HnswMap":
@@ -318,6 +334,24 @@ def normalize(points, device: int = 0, return_norm2: bool = False):
     L.check(L.idist_normalize_batch(_capi.f32p(pts), pts.shape[0], max(pts.shape[1], 1), _capi.f32p(out),
                                     _capi.f32p(s) if return_norm2 else None, int(device)))
     return (out, s) if return_norm2 else out
+
+
+def augment_dot(points, bound: float = 0.0, device: int = 0, return_norm2: bool = False):
+    """The rows a METRIC_DOT index holds for `points`, bit for bit (idist_dot_augment_batch): [n, dim + 1] rows (x, sqrt(S - s(x))),
+    s = the canonical squared-L2 distance of the row to the origin, S = `bound` or, when that is 0, the largest finite s.  Returns
+    (rows, S) — or (rows, S, s) with `return_norm2`.  A METRIC_L2SQ index over these rows, searched with the queries given a
+    trailing 0, returns the ids of the METRIC_DOT index; its distances d map to 0.5 * (d - (s(q) + S)).  A bound below a row's
+    squared norm, negative or not finite raises IdistError."""
+    pts = _as_points(points)
+    n, dim = pts.shape
+    out = np.empty((n, max(dim, 1) + 1), dtype=np.float32)
+    s = np.empty(n, dtype=np.float32)
+    S = C.c_float(0.0)
+    L = _lib()
+    L.check(L.idist_dot_augment_batch(_capi.f32p(pts), n, max(dim, 1), float(np.float32(bound)), _capi.f32p(out), _capi.f32p(s),
+                                      C.byref(S), int(device)))
+    S = np.float32(S.value)
+    return (out, S, s) if return_norm2 else (out, S)
 
 
 def _as_points(points) -> np.ndarray:
@@ -533,7 +567,8 @@ class Hnsw:
 
     def filter_bounds(self, queries, ids) -> np.ndarray:
         """The walk's reject filter over id lists: a lower bound of every distance, from the compact copy of the rows alone
-        (0 where there is none) — idist_filter_bound_batch."""
+        (0 where there is none) — idist_filter_bound_batch.  METRIC_DOT: the bounds are reported like the distances (a lower bound of
+        what `distances` returns); "no bound" is the trivial -(|q|^2 + S) / 2."""
         q = _as_points(queries)
         ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(q.shape[0], -1)
         out = np.zeros(ids.shape, dtype=np.float32)

@@ -7,6 +7,7 @@
 #include "idist_combine.hpp"
 #include "idist_merge.hpp"
 #include "idist_normalize.hpp"
+#include "idist_dot.hpp"
 
 #ifndef IDIST_EMU
 #include <hip/hip_runtime.h>
@@ -156,8 +157,11 @@ idist_status check_device(int32_t device) {
 idist_status validate_config(const idist_config* cfg, bool for_build) {
     if (!cfg) return fail(IDIST_ERR_INVALID_ARG, "config is null");
     if (cfg->ef_search > IDIST_MAX_EF) return fail(IDIST_ERR_INVALID_ARG, "ef_search %u > %u", cfg->ef_search, IDIST_MAX_EF);
-    if (cfg->metric != IDIST_METRIC_L2SQ && cfg->metric != IDIST_METRIC_L2 && cfg->metric != IDIST_METRIC_COSINE)
+    if (cfg->metric != IDIST_METRIC_L2SQ && cfg->metric != IDIST_METRIC_L2 && cfg->metric != IDIST_METRIC_COSINE &&
+        cfg->metric != IDIST_METRIC_DOT)
         return fail(IDIST_ERR_INVALID_ARG, "unknown metric %d", cfg->metric);
+    if (cfg->metric == IDIST_METRIC_DOT && !(cfg->dot_bound >= 0.0f && cfg->dot_bound < INFINITY))
+        return fail(IDIST_ERR_INVALID_ARG, "dot_bound %g is not a finite number >= 0", (double)cfg->dot_bound);
     if (cfg->tie_policy != IDIST_TIES_STRICT && cfg->tie_policy != IDIST_TIES_DROP)
         return fail(IDIST_ERR_INVALID_ARG, "unknown tie_policy %d", cfg->tie_policy);
     if (cfg->tie_capacity > 4096) return fail(IDIST_ERR_INVALID_ARG, "tie_capacity %u > 4096", cfg->tie_capacity);
@@ -172,7 +176,10 @@ idist_status validate_config(const idist_config* cfg, bool for_build) {
 // index's device copy, queries per launch, reported distances are halved — and every kernel and every policy that asks for the
 // metric (IndexView.metric, the MFMA paths) sees squared L2.
 inline bool is_cosine(const idist_config& cfg) { return cfg.metric == IDIST_METRIC_COSINE; }
-inline int32_t kernel_metric(const idist_config& cfg) { return is_cosine(cfg) ? (int32_t)IDIST_METRIC_L2SQ : cfg.metric; }
+// IDIST_METRIC_DOT is the squared-L2 index over rows with one more coordinate (idist_dot.hpp): an index keeps the caller's `dim`
+// (argument checks, query strides, what it reports) and `kdim` = dim + 1 (layout, geometry, filter, every kernel launch).
+inline bool is_dot(const idist_config& cfg) { return cfg.metric == IDIST_METRIC_DOT; }
+inline int32_t kernel_metric(const idist_config& cfg) { return is_cosine(cfg) || is_dot(cfg) ? (int32_t)IDIST_METRIC_L2SQ : cfg.metric; }
 
 }  // namespace
 
@@ -202,7 +209,9 @@ struct idist_index {
     mutable idist_search_ctx* comb_ctx[kCombineLeaders] = {nullptr};
     int32_t device = 0;
     idist_config cfg{};
-    uint32_t n = 0, dim = 0;
+    uint32_t n = 0, dim = 0;     // dim: the caller's
+    uint32_t kdim = 0;           // coordinates of a stored row: dim, or dim + 1 for IDIST_METRIC_DOT — what L and every kernel see
+    float dot_S = 0.0f;          // IDIST_METRIC_DOT: the bound S in use (cfg.dot_bound holds the same value once it is known)
     Layout L{};
     uint32_t n_upper = 0;
     uint32_t layer_len[IDIST_MAX_LAYERS] = {0};
@@ -227,7 +236,7 @@ struct idist_index {
         v.upper = d_upper;
         v.layer_off = d_layer_off;
         v.n = n;
-        v.dim = dim;
+        v.dim = kdim;
         v.stride = L.stride;
         v.nb = L.nb;
         v.rs = L.rs;
@@ -328,7 +337,9 @@ struct idist_search_ctx {
     uint32_t* d_ctr = nullptr;
     size_t cap_q = 0, cap_out = 0, cap_nq = 0;
     float* d_qn = nullptr;         // cosine indexes: the launch's queries, normalised (launch_search); grown like the staging above
-    size_t cap_qn = 0;
+    size_t cap_qn = 0;             // (DOT indexes: the launch's queries with the trailing 0, [nq][kdim])
+    float* d_sq = nullptr;         // DOT indexes: s(q) per query of the launch, for the report pass
+    size_t cap_sq = 0;
     bool tie_overflowed = false;
     uint32_t tie_cap = 0;          // tie capacity this context escalated to (0 = the index's)
     // strict ties, last resort: one bag of n keys per slot in HBM (the reference's candidate heap is unbounded, core/lib.rs:564)
@@ -364,6 +375,9 @@ struct idist_partitioned {
     uint32_t base[kMergeMaxLists + 1] = {0};
     uint32_t dim = 0;
     int32_t metric = 0, merge_device = 0;
+    float dot_S = 0.0f;                      // DOT: the bound every part holds
+    float *d_qm = nullptr, *d_sq = nullptr;  // DOT, on the merge device: the batch's queries and their s(q), for the report after the merge
+    size_t cap_qm = 0, cap_sq = 0;
     // on the merge device: the parts' lists [P][nq][width] and the merged result [nq][out_width]
     uint32_t *s_pid = nullptr, *s_cnt = nullptr, *s_ctr = nullptr, *o_pid = nullptr, *o_cnt = nullptr, *o_ctr = nullptr;
     float *s_dist = nullptr, *o_dist = nullptr;
@@ -433,6 +447,7 @@ idist_status index_alloc(uint32_t n, uint32_t dim, const idist_config* cfg, cons
     if (!out) return fail(IDIST_ERR_INVALID_ARG, "out is null");
     *out = nullptr;
     if (dim == 0 || dim > 65536) return fail(IDIST_ERR_INVALID_ARG, "dim %u out of [1,65536]", dim);
+    if (is_dot(*cfg) && dim > 65535) return fail(IDIST_ERR_INVALID_ARG, "dim %u out of [1,65535] for the inner-product metric (rows hold dim + 1 coordinates)", dim);
     if (n == 0xFFFFFFFFu) return fail(IDIST_ERR_INVALID_ARG, "n must be < u32::MAX (core/lib.rs:256)");
     if (n_upper >= IDIST_MAX_LAYERS) return fail(IDIST_ERR_INVALID_ARG, "more than %u layers", IDIST_MAX_LAYERS);
     CHK(check_device(device));
@@ -445,7 +460,9 @@ idist_status index_alloc(uint32_t n, uint32_t dim, const idist_config* cfg, cons
     ix->cfg = *cfg;
     ix->n = n;
     ix->dim = dim;
-    ix->L = make_layout(dim);
+    ix->kdim = dim + (is_dot(*cfg) ? 1u : 0u);
+    ix->dot_S = is_dot(*cfg) ? cfg->dot_bound : 0.0f;     // replication targets: the source's S; builds and imports: load_points_device
+    ix->L = make_layout(ix->kdim);
     ix->n_upper = n_upper;
     hipDeviceProp_t p;
     if (hipGetDeviceProperties(&p, device) == hipSuccess) ix->n_cu = p.multiProcessorCount;
@@ -499,9 +516,84 @@ idist_status launch_scale_half(float* d, size_t total, int n_cu, hipStream_t str
     return IDIST_OK;
 }
 
-// natural row-major device points -> blocked rows of the index (cosine: normalised there, the caller's rows are only read).
-// The ONLY place rows are normalised: replicas and broadcast targets copy device rows that already are x^.
+// the passes of IDIST_METRIC_DOT (idist_dot.hpp), enqueued on `stream`
+// s(x) of n natural rows into d_norm2; d_aug (may be nullptr): [n][dim + 1] = (row, 0), the augmented queries
+idist_status launch_dot_norms(const float* d_in, uint32_t n, uint32_t dim, float* d_norm2, float* d_aug, int n_cu, hipStream_t stream) {
+    if (n == 0) return IDIST_OK;
+    const uint32_t grid = std::min<uint32_t>((n + 7u) / 8u, (uint32_t)std::max(n_cu, 1) * 32u);
+    IDIST_LAUNCH(dot_norms_kernel, grid, 64, 0, stream, d_in, n, dim, d_norm2, d_aug);
+    HIPCHK(hipGetLastError());
+    return IDIST_OK;
+}
+// d -> 0.5f * (d - (s_q[row] + S)) over [nq][width] reported distances
+idist_status launch_dot_report(float* d, const float* d_sq, float S, uint32_t nq, uint32_t width, int n_cu, hipStream_t stream) {
+    const size_t total = (size_t)nq * width;
+    if (total == 0) return IDIST_OK;
+    const uint32_t vec = (width % 4u) == 0u && ((uintptr_t)d & 15u) == 0u ? 1u : 0u;
+    const uint32_t grid = (uint32_t)std::min<size_t>((total / 4u + 255u) / 256u + 1u, (size_t)std::max(n_cu, 1) * 8u);
+    IDIST_LAUNCH(dot_report_kernel, grid, 256, 0, stream, d, d_sq, S, total, width, vec);
+    HIPCHK(hipGetLastError());
+    return IDIST_OK;
+}
+constexpr uint32_t kDotMaxWaves = 1024;
+// The bound of step 2 of the definition for n rows whose s(x) sit in d_norm2: bound_in > 0 is checked against every finite s(x),
+// 0 derives the maximum.  Synchronises the device (null stream).  d_part: kDotMaxWaves + 1 u32 of device scratch.
+idist_status dot_bound_of(const float* d_norm2, uint32_t n, float bound_in, uint32_t* d_part, float* S_out) {
+    if (!(bound_in >= 0.0f && bound_in < INFINITY)) return fail(IDIST_ERR_INVALID_ARG, "dot_bound %g is not a finite number >= 0", (double)bound_in);
+    uint32_t mbits = 0;
+    if (n) {
+        const uint32_t waves = std::min<uint32_t>((n + 63u) / 64u, kDotMaxWaves);
+        IDIST_LAUNCH(dot_max_bits_kernel, waves, 64, 0, (hipStream_t) nullptr, d_norm2, n, d_part);
+        IDIST_LAUNCH(dot_max_bits_kernel, 1, 64, 0, (hipStream_t) nullptr, reinterpret_cast<const float*>(d_part), waves, d_part + kDotMaxWaves);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpy(&mbits, d_part + kDotMaxWaves, 4, hipMemcpyDeviceToHost));
+    }
+    float smax;
+    memcpy(&smax, &mbits, 4);
+    if (bound_in > 0.0f && smax > bound_in) {               // name a row: the first one above the bound
+        std::vector<float> h(n);
+        HIPCHK(hipMemcpy(h.data(), d_norm2, (size_t)n * 4, hipMemcpyDeviceToHost));
+        uint32_t r = 0;
+        while (r < n && !(h[r] > bound_in && h[r] < INFINITY)) r++;
+        return fail(IDIST_ERR_INVALID_ARG, "dot_bound %g is below the squared norm %g of row %u", (double)bound_in, (double)(r < n ? h[r] : smax), r);
+    }
+    *S_out = bound_in > 0.0f ? bound_in : smax;
+    return IDIST_OK;
+}
+// natural d_nat [n][dim] -> d_out [n][stride] rows of kdim = dim + 1 coordinates in the layout (nb, natural remainder); *S_io: the
+// bound given (0 = derive) on entry, the bound in use on return.  d_norm2_out (may be nullptr): s(x) per row.  Synchronises.
+idist_status dot_augment_device(const float* d_nat, float* d_out, uint32_t n, uint32_t dim, uint32_t stride, uint32_t nb, float* S_io,
+                                float* d_norm2_out, int n_cu) {
+    float* d_s = nullptr;
+    uint32_t* d_part = nullptr;
+    auto release = [&](idist_status st) { if (!d_norm2_out) hipFree(d_s); hipFree(d_part); return st; };
+    if (d_norm2_out) d_s = d_norm2_out;
+    else HIPCHK(hipMalloc((void**)&d_s, std::max<size_t>((size_t)n * 4, 256)));
+    if (hipMalloc((void**)&d_part, (kDotMaxWaves + 1) * 4) != hipSuccess) return release(fail(IDIST_ERR_HIP, "hipMalloc failed"));
+    idist_status st = launch_dot_norms(d_nat, n, dim, d_s, nullptr, n_cu, nullptr);
+    if (st != IDIST_OK) return release(st);
+    float S = 0.0f;
+    if ((st = dot_bound_of(d_s, n, *S_io, d_part, &S)) != IDIST_OK) return release(st);
+    if (d_out && n) {
+        const size_t total = (size_t)n * stride;
+        const int grid = (int)std::min<size_t>((total + 255) / 256, 65536);
+        IDIST_LAUNCH(dot_augment_rows_kernel, grid, 256, 0, (hipStream_t) nullptr, d_nat, d_out, n, dim, stride, nb, d_s, S);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return release(fail(IDIST_ERR_HIP, "dot_augment_rows_kernel failed"));
+    }
+    *S_io = S;
+    return release(IDIST_OK);
+}
+
+// natural row-major device points -> blocked rows of the index (cosine: normalised there, the caller's rows are only read; DOT:
+// augmented on the way, bound checked or derived).  The ONLY place rows are normalised / augmented: replicas and broadcast targets
+// copy device rows that already are x^ / x~.
 idist_status load_points_device(idist_index* ix, const float* d_nat) {
+    if (is_dot(ix->cfg)) {
+        float S = ix->cfg.dot_bound;
+        CHK(dot_augment_device(d_nat, ix->d_points, ix->n, ix->dim, ix->L.stride, ix->L.nb, &S, nullptr, ix->n_cu));
+        ix->dot_S = ix->cfg.dot_bound = S;
+        return IDIST_OK;
+    }
     if (ix->n == 0) return IDIST_OK;
     const size_t total = (size_t)ix->n * ix->L.stride;
     const int grid = (int)std::min<size_t>((total + 255) / 256, 65536);
@@ -1240,10 +1332,10 @@ idist_status filter_ensure(const idist_index* ix) {
     // robust range: mean and sigma of the central 98 % of the sampled coordinates (a few wild values — or heavy tails — must not
     // stretch the lattice: they are clamped, and only their own rows pay for it), sigma rescaled to the whole of a Gaussian
     std::vector<float> vals;
-    vals.reserve((size_t)ns * ix->dim);
+    vals.reserve((size_t)ns * ix->kdim);
     for (uint32_t r = 0; r < ns; r++)
         for (uint32_t pos = 0; pos < stride; pos++) {
-            if (natural_pos(pos, ix->L.nb) >= ix->dim) continue;
+            if (natural_pos(pos, ix->L.nb) >= ix->kdim) continue;
             const float v = smp[(size_t)r * stride + pos];
             if (std::fabs(v) <= 3.0e38f) vals.push_back(v);
         }
@@ -1274,7 +1366,7 @@ idist_status filter_ensure(const idist_index* ix) {
     f.dscale = f.step256 * f.step256;
     // every float step of the test (the conversion of I, dscale, the sums, the canonical chain of dim / 8 + 7 roundings) is covered
     f.up = 1.0f + 4.8828125e-4f + 6.0e-8f * (float)(ix->L.stride / 8u + 8u);
-    f.slack = 4.8e-7f * std::sqrt((float)ix->dim);
+    f.slack = 4.8e-7f * std::sqrt((float)ix->kdim);
     uint8_t* rows = nullptr;
     if (hipMalloc((void**)&rows, (size_t)ix->n * fs) != hipSuccess) {
         (void)hipGetLastError();
@@ -1282,7 +1374,7 @@ idist_status filter_ensure(const idist_index* ix) {
         return IDIST_OK;
     }
     const uint32_t grid = std::min<uint32_t>(ix->n, (uint32_t)ix->n_cu * 32u);
-    IDIST_LAUNCH(filter_rows_kernel, grid, 64, 0, nullptr, ix->d_points, ix->n, ix->dim, stride, ix->L.nb, rows, fs, f.lo, f.step256);
+    IDIST_LAUNCH(filter_rows_kernel, grid, 64, 0, nullptr, ix->d_points, ix->n, ix->kdim, stride, ix->L.nb, rows, fs, f.lo, f.step256);
     if (hipDeviceSynchronize() != hipSuccess) {
         const hipError_t e = hipGetLastError();
         hipFree(rows);
@@ -1314,6 +1406,28 @@ idist_status launch_search(const idist_index* ix, idist_search_ctx* ctx, const f
             ctx->cap_qn = cap;
         }
         CHK(launch_normalize(d_q, ctx->d_qn, nq, ix->dim, ix->dim, 0u, nullptr, ix->n_cu, stream));
+        d_q = ctx->d_qn;
+    }
+    // DOT: the same shape — the walk reads the queries with their trailing 0 from the context's buffer, s(q) is kept for the report
+    // pass behind the walk.  `prepared`: d_q already holds [nq][kdim] rows and the caller reports after its merge.
+    const bool dot = is_dot(ix->cfg) && !prepared;
+    if (dot) {
+        const size_t qb = (size_t)nq * ix->kdim * 4, sb = (size_t)nq * 4;
+        if (qb > ctx->cap_qn) {
+            size_t cap = std::max<size_t>(ctx->cap_qn, 4096);
+            while (cap < qb) cap <<= 1;
+            hipFree(ctx->d_qn); ctx->d_qn = nullptr; ctx->cap_qn = 0;
+            HIPCHK(hipMalloc((void**)&ctx->d_qn, cap));
+            ctx->cap_qn = cap;
+        }
+        if (sb > ctx->cap_sq) {
+            size_t cap = std::max<size_t>(ctx->cap_sq, 256);
+            while (cap < sb) cap <<= 1;
+            hipFree(ctx->d_sq); ctx->d_sq = nullptr; ctx->cap_sq = 0;
+            HIPCHK(hipMalloc((void**)&ctx->d_sq, cap));
+            ctx->cap_sq = cap;
+        }
+        CHK(launch_dot_norms(d_q, nq, ix->dim, ctx->d_sq, ctx->d_qn, ix->n_cu, stream));
         d_q = ctx->d_qn;
     }
     SearchArgs a{};
@@ -1542,6 +1656,7 @@ idist_status launch_search(const idist_index* ix, idist_search_ctx* ctx, const f
         ctx->recs[ctx->n_rec++ % IDIST_EVENT_RING] = {(int32_t)slot, 0.0f};
     }
     if (cosine) CHK(launch_scale_half(d_dist, (size_t)nq * ef, ix->n_cu, stream));
+    if (dot) CHK(launch_dot_report(d_dist, ctx->d_sq, ix->dot_S, nq, ef, ix->n_cu, stream));
     return IDIST_OK;
 }
 
@@ -1572,6 +1687,7 @@ idist_status idist_default_config(idist_config* cfg) {   // core/lib.rs:101-128
     cfg->max_batch = 0;
     cfg->tie_policy = IDIST_TIES_STRICT;
     cfg->tie_capacity = 0;
+    cfg->dot_bound = 0.0f;
     return IDIST_OK;
 }
 
@@ -1723,6 +1839,9 @@ idist_status idist_index_alloc(uint32_t n, uint32_t dim, const idist_config* cfg
                                uint32_t n_upper, int32_t device, idist_index** out) {
     CHK(validate_config(cfg, false));
     if (n_upper && !layer_len) return fail(IDIST_ERR_INVALID_ARG, "layer_len is null");
+    // the rows this index will be filled with already are x~: the S they were made with has to come with them
+    if (is_dot(*cfg) && !(cfg->dot_bound > 0.0f))
+        return fail(IDIST_ERR_INVALID_ARG, "an inner-product replication target needs the source's dot_bound (idist_index_get_info), got 0");
     return index_alloc(n, dim, cfg, layer_len, n_upper, device, out);
 }
 
@@ -1752,6 +1871,7 @@ idist_status idist_index_get_info(const idist_index* idx, idist_index_info* out)
     out->metric = idx->cfg.metric;
     out->device = idx->device;
     out->tie_capacity = tie_capacity(idx->cfg);
+    out->dot_bound = is_dot(idx->cfg) ? idx->dot_S : 0.0f;
     for (uint32_t l = 0; l < idx->n_upper; l++) out->layer_len[l] = idx->layer_len[l];
     return IDIST_OK;
 }
@@ -1832,6 +1952,7 @@ void idist_search_ctx_free(idist_search_ctx* c) {
     if (c->h_io) hipHostFree(c->h_io);
     hipFree(c->d_q);
     hipFree(c->d_qn);
+    hipFree(c->d_sq);
     hipFree(c->d_pid);
     hipFree(c->d_dist);
     hipFree(c->d_cnt);
@@ -2012,8 +2133,8 @@ static idist_status search_batch_impl(const idist_index* idx, idist_search_ctx* 
     // pinned, device-mapped buffer that the kernel reads and writes itself; the call is a host memcpy, one launch, one
     // stream sync, a host memcpy.  (The general path below costs six copy / memset calls of ~10 us each around the kernel.)
     const size_t io_need = qb + 2 * ob + (size_t)nq * 16 + idist_search_ctx::kIoHeadBytes;
-    // (not for cosine indexes: the completion word the kernel writes would run ahead of the pass that halves the distances)
-    if (io_need <= idist_search_ctx::kIoMaxBytes && !ctx->knobs.no_zero_copy && !is_cosine(idx->cfg)) {
+    // (not for cosine and DOT indexes: the completion word the kernel writes would run ahead of the pass behind the walk)
+    if (io_need <= idist_search_ctx::kIoMaxBytes && !ctx->knobs.no_zero_copy && !is_cosine(idx->cfg) && !is_dot(idx->cfg)) {
         if (io_need > ctx->io_cap) {
             size_t cap = idist_search_ctx::kIoMinBytes;
             while (cap < io_need) cap <<= 1;
@@ -2391,6 +2512,10 @@ static idist_status partitioned_check(idist_partitioned* p, uint32_t* ef_out) {
         if (ix->cfg.metric != first->cfg.metric) return fail(IDIST_ERR_INVALID_ARG, "part %zu: metric %d differs from part 0's %d", i, ix->cfg.metric, first->cfg.metric);
         if (ix->cfg.ef_search != first->cfg.ef_search)
             return fail(IDIST_ERR_INVALID_ARG, "part %zu: ef_search %u differs from part 0's %u", i, ix->cfg.ef_search, first->cfg.ef_search);
+        // DOT: one query augmentation and one report serve all parts, so every part must have been made with the same S, bit for bit
+        if (is_dot(ix->cfg) && memcmp(&ix->dot_S, &first->dot_S, 4) != 0)
+            return fail(IDIST_ERR_INVALID_ARG, "part %zu: dot_bound %.9g differs from part 0's %.9g (build every part with the bound of the whole set)",
+                        i, (double)ix->dot_S, (double)first->dot_S);
         p->base[i] = (uint32_t)n;
         n += ix->n;
         if (n >= (uint64_t)kInvalid) return fail(IDIST_ERR_INVALID_ARG, "part %zu: %llu points together do not fit a PointId", i, (unsigned long long)n);
@@ -2419,6 +2544,7 @@ idist_status idist_partitioned_new(const idist_index* const* parts, uint32_t n_p
     p->dim = parts[0]->dim;
     p->metric = parts[0]->cfg.metric;
     p->merge_device = parts[0]->device;
+    p->dot_S = parts[0]->dot_S;
     idist_status s = partitioned_check(p, nullptr);
     if (s != IDIST_OK) return bail(s);
     for (uint32_t i = 0; i < n_parts; i++) {
@@ -2450,6 +2576,7 @@ void idist_partitioned_free(idist_partitioned* p) {
         hipFree(pt.r_pid); hipFree(pt.r_dist); hipFree(pt.r_cnt); hipFree(pt.r_ctr);
     }
     for (auto& dv : p->devs) hipFree(dv.d_q);
+    hipFree(p->d_qm); hipFree(p->d_sq);
     hipFree(p->s_pid); hipFree(p->s_dist); hipFree(p->s_cnt); hipFree(p->s_ctr);
     hipFree(p->o_pid); hipFree(p->o_dist); hipFree(p->o_cnt); hipFree(p->o_ctr);
     if (p->ev0) hipEventDestroy(p->ev0);
@@ -2503,6 +2630,15 @@ static idist_status partitioned_reserve(idist_partitioned* p, uint32_t nq, uint3
 static idist_status bruteforce_impl(const idist_index* idx, const float* queries, uint32_t nq, uint32_t k, uint32_t* out_pid,
                                     float* out_dist, bool raw);
 
+// DOT: s(q) of the batch on the merge device (which is current), for the report behind the merge; enqueued on p->stream
+static idist_status partitioned_dot_norms(idist_partitioned* p, const float* queries, uint32_t nq) {
+    const size_t qb = (size_t)nq * p->dim * 4, sb = (size_t)nq * 4;
+    if (qb > p->cap_qm) { hipFree(p->d_qm); p->d_qm = nullptr; p->cap_qm = 0; HIPCHK(hipMalloc((void**)&p->d_qm, qb)); p->cap_qm = qb; }
+    if (sb > p->cap_sq) { hipFree(p->d_sq); p->d_sq = nullptr; p->cap_sq = 0; HIPCHK(hipMalloc((void**)&p->d_sq, sb)); p->cap_sq = sb; }
+    HIPCHK(hipMemcpyAsync(p->d_qm, queries, qb, hipMemcpyHostToDevice, p->stream));
+    return launch_dot_norms(p->d_qm, nq, p->dim, p->d_sq, nullptr, p->parts[0].idx->n_cu, p->stream);
+}
+
 // the merge kernel between two events + its result to the host; every part's list is complete in the staging memory.  Cosine
 // parts hand in squared-L2 distances of normalised vectors: they are halved HERE, after the merge — the merge relies on every
 // list being strictly ordered by (distance bits, id), which halving can break for denormal distances.
@@ -2518,6 +2654,9 @@ static idist_status partitioned_merge(idist_partitioned* p, uint32_t nq, uint32_
     HIPCHK(hipEventRecord(p->ev1, p->stream));
     p->timed = true;
     if (p->metric == IDIST_METRIC_COSINE) CHK(launch_scale_half(p->o_dist, (size_t)nq * out_width, p->parts[0].idx->n_cu, p->stream));
+    // DOT likewise: the merge needs the raw keys (non-negative, strictly ordered); the report follows it (partitioned_dot_norms ran
+    // on this stream before)
+    if (p->metric == IDIST_METRIC_DOT) CHK(launch_dot_report(p->o_dist, p->d_sq, p->dot_S, nq, out_width, p->parts[0].idx->n_cu, p->stream));
     const size_t ob = (size_t)nq * out_width * 4;
     HIPCHK(hipMemcpyAsync(out_pid, p->o_pid, ob, hipMemcpyDeviceToHost, p->stream));
     HIPCHK(hipMemcpyAsync(out_dist, p->o_dist, ob, hipMemcpyDeviceToHost, p->stream));
@@ -2542,9 +2681,13 @@ idist_status idist_partitioned_search_batch(idist_partitioned* p, const float* q
     }
     if (!out_pid || !out_dist) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
     const bool counters = out_counters != nullptr;
-    const size_t qb = (size_t)nq * p->dim * 4, row = (size_t)nq * ef;
+    const bool dot = p->metric == IDIST_METRIC_DOT;
+    const uint32_t kdim = p->dim + (dot ? 1u : 0u);
+    // (DOT: a device's buffer holds the [nq][kdim] rows the parts read, followed by the queries as uploaded)
+    const size_t qb = (size_t)nq * p->dim * 4, qa = dot ? (size_t)nq * kdim * 4 : 0, row = (size_t)nq * ef;
     HIPCHK(hipSetDevice(p->merge_device));
     CHK(partitioned_reserve(p, nq, ef, ef));
+    if (dot) CHK(partitioned_dot_norms(p, queries, nq));
     // 1. the queries, once per distinct device that has something to search
     for (size_t d = 0; d < p->devs.size(); d++) {
         idist_partitioned::Dev& dv = p->devs[d];
@@ -2552,8 +2695,12 @@ idist_status idist_partitioned_search_batch(idist_partitioned* p, const float* q
         for (auto& pt : p->parts) used |= pt.ctx && pt.dev_slot == (int)d;
         if (!used) continue;
         HIPCHK(hipSetDevice(dv.device));
-        if (qb > dv.cap_q) { hipFree(dv.d_q); dv.d_q = nullptr; dv.cap_q = 0; HIPCHK(hipMalloc((void**)&dv.d_q, qb)); dv.cap_q = qb; }
-        HIPCHK(hipMemcpy(dv.d_q, queries, qb, hipMemcpyHostToDevice));
+        if (qa + qb > dv.cap_q) { hipFree(dv.d_q); dv.d_q = nullptr; dv.cap_q = 0; HIPCHK(hipMalloc((void**)&dv.d_q, qa + qb)); dv.cap_q = qa + qb; }
+        HIPCHK(hipMemcpy(dv.d_q + qa / 4, queries, qb, hipMemcpyHostToDevice));
+        if (dot) {                                       // augmented once per device; the parts' launches take them as they are
+            CHK(launch_dot_norms(dv.d_q + qa / 4, nq, p->dim, nullptr, dv.d_q, p->parts[0].idx->n_cu, nullptr));
+            HIPCHK(hipStreamSynchronize(nullptr));
+        }
         if (p->metric == IDIST_METRIC_COSINE) {          // normalised once per device; the parts' launches take them as they are
             CHK(launch_normalize(dv.d_q, dv.d_q, nq, p->dim, p->dim, 0u, nullptr, p->parts[0].idx->n_cu, nullptr));
             HIPCHK(hipStreamSynchronize(nullptr));
@@ -2630,6 +2777,7 @@ idist_status idist_partitioned_bruteforce(idist_partitioned* p, const float* que
     const size_t P = p->parts.size(), row = (size_t)nq * k;
     HIPCHK(hipSetDevice(p->merge_device));
     CHK(partitioned_reserve(p, nq, k, k));
+    if (p->metric == IDIST_METRIC_DOT) CHK(partitioned_dot_norms(p, queries, nq));
     std::vector<uint32_t> h_pid(row), h_cnt(nq);
     std::vector<float> h_dist(row);
     for (size_t i = 0; i < P; i++) {
@@ -2668,16 +2816,23 @@ idist_status idist_partitioned_last_merge_ms(idist_partitioned* p, float* ms) {
     return IDIST_OK;
 }
 
+// DOT, the distance entry points: the staged natural queries d_q [nq][dim] -> *d_qa = [nq][kdim] rows with the trailing 0, followed
+// by s(q) [nq] (ONE allocation, the caller frees it).  Enqueued on `st`.
+static idist_status dot_stage_queries(const idist_index* idx, const float* d_q, uint32_t nq, float** d_qa, hipStream_t st) {
+    HIPCHK(hipMalloc((void**)d_qa, ((size_t)nq * idx->kdim + nq) * 4));
+    return launch_dot_norms(d_q, nq, idx->dim, *d_qa + (size_t)nq * idx->kdim, *d_qa, idx->n_cu, st);
+}
+
 idist_status idist_distance_batch(const idist_index* idx, const float* queries, uint32_t nq, const uint32_t* ids,
                                   uint32_t n_ids, float* out_dist) {
     if (!idx) return fail(IDIST_ERR_INVALID_ARG, "idx is null");
     if (nq == 0 || n_ids == 0) return IDIST_OK;
     if (!queries || !ids || !out_dist) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
     HIPCHK(hipSetDevice(idx->device));
-    float *d_q = nullptr, *d_out = nullptr;
+    float *d_q = nullptr, *d_out = nullptr, *d_qa = nullptr;
     uint32_t* d_ids = nullptr;
     const size_t qb = (size_t)nq * idx->dim * 4, ib = (size_t)nq * n_ids * 4;
-    auto release = [&]() { hipFree(d_q); hipFree(d_out); hipFree(d_ids); };
+    auto release = [&]() { hipFree(d_q); hipFree(d_qa); hipFree(d_out); hipFree(d_ids); };
     hipError_t e;
     if ((e = hipMalloc((void**)&d_q, qb)) != hipSuccess || (e = hipMalloc((void**)&d_out, ib)) != hipSuccess ||
         (e = hipMalloc((void**)&d_ids, ib)) != hipSuccess ||
@@ -2688,6 +2843,9 @@ idist_status idist_distance_batch(const idist_index* idx, const float* queries, 
     }
     const bool cosine = is_cosine(idx->cfg);
     if (cosine && launch_normalize(d_q, d_q, nq, idx->dim, idx->dim, 0u, nullptr, idx->n_cu, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
+    const bool dot = is_dot(idx->cfg);
+    if (dot && dot_stage_queries(idx, d_q, nq, &d_qa, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
+    const float* d_qk = dot ? d_qa : d_q;                                // what the kernel reads: [nq][kdim]
     const uint32_t chunks = (n_ids + 63u) / 64u;
     const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)nq * chunks, 1u << 20);
     const size_t smem = smem_bytes(idx->L.stride, 0, false);
@@ -2695,11 +2853,12 @@ idist_status idist_distance_batch(const idist_index* idx, const float* queries, 
 #define LAUNCH_DIST(NB_, RS_, TAIL_)                                                              \
     {                                                                                             \
         auto kD = distance_batch_kernel<NB_, RS_, TAIL_>;                                         \
-        IDIST_LAUNCH(kD, grid, 64, smem, (hipStream_t) nullptr, view, d_q, nq, d_ids, n_ids, d_out); \
+        IDIST_LAUNCH(kD, grid, 64, smem, (hipStream_t) nullptr, view, d_qk, nq, d_ids, n_ids, d_out); \
     }
     IDIST_DISPATCH(idx->L, LAUNCH_DIST);
 #undef LAUNCH_DIST
     if (cosine && launch_scale_half(d_out, (size_t)nq * n_ids, idx->n_cu, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
+    if (dot && launch_dot_report(d_out, d_qa + (size_t)nq * idx->kdim, idx->dot_S, nq, n_ids, idx->n_cu, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
     if ((e = hipGetLastError()) != hipSuccess || (e = hipMemcpy(out_dist, d_out, ib, hipMemcpyDeviceToHost)) != hipSuccess) {
         release();
         return fail(IDIST_ERR_HIP, "distance_batch: %s", hipGetErrorString(e));
@@ -2716,13 +2875,14 @@ idist_status idist_filter_bound_batch(const idist_index* idx, const float* queri
     HIPCHK(hipSetDevice(idx->device));
     if (filter_applies(idx)) CHK(filter_ensure(idx));
     const size_t qb = (size_t)nq * idx->dim * 4, ib = (size_t)nq * n_ids * 4;
-    if (idx->filt_state.load(std::memory_order_acquire) != 1) {          // no filter for this index: no bound
-        memset(out_bound, 0, ib);
+    const bool have_filter = idx->filt_state.load(std::memory_order_acquire) == 1;
+    if (!have_filter && !is_dot(idx->cfg)) {                             // no filter for this index: no bound
+        memset(out_bound, 0, ib);                                        // (DOT: "no bound" is -t / 2, reported below)
         return IDIST_OK;
     }
-    float *d_q = nullptr, *d_out = nullptr;
+    float *d_q = nullptr, *d_out = nullptr, *d_qa = nullptr;
     uint32_t* d_ids = nullptr;
-    auto release = [&]() { hipFree(d_q); hipFree(d_out); hipFree(d_ids); };
+    auto release = [&]() { hipFree(d_q); hipFree(d_qa); hipFree(d_out); hipFree(d_ids); };
     hipError_t e;
     if ((e = hipMalloc((void**)&d_q, qb)) != hipSuccess || (e = hipMalloc((void**)&d_out, ib)) != hipSuccess ||
         (e = hipMalloc((void**)&d_ids, ib)) != hipSuccess ||
@@ -2733,6 +2893,11 @@ idist_status idist_filter_bound_batch(const idist_index* idx, const float* queri
     }
     const bool cosine = is_cosine(idx->cfg);                             // (half a lower bound is a lower bound of half)
     if (cosine && launch_normalize(d_q, d_q, nq, idx->dim, idx->dim, 0u, nullptr, idx->n_cu, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
+    // DOT: the report is non-decreasing, so the reported bound stays a lower bound of the reported distance; "no bound" (raw 0)
+    // becomes the trivial bound -t / 2
+    const bool dot = is_dot(idx->cfg);
+    if (dot && dot_stage_queries(idx, d_q, nq, &d_qa, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
+    const float* d_qk = dot ? d_qa : d_q;                                // what the kernel reads: [nq][kdim]
     const uint32_t chunks = (n_ids + 63u) / 64u;
     const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)nq * chunks, 1u << 20);
     const size_t smem = smem_bytes(idx->L.stride, 0, false);
@@ -2740,11 +2905,13 @@ idist_status idist_filter_bound_batch(const idist_index* idx, const float* queri
 #define LAUNCH_FB(NB_, RS_, TAIL_)                                                               \
     {                                                                                             \
         auto kD = filter_bound_kernel<NB_, RS_, TAIL_>;                                           \
-        IDIST_LAUNCH(kD, grid, 64, smem, (hipStream_t) nullptr, view, d_q, nq, d_ids, n_ids, d_out); \
+        IDIST_LAUNCH(kD, grid, 64, smem, (hipStream_t) nullptr, view, d_qk, nq, d_ids, n_ids, d_out); \
     }
-    IDIST_DISPATCH(idx->L, LAUNCH_FB);
+    if (have_filter) IDIST_DISPATCH(idx->L, LAUNCH_FB);
+    else (void)hipMemset(d_out, 0, ib);
 #undef LAUNCH_FB
     if (cosine && launch_scale_half(d_out, (size_t)nq * n_ids, idx->n_cu, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
+    if (dot && launch_dot_report(d_out, d_qa + (size_t)nq * idx->kdim, idx->dot_S, nq, n_ids, idx->n_cu, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
     if ((e = hipGetLastError()) != hipSuccess || (e = hipMemcpy(out_bound, d_out, ib, hipMemcpyDeviceToHost)) != hipSuccess) {
         release();
         return fail(IDIST_ERR_HIP, "filter_bound_batch: %s", hipGetErrorString(e));
@@ -2753,8 +2920,8 @@ idist_status idist_filter_bound_batch(const idist_index* idx, const float* queri
     return IDIST_OK;
 }
 
-// raw (both brute-force paths): the squared-L2 distances of a cosine index are left as they are — the partitioned brute force
-// halves them after its merge (the queries are normalised either way)
+// raw (both brute-force paths): the squared-L2 distances of a cosine / DOT index are left as they are — the partitioned brute force
+// halves / reports them after its merge (the queries are normalised / augmented either way)
 static idist_status bruteforce_scan(const idist_index* idx, const float* queries, uint32_t nq, uint32_t k,
                                     uint32_t* out_pid, float* out_dist, bool raw) {
     if (!idx) return fail(IDIST_ERR_INVALID_ARG, "idx is null");
@@ -2762,10 +2929,10 @@ static idist_status bruteforce_scan(const idist_index* idx, const float* queries
     if (k == 0 || k > IDIST_MAX_EF) return fail(IDIST_ERR_INVALID_ARG, "k %u out of [1,%u]", k, IDIST_MAX_EF);
     if (!queries || !out_pid || !out_dist) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
     HIPCHK(hipSetDevice(idx->device));
-    float *d_q = nullptr, *d_dist = nullptr;
+    float *d_q = nullptr, *d_dist = nullptr, *d_qa = nullptr;
     uint32_t *d_pid = nullptr, *d_next = nullptr;
     const size_t qb = (size_t)nq * idx->dim * 4, ob = (size_t)nq * k * 4;
-    auto release = [&]() { hipFree(d_q); hipFree(d_dist); hipFree(d_pid); hipFree(d_next); };
+    auto release = [&]() { hipFree(d_q); hipFree(d_qa); hipFree(d_dist); hipFree(d_pid); hipFree(d_next); };
     hipError_t e;
     if ((e = hipMalloc((void**)&d_q, qb)) != hipSuccess || (e = hipMalloc((void**)&d_dist, ob)) != hipSuccess ||
         (e = hipMalloc((void**)&d_pid, ob)) != hipSuccess || (e = hipMalloc((void**)&d_next, 256)) != hipSuccess ||
@@ -2776,6 +2943,9 @@ static idist_status bruteforce_scan(const idist_index* idx, const float* queries
     }
     const bool cosine = is_cosine(idx->cfg);
     if (cosine && launch_normalize(d_q, d_q, nq, idx->dim, idx->dim, 0u, nullptr, idx->n_cu, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
+    const bool dot = is_dot(idx->cfg);
+    if (dot && dot_stage_queries(idx, d_q, nq, &d_qa, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
+    const float* d_qk = dot ? d_qa : d_q;                                // what the kernel reads: [nq][kdim]
     const uint32_t wcap = k + 64 + 8;
     const size_t smem = smem_bytes(idx->L.stride, wcap, false);
     const uint32_t grid = std::min<uint32_t>(nq, (uint32_t)idx->n_cu * 16);
@@ -2783,11 +2953,12 @@ static idist_status bruteforce_scan(const idist_index* idx, const float* queries
 #define LAUNCH_BF(NB_, RS_, TAIL_)                                                                          \
     {                                                                                                       \
         auto kF = bruteforce_kernel<NB_, RS_, TAIL_>;                                                       \
-        IDIST_LAUNCH(kF, grid, 64, smem, (hipStream_t) nullptr, view, d_q, nq, k, wcap, d_pid, d_dist, d_next); \
+        IDIST_LAUNCH(kF, grid, 64, smem, (hipStream_t) nullptr, view, d_qk, nq, k, wcap, d_pid, d_dist, d_next); \
     }
     IDIST_DISPATCH(idx->L, LAUNCH_BF);
 #undef LAUNCH_BF
     if (cosine && !raw && launch_scale_half(d_dist, (size_t)nq * k, idx->n_cu, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
+    if (dot && !raw && launch_dot_report(d_dist, d_qa + (size_t)nq * idx->kdim, idx->dot_S, nq, k, idx->n_cu, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
     if ((e = hipGetLastError()) != hipSuccess || (e = hipMemcpy(out_pid, d_pid, ob, hipMemcpyDeviceToHost)) != hipSuccess ||
         (e = hipMemcpy(out_dist, d_dist, ob, hipMemcpyDeviceToHost)) != hipSuccess) {
         release();
@@ -2803,7 +2974,7 @@ static idist_status bruteforce_scan(const idist_index* idx, const float* queries
 static idist_status bruteforce_mfma(const idist_index* idx, const float* queries, uint32_t nq, uint32_t k,
                                     uint32_t* out_pid, float* out_dist, int* fell_back, bool raw) {
     *fell_back = 0;
-    const bool cosine = is_cosine(idx->cfg);
+    const bool cosine = is_cosine(idx->cfg), dot = is_dot(idx->cfg);
     const uint32_t n = idx->n, stride = idx->L.stride;
     uint32_t S = 32768;
     if (const char* e = test_env("IDIST_BF_SAMPLE")) S = (uint32_t)atoi(e);
@@ -2812,8 +2983,10 @@ static idist_status bruteforce_mfma(const idist_index* idx, const float* queries
     const uint32_t QC = 8192;                                    // queries per pass (bounds the dense sample matrix)
     const uint32_t cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((uint64_t)8 * k * n / S + 256, 1024), 1u << 16);
     float *d_qnat = nullptr, *d_qb = nullptr, *d_qn = nullptr, *d_pn = nullptr, *d_dense = nullptr, *d_thr = nullptr, *d_dist = nullptr;
+    float *d_qraw = nullptr, *d_sq = nullptr;                    // DOT: the caller's queries as uploaded, their s(q); d_qnat then holds [qc][kdim]
     uint32_t *d_cand = nullptr, *d_cnt = nullptr, *d_pid = nullptr, *d_ovf = nullptr;
     auto release = [&]() {
+        hipFree(d_qraw); hipFree(d_sq);
         hipFree(d_qnat); hipFree(d_qb); hipFree(d_qn); hipFree(d_pn); hipFree(d_dense); hipFree(d_thr); hipFree(d_dist);
         hipFree(d_cand); hipFree(d_cnt); hipFree(d_pid); hipFree(d_ovf);
     };
@@ -2827,7 +3000,11 @@ static idist_status bruteforce_mfma(const idist_index* idx, const float* queries
     } while (0)
     const uint32_t qc_max = std::min(nq, QC);
     const uint32_t qc_pad = (qc_max + kTM - 1) / kTM * kTM;
-    MCHK(hipMalloc((void**)&d_qnat, (size_t)qc_max * idx->dim * 4));
+    MCHK(hipMalloc((void**)&d_qnat, (size_t)qc_max * idx->kdim * 4));
+    if (dot) {
+        MCHK(hipMalloc((void**)&d_qraw, (size_t)qc_max * idx->dim * 4));
+        MCHK(hipMalloc((void**)&d_sq, (size_t)qc_max * 4));
+    }
     MCHK(hipMalloc((void**)&d_qb, (size_t)qc_pad * stride * 4));
     MCHK(hipMalloc((void**)&d_qn, (size_t)qc_pad * 4));
     MCHK(hipMalloc((void**)&d_pn, (size_t)n * 4));
@@ -2850,13 +3027,14 @@ static idist_status bruteforce_mfma(const idist_index* idx, const float* queries
     for (uint32_t qb = 0; qb < nq; qb += QC) {
         const uint32_t qc = std::min(QC, nq - qb);
         const uint32_t qpad = (qc + kTM - 1) / kTM * kTM;
-        MCHK(hipMemcpy(d_qnat, queries + (size_t)qb * idx->dim, (size_t)qc * idx->dim * 4, hipMemcpyHostToDevice));
+        MCHK(hipMemcpy(dot ? d_qraw : d_qnat, queries + (size_t)qb * idx->dim, (size_t)qc * idx->dim * 4, hipMemcpyHostToDevice));
+        if (dot && launch_dot_norms(d_qraw, qc, idx->dim, d_sq, d_qnat, idx->n_cu, st) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
         if (cosine && launch_normalize(d_qnat, d_qnat, qc, idx->dim, idx->dim, 0u, nullptr, idx->n_cu, st) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
         MCHK(hipMemset(d_qb, 0, (size_t)qpad * stride * 4));
         {
             const size_t total = (size_t)qc * stride;
             const int grid = (int)std::min<size_t>((total + 255) / 256, 65536);
-            IDIST_LAUNCH(permute_rows_kernel, grid, 256, 0, st, d_qnat, d_qb, qc, idx->dim, stride, idx->L.nb);
+            IDIST_LAUNCH(permute_rows_kernel, grid, 256, 0, st, d_qnat, d_qb, qc, idx->kdim, stride, idx->L.nb);
         }
         IDIST_LAUNCH(row_norms_kernel, std::min<uint32_t>(qpad, 8192), 64, 0, st, d_qb, qpad, stride, d_qn);
         MfmaArgs a{};
@@ -2886,6 +3064,7 @@ static idist_status bruteforce_mfma(const idist_index* idx, const float* queries
 #undef LAUNCH_RR
         MCHK(hipGetLastError());
         if (cosine && !raw && launch_scale_half(d_dist, (size_t)qc * k, idx->n_cu, st) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
+        if (dot && !raw && launch_dot_report(d_dist, d_sq, idx->dot_S, qc, k, idx->n_cu, st) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
         MCHK(hipMemcpy(out_pid + (size_t)qb * k, d_pid, (size_t)qc * k * 4, hipMemcpyDeviceToHost));
         MCHK(hipMemcpy(out_dist + (size_t)qb * k, d_dist, (size_t)qc * k * 4, hipMemcpyDeviceToHost));
     }
@@ -2942,6 +3121,38 @@ idist_status idist_normalize_batch(const float* rows, uint32_t n, uint32_t dim, 
         release();
         return fail(IDIST_ERR_HIP, "normalize_batch: %s", hipGetErrorString(e));
     }
+    release();
+    return IDIST_OK;
+}
+
+idist_status idist_dot_augment_batch(const float* rows, uint32_t n, uint32_t dim, float bound_in, float* out_rows, float* out_norm2,
+                                     float* out_bound, int32_t device) {
+    if (dim == 0 || dim > 65535) return fail(IDIST_ERR_INVALID_ARG, "dim %u out of [1,65535]", dim);
+    if (!(bound_in >= 0.0f && bound_in < INFINITY)) return fail(IDIST_ERR_INVALID_ARG, "dot_bound %g is not a finite number >= 0", (double)bound_in);
+    if (n && !rows) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    CHK(check_device(device));
+    if (n == 0) { if (out_bound) *out_bound = bound_in; return IDIST_OK; }
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    const uint32_t kdim = dim + 1u;
+    float *d_x = nullptr, *d_s = nullptr, *d_a = nullptr;
+    const size_t xb = (size_t)n * dim * 4, ab = (size_t)n * kdim * 4;
+    auto release = [&]() { hipFree(d_x); hipFree(d_s); hipFree(d_a); };
+    hipError_t e;
+    if ((e = hipMalloc((void**)&d_x, xb)) != hipSuccess || (e = hipMalloc((void**)&d_s, (size_t)n * 4)) != hipSuccess ||
+        (out_rows && (e = hipMalloc((void**)&d_a, ab)) != hipSuccess) || (e = hipMemcpy(d_x, rows, xb, hipMemcpyHostToDevice)) != hipSuccess) {
+        release();
+        return fail(IDIST_ERR_HIP, "dot_augment_batch staging: %s", hipGetErrorString(e));
+    }
+    float S = bound_in;
+    const idist_status st = dot_augment_device(d_x, d_a, n, dim, kdim, 0u, &S, d_s, prop.multiProcessorCount);   // (natural x~ rows: stride kdim, no blocks)
+    if (st != IDIST_OK) { release(); return st; }
+    if ((out_rows && (e = hipMemcpy(out_rows, d_a, ab, hipMemcpyDeviceToHost)) != hipSuccess) ||
+        (out_norm2 && (e = hipMemcpy(out_norm2, d_s, (size_t)n * 4, hipMemcpyDeviceToHost)) != hipSuccess)) {
+        release();
+        return fail(IDIST_ERR_HIP, "dot_augment_batch: %s", hipGetErrorString(e));
+    }
+    if (out_bound) *out_bound = S;
     release();
     return IDIST_OK;
 }

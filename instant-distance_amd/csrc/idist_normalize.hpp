@@ -24,37 +24,46 @@
 
 namespace idist {
 
+// s(x) of one row for the eight lanes of a group (lane j = lane & 7 runs chain j): `src` holds `dim` coordinates in the layout (nb
+// full blocks, natural remainder; natural rows: nb = 0).  `on` false: the group has no row (the lanes still take part in the
+// fold's cross-lane moves).  The result is valid in all eight lanes.  Shared by the cosine and the inner-product passes
+// (idist_dot.hpp): ONE statement of the fold.
+__device__ __forceinline__ float row_norm2_group(const float* src, bool on, uint32_t dim, uint32_t nb, int lane) {
+    const int j = lane & 7;
+    const uint32_t dp = (dim + 3u) & ~3u, steps = dp / 8u, rs = steps - 4u * nb;   // chain steps beyond the blocks
+    const bool tail = (dp % 8u) == 4u;
+    const uint32_t rem0 = 32u * nb, tail0 = rem0 + 8u * rs + (uint32_t)(j & 3);
+    float acc = 0.0f;
+    if (on) {
+        for (uint32_t t = 0; t < nb; t++) {
+            const float4 v = *reinterpret_cast<const float4*>(src + 32u * t + 4u * (uint32_t)j);
+            acc = __builtin_fmaf(v.x, v.x, acc);
+            acc = __builtin_fmaf(v.y, v.y, acc);
+            acc = __builtin_fmaf(v.z, v.z, acc);
+            acc = __builtin_fmaf(v.w, v.w, acc);
+        }
+        for (uint32_t s = 0; s < rs; s++) {
+            const uint32_t e = rem0 + 8u * s + (uint32_t)j;      // (natural there: position == element)
+            const float x = e < dim ? src[e] : 0.0f;
+            acc = __builtin_fmaf(x, x, acc);
+        }
+    }
+    const float tq = on && tail && tail0 < dim ? src[tail0] : 0.0f;
+    const float s = fold_chains(acc, tail, tq, 0.0f);            // valid in lane j == 0 of the group
+    return __uint_as_float(bcast_u32(__float_as_uint(s), lane & ~7));
+}
+
 // rows: [n][ld] floats holding `dim` coordinates each in the layout (nb, natural remainder); vec != 0: ld % 4 == 0 and both
 // pointers 16-byte aligned.  out_norm2 (may be nullptr): s(x) per row.
 __global__ __launch_bounds__(64) void normalize_rows_kernel(const float* in, float* out, uint32_t n, uint32_t dim, uint32_t ld,
                                                             uint32_t nb, uint32_t vec, float* out_norm2) {
     const int lane = lane_id(), g = lane >> 3, j = lane & 7;
-    const uint32_t dp = (dim + 3u) & ~3u, steps = dp / 8u, rs = steps - 4u * nb;   // chain steps beyond the blocks
-    const bool tail = (dp % 8u) == 4u;
-    const uint32_t rem0 = 32u * nb, tail0 = rem0 + 8u * rs + (uint32_t)(j & 3);
     const uint32_t groups = (n + 7u) / 8u;
     for (uint32_t b = blockIdx.x; b < groups; b += gridDim.x) {
         const uint32_t row = 8u * b + (uint32_t)g;
         const bool on = row < n;
         const float* src = in + (size_t)(on ? row : 0u) * ld;
-        float acc = 0.0f;
-        if (on) {
-            for (uint32_t t = 0; t < nb; t++) {
-                const float4 v = *reinterpret_cast<const float4*>(src + 32u * t + 4u * (uint32_t)j);
-                acc = __builtin_fmaf(v.x, v.x, acc);
-                acc = __builtin_fmaf(v.y, v.y, acc);
-                acc = __builtin_fmaf(v.z, v.z, acc);
-                acc = __builtin_fmaf(v.w, v.w, acc);
-            }
-            for (uint32_t s = 0; s < rs; s++) {
-                const uint32_t e = rem0 + 8u * s + (uint32_t)j;      // (natural there: position == element)
-                const float x = e < dim ? src[e] : 0.0f;
-                acc = __builtin_fmaf(x, x, acc);
-            }
-        }
-        const float tq = on && tail && tail0 < dim ? src[tail0] : 0.0f;
-        const float s = fold_chains(acc, tail, tq, 0.0f);            // valid in lane j == 0 of the group
-        const float s0 = __uint_as_float(bcast_u32(__float_as_uint(s), lane & ~7));
+        const float s0 = row_norm2_group(src, on, dim, nb, lane);
         const float r = __builtin_sqrtf(s0);
         const bool scale = r > 0.0f && r < __builtin_inff();         // (NaN fails both)
         if (!on) continue;

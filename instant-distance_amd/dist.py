@@ -84,9 +84,12 @@ def replicate_index(hnsw: Hnsw | None, builder: Builder, src: int = 0, chunk_byt
         # does the source hold a host copy of the points (all n rows, f32)?  The host transport broadcasts it as it is.
         hp = hnsw.points
         meta[4] = 1 if (info.n == 0 or (tuple(hp.shape) == (info.n, info.dim) and hp.dtype == np.float32)) else 0
+        # METRIC_DOT: the bound S the source's rows were augmented with, as its bit pattern (0 for every other metric)
+        meta[5] = int(np.array([info.dot_bound], dtype=np.float32).view(np.uint32)[0])
         meta[8:8 + info.n_upper] = list(info.layer_len)[: info.n_upper]
     meta = _bcast_meta(meta, src)
     n, dim, n_upper, ef = int(meta[0]), int(meta[1]), int(meta[2]), int(meta[3])
+    dot_bound = float(np.array([int(meta[5])], dtype=np.uint32).view(np.float32)[0])
     layer_len = np.ascontiguousarray(meta[8:8 + n_upper].astype(np.uint32))
 
     def _all_ok(ok: bool) -> bool:
@@ -105,6 +108,7 @@ def replicate_index(hnsw: Hnsw | None, builder: Builder, src: int = 0, chunk_byt
             if rank != src:
                 cfg = builder._config()
                 cfg.ef_search = ef
+                cfg.dot_bound = dot_bound      # the broadcast rows already are augmented with the source's S
                 h = C.c_void_p()
                 L.check(L.idist_index_alloc(n, dim, C.byref(cfg), _capi.u32p(layer_len), n_upper, dev.index, C.byref(h)))
                 hnsw = Hnsw(h, np.zeros((n, 0), dtype=np.float32), ef)   # host copy of the points is not replicated
@@ -138,4 +142,5 @@ def replicate_index(hnsw: Hnsw | None, builder: Builder, src: int = 0, chunk_byt
             dist.broadcast(torch.from_numpy(arr.view(np.uint8).reshape(-1)), src=src)
     if rank == src:
         return hnsw
-    return Hnsw.from_parts(pts, zero, layers, builder.ef_search(ef))
+    # (METRIC_DOT: the caller's rows are augmented again, with the source's S — the same device rows bit for bit)
+    return Hnsw.from_parts(pts, zero, layers, builder.ef_search(ef).dot_bound(dot_bound))

@@ -10,12 +10,16 @@
 //
 // `trait Point { fn distance(&self, &Self) -> f32 }` is arbitrary user code in the reference and
 // cannot be shipped to a GPU.  Here a Point type exposes its coordinates as f32 and names one of
-// the two distances the reference itself ships, or the cosine distance the engine adds:
+// the two distances the reference itself ships, or the cosine distance / the inner product the engine adds:
 //     static constexpr int METRIC = IDIST_METRIC_L2SQ;   // FloatArray, py/lib.rs:378-421
 //     static constexpr int METRIC = IDIST_METRIC_L2;     // tests/all.rs:93-97, examples/colors.rs
 //     static constexpr int METRIC = IDIST_METRIC_COSINE; // 1 - cos: the L2SQ index over rows and queries the ENGINE normalises
 //                                                        // (include/idist.h); write_f32 hands over the point as it is, and the
 //                                                        // points this header keeps (Item::point, iter()) stay the caller's
+//     static constexpr int METRIC = IDIST_METRIC_DOT;    // inner product, nearest = largest q.x: the L2SQ index over rows the ENGINE
+//                                                        // gives one more coordinate (include/idist.h), reported as about -q.x;
+//                                                        // Builder::dot_bound(S) fixes the bound S (0 = from the rows); dim() stays
+//                                                        // the caller's, and so do the points this header keeps
 //     size_t dim() const;  void write_f32(float* out) const;
 // A Point without that interface is a compile-time error — there is no CPU fallback.
 // Errors: the reference API is infallible (it panics at core/lib.rs:256 and :148); every non-OK
@@ -135,6 +139,7 @@ public:
     Builder max_batch(uint32_t k) && { cfg_.max_batch = k; return std::move(*this); }
     Builder tie_policy(int32_t p) && { cfg_.tie_policy = p; return std::move(*this); }   // IDIST_TIES_STRICT / IDIST_TIES_DROP
     Builder tie_capacity(uint32_t n) && { cfg_.tie_capacity = n; return std::move(*this); }
+    Builder dot_bound(float S) && { cfg_.dot_bound = S; return std::move(*this); }       // IDIST_METRIC_DOT only; 0 = derive from the rows
     Builder device(int d) && { device_ = d; return std::move(*this); }
 
     template <class P, class V> HnswMap<P, V> build(std::vector<P> points, std::vector<V> values) && {         // :78-80

@@ -19,7 +19,7 @@ from typing import Sequence
 import numpy as np
 
 from . import _capi
-from ._capi import INVALID
+from ._capi import INVALID, METRIC_DOT
 from .api import BatchResult, Builder, Hnsw, Item, _as_points
 from .dist import shard_range
 
@@ -29,7 +29,8 @@ def _lib():
 
 
 class PartitionedHnsw:
-    """An ordered list of `Hnsw` parts with the same dim, metric and ef_search behind one search call."""
+    """An ordered list of `Hnsw` parts with the same dim, metric and ef_search (METRIC_DOT: and the same dot_bound) behind one
+    search call."""
 
     def __init__(self, handle, hnsws: Sequence[Hnsw]):
         self._h = handle
@@ -68,6 +69,12 @@ class PartitionedHnsw:
         pts = _as_points(points)
         n = pts.shape[0]
         P = int(parts)
+        if builder._metric == METRIC_DOT and builder._dot_bound == 0.0 and n:
+            # one query augmentation and one report serve all parts: every part is built with the bound of the WHOLE set
+            S = C.c_float(0.0)
+            L = _lib()
+            L.check(L.idist_dot_augment_batch(_capi.f32p(pts), n, max(pts.shape[1], 1), 0.0, None, None, C.byref(S), builder._device))
+            builder = copy.copy(builder).dot_bound(S.value)
         devs = [int(d) for d in devices] if devices else [builder._device]
         hnsws: list = [None] * P
         local: list = [None] * P

@@ -40,6 +40,7 @@ pub(crate) struct IdistConfig {
     max_batch: u32,    // 0 = concurrent inserts (the rayon schedule of lib.rs:316-318), 1 = the sequential loop
     tie_policy: i32,   // 0 = strict (the reference's results whatever the ties: the tie region grows, then spills to HBM), 1 = drop: see include/idist.h
     tie_capacity: u32, // 0 = 64
+    dot_bound: f32,    // Metric::Dot only: the bound S on the rows' squared norms, 0 = derive it from the rows
 }
 #[repr(C)] pub(crate) struct IdistIndex { _p: [u8; 0] }
 #[repr(C)] pub(crate) struct IdistSearchCtx { _p: [u8; 0] }
@@ -49,6 +50,7 @@ const IDIST_MAX_LAYERS: usize = 64;
 struct IdistIndexInfo {     // idist_index_info
     n: u32, dim: u32, row_stride: u32, n_upper: u32, ef_search: u32, metric: i32, device: i32,
     layer_len: [u32; IDIST_MAX_LAYERS], tie_capacity: u32,
+    dot_bound: f32,   // Metric::Dot: the S in use; 0 otherwise
 }
 
 extern "C" {
@@ -90,7 +92,8 @@ fn expect(status: i32) {
     }
 }
 
-/// Which distance a point type computes (`Point::METRIC`): one of the two the reference ships, or the engine's cosine distance.
+/// Which distance a point type computes (`Point::METRIC`): one of the two the reference ships, or the engine's cosine distance
+/// or inner product.
 #[derive(Clone, Copy, Debug, Eq, PartialEq)]
 pub enum Metric {
     /// `FloatArray::distance`, instant-distance-py/src/lib.rs:378-421 (squared L2, eight FMA chains)
@@ -100,6 +103,10 @@ pub enum Metric {
     /// cosine distance `1 - cos`: the `L2Sq` index over rows and queries the engine normalises itself (`IDIST_METRIC_COSINE`,
     /// include/idist.h); the crate's own `points` stay the caller's vectors
     Cosine = 2,
+    /// inner product, nearest = largest `q.x`: the `L2Sq` index over rows the engine gives one more coordinate,
+    /// `sqrt(S - |x|^2)` with `S` the largest squared norm (queries get a trailing 0), reported as `0.5 * (d - (|q|^2 + S))`,
+    /// approximately `-q.x` (`IDIST_METRIC_DOT`, include/idist.h; 3 is unassigned); the crate's own `points` stay the caller's vectors
+    Dot = 4,
 }
 
 /// Hardware queues: every `Search` owns a HIP stream, and the runtime multiplexes a process's streams onto
