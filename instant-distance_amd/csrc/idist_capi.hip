@@ -104,6 +104,39 @@ idist_status fail(idist_status st, const char* fmt, ...) {
         if (_s != IDIST_OK) return _s;   \
     } while (0)
 
+// Device scratch of a one-shot entry point: every buffer it handed out is freed when the function returns, whichever way it returns.
+struct Scratch {
+    std::vector<void*> owned;
+    Scratch() = default;
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch() { for (void* q : owned) hipFree(q); }
+    template <typename T> idist_status alloc(T** p, size_t count) {
+        owned.push_back(nullptr);
+        HIPCHK(hipMalloc(&owned.back(), count * sizeof(T)));
+        *p = (T*)owned.back();
+        return IDIST_OK;
+    }
+};
+
+// Grow-only staging: p holds at least `need` bytes afterwards, exactly `need` if it had to grow (hipFree waits for the device).
+// After a failed allocation p is null and cap 0, so the *_free functions and the next call stay safe.
+template <typename T> idist_status grow(T*& p, size_t& cap, size_t need) {
+    if (need <= cap) return IDIST_OK;
+    hipFree(p);
+    p = nullptr;
+    cap = 0;
+    HIPCHK(hipMalloc((void**)&p, need));
+    cap = need;
+    return IDIST_OK;
+}
+// `need` for the buffers that grow by doubling from `lo` bytes (0 stays 0)
+inline size_t doubled_from(size_t lo, size_t need) {
+    if (!need) return 0;
+    while (lo < need) lo <<= 1;
+    return lo;
+}
+
 struct Layout {
     uint32_t stride, nb, rs, tail;
 };
@@ -335,9 +368,9 @@ struct idist_search_ctx {
     float* d_dist = nullptr;
     uint32_t* d_cnt = nullptr;
     uint32_t* d_ctr = nullptr;
-    size_t cap_q = 0, cap_out = 0, cap_nq = 0;
-    float* d_qn = nullptr;         // cosine indexes: the launch's queries, normalised (launch_search); grown like the staging above
-    size_t cap_qn = 0;             // (DOT indexes: the launch's queries with the trailing 0, [nq][kdim])
+    size_t cap_q = 0, cap_pid = 0, cap_dist = 0, cap_cnt = 0, cap_ctr = 0;   // bytes, as every cap_* below
+    float* d_qn = nullptr;         // what MetricPasses::prepare writes for a launch (launch_search): the queries the kernel reads
+    size_t cap_qn = 0;             // (cosine: normalised; DOT: with the trailing 0, [nq][kdim])
     float* d_sq = nullptr;         // DOT indexes: s(q) per query of the launch, for the report pass
     size_t cap_sq = 0;
     bool tie_overflowed = false;
@@ -363,7 +396,7 @@ struct idist_partitioned {
         // parts away from the merge device write here first, then one peer copy per array
         uint32_t *r_pid = nullptr, *r_cnt = nullptr, *r_ctr = nullptr;
         float* r_dist = nullptr;
-        size_t r_cap_out = 0, r_cap_nq = 0;
+        size_t r_cap_pid = 0, r_cap_dist = 0, r_cap_cnt = 0, r_cap_ctr = 0;
     };
     struct Dev {
         int32_t device = 0;
@@ -381,7 +414,7 @@ struct idist_partitioned {
     // on the merge device: the parts' lists [P][nq][width] and the merged result [nq][out_width]
     uint32_t *s_pid = nullptr, *s_cnt = nullptr, *s_ctr = nullptr, *o_pid = nullptr, *o_cnt = nullptr, *o_ctr = nullptr;
     float *s_dist = nullptr, *o_dist = nullptr;
-    size_t cap_slab = 0, cap_nq = 0, cap_o = 0;   // elements: P*nq*width, nq, nq*out_width
+    size_t cap_s_pid = 0, cap_s_dist = 0, cap_s_cnt = 0, cap_s_ctr = 0, cap_o_pid = 0, cap_o_dist = 0, cap_o_cnt = 0, cap_o_ctr = 0;
     hipStream_t stream = nullptr;            // the merge and the copies of its result
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
@@ -535,6 +568,50 @@ idist_status launch_dot_report(float* d, const float* d_sq, float S, uint32_t nq
     HIPCHK(hipGetLastError());
     return IDIST_OK;
 }
+
+// The host side of the metrics that are reductions onto the squared-L2 index (cosine: idist_normalize.hpp, DOT: idist_dot.hpp):
+// ONE pass over a launch's queries in front of the kernels, ONE over the reported distances behind them — the kernels never learn
+// about the metric (kernel_metric, IndexView).  Every entry point goes through this pair; one that is handed prepared queries or
+// reports later itself (launch_search's `prepared`, the brute force's `raw`) skips the call.  L2SQ and L2 enqueue nothing.
+struct MetricPasses {
+    int32_t metric;
+    uint32_t dim, kdim;     // coordinates of a caller's query, of the row the kernels read
+    float S;                // DOT: the bound in use
+    int n_cu;
+    explicit MetricPasses(const idist_index* ix) : metric(ix->cfg.metric), dim(ix->dim), kdim(ix->kdim), S(ix->dot_S), n_cu(ix->n_cu) {}
+    explicit MetricPasses(const idist_partitioned* p)
+        : metric(p->metric), dim(p->dim), kdim(p->parts[0].idx->kdim), S(p->dot_S), n_cu(p->parts[0].idx->n_cu) {}
+    bool any() const { return metric == IDIST_METRIC_COSINE || metric == IDIST_METRIC_DOT; }
+    // scratch for nq queries, in floats: what prepare writes for the kernels, and s(q) for report
+    size_t qk_floats(uint32_t nq) const { return any() ? (size_t)nq * kdim : 0; }
+    size_t sq_floats(uint32_t nq) const { return metric == IDIST_METRIC_DOT ? nq : 0; }
+    bool in_place() const { return kdim == dim; }                              // prepare may write where it reads (staging copies only)
+    bool report_keeps_zero() const { return metric != IDIST_METRIC_DOT; }      // a raw 0 is reported as 0
+    // d_in [nq][dim] natural queries -> *d_qk: what the kernels read ([nq][kdim]: d_in itself, or d_qk_out).  DOT: s(q) to d_sq_out;
+    // either output may be null.  d_qk (may be null too) is only written on success.  Enqueued on `stream`.
+    idist_status prepare(const float* d_in, float* d_qk_out, float* d_sq_out, uint32_t nq, hipStream_t stream, const float** d_qk) const {
+        if (metric == IDIST_METRIC_COSINE) CHK(launch_normalize(d_in, d_qk_out, nq, dim, dim, 0u, nullptr, n_cu, stream));
+        if (metric == IDIST_METRIC_DOT) CHK(launch_dot_norms(d_in, nq, dim, d_sq_out, d_qk_out, n_cu, stream));
+        if (d_qk) *d_qk = any() ? d_qk_out : d_in;
+        return IDIST_OK;
+    }
+    // prepare for a staging copy d_q the library owns: in place where the rows keep their width, else into ONE more allocation of
+    // `mem` ([nq][kdim] rows followed by s(q)).  *d_sq: where report finds s(q).
+    idist_status prepare_own(float* d_q, Scratch& mem, uint32_t nq, hipStream_t stream, const float** d_qk, const float** d_sq) const {
+        float* out = d_q;
+        if (!in_place()) CHK(mem.alloc(&out, qk_floats(nq) + sq_floats(nq)));
+        float* sq = sq_floats(nq) ? out + qk_floats(nq) : nullptr;
+        *d_sq = sq;
+        return prepare(d_q, out, sq, nq, stream, d_qk);
+    }
+    // [nq][width] squared-L2 distances of the index -> what the metric reports; d_sq: what prepare wrote.  Enqueued on `stream`.
+    idist_status report(float* d_dist, const float* d_sq, uint32_t nq, uint32_t width, hipStream_t stream) const {
+        if (metric == IDIST_METRIC_COSINE) return launch_scale_half(d_dist, (size_t)nq * width, n_cu, stream);
+        if (metric == IDIST_METRIC_DOT) return launch_dot_report(d_dist, d_sq, S, nq, width, n_cu, stream);
+        return IDIST_OK;
+    }
+};
+
 constexpr uint32_t kDotMaxWaves = 1024;
 // The bound of step 2 of the definition for n rows whose s(x) sit in d_norm2: bound_in > 0 is checked against every finite s(x),
 // 0 derives the maximum.  Synchronises the device (null stream).  d_part: kDotMaxWaves + 1 u32 of device scratch.
@@ -564,24 +641,23 @@ idist_status dot_bound_of(const float* d_norm2, uint32_t n, float bound_in, uint
 // bound given (0 = derive) on entry, the bound in use on return.  d_norm2_out (may be nullptr): s(x) per row.  Synchronises.
 idist_status dot_augment_device(const float* d_nat, float* d_out, uint32_t n, uint32_t dim, uint32_t stride, uint32_t nb, float* S_io,
                                 float* d_norm2_out, int n_cu) {
-    float* d_s = nullptr;
+    Scratch mem;
+    float* d_s = d_norm2_out;
     uint32_t* d_part = nullptr;
-    auto release = [&](idist_status st) { if (!d_norm2_out) hipFree(d_s); hipFree(d_part); return st; };
-    if (d_norm2_out) d_s = d_norm2_out;
-    else HIPCHK(hipMalloc((void**)&d_s, std::max<size_t>((size_t)n * 4, 256)));
-    if (hipMalloc((void**)&d_part, (kDotMaxWaves + 1) * 4) != hipSuccess) return release(fail(IDIST_ERR_HIP, "hipMalloc failed"));
-    idist_status st = launch_dot_norms(d_nat, n, dim, d_s, nullptr, n_cu, nullptr);
-    if (st != IDIST_OK) return release(st);
+    if (!d_s) CHK(mem.alloc(&d_s, std::max<size_t>(n, 64)));
+    CHK(mem.alloc(&d_part, kDotMaxWaves + 1));
+    CHK(launch_dot_norms(d_nat, n, dim, d_s, nullptr, n_cu, nullptr));
     float S = 0.0f;
-    if ((st = dot_bound_of(d_s, n, *S_io, d_part, &S)) != IDIST_OK) return release(st);
+    CHK(dot_bound_of(d_s, n, *S_io, d_part, &S));
     if (d_out && n) {
         const size_t total = (size_t)n * stride;
         const int grid = (int)std::min<size_t>((total + 255) / 256, 65536);
         IDIST_LAUNCH(dot_augment_rows_kernel, grid, 256, 0, (hipStream_t) nullptr, d_nat, d_out, n, dim, stride, nb, d_s, S);
-        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return release(fail(IDIST_ERR_HIP, "dot_augment_rows_kernel failed"));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipDeviceSynchronize());
     }
     *S_io = S;
-    return release(IDIST_OK);
+    return IDIST_OK;
 }
 
 // natural row-major device points -> blocked rows of the index (cosine: normalised there, the caller's rows are only read; DOT:
@@ -606,14 +682,11 @@ idist_status load_points_device(idist_index* ix, const float* d_nat) {
 }
 idist_status load_points_host(idist_index* ix, const float* h_nat) {
     if (ix->n == 0) return IDIST_OK;
+    Scratch mem;
     float* d_nat = nullptr;
-    const size_t bytes = (size_t)ix->n * ix->dim * 4;
-    HIPCHK(hipMalloc((void**)&d_nat, bytes));
-    hipError_t e = hipMemcpy(d_nat, h_nat, bytes, hipMemcpyHostToDevice);
-    idist_status s = e == hipSuccess ? load_points_device(ix, d_nat)
-                                     : fail(IDIST_ERR_HIP, "hipMemcpy(points): %s", hipGetErrorString(e));
-    hipFree(d_nat);
-    return s;
+    CHK(mem.alloc(&d_nat, (size_t)ix->n * ix->dim));
+    HIPCHK(hipMemcpy(d_nat, h_nat, (size_t)ix->n * ix->dim * 4, hipMemcpyHostToDevice));
+    return load_points_device(ix, d_nat);
 }
 
 uint32_t default_slots(uint32_t n_points, int n_cu) {
@@ -1392,43 +1465,16 @@ idist_status launch_search(const idist_index* ix, idist_search_ctx* ctx, const f
                            bool prepared = false) {
     const uint32_t ef = ix->cfg.ef_search;
     CHK(variants_check(ctx->knobs.classic));
-    // Cosine: the walk reads a normalised copy of the queries that this context owns, and the distances it wrote are halved behind
-    // it — both on the launch's stream, outside the events that time the search kernel.  `prepared`: the caller normalised the
-    // queries itself and halves the distances later (the partitioned search: after its merge).
-    const bool cosine = is_cosine(ix->cfg) && !prepared;
-    if (cosine) {
-        const size_t qb = (size_t)nq * ix->dim * 4;
-        if (qb > ctx->cap_qn) {                                   // grows like the staging buffers; hipFree waits for the device
-            size_t cap = std::max<size_t>(ctx->cap_qn, 4096);
-            while (cap < qb) cap <<= 1;
-            hipFree(ctx->d_qn); ctx->d_qn = nullptr; ctx->cap_qn = 0;
-            HIPCHK(hipMalloc((void**)&ctx->d_qn, cap));
-            ctx->cap_qn = cap;
-        }
-        CHK(launch_normalize(d_q, ctx->d_qn, nq, ix->dim, ix->dim, 0u, nullptr, ix->n_cu, stream));
-        d_q = ctx->d_qn;
-    }
-    // DOT: the same shape — the walk reads the queries with their trailing 0 from the context's buffer, s(q) is kept for the report
-    // pass behind the walk.  `prepared`: d_q already holds [nq][kdim] rows and the caller reports after its merge.
-    const bool dot = is_dot(ix->cfg) && !prepared;
-    if (dot) {
-        const size_t qb = (size_t)nq * ix->kdim * 4, sb = (size_t)nq * 4;
-        if (qb > ctx->cap_qn) {
-            size_t cap = std::max<size_t>(ctx->cap_qn, 4096);
-            while (cap < qb) cap <<= 1;
-            hipFree(ctx->d_qn); ctx->d_qn = nullptr; ctx->cap_qn = 0;
-            HIPCHK(hipMalloc((void**)&ctx->d_qn, cap));
-            ctx->cap_qn = cap;
-        }
-        if (sb > ctx->cap_sq) {
-            size_t cap = std::max<size_t>(ctx->cap_sq, 256);
-            while (cap < sb) cap <<= 1;
-            hipFree(ctx->d_sq); ctx->d_sq = nullptr; ctx->cap_sq = 0;
-            HIPCHK(hipMalloc((void**)&ctx->d_sq, cap));
-            ctx->cap_sq = cap;
-        }
-        CHK(launch_dot_norms(d_q, nq, ix->dim, ctx->d_sq, ctx->d_qn, ix->n_cu, stream));
-        d_q = ctx->d_qn;
+    // Cosine and DOT: the walk reads the queries MetricPasses::prepare wrote into buffers this context owns (the caller's are only
+    // read), and the distances it wrote are reported behind it — both on the launch's stream, outside the events that time the
+    // search kernel.  `prepared`: d_q already holds what the kernels read and the caller reports later (the partitioned search:
+    // after its merge).
+    const MetricPasses metric(ix);
+    const bool passes = metric.any() && !prepared;
+    if (passes) {
+        CHK(grow(ctx->d_qn, ctx->cap_qn, doubled_from(4096, metric.qk_floats(nq) * 4)));
+        CHK(grow(ctx->d_sq, ctx->cap_sq, doubled_from(256, metric.sq_floats(nq) * 4)));
+        CHK(metric.prepare(d_q, ctx->d_qn, ctx->d_sq, nq, stream, &d_q));
     }
     SearchArgs a{};
     a.queries = d_q;
@@ -1655,8 +1701,7 @@ idist_status launch_search(const idist_index* ix, idist_search_ctx* ctx, const f
         ctx->n_launch++;
         ctx->recs[ctx->n_rec++ % IDIST_EVENT_RING] = {(int32_t)slot, 0.0f};
     }
-    if (cosine) CHK(launch_scale_half(d_dist, (size_t)nq * ef, ix->n_cu, stream));
-    if (dot) CHK(launch_dot_report(d_dist, ctx->d_sq, ix->dot_S, nq, ef, ix->n_cu, stream));
+    if (passes) CHK(metric.report(d_dist, ctx->d_sq, nq, ef, stream));
     return IDIST_OK;
 }
 
@@ -1976,7 +2021,7 @@ idist_status idist_search_ctx_reserve(idist_search_ctx* ctx, uint32_t slots) {
     return IDIST_OK;
 }
 
-// prepared: see launch_search (the partitioned search hands in normalised queries and halves the distances after its merge)
+// prepared: see launch_search (the partitioned search hands in what the kernels read and reports the distances after its merge)
 static idist_status search_batch_device_impl(const idist_index* idx, idist_search_ctx* ctx, const void* d_queries,
                                              uint32_t nq, void* d_out_pid, void* d_out_dist, void* d_out_count,
                                              void* d_out_counters, void* hip_stream, bool prepared) {
@@ -2038,6 +2083,16 @@ idist_status idist_search_ctx_tie_overflowed(idist_search_ctx* ctx, int32_t* out
     *out = ctx->tie_overflowed ? 1 : 0;
     ctx->tie_overflowed = false;
     return IDIST_OK;
+}
+
+// Reads the context's device-side status behind a launch (*st).  True: strict ties overflowed and the escalation made progress —
+// idist_search_ctx_status gave this context a larger tie region or the HBM bags — so the batch is simply searched again (queries
+// are independent and the results are overwritten).
+static bool status_asks_retry(const idist_index* idx, idist_search_ctx* ctx, idist_status* st) {
+    const uint32_t cap_before = std::max(tie_capacity(idx->cfg), ctx->tie_cap);
+    const bool spill_before = ctx->tie_spill;
+    *st = idist_search_ctx_status(ctx);
+    return *st == IDIST_ERR_TIE_OVERFLOW && (std::max(tie_capacity(idx->cfg), ctx->tie_cap) > cap_before || ctx->tie_spill != spill_before);
 }
 
 static idist_status resolve_time(idist_search_ctx* ctx, const idist_search_ctx::TimeRec& r, float* ms) {
@@ -2133,8 +2188,8 @@ static idist_status search_batch_impl(const idist_index* idx, idist_search_ctx* 
     // pinned, device-mapped buffer that the kernel reads and writes itself; the call is a host memcpy, one launch, one
     // stream sync, a host memcpy.  (The general path below costs six copy / memset calls of ~10 us each around the kernel.)
     const size_t io_need = qb + 2 * ob + (size_t)nq * 16 + idist_search_ctx::kIoHeadBytes;
-    // (not for cosine and DOT indexes: the completion word the kernel writes would run ahead of the pass behind the walk)
-    if (io_need <= idist_search_ctx::kIoMaxBytes && !ctx->knobs.no_zero_copy && !is_cosine(idx->cfg) && !is_dot(idx->cfg)) {
+    // (not for a metric with passes: the completion word the kernel writes would run ahead of the pass behind the walk)
+    if (io_need <= idist_search_ctx::kIoMaxBytes && !ctx->knobs.no_zero_copy && !MetricPasses(idx).any()) {
         if (io_need > ctx->io_cap) {
             size_t cap = idist_search_ctx::kIoMinBytes;
             while (cap < io_need) cap <<= 1;
@@ -2198,10 +2253,8 @@ static idist_status search_batch_impl(const idist_index* idx, idist_search_ctx* 
             uint32_t any = grid <= idist_search_ctx::kIoStatusSlots ? 0u : 1u;  // too many workgroups for the slots: ask the device
             for (uint32_t g = 0; g < grid && g < idist_search_ctx::kIoStatusSlots; g++) any |= h_status[g];
             if (any) {
-                const uint32_t cap_before = std::max(tie_capacity(idx->cfg), ctx->tie_cap);
-                const bool spill_before = ctx->tie_spill;
-                const idist_status s = idist_search_ctx_status(ctx);
-                if (s == IDIST_ERR_TIE_OVERFLOW && (std::max(tie_capacity(idx->cfg), ctx->tie_cap) > cap_before || ctx->tie_spill != spill_before)) continue;
+                idist_status s;
+                if (status_asks_retry(idx, ctx, &s)) continue;
                 if (s != IDIST_OK) return s;
             }
             memcpy(out_pid, h_pid, ob);
@@ -2211,19 +2264,11 @@ static idist_status search_batch_impl(const idist_index* idx, idist_search_ctx* 
             return IDIST_OK;
         }
     }
-    if (qb > ctx->cap_q) { hipFree(ctx->d_q); ctx->d_q = nullptr; ctx->cap_q = 0; HIPCHK(hipMalloc((void**)&ctx->d_q, qb)); ctx->cap_q = qb; }
-    if (ob > ctx->cap_out) {
-        hipFree(ctx->d_pid); hipFree(ctx->d_dist); ctx->d_pid = nullptr; ctx->d_dist = nullptr; ctx->cap_out = 0;
-        HIPCHK(hipMalloc((void**)&ctx->d_pid, ob));
-        HIPCHK(hipMalloc((void**)&ctx->d_dist, ob));
-        ctx->cap_out = ob;
-    }
-    if (nq > ctx->cap_nq) {
-        hipFree(ctx->d_cnt); hipFree(ctx->d_ctr); ctx->d_cnt = nullptr; ctx->d_ctr = nullptr; ctx->cap_nq = 0;
-        HIPCHK(hipMalloc((void**)&ctx->d_cnt, (size_t)nq * 4));
-        HIPCHK(hipMalloc((void**)&ctx->d_ctr, (size_t)nq * 12));
-        ctx->cap_nq = nq;
-    }
+    CHK(grow(ctx->d_q, ctx->cap_q, qb));
+    CHK(grow(ctx->d_pid, ctx->cap_pid, ob));
+    CHK(grow(ctx->d_dist, ctx->cap_dist, ob));
+    CHK(grow(ctx->d_cnt, ctx->cap_cnt, (size_t)nq * 4));
+    CHK(grow(ctx->d_ctr, ctx->cap_ctr, (size_t)nq * 12));
     HIPCHK(hipMemcpyAsync(ctx->d_q, queries, qb, hipMemcpyHostToDevice, ctx->stream));
     for (;;) {
         CHK(launch_search(idx, ctx, ctx->d_q, nq, ctx->d_pid, ctx->d_dist, ctx->d_cnt, out_counters ? ctx->d_ctr : nullptr,
@@ -2233,13 +2278,8 @@ static idist_status search_batch_impl(const idist_index* idx, idist_search_ctx* 
         HIPCHK(hipMemcpyAsync(out_count, ctx->d_cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, ctx->stream));
         if (out_counters) HIPCHK(hipMemcpyAsync(out_counters, ctx->d_ctr, (size_t)nq * 12, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        // strict ties: the tie region was too small -> idist_search_ctx_status enlarged it for this context; the
-        // batch is simply searched again (queries are independent and the results are overwritten)
-        const uint32_t cap_before = std::max(tie_capacity(idx->cfg), ctx->tie_cap);
-        const bool spill_before = ctx->tie_spill;
-        const idist_status s = idist_search_ctx_status(ctx);
-        if (s == IDIST_ERR_TIE_OVERFLOW && (std::max(tie_capacity(idx->cfg), ctx->tie_cap) > cap_before || ctx->tie_spill != spill_before)) continue;
-        return s;
+        idist_status s;
+        if (!status_asks_retry(idx, ctx, &s)) return s;
     }
 }
 
@@ -2603,45 +2643,36 @@ idist_status idist_partitioned_get_info(const idist_partitioned* p, idist_partit
 // staging on the merge device for P lists of `width` per query and a result of `out_width` (the merge device is current)
 static idist_status partitioned_reserve(idist_partitioned* p, uint32_t nq, uint32_t width, uint32_t out_width) {
     const size_t P = p->parts.size(), slab = P * nq * width, o = (size_t)nq * out_width;
-    if (slab > p->cap_slab) {
-        hipFree(p->s_pid); hipFree(p->s_dist); p->s_pid = nullptr; p->s_dist = nullptr; p->cap_slab = 0;
-        HIPCHK(hipMalloc((void**)&p->s_pid, slab * 4));
-        HIPCHK(hipMalloc((void**)&p->s_dist, slab * 4));
-        p->cap_slab = slab;
-    }
-    if (nq > p->cap_nq) {
-        hipFree(p->s_cnt); hipFree(p->s_ctr); hipFree(p->o_cnt); hipFree(p->o_ctr);
-        p->s_cnt = p->s_ctr = p->o_cnt = p->o_ctr = nullptr; p->cap_nq = 0;
-        HIPCHK(hipMalloc((void**)&p->s_cnt, P * nq * 4));
-        HIPCHK(hipMalloc((void**)&p->s_ctr, P * nq * 12));
-        HIPCHK(hipMalloc((void**)&p->o_cnt, (size_t)nq * 4));
-        HIPCHK(hipMalloc((void**)&p->o_ctr, (size_t)nq * 12));
-        p->cap_nq = nq;
-    }
-    if (o > p->cap_o) {
-        hipFree(p->o_pid); hipFree(p->o_dist); p->o_pid = nullptr; p->o_dist = nullptr; p->cap_o = 0;
-        HIPCHK(hipMalloc((void**)&p->o_pid, o * 4));
-        HIPCHK(hipMalloc((void**)&p->o_dist, o * 4));
-        p->cap_o = o;
-    }
+    CHK(grow(p->s_pid, p->cap_s_pid, slab * 4));
+    CHK(grow(p->s_dist, p->cap_s_dist, slab * 4));
+    CHK(grow(p->s_cnt, p->cap_s_cnt, P * nq * 4));
+    CHK(grow(p->s_ctr, p->cap_s_ctr, P * nq * 12));
+    CHK(grow(p->o_cnt, p->cap_o_cnt, (size_t)nq * 4));
+    CHK(grow(p->o_ctr, p->cap_o_ctr, (size_t)nq * 12));
+    CHK(grow(p->o_pid, p->cap_o_pid, o * 4));
+    CHK(grow(p->o_dist, p->cap_o_dist, o * 4));
     return IDIST_OK;
 }
 
 static idist_status bruteforce_impl(const idist_index* idx, const float* queries, uint32_t nq, uint32_t k, uint32_t* out_pid,
                                     float* out_dist, bool raw);
 
-// DOT: s(q) of the batch on the merge device (which is current), for the report behind the merge; enqueued on p->stream
-static idist_status partitioned_dot_norms(idist_partitioned* p, const float* queries, uint32_t nq) {
-    const size_t qb = (size_t)nq * p->dim * 4, sb = (size_t)nq * 4;
-    if (qb > p->cap_qm) { hipFree(p->d_qm); p->d_qm = nullptr; p->cap_qm = 0; HIPCHK(hipMalloc((void**)&p->d_qm, qb)); p->cap_qm = qb; }
-    if (sb > p->cap_sq) { hipFree(p->d_sq); p->d_sq = nullptr; p->cap_sq = 0; HIPCHK(hipMalloc((void**)&p->d_sq, sb)); p->cap_sq = sb; }
+// What the report behind the merge needs of the batch's queries — s(q), for a metric that has one — on the merge device (which is
+// current); enqueued on p->stream
+static idist_status partitioned_prepare_report(idist_partitioned* p, const float* queries, uint32_t nq) {
+    const MetricPasses metric(p);
+    if (!metric.sq_floats(nq)) return IDIST_OK;
+    const size_t qb = (size_t)nq * p->dim * 4;
+    CHK(grow(p->d_qm, p->cap_qm, qb));
+    CHK(grow(p->d_sq, p->cap_sq, metric.sq_floats(nq) * 4));
     HIPCHK(hipMemcpyAsync(p->d_qm, queries, qb, hipMemcpyHostToDevice, p->stream));
-    return launch_dot_norms(p->d_qm, nq, p->dim, p->d_sq, nullptr, p->parts[0].idx->n_cu, p->stream);
+    return metric.prepare(p->d_qm, nullptr, p->d_sq, nq, p->stream, nullptr);
 }
 
-// the merge kernel between two events + its result to the host; every part's list is complete in the staging memory.  Cosine
-// parts hand in squared-L2 distances of normalised vectors: they are halved HERE, after the merge — the merge relies on every
-// list being strictly ordered by (distance bits, id), which halving can break for denormal distances.
+// the merge kernel between two events + its result to the host; every part's list is complete in the staging memory.  The parts
+// hand in the index's raw squared-L2 distances: the metric's report runs HERE, after the merge (partitioned_prepare_report ran on
+// this stream before) — the merge relies on every list being strictly ordered by (distance bits, id) with non-negative keys, which
+// halving can break for denormal distances.
 static idist_status partitioned_merge(idist_partitioned* p, uint32_t nq, uint32_t width, uint32_t out_width, bool counters,
                                       uint32_t* out_pid, float* out_dist, uint32_t* out_count, uint32_t* out_counters) {
     MergeArgs a{};
@@ -2653,10 +2684,7 @@ static idist_status partitioned_merge(idist_partitioned* p, uint32_t nq, uint32_
     CHK(launch_merge(a, p->stream));
     HIPCHK(hipEventRecord(p->ev1, p->stream));
     p->timed = true;
-    if (p->metric == IDIST_METRIC_COSINE) CHK(launch_scale_half(p->o_dist, (size_t)nq * out_width, p->parts[0].idx->n_cu, p->stream));
-    // DOT likewise: the merge needs the raw keys (non-negative, strictly ordered); the report follows it (partitioned_dot_norms ran
-    // on this stream before)
-    if (p->metric == IDIST_METRIC_DOT) CHK(launch_dot_report(p->o_dist, p->d_sq, p->dot_S, nq, out_width, p->parts[0].idx->n_cu, p->stream));
+    CHK(MetricPasses(p).report(p->o_dist, p->d_sq, nq, out_width, p->stream));
     const size_t ob = (size_t)nq * out_width * 4;
     HIPCHK(hipMemcpyAsync(out_pid, p->o_pid, ob, hipMemcpyDeviceToHost, p->stream));
     HIPCHK(hipMemcpyAsync(out_dist, p->o_dist, ob, hipMemcpyDeviceToHost, p->stream));
@@ -2681,13 +2709,13 @@ idist_status idist_partitioned_search_batch(idist_partitioned* p, const float* q
     }
     if (!out_pid || !out_dist) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
     const bool counters = out_counters != nullptr;
-    const bool dot = p->metric == IDIST_METRIC_DOT;
-    const uint32_t kdim = p->dim + (dot ? 1u : 0u);
-    // (DOT: a device's buffer holds the [nq][kdim] rows the parts read, followed by the queries as uploaded)
-    const size_t qb = (size_t)nq * p->dim * 4, qa = dot ? (size_t)nq * kdim * 4 : 0, row = (size_t)nq * ef;
+    const MetricPasses metric(p);
+    // (a metric whose prepare cannot run in place: a device's buffer holds the [nq][kdim] rows the parts read, followed by the queries
+    // as uploaded)
+    const size_t qb = (size_t)nq * p->dim * 4, qa = metric.in_place() ? 0 : metric.qk_floats(nq) * 4, row = (size_t)nq * ef;
     HIPCHK(hipSetDevice(p->merge_device));
     CHK(partitioned_reserve(p, nq, ef, ef));
-    if (dot) CHK(partitioned_dot_norms(p, queries, nq));
+    CHK(partitioned_prepare_report(p, queries, nq));
     // 1. the queries, once per distinct device that has something to search
     for (size_t d = 0; d < p->devs.size(); d++) {
         idist_partitioned::Dev& dv = p->devs[d];
@@ -2695,14 +2723,10 @@ idist_status idist_partitioned_search_batch(idist_partitioned* p, const float* q
         for (auto& pt : p->parts) used |= pt.ctx && pt.dev_slot == (int)d;
         if (!used) continue;
         HIPCHK(hipSetDevice(dv.device));
-        if (qa + qb > dv.cap_q) { hipFree(dv.d_q); dv.d_q = nullptr; dv.cap_q = 0; HIPCHK(hipMalloc((void**)&dv.d_q, qa + qb)); dv.cap_q = qa + qb; }
+        CHK(grow(dv.d_q, dv.cap_q, qa + qb));
         HIPCHK(hipMemcpy(dv.d_q + qa / 4, queries, qb, hipMemcpyHostToDevice));
-        if (dot) {                                       // augmented once per device; the parts' launches take them as they are
-            CHK(launch_dot_norms(dv.d_q + qa / 4, nq, p->dim, nullptr, dv.d_q, p->parts[0].idx->n_cu, nullptr));
-            HIPCHK(hipStreamSynchronize(nullptr));
-        }
-        if (p->metric == IDIST_METRIC_COSINE) {          // normalised once per device; the parts' launches take them as they are
-            CHK(launch_normalize(dv.d_q, dv.d_q, nq, p->dim, p->dim, 0u, nullptr, p->parts[0].idx->n_cu, nullptr));
+        if (metric.any()) {                              // prepared once per device; the parts' launches take them as they are
+            CHK(metric.prepare(dv.d_q + qa / 4, dv.d_q, nullptr, nq, nullptr, nullptr));
             HIPCHK(hipStreamSynchronize(nullptr));
         }
     }
@@ -2716,18 +2740,10 @@ idist_status idist_partitioned_search_batch(idist_partitioned* p, const float* q
         HIPCHK(hipSetDevice(dev));
         if (dev == p->merge_device)
             return search_batch_device_impl(pt.idx, pt.ctx, p->devs[pt.dev_slot].d_q, nq, s_pid, s_dist, s_cnt, counters ? s_ctr : nullptr, pt.ctx->stream, true);
-        if (row > pt.r_cap_out) {
-            hipFree(pt.r_pid); hipFree(pt.r_dist); pt.r_pid = nullptr; pt.r_dist = nullptr; pt.r_cap_out = 0;
-            HIPCHK(hipMalloc((void**)&pt.r_pid, row * 4));
-            HIPCHK(hipMalloc((void**)&pt.r_dist, row * 4));
-            pt.r_cap_out = row;
-        }
-        if (nq > pt.r_cap_nq) {
-            hipFree(pt.r_cnt); hipFree(pt.r_ctr); pt.r_cnt = nullptr; pt.r_ctr = nullptr; pt.r_cap_nq = 0;
-            HIPCHK(hipMalloc((void**)&pt.r_cnt, (size_t)nq * 4));
-            HIPCHK(hipMalloc((void**)&pt.r_ctr, (size_t)nq * 12));
-            pt.r_cap_nq = nq;
-        }
+        CHK(grow(pt.r_pid, pt.r_cap_pid, row * 4));
+        CHK(grow(pt.r_dist, pt.r_cap_dist, row * 4));
+        CHK(grow(pt.r_cnt, pt.r_cap_cnt, (size_t)nq * 4));
+        CHK(grow(pt.r_ctr, pt.r_cap_ctr, (size_t)nq * 12));
         CHK(search_batch_device_impl(pt.idx, pt.ctx, p->devs[pt.dev_slot].d_q, nq, pt.r_pid, pt.r_dist, pt.r_cnt, counters ? pt.r_ctr : nullptr, pt.ctx->stream, true));
         HIPCHK(hipMemcpyPeerAsync(s_pid, p->merge_device, pt.r_pid, dev, row * 4, pt.ctx->stream));
         HIPCHK(hipMemcpyPeerAsync(s_dist, p->merge_device, pt.r_dist, dev, row * 4, pt.ctx->stream));
@@ -2750,14 +2766,12 @@ idist_status idist_partitioned_search_batch(idist_partitioned* p, const float* q
         for (;;) {
             HIPCHK(hipSetDevice(p->devs[pt.dev_slot].device));
             HIPCHK(hipStreamSynchronize(pt.ctx->stream));
-            const uint32_t cap_before = std::max(tie_capacity(pt.idx->cfg), pt.ctx->tie_cap);
-            const bool spill_before = pt.ctx->tie_spill;
-            const idist_status s = idist_search_ctx_status(pt.ctx);
-            if (s == IDIST_OK) break;
-            if (s == IDIST_ERR_TIE_OVERFLOW && (std::max(tie_capacity(pt.idx->cfg), pt.ctx->tie_cap) > cap_before || pt.ctx->tie_spill != spill_before)) {
+            idist_status s;
+            if (status_asks_retry(pt.idx, pt.ctx, &s)) {
                 CHK(enqueue(i));
                 continue;
             }
+            if (s == IDIST_OK) break;
             const std::string msg = g_err;
             return fail(s, "part %zu (device %d): %s", i, p->devs[pt.dev_slot].device, msg.c_str());
         }
@@ -2777,7 +2791,7 @@ idist_status idist_partitioned_bruteforce(idist_partitioned* p, const float* que
     const size_t P = p->parts.size(), row = (size_t)nq * k;
     HIPCHK(hipSetDevice(p->merge_device));
     CHK(partitioned_reserve(p, nq, k, k));
-    if (p->metric == IDIST_METRIC_DOT) CHK(partitioned_dot_norms(p, queries, nq));
+    CHK(partitioned_prepare_report(p, queries, nq));
     std::vector<uint32_t> h_pid(row), h_cnt(nq);
     std::vector<float> h_dist(row);
     for (size_t i = 0; i < P; i++) {
@@ -2816,112 +2830,69 @@ idist_status idist_partitioned_last_merge_ms(idist_partitioned* p, float* ms) {
     return IDIST_OK;
 }
 
-// DOT, the distance entry points: the staged natural queries d_q [nq][dim] -> *d_qa = [nq][kdim] rows with the trailing 0, followed
-// by s(q) [nq] (ONE allocation, the caller frees it).  Enqueued on `st`.
-static idist_status dot_stage_queries(const idist_index* idx, const float* d_q, uint32_t nq, float** d_qa, hipStream_t st) {
-    HIPCHK(hipMalloc((void**)d_qa, ((size_t)nq * idx->kdim + nq) * 4));
-    return launch_dot_norms(d_q, nq, idx->dim, *d_qa + (size_t)nq * idx->kdim, *d_qa, idx->n_cu, st);
+// idist_distance_batch (bound = false) and idist_filter_bound_batch (bound = true): one kernel over [nq][n_ids] (query, id) pairs
+// between the metric's passes.  A bound stays a bound under both reports: half a lower bound is a lower bound of half, and DOT's
+// report is non-decreasing — "no bound" (raw 0) becomes the trivial bound -t / 2 there.
+static idist_status pairs_batch(const idist_index* idx, const float* queries, uint32_t nq, const uint32_t* ids, uint32_t n_ids,
+                                float* out, bool bound) {
+    if (!idx) return fail(IDIST_ERR_INVALID_ARG, "idx is null");
+    if (nq == 0 || n_ids == 0) return IDIST_OK;
+    if (!queries || !ids || !out) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    HIPCHK(hipSetDevice(idx->device));
+    const MetricPasses metric(idx);
+    const size_t qb = (size_t)nq * idx->dim * 4, ib = (size_t)nq * n_ids * 4;
+    bool have_filter = false;
+    if (bound) {
+        if (filter_applies(idx)) CHK(filter_ensure(idx));
+        have_filter = idx->filt_state.load(std::memory_order_acquire) == 1;
+        if (!have_filter && metric.report_keeps_zero()) {                // no filter for this index: no bound
+            memset(out, 0, ib);
+            return IDIST_OK;
+        }
+    }
+    Scratch mem;
+    float *d_q = nullptr, *d_out = nullptr;
+    uint32_t* d_ids = nullptr;
+    CHK(mem.alloc(&d_q, qb / 4));
+    CHK(mem.alloc(&d_out, ib / 4));
+    CHK(mem.alloc(&d_ids, ib / 4));
+    HIPCHK(hipMemcpy(d_q, queries, qb, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_ids, ids, ib, hipMemcpyHostToDevice));
+    const float *d_qk = nullptr, *d_sq = nullptr;                        // what the kernel reads: [nq][kdim]
+    CHK(metric.prepare_own(d_q, mem, nq, nullptr, &d_qk, &d_sq));
+    const uint32_t chunks = (n_ids + 63u) / 64u;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)nq * chunks, 1u << 20);
+    const size_t smem = smem_bytes(idx->L.stride, 0, false);
+    IndexView view = idx->view();
+#define LAUNCH_PAIRS(NB_, RS_, TAIL_)                                                                 \
+    if (bound) {                                                                                      \
+        auto kD = filter_bound_kernel<NB_, RS_, TAIL_>;                                               \
+        IDIST_LAUNCH(kD, grid, 64, smem, (hipStream_t) nullptr, view, d_qk, nq, d_ids, n_ids, d_out); \
+    } else {                                                                                          \
+        auto kD = distance_batch_kernel<NB_, RS_, TAIL_>;                                             \
+        IDIST_LAUNCH(kD, grid, 64, smem, (hipStream_t) nullptr, view, d_qk, nq, d_ids, n_ids, d_out); \
+    }
+    if (have_filter || !bound) IDIST_DISPATCH(idx->L, LAUNCH_PAIRS);
+    else HIPCHK(hipMemset(d_out, 0, ib));
+#undef LAUNCH_PAIRS
+    HIPCHK(hipGetLastError());
+    CHK(metric.report(d_out, d_sq, nq, n_ids, nullptr));
+    HIPCHK(hipMemcpy(out, d_out, ib, hipMemcpyDeviceToHost));
+    return IDIST_OK;
 }
 
 idist_status idist_distance_batch(const idist_index* idx, const float* queries, uint32_t nq, const uint32_t* ids,
                                   uint32_t n_ids, float* out_dist) {
-    if (!idx) return fail(IDIST_ERR_INVALID_ARG, "idx is null");
-    if (nq == 0 || n_ids == 0) return IDIST_OK;
-    if (!queries || !ids || !out_dist) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
-    HIPCHK(hipSetDevice(idx->device));
-    float *d_q = nullptr, *d_out = nullptr, *d_qa = nullptr;
-    uint32_t* d_ids = nullptr;
-    const size_t qb = (size_t)nq * idx->dim * 4, ib = (size_t)nq * n_ids * 4;
-    auto release = [&]() { hipFree(d_q); hipFree(d_qa); hipFree(d_out); hipFree(d_ids); };
-    hipError_t e;
-    if ((e = hipMalloc((void**)&d_q, qb)) != hipSuccess || (e = hipMalloc((void**)&d_out, ib)) != hipSuccess ||
-        (e = hipMalloc((void**)&d_ids, ib)) != hipSuccess ||
-        (e = hipMemcpy(d_q, queries, qb, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(d_ids, ids, ib, hipMemcpyHostToDevice)) != hipSuccess) {
-        release();
-        return fail(IDIST_ERR_HIP, "distance_batch staging: %s", hipGetErrorString(e));
-    }
-    const bool cosine = is_cosine(idx->cfg);
-    if (cosine && launch_normalize(d_q, d_q, nq, idx->dim, idx->dim, 0u, nullptr, idx->n_cu, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
-    const bool dot = is_dot(idx->cfg);
-    if (dot && dot_stage_queries(idx, d_q, nq, &d_qa, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
-    const float* d_qk = dot ? d_qa : d_q;                                // what the kernel reads: [nq][kdim]
-    const uint32_t chunks = (n_ids + 63u) / 64u;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)nq * chunks, 1u << 20);
-    const size_t smem = smem_bytes(idx->L.stride, 0, false);
-    IndexView view = idx->view();
-#define LAUNCH_DIST(NB_, RS_, TAIL_)                                                              \
-    {                                                                                             \
-        auto kD = distance_batch_kernel<NB_, RS_, TAIL_>;                                         \
-        IDIST_LAUNCH(kD, grid, 64, smem, (hipStream_t) nullptr, view, d_qk, nq, d_ids, n_ids, d_out); \
-    }
-    IDIST_DISPATCH(idx->L, LAUNCH_DIST);
-#undef LAUNCH_DIST
-    if (cosine && launch_scale_half(d_out, (size_t)nq * n_ids, idx->n_cu, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
-    if (dot && launch_dot_report(d_out, d_qa + (size_t)nq * idx->kdim, idx->dot_S, nq, n_ids, idx->n_cu, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
-    if ((e = hipGetLastError()) != hipSuccess || (e = hipMemcpy(out_dist, d_out, ib, hipMemcpyDeviceToHost)) != hipSuccess) {
-        release();
-        return fail(IDIST_ERR_HIP, "distance_batch: %s", hipGetErrorString(e));
-    }
-    release();
-    return IDIST_OK;
+    return pairs_batch(idx, queries, nq, ids, n_ids, out_dist, false);
 }
 
 idist_status idist_filter_bound_batch(const idist_index* idx, const float* queries, uint32_t nq, const uint32_t* ids,
                                       uint32_t n_ids, float* out_bound) {
-    if (!idx) return fail(IDIST_ERR_INVALID_ARG, "idx is null");
-    if (nq == 0 || n_ids == 0) return IDIST_OK;
-    if (!queries || !ids || !out_bound) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
-    HIPCHK(hipSetDevice(idx->device));
-    if (filter_applies(idx)) CHK(filter_ensure(idx));
-    const size_t qb = (size_t)nq * idx->dim * 4, ib = (size_t)nq * n_ids * 4;
-    const bool have_filter = idx->filt_state.load(std::memory_order_acquire) == 1;
-    if (!have_filter && !is_dot(idx->cfg)) {                             // no filter for this index: no bound
-        memset(out_bound, 0, ib);                                        // (DOT: "no bound" is -t / 2, reported below)
-        return IDIST_OK;
-    }
-    float *d_q = nullptr, *d_out = nullptr, *d_qa = nullptr;
-    uint32_t* d_ids = nullptr;
-    auto release = [&]() { hipFree(d_q); hipFree(d_qa); hipFree(d_out); hipFree(d_ids); };
-    hipError_t e;
-    if ((e = hipMalloc((void**)&d_q, qb)) != hipSuccess || (e = hipMalloc((void**)&d_out, ib)) != hipSuccess ||
-        (e = hipMalloc((void**)&d_ids, ib)) != hipSuccess ||
-        (e = hipMemcpy(d_q, queries, qb, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(d_ids, ids, ib, hipMemcpyHostToDevice)) != hipSuccess) {
-        release();
-        return fail(IDIST_ERR_HIP, "filter_bound_batch staging: %s", hipGetErrorString(e));
-    }
-    const bool cosine = is_cosine(idx->cfg);                             // (half a lower bound is a lower bound of half)
-    if (cosine && launch_normalize(d_q, d_q, nq, idx->dim, idx->dim, 0u, nullptr, idx->n_cu, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
-    // DOT: the report is non-decreasing, so the reported bound stays a lower bound of the reported distance; "no bound" (raw 0)
-    // becomes the trivial bound -t / 2
-    const bool dot = is_dot(idx->cfg);
-    if (dot && dot_stage_queries(idx, d_q, nq, &d_qa, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
-    const float* d_qk = dot ? d_qa : d_q;                                // what the kernel reads: [nq][kdim]
-    const uint32_t chunks = (n_ids + 63u) / 64u;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)nq * chunks, 1u << 20);
-    const size_t smem = smem_bytes(idx->L.stride, 0, false);
-    IndexView view = idx->view();
-#define LAUNCH_FB(NB_, RS_, TAIL_)                                                               \
-    {                                                                                             \
-        auto kD = filter_bound_kernel<NB_, RS_, TAIL_>;                                           \
-        IDIST_LAUNCH(kD, grid, 64, smem, (hipStream_t) nullptr, view, d_qk, nq, d_ids, n_ids, d_out); \
-    }
-    if (have_filter) IDIST_DISPATCH(idx->L, LAUNCH_FB);
-    else (void)hipMemset(d_out, 0, ib);
-#undef LAUNCH_FB
-    if (cosine && launch_scale_half(d_out, (size_t)nq * n_ids, idx->n_cu, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
-    if (dot && launch_dot_report(d_out, d_qa + (size_t)nq * idx->kdim, idx->dot_S, nq, n_ids, idx->n_cu, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
-    if ((e = hipGetLastError()) != hipSuccess || (e = hipMemcpy(out_bound, d_out, ib, hipMemcpyDeviceToHost)) != hipSuccess) {
-        release();
-        return fail(IDIST_ERR_HIP, "filter_bound_batch: %s", hipGetErrorString(e));
-    }
-    release();
-    return IDIST_OK;
+    return pairs_batch(idx, queries, nq, ids, n_ids, out_bound, true);
 }
 
-// raw (both brute-force paths): the squared-L2 distances of a cosine / DOT index are left as they are — the partitioned brute force
-// halves / reports them after its merge (the queries are normalised / augmented either way)
+// raw (both brute-force paths): the queries are prepared, the squared-L2 distances of the index are left as they are — the
+// partitioned brute force reports them after its merge
 static idist_status bruteforce_scan(const idist_index* idx, const float* queries, uint32_t nq, uint32_t k,
                                     uint32_t* out_pid, float* out_dist, bool raw) {
     if (!idx) return fail(IDIST_ERR_INVALID_ARG, "idx is null");
@@ -2929,23 +2900,19 @@ static idist_status bruteforce_scan(const idist_index* idx, const float* queries
     if (k == 0 || k > IDIST_MAX_EF) return fail(IDIST_ERR_INVALID_ARG, "k %u out of [1,%u]", k, IDIST_MAX_EF);
     if (!queries || !out_pid || !out_dist) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
     HIPCHK(hipSetDevice(idx->device));
-    float *d_q = nullptr, *d_dist = nullptr, *d_qa = nullptr;
-    uint32_t *d_pid = nullptr, *d_next = nullptr;
+    const MetricPasses metric(idx);
     const size_t qb = (size_t)nq * idx->dim * 4, ob = (size_t)nq * k * 4;
-    auto release = [&]() { hipFree(d_q); hipFree(d_qa); hipFree(d_dist); hipFree(d_pid); hipFree(d_next); };
-    hipError_t e;
-    if ((e = hipMalloc((void**)&d_q, qb)) != hipSuccess || (e = hipMalloc((void**)&d_dist, ob)) != hipSuccess ||
-        (e = hipMalloc((void**)&d_pid, ob)) != hipSuccess || (e = hipMalloc((void**)&d_next, 256)) != hipSuccess ||
-        (e = hipMemset(d_next, 0, 256)) != hipSuccess ||
-        (e = hipMemcpy(d_q, queries, qb, hipMemcpyHostToDevice)) != hipSuccess) {
-        release();
-        return fail(IDIST_ERR_HIP, "bruteforce staging: %s", hipGetErrorString(e));
-    }
-    const bool cosine = is_cosine(idx->cfg);
-    if (cosine && launch_normalize(d_q, d_q, nq, idx->dim, idx->dim, 0u, nullptr, idx->n_cu, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
-    const bool dot = is_dot(idx->cfg);
-    if (dot && dot_stage_queries(idx, d_q, nq, &d_qa, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
-    const float* d_qk = dot ? d_qa : d_q;                                // what the kernel reads: [nq][kdim]
+    Scratch mem;
+    float *d_q = nullptr, *d_dist = nullptr;
+    uint32_t *d_pid = nullptr, *d_next = nullptr;
+    CHK(mem.alloc(&d_q, qb / 4));
+    CHK(mem.alloc(&d_dist, ob / 4));
+    CHK(mem.alloc(&d_pid, ob / 4));
+    CHK(mem.alloc(&d_next, 64));
+    HIPCHK(hipMemset(d_next, 0, 256));
+    HIPCHK(hipMemcpy(d_q, queries, qb, hipMemcpyHostToDevice));
+    const float *d_qk = nullptr, *d_sq = nullptr;                        // what the kernel reads: [nq][kdim]
+    CHK(metric.prepare_own(d_q, mem, nq, nullptr, &d_qk, &d_sq));
     const uint32_t wcap = k + 64 + 8;
     const size_t smem = smem_bytes(idx->L.stride, wcap, false);
     const uint32_t grid = std::min<uint32_t>(nq, (uint32_t)idx->n_cu * 16);
@@ -2957,14 +2924,10 @@ static idist_status bruteforce_scan(const idist_index* idx, const float* queries
     }
     IDIST_DISPATCH(idx->L, LAUNCH_BF);
 #undef LAUNCH_BF
-    if (cosine && !raw && launch_scale_half(d_dist, (size_t)nq * k, idx->n_cu, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
-    if (dot && !raw && launch_dot_report(d_dist, d_qa + (size_t)nq * idx->kdim, idx->dot_S, nq, k, idx->n_cu, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
-    if ((e = hipGetLastError()) != hipSuccess || (e = hipMemcpy(out_pid, d_pid, ob, hipMemcpyDeviceToHost)) != hipSuccess ||
-        (e = hipMemcpy(out_dist, d_dist, ob, hipMemcpyDeviceToHost)) != hipSuccess) {
-        release();
-        return fail(IDIST_ERR_HIP, "bruteforce: %s", hipGetErrorString(e));
-    }
-    release();
+    HIPCHK(hipGetLastError());
+    if (!raw) CHK(metric.report(d_dist, d_sq, nq, k, nullptr));
+    HIPCHK(hipMemcpy(out_pid, d_pid, ob, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_dist, d_dist, ob, hipMemcpyDeviceToHost));
     return IDIST_OK;
 }
 
@@ -2974,7 +2937,7 @@ static idist_status bruteforce_scan(const idist_index* idx, const float* queries
 static idist_status bruteforce_mfma(const idist_index* idx, const float* queries, uint32_t nq, uint32_t k,
                                     uint32_t* out_pid, float* out_dist, int* fell_back, bool raw) {
     *fell_back = 0;
-    const bool cosine = is_cosine(idx->cfg), dot = is_dot(idx->cfg);
+    const MetricPasses metric(idx);
     const uint32_t n = idx->n, stride = idx->L.stride;
     uint32_t S = 32768;
     if (const char* e = test_env("IDIST_BF_SAMPLE")) S = (uint32_t)atoi(e);
@@ -2982,55 +2945,43 @@ static idist_status bruteforce_mfma(const idist_index* idx, const float* queries
     const uint32_t S_pad = (S + kTN - 1) / kTN * kTN;
     const uint32_t QC = 8192;                                    // queries per pass (bounds the dense sample matrix)
     const uint32_t cap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((uint64_t)8 * k * n / S + 256, 1024), 1u << 16);
+    Scratch mem;
     float *d_qnat = nullptr, *d_qb = nullptr, *d_qn = nullptr, *d_pn = nullptr, *d_dense = nullptr, *d_thr = nullptr, *d_dist = nullptr;
-    float *d_qraw = nullptr, *d_sq = nullptr;                    // DOT: the caller's queries as uploaded, their s(q); d_qnat then holds [qc][kdim]
+    float *d_qup = nullptr, *d_sq = nullptr;                     // where a pass's queries are uploaded, their s(q); d_qnat: [qc][kdim], what the kernels read
     uint32_t *d_cand = nullptr, *d_cnt = nullptr, *d_pid = nullptr, *d_ovf = nullptr;
-    auto release = [&]() {
-        hipFree(d_qraw); hipFree(d_sq);
-        hipFree(d_qnat); hipFree(d_qb); hipFree(d_qn); hipFree(d_pn); hipFree(d_dense); hipFree(d_thr); hipFree(d_dist);
-        hipFree(d_cand); hipFree(d_cnt); hipFree(d_pid); hipFree(d_ovf);
-    };
-#define MCHK(expr)                                                                                  \
-    do {                                                                                            \
-        hipError_t _e = (expr);                                                                     \
-        if (_e != hipSuccess) {                                                                     \
-            release();                                                                              \
-            return fail(IDIST_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-        }                                                                                           \
-    } while (0)
     const uint32_t qc_max = std::min(nq, QC);
     const uint32_t qc_pad = (qc_max + kTM - 1) / kTM * kTM;
-    MCHK(hipMalloc((void**)&d_qnat, (size_t)qc_max * idx->kdim * 4));
-    if (dot) {
-        MCHK(hipMalloc((void**)&d_qraw, (size_t)qc_max * idx->dim * 4));
-        MCHK(hipMalloc((void**)&d_sq, (size_t)qc_max * 4));
+    CHK(mem.alloc(&d_qnat, (size_t)qc_max * idx->kdim));
+    d_qup = d_qnat;
+    if (!metric.in_place()) {                                    // (prepare widens the rows: the upload needs a buffer of its own)
+        CHK(mem.alloc(&d_qup, (size_t)qc_max * idx->dim));
+        CHK(mem.alloc(&d_sq, metric.sq_floats(qc_max)));
     }
-    MCHK(hipMalloc((void**)&d_qb, (size_t)qc_pad * stride * 4));
-    MCHK(hipMalloc((void**)&d_qn, (size_t)qc_pad * 4));
-    MCHK(hipMalloc((void**)&d_pn, (size_t)n * 4));
-    MCHK(hipMalloc((void**)&d_dense, (size_t)qc_pad * S_pad * 4));
-    MCHK(hipMalloc((void**)&d_thr, (size_t)qc_pad * 4));
-    MCHK(hipMalloc((void**)&d_cand, (size_t)qc_max * cap * 4));
-    MCHK(hipMalloc((void**)&d_cnt, (size_t)qc_pad * 4));
-    MCHK(hipMalloc((void**)&d_pid, (size_t)qc_max * k * 4));
-    MCHK(hipMalloc((void**)&d_dist, (size_t)qc_max * k * 4));
-    MCHK(hipMalloc((void**)&d_ovf, 256));
-    MCHK(hipMemset(d_ovf, 0, 256));
+    CHK(mem.alloc(&d_qb, (size_t)qc_pad * stride));
+    CHK(mem.alloc(&d_qn, qc_pad));
+    CHK(mem.alloc(&d_pn, n));
+    CHK(mem.alloc(&d_dense, (size_t)qc_pad * S_pad));
+    CHK(mem.alloc(&d_thr, qc_pad));
+    CHK(mem.alloc(&d_cand, (size_t)qc_max * cap));
+    CHK(mem.alloc(&d_cnt, qc_pad));
+    CHK(mem.alloc(&d_pid, (size_t)qc_max * k));
+    CHK(mem.alloc(&d_dist, (size_t)qc_max * k));
+    CHK(mem.alloc(&d_ovf, 64));
+    HIPCHK(hipMemset(d_ovf, 0, 256));
     hipStream_t st = nullptr;
     const uint32_t ngrid = std::min<uint32_t>(n, (uint32_t)idx->n_cu * 32);
     IDIST_LAUNCH(row_norms_kernel, ngrid, 64, 0, st, idx->d_points, n, stride, d_pn);
     std::vector<float> pn_h(n);
-    MCHK(hipMemcpy(pn_h.data(), d_pn, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(pn_h.data(), d_pn, (size_t)n * 4, hipMemcpyDeviceToHost));
     const float pn_max = *std::max_element(pn_h.begin(), pn_h.end());
     IndexView view = idx->view();
     const size_t smem_g = (size_t)2 * kTM * kLDP * 4;
     for (uint32_t qb = 0; qb < nq; qb += QC) {
         const uint32_t qc = std::min(QC, nq - qb);
         const uint32_t qpad = (qc + kTM - 1) / kTM * kTM;
-        MCHK(hipMemcpy(dot ? d_qraw : d_qnat, queries + (size_t)qb * idx->dim, (size_t)qc * idx->dim * 4, hipMemcpyHostToDevice));
-        if (dot && launch_dot_norms(d_qraw, qc, idx->dim, d_sq, d_qnat, idx->n_cu, st) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
-        if (cosine && launch_normalize(d_qnat, d_qnat, qc, idx->dim, idx->dim, 0u, nullptr, idx->n_cu, st) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
-        MCHK(hipMemset(d_qb, 0, (size_t)qpad * stride * 4));
+        HIPCHK(hipMemcpy(d_qup, queries + (size_t)qb * idx->dim, (size_t)qc * idx->dim * 4, hipMemcpyHostToDevice));
+        CHK(metric.prepare(d_qup, d_qnat, d_sq, qc, st, nullptr));
+        HIPCHK(hipMemset(d_qb, 0, (size_t)qpad * stride * 4));
         {
             const size_t total = (size_t)qc * stride;
             const int grid = (int)std::min<size_t>((total + 255) / 256, 65536);
@@ -3048,7 +2999,7 @@ static idist_status bruteforce_mfma(const idist_index* idx, const float* queries
         IDIST_LAUNCH(kth_threshold_kernel, std::min<uint32_t>(qc, 8192), 64, (size_t)(k + 72) * 8, st, d_dense, S_pad, S, qc, k,
                      k + 72, d_qn, pn_max, d_thr);
         // pass 2: all points, keep those under the threshold
-        MCHK(hipMemsetAsync(d_cnt, 0, (size_t)qpad * 4, st));
+        HIPCHK(hipMemsetAsync(d_cnt, 0, (size_t)qpad * 4, st));
         a.mode = 1; a.p_begin = 0; a.p_end = n;
         IDIST_LAUNCH(mfma_dist_kernel, nqt * ((n + kTN - 1) / kTN), 256, smem_g, st, a);
         // pass 3: canonical re-rank of the candidates
@@ -3062,16 +3013,13 @@ static idist_status bruteforce_mfma(const idist_index* idx, const float* queries
     }
         IDIST_DISPATCH(idx->L, LAUNCH_RR);
 #undef LAUNCH_RR
-        MCHK(hipGetLastError());
-        if (cosine && !raw && launch_scale_half(d_dist, (size_t)qc * k, idx->n_cu, st) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
-        if (dot && !raw && launch_dot_report(d_dist, d_sq, idx->dot_S, qc, k, idx->n_cu, st) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
-        MCHK(hipMemcpy(out_pid + (size_t)qb * k, d_pid, (size_t)qc * k * 4, hipMemcpyDeviceToHost));
-        MCHK(hipMemcpy(out_dist + (size_t)qb * k, d_dist, (size_t)qc * k * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipGetLastError());
+        if (!raw) CHK(metric.report(d_dist, d_sq, qc, k, st));
+        HIPCHK(hipMemcpy(out_pid + (size_t)qb * k, d_pid, (size_t)qc * k * 4, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(out_dist + (size_t)qb * k, d_dist, (size_t)qc * k * 4, hipMemcpyDeviceToHost));
     }
     uint32_t ovf = 0;
-    MCHK(hipMemcpy(&ovf, d_ovf, 4, hipMemcpyDeviceToHost));
-#undef MCHK
-    release();
+    HIPCHK(hipMemcpy(&ovf, d_ovf, 4, hipMemcpyDeviceToHost));
     if (ovf) { *fell_back = 1; return fail(IDIST_ERR_INTERNAL, "MFMA filter: %u candidate lists overflowed", ovf); }
     return IDIST_OK;
 }
@@ -3106,22 +3054,15 @@ idist_status idist_normalize_batch(const float* rows, uint32_t n, uint32_t dim, 
     CHK(check_device(device));
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
+    Scratch mem;
     float *d_x = nullptr, *d_s = nullptr;
     const size_t xb = (size_t)n * dim * 4;
-    auto release = [&]() { hipFree(d_x); hipFree(d_s); };
-    hipError_t e;
-    if ((e = hipMalloc((void**)&d_x, xb)) != hipSuccess || (out_norm2 && (e = hipMalloc((void**)&d_s, (size_t)n * 4)) != hipSuccess) ||
-        (e = hipMemcpy(d_x, rows, xb, hipMemcpyHostToDevice)) != hipSuccess) {
-        release();
-        return fail(IDIST_ERR_HIP, "normalize_batch staging: %s", hipGetErrorString(e));
-    }
-    if (launch_normalize(d_x, d_x, n, dim, dim, 0u, d_s, prop.multiProcessorCount, nullptr) != IDIST_OK) { release(); return IDIST_ERR_HIP; }
-    if ((e = hipMemcpy(out_rows, d_x, xb, hipMemcpyDeviceToHost)) != hipSuccess ||
-        (out_norm2 && (e = hipMemcpy(out_norm2, d_s, (size_t)n * 4, hipMemcpyDeviceToHost)) != hipSuccess)) {
-        release();
-        return fail(IDIST_ERR_HIP, "normalize_batch: %s", hipGetErrorString(e));
-    }
-    release();
+    CHK(mem.alloc(&d_x, xb / 4));
+    if (out_norm2) CHK(mem.alloc(&d_s, n));
+    HIPCHK(hipMemcpy(d_x, rows, xb, hipMemcpyHostToDevice));
+    CHK(launch_normalize(d_x, d_x, n, dim, dim, 0u, d_s, prop.multiProcessorCount, nullptr));
+    HIPCHK(hipMemcpy(out_rows, d_x, xb, hipMemcpyDeviceToHost));
+    if (out_norm2) HIPCHK(hipMemcpy(out_norm2, d_s, (size_t)n * 4, hipMemcpyDeviceToHost));
     return IDIST_OK;
 }
 
@@ -3135,25 +3076,18 @@ idist_status idist_dot_augment_batch(const float* rows, uint32_t n, uint32_t dim
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
     const uint32_t kdim = dim + 1u;
+    Scratch mem;
     float *d_x = nullptr, *d_s = nullptr, *d_a = nullptr;
     const size_t xb = (size_t)n * dim * 4, ab = (size_t)n * kdim * 4;
-    auto release = [&]() { hipFree(d_x); hipFree(d_s); hipFree(d_a); };
-    hipError_t e;
-    if ((e = hipMalloc((void**)&d_x, xb)) != hipSuccess || (e = hipMalloc((void**)&d_s, (size_t)n * 4)) != hipSuccess ||
-        (out_rows && (e = hipMalloc((void**)&d_a, ab)) != hipSuccess) || (e = hipMemcpy(d_x, rows, xb, hipMemcpyHostToDevice)) != hipSuccess) {
-        release();
-        return fail(IDIST_ERR_HIP, "dot_augment_batch staging: %s", hipGetErrorString(e));
-    }
+    CHK(mem.alloc(&d_x, xb / 4));
+    CHK(mem.alloc(&d_s, n));
+    if (out_rows) CHK(mem.alloc(&d_a, ab / 4));
+    HIPCHK(hipMemcpy(d_x, rows, xb, hipMemcpyHostToDevice));
     float S = bound_in;
-    const idist_status st = dot_augment_device(d_x, d_a, n, dim, kdim, 0u, &S, d_s, prop.multiProcessorCount);   // (natural x~ rows: stride kdim, no blocks)
-    if (st != IDIST_OK) { release(); return st; }
-    if ((out_rows && (e = hipMemcpy(out_rows, d_a, ab, hipMemcpyDeviceToHost)) != hipSuccess) ||
-        (out_norm2 && (e = hipMemcpy(out_norm2, d_s, (size_t)n * 4, hipMemcpyDeviceToHost)) != hipSuccess)) {
-        release();
-        return fail(IDIST_ERR_HIP, "dot_augment_batch: %s", hipGetErrorString(e));
-    }
+    CHK(dot_augment_device(d_x, d_a, n, dim, kdim, 0u, &S, d_s, prop.multiProcessorCount));   // (natural x~ rows: stride kdim, no blocks)
+    if (out_rows) HIPCHK(hipMemcpy(out_rows, d_a, ab, hipMemcpyDeviceToHost));
+    if (out_norm2) HIPCHK(hipMemcpy(out_norm2, d_s, (size_t)n * 4, hipMemcpyDeviceToHost));
     if (out_bound) *out_bound = S;
-    release();
     return IDIST_OK;
 }
 

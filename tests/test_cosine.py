@@ -319,6 +319,35 @@ def test_bruteforce_mfma_gpu(engine_loader, oracle):
     check_bruteforce(ida, oracle, 20000, 64, 300, 10, 2)
 
 
+def mfma_bruteforce_knobs(monkeypatch):
+    """every brute force takes the MFMA filter + canonical re-rank, whatever its size; a sample of 64 rows sets the thresholds"""
+    pc.use_test_build(monkeypatch)                     # (both knobs exist in the test build only)
+    monkeypatch.setenv("IDIST_BRUTEFORCE", "mfma")
+    monkeypatch.setenv("IDIST_BF_SAMPLE", "64")
+
+
+def test_bruteforce_mfma_path(eng, oracle, monkeypatch):
+    """The MFMA path at a size the emulator runs too: n = 300 and nq = 130 are no multiples of its tiles, and with n below the
+    smallest candidate capacity (1024) no list can overflow, so the call cannot fall back to the scan."""
+    ida, kind = eng
+    mfma_bruteforce_knobs(monkeypatch)
+    check_bruteforce(ida, oracle, 300, 20, 130, 10, 3)
+
+
+def test_partitioned_bruteforce_mfma_path(eng, oracle, monkeypatch):
+    """the parts' MFMA brute force leaves the distances raw: they are halved once, after the merge"""
+    ida, kind = eng
+    mfma_bruteforce_knobs(monkeypatch)
+    rng = np.random.default_rng(6)
+    x, q = scaled_rows(rng, 420, 20), scaled_rows(rng, 70, 20)
+    ph = ida.PartitionedHnsw.from_hnsws([scan_only(ida, np.ascontiguousarray(r), cosine_builder(ida)) for r in (x[:150], x[150:])])
+    xn, qn = np_normalize(oracle, x)[0], np_normalize(oracle, q)[0]
+    opid, odist = oracle.bruteforce(xn, qn, 10, metric=0, threads=8)
+    pid, dist = ph.bruteforce(q, 10)
+    assert np.array_equal(pid, opid)
+    assert np.array_equal(pc.bits(dist), halved(odist))
+
+
 # ---- 5. replicas and parts ----------------------------------------------------------------------------------------------
 def test_replicas_answer_as_the_root(eng, oracle):
     ida, kind = eng

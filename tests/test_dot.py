@@ -409,6 +409,37 @@ def test_bruteforce_mfma_gpu(engine_loader, oracle):
     check_bruteforce(ida, oracle, 20000, 63, 300, 10, 2)
 
 
+def mfma_bruteforce_knobs(monkeypatch):
+    """every brute force takes the MFMA filter + canonical re-rank, whatever its size; a sample of 64 rows sets the thresholds"""
+    pc.use_test_build(monkeypatch)                     # (both knobs exist in the test build only)
+    monkeypatch.setenv("IDIST_BRUTEFORCE", "mfma")
+    monkeypatch.setenv("IDIST_BF_SAMPLE", "64")
+
+
+def test_bruteforce_mfma_path(eng, oracle, monkeypatch):
+    """The MFMA path at a size the emulator runs too: n = 300 and nq = 130 are no multiples of its tiles, dim = 20 makes a 21-wide
+    row with tail and remainder, and with n below the smallest candidate capacity (1024) no list can overflow, so the call cannot
+    fall back to the scan."""
+    ida, kind = eng
+    mfma_bruteforce_knobs(monkeypatch)
+    check_bruteforce(ida, oracle, 300, 20, 130, 10, 3)
+
+
+def test_partitioned_bruteforce_mfma_path(eng, oracle, monkeypatch):
+    """the parts' MFMA brute force leaves the distances raw: they are reported once, after the merge"""
+    ida, kind = eng
+    mfma_bruteforce_knobs(monkeypatch)
+    rng = np.random.default_rng(6)
+    x, q = scaled_rows(rng, 420, 20), scaled_rows(rng, 70, 20)
+    xa, Sb, _ = np_augment(oracle, x)                                       # the bound of the WHOLE set
+    b = dot_builder(ida).dot_bound(Sb)
+    ph = ida.PartitionedHnsw.from_hnsws([scan_only(ida, np.ascontiguousarray(r), b) for r in (x[:150], x[150:])])
+    opid, odist = oracle.bruteforce(xa, np_queries(q), 10, metric=0, threads=8)
+    pid, dist = ph.bruteforce(q, 10)
+    assert np.array_equal(pid, opid)
+    assert np.array_equal(pc.bits(dist), reported(odist, np_norms(oracle, q), Sb))
+
+
 # ---- 5. replicas and imports --------------------------------------------------------------------------------------------
 def test_replicas_answer_as_the_root(eng, oracle):
     ida, kind = eng
