@@ -388,6 +388,50 @@ idist_status idist_partitioned_last_merge_ms(idist_partitioned* p, float* ms);
  * own time is set against. */
 idist_status idist_partitioned_last_search_kernel_ms(idist_partitioned* p, float* ms, uint32_t cap, uint32_t* n_out);
 
+/* ---- restricted search: the k nearest among an allowed subset --------------------------------------- */
+/* DEFINED through what is already exact: Hnsw::search (core/lib.rs:352-383) at growing ef_search, filtered, and an exact scan of the
+ * allowed rows below a derivable selectivity and when the ladder ends.  The walk itself is not touched.
+ *   A          the allowed set, a bitmap of (n + 31) / 32 u32 words: point `pid` is allowed iff bit pid % 32 of word pid / 32 is set;
+ *              bits at positions >= n are ignored.  One set per call, shared by the batch.
+ *   k          1 <= k <= ef_search of the index.
+ *   ladder     E[0] = ef_search, E[r + 1] = min(4 * E[r], IDIST_MAX_EF); it ends with the rung that equals IDIST_MAX_EF
+ *              (ef_search = 100: 100, 400, 1600, 4096).
+ *   max_rungs  -1: the whole ladder; m >= 0: only rungs r < m; 0: no rung at all = a restricted brute force (the ground truth for
+ *              recall).
+ * For one query:
+ *   1. n == 0, ef_search == 0 or |A| == 0: count 0, rung IDIST_RUNG_NONE.
+ *   2. |A| <= k: exact (step 5).
+ *   3. The start rung r0 is the first permitted r with E[r] * |A| >= k * n (64-bit integers): a rung whose expected number of
+ *      allowed hits is below k is not tried.  No such r: exact.
+ *   4. For r = r0, r0 + 1, ... among the permitted rungs: L = the result of Hnsw::search at ef_search = E[r] — for every metric the
+ *      raw distances of the stored rows, what idist_search_batch produces before its report pass.  At least k entries of L allowed:
+ *      the answer is the first k allowed entries of L, in L's order; rung = r; stop.
+ *   5. Exact: the k nearest points of A by the canonical distance, ordered by (distance, id) — idist_bruteforce restricted to A;
+ *      count = min(k, |A|); rung IDIST_RUNG_EXACT.
+ * Every query so gets exactly min(k, |A|) results.  Distances go through the metric's report once, at the end, on the [nq][k] result
+ * (as idist_partitioned_search_batch does); padding is IDIST_INVALID / +inf.  out_counters (optional, nq*3): {n_dist, n_exp0,
+ * n_expU} summed over the rungs that query actually ran; the exact step adds nothing to them (it shows in the rung).  A later rung
+ * whose ef_search does not fit a wave's LDS ends the ladder there as max_rungs would; the same failure at rung 0 is returned, as
+ * idist_search_batch returns it.  Strict ties: a rung whose tie region overflowed is searched again, IDIST_ERR_TIE_OVERFLOW never
+ * reaches the caller.  IDIST_ERR_INVALID_ARG: k out of range, max_rungs < -1, null pointers.
+ * Host pointers; blocks until done.  The call uses ctx as one `&mut Search` (its stream, its slots, staging memory the context owns
+ * and frees); idx stays shared and is never mutated — the rungs carry their own ef_search.  Staging: the widest rung holds
+ * 8 * E[r] bytes per query still pending.
+ * Cost: a query that climbs the whole ladder costs about 1.3 searches at ef_search 4096 (the rungs below add a quarter, a
+ * sixteenth, ...) plus a scan of A; max_rungs is the caller's bound.
+ * Out of scope: one set per query, device-pointer / stream variants, the partitioned index and idist_search_batch_sharded. */
+#define IDIST_RUNG_NONE  254u
+#define IDIST_RUNG_EXACT 255u
+idist_status idist_search_batch_allowed(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
+                                        const uint32_t* allow_bits, uint32_t k, int32_t max_rungs,
+                                        uint32_t* out_pid, float* out_dist,      /* nq*k */
+                                        uint32_t* out_count, uint32_t* out_rung, /* nq; out_rung may be NULL */
+                                        uint32_t* out_counters);                 /* nq*3 or NULL */
+/* HIP-event durations (ms) of the kernels the last idist_search_batch_allowed through ctx ran around its searches, summed over its
+ * rungs: the select passes, the pending-list passes, the exact step (scan + merge).  0 with IDIST_KERNEL_EVENTS=0.  The rungs' own
+ * search kernels are in idist_search_ctx_kernel_times. */
+idist_status idist_search_ctx_allowed_kernel_ms(idist_search_ctx* ctx, float* select_ms, float* pending_ms, float* exact_ms);
+
 /* Point::distance for id lists (core/lib.rs:780-782 as used at :709-710): out[q][i] =
  * distance(queries[q], points[ids[q][i]]) for i < n_ids; IDIST_INVALID ids give +inf.
  * Host pointers. The batched gather-L2 kernel on its own. */

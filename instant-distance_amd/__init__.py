@@ -9,10 +9,10 @@ The directory name is fixed by the repo contract; import it as
 # scalar calls/s.  That is a process-wide setting of the HOST's: neither libidist.so nor this package touches the environment —
 # an application that searches from many threads exports GPU_MAX_HW_QUEUES=16 before its first HIP call (bench.py does so before
 # it imports torch).
-from ._capi import (INVALID, M, M2, METRIC_COSINE, METRIC_DOT, METRIC_L2, METRIC_L2SQ, MAX_EF, TIES_DROP, TIES_STRICT, IdistError,
+from ._capi import (INVALID, M, M2, METRIC_COSINE, METRIC_DOT, METRIC_L2, METRIC_L2SQ, MAX_EF, RUNG_EXACT, RUNG_NONE, TIES_DROP, TIES_STRICT, IdistError,
                     LIB_PATH)
-from .api import (BatchResult, Builder, Heuristic, Hnsw, HnswMap, Item, MapItem, PointId, Search, augment_dot, normalize)
+from .api import (AllowedResult, BatchResult, Builder, Heuristic, Hnsw, HnswMap, Item, MapItem, PointId, Search, augment_dot, normalize)
 from .partition import PartitionedHnsw
 
-__all__ = ["Builder", "Heuristic", "Hnsw", "HnswMap", "PartitionedHnsw", "Search", "Item", "MapItem", "PointId", "BatchResult",
+__all__ = ["Builder", "Heuristic", "Hnsw", "HnswMap", "PartitionedHnsw", "Search", "Item", "MapItem", "PointId", "BatchResult", "AllowedResult", "RUNG_EXACT", "RUNG_NONE",
            "normalize", "augment_dot", "IdistError", "INVALID", "M", "M2", "METRIC_COSINE", "METRIC_DOT", "METRIC_L2", "METRIC_L2SQ", "MAX_EF", "TIES_DROP", "TIES_STRICT", "LIB_PATH"]

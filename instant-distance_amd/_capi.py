@@ -23,6 +23,8 @@ METRIC_L2SQ = 0
 METRIC_L2 = 1
 METRIC_COSINE = 2
 METRIC_DOT = 4   # (3 is unassigned and refused)
+RUNG_NONE = 254    # AllowedResult.rung: nothing to find (no points, ef_search 0, an empty allowed set)
+RUNG_EXACT = 255   # ... answered by the exact scan of the allowed rows
 TIES_STRICT = 0
 TIES_DROP = 1
 
@@ -136,6 +138,9 @@ SYMBOLS = {
     "idist_partitioned_bruteforce": (C.c_int32, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),
     "idist_partitioned_last_merge_ms": (C.c_int32, [_vp, C.POINTER(C.c_float)]),
     "idist_partitioned_last_search_kernel_ms": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p]),
+    "idist_search_batch_allowed": (C.c_int32, [_vp, _vp, _f32p, C.c_uint32, _u32p, C.c_uint32, C.c_int32, _u32p, _f32p, _u32p, _u32p,
+                                               _u32p]),
+    "idist_search_ctx_allowed_kernel_ms": (C.c_int32, [_vp, _f32p, _f32p, _f32p]),
     "idist_distance_batch": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, _f32p]),
     "idist_filter_bound_batch": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, _f32p]),
     "idist_bruteforce": (C.c_int32, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),

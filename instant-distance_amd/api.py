@@ -28,7 +28,7 @@ from typing import Any, Iterator, Sequence
 import numpy as np
 
 from . import _capi
-from ._capi import INVALID, M, M2, METRIC_COSINE, METRIC_DOT, METRIC_L2, METRIC_L2SQ, TIES_DROP, TIES_STRICT
+from ._capi import INVALID, M, M2, METRIC_COSINE, METRIC_DOT, METRIC_L2, METRIC_L2SQ, RUNG_EXACT, RUNG_NONE, TIES_DROP, TIES_STRICT
 
 PointId = int
 
@@ -257,6 +257,13 @@ class Search:
         the device to grow the context."""
         _lib().check(_lib().idist_search_ctx_reserve(self._bind(hnsw), int(slots)))
 
+    def allowed_kernel_ms(self) -> tuple[float, float, float]:
+        """HIP-event time (ms) of the select passes, the pending-list passes and the exact step (scan + merge) of the last
+        `search_allowed` through this Search; the rungs' own search kernels are in `kernel_times_ms`."""
+        a, b, c = C.c_float(0), C.c_float(0), C.c_float(0)
+        _lib().check(_lib().idist_search_ctx_allowed_kernel_ms(self._ctx, C.byref(a), C.byref(b), C.byref(c)))
+        return float(a.value), float(b.value), float(c.value)
+
     def kernel_times_ms(self, last: int = 64) -> np.ndarray:
         """HIP-event durations of the most recent search kernels launched through this Search."""
         out = np.zeros(last, dtype=np.float32)
@@ -320,6 +327,38 @@ class BatchResult:
     distance: np.ndarray  # [nq, ef_search] float32, +inf padded
     count: np.ndarray     # [nq]
     counters: np.ndarray | None  # [nq, 3] {n_dist, n_exp0, n_expU}
+
+
+@dataclass
+class AllowedResult:
+    """`Hnsw.search_allowed`: every query holds exactly min(k, allowed points) results."""
+    pid: np.ndarray       # [nq, k] uint32, INVALID padded
+    distance: np.ndarray  # [nq, k] float32, +inf padded
+    count: np.ndarray     # [nq]
+    rung: np.ndarray      # [nq] the rung of the ef ladder that answered the query, RUNG_EXACT (the scan of the allowed rows) or RUNG_NONE
+    counters: np.ndarray | None  # [nq, 3] {n_dist, n_exp0, n_expU} summed over the rungs the query ran
+
+
+def allowed_bitmap(allowed, n: int) -> np.ndarray:
+    """The allowed set of `search_allowed` as the ABI takes it: (n + 31) // 32 u32 words, bit pid % 32 of word pid // 32.  `allowed`: a
+    bool array of length n in PointId order, or an integer array of PointIds (duplicates are harmless)."""
+    a = np.asarray(allowed)
+    if a.dtype == np.bool_:
+        if a.shape != (n,):
+            raise ValueError(f"a bool `allowed` must have one entry per point: shape ({n},), got {a.shape}")
+        mask = a
+    else:
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise TypeError("`allowed` is a bool mask of length n or an integer array of PointIds")
+        ids = a.astype(np.int64).reshape(-1)
+        if ids.size and (ids.min() < 0 or ids.max() >= n):
+            raise IndexError(f"`allowed` names a PointId outside [0, {n})")
+        mask = np.zeros(n, dtype=bool)
+        mask[ids] = True
+    words = (n + 31) // 32
+    padded = np.zeros(words * 32, dtype=np.uint8)
+    padded[:n] = mask
+    return np.ascontiguousarray(np.packbits(padded, bitorder="little").view("<u4").astype(np.uint32))
 
 
 def normalize(points, device: int = 0, return_norm2: bool = False):
@@ -496,6 +535,31 @@ class Hnsw:
                                          _capi.u32p(cnt), _capi.u32p(ctr) if counters else None))
         return BatchResult(pid, dist, cnt, ctr)
 
+    def search_allowed(self, queries, allowed, k: int, search: Search, max_rungs: int = -1, counters: bool = False) -> AllowedResult:
+        """The k nearest among the points of `allowed` (idist_search_batch_allowed; 1 <= k <= ef_search): `Hnsw::search` at
+        ef_search, 4 ef_search, ... 4096, filtered — the first rung that holds k allowed points answers — and an exact scan of the
+        allowed rows when the set is too small for the ladder or the ladder ends.  `allowed`: a bool array of length n in PointId
+        order or an integer array of PointIds, one set for the whole batch.  `max_rungs`: -1 the whole ladder, m only its first m
+        rungs, 0 the exact scan alone (the ground truth for recall).  A query that climbs the whole ladder costs about 1.3 searches
+        at ef_search 4096 plus a scan of the allowed rows."""
+        q = _as_points(queries)
+        info = self.info()
+        if q.shape[0] and info.n and q.shape[1] != info.dim:
+            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
+        bits = allowed_bitmap(allowed, int(info.n))
+        nq, k = q.shape[0], int(k)
+        kk = max(k, 0)
+        pid = np.full((nq, kk), INVALID, dtype=np.uint32)
+        dist = np.full((nq, kk), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        rung = np.full(nq, RUNG_NONE, dtype=np.uint32)
+        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
+        ctx = search._bind(self)
+        L = _lib()
+        L.check(L.idist_search_batch_allowed(self._h, ctx, _capi.f32p(q), nq, _capi.u32p(bits), kk, int(max_rungs), _capi.u32p(pid),
+                                             _capi.f32p(dist), _capi.u32p(cnt), _capi.u32p(rung), _capi.u32p(ctr) if counters else None))
+        return AllowedResult(pid, dist, cnt, rung, ctr)
+
     def search_batch_device(self, search: Search, d_queries: int, nq: int, d_pid: int, d_dist: int, d_count: int,
                             d_counters: int = 0, stream: int = 0):
         """Device-pointer variant: inputs/outputs stay in HBM, enqueued on `stream` without a sync."""
@@ -609,6 +673,12 @@ class HnswMap:
         self.hnsw.search(point, search)
         search._items = [MapItem(it.distance, it.pid, it.point, self.values[it.pid]) for it in search._items]
         return search
+
+    def search_allowed(self, queries, allowed, k: int, search: Search, max_rungs: int = -1) -> list[list[MapItem]]:
+        """`Hnsw.search_allowed` with the values: per query its min(k, allowed points) results as `MapItem`s, nearest first."""
+        r = self.hnsw.search_allowed(queries, allowed, k, search, max_rungs)
+        return [[MapItem(float(r.distance[i, j]), int(r.pid[i, j]), self.hnsw.points[int(r.pid[i, j])], self.values[int(r.pid[i, j])])
+                 for j in range(int(r.count[i]))] for i in range(r.pid.shape[0])]
 
     def iter(self):
         return self.hnsw.iter()

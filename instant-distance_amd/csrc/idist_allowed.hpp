@@ -1,0 +1,189 @@
+// idist_allowed.hpp — the kernels around a restricted search (idist_search_batch_allowed, include/idist.h).
+//
+// A restricted search is DEFINED through what is already bit-exact: Hnsw::search at growing ef_search (the "rungs"), filtered by
+// the allowed set A, and an exact scan of A's rows where the ladder does not apply or ends.  The walk kernels are not touched;
+// everything here runs between their launches, on the launch's stream:
+//
+//   allowed_init_kernel     the result rows of all nq queries padded (kInvalid / +inf), count 0, rung NONE, counters 0, every query
+//                           pending.
+//   allowed_select_kernel   one wave per pending query: its rung result row against the bitmap (n / 8 bytes, L2-resident), ballot +
+//                           prefix-popcount compaction of the first k allowed entries into the row of the ORIGINAL query index.  k
+//                           found: count, rung, no longer pending.  The counters of the rung are added either way.  The same
+//                           kernel finishes the exact step (every entry of the merged scan is allowed): it writes what there is,
+//                           pads the row and closes the query whatever the count.
+//   allowed_pending_kernel  the pending queries in ascending order (a wave per 64 queries: the set flags in front of its chunk are
+//                           counted, not scanned — no atomics, the same list whatever the schedule), and their prepared rows
+//                           gathered into a contiguous buffer for the next rung's launch.
+//   allowed_scan_kernel     the exact step: bruteforce_kernel's machinery (dist_rounds, w_rank / w_insert with ef = k) over one
+//                           contiguous segment of the ascending id list of A per wave; grid = pending queries x S segments.  Each
+//                           wave writes its segment's sorted top-k as list s in merge_topk_kernel's input layout (base 0): the
+//                           merge by (distance bits, id) gives the k best, and ids are distinct, so the result does not depend on S.
+#pragma once
+#include "idist_kernels.hpp"
+#include "idist_merge.hpp"
+
+namespace idist {
+
+constexpr uint32_t kRungNone = 254u;     // IDIST_RUNG_NONE
+constexpr uint32_t kRungExact = 255u;    // IDIST_RUNG_EXACT
+
+__device__ __forceinline__ bool allowed_bit(const uint32_t* __restrict__ bits, uint32_t n, uint32_t pid) {
+    return pid < n && ((bits[pid >> 5] >> (pid & 31u)) & 1u) != 0u;
+}
+
+struct AllowedOut {
+    uint32_t* pid;        // [nq][k]
+    uint32_t* dist;       // [nq][k] f32 bit patterns
+    uint32_t* count;      // [nq]
+    uint32_t* rung;       // [nq]
+    uint32_t* counters;   // [nq][3] or nullptr
+    uint32_t* pending;    // [nq] 1: not answered yet
+    uint32_t nq, k;
+};
+
+__global__ void allowed_init_kernel(AllowedOut o) {
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (size_t)gridDim.x * blockDim.x;
+    const size_t total = (size_t)o.nq * o.k;
+    for (size_t i = tid; i < total; i += nth) {
+        o.pid[i] = kInvalid;
+        o.dist[i] = 0x7f800000u;
+    }
+    for (size_t q = tid; q < o.nq; q += nth) {
+        o.count[q] = 0u;
+        o.rung[q] = kRungNone;
+        o.pending[q] = 1u;
+        if (o.counters) { o.counters[3 * q] = 0u; o.counters[3 * q + 1] = 0u; o.counters[3 * q + 2] = 0u; }
+    }
+}
+
+// r_pid / r_dist: [np][width] result rows of the np pending queries, r_count [np], r_counters [np][3] or nullptr.  list [np]: the
+// original query index of every row (nullptr: the identity).  rung: what a query answered here reports.  exact != 0: the rows are
+// the merged scan of A — written, padded and closed whatever their count.
+__global__ __launch_bounds__(64) void allowed_select_kernel(AllowedOut o, const uint32_t* __restrict__ bits, uint32_t n,
+                                                            const uint32_t* __restrict__ r_pid, const uint32_t* __restrict__ r_dist,
+                                                            const uint32_t* __restrict__ r_count, const uint32_t* __restrict__ r_counters,
+                                                            uint32_t width, const uint32_t* __restrict__ list, uint32_t np,
+                                                            uint32_t rung, uint32_t exact) {
+    const int lane = lane_id();
+    const uint64_t below = (1ull << lane) - 1ull;
+    for (uint32_t p = blockIdx.x; p < np; p += gridDim.x) {
+        const uint32_t q = list ? list[p] : p;
+        uint32_t cnt = r_count[p];
+        cnt = cnt < width ? cnt : width;
+        const uint32_t* row_pid = r_pid + (size_t)p * width;
+        const uint32_t* row_dist = r_dist + (size_t)p * width;
+        uint32_t* o_pid = o.pid + (size_t)q * o.k;
+        uint32_t* o_dist = o.dist + (size_t)q * o.k;
+        uint32_t taken = 0;
+        for (uint32_t i0 = 0; i0 < cnt && taken < o.k; i0 += 64u) {
+            const uint32_t i = i0 + (uint32_t)lane;
+            uint32_t id = kInvalid;
+            if (i < cnt) id = row_pid[i];
+            const bool ok = i < cnt && allowed_bit(bits, n, id);
+            const uint64_t m = __ballot(ok);
+            const uint32_t pos = taken + (uint32_t)__popcll(m & below);
+            if (ok && pos < o.k) {
+                o_pid[pos] = id;
+                o_dist[pos] = row_dist[i];
+            }
+            taken += (uint32_t)__popcll(m);
+        }
+        taken = taken < o.k ? taken : o.k;
+        if (o.counters && r_counters && lane < 3) o.counters[(size_t)q * 3u + lane] += r_counters[(size_t)p * 3u + lane];
+        if (exact) {
+            for (uint32_t r = taken + (uint32_t)lane; r < o.k; r += 64u) {
+                o_pid[r] = kInvalid;
+                o_dist[r] = 0x7f800000u;
+            }
+        }
+        if (lane == 0 && (exact || taken == o.k)) {
+            o.count[q] = taken;
+            o.rung[q] = rung;
+            o.pending[q] = 0u;
+        }
+    }
+}
+
+// pending [nq] -> list: the pending query indices, ascending; pend_q [np][kdim]: their rows of `queries` [nq][kdim]; *n_pending = np.
+// grid = ceil(nq / 64) waves EXACTLY: wave b owns the queries [64 b, 64 b + 64) and the last one writes the total.
+__global__ __launch_bounds__(64) void allowed_pending_kernel(const uint32_t* __restrict__ pending, uint32_t nq,
+                                                             const float* __restrict__ queries, uint32_t kdim,
+                                                             uint32_t* __restrict__ list, float* __restrict__ pend_q,
+                                                             uint32_t* __restrict__ n_pending) {
+    const int lane = lane_id();
+    const uint32_t first = blockIdx.x * 64u;
+    uint32_t before = 0;
+    for (uint32_t i = (uint32_t)lane; i < first; i += 64u) before += pending[i] ? 1u : 0u;
+    before = wave_sum_u32(before);
+    const uint32_t q = first + (uint32_t)lane;
+    const bool on = q < nq && pending[q] != 0u;
+    const uint64_t m = __ballot(on);
+    if (on) list[before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = q;
+    uint64_t rest = m;
+    uint32_t pos = before;
+    while (rest) {
+        const int j = __builtin_ctzll(rest);
+        rest &= rest - 1ull;
+        const float* src = queries + (size_t)(first + (uint32_t)j) * kdim;
+        float* dst = pend_q + (size_t)pos * kdim;
+        for (uint32_t e = (uint32_t)lane; e < kdim; e += 64u) dst[e] = src[e];
+        pos++;
+    }
+    if (blockIdx.x == gridDim.x - 1u && lane == 0) *n_pending = before + (uint32_t)__popcll(m);
+}
+
+// The exact step.  ids [n_ids]: A's points, ascending; cut into S contiguous segments [n_ids s / S, n_ids (s + 1) / S).  queries
+// [np][dim]: the pending queries' rows.  Work item w = p * S + s; out_pid / out_dist [S][np][k], out_count [S][np] (merge_topk_kernel's
+// input layout).  Only the first out_count entries of a list are written.
+template <int NB, int RS, int TAIL>
+__global__ __launch_bounds__(64) void allowed_scan_kernel(IndexView ix, const float* __restrict__ queries, uint32_t np,
+                                                          const uint32_t* __restrict__ ids, uint32_t n_ids, uint32_t S, uint32_t k,
+                                                          uint32_t wcap, uint32_t* out_pid, uint32_t* out_dist, uint32_t* out_count) {
+    IDIST_DYN_SMEM(smem_raw);
+    const Smem sm = carve(smem_raw, ix.stride, wcap, false);
+    const int lane = lane_id();
+    const uint32_t nb = NB >= 0 ? (uint32_t)NB : ix.nb;
+    const uint64_t items = (uint64_t)np * S;
+    for (uint64_t w = blockIdx.x; w < items; w += gridDim.x) {
+        const uint32_t p = (uint32_t)(w / S), s = (uint32_t)(w % S);
+        const uint32_t lo = (uint32_t)((uint64_t)n_ids * s / S), hi = (uint32_t)((uint64_t)n_ids * (s + 1u) / S);
+        wave_sync();
+        for (uint32_t o = lane; o < ix.stride; o += 64) sm.q[o] = 0.0f;
+        wave_sync();
+        for (uint32_t e = lane; e < ix.dim; e += 64) sm.q[blocked_pos(e, nb)] = queries[(size_t)p * ix.dim + e];
+        wave_sync();
+        WState st{sm.W, 0, (int)k, 0, 0u};
+        for (uint32_t base = lo; base < hi; base += 64u) {
+            const int na = hi - base < 64u ? (int)(hi - base) : 64;
+            uint32_t id = kInvalid;
+            if (lane < na) {
+                id = ids[base + (uint32_t)lane];
+                sm.act_pid[lane] = id;
+            }
+            wave_sync();
+            dist_rounds<NB, RS, TAIL>(ix, sm.q, sm.act_pid, sm.act_dist, na);
+            wave_sync();
+            uint64_t key = kMaxKey;
+            if (lane < na) key = ((uint64_t)sm.act_dist[lane] << 32) | id;
+            const uint64_t thr = st.plen >= st.ef ? (st.W[st.ef - 1] & kKeyMask) : kMaxKey + 1ull;
+            uint64_t pm = __ballot(lane < na && key < thr);
+            while (pm) {
+                const int i = __builtin_ctzll(pm);
+                pm &= pm - 1ull;
+                const uint64_t kk = bcast_u64(key, i);
+                const int idx = w_rank(st, kk);
+                if (idx < st.ef) w_insert(st, idx, kk);
+            }
+            if (st.plen > st.ef) st.plen = st.ef;   // plain truncate (no candidates here)
+            wave_sync();
+        }
+        const size_t row = ((size_t)s * np + p) * k;
+        for (uint32_t i = lane; i < (uint32_t)st.plen; i += 64) {
+            out_pid[row + i] = (uint32_t)st.W[i];
+            out_dist[row + i] = (uint32_t)((st.W[i] & kKeyMask) >> 32);
+        }
+        if (lane == 0) out_count[(size_t)s * np + p] = (uint32_t)st.plen;
+    }
+}
+
+}  // namespace idist

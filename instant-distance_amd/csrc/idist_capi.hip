@@ -8,6 +8,7 @@
 #include "idist_merge.hpp"
 #include "idist_normalize.hpp"
 #include "idist_dot.hpp"
+#include "idist_allowed.hpp"
 
 #ifndef IDIST_EMU
 #include <hip/hip_runtime.h>
@@ -307,6 +308,8 @@ struct Knobs {
     bool no_zero_copy = false;    // IDIST_NO_ZERO_COPY=1: narrow host-pointer batches take the general (staged) path too (test / A-B knob)
     int ea = 0;                   // IDIST_EA=<k> (measurement builds only, -DIDIST_EA_PROBE): early abandon after k blocks of a 300-d row
     uint32_t w2_ef = 0xFFFFFFFFu; // IDIST_W2_EF=<ef>: from this ef_search on, wide on-chip batches run two 256-register waves per SIMD (A/B knob; default: policy)
+    uint32_t allowed_segments = 0;    // IDIST_ALLOWED_SEGMENTS=<1..64>: segments of the exact step of a restricted search (test knob: the result
+                                      // must not depend on it; default: by the number of pending queries)
     uint32_t quad_nq = 0xFFFFFFFFu;   // IDIST_QUAD_NQ: batches up to this many queries run four waves per query (default: two
                                       // workgroups per CU, one for 768-d rows; 0 = never)
     static Knobs from_env() {
@@ -314,6 +317,7 @@ struct Knobs {
         warn_ignored_knobs();
         if (const char* e = test_env("IDIST_EA")) k.ea = atoi(e);
         if (const char* e = test_env("IDIST_W2_EF")) k.w2_ef = (uint32_t)strtoul(e, nullptr, 10);
+        if (const char* e = test_env("IDIST_ALLOWED_SEGMENTS")) k.allowed_segments = std::min(64u, (uint32_t)std::max(0, atoi(e)));
         if (const char* e = test_env("IDIST_LATENCY_NQ")) k.latency_nq = (uint32_t)strtoul(e, nullptr, 10);
         if (const char* e = test_env("IDIST_QUAD_NQ")) k.quad_nq = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 0xFFFFFFFEul);
         if (const char* e = test_env("IDIST_WALK")) k.classic = e[0] == 'c';      // (honoured by the test build only, see variants_check)
@@ -373,6 +377,20 @@ struct idist_search_ctx {
     size_t cap_qn = 0;             // (cosine: normalised; DOT: with the trailing 0, [nq][kdim])
     float* d_sq = nullptr;         // DOT indexes: s(q) per query of the launch, for the report pass
     size_t cap_sq = 0;
+    // staging of idist_search_batch_allowed (grow-only, freed with the context): the bitmap and the ascending id list of A, the
+    // pending flags / list / count / gathered query rows, the [nq][k] result with its counts, rungs and counters, and the merged
+    // scan of the exact step.  The rungs' result rows and the scan's segment lists use d_pid / d_dist / d_cnt / d_ctr above.
+    struct Buf {
+        void* p = nullptr;
+        size_t cap = 0;
+        template <typename T> T* as() const { return static_cast<T*>(p); }
+    };
+    Buf al_bits, al_ids, al_flag, al_list, al_npend, al_pq, al_opid, al_odist, al_ocnt, al_orung, al_octr, al_mpid, al_mdist, al_mcnt;
+    static constexpr uint32_t kAllowedEvents = 40;   // a pair per select / pending pass of at most seven rungs + the exact step's two
+    hipEvent_t al_ev[kAllowedEvents] = {nullptr};    // (created on first use, resolved when the call has synchronised its stream)
+    uint8_t al_ev_which[kAllowedEvents / 2] = {0};
+    uint32_t al_ev_used = 0;
+    float al_ms[3] = {0.0f, 0.0f, 0.0f};   // the last call's select, pending and scan + merge kernels, summed over its rungs
     bool tie_overflowed = false;
     uint32_t tie_cap = 0;          // tie capacity this context escalated to (0 = the index's)
     // strict ties, last resort: one bag of n keys per slot in HBM (the reference's candidate heap is unbounded, core/lib.rs:564)
@@ -1462,8 +1480,11 @@ idist_status filter_ensure(const idist_index* ix) {
 idist_status launch_search(const idist_index* ix, idist_search_ctx* ctx, const float* d_q, uint32_t nq,
                            uint32_t* d_pid, float* d_dist, uint32_t* d_cnt, uint32_t* d_ctr, hipStream_t stream,
                            uint32_t* status_host = nullptr, uint32_t* grid_out = nullptr, uint32_t* done_host = nullptr, uint32_t done_seq = 0,
-                           bool prepared = false) {
-    const uint32_t ef = ix->cfg.ef_search;
+                           bool prepared = false, uint32_t ef_arg = 0, bool* lds_short = nullptr) {
+    // ef_arg: the ef_search of this launch when it is not the index's (the rungs of a restricted search: the index is shared and
+    // never mutated).  *lds_short: set when the launch was refused because this ef_search does not fit a wave's LDS.
+    const uint32_t ef = ef_arg ? ef_arg : ix->cfg.ef_search;
+    if (lds_short) *lds_short = false;
     CHK(variants_check(ctx->knobs.classic));
     // Cosine and DOT: the walk reads the queries MetricPasses::prepare wrote into buffers this context owns (the caller's are only
     // read), and the distances it wrote are reported behind it — both on the launch's stream, outside the events that time the
@@ -1600,7 +1621,10 @@ idist_status launch_search(const idist_index* ix, idist_search_ctx* ctx, const f
                      smem_bytes(ix->L.stride, a.wcap, false, kBloomLatWords, a.vis.dirty_words) <= 64 * 1024;
     const size_t smem = smem_bytes(ix->L.stride, a.wcap, false, on_chip ? (1u << tab_log2) : (lat ? kBloomLatWords : kBloomWords),
                                    a.vis.dirty_words, !thin);
-    if (smem > 64 * 1024) return fail(IDIST_ERR_INVALID_ARG, "dim/ef_search need %zu B of LDS per wave (> 64 KiB)", smem);
+    if (smem > 64 * 1024) {
+        if (lds_short) *lds_short = true;
+        return fail(IDIST_ERR_INVALID_ARG, "dim/ef_search need %zu B of LDS per wave (> 64 KiB)", smem);
+    }
     const uint32_t grid = std::min(std::min(nq, ctx->slots), resident);
     [[maybe_unused]] const bool classic = ctx->knobs.classic;   // (test build: IDIST_VARIANT_SEARCH_*)
     IndexView view = ix->view();
@@ -2002,6 +2026,11 @@ void idist_search_ctx_free(idist_search_ctx* c) {
     hipFree(c->d_dist);
     hipFree(c->d_cnt);
     hipFree(c->d_ctr);
+    for (idist_search_ctx::Buf* b : {&c->al_bits, &c->al_ids, &c->al_flag, &c->al_list, &c->al_npend, &c->al_pq, &c->al_opid, &c->al_odist,
+                                     &c->al_ocnt, &c->al_orung, &c->al_octr, &c->al_mpid, &c->al_mdist, &c->al_mcnt})
+        hipFree(b->p);
+    for (hipEvent_t e : c->al_ev)
+        if (e) hipEventDestroy(e);
     for (uint32_t i = 0; i < IDIST_EVENT_RING; i++) {
         if (c->ev0[i]) hipEventDestroy(c->ev0[i]);
         if (c->ev1[i]) hipEventDestroy(c->ev1[i]);
@@ -3045,6 +3074,231 @@ static idist_status bruteforce_impl(const idist_index* idx, const float* queries
 idist_status idist_bruteforce(const idist_index* idx, const float* queries, uint32_t nq, uint32_t k,
                               uint32_t* out_pid, float* out_dist) {
     return bruteforce_impl(idx, queries, nq, k, out_pid, out_dist, false);
+}
+
+// ---- restricted search: the ef ladder over Hnsw::search, exact scan of the allowed rows ----
+extern "C++" {
+namespace {
+
+// `fn` enqueues kernels on the context's stream between two HIP events (kernel events on); allowed_times_resolve adds their
+// durations to ctx->al_ms[which] once the call has synchronised the stream — no synchronisation of its own
+template <typename F> idist_status allowed_timed(idist_search_ctx* ctx, int which, F fn) {
+    const uint32_t u = ctx->al_ev_used;
+    if (!ctx->knobs.events || u + 2 > idist_search_ctx::kAllowedEvents) return fn();
+    for (uint32_t i = u; i < u + 2; i++)
+        if (!ctx->al_ev[i]) HIPCHK(hipEventCreate(&ctx->al_ev[i]));
+    HIPCHK(hipEventRecord(ctx->al_ev[u], ctx->stream));
+    CHK(fn());
+    HIPCHK(hipEventRecord(ctx->al_ev[u + 1], ctx->stream));
+    ctx->al_ev_which[u / 2] = (uint8_t)which;
+    ctx->al_ev_used = u + 2;
+    return IDIST_OK;
+}
+idist_status allowed_times_resolve(idist_search_ctx* ctx) {
+    for (uint32_t u = 0; u < ctx->al_ev_used; u += 2) {
+        float ms = 0.0f;
+        HIPCHK(hipEventElapsedTime(&ms, ctx->al_ev[u], ctx->al_ev[u + 1]));
+        ctx->al_ms[ctx->al_ev_which[u / 2]] += ms;
+    }
+    ctx->al_ev_used = 0;
+    return IDIST_OK;
+}
+
+idist_status allowed_select(idist_search_ctx* ctx, const AllowedOut& o, uint32_t n, const uint32_t* r_pid, const float* r_dist,
+                            const uint32_t* r_cnt, const uint32_t* r_ctr, uint32_t width, const uint32_t* list, uint32_t np,
+                            uint32_t rung, bool exact) {
+    auto select_pass = [&]() -> idist_status {
+        const uint32_t grid = std::min<uint32_t>(np, 65536u);                 // one wave per pending query; the kernel strides over the rest
+        IDIST_LAUNCH(allowed_select_kernel, grid, 64, 0, ctx->stream, o, ctx->al_bits.as<uint32_t>(), n, r_pid,
+                     reinterpret_cast<const uint32_t*>(r_dist), r_cnt, r_ctr, width, list, np, rung, exact ? 1u : 0u);
+        HIPCHK(hipGetLastError());
+        return IDIST_OK;
+    };
+    return allowed_timed(ctx, 0, select_pass);
+}
+
+}  // namespace
+}  // extern "C++"
+
+idist_status idist_search_batch_allowed(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
+                                        const uint32_t* allow_bits, uint32_t k, int32_t max_rungs, uint32_t* out_pid,
+                                        float* out_dist, uint32_t* out_count, uint32_t* out_rung, uint32_t* out_counters) {
+    CHK(check_ctx(idx, ctx));
+    const uint32_t n = idx->n, ef0 = idx->cfg.ef_search;
+    if (max_rungs < -1) return fail(IDIST_ERR_INVALID_ARG, "max_rungs %d: -1 (the whole ladder) or a number of rungs >= 0", max_rungs);
+    if (k == 0 || k > IDIST_MAX_EF) return fail(IDIST_ERR_INVALID_ARG, "k %u out of [1,%u]", k, IDIST_MAX_EF);
+    if (ef0 != 0 && k > ef0) return fail(IDIST_ERR_INVALID_ARG, "k %u > ef_search %u", k, ef0);
+    if (nq == 0) return IDIST_OK;
+    if (!queries || !out_pid || !out_dist || !out_count || (n && !allow_bits)) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    // A: the bitmap with the bits at positions >= n cleared, its size, and (when an exact step needs it) its ascending id list
+    const uint32_t words = (n + 31u) / 32u;
+    std::vector<uint32_t> bits(allow_bits, allow_bits + words);
+    if (n % 32u) bits[words - 1] &= (1u << (n % 32u)) - 1u;
+    uint64_t n_allowed = 0;
+    for (const uint32_t w : bits) n_allowed += (uint64_t)__builtin_popcount(w);
+    const size_t ob = (size_t)nq * k * 4;
+    if (n == 0 || ef0 == 0 || n_allowed == 0) {                              // step 1: nothing to find
+        for (size_t i = 0; i < (size_t)nq * k; i++) { out_pid[i] = IDIST_INVALID; out_dist[i] = INFINITY; }
+        memset(out_count, 0, (size_t)nq * 4);
+        if (out_rung) std::fill(out_rung, out_rung + nq, (uint32_t)IDIST_RUNG_NONE);
+        if (out_counters) memset(out_counters, 0, (size_t)nq * 12);
+        return IDIST_OK;
+    }
+    // the ladder E[0] = ef_search, E[r + 1] = min(4 E[r], IDIST_MAX_EF), ending with the rung that equals IDIST_MAX_EF; the
+    // permitted rungs are r < n_rungs; the start rung is the first whose expected number of allowed hits reaches k (64-bit)
+    uint32_t E[8], n_rungs = 0;
+    for (uint32_t e = ef0;; e = std::min<uint32_t>(4u * e, IDIST_MAX_EF)) {
+        E[n_rungs++] = e;
+        if (e >= IDIST_MAX_EF) break;
+    }
+    if (max_rungs >= 0) n_rungs = std::min<uint32_t>(n_rungs, (uint32_t)max_rungs);
+    uint32_t r0 = n_rungs;
+    if (n_allowed > k)
+        for (uint32_t r = 0; r < n_rungs && r0 == n_rungs; r++)
+            if ((uint64_t)E[r] * n_allowed >= (uint64_t)k * n) r0 = r;
+
+    HIPCHK(hipSetDevice(idx->device));
+    hipStream_t stream = ctx->stream;
+    const MetricPasses metric(idx);
+    const uint32_t kdim = idx->kdim;
+    const size_t qb = (size_t)nq * idx->dim * 4;
+    const bool counters = out_counters != nullptr;
+    ctx->al_ms[0] = ctx->al_ms[1] = ctx->al_ms[2] = 0.0f;
+    ctx->al_ev_used = 0;
+    CHK(grow(ctx->d_q, ctx->cap_q, qb));
+    CHK(grow(ctx->al_bits.p, ctx->al_bits.cap, (size_t)words * 4));
+    CHK(grow(ctx->al_flag.p, ctx->al_flag.cap, (size_t)nq * 4));
+    CHK(grow(ctx->al_list.p, ctx->al_list.cap, (size_t)nq * 4));
+    CHK(grow(ctx->al_npend.p, ctx->al_npend.cap, 256));
+    CHK(grow(ctx->al_pq.p, ctx->al_pq.cap, (size_t)nq * kdim * 4));
+    CHK(grow(ctx->al_opid.p, ctx->al_opid.cap, ob));
+    CHK(grow(ctx->al_odist.p, ctx->al_odist.cap, ob));
+    CHK(grow(ctx->al_ocnt.p, ctx->al_ocnt.cap, (size_t)nq * 4));
+    CHK(grow(ctx->al_orung.p, ctx->al_orung.cap, (size_t)nq * 4));
+    CHK(grow(ctx->al_octr.p, ctx->al_octr.cap, (size_t)nq * 12));
+    HIPCHK(hipMemcpyAsync(ctx->d_q, queries, qb, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(ctx->al_bits.p, bits.data(), (size_t)words * 4, hipMemcpyHostToDevice, stream));
+    // cosine / DOT: the queries are prepared ONCE per call, every rung and the scan take them as they are (prepared = true), and the
+    // metric's report runs once, at the end, on the [nq][k] result — as the partitioned search does, and for its reason
+    const float* d_qk = ctx->d_q;
+    if (metric.any()) {
+        CHK(grow(ctx->d_qn, ctx->cap_qn, doubled_from(4096, metric.qk_floats(nq) * 4)));
+        CHK(grow(ctx->d_sq, ctx->cap_sq, doubled_from(256, metric.sq_floats(nq) * 4)));
+        CHK(metric.prepare(ctx->d_q, ctx->d_qn, ctx->d_sq, nq, stream, &d_qk));
+    }
+    AllowedOut o{};
+    o.pid = ctx->al_opid.as<uint32_t>(); o.dist = ctx->al_odist.as<uint32_t>(); o.count = ctx->al_ocnt.as<uint32_t>();
+    o.rung = ctx->al_orung.as<uint32_t>(); o.counters = counters ? ctx->al_octr.as<uint32_t>() : nullptr;
+    o.pending = ctx->al_flag.as<uint32_t>(); o.nq = nq; o.k = k;
+    {
+        const uint32_t grid = (uint32_t)std::min<size_t>(((size_t)nq * k + 255) / 256, (size_t)std::max(ctx->n_cu, 1) * 8u);
+        IDIST_LAUNCH(allowed_init_kernel, grid, 256, 0, stream, o);
+        HIPCHK(hipGetLastError());
+    }
+    // the pending queries: all of them, in place, until the first rung has answered some
+    uint32_t np = nq;
+    std::vector<uint32_t> ids;                                   // (lives until the last synchronisation: it is uploaded asynchronously)
+    const uint32_t* d_list = nullptr;
+    const float* d_pq = d_qk;
+    for (uint32_t r = r0; r < n_rungs && np; r++) {
+        const uint32_t ef = E[r];
+        const size_t rb = (size_t)np * ef * 4;
+        CHK(grow(ctx->d_pid, ctx->cap_pid, rb));
+        CHK(grow(ctx->d_dist, ctx->cap_dist, rb));
+        CHK(grow(ctx->d_cnt, ctx->cap_cnt, (size_t)np * 4));
+        CHK(grow(ctx->d_ctr, ctx->cap_ctr, (size_t)np * 12));
+        bool lds_short = false, ended = false;
+        for (;;) {
+            const idist_status ls = launch_search(idx, ctx, d_pq, np, ctx->d_pid, ctx->d_dist, ctx->d_cnt, counters ? ctx->d_ctr : nullptr,
+                                                  stream, nullptr, nullptr, nullptr, 0, true, ef, &lds_short);
+            if (ls != IDIST_OK) {
+                // a later rung that does not fit a wave's LDS ends the ladder as max_rungs would; rung 0 fails as idist_search_batch does
+                if (lds_short && r != 0) { ended = true; break; }
+                return ls;
+            }
+            HIPCHK(hipStreamSynchronize(stream));
+            idist_status s;
+            if (status_asks_retry(idx, ctx, &s)) continue;      // strict ties: the same rung again with the larger region / the bags
+            if (s != IDIST_OK) return s;
+            break;
+        }
+        if (ended) break;
+        CHK(allowed_select(ctx, o, n, ctx->d_pid, ctx->d_dist, ctx->d_cnt, counters ? ctx->d_ctr : nullptr, ef, d_list, np, r, false));
+        auto pending_pass = [&]() -> idist_status {
+            IDIST_LAUNCH(allowed_pending_kernel, (nq + 63u) / 64u, 64, 0, stream, o.pending, nq, d_qk, kdim, ctx->al_list.as<uint32_t>(),
+                         ctx->al_pq.as<float>(), ctx->al_npend.as<uint32_t>());
+            HIPCHK(hipGetLastError());
+            return IDIST_OK;
+        };
+        CHK(allowed_timed(ctx, 1, pending_pass));
+        HIPCHK(hipMemcpyAsync(&np, ctx->al_npend.p, 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        d_list = ctx->al_list.as<uint32_t>();
+        d_pq = ctx->al_pq.as<float>();
+    }
+    if (np) {
+        // step 5, exact: the ascending id list of A cut into S segments, one wave per (pending query, segment), the segments'
+        // top-k lists merged by (distance bits, id).  S: enough waves for the chip when few queries are left over a large A, never
+        // segments of less than one 64-row round; the result does not depend on it
+        ids.reserve((size_t)n_allowed);
+        for (uint32_t w = 0; w < words; w++)
+            for (uint32_t m = bits[w]; m; m &= m - 1u) ids.push_back(32u * w + (uint32_t)__builtin_ctz(m));
+        const uint32_t n_ids = (uint32_t)ids.size();
+        uint32_t S = (uint32_t)std::min<uint64_t>(((uint64_t)std::max(ctx->n_cu, 1) * 16u + np - 1u) / np, (n_ids + 63u) / 64u);
+        if (ctx->knobs.allowed_segments) S = ctx->knobs.allowed_segments;
+        S = std::min(std::max(S, 1u), kMergeMaxLists);
+        const size_t sb = (size_t)S * np * k * 4, mb = (size_t)np * k * 4;
+        CHK(grow(ctx->al_ids.p, ctx->al_ids.cap, (size_t)n_ids * 4));
+        CHK(grow(ctx->d_pid, ctx->cap_pid, sb));
+        CHK(grow(ctx->d_dist, ctx->cap_dist, sb));
+        CHK(grow(ctx->d_cnt, ctx->cap_cnt, (size_t)S * np * 4));
+        CHK(grow(ctx->al_mpid.p, ctx->al_mpid.cap, mb));
+        CHK(grow(ctx->al_mdist.p, ctx->al_mdist.cap, mb));
+        CHK(grow(ctx->al_mcnt.p, ctx->al_mcnt.cap, (size_t)np * 4));
+        HIPCHK(hipMemcpyAsync(ctx->al_ids.p, ids.data(), (size_t)n_ids * 4, hipMemcpyHostToDevice, stream));
+        const uint32_t wcap = k + 64 + 8;
+        const size_t smem = smem_bytes(idx->L.stride, wcap, false);
+        if (smem > 64 * 1024) return fail(IDIST_ERR_INVALID_ARG, "dim/k need %zu B of LDS per wave (> 64 KiB)", smem);
+        auto scan_and_merge = [&]() -> idist_status {
+            const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)np * S, (uint64_t)std::max(ctx->n_cu, 1) * 64u);
+            IndexView view = idx->view();
+            uint32_t *s_pid = ctx->d_pid, *s_dist = reinterpret_cast<uint32_t*>(ctx->d_dist), *s_cnt = ctx->d_cnt;
+            const uint32_t* d_ids = ctx->al_ids.as<uint32_t>();
+#define LAUNCH_AS(NB_, RS_, TAIL_)                                                                                        \
+    {                                                                                                                     \
+        auto kA = allowed_scan_kernel<NB_, RS_, TAIL_>;                                                                   \
+        IDIST_LAUNCH(kA, grid, 64, smem, stream, view, d_pq, np, d_ids, n_ids, S, k, wcap, s_pid, s_dist, s_cnt);          \
+    }
+            IDIST_DISPATCH(idx->L, LAUNCH_AS);
+#undef LAUNCH_AS
+            HIPCHK(hipGetLastError());
+            MergeArgs a{};
+            a.pid = s_pid; a.dist = s_dist; a.count = s_cnt; a.counters = nullptr;
+            a.n_lists = S; a.nq = np; a.width = k; a.out_width = k;
+            a.out_pid = ctx->al_mpid.as<uint32_t>(); a.out_dist = ctx->al_mdist.as<uint32_t>(); a.out_count = ctx->al_mcnt.as<uint32_t>();
+            a.out_counters = nullptr;
+            return launch_merge(a, stream);
+        };
+        CHK(allowed_timed(ctx, 2, scan_and_merge));
+        CHK(allowed_select(ctx, o, n, ctx->al_mpid.as<uint32_t>(), ctx->al_mdist.as<float>(), ctx->al_mcnt.as<uint32_t>(), nullptr, k,
+                           d_list, np, IDIST_RUNG_EXACT, true));
+    }
+    CHK(metric.report(ctx->al_odist.as<float>(), ctx->d_sq, nq, k, stream));
+    HIPCHK(hipMemcpyAsync(out_pid, ctx->al_opid.p, ob, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(out_dist, ctx->al_odist.p, ob, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(out_count, ctx->al_ocnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, stream));
+    if (out_rung) HIPCHK(hipMemcpyAsync(out_rung, ctx->al_orung.p, (size_t)nq * 4, hipMemcpyDeviceToHost, stream));
+    if (counters) HIPCHK(hipMemcpyAsync(out_counters, ctx->al_octr.p, (size_t)nq * 12, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    return allowed_times_resolve(ctx);
+}
+
+idist_status idist_search_ctx_allowed_kernel_ms(idist_search_ctx* ctx, float* select_ms, float* pending_ms, float* exact_ms) {
+    if (!ctx || !select_ms || !pending_ms || !exact_ms) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    *select_ms = ctx->al_ms[0];
+    *pending_ms = ctx->al_ms[1];
+    *exact_ms = ctx->al_ms[2];
+    return IDIST_OK;
 }
 
 idist_status idist_normalize_batch(const float* rows, uint32_t n, uint32_t dim, float* out_rows, float* out_norm2, int32_t device) {

@@ -233,6 +233,32 @@ public:
             out.push_back(Item<P>{search.dist_[i], PointId{search.pid_[i]}, &points_[search.pid_[i]]});
         return out;
     }
+    // The k nearest among the allowed points (idist_search_batch_allowed, include/idist.h; not in the reference): Hnsw::search at
+    // ef_search, 4 ef_search, ... 4096, filtered — the first rung that holds k allowed points answers — and an exact scan of the
+    // allowed rows when the set is too small for the ladder or the ladder ends.  allowed[pid]: one flag per point, PointId order.
+    // 1 <= k <= ef_search; max_rungs: -1 the whole ladder, m its first m rungs, 0 the exact scan alone.  Exactly
+    // min(k, allowed points) items, nearest first; *rung (optional): the rung that answered, IDIST_RUNG_EXACT or IDIST_RUNG_NONE.
+    std::vector<Item<P>> search_allowed(const P& point, const std::vector<bool>& allowed, size_t k, Search& search, int32_t max_rungs = -1,
+                                        uint32_t* rung = nullptr) const {
+        if (allowed.size() != points_.size()) throw Error(IDIST_ERR_INVALID_ARG, "allowed needs one flag per point");
+        std::vector<uint32_t> bits((points_.size() + 31) / 32 + 1, 0u);
+        for (size_t i = 0; i < allowed.size(); i++)
+            if (allowed[i]) bits[i / 32] |= 1u << (i % 32);
+        std::vector<float> q(points_.empty() ? 1 : points_[0].dim());
+        point.write_f32(q.data());
+        std::vector<uint32_t> pid(k ? k : 1);
+        std::vector<float> dist(k ? k : 1);
+        uint32_t cnt = 0, r = IDIST_RUNG_NONE;
+        check(idist_search_batch_allowed(idx_, search.bind(idx_, uid_), q.data(), 1, bits.data(), (uint32_t)k, max_rungs, pid.data(),
+                                         dist.data(), &cnt, &r, nullptr));
+        if (rung) *rung = r;
+        search.pid_.assign(pid.begin(), pid.begin() + cnt);
+        search.dist_.assign(dist.begin(), dist.begin() + cnt);
+        std::vector<Item<P>> out;
+        for (size_t i = 0; i < search.pid_.size(); i++)
+            out.push_back(Item<P>{search.dist_[i], PointId{search.pid_[i]}, &points_[search.pid_[i]]});
+        return out;
+    }
     const P& operator[](PointId pid) const { return points_[pid.v]; }                                           // Index<PointId>
     size_t len() const { return points_.size(); }
     const std::vector<P>& points() const { return points_; }
@@ -268,6 +294,14 @@ public:
     std::vector<MapItem<P, V>> search(const P& point, Search& search) const {                                  // :154-162
         std::vector<MapItem<P, V>> out;
         for (auto& it : hnsw_.search(point, search)) out.push_back(MapItem<P, V>{it.distance, it.pid, it.point, &values[it.pid.v]});
+        return out;
+    }
+    // Hnsw::search_allowed with the values
+    std::vector<MapItem<P, V>> search_allowed(const P& point, const std::vector<bool>& allowed, size_t k, Search& search,
+                                              int32_t max_rungs = -1, uint32_t* rung = nullptr) const {
+        std::vector<MapItem<P, V>> out;
+        for (auto& it : hnsw_.search_allowed(point, allowed, k, search, max_rungs, rung))
+            out.push_back(MapItem<P, V>{it.distance, it.pid, it.point, &values[it.pid.v]});
         return out;
     }
     std::vector<V> values;

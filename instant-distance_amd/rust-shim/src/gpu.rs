@@ -70,6 +70,10 @@ extern "C" {
     fn idist_search_batch(idx: *const IdistIndex, ctx: *mut IdistSearchCtx, queries: *const f32, nq: u32,
                           out_pid: *mut u32, out_dist: *mut f32, out_count: *mut u32,
                           out_counters: *mut u32) -> i32;
+    // restricted search (include/idist.h): the k nearest among the points whose bit is set in allow_bits
+    fn idist_search_batch_allowed(idx: *const IdistIndex, ctx: *mut IdistSearchCtx, queries: *const f32, nq: u32,
+                                  allow_bits: *const u32, k: u32, max_rungs: i32, out_pid: *mut u32, out_dist: *mut f32,
+                                  out_count: *mut u32, out_rung: *mut u32, out_counters: *mut u32) -> i32;
     // several GPUs of one node: replicate once, shard the queries of a batch
     fn idist_replicate(root: *const IdistIndex, devices: *const i32, n_devices: u32, replicas: *mut *mut IdistIndex) -> i32;
     // the same as one RCCL broadcast per buffer (ncclCommInitAll over the devices, inside libidist)
@@ -279,6 +283,26 @@ impl Ctx {
         let mut cnt = vec![0u32; nq];
         expect(unsafe { idist_search_batch(g.idx, c, queries.as_ptr(), nq as u32, self.pid.as_mut_ptr(), self.dist.as_mut_ptr(), cnt.as_mut_ptr(), std::ptr::null_mut()) });
         (0..nq).map(|i| (0..cnt[i] as usize).map(|j| Candidate { distance: self.dist[i * ef + j].into(), pid: PointId(self.pid[i * ef + j]) }).collect()).collect()
+    }
+}
+
+/// `AllowedResult::rung`: nothing to find (no points, ef_search 0, an empty allowed set) / answered by the exact scan of the allowed rows.
+pub const RUNG_NONE: u32 = 254;
+pub const RUNG_EXACT: u32 = 255;
+
+impl Ctx {
+    /// Additive API (`Hnsw::search_allowed`): the k nearest among the allowed points for every query of a slice.  `allow_bits`:
+    /// (n + 31) / 32 words, point `pid` is allowed iff bit `pid % 32` of word `pid / 32` is set; 1 <= k <= ef_search; `max_rungs`:
+    /// -1 the whole ef ladder, m its first m rungs, 0 the exact scan alone.  Row i holds exactly min(k, allowed points) candidates,
+    /// nearest first, and the rung that answered (`RUNG_EXACT`, `RUNG_NONE`).
+    pub(crate) fn search_allowed(&mut self, g: &GpuIndex, queries: &[f32], allow_bits: &[u32], k: usize, max_rungs: i32) -> Vec<(Vec<Candidate>, u32)> {
+        let nq = queries.len() / g.dim;
+        let c = self.bind(g, 0);
+        self.pid.resize(nq * k.max(1), 0);
+        self.dist.resize(nq * k.max(1), 0.0);
+        let (mut cnt, mut rung) = (vec![0u32; nq], vec![RUNG_NONE; nq]);
+        expect(unsafe { idist_search_batch_allowed(g.idx, c, queries.as_ptr(), nq as u32, allow_bits.as_ptr(), k as u32, max_rungs, self.pid.as_mut_ptr(), self.dist.as_mut_ptr(), cnt.as_mut_ptr(), rung.as_mut_ptr(), std::ptr::null_mut()) });
+        (0..nq).map(|i| ((0..cnt[i] as usize).map(|j| Candidate { distance: self.dist[i * k + j].into(), pid: PointId(self.pid[i * k + j]) }).collect(), rung[i])).collect()
     }
 }
 
