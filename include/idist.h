@@ -392,7 +392,7 @@ idist_status idist_partitioned_last_search_kernel_ms(idist_partitioned* p, float
 /* DEFINED through what is already exact: Hnsw::search (core/lib.rs:352-383) at growing ef_search, filtered, and an exact scan of the
  * allowed rows below a derivable selectivity and when the ladder ends.  The walk itself is not touched.
  *   A          the allowed set, a bitmap of (n + 31) / 32 u32 words: point `pid` is allowed iff bit pid % 32 of word pid / 32 is set;
- *              bits at positions >= n are ignored.  One set per call, shared by the batch.
+ *              bits at positions >= n are ignored.  One set per call, shared by the batch (several: idist_search_batch_allowed_sets).
  *   k          1 <= k <= ef_search of the index.
  *   ladder     E[0] = ef_search, E[r + 1] = min(4 * E[r], IDIST_MAX_EF); it ends with the rung that equals IDIST_MAX_EF
  *              (ef_search = 100: 100, 400, 1600, 4096).
@@ -419,7 +419,8 @@ idist_status idist_partitioned_last_search_kernel_ms(idist_partitioned* p, float
  * 8 * E[r] bytes per query still pending.
  * Cost: a query that climbs the whole ladder costs about 1.3 searches at ef_search 4096 (the rungs below add a quarter, a
  * sixteenth, ...) plus a scan of A; max_rungs is the caller's bound.
- * Out of scope: one set per query, device-pointer / stream variants, the partitioned index and idist_search_batch_sharded. */
+ * Out of scope: device-pointer / stream variants, the partitioned index and idist_search_batch_sharded.  Several sets in one call:
+ * idist_search_batch_allowed_sets below. */
 #define IDIST_RUNG_NONE  254u
 #define IDIST_RUNG_EXACT 255u
 idist_status idist_search_batch_allowed(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
@@ -427,9 +428,36 @@ idist_status idist_search_batch_allowed(const idist_index* idx, idist_search_ctx
                                         uint32_t* out_pid, float* out_dist,      /* nq*k */
                                         uint32_t* out_count, uint32_t* out_rung, /* nq; out_rung may be NULL */
                                         uint32_t* out_counters);                 /* nq*3 or NULL */
-/* HIP-event durations (ms) of the kernels the last idist_search_batch_allowed through ctx ran around its searches, summed over its
- * rungs: the select passes, the pending-list passes, the exact step (scan + merge).  0 with IDIST_KERNEL_EVENTS=0.  The rungs' own
- * search kernels are in idist_search_ctx_kernel_times. */
+/* Several allowed sets per call, one per query: tenants, ACL groups, categories and date ranges mixed in one batch.
+ *   allow_bits  n_sets bitmaps of (n + 31) / 32 words each, one after the other, each as in idist_search_batch_allowed; bits at
+ *               positions >= n of every set are ignored.  The buffer is neither written nor copied on the host to clean it.
+ *   n_sets      >= 1.
+ *   set_of      [nq]: query q is restricted to set set_of[q] (< n_sets).  NULL: query q uses set q, and n_sets must equal nq.
+ * DEFINITION: row q of every output is row 0 of
+ *   idist_search_batch_allowed(idx, ctx, &queries[q * dim], 1, allow_bits + set_of[q] * ((n + 31) / 32), k, max_rungs, ...)
+ * — ids, order, distance bits, count, rung and counters.  Nothing else is new: the ladder, the start rule, the exact step, the
+ * metric's report on the final [nq][k] result, the padding, the strict-tie retry and max_rungs are the single-set call's.  Every
+ * query evaluates the start rule E[r] * |A| >= k * n with its own set's size, so the queries of one call may start on different
+ * rungs: a query waits, unlaunched, until its start rung comes up, and its counters sum only the rungs it ran.  A later rung that
+ * does not fit a wave's LDS ends the ladder for every query still waiting or pending (they are answered exactly); the same failure
+ * on rung 0 is returned.  The call fails whenever one of those single-set calls would fail.
+ * IDIST_ERR_INVALID_ARG: n_sets == 0; set_of == NULL with n_sets != nq; a set_of[q] >= n_sets (the message names q); k out of range,
+ * max_rungs < -1, null pointers.
+ * The sets' sizes and start rungs are counted on the device; the exact step reads the bitmaps themselves (no id list is made, the
+ * staging does not grow with n_sets beyond the n_sets * ((n + 31) / 32) * 4 bytes of the bitmaps): n / 8 bytes of bitmap per
+ * (pending query, call) on top of the allowed rows.
+ * Host pointers; blocks until done; ctx is the `&mut Search`, idx is never mutated — as the single-set call.
+ * Out of scope: device-pointer / stream variants, the partitioned index and idist_search_batch_sharded. */
+idist_status idist_search_batch_allowed_sets(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
+                                             const uint32_t* allow_bits,              /* [n_sets][(n + 31) / 32] */
+                                             uint32_t n_sets, const uint32_t* set_of, /* [nq] or NULL */
+                                             uint32_t k, int32_t max_rungs,
+                                             uint32_t* out_pid, float* out_dist,      /* nq*k */
+                                             uint32_t* out_count, uint32_t* out_rung, /* nq; out_rung may be NULL */
+                                             uint32_t* out_counters);                 /* nq*3 or NULL */
+/* HIP-event durations (ms) of the kernels the last idist_search_batch_allowed / idist_search_batch_allowed_sets through ctx ran
+ * around its searches, summed over its rungs: the select passes (and the several-sets call's count pass), the pending-list passes,
+ * the exact step (scan + merge).  0 with IDIST_KERNEL_EVENTS=0.  The rungs' own search kernels are in idist_search_ctx_kernel_times. */
 idist_status idist_search_ctx_allowed_kernel_ms(idist_search_ctx* ctx, float* select_ms, float* pending_ms, float* exact_ms);
 
 /* Point::distance for id lists (core/lib.rs:780-782 as used at :709-710): out[q][i] =

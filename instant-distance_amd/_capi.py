@@ -140,6 +140,8 @@ SYMBOLS = {
     "idist_partitioned_last_search_kernel_ms": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p]),
     "idist_search_batch_allowed": (C.c_int32, [_vp, _vp, _f32p, C.c_uint32, _u32p, C.c_uint32, C.c_int32, _u32p, _f32p, _u32p, _u32p,
                                                _u32p]),
+    "idist_search_batch_allowed_sets": (C.c_int32, [_vp, _vp, _f32p, C.c_uint32, _u32p, C.c_uint32, _u32p, C.c_uint32, C.c_int32, _u32p,
+                                                    _f32p, _u32p, _u32p, _u32p]),
     "idist_search_ctx_allowed_kernel_ms": (C.c_int32, [_vp, _f32p, _f32p, _f32p]),
     "idist_distance_batch": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, _f32p]),
     "idist_filter_bound_batch": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, _f32p]),

@@ -361,6 +361,26 @@ def allowed_bitmap(allowed, n: int) -> np.ndarray:
     return np.ascontiguousarray(np.packbits(padded, bitorder="little").view("<u4").astype(np.uint32))
 
 
+def allowed_bitmaps(sets, n: int) -> np.ndarray:
+    """The allowed sets of `search_allowed_sets` as the ABI takes them: uint32 [n_sets][(n + 31) // 32].  `sets`: a ready bitmap of that
+    shape and dtype, a 2-D bool array [n_sets][n], or a sequence whose entries follow `allowed_bitmap`'s rules (bool masks of length
+    n, integer arrays of PointIds)."""
+    words = (n + 31) // 32
+    if isinstance(sets, np.ndarray) and sets.ndim == 2 and sets.dtype == np.uint32:
+        if sets.shape[1] != words:
+            raise ValueError(f"a uint32 `sets` is a bitmap of shape (n_sets, {words}), got {sets.shape}")
+        return np.ascontiguousarray(sets)
+    if isinstance(sets, np.ndarray) and sets.dtype == np.bool_:
+        if sets.ndim != 2 or sets.shape[1] != n:
+            raise ValueError(f"a bool `sets` must have one row per set and one entry per point: shape (n_sets, {n}), got {sets.shape}")
+    elif isinstance(sets, np.ndarray) and sets.ndim != 2 and sets.dtype != object:
+        raise ValueError("`sets` is a sequence of sets, a 2-D bool array or a uint32 bitmap [n_sets][words]")
+    out = np.zeros((len(sets), words), dtype=np.uint32)
+    for i, a in enumerate(sets):
+        out[i] = allowed_bitmap(a, n)
+    return out
+
+
 def normalize(points, device: int = 0, return_norm2: bool = False):
     """x / sqrt(s(x)) per row, s = the canonical squared-L2 distance of the row to the origin (idist_normalize_batch): the rows a
     METRIC_COSINE index holds for `points`, bit for bit — an METRIC_L2SQ index over `normalize(points)` searched with
@@ -560,6 +580,46 @@ class Hnsw:
                                              _capi.f32p(dist), _capi.u32p(cnt), _capi.u32p(rung), _capi.u32p(ctr) if counters else None))
         return AllowedResult(pid, dist, cnt, rung, ctr)
 
+    def search_allowed_sets(self, queries, sets, set_of, k: int, search: Search, max_rungs: int = -1, counters: bool = False) -> AllowedResult:
+        """`search_allowed` with several allowed sets in one call, one per query (idist_search_batch_allowed_sets): row q is exactly
+        what `search_allowed(queries[q], sets[set_of[q]], k, ...)` returns.  `sets`: a sequence of bool masks or of PointId arrays
+        (`allowed_bitmap`'s rules), a 2-D bool array [n_sets][n] or a ready uint32 bitmap [n_sets][(n + 31) // 32].  `set_of`: the set
+        index of every query; None: query q uses set q (one set per query).  Queries start on the rung their own set's size calls
+        for; the exact step reads n / 8 bytes of its set's bitmap per query on top of the allowed rows."""
+        q = _as_points(queries)
+        info = self.info()
+        if q.shape[0] and info.n and q.shape[1] != info.dim:
+            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
+        bits = allowed_bitmaps(sets, int(info.n))
+        nq, k, n_sets = q.shape[0], int(k), bits.shape[0]
+        if set_of is None:
+            if n_sets != nq:
+                raise ValueError(f"set_of=None means one set per query: {n_sets} sets for {nq} queries")
+            so = None
+        else:
+            so = np.asarray(set_of)
+            if so.size and not np.issubdtype(so.dtype, np.integer):
+                raise TypeError("`set_of` is an integer array of set indices, one per query")
+            if so.shape != (nq,):
+                raise ValueError(f"`set_of` must have one entry per query: shape ({nq},), got {so.shape}")
+            if so.size and (so.min() < 0 or so.max() >= n_sets):
+                raise IndexError(f"`set_of` names a set outside [0, {n_sets})")
+            so = np.ascontiguousarray(so.astype(np.uint32))
+        kk = max(k, 0)
+        pid = np.full((nq, kk), INVALID, dtype=np.uint32)
+        dist = np.full((nq, kk), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        rung = np.full(nq, RUNG_NONE, dtype=np.uint32)
+        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
+        if n_sets == 0 and nq == 0:
+            return AllowedResult(pid, dist, cnt, rung, ctr)
+        ctx = search._bind(self)
+        L = _lib()
+        L.check(L.idist_search_batch_allowed_sets(self._h, ctx, _capi.f32p(q), nq, _capi.u32p(bits), n_sets, _capi.u32p(so) if so is not None else None,
+                                                  kk, int(max_rungs), _capi.u32p(pid), _capi.f32p(dist), _capi.u32p(cnt), _capi.u32p(rung),
+                                                  _capi.u32p(ctr) if counters else None))
+        return AllowedResult(pid, dist, cnt, rung, ctr)
+
     def search_batch_device(self, search: Search, d_queries: int, nq: int, d_pid: int, d_dist: int, d_count: int,
                             d_counters: int = 0, stream: int = 0):
         """Device-pointer variant: inputs/outputs stay in HBM, enqueued on `stream` without a sync."""
@@ -677,6 +737,12 @@ class HnswMap:
     def search_allowed(self, queries, allowed, k: int, search: Search, max_rungs: int = -1) -> list[list[MapItem]]:
         """`Hnsw.search_allowed` with the values: per query its min(k, allowed points) results as `MapItem`s, nearest first."""
         r = self.hnsw.search_allowed(queries, allowed, k, search, max_rungs)
+        return [[MapItem(float(r.distance[i, j]), int(r.pid[i, j]), self.hnsw.points[int(r.pid[i, j])], self.values[int(r.pid[i, j])])
+                 for j in range(int(r.count[i]))] for i in range(r.pid.shape[0])]
+
+    def search_allowed_sets(self, queries, sets, set_of, k: int, search: Search, max_rungs: int = -1) -> list[list[MapItem]]:
+        """`Hnsw.search_allowed_sets` with the values: per query its min(k, points of its set) results as `MapItem`s, nearest first."""
+        r = self.hnsw.search_allowed_sets(queries, sets, set_of, k, search, max_rungs)
         return [[MapItem(float(r.distance[i, j]), int(r.pid[i, j]), self.hnsw.points[int(r.pid[i, j])], self.values[int(r.pid[i, j])])
                  for j in range(int(r.count[i]))] for i in range(r.pid.shape[0])]
 

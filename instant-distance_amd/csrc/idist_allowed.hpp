@@ -18,6 +18,23 @@
 //                           contiguous segment of the ascending id list of A per wave; grid = pending queries x S segments.  Each
 //                           wave writes its segment's sorted top-k as list s in merge_topk_kernel's input layout (base 0): the
 //                           merge by (distance bits, id) gives the k best, and ids are distinct, so the result does not depend on S.
+//
+// Several allowed sets per call, one per query (idist_search_batch_allowed_sets): row q is what the single-set call returns for
+// query q alone with its own set, so the same kernels serve, told which bitmap a query reads:
+//
+//   allowed_count_kernel      one wave per set: popcount of its words (the last partial word masked), then the start rule
+//                             E[r] * |A| >= k * n in 64-bit integers -> start[s]: a rung index, kRungExact (|A| <= k, or no permitted
+//                             rung qualifies) or kRungNone (the empty set).  No atomics.
+//   allowed_init_kernel       with a start table: first[q] = start[set of q]; a query whose set is empty is closed at once.
+//   allowed_select_kernel     with set_of: the row is filtered by the bitmap of the query's own set.
+//   allowed_pending_kernel    with first / rung: a query is gathered iff it is pending and first[q] <= rung — a query waits,
+//                             unlaunched, until its start rung comes up; rung = kRungExact gathers everything still pending.
+//   allowed_scan_bits_kernel  the exact step straight from the bitmap: grid = pending queries x S segments of the 64-id windows of
+//                             [0, n).  A wave takes 64 windows at a time (one 64-bit load per lane), skips the all-zero ones by a
+//                             ballot, and compacts the set bits of the others into ascending ids by prefix popcount, in batches of
+//                             64 in act_pid; an id that does not fit the batch stays in its lane's register until the batch has been
+//                             ranked and opens the next one.  Everything after that is allowed_scan_kernel's.  No id list exists,
+//                             on the host or the device; the staging does not depend on the number of sets.
 #pragma once
 #include "idist_kernels.hpp"
 #include "idist_merge.hpp"
@@ -41,7 +58,10 @@ struct AllowedOut {
     uint32_t nq, k;
 };
 
-__global__ void allowed_init_kernel(AllowedOut o) {
+// start [n_sets] / set_of [nq] / first [nq]: the several-sets call (start == nullptr: one set, every query pending).  first[q] =
+// start[set_of[q]]: the first rung query q runs, kRungExact, or kRungNone — the query is then closed here, with count 0.
+__global__ void allowed_init_kernel(AllowedOut o, const uint32_t* __restrict__ start = nullptr, const uint32_t* __restrict__ set_of = nullptr,
+                                    uint32_t* __restrict__ first = nullptr) {
     const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (size_t)gridDim.x * blockDim.x;
     const size_t total = (size_t)o.nq * o.k;
     for (size_t i = tid; i < total; i += nth) {
@@ -51,23 +71,32 @@ __global__ void allowed_init_kernel(AllowedOut o) {
     for (size_t q = tid; q < o.nq; q += nth) {
         o.count[q] = 0u;
         o.rung[q] = kRungNone;
-        o.pending[q] = 1u;
+        uint32_t f = 0u;
+        if (start) {
+            f = start[set_of[q]];
+            first[q] = f;
+        }
+        o.pending[q] = f == kRungNone ? 0u : 1u;
         if (o.counters) { o.counters[3 * q] = 0u; o.counters[3 * q + 1] = 0u; o.counters[3 * q + 2] = 0u; }
     }
 }
 
 // r_pid / r_dist: [np][width] result rows of the np pending queries, r_count [np], r_counters [np][3] or nullptr.  list [np]: the
 // original query index of every row (nullptr: the identity).  rung: what a query answered here reports.  exact != 0: the rows are
-// the merged scan of A — written, padded and closed whatever their count.
+// the merged scan of A — written, padded and closed whatever their count.  set_of [nq] (nullptr: one set): query q reads the bitmap
+// at bits + set_of[q] * words.
 __global__ __launch_bounds__(64) void allowed_select_kernel(AllowedOut o, const uint32_t* __restrict__ bits, uint32_t n,
                                                             const uint32_t* __restrict__ r_pid, const uint32_t* __restrict__ r_dist,
                                                             const uint32_t* __restrict__ r_count, const uint32_t* __restrict__ r_counters,
                                                             uint32_t width, const uint32_t* __restrict__ list, uint32_t np,
-                                                            uint32_t rung, uint32_t exact) {
+                                                            uint32_t rung, uint32_t exact,
+                                                            const uint32_t* __restrict__ set_of = nullptr, uint32_t words = 0) {
     const int lane = lane_id();
     const uint64_t below = (1ull << lane) - 1ull;
+    const uint32_t* const all_bits = bits;
     for (uint32_t p = blockIdx.x; p < np; p += gridDim.x) {
         const uint32_t q = list ? list[p] : p;
+        if (set_of) bits = all_bits + (size_t)set_of[q] * words;
         uint32_t cnt = r_count[p];
         cnt = cnt < width ? cnt : width;
         const uint32_t* row_pid = r_pid + (size_t)p * width;
@@ -106,17 +135,19 @@ __global__ __launch_bounds__(64) void allowed_select_kernel(AllowedOut o, const 
 
 // pending [nq] -> list: the pending query indices, ascending; pend_q [np][kdim]: their rows of `queries` [nq][kdim]; *n_pending = np.
 // grid = ceil(nq / 64) waves EXACTLY: wave b owns the queries [64 b, 64 b + 64) and the last one writes the total.
+// first [nq] (nullptr: every pending query is gathered): only the pending queries with first[q] <= rung are — the others wait.
 __global__ __launch_bounds__(64) void allowed_pending_kernel(const uint32_t* __restrict__ pending, uint32_t nq,
                                                              const float* __restrict__ queries, uint32_t kdim,
                                                              uint32_t* __restrict__ list, float* __restrict__ pend_q,
-                                                             uint32_t* __restrict__ n_pending) {
+                                                             uint32_t* __restrict__ n_pending,
+                                                             const uint32_t* __restrict__ first_rung = nullptr, uint32_t rung = 0) {
     const int lane = lane_id();
     const uint32_t first = blockIdx.x * 64u;
     uint32_t before = 0;
-    for (uint32_t i = (uint32_t)lane; i < first; i += 64u) before += pending[i] ? 1u : 0u;
+    for (uint32_t i = (uint32_t)lane; i < first; i += 64u) before += pending[i] && (!first_rung || first_rung[i] <= rung) ? 1u : 0u;
     before = wave_sum_u32(before);
     const uint32_t q = first + (uint32_t)lane;
-    const bool on = q < nq && pending[q] != 0u;
+    const bool on = q < nq && pending[q] != 0u && (!first_rung || first_rung[q] <= rung);
     const uint64_t m = __ballot(on);
     if (on) list[before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = q;
     uint64_t rest = m;
@@ -177,6 +208,133 @@ __global__ __launch_bounds__(64) void allowed_scan_kernel(IndexView ix, const fl
             if (st.plen > st.ef) st.plen = st.ef;   // plain truncate (no candidates here)
             wave_sync();
         }
+        const size_t row = ((size_t)s * np + p) * k;
+        for (uint32_t i = lane; i < (uint32_t)st.plen; i += 64) {
+            out_pid[row + i] = (uint32_t)st.W[i];
+            out_dist[row + i] = (uint32_t)((st.W[i] & kKeyMask) >> 32);
+        }
+        if (lane == 0) out_count[(size_t)s * np + p] = (uint32_t)st.plen;
+    }
+}
+
+// ---- several sets per call ----------------------------------------------------------------------------------------------------
+
+struct AllowedLadder {
+    uint32_t E[8];        // ef_search of the permitted rungs
+    uint32_t n_rungs;     // (max_rungs applied)
+};
+
+// bits [n_sets][words] -> size [n_sets] = |A_s| (bits at positions >= n not counted), start [n_sets]: the first permitted rung r
+// with E[r] |A_s| >= k n (64-bit), kRungExact when |A_s| <= k or no rung qualifies, kRungNone for the empty set.  One wave per set
+// (the grid strides over the rest): a sum of popcounts, the same whatever the schedule.
+__global__ __launch_bounds__(64) void allowed_count_kernel(const uint32_t* __restrict__ bits, uint32_t n, uint32_t words, uint32_t n_sets,
+                                                           uint32_t k, AllowedLadder lad, uint32_t* __restrict__ size,
+                                                           uint32_t* __restrict__ start) {
+    const int lane = lane_id();
+    const uint32_t last_mask = n % 32u ? (1u << (n % 32u)) - 1u : 0xFFFFFFFFu;
+    for (uint32_t s = blockIdx.x; s < n_sets; s += gridDim.x) {
+        const uint32_t* b = bits + (size_t)s * words;
+        uint32_t c = 0;
+        for (uint32_t w = (uint32_t)lane; w < words; w += 64u) {
+            const uint32_t v = b[w] & (w + 1u == words ? last_mask : 0xFFFFFFFFu);
+            c += (uint32_t)__popcll((uint64_t)v);
+        }
+        c = wave_sum_u32(c);                                  // <= n
+        uint32_t r0 = kRungExact;
+        if (c == 0u) r0 = kRungNone;
+        else if (c > k)
+            for (uint32_t r = 0; r < lad.n_rungs && r0 == kRungExact; r++)
+                if ((uint64_t)lad.E[r] * c >= (uint64_t)k * n) r0 = r;
+        if (lane == 0) {
+            size[s] = c;
+            start[s] = r0;
+        }
+    }
+}
+
+// The 64-bit window `win` (ids [64 win, 64 win + 64)) of a bitmap of `words` u32 words over n points, bits at positions >= n cleared.
+__device__ __forceinline__ uint64_t allowed_window(const uint32_t* __restrict__ bits, uint32_t n, uint32_t words, uint32_t win) {
+    const uint32_t w0 = 2u * win;
+    uint64_t m = 0;
+    if (w0 < words) m = bits[w0];
+    if (w0 + 1u < words) m |= (uint64_t)bits[w0 + 1u] << 32;
+    const uint64_t lo = 64ull * win;
+    if (lo + 64u > n) m = lo >= n ? 0ull : m & ((1ull << (n - lo)) - 1ull);
+    return m;
+}
+
+// One batch of the exact step: the na ids in act_pid measured and ranked into the wave's top-k (allowed_scan_kernel's loop body).
+template <int NB, int RS, int TAIL>
+__device__ __forceinline__ void allowed_rank_batch(const IndexView& ix, const Smem& sm, WState& st, int na) {
+    const int lane = lane_id();
+    wave_sync();
+    dist_rounds<NB, RS, TAIL>(ix, sm.q, sm.act_pid, sm.act_dist, na);
+    wave_sync();
+    uint64_t key = kMaxKey;
+    if (lane < na) key = ((uint64_t)sm.act_dist[lane] << 32) | sm.act_pid[lane];
+    const uint64_t thr = st.plen >= st.ef ? (st.W[st.ef - 1] & kKeyMask) : kMaxKey + 1ull;
+    uint64_t pm = __ballot(lane < na && key < thr);
+    while (pm) {
+        const int i = __builtin_ctzll(pm);
+        pm &= pm - 1ull;
+        const uint64_t kk = bcast_u64(key, i);
+        const int idx = w_rank(st, kk);
+        if (idx < st.ef) w_insert(st, idx, kk);
+    }
+    if (st.plen > st.ef) st.plen = st.ef;   // plain truncate (no candidates here)
+    wave_sync();
+}
+
+// The exact step of the several-sets call, straight from the bitmaps.  bits [n_sets][words]; list [np] (nullptr: the identity): the
+// original query index of pending row p, set_of [nq]: its set.  The n_win = ceil(n / 64) windows of [0, n) are cut into S contiguous
+// segments [n_win s / S, n_win (s + 1) / S) (an empty one yields an empty list).  Work item w = p * S + s; the outputs as
+// allowed_scan_kernel's.  Ids reach act_pid ascending and are distinct, so the result depends neither on S nor on the batches.
+template <int NB, int RS, int TAIL>
+__global__ __launch_bounds__(64) void allowed_scan_bits_kernel(IndexView ix, const float* __restrict__ queries, uint32_t np,
+                                                               const uint32_t* __restrict__ bits, uint32_t n, uint32_t words,
+                                                               const uint32_t* __restrict__ list, const uint32_t* __restrict__ set_of,
+                                                               uint32_t S, uint32_t k, uint32_t wcap, uint32_t* out_pid,
+                                                               uint32_t* out_dist, uint32_t* out_count) {
+    IDIST_DYN_SMEM(smem_raw);
+    const Smem sm = carve(smem_raw, ix.stride, wcap, false);
+    const int lane = lane_id();
+    const uint64_t below = (1ull << lane) - 1ull;
+    const uint32_t nb = NB >= 0 ? (uint32_t)NB : ix.nb;
+    const uint32_t n_win = (uint32_t)(((uint64_t)n + 63u) / 64u);
+    const uint64_t items = (uint64_t)np * S;
+    for (uint64_t w = blockIdx.x; w < items; w += gridDim.x) {
+        const uint32_t p = (uint32_t)(w / S), s = (uint32_t)(w % S);
+        const uint32_t lo = (uint32_t)((uint64_t)n_win * s / S), hi = (uint32_t)((uint64_t)n_win * (s + 1u) / S);
+        const uint32_t* b = bits + (size_t)set_of[list ? list[p] : p] * words;
+        wave_sync();
+        for (uint32_t o = lane; o < ix.stride; o += 64) sm.q[o] = 0.0f;
+        wave_sync();
+        for (uint32_t e = lane; e < ix.dim; e += 64) sm.q[blocked_pos(e, nb)] = queries[(size_t)p * ix.dim + e];
+        wave_sync();
+        WState st{sm.W, 0, (int)k, 0, 0u};
+        uint32_t fill = 0;                                    // ids waiting in act_pid, < 64 between windows
+        for (uint32_t g = lo; g < hi; g += 64u) {
+            const uint32_t mine = g + (uint32_t)lane;         // lane j holds window g + j
+            const uint64_t win = mine < hi ? allowed_window(b, n, words, mine) : 0ull;
+            uint64_t nz = __ballot(win != 0ull);
+            while (nz) {
+                const int j = __builtin_ctzll(nz);
+                nz &= nz - 1ull;
+                // (j comes from a ballot: wave-uniform, so the window travels through scalar registers and `fill` stays uniform)
+                const uint64_t m = ((uint64_t)readlane_u32((uint32_t)(win >> 32), j) << 32) | readlane_u32((uint32_t)win, j);
+                const bool ok = ((m >> lane) & 1ull) != 0ull;
+                const uint32_t id = (g + (uint32_t)j) * 64u + (uint32_t)lane;
+                const uint32_t pos = fill + (uint32_t)__popcll(m & below);
+                if (ok && pos < 64u) sm.act_pid[pos] = id;
+                fill += (uint32_t)__popcll(m);
+                if (fill >= 64u) {
+                    allowed_rank_batch<NB, RS, TAIL>(ix, sm, st, 64);
+                    if (ok && pos >= 64u) sm.act_pid[pos - 64u] = id;     // carried over in the lane's register
+                    fill -= 64u;
+                }
+            }
+        }
+        if (fill) allowed_rank_batch<NB, RS, TAIL>(ix, sm, st, (int)fill);
         const size_t row = ((size_t)s * np + p) * k;
         for (uint32_t i = lane; i < (uint32_t)st.plen; i += 64) {
             out_pid[row + i] = (uint32_t)st.W[i];

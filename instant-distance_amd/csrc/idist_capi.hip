@@ -385,8 +385,12 @@ struct idist_search_ctx {
         size_t cap = 0;
         template <typename T> T* as() const { return static_cast<T*>(p); }
     };
+    // idist_search_batch_allowed_sets adds: every set's bitmap in al_bits, the set of every query, |A_s| and the start rung per set,
+    // the first rung per query.
     Buf al_bits, al_ids, al_flag, al_list, al_npend, al_pq, al_opid, al_odist, al_ocnt, al_orung, al_octr, al_mpid, al_mdist, al_mcnt;
-    static constexpr uint32_t kAllowedEvents = 40;   // a pair per select / pending pass of at most seven rungs + the exact step's two
+    Buf al_setof, al_size, al_start, al_first;
+    static constexpr uint32_t kAllowedEvents = 64;   // a pair per select / pending pass of at most seven rungs + the exact step's two;
+                                                     // the several-sets call: + its count pass and a pending pass in front of every launch
     hipEvent_t al_ev[kAllowedEvents] = {nullptr};    // (created on first use, resolved when the call has synchronised its stream)
     uint8_t al_ev_which[kAllowedEvents / 2] = {0};
     uint32_t al_ev_used = 0;
@@ -2027,7 +2031,8 @@ void idist_search_ctx_free(idist_search_ctx* c) {
     hipFree(c->d_cnt);
     hipFree(c->d_ctr);
     for (idist_search_ctx::Buf* b : {&c->al_bits, &c->al_ids, &c->al_flag, &c->al_list, &c->al_npend, &c->al_pq, &c->al_opid, &c->al_odist,
-                                     &c->al_ocnt, &c->al_orung, &c->al_octr, &c->al_mpid, &c->al_mdist, &c->al_mcnt})
+                                     &c->al_ocnt, &c->al_orung, &c->al_octr, &c->al_mpid, &c->al_mdist, &c->al_mcnt, &c->al_setof, &c->al_size,
+                                     &c->al_start, &c->al_first})
         hipFree(b->p);
     for (hipEvent_t e : c->al_ev)
         if (e) hipEventDestroy(e);
@@ -3106,11 +3111,12 @@ idist_status allowed_times_resolve(idist_search_ctx* ctx) {
 
 idist_status allowed_select(idist_search_ctx* ctx, const AllowedOut& o, uint32_t n, const uint32_t* r_pid, const float* r_dist,
                             const uint32_t* r_cnt, const uint32_t* r_ctr, uint32_t width, const uint32_t* list, uint32_t np,
-                            uint32_t rung, bool exact) {
+                            uint32_t rung, bool exact, const uint32_t* set_of = nullptr, uint32_t words = 0) {
     auto select_pass = [&]() -> idist_status {
         const uint32_t grid = std::min<uint32_t>(np, 65536u);                 // one wave per pending query; the kernel strides over the rest
         IDIST_LAUNCH(allowed_select_kernel, grid, 64, 0, ctx->stream, o, ctx->al_bits.as<uint32_t>(), n, r_pid,
-                     reinterpret_cast<const uint32_t*>(r_dist), r_cnt, r_ctr, width, list, np, rung, exact ? 1u : 0u);
+                     reinterpret_cast<const uint32_t*>(r_dist), r_cnt, r_ctr, width, list, np, rung, exact ? 1u : 0u, set_of,
+                     words);
         HIPCHK(hipGetLastError());
         return IDIST_OK;
     };
@@ -3282,6 +3288,227 @@ idist_status idist_search_batch_allowed(const idist_index* idx, idist_search_ctx
         CHK(allowed_timed(ctx, 2, scan_and_merge));
         CHK(allowed_select(ctx, o, n, ctx->al_mpid.as<uint32_t>(), ctx->al_mdist.as<float>(), ctx->al_mcnt.as<uint32_t>(), nullptr, k,
                            d_list, np, IDIST_RUNG_EXACT, true));
+    }
+    CHK(metric.report(ctx->al_odist.as<float>(), ctx->d_sq, nq, k, stream));
+    HIPCHK(hipMemcpyAsync(out_pid, ctx->al_opid.p, ob, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(out_dist, ctx->al_odist.p, ob, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(out_count, ctx->al_ocnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, stream));
+    if (out_rung) HIPCHK(hipMemcpyAsync(out_rung, ctx->al_orung.p, (size_t)nq * 4, hipMemcpyDeviceToHost, stream));
+    if (counters) HIPCHK(hipMemcpyAsync(out_counters, ctx->al_octr.p, (size_t)nq * 12, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    return allowed_times_resolve(ctx);
+}
+
+idist_status idist_search_batch_allowed_sets(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
+                                             const uint32_t* allow_bits, uint32_t n_sets, const uint32_t* set_of, uint32_t k,
+                                             int32_t max_rungs, uint32_t* out_pid, float* out_dist, uint32_t* out_count,
+                                             uint32_t* out_rung, uint32_t* out_counters) {
+    CHK(check_ctx(idx, ctx));
+    const uint32_t n = idx->n, ef0 = idx->cfg.ef_search;
+    if (max_rungs < -1) return fail(IDIST_ERR_INVALID_ARG, "max_rungs %d: -1 (the whole ladder) or a number of rungs >= 0", max_rungs);
+    if (k == 0 || k > IDIST_MAX_EF) return fail(IDIST_ERR_INVALID_ARG, "k %u out of [1,%u]", k, IDIST_MAX_EF);
+    if (ef0 != 0 && k > ef0) return fail(IDIST_ERR_INVALID_ARG, "k %u > ef_search %u", k, ef0);
+    if (n_sets == 0) return fail(IDIST_ERR_INVALID_ARG, "n_sets 0: at least one allowed set");
+    if (nq == 0) return IDIST_OK;
+    if (!set_of && n_sets != nq) return fail(IDIST_ERR_INVALID_ARG, "set_of is null (query q uses set q) but n_sets %u != nq %u", n_sets, nq);
+    if (!queries || !out_pid || !out_dist || !out_count || (n && !allow_bits)) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    if (set_of)
+        for (uint32_t q = 0; q < nq; q++)
+            if (set_of[q] >= n_sets) return fail(IDIST_ERR_INVALID_ARG, "set_of[%u] = %u: query %u names a set outside [0,%u)", q, set_of[q], q, n_sets);
+    const size_t ob = (size_t)nq * k * 4;
+    if (n == 0 || ef0 == 0) {                                                // step 1: nothing to find, whatever the sets
+        for (size_t i = 0; i < (size_t)nq * k; i++) { out_pid[i] = IDIST_INVALID; out_dist[i] = INFINITY; }
+        memset(out_count, 0, (size_t)nq * 4);
+        if (out_rung) std::fill(out_rung, out_rung + nq, (uint32_t)IDIST_RUNG_NONE);
+        if (out_counters) memset(out_counters, 0, (size_t)nq * 12);
+        return IDIST_OK;
+    }
+    // the permitted rungs, as idist_search_batch_allowed has them; every set's size and start rung come from the device
+    const uint32_t words = (n + 31u) / 32u;
+    AllowedLadder lad{};
+    for (uint32_t e = ef0;; e = std::min<uint32_t>(4u * e, IDIST_MAX_EF)) {
+        lad.E[lad.n_rungs++] = e;
+        if (e >= IDIST_MAX_EF) break;
+    }
+    if (max_rungs >= 0) lad.n_rungs = std::min<uint32_t>(lad.n_rungs, (uint32_t)max_rungs);
+    const uint32_t n_rungs = lad.n_rungs;
+
+    HIPCHK(hipSetDevice(idx->device));
+    hipStream_t stream = ctx->stream;
+    const MetricPasses metric(idx);
+    const uint32_t kdim = idx->kdim;
+    const size_t qb = (size_t)nq * idx->dim * 4, bb = (size_t)n_sets * words * 4;
+    const bool counters = out_counters != nullptr;
+    ctx->al_ms[0] = ctx->al_ms[1] = ctx->al_ms[2] = 0.0f;
+    ctx->al_ev_used = 0;
+    CHK(grow(ctx->d_q, ctx->cap_q, qb));
+    CHK(grow(ctx->al_bits.p, ctx->al_bits.cap, bb));
+    CHK(grow(ctx->al_setof.p, ctx->al_setof.cap, (size_t)nq * 4));
+    CHK(grow(ctx->al_size.p, ctx->al_size.cap, (size_t)n_sets * 4));
+    CHK(grow(ctx->al_start.p, ctx->al_start.cap, (size_t)n_sets * 4));
+    CHK(grow(ctx->al_first.p, ctx->al_first.cap, (size_t)nq * 4));
+    CHK(grow(ctx->al_flag.p, ctx->al_flag.cap, (size_t)nq * 4));
+    CHK(grow(ctx->al_list.p, ctx->al_list.cap, (size_t)nq * 4));
+    CHK(grow(ctx->al_npend.p, ctx->al_npend.cap, 256));
+    CHK(grow(ctx->al_pq.p, ctx->al_pq.cap, (size_t)nq * kdim * 4));
+    CHK(grow(ctx->al_opid.p, ctx->al_opid.cap, ob));
+    CHK(grow(ctx->al_odist.p, ctx->al_odist.cap, ob));
+    CHK(grow(ctx->al_ocnt.p, ctx->al_ocnt.cap, (size_t)nq * 4));
+    CHK(grow(ctx->al_orung.p, ctx->al_orung.cap, (size_t)nq * 4));
+    CHK(grow(ctx->al_octr.p, ctx->al_octr.cap, (size_t)nq * 12));
+    std::vector<uint32_t> own_set;                               // set_of == NULL: query q uses set q
+    if (!set_of) {
+        own_set.resize(nq);
+        for (uint32_t q = 0; q < nq; q++) own_set[q] = q;
+        set_of = own_set.data();
+    }
+    HIPCHK(hipMemcpyAsync(ctx->d_q, queries, qb, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(ctx->al_bits.p, allow_bits, bb, hipMemcpyHostToDevice, stream));     // as the caller has them: padding bits are masked where they are read
+    HIPCHK(hipMemcpyAsync(ctx->al_setof.p, set_of, (size_t)nq * 4, hipMemcpyHostToDevice, stream));
+    const uint32_t* d_bits = ctx->al_bits.as<uint32_t>();
+    const uint32_t* d_setof = ctx->al_setof.as<uint32_t>();
+    const uint32_t* d_first = ctx->al_first.as<uint32_t>();
+    auto count_pass = [&]() -> idist_status {
+        const uint32_t grid = std::min<uint32_t>(n_sets, (uint32_t)std::max(ctx->n_cu, 1) * 32u);
+        IDIST_LAUNCH(allowed_count_kernel, grid, 64, 0, stream, d_bits, n, words, n_sets, k, lad, ctx->al_size.as<uint32_t>(),
+                     ctx->al_start.as<uint32_t>());
+        HIPCHK(hipGetLastError());
+        return IDIST_OK;
+    };
+    CHK(allowed_timed(ctx, 0, count_pass));
+    std::vector<uint32_t> start(n_sets);
+    HIPCHK(hipMemcpyAsync(start.data(), ctx->al_start.p, (size_t)n_sets * 4, hipMemcpyDeviceToHost, stream));
+    const float* d_qk = ctx->d_q;
+    if (metric.any()) {
+        CHK(grow(ctx->d_qn, ctx->cap_qn, doubled_from(4096, metric.qk_floats(nq) * 4)));
+        CHK(grow(ctx->d_sq, ctx->cap_sq, doubled_from(256, metric.sq_floats(nq) * 4)));
+        CHK(metric.prepare(ctx->d_q, ctx->d_qn, ctx->d_sq, nq, stream, &d_qk));
+    }
+    AllowedOut o{};
+    o.pid = ctx->al_opid.as<uint32_t>(); o.dist = ctx->al_odist.as<uint32_t>(); o.count = ctx->al_ocnt.as<uint32_t>();
+    o.rung = ctx->al_orung.as<uint32_t>(); o.counters = counters ? ctx->al_octr.as<uint32_t>() : nullptr;
+    o.pending = ctx->al_flag.as<uint32_t>(); o.nq = nq; o.k = k;
+    {
+        const uint32_t grid = (uint32_t)std::min<size_t>(((size_t)nq * k + 255) / 256, (size_t)std::max(ctx->n_cu, 1) * 8u);
+        IDIST_LAUNCH(allowed_init_kernel, grid, 256, 0, stream, o, ctx->al_start.as<uint32_t>(), d_setof, ctx->al_first.as<uint32_t>());
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipStreamSynchronize(stream));
+    // how many queries start on which rung: what tells "nobody runs this rung, but some are still waiting" from "nobody is left"
+    uint32_t starts[8] = {0}, n_exact = 0;
+    for (uint32_t q = 0; q < nq; q++) {
+        const uint32_t f = start[set_of[q]];
+        if (f < 8u) starts[f]++;
+        else if (f == kRungExact) n_exact++;
+    }
+    auto next_start = [&](uint32_t from) {                      // the first rung >= from some query starts on (n_rungs: none)
+        while (from < n_rungs && !starts[from]) from++;
+        return std::min(from, n_rungs);
+    };
+    auto waiting_after = [&](uint32_t r) {                      // queries whose first step comes after rung r
+        uint32_t w = n_exact;
+        for (uint32_t i = r + 1u; i < n_rungs; i++) w += starts[i];
+        return w;
+    };
+    // the queries of a launch: the pending ones whose first rung has come up (rung kRungExact: everything still pending), ascending
+    uint32_t np = 0;
+    const uint32_t* d_list = nullptr;
+    const float* d_pq = d_qk;
+    auto gather = [&](uint32_t rung) -> idist_status {
+        auto pending_pass = [&]() -> idist_status {
+            IDIST_LAUNCH(allowed_pending_kernel, (nq + 63u) / 64u, 64, 0, stream, o.pending, nq, d_qk, kdim, ctx->al_list.as<uint32_t>(),
+                         ctx->al_pq.as<float>(), ctx->al_npend.as<uint32_t>(), d_first, rung);
+            HIPCHK(hipGetLastError());
+            return IDIST_OK;
+        };
+        CHK(allowed_timed(ctx, 1, pending_pass));
+        HIPCHK(hipMemcpyAsync(&np, ctx->al_npend.p, 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        d_list = ctx->al_list.as<uint32_t>();
+        d_pq = ctx->al_pq.as<float>();
+        return IDIST_OK;
+    };
+    uint32_t r = next_start(0);
+    bool all_done = false;
+    // every query on the same first step: the batch as it is, in place, as the single-set call launches it
+    bool in_place = (r < n_rungs && starts[r] == nq) || n_exact == nq;
+    if (in_place) np = nq;
+    while (r < n_rungs) {
+        if (!in_place) {
+            CHK(gather(r));
+            if (!np) {
+                if (!waiting_after(r)) { all_done = true; break; }
+                r = next_start(r + 1u);                          // nobody runs this rung, the waiting ones start later
+                continue;
+            }
+        }
+        in_place = false;
+        const uint32_t ef = lad.E[r];
+        const size_t rb = (size_t)np * ef * 4;
+        CHK(grow(ctx->d_pid, ctx->cap_pid, rb));
+        CHK(grow(ctx->d_dist, ctx->cap_dist, rb));
+        CHK(grow(ctx->d_cnt, ctx->cap_cnt, (size_t)np * 4));
+        CHK(grow(ctx->d_ctr, ctx->cap_ctr, (size_t)np * 12));
+        bool lds_short = false, ended = false;
+        for (;;) {
+            const idist_status ls = launch_search(idx, ctx, d_pq, np, ctx->d_pid, ctx->d_dist, ctx->d_cnt, counters ? ctx->d_ctr : nullptr,
+                                                  stream, nullptr, nullptr, nullptr, 0, true, ef, &lds_short);
+            if (ls != IDIST_OK) {
+                // a later rung that does not fit a wave's LDS ends the ladder for everyone still waiting or pending; rung 0 fails
+                if (lds_short && r != 0) { ended = true; break; }
+                return ls;
+            }
+            HIPCHK(hipStreamSynchronize(stream));
+            idist_status s;
+            if (status_asks_retry(idx, ctx, &s)) continue;      // strict ties: the same rung again with the larger region / the bags
+            if (s != IDIST_OK) return s;
+            break;
+        }
+        if (ended) break;
+        CHK(allowed_select(ctx, o, n, ctx->d_pid, ctx->d_dist, ctx->d_cnt, counters ? ctx->d_ctr : nullptr, ef, d_list, np, r, false,
+                           d_setof, words));
+        r++;
+    }
+    if (!all_done && !in_place) CHK(gather(kRungExact));
+    if (!all_done && np) {
+        // step 5, exact, straight from the bitmaps: the 64-id windows of [0, n) cut into S segments, one wave per (pending query,
+        // segment); S as in the single-set call, never narrower than one window
+        const uint32_t n_win = (uint32_t)(((uint64_t)n + 63u) / 64u);
+        uint32_t S = (uint32_t)std::min<uint64_t>(((uint64_t)std::max(ctx->n_cu, 1) * 16u + np - 1u) / np, n_win);
+        if (ctx->knobs.allowed_segments) S = ctx->knobs.allowed_segments;
+        S = std::min(std::max(S, 1u), kMergeMaxLists);
+        const size_t sb = (size_t)S * np * k * 4, mb = (size_t)np * k * 4;
+        CHK(grow(ctx->d_pid, ctx->cap_pid, sb));
+        CHK(grow(ctx->d_dist, ctx->cap_dist, sb));
+        CHK(grow(ctx->d_cnt, ctx->cap_cnt, (size_t)S * np * 4));
+        CHK(grow(ctx->al_mpid.p, ctx->al_mpid.cap, mb));
+        CHK(grow(ctx->al_mdist.p, ctx->al_mdist.cap, mb));
+        CHK(grow(ctx->al_mcnt.p, ctx->al_mcnt.cap, (size_t)np * 4));
+        const uint32_t wcap = k + 64 + 8;
+        const size_t smem = smem_bytes(idx->L.stride, wcap, false);
+        if (smem > 64 * 1024) return fail(IDIST_ERR_INVALID_ARG, "dim/k need %zu B of LDS per wave (> 64 KiB)", smem);
+        auto scan_and_merge = [&]() -> idist_status {
+            const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)np * S, (uint64_t)std::max(ctx->n_cu, 1) * 64u);
+            IndexView view = idx->view();
+            uint32_t *s_pid = ctx->d_pid, *s_dist = reinterpret_cast<uint32_t*>(ctx->d_dist), *s_cnt = ctx->d_cnt;
+#define LAUNCH_AS(NB_, RS_, TAIL_)                                                                                                 \
+    {                                                                                                                              \
+        auto kA = allowed_scan_bits_kernel<NB_, RS_, TAIL_>;                                                                       \
+        IDIST_LAUNCH(kA, grid, 64, smem, stream, view, d_pq, np, d_bits, n, words, d_list, d_setof, S, k, wcap, s_pid, s_dist, s_cnt); \
+    }
+            IDIST_DISPATCH(idx->L, LAUNCH_AS);
+#undef LAUNCH_AS
+            HIPCHK(hipGetLastError());
+            MergeArgs a{};
+            a.pid = s_pid; a.dist = s_dist; a.count = s_cnt; a.counters = nullptr;
+            a.n_lists = S; a.nq = np; a.width = k; a.out_width = k;
+            a.out_pid = ctx->al_mpid.as<uint32_t>(); a.out_dist = ctx->al_mdist.as<uint32_t>(); a.out_count = ctx->al_mcnt.as<uint32_t>();
+            a.out_counters = nullptr;
+            return launch_merge(a, stream);
+        };
+        CHK(allowed_timed(ctx, 2, scan_and_merge));
+        CHK(allowed_select(ctx, o, n, ctx->al_mpid.as<uint32_t>(), ctx->al_mdist.as<float>(), ctx->al_mcnt.as<uint32_t>(), nullptr, k,
+                           d_list, np, IDIST_RUNG_EXACT, true, d_setof, words));
     }
     CHK(metric.report(ctx->al_odist.as<float>(), ctx->d_sq, nq, k, stream));
     HIPCHK(hipMemcpyAsync(out_pid, ctx->al_opid.p, ob, hipMemcpyDeviceToHost, stream));

@@ -259,6 +259,35 @@ public:
             out.push_back(Item<P>{search.dist_[i], PointId{search.pid_[i]}, &points_[search.pid_[i]]});
         return out;
     }
+    // Hnsw::search_allowed for several points in one call, each within a set of its own (idist_search_batch_allowed_sets): sets[s][pid]
+    // one flag per point, set_of[i] the set of points[i] (empty: point i uses set i, one set per point).  Entry i of the result is
+    // exactly what search_allowed(points[i], sets[set_of[i]], k, ...) returns; *rungs (optional): the rung that answered each point.
+    std::vector<std::vector<Item<P>>> search_allowed_sets(const std::vector<P>& points, const std::vector<std::vector<bool>>& sets,
+                                                          const std::vector<uint32_t>& set_of, size_t k, Search& search,
+                                                          int32_t max_rungs = -1, std::vector<uint32_t>* rungs = nullptr) const {
+        const size_t nq = points.size(), words = (points_.size() + 31) / 32, dim = points_.empty() ? 1 : points_[0].dim();
+        if (!set_of.empty() && set_of.size() != nq) throw Error(IDIST_ERR_INVALID_ARG, "set_of needs one set index per point");
+        std::vector<uint32_t> bits(sets.size() * words + 1, 0u);
+        for (size_t s = 0; s < sets.size(); s++) {
+            if (sets[s].size() != points_.size()) throw Error(IDIST_ERR_INVALID_ARG, "every set needs one flag per point");
+            for (size_t i = 0; i < sets[s].size(); i++)
+                if (sets[s][i]) bits[s * words + i / 32] |= 1u << (i % 32);
+        }
+        std::vector<float> q(nq * dim + 1);
+        for (size_t i = 0; i < nq; i++) points[i].write_f32(q.data() + i * dim);
+        const size_t kk = k ? k : 1;
+        std::vector<uint32_t> pid(nq * kk + 1), cnt(nq + 1, 0u), r(nq + 1, IDIST_RUNG_NONE);
+        std::vector<float> dist(nq * kk + 1);
+        check(idist_search_batch_allowed_sets(idx_, search.bind(idx_, uid_), q.data(), (uint32_t)nq, bits.data(), (uint32_t)sets.size(),
+                                              set_of.empty() ? nullptr : set_of.data(), (uint32_t)k, max_rungs, pid.data(), dist.data(),
+                                              cnt.data(), r.data(), nullptr));
+        if (rungs) rungs->assign(r.begin(), r.begin() + nq);
+        std::vector<std::vector<Item<P>>> out(nq);
+        for (size_t i = 0; i < nq; i++)
+            for (size_t j = 0; j < cnt[i]; j++)
+                out[i].push_back(Item<P>{dist[i * k + j], PointId{pid[i * k + j]}, &points_[pid[i * k + j]]});
+        return out;
+    }
     const P& operator[](PointId pid) const { return points_[pid.v]; }                                           // Index<PointId>
     size_t len() const { return points_.size(); }
     const std::vector<P>& points() const { return points_; }

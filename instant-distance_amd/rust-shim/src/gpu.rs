@@ -74,6 +74,11 @@ extern "C" {
     fn idist_search_batch_allowed(idx: *const IdistIndex, ctx: *mut IdistSearchCtx, queries: *const f32, nq: u32,
                                   allow_bits: *const u32, k: u32, max_rungs: i32, out_pid: *mut u32, out_dist: *mut f32,
                                   out_count: *mut u32, out_rung: *mut u32, out_counters: *mut u32) -> i32;
+    // the same with several allowed sets in one call, one per query: allow_bits [n_sets][(n + 31) / 32], set_of [nq] or null
+    fn idist_search_batch_allowed_sets(idx: *const IdistIndex, ctx: *mut IdistSearchCtx, queries: *const f32, nq: u32,
+                                       allow_bits: *const u32, n_sets: u32, set_of: *const u32, k: u32, max_rungs: i32,
+                                       out_pid: *mut u32, out_dist: *mut f32, out_count: *mut u32, out_rung: *mut u32,
+                                       out_counters: *mut u32) -> i32;
     // several GPUs of one node: replicate once, shard the queries of a batch
     fn idist_replicate(root: *const IdistIndex, devices: *const i32, n_devices: u32, replicas: *mut *mut IdistIndex) -> i32;
     // the same as one RCCL broadcast per buffer (ncclCommInitAll over the devices, inside libidist)
@@ -302,6 +307,22 @@ impl Ctx {
         self.dist.resize(nq * k.max(1), 0.0);
         let (mut cnt, mut rung) = (vec![0u32; nq], vec![RUNG_NONE; nq]);
         expect(unsafe { idist_search_batch_allowed(g.idx, c, queries.as_ptr(), nq as u32, allow_bits.as_ptr(), k as u32, max_rungs, self.pid.as_mut_ptr(), self.dist.as_mut_ptr(), cnt.as_mut_ptr(), rung.as_mut_ptr(), std::ptr::null_mut()) });
+        (0..nq).map(|i| ((0..cnt[i] as usize).map(|j| Candidate { distance: self.dist[i * k + j].into(), pid: PointId(self.pid[i * k + j]) }).collect(), rung[i])).collect()
+    }
+
+    /// Additive API (`Hnsw::search_allowed_sets`): `search_allowed` with several allowed sets in one call, one per query.
+    /// `allow_bits`: n_sets bitmaps of (n + 31) / 32 words each, one after the other; `set_of[i]`: the set of query i (`None`: query i
+    /// uses set i, n_sets must equal the number of queries).  Row i is exactly what `search_allowed` returns for query i alone
+    /// with its own set.
+    pub(crate) fn search_allowed_sets(&mut self, g: &GpuIndex, queries: &[f32], allow_bits: &[u32], n_sets: usize, set_of: Option<&[u32]>, k: usize, max_rungs: i32) -> Vec<(Vec<Candidate>, u32)> {
+        let nq = queries.len() / g.dim;
+        assert!(set_of.map_or(true, |s| s.len() == nq), "set_of needs one set index per query");
+        let c = self.bind(g, 0);
+        self.pid.resize(nq * k.max(1), 0);
+        self.dist.resize(nq * k.max(1), 0.0);
+        let (mut cnt, mut rung) = (vec![0u32; nq], vec![RUNG_NONE; nq]);
+        let so = set_of.map_or(std::ptr::null(), |s| s.as_ptr());
+        expect(unsafe { idist_search_batch_allowed_sets(g.idx, c, queries.as_ptr(), nq as u32, allow_bits.as_ptr(), n_sets as u32, so, k as u32, max_rungs, self.pid.as_mut_ptr(), self.dist.as_mut_ptr(), cnt.as_mut_ptr(), rung.as_mut_ptr(), std::ptr::null_mut()) });
         (0..nq).map(|i| ((0..cnt[i] as usize).map(|j| Candidate { distance: self.dist[i * k + j].into(), pid: PointId(self.pid[i * k + j]) }).collect(), rung[i])).collect()
     }
 }
