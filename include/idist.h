@@ -419,8 +419,8 @@ idist_status idist_partitioned_last_search_kernel_ms(idist_partitioned* p, float
  * 8 * E[r] bytes per query still pending.
  * Cost: a query that climbs the whole ladder costs about 1.3 searches at ef_search 4096 (the rungs below add a quarter, a
  * sixteenth, ...) plus a scan of A; max_rungs is the caller's bound.
- * Out of scope: device-pointer / stream variants, the partitioned index and idist_search_batch_sharded.  Several sets in one call:
- * idist_search_batch_allowed_sets below. */
+ * Out of scope: device-pointer / stream variants and idist_search_batch_sharded.  Several sets in one call:
+ * idist_search_batch_allowed_sets below; the partitioned index: idist_partitioned_search_batch_allowed_sets. */
 #define IDIST_RUNG_NONE  254u
 #define IDIST_RUNG_EXACT 255u
 idist_status idist_search_batch_allowed(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
@@ -447,7 +447,8 @@ idist_status idist_search_batch_allowed(const idist_index* idx, idist_search_ctx
  * staging does not grow with n_sets beyond the n_sets * ((n + 31) / 32) * 4 bytes of the bitmaps): n / 8 bytes of bitmap per
  * (pending query, call) on top of the allowed rows.
  * Host pointers; blocks until done; ctx is the `&mut Search`, idx is never mutated — as the single-set call.
- * Out of scope: device-pointer / stream variants, the partitioned index and idist_search_batch_sharded. */
+ * Out of scope: device-pointer / stream variants and idist_search_batch_sharded.  The partitioned index:
+ * idist_partitioned_search_batch_allowed_sets below. */
 idist_status idist_search_batch_allowed_sets(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
                                              const uint32_t* allow_bits,              /* [n_sets][(n + 31) / 32] */
                                              uint32_t n_sets, const uint32_t* set_of, /* [nq] or NULL */
@@ -455,6 +456,51 @@ idist_status idist_search_batch_allowed_sets(const idist_index* idx, idist_searc
                                              uint32_t* out_pid, float* out_dist,      /* nq*k */
                                              uint32_t* out_count, uint32_t* out_rung, /* nq; out_rung may be NULL */
                                              uint32_t* out_counters);                 /* nq*3 or NULL */
+/* Restricted search over a partitioned index, one allowed set per query: the two exact things above, composed.
+ *   allow_bits  n_sets bitmaps over the GLOBAL ids: (N + 31) / 32 words each, N = the points in all parts, bit g = global id g; bits at
+ *               positions >= N are ignored.  The buffer is neither written nor copied on the host to clean it.
+ *   set_of      as in idist_search_batch_allowed_sets.
+ * DEFINITION: A_p = the slice of query q's set that falls into part p (bit i of A_p = bit base[p] + i of the set, i < n_p).  Row q is the
+ * merge of the P lists
+ *   idist_search_batch_allowed(part p, ctx, &queries[q * dim], 1, A_p, k, max_rungs, ...)      raw distances, ids + base[p]
+ * by the reference's `Candidate` order (distance bits, then global id), the first k kept — the merge of
+ * idist_partitioned_search_batch at width k.  So:
+ *   - every part runs its own ladder with its own start rule on |A_p| and n_p: a part that holds none of a query's allowed points
+ *     answers IDIST_RUNG_NONE at once, one where they are rare goes straight to the exact scan (range- or tenant-partitioned data);
+ *   - count = min(k, sum over p of min(k, |A_p|)) = min(k, |A|), the guarantee of the single-index call;
+ *   - out_counters = the parts' counters summed; out_rung[q * n_parts + p] = part p's rung for query q (IDIST_RUNG_NONE for an empty
+ *     part or an empty slice);
+ *   - the metric's report runs once, after the merge, on the [nq][k] result; padding is IDIST_INVALID / +inf;
+ *   - IDIST_ERR_TIE_OVERFLOW never reaches the caller; a part's failure on rung 0 (a wave's LDS) is returned, the message prefixed
+ *     "part <p> (device <d>): " as idist_partitioned_search_batch does;
+ *   - 1 <= k <= ef_search; N == 0 or ef_search == 0: every count 0, every rung IDIST_RUNG_NONE, every counter 0.
+ * One part is the identity: every output equals idist_search_batch_allowed_sets on that part.
+ * IDIST_ERR_INVALID_ARG: the cases of idist_search_batch_allowed_sets; the parts' dim / metric / ef_search are compared again at every
+ * call.  Every part finds k of its own although the union needs only k (as every part of idist_partitioned_search_batch returns
+ * ef_search): the price of a definition that composes two exact things.
+ * The queries and set_of are uploaded once per distinct device; of the bitmaps every part's device receives the words that hold the
+ * part's bits (one strided copy: the bitmaps' size in total, plus at most one word per set and part) and cuts its own bitmaps out of
+ * them on the device (idist_allowed_slice_device's kernel).  The ladders block on the host once per rung, so the parts run side by
+ * side, one host thread per non-empty part for the duration of the call.  Host pointers; blocks until done; p is used by one thread
+ * at a time.  Out of scope: device-pointer / stream variants and idist_search_batch_sharded. */
+idist_status idist_partitioned_search_batch_allowed_sets(idist_partitioned* p, const float* queries, uint32_t nq,
+                                                         const uint32_t* allow_bits,              /* [n_sets][(N + 31) / 32] */
+                                                         uint32_t n_sets, const uint32_t* set_of, /* [nq] or NULL */
+                                                         uint32_t k, int32_t max_rungs,
+                                                         uint32_t* out_pid, float* out_dist,      /* nq*k, global ids */
+                                                         uint32_t* out_count,                     /* nq */
+                                                         uint32_t* out_rung,                      /* [nq][n_parts] or NULL */
+                                                         uint32_t* out_counters);                 /* nq*3 or NULL */
+/* Host time (ms) the last idist_partitioned_search_batch_allowed_sets through p spent on the bitmaps: the strided uploads and the
+ * slice kernels of all parts (waited for, to be timed, unless IDIST_KERNEL_EVENTS=0).  0 before the first call. */
+idist_status idist_partitioned_last_allowed_slice_ms(idist_partitioned* p, float* ms);
+/* The slice on its own: d_bits holds n_sets rows of pitch_words u32 words, d_out n_sets rows of (n_out + 31) / 32 words, both in the
+ * memory of `device`.  out[s] bit i = in[s] bit bit_offset + i for i < n_out; the bits at positions >= n_out of a row's last word are
+ * written as 0.  No source word at or beyond (bit_offset + n_out + 31) / 32 of a row is read: the source may end exactly there
+ * (a smaller pitch_words is IDIST_ERR_INVALID_ARG).  n_out == 0 or n_sets == 0: nothing is done.  Enqueued on `hip_stream` (a
+ * hipStream_t, may be NULL) without synchronising, as idist_merge_topk_device. */
+idist_status idist_allowed_slice_device(const void* d_bits, uint32_t n_sets, uint32_t pitch_words, uint64_t bit_offset,
+                                        uint32_t n_out, void* d_out, int32_t device, void* hip_stream);
 /* HIP-event durations (ms) of the kernels the last idist_search_batch_allowed / idist_search_batch_allowed_sets through ctx ran
  * around its searches, summed over its rungs: the select passes (and the several-sets call's count pass), the pending-list passes,
  * the exact step (scan + merge).  0 with IDIST_KERNEL_EVENTS=0.  The rungs' own search kernels are in idist_search_ctx_kernel_times. */

@@ -35,6 +35,12 @@
 //                             64 in act_pid; an id that does not fit the batch stays in its lane's register until the batch has been
 //                             ranked and opens the next one.  Everything after that is allowed_scan_kernel's.  No id list exists,
 //                             on the host or the device; the staging does not depend on the number of sets.
+//
+// The partitioned index (idist_partitioned_search_batch_allowed_sets): every part runs the several-sets call on ITS slice of the
+// caller's global bitmaps, and base[p] is no multiple of 32 in general:
+//
+//   allowed_slice_kernel      out[s] bit i = in[s] bit bit_offset + i, i < n_out: one lane per output word, two adjacent source words
+//                             joined by a 64-bit shift, the last word of a row masked.  No LDS, no atomics.
 #pragma once
 #include "idist_kernels.hpp"
 #include "idist_merge.hpp"
@@ -341,6 +347,33 @@ __global__ __launch_bounds__(64) void allowed_scan_bits_kernel(IndexView ix, con
             out_dist[row + i] = (uint32_t)((st.W[i] & kKeyMask) >> 32);
         }
         if (lane == 0) out_count[(size_t)s * np + p] = (uint32_t)st.plen;
+    }
+}
+
+// ---- a bit range of every set: the slice of the global bitmaps that falls into one part ----------------------------------------------
+
+// in [n_sets][pitch] words -> out [n_sets][ceil(n_out / 32)]: bit i of out[s] = bit bit_offset + i of in[s] for i < n_out, the bits
+// at positions >= n_out of a row's last word 0.  Of a source row only the words below ceil((bit_offset + n_out) / 32) are read (the
+// row may end there): the second word of a pair is loaded only when the shift needs it and it lies below that bound.  One lane per
+// output word, consecutive lanes on consecutive words of a row; the grid strides over the rest.  n_out >= 1.
+__global__ void allowed_slice_kernel(const uint32_t* __restrict__ in, uint32_t n_sets, uint32_t pitch, uint64_t bit_offset,
+                                     uint32_t n_out, uint32_t* __restrict__ out) {
+    const size_t tid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (size_t)gridDim.x * blockDim.x;
+    const uint32_t words_out = (uint32_t)(((uint64_t)n_out + 31u) / 32u);
+    const uint64_t w0 = bit_offset / 32u, w_end = (bit_offset + n_out + 31u) / 32u;
+    const uint32_t sh = (uint32_t)(bit_offset % 32u);
+    const uint32_t last_mask = n_out % 32u ? (1u << (n_out % 32u)) - 1u : 0xFFFFFFFFu;
+    const size_t total = (size_t)n_sets * words_out;
+    for (size_t i = tid; i < total; i += nth) {
+        const size_t s = i / words_out;
+        const uint32_t w = (uint32_t)(i % words_out);
+        const uint32_t* row = in + s * pitch;
+        const uint64_t a = w0 + w;                            // < w_end: bit 32 w of the slice exists
+        uint64_t v = row[a];
+        if (sh != 0u && a + 1u < w_end) v |= (uint64_t)row[a + 1u] << 32;
+        uint32_t r = (uint32_t)(v >> sh);
+        if (w + 1u == words_out) r &= last_mask;
+        out[i] = r;
     }
 }
 

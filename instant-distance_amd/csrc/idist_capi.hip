@@ -389,6 +389,9 @@ struct idist_search_ctx {
     // the first rung per query.
     Buf al_bits, al_ids, al_flag, al_list, al_npend, al_pq, al_opid, al_odist, al_ocnt, al_orung, al_octr, al_mpid, al_mdist, al_mcnt;
     Buf al_setof, al_size, al_start, al_first;
+    // idist_partitioned_search_batch_allowed_sets adds: the words of the caller's global bitmaps that hold this part's bits, as
+    // uploaded (allowed_slice_kernel cuts the part's own bitmaps out of them into al_bits)
+    Buf al_raw;
     static constexpr uint32_t kAllowedEvents = 64;   // a pair per select / pending pass of at most seven rungs + the exact step's two;
                                                      // the several-sets call: + its count pass and a pending pass in front of every launch
     hipEvent_t al_ev[kAllowedEvents] = {nullptr};    // (created on first use, resolved when the call has synchronised its stream)
@@ -424,6 +427,8 @@ struct idist_partitioned {
         int32_t device = 0;
         float* d_q = nullptr;                // the batch's queries, uploaded once per distinct device
         size_t cap_q = 0;
+        uint32_t* d_setof = nullptr;         // restricted search: the set of every query, uploaded once per distinct device
+        size_t cap_setof = 0;
     };
     std::vector<Part> parts;
     std::vector<Dev> devs;
@@ -437,6 +442,9 @@ struct idist_partitioned {
     uint32_t *s_pid = nullptr, *s_cnt = nullptr, *s_ctr = nullptr, *o_pid = nullptr, *o_cnt = nullptr, *o_ctr = nullptr;
     float *s_dist = nullptr, *o_dist = nullptr;
     size_t cap_s_pid = 0, cap_s_dist = 0, cap_s_cnt = 0, cap_s_ctr = 0, cap_o_pid = 0, cap_o_dist = 0, cap_o_cnt = 0, cap_o_ctr = 0;
+    uint32_t* s_rung = nullptr;              // restricted search: the parts' rungs [P][nq]
+    size_t cap_s_rung = 0;
+    float al_slice_ms = 0.0f;                // ... and the host time its last call spent on the bitmaps: upload + slice, every part
     hipStream_t stream = nullptr;            // the merge and the copies of its result
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
@@ -2032,7 +2040,7 @@ void idist_search_ctx_free(idist_search_ctx* c) {
     hipFree(c->d_ctr);
     for (idist_search_ctx::Buf* b : {&c->al_bits, &c->al_ids, &c->al_flag, &c->al_list, &c->al_npend, &c->al_pq, &c->al_opid, &c->al_odist,
                                      &c->al_ocnt, &c->al_orung, &c->al_octr, &c->al_mpid, &c->al_mdist, &c->al_mcnt, &c->al_setof, &c->al_size,
-                                     &c->al_start, &c->al_first})
+                                     &c->al_start, &c->al_first, &c->al_raw})
         hipFree(b->p);
     for (hipEvent_t e : c->al_ev)
         if (e) hipEventDestroy(e);
@@ -2649,8 +2657,8 @@ void idist_partitioned_free(idist_partitioned* p) {
         idist_search_ctx_free(pt.ctx);
         hipFree(pt.r_pid); hipFree(pt.r_dist); hipFree(pt.r_cnt); hipFree(pt.r_ctr);
     }
-    for (auto& dv : p->devs) hipFree(dv.d_q);
-    hipFree(p->d_qm); hipFree(p->d_sq);
+    for (auto& dv : p->devs) { hipFree(dv.d_q); hipFree(dv.d_setof); }
+    hipFree(p->d_qm); hipFree(p->d_sq); hipFree(p->s_rung);
     hipFree(p->s_pid); hipFree(p->s_dist); hipFree(p->s_cnt); hipFree(p->s_ctr);
     hipFree(p->o_pid); hipFree(p->o_dist); hipFree(p->o_cnt); hipFree(p->o_ctr);
     if (p->ev0) hipEventDestroy(p->ev0);
@@ -2728,6 +2736,28 @@ static idist_status partitioned_merge(idist_partitioned* p, uint32_t nq, uint32_
     return IDIST_OK;
 }
 
+// The batch's queries, once per distinct device that has something to search, as the parts' launches read them (prepared = true):
+// Dev::d_q holds the [nq][kdim] rows in front (a metric whose prepare cannot run in place: followed by the queries as uploaded).
+// Leaves another device current.
+static idist_status partitioned_upload_queries(idist_partitioned* p, const float* queries, uint32_t nq) {
+    const MetricPasses metric(p);
+    const size_t qb = (size_t)nq * p->dim * 4, qa = metric.in_place() ? 0 : metric.qk_floats(nq) * 4;
+    for (size_t d = 0; d < p->devs.size(); d++) {
+        idist_partitioned::Dev& dv = p->devs[d];
+        bool used = false;
+        for (auto& pt : p->parts) used |= pt.ctx && pt.dev_slot == (int)d;
+        if (!used) continue;
+        HIPCHK(hipSetDevice(dv.device));
+        CHK(grow(dv.d_q, dv.cap_q, qa + qb));
+        HIPCHK(hipMemcpy(dv.d_q + qa / 4, queries, qb, hipMemcpyHostToDevice));
+        if (metric.any()) {                              // prepared once per device; the parts' launches take them as they are
+            CHK(metric.prepare(dv.d_q + qa / 4, dv.d_q, nullptr, nq, nullptr, nullptr));
+            HIPCHK(hipStreamSynchronize(nullptr));
+        }
+    }
+    return IDIST_OK;
+}
+
 idist_status idist_partitioned_search_batch(idist_partitioned* p, const float* queries, uint32_t nq, uint32_t* out_pid,
                                             float* out_dist, uint32_t* out_count, uint32_t* out_counters) {
     if (!p) return fail(IDIST_ERR_INVALID_ARG, "null argument");
@@ -2743,27 +2773,12 @@ idist_status idist_partitioned_search_batch(idist_partitioned* p, const float* q
     }
     if (!out_pid || !out_dist) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
     const bool counters = out_counters != nullptr;
-    const MetricPasses metric(p);
-    // (a metric whose prepare cannot run in place: a device's buffer holds the [nq][kdim] rows the parts read, followed by the queries
-    // as uploaded)
-    const size_t qb = (size_t)nq * p->dim * 4, qa = metric.in_place() ? 0 : metric.qk_floats(nq) * 4, row = (size_t)nq * ef;
+    const size_t row = (size_t)nq * ef;
     HIPCHK(hipSetDevice(p->merge_device));
     CHK(partitioned_reserve(p, nq, ef, ef));
     CHK(partitioned_prepare_report(p, queries, nq));
     // 1. the queries, once per distinct device that has something to search
-    for (size_t d = 0; d < p->devs.size(); d++) {
-        idist_partitioned::Dev& dv = p->devs[d];
-        bool used = false;
-        for (auto& pt : p->parts) used |= pt.ctx && pt.dev_slot == (int)d;
-        if (!used) continue;
-        HIPCHK(hipSetDevice(dv.device));
-        CHK(grow(dv.d_q, dv.cap_q, qa + qb));
-        HIPCHK(hipMemcpy(dv.d_q + qa / 4, queries, qb, hipMemcpyHostToDevice));
-        if (metric.any()) {                              // prepared once per device; the parts' launches take them as they are
-            CHK(metric.prepare(dv.d_q + qa / 4, dv.d_q, nullptr, nq, nullptr, nullptr));
-            HIPCHK(hipStreamSynchronize(nullptr));
-        }
-    }
+    CHK(partitioned_upload_queries(p, queries, nq));
     // 2. every part on its own stream: on the merge device straight into its slice of the staging memory, elsewhere into memory of
     //    its own device followed by one peer copy per array
     auto enqueue = [&](size_t i) -> idist_status {
@@ -3299,30 +3314,19 @@ idist_status idist_search_batch_allowed(const idist_index* idx, idist_search_ctx
     return allowed_times_resolve(ctx);
 }
 
-idist_status idist_search_batch_allowed_sets(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
-                                             const uint32_t* allow_bits, uint32_t n_sets, const uint32_t* set_of, uint32_t k,
-                                             int32_t max_rungs, uint32_t* out_pid, float* out_dist, uint32_t* out_count,
-                                             uint32_t* out_rung, uint32_t* out_counters) {
-    CHK(check_ctx(idx, ctx));
+extern "C++" {
+namespace {
+
+// The several-sets call between its uploads and its report: everything already in the memory of the index's device (which is
+// current).  d_qk [nq][kdim]: the queries as the kernels read them (MetricPasses::prepare has run, or the metric has none); d_bits
+// [n_sets][(n + 31) / 32]; d_setof [nq] and its host copy set_of (never null here).  o.pid / dist / count / rung / counters: where the
+// [nq][k] result goes, RAW distances — the caller reports; o.pending is set here.  n > 0, ef_search > 0, nq > 0 and the arguments
+// checked.  Blocks on ctx->stream once per rung; on return the last passes are enqueued there, not waited for: the caller
+// synchronises the stream and calls allowed_times_resolve.
+idist_status allowed_sets_device(const idist_index* idx, idist_search_ctx* ctx, const float* d_qk, uint32_t nq, const uint32_t* d_bits,
+                                 uint32_t n_sets, const uint32_t* d_setof, const uint32_t* set_of, uint32_t k, int32_t max_rungs,
+                                 AllowedOut o) {
     const uint32_t n = idx->n, ef0 = idx->cfg.ef_search;
-    if (max_rungs < -1) return fail(IDIST_ERR_INVALID_ARG, "max_rungs %d: -1 (the whole ladder) or a number of rungs >= 0", max_rungs);
-    if (k == 0 || k > IDIST_MAX_EF) return fail(IDIST_ERR_INVALID_ARG, "k %u out of [1,%u]", k, IDIST_MAX_EF);
-    if (ef0 != 0 && k > ef0) return fail(IDIST_ERR_INVALID_ARG, "k %u > ef_search %u", k, ef0);
-    if (n_sets == 0) return fail(IDIST_ERR_INVALID_ARG, "n_sets 0: at least one allowed set");
-    if (nq == 0) return IDIST_OK;
-    if (!set_of && n_sets != nq) return fail(IDIST_ERR_INVALID_ARG, "set_of is null (query q uses set q) but n_sets %u != nq %u", n_sets, nq);
-    if (!queries || !out_pid || !out_dist || !out_count || (n && !allow_bits)) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
-    if (set_of)
-        for (uint32_t q = 0; q < nq; q++)
-            if (set_of[q] >= n_sets) return fail(IDIST_ERR_INVALID_ARG, "set_of[%u] = %u: query %u names a set outside [0,%u)", q, set_of[q], q, n_sets);
-    const size_t ob = (size_t)nq * k * 4;
-    if (n == 0 || ef0 == 0) {                                                // step 1: nothing to find, whatever the sets
-        for (size_t i = 0; i < (size_t)nq * k; i++) { out_pid[i] = IDIST_INVALID; out_dist[i] = INFINITY; }
-        memset(out_count, 0, (size_t)nq * 4);
-        if (out_rung) std::fill(out_rung, out_rung + nq, (uint32_t)IDIST_RUNG_NONE);
-        if (out_counters) memset(out_counters, 0, (size_t)nq * 12);
-        return IDIST_OK;
-    }
     // the permitted rungs, as idist_search_batch_allowed has them; every set's size and start rung come from the device
     const uint32_t words = (n + 31u) / 32u;
     AllowedLadder lad{};
@@ -3332,18 +3336,11 @@ idist_status idist_search_batch_allowed_sets(const idist_index* idx, idist_searc
     }
     if (max_rungs >= 0) lad.n_rungs = std::min<uint32_t>(lad.n_rungs, (uint32_t)max_rungs);
     const uint32_t n_rungs = lad.n_rungs;
-
-    HIPCHK(hipSetDevice(idx->device));
     hipStream_t stream = ctx->stream;
-    const MetricPasses metric(idx);
     const uint32_t kdim = idx->kdim;
-    const size_t qb = (size_t)nq * idx->dim * 4, bb = (size_t)n_sets * words * 4;
-    const bool counters = out_counters != nullptr;
+    const bool counters = o.counters != nullptr;
     ctx->al_ms[0] = ctx->al_ms[1] = ctx->al_ms[2] = 0.0f;
     ctx->al_ev_used = 0;
-    CHK(grow(ctx->d_q, ctx->cap_q, qb));
-    CHK(grow(ctx->al_bits.p, ctx->al_bits.cap, bb));
-    CHK(grow(ctx->al_setof.p, ctx->al_setof.cap, (size_t)nq * 4));
     CHK(grow(ctx->al_size.p, ctx->al_size.cap, (size_t)n_sets * 4));
     CHK(grow(ctx->al_start.p, ctx->al_start.cap, (size_t)n_sets * 4));
     CHK(grow(ctx->al_first.p, ctx->al_first.cap, (size_t)nq * 4));
@@ -3351,22 +3348,7 @@ idist_status idist_search_batch_allowed_sets(const idist_index* idx, idist_searc
     CHK(grow(ctx->al_list.p, ctx->al_list.cap, (size_t)nq * 4));
     CHK(grow(ctx->al_npend.p, ctx->al_npend.cap, 256));
     CHK(grow(ctx->al_pq.p, ctx->al_pq.cap, (size_t)nq * kdim * 4));
-    CHK(grow(ctx->al_opid.p, ctx->al_opid.cap, ob));
-    CHK(grow(ctx->al_odist.p, ctx->al_odist.cap, ob));
-    CHK(grow(ctx->al_ocnt.p, ctx->al_ocnt.cap, (size_t)nq * 4));
-    CHK(grow(ctx->al_orung.p, ctx->al_orung.cap, (size_t)nq * 4));
-    CHK(grow(ctx->al_octr.p, ctx->al_octr.cap, (size_t)nq * 12));
-    std::vector<uint32_t> own_set;                               // set_of == NULL: query q uses set q
-    if (!set_of) {
-        own_set.resize(nq);
-        for (uint32_t q = 0; q < nq; q++) own_set[q] = q;
-        set_of = own_set.data();
-    }
-    HIPCHK(hipMemcpyAsync(ctx->d_q, queries, qb, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(ctx->al_bits.p, allow_bits, bb, hipMemcpyHostToDevice, stream));     // as the caller has them: padding bits are masked where they are read
-    HIPCHK(hipMemcpyAsync(ctx->al_setof.p, set_of, (size_t)nq * 4, hipMemcpyHostToDevice, stream));
-    const uint32_t* d_bits = ctx->al_bits.as<uint32_t>();
-    const uint32_t* d_setof = ctx->al_setof.as<uint32_t>();
+    o.pending = ctx->al_flag.as<uint32_t>(); o.nq = nq; o.k = k;
     const uint32_t* d_first = ctx->al_first.as<uint32_t>();
     auto count_pass = [&]() -> idist_status {
         const uint32_t grid = std::min<uint32_t>(n_sets, (uint32_t)std::max(ctx->n_cu, 1) * 32u);
@@ -3378,16 +3360,6 @@ idist_status idist_search_batch_allowed_sets(const idist_index* idx, idist_searc
     CHK(allowed_timed(ctx, 0, count_pass));
     std::vector<uint32_t> start(n_sets);
     HIPCHK(hipMemcpyAsync(start.data(), ctx->al_start.p, (size_t)n_sets * 4, hipMemcpyDeviceToHost, stream));
-    const float* d_qk = ctx->d_q;
-    if (metric.any()) {
-        CHK(grow(ctx->d_qn, ctx->cap_qn, doubled_from(4096, metric.qk_floats(nq) * 4)));
-        CHK(grow(ctx->d_sq, ctx->cap_sq, doubled_from(256, metric.sq_floats(nq) * 4)));
-        CHK(metric.prepare(ctx->d_q, ctx->d_qn, ctx->d_sq, nq, stream, &d_qk));
-    }
-    AllowedOut o{};
-    o.pid = ctx->al_opid.as<uint32_t>(); o.dist = ctx->al_odist.as<uint32_t>(); o.count = ctx->al_ocnt.as<uint32_t>();
-    o.rung = ctx->al_orung.as<uint32_t>(); o.counters = counters ? ctx->al_octr.as<uint32_t>() : nullptr;
-    o.pending = ctx->al_flag.as<uint32_t>(); o.nq = nq; o.k = k;
     {
         const uint32_t grid = (uint32_t)std::min<size_t>(((size_t)nq * k + 255) / 256, (size_t)std::max(ctx->n_cu, 1) * 8u);
         IDIST_LAUNCH(allowed_init_kernel, grid, 256, 0, stream, o, ctx->al_start.as<uint32_t>(), d_setof, ctx->al_first.as<uint32_t>());
@@ -3510,6 +3482,71 @@ idist_status idist_search_batch_allowed_sets(const idist_index* idx, idist_searc
         CHK(allowed_select(ctx, o, n, ctx->al_mpid.as<uint32_t>(), ctx->al_mdist.as<float>(), ctx->al_mcnt.as<uint32_t>(), nullptr, k,
                            d_list, np, IDIST_RUNG_EXACT, true, d_setof, words));
     }
+    return IDIST_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+idist_status idist_search_batch_allowed_sets(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
+                                             const uint32_t* allow_bits, uint32_t n_sets, const uint32_t* set_of, uint32_t k,
+                                             int32_t max_rungs, uint32_t* out_pid, float* out_dist, uint32_t* out_count,
+                                             uint32_t* out_rung, uint32_t* out_counters) {
+    CHK(check_ctx(idx, ctx));
+    const uint32_t n = idx->n, ef0 = idx->cfg.ef_search;
+    if (max_rungs < -1) return fail(IDIST_ERR_INVALID_ARG, "max_rungs %d: -1 (the whole ladder) or a number of rungs >= 0", max_rungs);
+    if (k == 0 || k > IDIST_MAX_EF) return fail(IDIST_ERR_INVALID_ARG, "k %u out of [1,%u]", k, IDIST_MAX_EF);
+    if (ef0 != 0 && k > ef0) return fail(IDIST_ERR_INVALID_ARG, "k %u > ef_search %u", k, ef0);
+    if (n_sets == 0) return fail(IDIST_ERR_INVALID_ARG, "n_sets 0: at least one allowed set");
+    if (nq == 0) return IDIST_OK;
+    if (!set_of && n_sets != nq) return fail(IDIST_ERR_INVALID_ARG, "set_of is null (query q uses set q) but n_sets %u != nq %u", n_sets, nq);
+    if (!queries || !out_pid || !out_dist || !out_count || (n && !allow_bits)) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    if (set_of)
+        for (uint32_t q = 0; q < nq; q++)
+            if (set_of[q] >= n_sets) return fail(IDIST_ERR_INVALID_ARG, "set_of[%u] = %u: query %u names a set outside [0,%u)", q, set_of[q], q, n_sets);
+    const size_t ob = (size_t)nq * k * 4;
+    if (n == 0 || ef0 == 0) {                                                // step 1: nothing to find, whatever the sets
+        for (size_t i = 0; i < (size_t)nq * k; i++) { out_pid[i] = IDIST_INVALID; out_dist[i] = INFINITY; }
+        memset(out_count, 0, (size_t)nq * 4);
+        if (out_rung) std::fill(out_rung, out_rung + nq, (uint32_t)IDIST_RUNG_NONE);
+        if (out_counters) memset(out_counters, 0, (size_t)nq * 12);
+        return IDIST_OK;
+    }
+    // upload, the call on the device, report, download
+    const uint32_t words = (n + 31u) / 32u;
+    HIPCHK(hipSetDevice(idx->device));
+    hipStream_t stream = ctx->stream;
+    const MetricPasses metric(idx);
+    const size_t qb = (size_t)nq * idx->dim * 4, bb = (size_t)n_sets * words * 4;
+    const bool counters = out_counters != nullptr;
+    CHK(grow(ctx->d_q, ctx->cap_q, qb));
+    CHK(grow(ctx->al_bits.p, ctx->al_bits.cap, bb));
+    CHK(grow(ctx->al_setof.p, ctx->al_setof.cap, (size_t)nq * 4));
+    CHK(grow(ctx->al_opid.p, ctx->al_opid.cap, ob));
+    CHK(grow(ctx->al_odist.p, ctx->al_odist.cap, ob));
+    CHK(grow(ctx->al_ocnt.p, ctx->al_ocnt.cap, (size_t)nq * 4));
+    CHK(grow(ctx->al_orung.p, ctx->al_orung.cap, (size_t)nq * 4));
+    CHK(grow(ctx->al_octr.p, ctx->al_octr.cap, (size_t)nq * 12));
+    std::vector<uint32_t> own_set;                               // set_of == NULL: query q uses set q
+    if (!set_of) {
+        own_set.resize(nq);
+        for (uint32_t q = 0; q < nq; q++) own_set[q] = q;
+        set_of = own_set.data();
+    }
+    HIPCHK(hipMemcpyAsync(ctx->d_q, queries, qb, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(ctx->al_bits.p, allow_bits, bb, hipMemcpyHostToDevice, stream));     // as the caller has them: padding bits are masked where they are read
+    HIPCHK(hipMemcpyAsync(ctx->al_setof.p, set_of, (size_t)nq * 4, hipMemcpyHostToDevice, stream));
+    // cosine / DOT: the queries are prepared ONCE per call, as the single-set call prepares them
+    const float* d_qk = ctx->d_q;
+    if (metric.any()) {
+        CHK(grow(ctx->d_qn, ctx->cap_qn, doubled_from(4096, metric.qk_floats(nq) * 4)));
+        CHK(grow(ctx->d_sq, ctx->cap_sq, doubled_from(256, metric.sq_floats(nq) * 4)));
+        CHK(metric.prepare(ctx->d_q, ctx->d_qn, ctx->d_sq, nq, stream, &d_qk));
+    }
+    AllowedOut o{};
+    o.pid = ctx->al_opid.as<uint32_t>(); o.dist = ctx->al_odist.as<uint32_t>(); o.count = ctx->al_ocnt.as<uint32_t>();
+    o.rung = ctx->al_orung.as<uint32_t>(); o.counters = counters ? ctx->al_octr.as<uint32_t>() : nullptr;
+    CHK(allowed_sets_device(idx, ctx, d_qk, nq, ctx->al_bits.as<uint32_t>(), n_sets, ctx->al_setof.as<uint32_t>(), set_of, k, max_rungs, o));
     CHK(metric.report(ctx->al_odist.as<float>(), ctx->d_sq, nq, k, stream));
     HIPCHK(hipMemcpyAsync(out_pid, ctx->al_opid.p, ob, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipMemcpyAsync(out_dist, ctx->al_odist.p, ob, hipMemcpyDeviceToHost, stream));
@@ -3518,6 +3555,187 @@ idist_status idist_search_batch_allowed_sets(const idist_index* idx, idist_searc
     if (counters) HIPCHK(hipMemcpyAsync(out_counters, ctx->al_octr.p, (size_t)nq * 12, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
     return allowed_times_resolve(ctx);
+}
+
+idist_status idist_allowed_slice_device(const void* d_bits, uint32_t n_sets, uint32_t pitch_words, uint64_t bit_offset, uint32_t n_out,
+                                        void* d_out, int32_t device, void* hip_stream) {
+    if (n_out == 0 || n_sets == 0) return IDIST_OK;
+    if (!d_bits || !d_out) return fail(IDIST_ERR_INVALID_ARG, "null device pointer");
+    const uint64_t w_end = (bit_offset + n_out + 31u) / 32u;             // words of a source row that may be read
+    if (pitch_words < w_end)
+        return fail(IDIST_ERR_INVALID_ARG, "pitch_words %u: bits [%llu, %llu) of a row need %llu words", pitch_words,
+                    (unsigned long long)bit_offset, (unsigned long long)(bit_offset + n_out), (unsigned long long)w_end);
+    int cnt = 0;
+    if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return fail(IDIST_ERR_NO_DEVICE, "no HIP device visible; libidist has no CPU path");
+    if (device < 0 || device >= cnt) return fail(IDIST_ERR_INVALID_ARG, "device %d out of range [0,%d)", device, cnt);
+    HIPCHK(hipSetDevice(device));
+    const size_t total = (size_t)n_sets * (((size_t)n_out + 31u) / 32u);
+    const uint32_t grid = (uint32_t)std::min<size_t>((total + 255u) / 256u, 4096u);   // one lane per output word; the kernel strides over the rest
+    IDIST_LAUNCH(allowed_slice_kernel, grid, 256, 0, (hipStream_t)hip_stream, (const uint32_t*)d_bits, n_sets, pitch_words, bit_offset, n_out,
+                 (uint32_t*)d_out);
+    HIPCHK(hipGetLastError());
+    return IDIST_OK;
+}
+
+idist_status idist_partitioned_search_batch_allowed_sets(idist_partitioned* p, const float* queries, uint32_t nq,
+                                                         const uint32_t* allow_bits, uint32_t n_sets, const uint32_t* set_of, uint32_t k,
+                                                         int32_t max_rungs, uint32_t* out_pid, float* out_dist, uint32_t* out_count,
+                                                         uint32_t* out_rung, uint32_t* out_counters) {
+    if (!p) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    uint32_t ef = 0;
+    CHK(partitioned_check(p, &ef));
+    const size_t P = p->parts.size();
+    const uint32_t N = p->base[P];
+    if (max_rungs < -1) return fail(IDIST_ERR_INVALID_ARG, "max_rungs %d: -1 (the whole ladder) or a number of rungs >= 0", max_rungs);
+    if (k == 0 || k > IDIST_MAX_EF) return fail(IDIST_ERR_INVALID_ARG, "k %u out of [1,%u]", k, IDIST_MAX_EF);
+    if (ef != 0 && k > ef) return fail(IDIST_ERR_INVALID_ARG, "k %u > ef_search %u", k, ef);
+    if (n_sets == 0) return fail(IDIST_ERR_INVALID_ARG, "n_sets 0: at least one allowed set");
+    if (nq == 0) return IDIST_OK;
+    if (!set_of && n_sets != nq) return fail(IDIST_ERR_INVALID_ARG, "set_of is null (query q uses set q) but n_sets %u != nq %u", n_sets, nq);
+    if (!queries || !out_pid || !out_dist || !out_count || (N && !allow_bits)) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    if (set_of)
+        for (uint32_t q = 0; q < nq; q++)
+            if (set_of[q] >= n_sets) return fail(IDIST_ERR_INVALID_ARG, "set_of[%u] = %u: query %u names a set outside [0,%u)", q, set_of[q], q, n_sets);
+    if (out_rung) std::fill(out_rung, out_rung + (size_t)nq * P, (uint32_t)IDIST_RUNG_NONE);   // (empty parts keep it)
+    p->al_slice_ms = 0.0f;
+    if (N == 0 || ef == 0) {                                                 // nothing to find, whatever the sets
+        for (size_t i = 0; i < (size_t)nq * k; i++) { out_pid[i] = IDIST_INVALID; out_dist[i] = INFINITY; }
+        memset(out_count, 0, (size_t)nq * 4);
+        if (out_counters) memset(out_counters, 0, (size_t)nq * 12);
+        return IDIST_OK;
+    }
+    const bool counters = out_counters != nullptr;
+    const size_t W = ((size_t)N + 31u) / 32u, row = (size_t)nq * k;
+    std::vector<uint32_t> own_set;                               // set_of == NULL: query q uses set q
+    if (!set_of) {
+        own_set.resize(nq);
+        for (uint32_t q = 0; q < nq; q++) own_set[q] = q;
+        set_of = own_set.data();
+    }
+    HIPCHK(hipSetDevice(p->merge_device));
+    CHK(partitioned_reserve(p, nq, k, k));
+    CHK(grow(p->s_rung, p->cap_s_rung, P * nq * 4));
+    CHK(partitioned_prepare_report(p, queries, nq));
+    // 1. the queries and the set of every query, once per distinct device that has something to search
+    CHK(partitioned_upload_queries(p, queries, nq));
+    for (size_t d = 0; d < p->devs.size(); d++) {
+        idist_partitioned::Dev& dv = p->devs[d];
+        bool used = false;
+        for (auto& pt : p->parts) used |= pt.ctx && pt.dev_slot == (int)d;
+        if (!used) continue;
+        HIPCHK(hipSetDevice(dv.device));
+        CHK(grow(dv.d_setof, dv.cap_setof, (size_t)nq * 4));
+        HIPCHK(hipMemcpy(dv.d_setof, set_of, (size_t)nq * 4, hipMemcpyHostToDevice));
+    }
+    // 2. every part's bitmaps: the words [base / 32, ceil((base + n_p) / 32)) of every set in ONE strided copy out of the caller's
+    //    buffer (which is only read), then the slice kernel shifts them by base % 32 on the part's stream — the part's own
+    //    [n_sets][(n_p + 31) / 32], the bits behind n_p cleared
+    const auto t0 = std::chrono::steady_clock::now();
+    for (size_t i = 0; i < P; i++) {
+        idist_partitioned::Part& pt = p->parts[i];
+        if (!pt.ctx) continue;
+        const uint32_t n_p = pt.idx->n, w0 = p->base[i] / 32u, sh = p->base[i] % 32u;
+        const size_t nw = ((size_t)sh + n_p + 31u) / 32u, words = ((size_t)n_p + 31u) / 32u;
+        HIPCHK(hipSetDevice(p->devs[pt.dev_slot].device));
+        CHK(grow(pt.ctx->al_raw.p, pt.ctx->al_raw.cap, (size_t)n_sets * nw * 4));
+        CHK(grow(pt.ctx->al_bits.p, pt.ctx->al_bits.cap, (size_t)n_sets * words * 4));
+        if (n_sets == 1) HIPCHK(hipMemcpy(pt.ctx->al_raw.p, allow_bits + w0, nw * 4, hipMemcpyHostToDevice));
+        else HIPCHK(hipMemcpy2D(pt.ctx->al_raw.p, nw * 4, allow_bits + w0, W * 4, nw * 4, n_sets, hipMemcpyHostToDevice));
+        const size_t total = (size_t)n_sets * words;
+        const uint32_t grid = (uint32_t)std::min<size_t>((total + 255u) / 256u, (size_t)std::max(pt.ctx->n_cu, 1) * 8u);
+        IDIST_LAUNCH(allowed_slice_kernel, grid, 256, 0, pt.ctx->stream, pt.ctx->al_raw.as<uint32_t>(), n_sets, (uint32_t)nw, (uint64_t)sh, n_p,
+                     pt.ctx->al_bits.as<uint32_t>());
+        HIPCHK(hipGetLastError());
+    }
+    for (size_t i = 0; i < P; i++) {                     // (waited for only to be timed: the ladders run on the same streams)
+        idist_partitioned::Part& pt = p->parts[i];
+        if (!pt.ctx || !pt.ctx->knobs.events) continue;
+        HIPCHK(hipSetDevice(p->devs[pt.dev_slot].device));
+        HIPCHK(hipStreamSynchronize(pt.ctx->stream));
+    }
+    p->al_slice_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    // 3. the ladders block on the host, one synchronisation per rung: one thread per non-empty part, each with the part's own context
+    //    and stream.  On the merge device straight into the part's slice of the staging memory, elsewhere into memory of the part's
+    //    device followed by one peer copy per array.  A worker keeps its status and message (g_err is thread-local).
+    std::vector<idist_status> st(P, IDIST_OK);
+    std::vector<std::string> msg(P);
+    auto part = [&](size_t i) -> idist_status {
+        idist_partitioned::Part& pt = p->parts[i];
+        idist_search_ctx* ctx = pt.ctx;
+        const idist_partitioned::Dev& dv = p->devs[pt.dev_slot];
+        const int32_t dev = dv.device;
+        uint32_t *s_pid = p->s_pid + i * row, *s_cnt = p->s_cnt + i * nq, *s_ctr = p->s_ctr + i * nq * 3, *s_rung = p->s_rung + i * nq;
+        float* s_dist = p->s_dist + i * row;
+        HIPCHK(hipSetDevice(dev));
+        AllowedOut o{};
+        if (dev == p->merge_device) {
+            o.pid = s_pid; o.dist = reinterpret_cast<uint32_t*>(s_dist); o.count = s_cnt; o.rung = s_rung; o.counters = counters ? s_ctr : nullptr;
+        } else {
+            CHK(grow(ctx->al_opid.p, ctx->al_opid.cap, row * 4));
+            CHK(grow(ctx->al_odist.p, ctx->al_odist.cap, row * 4));
+            CHK(grow(ctx->al_ocnt.p, ctx->al_ocnt.cap, (size_t)nq * 4));
+            CHK(grow(ctx->al_orung.p, ctx->al_orung.cap, (size_t)nq * 4));
+            CHK(grow(ctx->al_octr.p, ctx->al_octr.cap, (size_t)nq * 12));
+            o.pid = ctx->al_opid.as<uint32_t>(); o.dist = ctx->al_odist.as<uint32_t>(); o.count = ctx->al_ocnt.as<uint32_t>();
+            o.rung = ctx->al_orung.as<uint32_t>(); o.counters = counters ? ctx->al_octr.as<uint32_t>() : nullptr;
+        }
+        CHK(allowed_sets_device(pt.idx, ctx, dv.d_q, nq, ctx->al_bits.as<uint32_t>(), n_sets, dv.d_setof, set_of, k, max_rungs, o));
+        if (dev != p->merge_device) {
+            HIPCHK(hipMemcpyPeerAsync(s_pid, p->merge_device, o.pid, dev, row * 4, ctx->stream));
+            HIPCHK(hipMemcpyPeerAsync(s_dist, p->merge_device, o.dist, dev, row * 4, ctx->stream));
+            HIPCHK(hipMemcpyPeerAsync(s_cnt, p->merge_device, o.count, dev, (size_t)nq * 4, ctx->stream));
+            HIPCHK(hipMemcpyPeerAsync(s_rung, p->merge_device, o.rung, dev, (size_t)nq * 4, ctx->stream));
+            if (counters) HIPCHK(hipMemcpyPeerAsync(s_ctr, p->merge_device, o.counters, dev, (size_t)nq * 12, ctx->stream));
+        }
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        return allowed_times_resolve(ctx);
+    };
+    auto work = [&](size_t i) {
+        st[i] = part(i);
+        if (st[i] != IDIST_OK) msg[i] = g_err;
+    };
+    {
+        std::vector<std::thread> threads;
+        long first = -1;                                 // the first non-empty part runs on the calling thread
+        for (size_t i = 0; i < P; i++) {
+            if (!p->parts[i].ctx) continue;
+            if (first < 0) { first = (long)i; continue; }
+            try {
+                threads.emplace_back(work, i);
+            } catch (...) {                              // no thread to be had: the part runs here, after the others were started
+                work(i);
+            }
+        }
+        if (first >= 0) work((size_t)first);
+        for (auto& t : threads) t.join();                // every thread is joined before any return
+    }
+    for (size_t i = 0; i < P; i++)
+        if (st[i] != IDIST_OK) return fail(st[i], "part %zu (device %d): %s", i, p->devs[p->parts[i].dev_slot].device, msg[i].c_str());
+    // 4. the union: empty parts hand in lists of length 0; the parts' rungs come back [P][nq] and are transposed on the host
+    HIPCHK(hipSetDevice(p->merge_device));
+    for (size_t i = 0; i < P; i++) {
+        if (p->parts[i].ctx) continue;
+        HIPCHK(hipMemsetAsync(p->s_cnt + i * nq, 0, (size_t)nq * 4, p->stream));
+        if (counters) HIPCHK(hipMemsetAsync(p->s_ctr + i * nq * 3, 0, (size_t)nq * 12, p->stream));
+    }
+    std::vector<uint32_t> rungs;
+    if (out_rung) {
+        rungs.resize(P * nq);
+        HIPCHK(hipMemcpyAsync(rungs.data(), p->s_rung, P * nq * 4, hipMemcpyDeviceToHost, p->stream));
+    }
+    CHK(partitioned_merge(p, nq, k, k, counters, out_pid, out_dist, out_count, out_counters));
+    if (out_rung)
+        for (size_t i = 0; i < P; i++) {
+            if (!p->parts[i].ctx) continue;
+            for (uint32_t q = 0; q < nq; q++) out_rung[(size_t)q * P + i] = rungs[i * nq + q];
+        }
+    return IDIST_OK;
+}
+
+idist_status idist_partitioned_last_allowed_slice_ms(idist_partitioned* p, float* ms) {
+    if (!p || !ms) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    *ms = p->al_slice_ms;
+    return IDIST_OK;
 }
 
 idist_status idist_search_ctx_allowed_kernel_ms(idist_search_ctx* ctx, float* select_ms, float* pending_ms, float* exact_ms) {

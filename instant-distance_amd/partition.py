@@ -19,8 +19,8 @@ from typing import Sequence
 import numpy as np
 
 from . import _capi
-from ._capi import INVALID, METRIC_DOT
-from .api import BatchResult, Builder, Hnsw, Item, _as_points
+from ._capi import INVALID, METRIC_DOT, RUNG_NONE
+from .api import AllowedResult, BatchResult, Builder, Hnsw, Item, _as_points, allowed_bitmap, allowed_bitmaps
 from .dist import shard_range
 
 
@@ -166,6 +166,67 @@ class PartitionedHnsw:
         """One query: the merged items, nearest first; `Item.pid` is the global id."""
         r = self.search_batch(np.asarray(point, dtype=np.float32).reshape(1, -1))
         return [Item(float(r.distance[0, i]), int(r.pid[0, i]), self[int(r.pid[0, i])]) for i in range(int(r.count[0]))]
+
+    def search_allowed_sets(self, queries, sets, set_of, k: int, max_rungs: int = -1, counters: bool = False) -> AllowedResult:
+        """The k nearest among an allowed subset, several sets in one call, one per query
+        (idist_partitioned_search_batch_allowed_sets): `Hnsw.search_allowed_sets` on every part with the slice of each set that
+        falls into it, merged — exactly min(k, allowed points) results per query, global ids.  `sets` names GLOBAL ids: a sequence of
+        bool masks of length len(self) or of global-id arrays, a 2-D bool array [n_sets][len(self)] or a ready uint32 bitmap
+        [n_sets][(len(self) + 31) // 32].  `set_of`: the set index of every query; None: query q uses set q.  `AllowedResult.rung` has
+        shape (nq, n_parts): every part climbs its own ladder (a part that holds none of a query's allowed points answers RUNG_NONE
+        at once; one where they are rare scans them exactly)."""
+        q = _as_points(queries)
+        info = self.info()
+        n, P = int(info.n), int(info.n_parts)
+        if q.shape[0] and n and q.shape[1] != info.dim:
+            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
+        bits = allowed_bitmaps(sets, n)
+        nq, k, n_sets = q.shape[0], int(k), bits.shape[0]
+        if set_of is None:
+            if n_sets != nq:
+                raise ValueError(f"set_of=None means one set per query: {n_sets} sets for {nq} queries")
+            so = None
+        else:
+            so = np.asarray(set_of)
+            if so.size and not np.issubdtype(so.dtype, np.integer):
+                raise TypeError("`set_of` is an integer array of set indices, one per query")
+            if so.shape != (nq,):
+                raise ValueError(f"`set_of` must have one entry per query: shape ({nq},), got {so.shape}")
+            if so.size and (so.min() < 0 or so.max() >= n_sets):
+                raise IndexError(f"`set_of` names a set outside [0, {n_sets})")
+            so = np.ascontiguousarray(so.astype(np.uint32))
+        kk = max(k, 0)
+        pid = np.full((nq, kk), INVALID, dtype=np.uint32)
+        dist = np.full((nq, kk), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        rung = np.full((nq, P), RUNG_NONE, dtype=np.uint32)
+        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
+        if n_sets == 0 and nq == 0:
+            return AllowedResult(pid, dist, cnt, rung, ctr)
+        L = _lib()
+        L.check(L.idist_partitioned_search_batch_allowed_sets(self._h, _capi.f32p(q), nq, _capi.u32p(bits), n_sets,
+                                                              _capi.u32p(so) if so is not None else None, kk, int(max_rungs),
+                                                              _capi.u32p(pid), _capi.f32p(dist), _capi.u32p(cnt), _capi.u32p(rung),
+                                                              _capi.u32p(ctr) if counters else None))
+        return AllowedResult(pid, dist, cnt, rung, ctr)
+
+    def search_allowed(self, queries, allowed, k: int, max_rungs: int = -1, counters: bool = False) -> AllowedResult:
+        """`search_allowed_sets` with ONE set shared by the batch: `allowed` is a bool mask of length len(self) or an integer array
+        of global ids (`allowed_bitmap`'s rules)."""
+        q = _as_points(queries)
+        bits = allowed_bitmap(allowed, len(self)).reshape(1, -1)
+        return self.search_allowed_sets(q, bits, np.zeros(q.shape[0], dtype=np.uint32), k, max_rungs=max_rungs, counters=counters)
+
+    def search_one_allowed(self, point, allowed, k: int) -> list[Item]:
+        """One query: its min(k, allowed points) nearest allowed items, nearest first; `Item.pid` is the global id."""
+        r = self.search_allowed(np.asarray(point, dtype=np.float32).reshape(1, -1), allowed, k)
+        return [Item(float(r.distance[0, i]), int(r.pid[0, i]), self[int(r.pid[0, i])]) for i in range(int(r.count[0]))]
+
+    def last_allowed_slice_ms(self) -> float:
+        """Host time the last restricted search spent on the bitmaps (the parts' strided uploads + slice kernels), milliseconds."""
+        ms = C.c_float(0.0)
+        _lib().check(_lib().idist_partitioned_last_allowed_slice_ms(self._h, C.byref(ms)))
+        return float(ms.value)
 
     def bruteforce(self, queries, k: int) -> tuple[np.ndarray, np.ndarray]:
         """Exact k-NN over all parts (global ids, ties by id): every part's exhaustive scan, merged."""
