@@ -1413,11 +1413,31 @@ constexpr uint32_t kLongWalkEf = 512u;   // ef_search from which wide on-chip ba
 // kept.  Gathering the rows with the non-temporal hint (leaving the cache to the bitmaps) costs 11-15 % at every ef_search and 30 % of
 // the build (`make nt`, profiles/r05/probe_r05e_rows_nontemporal_ab_c3.jsonl): the row gathers live on Infinity-Cache hits too.
 // The compact copy of the rows behind the walk's reject filter (FilterView): made once per index, here.  The lattice [lo, lo + 255
-// step] comes from a sample of the rows (mean +- 5 sigma of the coordinates, clipped to the sample's range): its choice decides how
-// many candidates the filter can reject, never a result — a coordinate outside it is clamped and its error is part of the row's
-// recorded |p - p^|.  Runs on the null stream and waits for it (an index is immutable once it is searched; its rows are in place).
-// Geometries the search kernels have no filter tile for (compact rows beyond four 128-B chunks without a compile-time instantiation)
-// and indexes the copy finds no memory for simply run without it.
+// step] comes from a sample of up to 2048 rows: mean +- 5 sigma of the central 98 % of the sampled coordinates (sigma rescaled to
+// the whole of a Gaussian), clipped to the sample's range + a quarter sigma.  Its choice decides how many candidates the filter can
+// reject, never a result — a coordinate outside it is clamped and its error is part of the row's recorded |p - p^|.  Runs on the
+// null stream and waits for it (an index is immutable once it is searched; its rows are in place).
+// Geometries the search kernels have no filter tile for (no compile-time instantiation and a compact row beyond the fat tile's
+// thirteen 128-B chunks; the thin tile holds five), indexes the copy finds no memory for and indexes whose lattice step lies
+// outside [kFilterMinStep256, kFilterMaxStep256] simply run without it (filt_state = 2).
+//
+// The scale range.  The test of filter_rounds, dh = (float)I * dscale > ((st + E) up)^2, is a proof only while every float step in
+// it and in the canonical chain it speaks about has a RELATIVE error of 2^-24 — `up` is made of such errors — so nothing on the
+// way may be a denormal, and with step256 = s the quantities are tied to s:
+//   * dscale = s^2 >= 2^-116 is normal, and I is an integer, so dh is 0 or >= dscale: normal too.  (Below s ~ 1e-19, dscale has
+//     a handful of significant bits — at 2^-74 it is 12 % too large and every bound exceeded the distance — and below 3.7e-23 it is 0.)
+//   * E >= fq.eq >= slack * mag >= 4.8e-7 sqrt(dim) 65536 s = 2^-5 sqrt(dim) s, so the right-hand side is >= 2^-10 dim s^2: normal.
+//   * filter_stage_query's e * e terms may underflow (|e| <= s / 2, and any smaller): each loses at most 2^-150, sqrt(dim) 2^-75 in
+//     |q - q^| — a 4096th of slack * mag >= sqrt(dim) 2^-63, which is twice what the f32 evaluation of e needs.
+//   * the canonical chain's terms (q_k - p_k)^2 may underflow for a pair the filter rejects: its float result is then up to
+//     dim 2^-150 below what `up` accounts for.  A rejected pair has |q - p| >= st up' + E (up' - 1) with up' - 1 >= 2^-11, so its
+//     squared distance clears st^2 (1 + 2^-10) by E^2 2^-22 >= 2^-32 dim s^2 >= dim 2^-148: the underflow cannot bring it to st^2.
+//   * upwards dscale must stay finite (inf * I would "prove" anything); dh itself may overflow to +inf — then the exact product
+//     is beyond FLT_MAX and a finite right-hand side is still exceeded (idist_filter_bound_batch clamps it to report a finite bound).
+// So the filter is active for 2^-58 <= step256 <= 2^60 — a spread (hi - lo) of the bulk of the coordinates between 2^-42 (2.3e-13)
+// and 2^76 (7.6e22), wherever the data sits — and such data is ordinary: at the lower end typical squared distances are dim 1e-26,
+// at the upper end they overflow.  Outside it every walk is the unfiltered one (tests/test_data_scale.py runs both sides).
+constexpr float kFilterMinStep256 = 0x1p-58f, kFilterMaxStep256 = 0x1p60f;
 bool filter_applies(const idist_index* ix) {
     return ix->n > 0 && (has_template_geometry(ix->L) || filt_stride(ix->L.stride) <= 128u * (uint32_t)kFiltRtChunksFat);
 }
@@ -1465,6 +1485,10 @@ idist_status filter_ensure(const idist_index* ix) {
     f.fstride = fs;
     f.lo = (float)lo;
     f.step256 = (float)((hi - lo) / 65280.0);                            // 255 steps of 256 sub-steps
+    if (!(f.step256 >= kFilterMinStep256 && f.step256 <= kFilterMaxStep256)) {      // (see above: the bound would be no proof)
+        ix->filt_state.store(2, std::memory_order_release);
+        return IDIST_OK;
+    }
     f.qscale = 1.0f / f.step256;
     f.dscale = f.step256 * f.step256;
     // every float step of the test (the conversion of I, dscale, the sums, the canonical chain of dim / 8 + 7 roundings) is covered

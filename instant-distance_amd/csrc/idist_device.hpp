@@ -61,7 +61,7 @@ struct FilterView {
     uint32_t fstride = 0;            // bytes per compact row: stride codes + 8 bytes of metadata, rounded up to 64
     float lo = 0.0f, step256 = 0.0f; // lattice: p^ = lo + (256 u) * step256, q^ = lo + Q * step256 (Q: 16 bits)
     float qscale = 0.0f;             // 1 / step256
-    float dscale = 0.0f;             // step256^2: |q^ - p^|^2 = I * dscale
+    float dscale = 0.0f;             // step256^2: |q^ - p^|^2 = I * dscale (a normal float: filter_ensure refuses lattices outside 2^-58 <= step256 <= 2^60)
     float up = 1.0f;                 // safety factor > 1 on the threshold side (rounding of every float step, of the canonical sum)
     float slack = 0.0f;              // absolute slack of a query's own lattice error (f32 evaluation), per sqrt(dim) * magnitude
 };
@@ -822,7 +822,9 @@ __device__ __forceinline__ void filter_rounds(const IndexView& ix, const FilterQ
             const float dh = (float)I * ix.f.dscale;                      // |q^ - p^|^2
             if constexpr (BOUND) {
                 // rejected iff dh > ((st + E) up)^2  <=>  st < sqrt(dh) / up - E: that supremum, rounded down
-                float b = __builtin_sqrtf(dh) * 0.999999f / ix.f.up - (__uint_as_float(ep) + fq.eq) * 1.000001f;
+                // (dh = +inf: the exact product is beyond FLT_MAX, any finite value is below it; NaN stays NaN)
+                const float dhb = dh > 3.0e38f ? 3.0e38f : dh;
+                float b = __builtin_sqrtf(dhb) * 0.999999f / ix.f.up - (__uint_as_float(ep) + fq.eq) * 1.000001f;
                 b = b > 0.0f ? b : 0.0f;                                  // (NaN: 0 — no bound)
                 act_dist[kf] = __float_as_uint(ix.metric ? b : b * b * 0.999999f);
             } else {

@@ -145,7 +145,10 @@ def bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
-def gen_points(rng, n, dim, kind="uniform"):
+def gen_points(rng, n, dim, kind="uniform", scale=0):
+    """scale: the coordinates times 2^scale — an exact rescaling of every f32 operation until something under- or overflows"""
+    if scale:
+        return np.ldexp(gen_points(rng, n, dim, kind), scale).astype(np.float32)
     if kind == "uniform":        # what the reference's tests use (tests/all.rs:59, test.py:5)
         return rng.random((n, dim), dtype=np.float32)
     if kind == "grid":           # integer coordinates: exact ties in the distance (examples/colors.rs style)
@@ -219,10 +222,10 @@ def check_search_parity(ida, oracle, n, dim, ef_search=100, metric=0, kind="unif
 
 
 def check_build_exact(ida, oracle, n, dim, metric=0, kind="uniform", ef_construction=100, keep_pruned=True, seed=0,
-                      heuristic=True, extend=False, max_batch=1, variants=None):
+                      heuristic=True, extend=False, max_batch=1, variants=None, scale=0):
     """max_batch = 1: zero/layers byte-identical to the oracle's sequential build."""
     rng = np.random.default_rng(seed)
-    pts = gen_points(rng, n, dim, kind)
+    pts = gen_points(rng, n, dim, kind, scale)
     cfg = oracle.default_config(metric=metric, ef_construction=ef_construction, keep_pruned=int(keep_pruned),
                                 has_heuristic=int(heuristic), extend_candidates=int(extend))
     oix = oracle.Index.build(pts, cfg, threads=1)

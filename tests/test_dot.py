@@ -197,12 +197,12 @@ def test_augment_refusals(eng, oracle):
 _GRAPHS = {}
 
 
-def dot_graph(oracle, n, dim, seed=11):
-    """raw rows, x~, S and the oracle's L2SQ graph over x~ (cached: ef_search does not enter a build)"""
-    key = (n, dim, seed)
+def dot_graph(oracle, n, dim, seed=11, scale=0):
+    """raw rows (times 2^scale), x~, S and the oracle's L2SQ graph over x~ (cached: ef_search does not enter a build)"""
+    key = (n, dim, seed, scale)
     if key not in _GRAPHS:
         rng = np.random.default_rng(seed)
-        x = scaled_rows(rng, n, dim, "uniform")
+        x = np.ldexp(scaled_rows(rng, n, dim, "uniform"), scale).astype(np.float32)
         xa, Sb, _ = np_augment(oracle, x)
         o = oracle.Index.build(xa, oracle.default_config(metric=0), threads=8 if n > 1000 else 1)
         _GRAPHS.clear()
@@ -210,8 +210,8 @@ def dot_graph(oracle, n, dim, seed=11):
     return _GRAPHS[key]
 
 
-def check_dot_search(ida, oracle, kind, n, dim, ef, wide):
-    x, xa, Sb, zero, layers = dot_graph(oracle, n, dim)
+def check_dot_search(ida, oracle, kind, n, dim, ef, wide, scale=0):
+    x, xa, Sb, zero, layers = dot_graph(oracle, n, dim, scale=scale)
     oix = oracle.Index.from_arrays(xa, zero, layers, oracle.default_config(metric=0, ef_search=ef))
     h = ida.Hnsw.from_parts(x, zero, layers, dot_builder(ida, ef))          # raw rows: the import augments
     info = h.info()
@@ -219,7 +219,7 @@ def check_dot_search(ida, oracle, kind, n, dim, ef, wide):
     rng = np.random.default_rng(1000 * dim + ef)
     search = ida.Search()
     for nq in (7, wide, 1):
-        q = scaled_rows(rng, nq, dim, "uniform")
+        q = np.ldexp(scaled_rows(rng, nq, dim, "uniform"), scale).astype(np.float32)
         if nq > 2:
             q[1] = x[min(5, n - 1)] * np.float32(4.0)
         keep = q.copy()
