@@ -506,6 +506,49 @@ idist_status idist_allowed_slice_device(const void* d_bits, uint32_t n_sets, uin
  * the exact step (scan + merge).  0 with IDIST_KERNEL_EVENTS=0.  The rungs' own search kernels are in idist_search_ctx_kernel_times. */
 idist_status idist_search_ctx_allowed_kernel_ms(idist_search_ctx* ctx, float* select_ms, float* pending_ms, float* exact_ms);
 
+/* ---- range search: every point within a radius ------------------------------------------------------- */
+/* Defined, as the restricted search is, through Hnsw::search at growing ef_search and an exact scan where that ladder ends.  The
+ * walk itself is not touched.
+ *   radius     one f32 for the batch (n_radius == 1) or one per query (n_radius == nq).  NaN is IDIST_ERR_INVALID_ARG (the message
+ *              names the query); +inf, 0, -0.0 and negative radii are legal (IDIST_METRIC_DOT reports about -q.x).
+ *   max_rungs  as in idist_search_batch_allowed: -1 the whole ladder, m >= 0 only the rungs r < m, 0 the exact scan alone (the
+ *              ground truth for recall).  The ladder is that call's: E[0] = ef_search, E[r + 1] = min(4 * E[r], IDIST_MAX_EF).
+ *   within     point x is within the radius of query q iff report(d) <= r_q as an f32 comparison: d the RAW canonical distance of the
+ *              stored row (what idist_search_batch holds before its report pass), report the metric's: the identity for L2SQ and L2,
+ *              0.5f * d for cosine, 0.5f * (d - (s(q) + S)) for DOT with +inf and NaN reported unchanged.  A NaN distance is never
+ *              within.  report is non-decreasing in d (every float step is monotone), so the entries of a sorted list that are
+ *              within are a prefix of it.
+ * For one query:
+ *   1. n == 0 or ef_search == 0: count 0, rung IDIST_RUNG_NONE.
+ *   2. For r = 0, 1, ... among the permitted rungs: L = the result of Hnsw::search at ef_search = E[r], c entries.  c == E[r] and
+ *      every entry within: the list is saturated, the next rung runs.  Otherwise the answer is the prefix of L that is within, in L's
+ *      order; rung = r; stop (a count of 0 is an answer).
+ *   3. The ladder ended saturated, or max_rungs == 0: exact — every point within the radius, ordered by (raw distance bits, id);
+ *      rung IDIST_RUNG_EXACT.
+ *   4. Reported distances are report(d), applied once, at the end.
+ *   5. out_counters sums {n_dist, n_exp0, n_expU} over the rungs the query ran; the exact step adds nothing.
+ * A later rung that does not fit a wave's LDS ends the ladder as max_rungs would (on rung 0 the failure is returned), and a strict-tie
+ * overflow is retried and never reaches the caller, as in idist_search_batch_allowed.  What a rung returns for a query does not depend
+ * on who else is pending: every row of the batch is what the call returns for that query alone.
+ *   out_lims   [nq + 1], lims[0] = 0: query q owns the entries [lims[q], lims[q + 1]) of the flat pid / distance arrays
+ *              idist_search_ctx_range_fetch hands out.  out_rung [nq], out_counters [nq][3]: may be NULL.
+ *   max_total  the caller's bound on lims[nq].  When the results known after a step (a rung, the exact step) exceed it the call returns
+ *              IDIST_ERR_INVALID_ARG — the message says how many were known by then — and the context holds no results: nothing is
+ *              truncated silently.
+ * Host pointers; the call blocks until done.  ctx is the `&mut Search`: it owns the staging and keeps the results until the next
+ * range call or until they are fetched; idx is never mutated.  nq == 0: lims[0] = 0. */
+idist_status idist_search_batch_range(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
+                                      const float* radius, uint32_t n_radius, int32_t max_rungs, uint64_t max_total,
+                                      uint64_t* out_lims, uint32_t* out_rung, uint32_t* out_counters);
+/* The results of the last successful idist_search_batch_range through ctx: out_pid / out_dist [lims[nq]] each (may be NULL when that is
+ * 0), in query order, reported distances.  They are handed out once: a fetch without a preceding successful range call (or a second
+ * one) is IDIST_ERR_INVALID_ARG. */
+idist_status idist_search_ctx_range_fetch(idist_search_ctx* ctx, uint32_t* out_pid, float* out_dist);
+/* HIP-event durations (ms) of the kernels the last idist_search_batch_range through ctx ran around its searches: the select passes
+ * (limits, within-prefixes, offsets, copies, pending lists), the exact step's two scans with their offsets, the sort.  0 with
+ * IDIST_KERNEL_EVENTS=0.  The rungs' own search kernels are in idist_search_ctx_kernel_times. */
+idist_status idist_search_ctx_range_kernel_ms(idist_search_ctx* ctx, float* select_ms, float* scan_ms, float* sort_ms);
+
 /* Point::distance for id lists (core/lib.rs:780-782 as used at :709-710): out[q][i] =
  * distance(queries[q], points[ids[q][i]]) for i < n_ids; IDIST_INVALID ids give +inf.
  * Host pointers. The batched gather-L2 kernel on its own. */

@@ -92,6 +92,7 @@ class PartitionedInfo(C.Structure):
 # every symbol include/idist.h declares: name -> (restype, argtypes)
 _f32p = C.POINTER(C.c_float)
 _u32p = C.POINTER(C.c_uint32)
+_u64p = C.POINTER(C.c_uint64)
 _vp = C.c_void_p
 SYMBOLS = {
     "idist_last_error": (C.c_char_p, []),
@@ -143,6 +144,9 @@ SYMBOLS = {
     "idist_search_batch_allowed_sets": (C.c_int32, [_vp, _vp, _f32p, C.c_uint32, _u32p, C.c_uint32, _u32p, C.c_uint32, C.c_int32, _u32p,
                                                     _f32p, _u32p, _u32p, _u32p]),
     "idist_search_ctx_allowed_kernel_ms": (C.c_int32, [_vp, _f32p, _f32p, _f32p]),
+    "idist_search_batch_range": (C.c_int32, [_vp, _vp, _f32p, C.c_uint32, _f32p, C.c_uint32, C.c_int32, C.c_uint64, _u64p, _u32p, _u32p]),
+    "idist_search_ctx_range_fetch": (C.c_int32, [_vp, _u32p, _f32p]),
+    "idist_search_ctx_range_kernel_ms": (C.c_int32, [_vp, _f32p, _f32p, _f32p]),
     "idist_partitioned_search_batch_allowed_sets": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, _u32p, C.c_uint32, C.c_int32,
                                                                 _u32p, _f32p, _u32p, _u32p, _u32p]),
     "idist_partitioned_last_allowed_slice_ms": (C.c_int32, [_vp, C.POINTER(C.c_float)]),
@@ -213,3 +217,7 @@ def f32p(a: np.ndarray):
 
 def u32p(a: np.ndarray):
     return a.ctypes.data_as(_u32p)
+
+
+def u64p(a: np.ndarray):
+    return a.ctypes.data_as(_u64p)

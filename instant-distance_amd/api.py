@@ -264,6 +264,13 @@ class Search:
         _lib().check(_lib().idist_search_ctx_allowed_kernel_ms(self._ctx, C.byref(a), C.byref(b), C.byref(c)))
         return float(a.value), float(b.value), float(c.value)
 
+    def range_kernel_ms(self) -> tuple[float, float, float]:
+        """HIP-event time (ms) of the select passes (limits, within-prefixes, offsets, copies, pending lists), the exact step's two
+        scans and the sort of the last `search_range` through this Search; the rungs' own search kernels are in `kernel_times_ms`."""
+        a, b, c = C.c_float(0), C.c_float(0), C.c_float(0)
+        _lib().check(_lib().idist_search_ctx_range_kernel_ms(self._ctx, C.byref(a), C.byref(b), C.byref(c)))
+        return float(a.value), float(b.value), float(c.value)
+
     def kernel_times_ms(self, last: int = 64) -> np.ndarray:
         """HIP-event durations of the most recent search kernels launched through this Search."""
         out = np.zeros(last, dtype=np.float32)
@@ -336,6 +343,16 @@ class AllowedResult:
     distance: np.ndarray  # [nq, k] float32, +inf padded
     count: np.ndarray     # [nq]
     rung: np.ndarray      # [nq] the rung of the ef ladder that answered the query, RUNG_EXACT (the scan of the allowed rows) or RUNG_NONE
+    counters: np.ndarray | None  # [nq, 3] {n_dist, n_exp0, n_expU} summed over the rungs the query ran
+
+
+@dataclass
+class RangeResult:
+    """`Hnsw.search_range`: query q owns the entries [lims[q], lims[q + 1]) of `pid` and `distance`, nearest first."""
+    lims: np.ndarray      # [nq + 1] uint64, lims[0] = 0
+    pid: np.ndarray       # [lims[nq]] uint32
+    distance: np.ndarray  # [lims[nq]] float32, as the metric reports them
+    rung: np.ndarray      # [nq] the rung of the ef ladder that answered the query, RUNG_EXACT (the scan of every row) or RUNG_NONE
     counters: np.ndarray | None  # [nq, 3] {n_dist, n_exp0, n_expU} summed over the rungs the query ran
 
 
@@ -580,6 +597,35 @@ class Hnsw:
                                              _capi.f32p(dist), _capi.u32p(cnt), _capi.u32p(rung), _capi.u32p(ctr) if counters else None))
         return AllowedResult(pid, dist, cnt, rung, ctr)
 
+    def search_range(self, queries, radius, search: Search, max_rungs: int = -1, max_total: int = 64 * 2**20,
+                     counters: bool = False) -> RangeResult:
+        """Every point within `radius` of each query (idist_search_batch_range): `Hnsw::search` at ef_search, 4 ef_search, ... 4096
+        while a rung's list is full and wholly within the radius — the first list that is not answers with its within-prefix — and an
+        exact scan of every row where the ladder ends.  `radius`: a float for the batch or an array of one per query, compared with the
+        distances the metric reports (`<=`); NaN is refused.  `max_rungs`: -1 the whole ladder, m only its first m rungs, 0 the exact
+        scan alone (the ground truth for recall).  `max_total` bounds the number of results of the whole batch: beyond it the call
+        raises instead of truncating (the default, 64 Mi results = 512 MB of keys on the device, is a choice, not a measurement)."""
+        q = _as_points(queries)
+        info = self.info()
+        if q.shape[0] and info.n and q.shape[1] != info.dim:
+            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
+        nq = q.shape[0]
+        rad = np.ascontiguousarray(np.asarray(radius, dtype=np.float32).reshape(-1))
+        if rad.size != 1 and rad.size != nq:
+            raise ValueError(f"`radius` is one float or an array of nq = {nq}, got {rad.size}")
+        lims = np.zeros(nq + 1, dtype=np.uint64)
+        rung = np.full(nq, RUNG_NONE, dtype=np.uint32)
+        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
+        ctx = search._bind(self)
+        L = _lib()
+        L.check(L.idist_search_batch_range(self._h, ctx, _capi.f32p(q), nq, _capi.f32p(rad), int(rad.size), int(max_rungs), int(max_total),
+                                           _capi.u64p(lims), _capi.u32p(rung), _capi.u32p(ctr) if counters else None))
+        total = int(lims[nq])
+        pid = np.zeros(total, dtype=np.uint32)
+        dist = np.zeros(total, dtype=np.float32)
+        L.check(L.idist_search_ctx_range_fetch(ctx, _capi.u32p(pid), _capi.f32p(dist)))
+        return RangeResult(lims, pid, dist, rung, ctr)
+
     def search_allowed_sets(self, queries, sets, set_of, k: int, search: Search, max_rungs: int = -1, counters: bool = False) -> AllowedResult:
         """`search_allowed` with several allowed sets in one call, one per query (idist_search_batch_allowed_sets): row q is exactly
         what `search_allowed(queries[q], sets[set_of[q]], k, ...)` returns.  `sets`: a sequence of bool masks or of PointId arrays
@@ -739,6 +785,12 @@ class HnswMap:
         r = self.hnsw.search_allowed(queries, allowed, k, search, max_rungs)
         return [[MapItem(float(r.distance[i, j]), int(r.pid[i, j]), self.hnsw.points[int(r.pid[i, j])], self.values[int(r.pid[i, j])])
                  for j in range(int(r.count[i]))] for i in range(r.pid.shape[0])]
+
+    def search_range(self, queries, radius, search: Search, max_rungs: int = -1, max_total: int = 64 * 2**20) -> list[list[MapItem]]:
+        """`Hnsw.search_range` with the values: per query every result within its radius as `MapItem`s, nearest first."""
+        r = self.hnsw.search_range(queries, radius, search, max_rungs, max_total)
+        return [[MapItem(float(r.distance[j]), int(r.pid[j]), self.hnsw.points[int(r.pid[j])], self.values[int(r.pid[j])])
+                 for j in range(int(r.lims[i]), int(r.lims[i + 1]))] for i in range(len(r.lims) - 1)]
 
     def search_allowed_sets(self, queries, sets, set_of, k: int, search: Search, max_rungs: int = -1) -> list[list[MapItem]]:
         """`Hnsw.search_allowed_sets` with the values: per query its min(k, points of its set) results as `MapItem`s, nearest first."""

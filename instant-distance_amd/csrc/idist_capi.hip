@@ -9,6 +9,7 @@
 #include "idist_normalize.hpp"
 #include "idist_dot.hpp"
 #include "idist_allowed.hpp"
+#include "idist_range.hpp"
 
 #ifndef IDIST_EMU
 #include <hip/hip_runtime.h>
@@ -33,6 +34,8 @@
 #include <vector>
 
 using namespace idist;
+static_assert(kRangeCosine == IDIST_METRIC_COSINE && kRangeDot == IDIST_METRIC_DOT && kRungNone == IDIST_RUNG_NONE && kRungExact == IDIST_RUNG_EXACT,
+              "idist_range.hpp / idist_allowed.hpp restate constants of include/idist.h");
 
 // (The HIP runtime multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues — default 4, read once when the
 // runtime starts.  One `Search` per host thread = one stream per thread: a host that runs more than four of them sets
@@ -310,6 +313,9 @@ struct Knobs {
     uint32_t w2_ef = 0xFFFFFFFFu; // IDIST_W2_EF=<ef>: from this ef_search on, wide on-chip batches run two 256-register waves per SIMD (A/B knob; default: policy)
     uint32_t allowed_segments = 0;    // IDIST_ALLOWED_SEGMENTS=<1..64>: segments of the exact step of a restricted search (test knob: the result
                                       // must not depend on it; default: by the number of pending queries)
+    uint32_t range_segments = 0;      // IDIST_RANGE_SEGMENTS=<1..64>: segments of the exact step of a range search (test knob, as allowed_segments)
+    uint32_t range_sort_chunk = 0;    // IDIST_RANGE_SORT_CHUNK=<128..4096, a power of two>: keys a wave of the range search's sort holds in
+                                      // LDS (test knob: small chunks send short lists through the global-memory strides; default 2048)
     uint32_t quad_nq = 0xFFFFFFFFu;   // IDIST_QUAD_NQ: batches up to this many queries run four waves per query (default: two
                                       // workgroups per CU, one for 768-d rows; 0 = never)
     static Knobs from_env() {
@@ -318,6 +324,11 @@ struct Knobs {
         if (const char* e = test_env("IDIST_EA")) k.ea = atoi(e);
         if (const char* e = test_env("IDIST_W2_EF")) k.w2_ef = (uint32_t)strtoul(e, nullptr, 10);
         if (const char* e = test_env("IDIST_ALLOWED_SEGMENTS")) k.allowed_segments = std::min(64u, (uint32_t)std::max(0, atoi(e)));
+        if (const char* e = test_env("IDIST_RANGE_SEGMENTS")) k.range_segments = std::min(64u, (uint32_t)std::max(0, atoi(e)));
+        if (const char* e = test_env("IDIST_RANGE_SORT_CHUNK")) {
+            const uint32_t c = (uint32_t)std::max(0, atoi(e));
+            if (c >= 128u && c <= 4096u && (c & (c - 1u)) == 0u) k.range_sort_chunk = c;
+        }
         if (const char* e = test_env("IDIST_LATENCY_NQ")) k.latency_nq = (uint32_t)strtoul(e, nullptr, 10);
         if (const char* e = test_env("IDIST_QUAD_NQ")) k.quad_nq = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 0xFFFFFFFEul);
         if (const char* e = test_env("IDIST_WALK")) k.classic = e[0] == 'c';      // (honoured by the test build only, see variants_check)
@@ -397,7 +408,16 @@ struct idist_search_ctx {
     hipEvent_t al_ev[kAllowedEvents] = {nullptr};    // (created on first use, resolved when the call has synchronised its stream)
     uint8_t al_ev_which[kAllowedEvents / 2] = {0};
     uint32_t al_ev_used = 0;
-    float al_ms[3] = {0.0f, 0.0f, 0.0f};   // the last call's select, pending and scan + merge kernels, summed over its rungs
+    float al_ms[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // the last call's select, pending and scan + merge kernels, summed over its
+                                                             // rungs; [3..5]: the last range search's select, scan and sort kernels
+    // staging of idist_search_batch_range (grow-only, freed with the context).  What idist_search_ctx_range_fetch needs lives in rg_*
+    // buffers no other call writes: the keys in completion order, every query's count, offset and report term.  The pending flags /
+    // list / gathered rows, rungs and counters use the restricted search's al_* buffers, the rungs' rows d_pid / d_dist / d_cnt / d_ctr.
+    Buf rg_radius, rg_lim, rg_term, rg_cnt, rg_off, rg_stepcnt, rg_stepoff, rg_chunks, rg_keys, rg_exoff, rg_exlen, rg_lims, rg_opid, rg_odist, rg_list;
+    bool rg_valid = false;         // a successful range call's results are held (until the next one, or the fetch)
+    uint32_t rg_nq = 0;
+    uint64_t rg_total = 0;
+    int32_t rg_metric = 0;
     bool tie_overflowed = false;
     uint32_t tie_cap = 0;          // tie capacity this context escalated to (0 = the index's)
     // strict ties, last resort: one bag of n keys per slot in HBM (the reference's candidate heap is unbounded, core/lib.rs:564)
@@ -2064,7 +2084,9 @@ void idist_search_ctx_free(idist_search_ctx* c) {
     hipFree(c->d_ctr);
     for (idist_search_ctx::Buf* b : {&c->al_bits, &c->al_ids, &c->al_flag, &c->al_list, &c->al_npend, &c->al_pq, &c->al_opid, &c->al_odist,
                                      &c->al_ocnt, &c->al_orung, &c->al_octr, &c->al_mpid, &c->al_mdist, &c->al_mcnt, &c->al_setof, &c->al_size,
-                                     &c->al_start, &c->al_first, &c->al_raw})
+                                     &c->al_start, &c->al_first, &c->al_raw, &c->rg_radius, &c->rg_lim, &c->rg_term,
+                                     &c->rg_cnt, &c->rg_off, &c->rg_stepcnt, &c->rg_stepoff, &c->rg_chunks, &c->rg_keys, &c->rg_exoff, &c->rg_exlen,
+                                     &c->rg_lims, &c->rg_opid, &c->rg_odist, &c->rg_list})
         hipFree(b->p);
     for (hipEvent_t e : c->al_ev)
         if (e) hipEventDestroy(e);
@@ -3767,6 +3789,327 @@ idist_status idist_search_ctx_allowed_kernel_ms(idist_search_ctx* ctx, float* se
     *select_ms = ctx->al_ms[0];
     *pending_ms = ctx->al_ms[1];
     *exact_ms = ctx->al_ms[2];
+    return IDIST_OK;
+}
+
+// ---- range search: every point within a radius; the ef ladder over Hnsw::search, exact scan of every row ----
+extern "C++" {
+namespace {
+
+// the result buffer keeps what it holds when it grows (grow() alone frees first)
+idist_status range_grow_keys(idist_search_ctx* ctx, uint64_t used, uint64_t need) {
+    const size_t need_b = (size_t)need * 8;
+    if (need_b <= ctx->rg_keys.cap) return IDIST_OK;
+    void* fresh = nullptr;
+    size_t cap = 0;
+    CHK(grow(fresh, cap, doubled_from(4096, need_b)));
+    if (used) {
+        const hipError_t e = hipMemcpyAsync(fresh, ctx->rg_keys.p, (size_t)used * 8, hipMemcpyDeviceToDevice, ctx->stream);
+        if (e != hipSuccess) { hipFree(fresh); HIPCHK(e); }
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    hipFree(ctx->rg_keys.p);
+    ctx->rg_keys.p = fresh;
+    ctx->rg_keys.cap = cap;
+    return IDIST_OK;
+}
+
+// off [N + 1] = base + the exclusive prefix sum of cnt [N] (off[N]: the total), enqueued on the context's stream
+idist_status range_prefix(idist_search_ctx* ctx, const uint32_t* cnt, uint64_t N, uint64_t base, uint64_t* off) {
+    const uint64_t chunks = (N + 63u) / 64u;
+    if (chunks == 0) return IDIST_OK;
+    CHK(grow(ctx->rg_chunks.p, ctx->rg_chunks.cap, doubled_from(256, (size_t)chunks * 8)));
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(chunks, 65536u);
+    IDIST_LAUNCH(range_chunk_sums_kernel, grid, 64, 0, ctx->stream, cnt, N, ctx->rg_chunks.as<uint64_t>());
+    IDIST_LAUNCH(range_offsets_kernel, grid, 64, 0, ctx->stream, cnt, N, ctx->rg_chunks.as<uint64_t>(), base, off);
+    HIPCHK(hipGetLastError());
+    return IDIST_OK;
+}
+
+// every list [ex_off[p], + ex_len[p]) of the result buffer ascending; max_len: the longest of them
+idist_status range_sort(idist_search_ctx* ctx, uint32_t np, uint64_t max_len) {
+    if (max_len < 2) return IDIST_OK;
+    uint64_t P = 2;
+    while (P < max_len) P <<= 1;
+    const uint32_t chunk = ctx->knobs.range_sort_chunk ? ctx->knobs.range_sort_chunk : 2048u;
+    const uint32_t chunks_max = (uint32_t)std::max<uint64_t>(P / chunk, 1u);
+    const uint64_t pairs_max = P / 2u;
+    uint64_t* keys = ctx->rg_keys.as<uint64_t>();
+    const uint64_t* off = ctx->rg_exoff.as<uint64_t>();
+    const uint32_t* len = ctx->rg_exlen.as<uint32_t>();
+    const uint64_t cap = (uint64_t)std::max(ctx->n_cu, 1) * 64u;
+    const uint32_t grid_l = (uint32_t)std::min<uint64_t>((uint64_t)np * chunks_max, cap);
+    const uint32_t grid_g = (uint32_t)std::min<uint64_t>((uint64_t)np * ((pairs_max + 63u) / 64u), cap);
+    const size_t smem = (size_t)chunk * 8;
+    IDIST_LAUNCH(range_sort_kernel, grid_l, 64, smem, ctx->stream, keys, off, len, np, chunk, chunks_max, pairs_max, (uint32_t)kSortLocal,
+                 (uint64_t)0, (uint64_t)0);
+    for (uint64_t k = 2ull * chunk; k <= P; k <<= 1) {
+        IDIST_LAUNCH(range_sort_kernel, grid_g, 64, 0, ctx->stream, keys, off, len, np, chunk, chunks_max, pairs_max, (uint32_t)kSortFlip, k,
+                     (uint64_t)0);
+        for (uint64_t j = k / 4u; j >= chunk; j >>= 1)
+            IDIST_LAUNCH(range_sort_kernel, grid_g, 64, 0, ctx->stream, keys, off, len, np, chunk, chunks_max, pairs_max,
+                         (uint32_t)kSortDisperse, k, j);
+        IDIST_LAUNCH(range_sort_kernel, grid_l, 64, smem, ctx->stream, keys, off, len, np, chunk, chunks_max, pairs_max,
+                     (uint32_t)kSortLocalTail, k, (uint64_t)0);
+    }
+    HIPCHK(hipGetLastError());
+    return IDIST_OK;
+}
+
+idist_status range_too_many(uint64_t known, uint64_t max_total, const char* after) {
+    return fail(IDIST_ERR_INVALID_ARG, "range search: %llu results known after %s exceed max_total %llu (nothing is returned)",
+                (unsigned long long)known, after, (unsigned long long)max_total);
+}
+
+}  // namespace
+}  // extern "C++"
+
+idist_status idist_search_batch_range(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
+                                      const float* radius, uint32_t n_radius, int32_t max_rungs, uint64_t max_total,
+                                      uint64_t* out_lims, uint32_t* out_rung, uint32_t* out_counters) {
+    CHK(check_ctx(idx, ctx));
+    ctx->rg_valid = false;                                                   // whatever happens next, the previous results are gone
+    const uint32_t n = idx->n, ef0 = idx->cfg.ef_search;
+    if (max_rungs < -1) return fail(IDIST_ERR_INVALID_ARG, "max_rungs %d: -1 (the whole ladder) or a number of rungs >= 0", max_rungs);
+    if (!out_lims) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    if (nq && n_radius != 1 && n_radius != nq) return fail(IDIST_ERR_INVALID_ARG, "n_radius %u: 1 (one radius for the batch) or nq = %u", n_radius, nq);
+    if (nq && (!queries || !radius)) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    for (uint32_t i = 0; nq && i < n_radius; i++)
+        if (radius[i] != radius[i]) {
+            if (n_radius == 1) return fail(IDIST_ERR_INVALID_ARG, "the radius of the batch (query 0 and every other) is NaN");
+            return fail(IDIST_ERR_INVALID_ARG, "the radius of query %u is NaN", i);
+        }
+    ctx->rg_nq = nq;
+    ctx->rg_total = 0;
+    ctx->rg_metric = idx->cfg.metric;
+    ctx->al_ms[3] = ctx->al_ms[4] = ctx->al_ms[5] = 0.0f;
+    ctx->al_ev_used = 0;
+    if (nq == 0 || n == 0 || ef0 == 0) {                                     // step 1: nothing to find
+        std::fill(out_lims, out_lims + nq + 1, (uint64_t)0);
+        if (out_rung) std::fill(out_rung, out_rung + nq, (uint32_t)IDIST_RUNG_NONE);
+        if (out_counters) memset(out_counters, 0, (size_t)nq * 12);
+        ctx->rg_valid = true;
+        return IDIST_OK;
+    }
+    uint32_t E[8], n_rungs = 0;
+    for (uint32_t e = ef0;; e = std::min<uint32_t>(4u * e, IDIST_MAX_EF)) {
+        E[n_rungs++] = e;
+        if (e >= IDIST_MAX_EF) break;
+    }
+    if (max_rungs >= 0) n_rungs = std::min<uint32_t>(n_rungs, (uint32_t)max_rungs);
+
+    HIPCHK(hipSetDevice(idx->device));
+    hipStream_t stream = ctx->stream;
+    const MetricPasses metric(idx);
+    const uint32_t kdim = idx->kdim, kmetric = (uint32_t)idx->cfg.metric;
+    const size_t qb = (size_t)nq * idx->dim * 4;
+    const bool counters = out_counters != nullptr;
+    CHK(grow(ctx->d_q, ctx->cap_q, qb));
+    CHK(grow(ctx->rg_radius.p, ctx->rg_radius.cap, (size_t)n_radius * 4));
+    CHK(grow(ctx->rg_lim.p, ctx->rg_lim.cap, (size_t)nq * 8));
+    CHK(grow(ctx->rg_term.p, ctx->rg_term.cap, (size_t)nq * 4));
+    CHK(grow(ctx->rg_cnt.p, ctx->rg_cnt.cap, (size_t)nq * 4));
+    CHK(grow(ctx->rg_off.p, ctx->rg_off.cap, (size_t)nq * 8));
+    CHK(grow(ctx->rg_stepcnt.p, ctx->rg_stepcnt.cap, (size_t)nq * 4));
+    CHK(grow(ctx->rg_stepoff.p, ctx->rg_stepoff.cap, ((size_t)nq + 1) * 8));
+    CHK(grow(ctx->rg_lims.p, ctx->rg_lims.cap, ((size_t)nq + 1) * 8));
+    CHK(grow(ctx->al_flag.p, ctx->al_flag.cap, (size_t)nq * 4));
+    CHK(grow(ctx->al_list.p, ctx->al_list.cap, (size_t)nq * 4));
+    CHK(grow(ctx->al_npend.p, ctx->al_npend.cap, 256));
+    CHK(grow(ctx->al_pq.p, ctx->al_pq.cap, (size_t)nq * kdim * 4));
+    CHK(grow(ctx->rg_list.p, ctx->rg_list.cap, (size_t)nq * 4));
+    CHK(grow(ctx->al_orung.p, ctx->al_orung.cap, (size_t)nq * 4));
+    CHK(grow(ctx->al_octr.p, ctx->al_octr.cap, (size_t)nq * 12));
+    HIPCHK(hipMemcpyAsync(ctx->d_q, queries, qb, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(ctx->rg_radius.p, radius, (size_t)n_radius * 4, hipMemcpyHostToDevice, stream));
+    // cosine / DOT: the queries are prepared ONCE per call, every rung and the scan take them as they are (prepared = true); the
+    // metric's report is applied once, to what the fetch hands out
+    const float* d_qk = ctx->d_q;
+    if (metric.any()) {
+        CHK(grow(ctx->d_qn, ctx->cap_qn, doubled_from(4096, metric.qk_floats(nq) * 4)));
+        CHK(grow(ctx->d_sq, ctx->cap_sq, doubled_from(256, metric.sq_floats(nq) * 4)));
+        CHK(metric.prepare(ctx->d_q, ctx->d_qn, ctx->d_sq, nq, stream, &d_qk));
+    }
+    RangeState st{};
+    st.lim = ctx->rg_lim.as<uint32_t>(); st.term = ctx->rg_term.as<float>(); st.count = ctx->rg_cnt.as<uint32_t>();
+    st.off = ctx->rg_off.as<uint64_t>(); st.rung = ctx->al_orung.as<uint32_t>(); st.counters = counters ? ctx->al_octr.as<uint32_t>() : nullptr;
+    st.pending = ctx->al_flag.as<uint32_t>(); st.nq = nq;
+    const uint32_t waves_cap = (uint32_t)std::max(ctx->n_cu, 1) * 64u;
+    auto init_pass = [&]() -> idist_status {
+        const uint32_t grid = std::min<uint32_t>((nq + 255u) / 256u, (uint32_t)std::max(ctx->n_cu, 1) * 8u);
+        IDIST_LAUNCH(range_init_kernel, grid, 256, 0, stream, st, ctx->rg_radius.as<float>(), n_radius, kmetric, ctx->d_sq, idx->dot_S);
+        HIPCHK(hipGetLastError());
+        return IDIST_OK;
+    };
+    CHK(allowed_timed(ctx, 3, init_pass));
+    uint32_t np = nq;
+    uint64_t total = 0;                                          // keys in the result buffer so far
+    const uint32_t* d_list = nullptr;
+    const float* d_pq = d_qk;
+    uint32_t* step_cnt = ctx->rg_stepcnt.as<uint32_t>();
+    uint64_t* step_off = ctx->rg_stepoff.as<uint64_t>();
+    for (uint32_t r = 0; r < n_rungs && np; r++) {
+        const uint32_t ef = E[r];
+        const size_t rb = (size_t)np * ef * 4;
+        CHK(grow(ctx->d_pid, ctx->cap_pid, rb));
+        CHK(grow(ctx->d_dist, ctx->cap_dist, rb));
+        CHK(grow(ctx->d_cnt, ctx->cap_cnt, (size_t)np * 4));
+        CHK(grow(ctx->d_ctr, ctx->cap_ctr, (size_t)np * 12));
+        bool lds_short = false, ended = false;
+        for (;;) {
+            const idist_status ls = launch_search(idx, ctx, d_pq, np, ctx->d_pid, ctx->d_dist, ctx->d_cnt, counters ? ctx->d_ctr : nullptr,
+                                                  stream, nullptr, nullptr, nullptr, 0, true, ef, &lds_short);
+            if (ls != IDIST_OK) {
+                // a later rung that does not fit a wave's LDS ends the ladder as max_rungs would; rung 0 fails as idist_search_batch does
+                if (lds_short && r != 0) { ended = true; break; }
+                return ls;
+            }
+            HIPCHK(hipStreamSynchronize(stream));
+            idist_status s;
+            if (status_asks_retry(idx, ctx, &s)) continue;      // strict ties: the same rung again with the larger region / the bags
+            if (s != IDIST_OK) return s;
+            break;
+        }
+        if (ended) break;
+        const uint32_t np_step = np;
+        auto select_pass = [&]() -> idist_status {
+            IDIST_LAUNCH(range_select_kernel, std::min(np_step, 65536u), 64, 0, stream, st, reinterpret_cast<const uint32_t*>(ctx->d_dist),
+                         ctx->d_cnt, counters ? ctx->d_ctr : nullptr, ef, d_list, np_step, r, step_cnt);
+            HIPCHK(hipGetLastError());
+            return range_prefix(ctx, step_cnt, np_step, total, step_off);
+        };
+        CHK(allowed_timed(ctx, 3, select_pass));
+        // the pending queries of the next rung, gathered BEFORE the copy so that one synchronisation reads the new total and their
+        // number: the copy still needs this rung's list, so the lists alternate between two buffers (the rows of this rung stay
+        // where they are until the copy has run; the next rows go to al_pq)
+        uint32_t* next_list = d_list == ctx->al_list.as<uint32_t>() ? ctx->rg_list.as<uint32_t>() : ctx->al_list.as<uint32_t>();
+        auto pending_pass = [&]() -> idist_status {
+            IDIST_LAUNCH(allowed_pending_kernel, (nq + 63u) / 64u, 64, 0, stream, st.pending, nq, d_qk, kdim, next_list, ctx->al_pq.as<float>(),
+                         ctx->al_npend.as<uint32_t>());
+            HIPCHK(hipGetLastError());
+            return IDIST_OK;
+        };
+        CHK(allowed_timed(ctx, 3, pending_pass));
+        uint64_t new_total = 0;
+        HIPCHK(hipMemcpyAsync(&new_total, step_off + np_step, 8, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(&np, ctx->al_npend.p, 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (new_total > max_total) {
+            char after[32];
+            snprintf(after, sizeof(after), "rung %u", r);
+            return range_too_many(new_total, max_total, after);
+        }
+        CHK(range_grow_keys(ctx, total, new_total));
+        auto copy_pass = [&]() -> idist_status {
+            IDIST_LAUNCH(range_copy_kernel, std::min(np_step, 65536u), 64, 0, stream, st, ctx->d_pid, reinterpret_cast<const uint32_t*>(ctx->d_dist),
+                         ef, d_list, np_step, step_cnt, step_off, ctx->rg_keys.as<uint64_t>());
+            HIPCHK(hipGetLastError());
+            return IDIST_OK;
+        };
+        CHK(allowed_timed(ctx, 3, copy_pass));                  // (enqueued, not waited for: the next launch follows it in stream order)
+        total = new_total;
+        d_list = next_list;
+        d_pq = ctx->al_pq.as<float>();
+    }
+    if (np) {
+        // step 3, exact: [0, n) cut into S segments, one wave per (pending query, segment); S: enough waves for the chip when few
+        // queries are left, never segments of less than one 64-row round; the result does not depend on it
+        uint32_t S = (uint32_t)std::min<uint64_t>(((uint64_t)std::max(ctx->n_cu, 1) * 16u + np - 1u) / np, ((uint64_t)n + 63u) / 64u);
+        if (ctx->knobs.range_segments) S = ctx->knobs.range_segments;
+        S = std::min(std::max(S, 1u), 64u);
+        const uint64_t items = (uint64_t)np * S;
+        CHK(grow(ctx->d_cnt, ctx->cap_cnt, (size_t)items * 4));
+        CHK(grow(ctx->rg_stepoff.p, ctx->rg_stepoff.cap, (size_t)(items + 1) * 8));
+        CHK(grow(ctx->rg_exoff.p, ctx->rg_exoff.cap, (size_t)np * 8));
+        CHK(grow(ctx->rg_exlen.p, ctx->rg_exlen.cap, (size_t)np * 4));
+        uint32_t* seg_cnt = ctx->d_cnt;
+        uint64_t* seg_off = ctx->rg_stepoff.as<uint64_t>();
+        const size_t smem = smem_bytes(idx->L.stride, 0, false);
+        if (smem > 64 * 1024) return fail(IDIST_ERR_INVALID_ARG, "dim needs %zu B of LDS per wave (> 64 KiB)", smem);
+        const uint32_t grid = (uint32_t)std::min<uint64_t>(items, waves_cap);
+        IndexView view = idx->view();
+        auto scan_pass = [&](uint64_t* keys) -> idist_status {
+            const uint32_t* d_lim = st.lim;
+#define LAUNCH_AS(NB_, RS_, TAIL_)                                                                               \
+    {                                                                                                            \
+        auto kR = range_scan_kernel<NB_, RS_, TAIL_>;                                                            \
+        IDIST_LAUNCH(kR, grid, 64, smem, stream, view, d_pq, np, d_list, d_lim, S, seg_cnt, seg_off, keys);      \
+    }
+            IDIST_DISPATCH(idx->L, LAUNCH_AS);
+#undef LAUNCH_AS
+            HIPCHK(hipGetLastError());
+            return IDIST_OK;
+        };
+        auto count_pass = [&]() -> idist_status {
+            CHK(scan_pass(nullptr));
+            CHK(range_prefix(ctx, seg_cnt, items, total, seg_off));
+            IDIST_LAUNCH(range_close_kernel, std::min<uint32_t>((np + 255u) / 256u, 1024u), 256, 0, stream, st, d_list, np, S, seg_off,
+                         ctx->rg_exoff.as<uint64_t>(), ctx->rg_exlen.as<uint32_t>());
+            HIPCHK(hipGetLastError());
+            return IDIST_OK;
+        };
+        CHK(allowed_timed(ctx, 4, count_pass));
+        uint64_t new_total = 0;
+        std::vector<uint32_t> ex_len(np);
+        HIPCHK(hipMemcpyAsync(&new_total, seg_off + items, 8, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(ex_len.data(), ctx->rg_exlen.p, (size_t)np * 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (new_total > max_total) return range_too_many(new_total, max_total, "the exact step");
+        CHK(range_grow_keys(ctx, total, new_total));
+        auto write_pass = [&]() -> idist_status { return scan_pass(ctx->rg_keys.as<uint64_t>()); };
+        CHK(allowed_timed(ctx, 4, write_pass));
+        const uint64_t max_len = *std::max_element(ex_len.begin(), ex_len.end());
+        auto sort_pass = [&]() -> idist_status { return range_sort(ctx, np, max_len); };
+        CHK(allowed_timed(ctx, 5, sort_pass));
+        total = new_total;
+    }
+    // lims: the prefix sum of the counts, in query order
+    uint64_t* d_lims = ctx->rg_lims.as<uint64_t>();
+    auto lims_pass = [&]() -> idist_status { return range_prefix(ctx, st.count, nq, 0, d_lims); };
+    CHK(allowed_timed(ctx, 3, lims_pass));
+    HIPCHK(hipMemcpyAsync(out_lims, d_lims, ((size_t)nq + 1) * 8, hipMemcpyDeviceToHost, stream));
+    if (out_rung) HIPCHK(hipMemcpyAsync(out_rung, ctx->al_orung.p, (size_t)nq * 4, hipMemcpyDeviceToHost, stream));
+    if (counters) HIPCHK(hipMemcpyAsync(out_counters, ctx->al_octr.p, (size_t)nq * 12, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    CHK(allowed_times_resolve(ctx));
+    if (out_lims[nq] != total) return fail(IDIST_ERR_INTERNAL, "range search: the counts sum to %llu, the result buffer holds %llu",
+                                           (unsigned long long)out_lims[nq], (unsigned long long)total);
+    ctx->rg_total = total;
+    ctx->rg_valid = true;
+    return IDIST_OK;
+}
+
+idist_status idist_search_ctx_range_fetch(idist_search_ctx* ctx, uint32_t* out_pid, float* out_dist) {
+    if (!ctx) return fail(IDIST_ERR_INVALID_ARG, "ctx is null");
+    if (!ctx->rg_valid) return fail(IDIST_ERR_INVALID_ARG, "no range search results are held: call idist_search_batch_range first (a fetch hands them out once)");
+    const uint64_t total = ctx->rg_total;
+    if (total == 0) {
+        ctx->rg_valid = false;
+        return IDIST_OK;
+    }
+    if (!out_pid || !out_dist) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    CHK(grow(ctx->rg_opid.p, ctx->rg_opid.cap, doubled_from(4096, (size_t)total * 4)));
+    CHK(grow(ctx->rg_odist.p, ctx->rg_odist.cap, doubled_from(4096, (size_t)total * 4)));
+    RangeState st{};
+    st.term = ctx->rg_term.as<float>(); st.count = ctx->rg_cnt.as<uint32_t>(); st.off = ctx->rg_off.as<uint64_t>(); st.nq = ctx->rg_nq;
+    const uint32_t grid = std::min<uint32_t>(ctx->rg_nq, (uint32_t)std::max(ctx->n_cu, 1) * 64u);
+    IDIST_LAUNCH(range_gather_kernel, grid, 64, 0, stream, st, ctx->rg_keys.as<uint64_t>(), ctx->rg_lims.as<uint64_t>(), (uint32_t)ctx->rg_metric,
+                 ctx->rg_opid.as<uint32_t>(), ctx->rg_odist.as<float>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out_pid, ctx->rg_opid.p, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(out_dist, ctx->rg_odist.p, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    ctx->rg_valid = false;
+    return IDIST_OK;
+}
+
+idist_status idist_search_ctx_range_kernel_ms(idist_search_ctx* ctx, float* select_ms, float* scan_ms, float* sort_ms) {
+    if (!ctx || !select_ms || !scan_ms || !sort_ms) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    *select_ms = ctx->al_ms[3];
+    *scan_ms = ctx->al_ms[4];
+    *sort_ms = ctx->al_ms[5];
     return IDIST_OK;
 }
 
