@@ -388,31 +388,36 @@ struct idist_search_ctx {
     size_t cap_qn = 0;             // (cosine: normalised; DOT: with the trailing 0, [nq][kdim])
     float* d_sq = nullptr;         // DOT indexes: s(q) per query of the launch, for the report pass
     size_t cap_sq = 0;
-    // staging of idist_search_batch_allowed (grow-only, freed with the context): the bitmap and the ascending id list of A, the
-    // pending flags / list / count / gathered query rows, the [nq][k] result with its counts, rungs and counters, and the merged
-    // scan of the exact step.  The rungs' result rows and the scan's segment lists use d_pid / d_dist / d_cnt / d_ctr above.
+    // Staging of the ladder searches (grow-only, freed with the context), by role.
+    //  * The ladder's, shared by the restricted and the range search: the pending flags, the ascending list of the pending queries,
+    //    their number and their gathered rows (al_flag, al_list, al_npend, al_pq), every query's rung and counters (al_orung, al_octr).
+    //    A rung's result rows and an exact scan's segment lists use d_pid / d_dist / d_cnt / d_ctr above, the queries d_q / d_qn / d_sq.
+    //  * The restricted search's: the bitmap of A or of every set (al_bits), A's ascending id list (al_ids: the single-set call), the
+    //    [nq][k] result with its counts (al_o*), the merged scan of the exact step (al_m*); several sets: the set of every query, |A_s|
+    //    and the start rung per set, the first rung per query (al_setof, al_size, al_start, al_first); a part of a partitioned index:
+    //    the words of the caller's global bitmaps that hold its bits, as uploaded (al_raw: allowed_slice_kernel cuts al_bits out of them).
+    //  * The range search's: rg_*.  What idist_search_ctx_range_fetch needs lives in buffers no other call writes: the keys in
+    //    completion order, every query's count, offset and report term.  rg_list: the second pending list (a rung's copy pass still
+    //    reads the list that the next rung's pending pass replaces).
     struct Buf {
         void* p = nullptr;
         size_t cap = 0;
         template <typename T> T* as() const { return static_cast<T*>(p); }
     };
-    // idist_search_batch_allowed_sets adds: every set's bitmap in al_bits, the set of every query, |A_s| and the start rung per set,
-    // the first rung per query.
-    Buf al_bits, al_ids, al_flag, al_list, al_npend, al_pq, al_opid, al_odist, al_ocnt, al_orung, al_octr, al_mpid, al_mdist, al_mcnt;
-    Buf al_setof, al_size, al_start, al_first;
-    // idist_partitioned_search_batch_allowed_sets adds: the words of the caller's global bitmaps that hold this part's bits, as
-    // uploaded (allowed_slice_kernel cuts the part's own bitmaps out of them into al_bits)
-    Buf al_raw;
-    static constexpr uint32_t kAllowedEvents = 64;   // a pair per select / pending pass of at most seven rungs + the exact step's two;
-                                                     // the several-sets call: + its count pass and a pending pass in front of every launch
-    hipEvent_t al_ev[kAllowedEvents] = {nullptr};    // (created on first use, resolved when the call has synchronised its stream)
-    uint8_t al_ev_which[kAllowedEvents / 2] = {0};
+    Buf al_flag, al_list, al_npend, al_pq, al_orung, al_octr;
+    Buf al_bits, al_ids, al_opid, al_odist, al_ocnt, al_mpid, al_mdist, al_mcnt, al_setof, al_size, al_start, al_first, al_raw;
+    // The passes a call times (ladder_timed): a pair of events each, created on first use, resolved when the call has synchronised its
+    // stream.  A restricted search: a pair per select and pending pass of at most seven rungs + the exact step's two; several sets: + the
+    // count pass and a pending pass in front of every launch.  A range search: three pairs per rung (select, pending, copy) + five
+    // (init, the exact step's three, lims).  Pairs beyond kAllowedEvents are not timed.
+    static constexpr uint32_t kAllowedEvents = 64;
+    hipEvent_t al_ev[kAllowedEvents] = {nullptr};
+    uint8_t al_ev_which[kAllowedEvents / 2] = {0};   // the slot of al_ms a pair adds to
     uint32_t al_ev_used = 0;
-    float al_ms[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // the last call's select, pending and scan + merge kernels, summed over its
-                                                             // rungs; [3..5]: the last range search's select, scan and sort kernels
-    // staging of idist_search_batch_range (grow-only, freed with the context).  What idist_search_ctx_range_fetch needs lives in rg_*
-    // buffers no other call writes: the keys in completion order, every query's count, offset and report term.  The pending flags /
-    // list / gathered rows, rungs and counters use the restricted search's al_* buffers, the rungs' rows d_pid / d_dist / d_cnt / d_ctr.
+    // al_ms[0..2]: the last restricted search's select (+ count), pending and exact scan + merge kernels, summed over its rungs
+    // (idist_search_ctx_allowed_kernel_ms); [3..5]: the last range search's select (+ init, prefix, pending, copy, lims), exact scan
+    // and sort kernels (idist_search_ctx_range_kernel_ms)
+    float al_ms[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     Buf rg_radius, rg_lim, rg_term, rg_cnt, rg_off, rg_stepcnt, rg_stepoff, rg_chunks, rg_keys, rg_exoff, rg_exlen, rg_lims, rg_opid, rg_odist, rg_list;
     bool rg_valid = false;         // a successful range call's results are held (until the next one, or the fetch)
     uint32_t rg_nq = 0;
@@ -3142,13 +3147,14 @@ idist_status idist_bruteforce(const idist_index* idx, const float* queries, uint
     return bruteforce_impl(idx, queries, nq, k, out_pid, out_dist, false);
 }
 
-// ---- restricted search: the ef ladder over Hnsw::search, exact scan of the allowed rows ----
+// ---- the ef ladder over Hnsw::search, then an exact scan: what the restricted searches and the range
+// ---- search (§4.9) share ----
 extern "C++" {
 namespace {
 
-// `fn` enqueues kernels on the context's stream between two HIP events (kernel events on); allowed_times_resolve adds their
+// `fn` enqueues kernels on the context's stream between two HIP events (kernel events on); ladder_times_resolve adds their
 // durations to ctx->al_ms[which] once the call has synchronised the stream — no synchronisation of its own
-template <typename F> idist_status allowed_timed(idist_search_ctx* ctx, int which, F fn) {
+template <typename F> idist_status ladder_timed(idist_search_ctx* ctx, int which, F fn) {
     const uint32_t u = ctx->al_ev_used;
     if (!ctx->knobs.events || u + 2 > idist_search_ctx::kAllowedEvents) return fn();
     for (uint32_t i = u; i < u + 2; i++)
@@ -3160,7 +3166,7 @@ template <typename F> idist_status allowed_timed(idist_search_ctx* ctx, int whic
     ctx->al_ev_used = u + 2;
     return IDIST_OK;
 }
-idist_status allowed_times_resolve(idist_search_ctx* ctx) {
+idist_status ladder_times_resolve(idist_search_ctx* ctx) {
     for (uint32_t u = 0; u < ctx->al_ev_used; u += 2) {
         float ms = 0.0f;
         HIPCHK(hipEventElapsedTime(&ms, ctx->al_ev[u], ctx->al_ev[u + 1]));
@@ -3168,6 +3174,114 @@ idist_status allowed_times_resolve(idist_search_ctx* ctx) {
     }
     ctx->al_ev_used = 0;
     return IDIST_OK;
+}
+
+// the argument checks, each message once (the range search has no k: it checks max_rungs alone)
+idist_status check_max_rungs(int32_t max_rungs) {
+    if (max_rungs < -1) return fail(IDIST_ERR_INVALID_ARG, "max_rungs %d: -1 (the whole ladder) or a number of rungs >= 0", max_rungs);
+    return IDIST_OK;
+}
+idist_status check_ladder_args(int32_t max_rungs, uint32_t k, uint32_t ef0) {
+    CHK(check_max_rungs(max_rungs));
+    if (k == 0 || k > IDIST_MAX_EF) return fail(IDIST_ERR_INVALID_ARG, "k %u out of [1,%u]", k, IDIST_MAX_EF);
+    if (ef0 != 0 && k > ef0) return fail(IDIST_ERR_INVALID_ARG, "k %u > ef_search %u", k, ef0);
+    return IDIST_OK;
+}
+// (nq == 0 is no error: the caller returns at once, whatever set_of says)
+idist_status check_sets_args(uint32_t n_sets, const uint32_t* set_of, uint32_t nq) {
+    if (n_sets == 0) return fail(IDIST_ERR_INVALID_ARG, "n_sets 0: at least one allowed set");
+    if (nq == 0) return IDIST_OK;
+    if (!set_of && n_sets != nq) return fail(IDIST_ERR_INVALID_ARG, "set_of is null (query q uses set q) but n_sets %u != nq %u", n_sets, nq);
+    if (set_of)
+        for (uint32_t q = 0; q < nq; q++)
+            if (set_of[q] >= n_sets) return fail(IDIST_ERR_INVALID_ARG, "set_of[%u] = %u: query %u names a set outside [0,%u)", q, set_of[q], q, n_sets);
+    return IDIST_OK;
+}
+
+// step 1, nothing to find: every output array the caller hands in (null: it has none, or fills it its own way)
+void fill_nothing_found(uint32_t nq, uint32_t k, uint32_t* out_pid, float* out_dist, uint32_t* out_count, uint32_t* out_rung,
+                        uint32_t* out_counters) {
+    if (out_pid) std::fill(out_pid, out_pid + (size_t)nq * k, (uint32_t)IDIST_INVALID);
+    if (out_dist) std::fill(out_dist, out_dist + (size_t)nq * k, INFINITY);
+    if (out_count) memset(out_count, 0, (size_t)nq * 4);
+    if (out_rung) std::fill(out_rung, out_rung + nq, (uint32_t)IDIST_RUNG_NONE);
+    if (out_counters) memset(out_counters, 0, (size_t)nq * 12);
+}
+
+// the ladder E[0] = ef_search, E[r + 1] = min(4 E[r], IDIST_MAX_EF), ending with the rung that equals IDIST_MAX_EF; the permitted
+// rungs are r < n_rungs.  ef0 > 0.
+AllowedLadder make_ladder(uint32_t ef0, int32_t max_rungs) {
+    AllowedLadder lad{};
+    for (uint32_t e = ef0;; e = std::min<uint32_t>(4u * e, IDIST_MAX_EF)) {
+        lad.E[lad.n_rungs++] = e;
+        if (e >= IDIST_MAX_EF) break;
+    }
+    if (max_rungs >= 0) lad.n_rungs = std::min<uint32_t>(lad.n_rungs, (uint32_t)max_rungs);
+    return lad;
+}
+
+// *d_qk [nq][kdim]: the queries as the kernels read them.  Cosine / DOT: prepared ONCE per call, every rung and the exact scan take
+// them as they are (prepared = true), and the caller reports once, on the call's result — as the partitioned search does
+idist_status ladder_upload_queries(const idist_index* idx, idist_search_ctx* ctx, const MetricPasses& metric, const float* queries,
+                                   uint32_t nq, const float** d_qk) {
+    const size_t qb = (size_t)nq * idx->dim * 4;
+    CHK(grow(ctx->d_q, ctx->cap_q, qb));
+    HIPCHK(hipMemcpyAsync(ctx->d_q, queries, qb, hipMemcpyHostToDevice, ctx->stream));
+    *d_qk = ctx->d_q;
+    if (metric.any()) {
+        CHK(grow(ctx->d_qn, ctx->cap_qn, doubled_from(4096, metric.qk_floats(nq) * 4)));
+        CHK(grow(ctx->d_sq, ctx->cap_sq, doubled_from(256, metric.sq_floats(nq) * 4)));
+        CHK(metric.prepare(ctx->d_q, ctx->d_qn, ctx->d_sq, nq, ctx->stream, d_qk));
+    }
+    return IDIST_OK;
+}
+
+// One rung: Hnsw::search at `ef` for the queries d_pq [np][kdim] into ctx->d_pid / d_dist [np][ef], d_cnt, d_ctr; blocks on the
+// context's stream.  *ended: the ladder is over, nothing was launched.
+idist_status ladder_rung(const idist_index* idx, idist_search_ctx* ctx, const float* d_pq, uint32_t np, uint32_t ef, uint32_t r,
+                         bool counters, bool* ended) {
+    *ended = false;
+    const size_t rb = (size_t)np * ef * 4;
+    CHK(grow(ctx->d_pid, ctx->cap_pid, rb));
+    CHK(grow(ctx->d_dist, ctx->cap_dist, rb));
+    CHK(grow(ctx->d_cnt, ctx->cap_cnt, (size_t)np * 4));
+    CHK(grow(ctx->d_ctr, ctx->cap_ctr, (size_t)np * 12));
+    for (;;) {
+        bool lds_short = false;
+        const idist_status ls = launch_search(idx, ctx, d_pq, np, ctx->d_pid, ctx->d_dist, ctx->d_cnt, counters ? ctx->d_ctr : nullptr,
+                                              ctx->stream, nullptr, nullptr, nullptr, 0, true, ef, &lds_short);
+        if (ls != IDIST_OK) {
+            // a later rung that does not fit a wave's LDS ends the ladder as max_rungs would; rung 0 fails as idist_search_batch does
+            if (lds_short && r != 0) { *ended = true; return IDIST_OK; }
+            return ls;
+        }
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        idist_status s;
+        if (status_asks_retry(idx, ctx, &s)) continue;          // strict ties: the same rung again with the larger region / the bags
+        return s;
+    }
+}
+
+// The pending pass, enqueued only: the pending queries (d_first: whose first rung is <= rung) ascending into list_out, their rows
+// into ctx->al_pq, their number into ctx->al_npend — which the caller reads back (the range search: with its new total, in one wait)
+idist_status ladder_pending(idist_search_ctx* ctx, const uint32_t* pending, uint32_t nq, const float* d_qk, uint32_t kdim,
+                            uint32_t* list_out, int which_timer, const uint32_t* d_first = nullptr, uint32_t rung = 0) {
+    auto pending_pass = [&]() -> idist_status {
+        IDIST_LAUNCH(allowed_pending_kernel, (nq + 63u) / 64u, 64, 0, ctx->stream, pending, nq, d_qk, kdim, list_out, ctx->al_pq.as<float>(),
+                     ctx->al_npend.as<uint32_t>(), d_first, rung);
+        HIPCHK(hipGetLastError());
+        return IDIST_OK;
+    };
+    return ladder_timed(ctx, which_timer, pending_pass);
+}
+
+// S of an exact step, `units` rows per pending query cut into S segments: enough waves for the chip when few queries are left,
+// never segments of less than one 64-row round; the test knob overrides; at most 64.  The result does not depend on it.
+uint32_t exact_segments(const idist_search_ctx* ctx, uint32_t np, uint64_t units, uint32_t knob) {
+    static_assert(kMergeMaxLists == 64, "the range search's bound is the merge's");
+    uint32_t S = (uint32_t)std::min<uint64_t>(((uint64_t)std::max(ctx->n_cu, 1) * 16u + np - 1u) / np, (units + 63u) / 64u);
+    if (knob) S = knob;
+    return std::min(std::max(S, 1u), kMergeMaxLists);
 }
 
 idist_status allowed_select(idist_search_ctx* ctx, const AllowedOut& o, uint32_t n, const uint32_t* r_pid, const float* r_dist,
@@ -3181,20 +3295,76 @@ idist_status allowed_select(idist_search_ctx* ctx, const AllowedOut& o, uint32_t
         HIPCHK(hipGetLastError());
         return IDIST_OK;
     };
-    return allowed_timed(ctx, 0, select_pass);
+    return ladder_timed(ctx, 0, select_pass);
+}
+
+// Step 5 of the restricted search, exact, around either scan kernel: launch_scan enqueues one wave per (pending query, segment),
+// each writing its segment's top-k as list s of the merge by (distance bits, id); the k best are selected as rung IDIST_RUNG_EXACT
+template <typename F>
+idist_status allowed_exact_step(const idist_index* idx, idist_search_ctx* ctx, const AllowedOut& o, uint32_t np, uint32_t k, uint32_t S,
+                                const uint32_t* d_list, const uint32_t* d_setof, uint32_t words, F launch_scan) {
+    const size_t sb = (size_t)S * np * k * 4, mb = (size_t)np * k * 4;
+    CHK(grow(ctx->d_pid, ctx->cap_pid, sb));
+    CHK(grow(ctx->d_dist, ctx->cap_dist, sb));
+    CHK(grow(ctx->d_cnt, ctx->cap_cnt, (size_t)S * np * 4));
+    CHK(grow(ctx->al_mpid.p, ctx->al_mpid.cap, mb));
+    CHK(grow(ctx->al_mdist.p, ctx->al_mdist.cap, mb));
+    CHK(grow(ctx->al_mcnt.p, ctx->al_mcnt.cap, (size_t)np * 4));
+    const uint32_t wcap = k + 64 + 8;
+    const size_t smem = smem_bytes(idx->L.stride, wcap, false);
+    if (smem > 64 * 1024) return fail(IDIST_ERR_INVALID_ARG, "dim/k need %zu B of LDS per wave (> 64 KiB)", smem);
+    auto scan_and_merge = [&]() -> idist_status {
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)np * S, (uint64_t)std::max(ctx->n_cu, 1) * 64u);
+        uint32_t *s_pid = ctx->d_pid, *s_dist = reinterpret_cast<uint32_t*>(ctx->d_dist), *s_cnt = ctx->d_cnt;
+        launch_scan(grid, smem, S, wcap, s_pid, s_dist, s_cnt);
+        HIPCHK(hipGetLastError());
+        MergeArgs a{};
+        a.pid = s_pid; a.dist = s_dist; a.count = s_cnt; a.counters = nullptr;
+        a.n_lists = S; a.nq = np; a.width = k; a.out_width = k;
+        a.out_pid = ctx->al_mpid.as<uint32_t>(); a.out_dist = ctx->al_mdist.as<uint32_t>(); a.out_count = ctx->al_mcnt.as<uint32_t>();
+        a.out_counters = nullptr;
+        return launch_merge(a, ctx->stream);
+    };
+    CHK(ladder_timed(ctx, 2, scan_and_merge));
+    return allowed_select(ctx, o, idx->n, ctx->al_mpid.as<uint32_t>(), ctx->al_mdist.as<float>(), ctx->al_mcnt.as<uint32_t>(), nullptr, k,
+                          d_list, np, IDIST_RUNG_EXACT, true, d_setof, words);
+}
+
+// a call's [nq][k] result with its counts, rungs and counters in the context's own memory
+idist_status allowed_out_in_ctx(idist_search_ctx* ctx, uint32_t nq, uint32_t k, bool counters, AllowedOut* o) {
+    const size_t ob = (size_t)nq * k * 4;
+    CHK(grow(ctx->al_opid.p, ctx->al_opid.cap, ob));
+    CHK(grow(ctx->al_odist.p, ctx->al_odist.cap, ob));
+    CHK(grow(ctx->al_ocnt.p, ctx->al_ocnt.cap, (size_t)nq * 4));
+    CHK(grow(ctx->al_orung.p, ctx->al_orung.cap, (size_t)nq * 4));
+    CHK(grow(ctx->al_octr.p, ctx->al_octr.cap, (size_t)nq * 12));
+    o->pid = ctx->al_opid.as<uint32_t>(); o->dist = ctx->al_odist.as<uint32_t>(); o->count = ctx->al_ocnt.as<uint32_t>();
+    o->rung = ctx->al_orung.as<uint32_t>(); o->counters = counters ? ctx->al_octr.as<uint32_t>() : nullptr;
+    return IDIST_OK;
+}
+// ... and its way back to the caller, enqueued: the caller synchronises the stream and calls ladder_times_resolve
+idist_status allowed_download(idist_search_ctx* ctx, uint32_t nq, uint32_t k, uint32_t* out_pid, float* out_dist, uint32_t* out_count,
+                              uint32_t* out_rung, uint32_t* out_counters) {
+    const size_t ob = (size_t)nq * k * 4;
+    HIPCHK(hipMemcpyAsync(out_pid, ctx->al_opid.p, ob, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(out_dist, ctx->al_odist.p, ob, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(out_count, ctx->al_ocnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_rung) HIPCHK(hipMemcpyAsync(out_rung, ctx->al_orung.p, (size_t)nq * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_counters) HIPCHK(hipMemcpyAsync(out_counters, ctx->al_octr.p, (size_t)nq * 12, hipMemcpyDeviceToHost, ctx->stream));
+    return IDIST_OK;
 }
 
 }  // namespace
 }  // extern "C++"
 
+// ---- restricted search: the ladder filtered by an allowed set, exact scan of the allowed rows ----
+// (not the several-sets call with n_sets = 1: the bitmap scan, a count pass and one more synchronisation are a speed nobody has measured)
 idist_status idist_search_batch_allowed(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
                                         const uint32_t* allow_bits, uint32_t k, int32_t max_rungs, uint32_t* out_pid,
                                         float* out_dist, uint32_t* out_count, uint32_t* out_rung, uint32_t* out_counters) {
     CHK(check_ctx(idx, ctx));
     const uint32_t n = idx->n, ef0 = idx->cfg.ef_search;
-    if (max_rungs < -1) return fail(IDIST_ERR_INVALID_ARG, "max_rungs %d: -1 (the whole ladder) or a number of rungs >= 0", max_rungs);
-    if (k == 0 || k > IDIST_MAX_EF) return fail(IDIST_ERR_INVALID_ARG, "k %u out of [1,%u]", k, IDIST_MAX_EF);
-    if (ef0 != 0 && k > ef0) return fail(IDIST_ERR_INVALID_ARG, "k %u > ef_search %u", k, ef0);
+    CHK(check_ladder_args(max_rungs, k, ef0));
     if (nq == 0) return IDIST_OK;
     if (!queries || !out_pid || !out_dist || !out_count || (n && !allow_bits)) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
     // A: the bitmap with the bits at positions >= n cleared, its size, and (when an exact step needs it) its ascending id list
@@ -3203,60 +3373,35 @@ idist_status idist_search_batch_allowed(const idist_index* idx, idist_search_ctx
     if (n % 32u) bits[words - 1] &= (1u << (n % 32u)) - 1u;
     uint64_t n_allowed = 0;
     for (const uint32_t w : bits) n_allowed += (uint64_t)__builtin_popcount(w);
-    const size_t ob = (size_t)nq * k * 4;
     if (n == 0 || ef0 == 0 || n_allowed == 0) {                              // step 1: nothing to find
-        for (size_t i = 0; i < (size_t)nq * k; i++) { out_pid[i] = IDIST_INVALID; out_dist[i] = INFINITY; }
-        memset(out_count, 0, (size_t)nq * 4);
-        if (out_rung) std::fill(out_rung, out_rung + nq, (uint32_t)IDIST_RUNG_NONE);
-        if (out_counters) memset(out_counters, 0, (size_t)nq * 12);
+        fill_nothing_found(nq, k, out_pid, out_dist, out_count, out_rung, out_counters);
         return IDIST_OK;
     }
-    // the ladder E[0] = ef_search, E[r + 1] = min(4 E[r], IDIST_MAX_EF), ending with the rung that equals IDIST_MAX_EF; the
-    // permitted rungs are r < n_rungs; the start rung is the first whose expected number of allowed hits reaches k (64-bit)
-    uint32_t E[8], n_rungs = 0;
-    for (uint32_t e = ef0;; e = std::min<uint32_t>(4u * e, IDIST_MAX_EF)) {
-        E[n_rungs++] = e;
-        if (e >= IDIST_MAX_EF) break;
-    }
-    if (max_rungs >= 0) n_rungs = std::min<uint32_t>(n_rungs, (uint32_t)max_rungs);
-    uint32_t r0 = n_rungs;
+    // the start rung is the first permitted one whose expected number of allowed hits reaches k (64-bit)
+    const AllowedLadder lad = make_ladder(ef0, max_rungs);
+    uint32_t r0 = lad.n_rungs;
     if (n_allowed > k)
-        for (uint32_t r = 0; r < n_rungs && r0 == n_rungs; r++)
-            if ((uint64_t)E[r] * n_allowed >= (uint64_t)k * n) r0 = r;
+        for (uint32_t r = 0; r < lad.n_rungs && r0 == lad.n_rungs; r++)
+            if ((uint64_t)lad.E[r] * n_allowed >= (uint64_t)k * n) r0 = r;
 
     HIPCHK(hipSetDevice(idx->device));
     hipStream_t stream = ctx->stream;
     const MetricPasses metric(idx);
     const uint32_t kdim = idx->kdim;
-    const size_t qb = (size_t)nq * idx->dim * 4;
     const bool counters = out_counters != nullptr;
     ctx->al_ms[0] = ctx->al_ms[1] = ctx->al_ms[2] = 0.0f;
     ctx->al_ev_used = 0;
-    CHK(grow(ctx->d_q, ctx->cap_q, qb));
     CHK(grow(ctx->al_bits.p, ctx->al_bits.cap, (size_t)words * 4));
     CHK(grow(ctx->al_flag.p, ctx->al_flag.cap, (size_t)nq * 4));
     CHK(grow(ctx->al_list.p, ctx->al_list.cap, (size_t)nq * 4));
     CHK(grow(ctx->al_npend.p, ctx->al_npend.cap, 256));
     CHK(grow(ctx->al_pq.p, ctx->al_pq.cap, (size_t)nq * kdim * 4));
-    CHK(grow(ctx->al_opid.p, ctx->al_opid.cap, ob));
-    CHK(grow(ctx->al_odist.p, ctx->al_odist.cap, ob));
-    CHK(grow(ctx->al_ocnt.p, ctx->al_ocnt.cap, (size_t)nq * 4));
-    CHK(grow(ctx->al_orung.p, ctx->al_orung.cap, (size_t)nq * 4));
-    CHK(grow(ctx->al_octr.p, ctx->al_octr.cap, (size_t)nq * 12));
-    HIPCHK(hipMemcpyAsync(ctx->d_q, queries, qb, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(ctx->al_bits.p, bits.data(), (size_t)words * 4, hipMemcpyHostToDevice, stream));
-    // cosine / DOT: the queries are prepared ONCE per call, every rung and the scan take them as they are (prepared = true), and the
-    // metric's report runs once, at the end, on the [nq][k] result — as the partitioned search does, and for its reason
-    const float* d_qk = ctx->d_q;
-    if (metric.any()) {
-        CHK(grow(ctx->d_qn, ctx->cap_qn, doubled_from(4096, metric.qk_floats(nq) * 4)));
-        CHK(grow(ctx->d_sq, ctx->cap_sq, doubled_from(256, metric.sq_floats(nq) * 4)));
-        CHK(metric.prepare(ctx->d_q, ctx->d_qn, ctx->d_sq, nq, stream, &d_qk));
-    }
     AllowedOut o{};
-    o.pid = ctx->al_opid.as<uint32_t>(); o.dist = ctx->al_odist.as<uint32_t>(); o.count = ctx->al_ocnt.as<uint32_t>();
-    o.rung = ctx->al_orung.as<uint32_t>(); o.counters = counters ? ctx->al_octr.as<uint32_t>() : nullptr;
+    CHK(allowed_out_in_ctx(ctx, nq, k, counters, &o));
     o.pending = ctx->al_flag.as<uint32_t>(); o.nq = nq; o.k = k;
+    HIPCHK(hipMemcpyAsync(ctx->al_bits.p, bits.data(), (size_t)words * 4, hipMemcpyHostToDevice, stream));
+    const float* d_qk = nullptr;
+    CHK(ladder_upload_queries(idx, ctx, metric, queries, nq, &d_qk));
     {
         const uint32_t grid = (uint32_t)std::min<size_t>(((size_t)nq * k + 255) / 256, (size_t)std::max(ctx->n_cu, 1) * 8u);
         IDIST_LAUNCH(allowed_init_kernel, grid, 256, 0, stream, o);
@@ -3267,70 +3412,29 @@ idist_status idist_search_batch_allowed(const idist_index* idx, idist_search_ctx
     std::vector<uint32_t> ids;                                   // (lives until the last synchronisation: it is uploaded asynchronously)
     const uint32_t* d_list = nullptr;
     const float* d_pq = d_qk;
-    for (uint32_t r = r0; r < n_rungs && np; r++) {
-        const uint32_t ef = E[r];
-        const size_t rb = (size_t)np * ef * 4;
-        CHK(grow(ctx->d_pid, ctx->cap_pid, rb));
-        CHK(grow(ctx->d_dist, ctx->cap_dist, rb));
-        CHK(grow(ctx->d_cnt, ctx->cap_cnt, (size_t)np * 4));
-        CHK(grow(ctx->d_ctr, ctx->cap_ctr, (size_t)np * 12));
-        bool lds_short = false, ended = false;
-        for (;;) {
-            const idist_status ls = launch_search(idx, ctx, d_pq, np, ctx->d_pid, ctx->d_dist, ctx->d_cnt, counters ? ctx->d_ctr : nullptr,
-                                                  stream, nullptr, nullptr, nullptr, 0, true, ef, &lds_short);
-            if (ls != IDIST_OK) {
-                // a later rung that does not fit a wave's LDS ends the ladder as max_rungs would; rung 0 fails as idist_search_batch does
-                if (lds_short && r != 0) { ended = true; break; }
-                return ls;
-            }
-            HIPCHK(hipStreamSynchronize(stream));
-            idist_status s;
-            if (status_asks_retry(idx, ctx, &s)) continue;      // strict ties: the same rung again with the larger region / the bags
-            if (s != IDIST_OK) return s;
-            break;
-        }
+    for (uint32_t r = r0; r < lad.n_rungs && np; r++) {
+        const uint32_t ef = lad.E[r];
+        bool ended = false;
+        CHK(ladder_rung(idx, ctx, d_pq, np, ef, r, counters, &ended));
         if (ended) break;
         CHK(allowed_select(ctx, o, n, ctx->d_pid, ctx->d_dist, ctx->d_cnt, counters ? ctx->d_ctr : nullptr, ef, d_list, np, r, false));
-        auto pending_pass = [&]() -> idist_status {
-            IDIST_LAUNCH(allowed_pending_kernel, (nq + 63u) / 64u, 64, 0, stream, o.pending, nq, d_qk, kdim, ctx->al_list.as<uint32_t>(),
-                         ctx->al_pq.as<float>(), ctx->al_npend.as<uint32_t>());
-            HIPCHK(hipGetLastError());
-            return IDIST_OK;
-        };
-        CHK(allowed_timed(ctx, 1, pending_pass));
+        CHK(ladder_pending(ctx, o.pending, nq, d_qk, kdim, ctx->al_list.as<uint32_t>(), 1));
         HIPCHK(hipMemcpyAsync(&np, ctx->al_npend.p, 4, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
         d_list = ctx->al_list.as<uint32_t>();
         d_pq = ctx->al_pq.as<float>();
     }
     if (np) {
-        // step 5, exact: the ascending id list of A cut into S segments, one wave per (pending query, segment), the segments'
-        // top-k lists merged by (distance bits, id).  S: enough waves for the chip when few queries are left over a large A, never
-        // segments of less than one 64-row round; the result does not depend on it
+        // step 5, exact: the ascending id list of A cut into S segments, the segments' top-k lists merged
         ids.reserve((size_t)n_allowed);
         for (uint32_t w = 0; w < words; w++)
             for (uint32_t m = bits[w]; m; m &= m - 1u) ids.push_back(32u * w + (uint32_t)__builtin_ctz(m));
         const uint32_t n_ids = (uint32_t)ids.size();
-        uint32_t S = (uint32_t)std::min<uint64_t>(((uint64_t)std::max(ctx->n_cu, 1) * 16u + np - 1u) / np, (n_ids + 63u) / 64u);
-        if (ctx->knobs.allowed_segments) S = ctx->knobs.allowed_segments;
-        S = std::min(std::max(S, 1u), kMergeMaxLists);
-        const size_t sb = (size_t)S * np * k * 4, mb = (size_t)np * k * 4;
         CHK(grow(ctx->al_ids.p, ctx->al_ids.cap, (size_t)n_ids * 4));
-        CHK(grow(ctx->d_pid, ctx->cap_pid, sb));
-        CHK(grow(ctx->d_dist, ctx->cap_dist, sb));
-        CHK(grow(ctx->d_cnt, ctx->cap_cnt, (size_t)S * np * 4));
-        CHK(grow(ctx->al_mpid.p, ctx->al_mpid.cap, mb));
-        CHK(grow(ctx->al_mdist.p, ctx->al_mdist.cap, mb));
-        CHK(grow(ctx->al_mcnt.p, ctx->al_mcnt.cap, (size_t)np * 4));
         HIPCHK(hipMemcpyAsync(ctx->al_ids.p, ids.data(), (size_t)n_ids * 4, hipMemcpyHostToDevice, stream));
-        const uint32_t wcap = k + 64 + 8;
-        const size_t smem = smem_bytes(idx->L.stride, wcap, false);
-        if (smem > 64 * 1024) return fail(IDIST_ERR_INVALID_ARG, "dim/k need %zu B of LDS per wave (> 64 KiB)", smem);
-        auto scan_and_merge = [&]() -> idist_status {
-            const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)np * S, (uint64_t)std::max(ctx->n_cu, 1) * 64u);
-            IndexView view = idx->view();
-            uint32_t *s_pid = ctx->d_pid, *s_dist = reinterpret_cast<uint32_t*>(ctx->d_dist), *s_cnt = ctx->d_cnt;
-            const uint32_t* d_ids = ctx->al_ids.as<uint32_t>();
+        const uint32_t* d_ids = ctx->al_ids.as<uint32_t>();
+        const IndexView view = idx->view();
+        auto scan_ids = [&](uint32_t grid, size_t smem, uint32_t S, uint32_t wcap, uint32_t* s_pid, uint32_t* s_dist, uint32_t* s_cnt) {
 #define LAUNCH_AS(NB_, RS_, TAIL_)                                                                                        \
     {                                                                                                                     \
         auto kA = allowed_scan_kernel<NB_, RS_, TAIL_>;                                                                   \
@@ -3338,26 +3442,13 @@ idist_status idist_search_batch_allowed(const idist_index* idx, idist_search_ctx
     }
             IDIST_DISPATCH(idx->L, LAUNCH_AS);
 #undef LAUNCH_AS
-            HIPCHK(hipGetLastError());
-            MergeArgs a{};
-            a.pid = s_pid; a.dist = s_dist; a.count = s_cnt; a.counters = nullptr;
-            a.n_lists = S; a.nq = np; a.width = k; a.out_width = k;
-            a.out_pid = ctx->al_mpid.as<uint32_t>(); a.out_dist = ctx->al_mdist.as<uint32_t>(); a.out_count = ctx->al_mcnt.as<uint32_t>();
-            a.out_counters = nullptr;
-            return launch_merge(a, stream);
         };
-        CHK(allowed_timed(ctx, 2, scan_and_merge));
-        CHK(allowed_select(ctx, o, n, ctx->al_mpid.as<uint32_t>(), ctx->al_mdist.as<float>(), ctx->al_mcnt.as<uint32_t>(), nullptr, k,
-                           d_list, np, IDIST_RUNG_EXACT, true));
+        CHK(allowed_exact_step(idx, ctx, o, np, k, exact_segments(ctx, np, n_ids, ctx->knobs.allowed_segments), d_list, nullptr, 0, scan_ids));
     }
     CHK(metric.report(ctx->al_odist.as<float>(), ctx->d_sq, nq, k, stream));
-    HIPCHK(hipMemcpyAsync(out_pid, ctx->al_opid.p, ob, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(out_dist, ctx->al_odist.p, ob, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(out_count, ctx->al_ocnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, stream));
-    if (out_rung) HIPCHK(hipMemcpyAsync(out_rung, ctx->al_orung.p, (size_t)nq * 4, hipMemcpyDeviceToHost, stream));
-    if (counters) HIPCHK(hipMemcpyAsync(out_counters, ctx->al_octr.p, (size_t)nq * 12, hipMemcpyDeviceToHost, stream));
+    CHK(allowed_download(ctx, nq, k, out_pid, out_dist, out_count, out_rung, out_counters));
     HIPCHK(hipStreamSynchronize(stream));
-    return allowed_times_resolve(ctx);
+    return ladder_times_resolve(ctx);
 }
 
 extern "C++" {
@@ -3368,19 +3459,14 @@ namespace {
 // [n_sets][(n + 31) / 32]; d_setof [nq] and its host copy set_of (never null here).  o.pid / dist / count / rung / counters: where the
 // [nq][k] result goes, RAW distances — the caller reports; o.pending is set here.  n > 0, ef_search > 0, nq > 0 and the arguments
 // checked.  Blocks on ctx->stream once per rung; on return the last passes are enqueued there, not waited for: the caller
-// synchronises the stream and calls allowed_times_resolve.
+// synchronises the stream and calls ladder_times_resolve.
 idist_status allowed_sets_device(const idist_index* idx, idist_search_ctx* ctx, const float* d_qk, uint32_t nq, const uint32_t* d_bits,
                                  uint32_t n_sets, const uint32_t* d_setof, const uint32_t* set_of, uint32_t k, int32_t max_rungs,
                                  AllowedOut o) {
-    const uint32_t n = idx->n, ef0 = idx->cfg.ef_search;
+    const uint32_t n = idx->n;
     // the permitted rungs, as idist_search_batch_allowed has them; every set's size and start rung come from the device
     const uint32_t words = (n + 31u) / 32u;
-    AllowedLadder lad{};
-    for (uint32_t e = ef0;; e = std::min<uint32_t>(4u * e, IDIST_MAX_EF)) {
-        lad.E[lad.n_rungs++] = e;
-        if (e >= IDIST_MAX_EF) break;
-    }
-    if (max_rungs >= 0) lad.n_rungs = std::min<uint32_t>(lad.n_rungs, (uint32_t)max_rungs);
+    const AllowedLadder lad = make_ladder(idx->cfg.ef_search, max_rungs);
     const uint32_t n_rungs = lad.n_rungs;
     hipStream_t stream = ctx->stream;
     const uint32_t kdim = idx->kdim;
@@ -3403,7 +3489,7 @@ idist_status allowed_sets_device(const idist_index* idx, idist_search_ctx* ctx, 
         HIPCHK(hipGetLastError());
         return IDIST_OK;
     };
-    CHK(allowed_timed(ctx, 0, count_pass));
+    CHK(ladder_timed(ctx, 0, count_pass));
     std::vector<uint32_t> start(n_sets);
     HIPCHK(hipMemcpyAsync(start.data(), ctx->al_start.p, (size_t)n_sets * 4, hipMemcpyDeviceToHost, stream));
     {
@@ -3433,13 +3519,7 @@ idist_status allowed_sets_device(const idist_index* idx, idist_search_ctx* ctx, 
     const uint32_t* d_list = nullptr;
     const float* d_pq = d_qk;
     auto gather = [&](uint32_t rung) -> idist_status {
-        auto pending_pass = [&]() -> idist_status {
-            IDIST_LAUNCH(allowed_pending_kernel, (nq + 63u) / 64u, 64, 0, stream, o.pending, nq, d_qk, kdim, ctx->al_list.as<uint32_t>(),
-                         ctx->al_pq.as<float>(), ctx->al_npend.as<uint32_t>(), d_first, rung);
-            HIPCHK(hipGetLastError());
-            return IDIST_OK;
-        };
-        CHK(allowed_timed(ctx, 1, pending_pass));
+        CHK(ladder_pending(ctx, o.pending, nq, d_qk, kdim, ctx->al_list.as<uint32_t>(), 1, d_first, rung));
         HIPCHK(hipMemcpyAsync(&np, ctx->al_npend.p, 4, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
         d_list = ctx->al_list.as<uint32_t>();
@@ -3462,26 +3542,8 @@ idist_status allowed_sets_device(const idist_index* idx, idist_search_ctx* ctx, 
         }
         in_place = false;
         const uint32_t ef = lad.E[r];
-        const size_t rb = (size_t)np * ef * 4;
-        CHK(grow(ctx->d_pid, ctx->cap_pid, rb));
-        CHK(grow(ctx->d_dist, ctx->cap_dist, rb));
-        CHK(grow(ctx->d_cnt, ctx->cap_cnt, (size_t)np * 4));
-        CHK(grow(ctx->d_ctr, ctx->cap_ctr, (size_t)np * 12));
-        bool lds_short = false, ended = false;
-        for (;;) {
-            const idist_status ls = launch_search(idx, ctx, d_pq, np, ctx->d_pid, ctx->d_dist, ctx->d_cnt, counters ? ctx->d_ctr : nullptr,
-                                                  stream, nullptr, nullptr, nullptr, 0, true, ef, &lds_short);
-            if (ls != IDIST_OK) {
-                // a later rung that does not fit a wave's LDS ends the ladder for everyone still waiting or pending; rung 0 fails
-                if (lds_short && r != 0) { ended = true; break; }
-                return ls;
-            }
-            HIPCHK(hipStreamSynchronize(stream));
-            idist_status s;
-            if (status_asks_retry(idx, ctx, &s)) continue;      // strict ties: the same rung again with the larger region / the bags
-            if (s != IDIST_OK) return s;
-            break;
-        }
+        bool ended = false;
+        CHK(ladder_rung(idx, ctx, d_pq, np, ef, r, counters, &ended));
         if (ended) break;
         CHK(allowed_select(ctx, o, n, ctx->d_pid, ctx->d_dist, ctx->d_cnt, counters ? ctx->d_ctr : nullptr, ef, d_list, np, r, false,
                            d_setof, words));
@@ -3489,26 +3551,9 @@ idist_status allowed_sets_device(const idist_index* idx, idist_search_ctx* ctx, 
     }
     if (!all_done && !in_place) CHK(gather(kRungExact));
     if (!all_done && np) {
-        // step 5, exact, straight from the bitmaps: the 64-id windows of [0, n) cut into S segments, one wave per (pending query,
-        // segment); S as in the single-set call, never narrower than one window
-        const uint32_t n_win = (uint32_t)(((uint64_t)n + 63u) / 64u);
-        uint32_t S = (uint32_t)std::min<uint64_t>(((uint64_t)std::max(ctx->n_cu, 1) * 16u + np - 1u) / np, n_win);
-        if (ctx->knobs.allowed_segments) S = ctx->knobs.allowed_segments;
-        S = std::min(std::max(S, 1u), kMergeMaxLists);
-        const size_t sb = (size_t)S * np * k * 4, mb = (size_t)np * k * 4;
-        CHK(grow(ctx->d_pid, ctx->cap_pid, sb));
-        CHK(grow(ctx->d_dist, ctx->cap_dist, sb));
-        CHK(grow(ctx->d_cnt, ctx->cap_cnt, (size_t)S * np * 4));
-        CHK(grow(ctx->al_mpid.p, ctx->al_mpid.cap, mb));
-        CHK(grow(ctx->al_mdist.p, ctx->al_mdist.cap, mb));
-        CHK(grow(ctx->al_mcnt.p, ctx->al_mcnt.cap, (size_t)np * 4));
-        const uint32_t wcap = k + 64 + 8;
-        const size_t smem = smem_bytes(idx->L.stride, wcap, false);
-        if (smem > 64 * 1024) return fail(IDIST_ERR_INVALID_ARG, "dim/k need %zu B of LDS per wave (> 64 KiB)", smem);
-        auto scan_and_merge = [&]() -> idist_status {
-            const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)np * S, (uint64_t)std::max(ctx->n_cu, 1) * 64u);
-            IndexView view = idx->view();
-            uint32_t *s_pid = ctx->d_pid, *s_dist = reinterpret_cast<uint32_t*>(ctx->d_dist), *s_cnt = ctx->d_cnt;
+        // step 5, exact, straight from the bitmaps: the 64-id windows of [0, n) cut into S segments, never narrower than one window
+        const IndexView view = idx->view();
+        auto scan_bits = [&](uint32_t grid, size_t smem, uint32_t S, uint32_t wcap, uint32_t* s_pid, uint32_t* s_dist, uint32_t* s_cnt) {
 #define LAUNCH_AS(NB_, RS_, TAIL_)                                                                                                 \
     {                                                                                                                              \
         auto kA = allowed_scan_bits_kernel<NB_, RS_, TAIL_>;                                                                       \
@@ -3516,17 +3561,8 @@ idist_status allowed_sets_device(const idist_index* idx, idist_search_ctx* ctx, 
     }
             IDIST_DISPATCH(idx->L, LAUNCH_AS);
 #undef LAUNCH_AS
-            HIPCHK(hipGetLastError());
-            MergeArgs a{};
-            a.pid = s_pid; a.dist = s_dist; a.count = s_cnt; a.counters = nullptr;
-            a.n_lists = S; a.nq = np; a.width = k; a.out_width = k;
-            a.out_pid = ctx->al_mpid.as<uint32_t>(); a.out_dist = ctx->al_mdist.as<uint32_t>(); a.out_count = ctx->al_mcnt.as<uint32_t>();
-            a.out_counters = nullptr;
-            return launch_merge(a, stream);
         };
-        CHK(allowed_timed(ctx, 2, scan_and_merge));
-        CHK(allowed_select(ctx, o, n, ctx->al_mpid.as<uint32_t>(), ctx->al_mdist.as<float>(), ctx->al_mcnt.as<uint32_t>(), nullptr, k,
-                           d_list, np, IDIST_RUNG_EXACT, true, d_setof, words));
+        CHK(allowed_exact_step(idx, ctx, o, np, k, exact_segments(ctx, np, n, ctx->knobs.allowed_segments), d_list, d_setof, words, scan_bits));
     }
     return IDIST_OK;
 }
@@ -3540,22 +3576,12 @@ idist_status idist_search_batch_allowed_sets(const idist_index* idx, idist_searc
                                              uint32_t* out_rung, uint32_t* out_counters) {
     CHK(check_ctx(idx, ctx));
     const uint32_t n = idx->n, ef0 = idx->cfg.ef_search;
-    if (max_rungs < -1) return fail(IDIST_ERR_INVALID_ARG, "max_rungs %d: -1 (the whole ladder) or a number of rungs >= 0", max_rungs);
-    if (k == 0 || k > IDIST_MAX_EF) return fail(IDIST_ERR_INVALID_ARG, "k %u out of [1,%u]", k, IDIST_MAX_EF);
-    if (ef0 != 0 && k > ef0) return fail(IDIST_ERR_INVALID_ARG, "k %u > ef_search %u", k, ef0);
-    if (n_sets == 0) return fail(IDIST_ERR_INVALID_ARG, "n_sets 0: at least one allowed set");
+    CHK(check_ladder_args(max_rungs, k, ef0));
+    CHK(check_sets_args(n_sets, set_of, nq));
     if (nq == 0) return IDIST_OK;
-    if (!set_of && n_sets != nq) return fail(IDIST_ERR_INVALID_ARG, "set_of is null (query q uses set q) but n_sets %u != nq %u", n_sets, nq);
     if (!queries || !out_pid || !out_dist || !out_count || (n && !allow_bits)) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
-    if (set_of)
-        for (uint32_t q = 0; q < nq; q++)
-            if (set_of[q] >= n_sets) return fail(IDIST_ERR_INVALID_ARG, "set_of[%u] = %u: query %u names a set outside [0,%u)", q, set_of[q], q, n_sets);
-    const size_t ob = (size_t)nq * k * 4;
     if (n == 0 || ef0 == 0) {                                                // step 1: nothing to find, whatever the sets
-        for (size_t i = 0; i < (size_t)nq * k; i++) { out_pid[i] = IDIST_INVALID; out_dist[i] = INFINITY; }
-        memset(out_count, 0, (size_t)nq * 4);
-        if (out_rung) std::fill(out_rung, out_rung + nq, (uint32_t)IDIST_RUNG_NONE);
-        if (out_counters) memset(out_counters, 0, (size_t)nq * 12);
+        fill_nothing_found(nq, k, out_pid, out_dist, out_count, out_rung, out_counters);
         return IDIST_OK;
     }
     // upload, the call on the device, report, download
@@ -3563,44 +3589,26 @@ idist_status idist_search_batch_allowed_sets(const idist_index* idx, idist_searc
     HIPCHK(hipSetDevice(idx->device));
     hipStream_t stream = ctx->stream;
     const MetricPasses metric(idx);
-    const size_t qb = (size_t)nq * idx->dim * 4, bb = (size_t)n_sets * words * 4;
-    const bool counters = out_counters != nullptr;
-    CHK(grow(ctx->d_q, ctx->cap_q, qb));
+    const size_t bb = (size_t)n_sets * words * 4;
     CHK(grow(ctx->al_bits.p, ctx->al_bits.cap, bb));
     CHK(grow(ctx->al_setof.p, ctx->al_setof.cap, (size_t)nq * 4));
-    CHK(grow(ctx->al_opid.p, ctx->al_opid.cap, ob));
-    CHK(grow(ctx->al_odist.p, ctx->al_odist.cap, ob));
-    CHK(grow(ctx->al_ocnt.p, ctx->al_ocnt.cap, (size_t)nq * 4));
-    CHK(grow(ctx->al_orung.p, ctx->al_orung.cap, (size_t)nq * 4));
-    CHK(grow(ctx->al_octr.p, ctx->al_octr.cap, (size_t)nq * 12));
+    AllowedOut o{};
+    CHK(allowed_out_in_ctx(ctx, nq, k, out_counters != nullptr, &o));
     std::vector<uint32_t> own_set;                               // set_of == NULL: query q uses set q
     if (!set_of) {
         own_set.resize(nq);
         for (uint32_t q = 0; q < nq; q++) own_set[q] = q;
         set_of = own_set.data();
     }
-    HIPCHK(hipMemcpyAsync(ctx->d_q, queries, qb, hipMemcpyHostToDevice, stream));
     HIPCHK(hipMemcpyAsync(ctx->al_bits.p, allow_bits, bb, hipMemcpyHostToDevice, stream));     // as the caller has them: padding bits are masked where they are read
     HIPCHK(hipMemcpyAsync(ctx->al_setof.p, set_of, (size_t)nq * 4, hipMemcpyHostToDevice, stream));
-    // cosine / DOT: the queries are prepared ONCE per call, as the single-set call prepares them
-    const float* d_qk = ctx->d_q;
-    if (metric.any()) {
-        CHK(grow(ctx->d_qn, ctx->cap_qn, doubled_from(4096, metric.qk_floats(nq) * 4)));
-        CHK(grow(ctx->d_sq, ctx->cap_sq, doubled_from(256, metric.sq_floats(nq) * 4)));
-        CHK(metric.prepare(ctx->d_q, ctx->d_qn, ctx->d_sq, nq, stream, &d_qk));
-    }
-    AllowedOut o{};
-    o.pid = ctx->al_opid.as<uint32_t>(); o.dist = ctx->al_odist.as<uint32_t>(); o.count = ctx->al_ocnt.as<uint32_t>();
-    o.rung = ctx->al_orung.as<uint32_t>(); o.counters = counters ? ctx->al_octr.as<uint32_t>() : nullptr;
+    const float* d_qk = nullptr;
+    CHK(ladder_upload_queries(idx, ctx, metric, queries, nq, &d_qk));
     CHK(allowed_sets_device(idx, ctx, d_qk, nq, ctx->al_bits.as<uint32_t>(), n_sets, ctx->al_setof.as<uint32_t>(), set_of, k, max_rungs, o));
     CHK(metric.report(ctx->al_odist.as<float>(), ctx->d_sq, nq, k, stream));
-    HIPCHK(hipMemcpyAsync(out_pid, ctx->al_opid.p, ob, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(out_dist, ctx->al_odist.p, ob, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipMemcpyAsync(out_count, ctx->al_ocnt.p, (size_t)nq * 4, hipMemcpyDeviceToHost, stream));
-    if (out_rung) HIPCHK(hipMemcpyAsync(out_rung, ctx->al_orung.p, (size_t)nq * 4, hipMemcpyDeviceToHost, stream));
-    if (counters) HIPCHK(hipMemcpyAsync(out_counters, ctx->al_octr.p, (size_t)nq * 12, hipMemcpyDeviceToHost, stream));
+    CHK(allowed_download(ctx, nq, k, out_pid, out_dist, out_count, out_rung, out_counters));
     HIPCHK(hipStreamSynchronize(stream));
-    return allowed_times_resolve(ctx);
+    return ladder_times_resolve(ctx);
 }
 
 idist_status idist_allowed_slice_device(const void* d_bits, uint32_t n_sets, uint32_t pitch_words, uint64_t bit_offset, uint32_t n_out,
@@ -3632,22 +3640,14 @@ idist_status idist_partitioned_search_batch_allowed_sets(idist_partitioned* p, c
     CHK(partitioned_check(p, &ef));
     const size_t P = p->parts.size();
     const uint32_t N = p->base[P];
-    if (max_rungs < -1) return fail(IDIST_ERR_INVALID_ARG, "max_rungs %d: -1 (the whole ladder) or a number of rungs >= 0", max_rungs);
-    if (k == 0 || k > IDIST_MAX_EF) return fail(IDIST_ERR_INVALID_ARG, "k %u out of [1,%u]", k, IDIST_MAX_EF);
-    if (ef != 0 && k > ef) return fail(IDIST_ERR_INVALID_ARG, "k %u > ef_search %u", k, ef);
-    if (n_sets == 0) return fail(IDIST_ERR_INVALID_ARG, "n_sets 0: at least one allowed set");
+    CHK(check_ladder_args(max_rungs, k, ef));
+    CHK(check_sets_args(n_sets, set_of, nq));
     if (nq == 0) return IDIST_OK;
-    if (!set_of && n_sets != nq) return fail(IDIST_ERR_INVALID_ARG, "set_of is null (query q uses set q) but n_sets %u != nq %u", n_sets, nq);
     if (!queries || !out_pid || !out_dist || !out_count || (N && !allow_bits)) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
-    if (set_of)
-        for (uint32_t q = 0; q < nq; q++)
-            if (set_of[q] >= n_sets) return fail(IDIST_ERR_INVALID_ARG, "set_of[%u] = %u: query %u names a set outside [0,%u)", q, set_of[q], q, n_sets);
     if (out_rung) std::fill(out_rung, out_rung + (size_t)nq * P, (uint32_t)IDIST_RUNG_NONE);   // (empty parts keep it)
     p->al_slice_ms = 0.0f;
     if (N == 0 || ef == 0) {                                                 // nothing to find, whatever the sets
-        for (size_t i = 0; i < (size_t)nq * k; i++) { out_pid[i] = IDIST_INVALID; out_dist[i] = INFINITY; }
-        memset(out_count, 0, (size_t)nq * 4);
-        if (out_counters) memset(out_counters, 0, (size_t)nq * 12);
+        fill_nothing_found(nq, k, out_pid, out_dist, out_count, nullptr, out_counters);     // (out_rung [nq][P] is filled above)
         return IDIST_OK;
     }
     const bool counters = out_counters != nullptr;
@@ -3717,13 +3717,7 @@ idist_status idist_partitioned_search_batch_allowed_sets(idist_partitioned* p, c
         if (dev == p->merge_device) {
             o.pid = s_pid; o.dist = reinterpret_cast<uint32_t*>(s_dist); o.count = s_cnt; o.rung = s_rung; o.counters = counters ? s_ctr : nullptr;
         } else {
-            CHK(grow(ctx->al_opid.p, ctx->al_opid.cap, row * 4));
-            CHK(grow(ctx->al_odist.p, ctx->al_odist.cap, row * 4));
-            CHK(grow(ctx->al_ocnt.p, ctx->al_ocnt.cap, (size_t)nq * 4));
-            CHK(grow(ctx->al_orung.p, ctx->al_orung.cap, (size_t)nq * 4));
-            CHK(grow(ctx->al_octr.p, ctx->al_octr.cap, (size_t)nq * 12));
-            o.pid = ctx->al_opid.as<uint32_t>(); o.dist = ctx->al_odist.as<uint32_t>(); o.count = ctx->al_ocnt.as<uint32_t>();
-            o.rung = ctx->al_orung.as<uint32_t>(); o.counters = counters ? ctx->al_octr.as<uint32_t>() : nullptr;
+            CHK(allowed_out_in_ctx(ctx, nq, k, counters, &o));
         }
         CHK(allowed_sets_device(pt.idx, ctx, dv.d_q, nq, ctx->al_bits.as<uint32_t>(), n_sets, dv.d_setof, set_of, k, max_rungs, o));
         if (dev != p->merge_device) {
@@ -3734,7 +3728,7 @@ idist_status idist_partitioned_search_batch_allowed_sets(idist_partitioned* p, c
             if (counters) HIPCHK(hipMemcpyPeerAsync(s_ctr, p->merge_device, o.counters, dev, (size_t)nq * 12, ctx->stream));
         }
         HIPCHK(hipStreamSynchronize(ctx->stream));
-        return allowed_times_resolve(ctx);
+        return ladder_times_resolve(ctx);
     };
     auto work = [&](size_t i) {
         st[i] = part(i);
@@ -3870,7 +3864,7 @@ idist_status idist_search_batch_range(const idist_index* idx, idist_search_ctx* 
     CHK(check_ctx(idx, ctx));
     ctx->rg_valid = false;                                                   // whatever happens next, the previous results are gone
     const uint32_t n = idx->n, ef0 = idx->cfg.ef_search;
-    if (max_rungs < -1) return fail(IDIST_ERR_INVALID_ARG, "max_rungs %d: -1 (the whole ladder) or a number of rungs >= 0", max_rungs);
+    CHK(check_max_rungs(max_rungs));
     if (!out_lims) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
     if (nq && n_radius != 1 && n_radius != nq) return fail(IDIST_ERR_INVALID_ARG, "n_radius %u: 1 (one radius for the batch) or nq = %u", n_radius, nq);
     if (nq && (!queries || !radius)) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
@@ -3886,25 +3880,17 @@ idist_status idist_search_batch_range(const idist_index* idx, idist_search_ctx* 
     ctx->al_ev_used = 0;
     if (nq == 0 || n == 0 || ef0 == 0) {                                     // step 1: nothing to find
         std::fill(out_lims, out_lims + nq + 1, (uint64_t)0);
-        if (out_rung) std::fill(out_rung, out_rung + nq, (uint32_t)IDIST_RUNG_NONE);
-        if (out_counters) memset(out_counters, 0, (size_t)nq * 12);
+        fill_nothing_found(nq, 0, nullptr, nullptr, nullptr, out_rung, out_counters);
         ctx->rg_valid = true;
         return IDIST_OK;
     }
-    uint32_t E[8], n_rungs = 0;
-    for (uint32_t e = ef0;; e = std::min<uint32_t>(4u * e, IDIST_MAX_EF)) {
-        E[n_rungs++] = e;
-        if (e >= IDIST_MAX_EF) break;
-    }
-    if (max_rungs >= 0) n_rungs = std::min<uint32_t>(n_rungs, (uint32_t)max_rungs);
+    const AllowedLadder lad = make_ladder(ef0, max_rungs);
 
     HIPCHK(hipSetDevice(idx->device));
     hipStream_t stream = ctx->stream;
     const MetricPasses metric(idx);
     const uint32_t kdim = idx->kdim, kmetric = (uint32_t)idx->cfg.metric;
-    const size_t qb = (size_t)nq * idx->dim * 4;
     const bool counters = out_counters != nullptr;
-    CHK(grow(ctx->d_q, ctx->cap_q, qb));
     CHK(grow(ctx->rg_radius.p, ctx->rg_radius.cap, (size_t)n_radius * 4));
     CHK(grow(ctx->rg_lim.p, ctx->rg_lim.cap, (size_t)nq * 8));
     CHK(grow(ctx->rg_term.p, ctx->rg_term.cap, (size_t)nq * 4));
@@ -3920,16 +3906,9 @@ idist_status idist_search_batch_range(const idist_index* idx, idist_search_ctx* 
     CHK(grow(ctx->rg_list.p, ctx->rg_list.cap, (size_t)nq * 4));
     CHK(grow(ctx->al_orung.p, ctx->al_orung.cap, (size_t)nq * 4));
     CHK(grow(ctx->al_octr.p, ctx->al_octr.cap, (size_t)nq * 12));
-    HIPCHK(hipMemcpyAsync(ctx->d_q, queries, qb, hipMemcpyHostToDevice, stream));
     HIPCHK(hipMemcpyAsync(ctx->rg_radius.p, radius, (size_t)n_radius * 4, hipMemcpyHostToDevice, stream));
-    // cosine / DOT: the queries are prepared ONCE per call, every rung and the scan take them as they are (prepared = true); the
-    // metric's report is applied once, to what the fetch hands out
-    const float* d_qk = ctx->d_q;
-    if (metric.any()) {
-        CHK(grow(ctx->d_qn, ctx->cap_qn, doubled_from(4096, metric.qk_floats(nq) * 4)));
-        CHK(grow(ctx->d_sq, ctx->cap_sq, doubled_from(256, metric.sq_floats(nq) * 4)));
-        CHK(metric.prepare(ctx->d_q, ctx->d_qn, ctx->d_sq, nq, stream, &d_qk));
-    }
+    const float* d_qk = nullptr;                                 // (the metric's report is applied once, to what the fetch hands out)
+    CHK(ladder_upload_queries(idx, ctx, metric, queries, nq, &d_qk));
     RangeState st{};
     st.lim = ctx->rg_lim.as<uint32_t>(); st.term = ctx->rg_term.as<float>(); st.count = ctx->rg_cnt.as<uint32_t>();
     st.off = ctx->rg_off.as<uint64_t>(); st.rung = ctx->al_orung.as<uint32_t>(); st.counters = counters ? ctx->al_octr.as<uint32_t>() : nullptr;
@@ -3941,35 +3920,17 @@ idist_status idist_search_batch_range(const idist_index* idx, idist_search_ctx* 
         HIPCHK(hipGetLastError());
         return IDIST_OK;
     };
-    CHK(allowed_timed(ctx, 3, init_pass));
+    CHK(ladder_timed(ctx, 3, init_pass));
     uint32_t np = nq;
     uint64_t total = 0;                                          // keys in the result buffer so far
     const uint32_t* d_list = nullptr;
     const float* d_pq = d_qk;
     uint32_t* step_cnt = ctx->rg_stepcnt.as<uint32_t>();
     uint64_t* step_off = ctx->rg_stepoff.as<uint64_t>();
-    for (uint32_t r = 0; r < n_rungs && np; r++) {
-        const uint32_t ef = E[r];
-        const size_t rb = (size_t)np * ef * 4;
-        CHK(grow(ctx->d_pid, ctx->cap_pid, rb));
-        CHK(grow(ctx->d_dist, ctx->cap_dist, rb));
-        CHK(grow(ctx->d_cnt, ctx->cap_cnt, (size_t)np * 4));
-        CHK(grow(ctx->d_ctr, ctx->cap_ctr, (size_t)np * 12));
-        bool lds_short = false, ended = false;
-        for (;;) {
-            const idist_status ls = launch_search(idx, ctx, d_pq, np, ctx->d_pid, ctx->d_dist, ctx->d_cnt, counters ? ctx->d_ctr : nullptr,
-                                                  stream, nullptr, nullptr, nullptr, 0, true, ef, &lds_short);
-            if (ls != IDIST_OK) {
-                // a later rung that does not fit a wave's LDS ends the ladder as max_rungs would; rung 0 fails as idist_search_batch does
-                if (lds_short && r != 0) { ended = true; break; }
-                return ls;
-            }
-            HIPCHK(hipStreamSynchronize(stream));
-            idist_status s;
-            if (status_asks_retry(idx, ctx, &s)) continue;      // strict ties: the same rung again with the larger region / the bags
-            if (s != IDIST_OK) return s;
-            break;
-        }
+    for (uint32_t r = 0; r < lad.n_rungs && np; r++) {
+        const uint32_t ef = lad.E[r];
+        bool ended = false;
+        CHK(ladder_rung(idx, ctx, d_pq, np, ef, r, counters, &ended));
         if (ended) break;
         const uint32_t np_step = np;
         auto select_pass = [&]() -> idist_status {
@@ -3978,18 +3939,12 @@ idist_status idist_search_batch_range(const idist_index* idx, idist_search_ctx* 
             HIPCHK(hipGetLastError());
             return range_prefix(ctx, step_cnt, np_step, total, step_off);
         };
-        CHK(allowed_timed(ctx, 3, select_pass));
+        CHK(ladder_timed(ctx, 3, select_pass));
         // the pending queries of the next rung, gathered BEFORE the copy so that one synchronisation reads the new total and their
         // number: the copy still needs this rung's list, so the lists alternate between two buffers (the rows of this rung stay
         // where they are until the copy has run; the next rows go to al_pq)
         uint32_t* next_list = d_list == ctx->al_list.as<uint32_t>() ? ctx->rg_list.as<uint32_t>() : ctx->al_list.as<uint32_t>();
-        auto pending_pass = [&]() -> idist_status {
-            IDIST_LAUNCH(allowed_pending_kernel, (nq + 63u) / 64u, 64, 0, stream, st.pending, nq, d_qk, kdim, next_list, ctx->al_pq.as<float>(),
-                         ctx->al_npend.as<uint32_t>());
-            HIPCHK(hipGetLastError());
-            return IDIST_OK;
-        };
-        CHK(allowed_timed(ctx, 3, pending_pass));
+        CHK(ladder_pending(ctx, st.pending, nq, d_qk, kdim, next_list, 3));
         uint64_t new_total = 0;
         HIPCHK(hipMemcpyAsync(&new_total, step_off + np_step, 8, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipMemcpyAsync(&np, ctx->al_npend.p, 4, hipMemcpyDeviceToHost, stream));
@@ -4006,17 +3961,14 @@ idist_status idist_search_batch_range(const idist_index* idx, idist_search_ctx* 
             HIPCHK(hipGetLastError());
             return IDIST_OK;
         };
-        CHK(allowed_timed(ctx, 3, copy_pass));                  // (enqueued, not waited for: the next launch follows it in stream order)
+        CHK(ladder_timed(ctx, 3, copy_pass));                  // (enqueued, not waited for: the next launch follows it in stream order)
         total = new_total;
         d_list = next_list;
         d_pq = ctx->al_pq.as<float>();
     }
     if (np) {
-        // step 3, exact: [0, n) cut into S segments, one wave per (pending query, segment); S: enough waves for the chip when few
-        // queries are left, never segments of less than one 64-row round; the result does not depend on it
-        uint32_t S = (uint32_t)std::min<uint64_t>(((uint64_t)std::max(ctx->n_cu, 1) * 16u + np - 1u) / np, ((uint64_t)n + 63u) / 64u);
-        if (ctx->knobs.range_segments) S = ctx->knobs.range_segments;
-        S = std::min(std::max(S, 1u), 64u);
+        // step 3, exact: [0, n) cut into S segments, one wave per (pending query, segment)
+        const uint32_t S = exact_segments(ctx, np, n, ctx->knobs.range_segments);
         const uint64_t items = (uint64_t)np * S;
         CHK(grow(ctx->d_cnt, ctx->cap_cnt, (size_t)items * 4));
         CHK(grow(ctx->rg_stepoff.p, ctx->rg_stepoff.cap, (size_t)(items + 1) * 8));
@@ -4048,7 +4000,7 @@ idist_status idist_search_batch_range(const idist_index* idx, idist_search_ctx* 
             HIPCHK(hipGetLastError());
             return IDIST_OK;
         };
-        CHK(allowed_timed(ctx, 4, count_pass));
+        CHK(ladder_timed(ctx, 4, count_pass));
         uint64_t new_total = 0;
         std::vector<uint32_t> ex_len(np);
         HIPCHK(hipMemcpyAsync(&new_total, seg_off + items, 8, hipMemcpyDeviceToHost, stream));
@@ -4057,21 +4009,21 @@ idist_status idist_search_batch_range(const idist_index* idx, idist_search_ctx* 
         if (new_total > max_total) return range_too_many(new_total, max_total, "the exact step");
         CHK(range_grow_keys(ctx, total, new_total));
         auto write_pass = [&]() -> idist_status { return scan_pass(ctx->rg_keys.as<uint64_t>()); };
-        CHK(allowed_timed(ctx, 4, write_pass));
+        CHK(ladder_timed(ctx, 4, write_pass));
         const uint64_t max_len = *std::max_element(ex_len.begin(), ex_len.end());
         auto sort_pass = [&]() -> idist_status { return range_sort(ctx, np, max_len); };
-        CHK(allowed_timed(ctx, 5, sort_pass));
+        CHK(ladder_timed(ctx, 5, sort_pass));
         total = new_total;
     }
     // lims: the prefix sum of the counts, in query order
     uint64_t* d_lims = ctx->rg_lims.as<uint64_t>();
     auto lims_pass = [&]() -> idist_status { return range_prefix(ctx, st.count, nq, 0, d_lims); };
-    CHK(allowed_timed(ctx, 3, lims_pass));
+    CHK(ladder_timed(ctx, 3, lims_pass));
     HIPCHK(hipMemcpyAsync(out_lims, d_lims, ((size_t)nq + 1) * 8, hipMemcpyDeviceToHost, stream));
     if (out_rung) HIPCHK(hipMemcpyAsync(out_rung, ctx->al_orung.p, (size_t)nq * 4, hipMemcpyDeviceToHost, stream));
     if (counters) HIPCHK(hipMemcpyAsync(out_counters, ctx->al_octr.p, (size_t)nq * 12, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
-    CHK(allowed_times_resolve(ctx));
+    CHK(ladder_times_resolve(ctx));
     if (out_lims[nq] != total) return fail(IDIST_ERR_INTERNAL, "range search: the counts sum to %llu, the result buffer holds %llu",
                                            (unsigned long long)out_lims[nq], (unsigned long long)total);
     ctx->rg_total = total;

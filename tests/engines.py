@@ -20,8 +20,10 @@ def engine_params():
 
 
 def build_emu():
-    srcs = [os.path.join(ROOT, "instant-distance_amd", "csrc", f) for f in
-            ("idist_capi.hip", "idist_kernels.hpp", "idist_device.hpp", "idist_mfma.hpp", "idist_combine.hpp")]
+    # everything the emulator library is compiled from: every source of csrc, the C ABI, the emulator itself
+    csrc = os.path.join(ROOT, "instant-distance_amd", "csrc")
+    srcs = [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".hpp"))]
+    srcs += [os.path.join(ROOT, "include", "idist.h")]
     srcs += [os.path.join(ROOT, "tests", "simt", f) for f in ("hip_emu.hpp", "hip_emu.cpp")]
     def stale():
         return not os.path.exists(EMU_SO) or os.path.getmtime(EMU_SO) < max(os.path.getmtime(s) for s in srcs)

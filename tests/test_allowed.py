@@ -386,7 +386,65 @@ def test_hnsw_map(eng):
         assert all(values[int(np.flatnonzero((pts == it.point).all(axis=1))[0])] == it.value for it in row)
 
 
-# ---- 8. the C++ mirror -------------------------------------------------------------------------------------------------------------
+# ---- 8. a rung that does not fit a wave's LDS ends the ladder ------------------------------------------------------------------------
+# The walk's LDS per wave (smem_bytes, idist_kernels.hpp): 4 stride + 8 wcap + 512 + 1056 (QuadCtl) + 4 (2048 Bloom + 64 dirty words)
+# = 4 stride + 8 wcap + 10016 bytes, wcap = ef + 64 + 64 (ties) + 8; refused beyond 65536.  dim 13200 is stride 13200 = 52800 B (no
+# on-chip set fits 40 KiB next to it: every rung is the bitmap walk), so on the ladder 16, 64, 256, ...
+#   ef  16: 52800 + 8 * 152 + 10016 = 64032   launches
+#   ef  64: 52800 + 8 * 200 + 10016 = 64416   launches
+#   ef 256: 52800 + 8 * 392 + 10016 = 65952   refused: rung 2 ends the ladder, as max_rungs = 2 would
+LDS_DIM, LDS_EF, LDS_R_END = 13200, 16, 2
+LDS_MESSAGE = "of LDS per wave (> 64 KiB)"
+
+
+def lds_points():
+    """256 x 13200-d and 8 queries, the same for both engines (the arithmetic above has no small version): eight coordinates carry
+    the geometry, the others a hundredth of it, so that a set can be near some queries and far from others"""
+    rng = np.random.default_rng(41)
+    scale = np.full(LDS_DIM, 0.01, np.float32)
+    scale[:8] = 1.0
+    return rng.random((256, LDS_DIM), dtype=np.float32) * scale, rng.random((8, LDS_DIM), dtype=np.float32) * scale
+
+
+def lds_case(oracle):
+    """(the case, k, two allowed sets: the fifth of the points farthest from query 0 — starts on rung 0, query 0 for one is still
+    pending behind rung 1 — and eight points — its start rule names rung 2, the refused one)"""
+    if "lds" not in _CASES:
+        _CASES["lds"] = Case(oracle, *lds_points(), LDS_EF)
+    c = _CASES["lds"]
+    d0 = ((c.pts[:, :8] - c.q[0, :8]) ** 2).sum(axis=1)
+    few = np.zeros(len(c.pts), bool)
+    few[np.random.default_rng(42).choice(len(c.pts), 8, replace=False)] = True
+    return c, 3, [d0 >= np.sort(d0)[-51], few]
+
+
+def lds_rung0_refused(ida, c, call):
+    """ef_search = the refused rung's: `call(h)` fails as search_batch does, with its message"""
+    h = ida.Hnsw.from_parts(c.pts, c.zero, c.layers, ida.Builder().ef_search(ladder(LDS_EF)[LDS_R_END]))
+    with pytest.raises(ida.IdistError) as e0:
+        h.search_batch(c.q, ida.Search())
+    with pytest.raises(ida.IdistError) as e1:
+        call(h)
+    assert LDS_MESSAGE in e0.value.message and "dim/ef_search need" in e0.value.message
+    assert (e1.value.status, e1.value.message) == (e0.value.status, e0.value.message)
+
+
+def test_lds_short_rung_ends_the_ladder(eng, oracle):
+    ida, kind = eng
+    c, k, masks = lds_case(oracle)
+    h = c.hnsw(ida)
+    seen = set()
+    for i, mask in enumerate(masks):
+        want = c.model(mask, k, max_rungs=LDS_R_END)
+        print("set", i, "rungs", want[3].tolist(), "causes", want[5].tolist())
+        check(h.search_allowed(c.q, mask, k, ida.Search(), counters=True), want, f"set {i}, the whole ladder")
+        seen |= set(zip(want[3].tolist(), want[5].tolist()))
+    assert (EXACT, "ended") in seen and (EXACT, "start") in seen and any(r < LDS_R_END for r, _ in seen)
+    assert next(r for r, e in enumerate(ladder(LDS_EF)) if e * int(masks[1].sum()) >= k * len(c.pts)) == LDS_R_END   # (the small set's first rung)
+    lds_rung0_refused(ida, c, lambda hb: hb.search_allowed(c.q, masks[0], k, ida.Search()))
+
+
+# ---- 9. the C++ mirror -------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 def test_host_cpp_allowed(tmp_path):
     """host/instant_distance.hpp's Hnsw::search_allowed, compiled against libidist.so and run (tests/host/allowed.cpp checks it

@@ -15,7 +15,7 @@ import pytest
 
 import parity_cases as pc
 from engines import engine_params
-from test_allowed import Case, allowed_sets, check, ladder, main_case, small_case
+from test_allowed import LDS_R_END, Case, allowed_sets, check, ladder, lds_case, lds_rung0_refused, main_case, small_case
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID = 0xFFFFFFFF
@@ -390,7 +390,24 @@ def test_hnsw_map(eng):
         assert all(values[int(np.flatnonzero((pts == it.point).all(axis=1))[0])] == it.value for it in row)
 
 
-# ---- 8. the C++ mirror -----------------------------------------------------------------------------------------------------------------------
+# ---- 8. a rung that does not fit a wave's LDS ends the ladder (the shape and its arithmetic: tests/test_allowed.py) ----------------------
+def test_lds_short_rung_ends_the_ladder(eng, oracle):
+    """three sets in one call: queries pending behind rung 1, queries WAITING for rung 2 (the refused one) and queries answered on
+    rung 0 — the call returns what max_rungs = 2 defines"""
+    ida, kind = eng
+    c, k, masks = lds_case(oracle)
+    masks = masks + [np.ones(len(c.pts), bool)]
+    set_of = np.arange(len(c.q)) % 3
+    assert start_rung(c, masks[1], k) == LDS_R_END and start_rung(c, masks[0], k) == 0
+    want = rows_of([c.model(m, k, max_rungs=LDS_R_END) for m in masks], set_of)
+    print("rungs", want[3].tolist(), "causes", want[5].tolist())
+    seen = set(zip(want[3].tolist(), want[5].tolist()))
+    assert (EXACT, "ended") in seen and (EXACT, "start") in seen and (0, "") in seen
+    check(c.hnsw(ida).search_allowed_sets(c.q, masks, set_of, k, ida.Search(), counters=True), want, "the whole ladder")
+    lds_rung0_refused(ida, c, lambda hb: hb.search_allowed_sets(c.q, masks, set_of, k, ida.Search()))
+
+
+# ---- 9. the C++ mirror -----------------------------------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 def test_host_cpp_allowed_sets(tmp_path):
     """host/instant_distance.hpp's Hnsw::search_allowed_sets, compiled against libidist.so and run (tests/host/allowed_sets.cpp

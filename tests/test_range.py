@@ -12,7 +12,7 @@ import pytest
 
 import parity_cases as pc
 from engines import engine_params
-from test_allowed import Case, ladder
+from test_allowed import LDS_EF, LDS_R_END, Case, ladder, lds_points, lds_rung0_refused
 from test_cosine import halved, np_normalize
 from test_dot import np_augment, np_norms, np_queries, reported
 
@@ -408,3 +408,19 @@ def test_non_finite_queries(eng, oracle):
         check(got, want, f"max_rungs {m}")
         assert np.all(np.isposinf(got.distance[int(got.lims[1]):int(got.lims[3])]))
     assert counts(rc.model(rad, 0))[1] == n
+
+
+# ---- 11. a rung that does not fit a wave's LDS ends the ladder (the shape and its arithmetic: tests/test_allowed.py) ---------------
+def test_lds_short_rung_ends_the_ladder(eng, oracle):
+    """radii that hold more than the 64 results of rung 1 leave their queries pending when rung 2 is refused: the call returns what
+    max_rungs = 2 defines"""
+    ida, kind = eng
+    if "lds" not in _CASES:
+        _CASES["lds"] = RCase(oracle, *lds_points(), LDS_EF)
+    rc = _CASES["lds"]
+    rad = radii_of(rc, ["below", "ef", "4ef", "n/2", "inf", 0, "ef+1", "big"])
+    want = rc.model(rad, max_rungs=LDS_R_END)
+    print("rungs", want[3].tolist(), "counts", counts(want).tolist())
+    assert {0, 1, EXACT} <= set(want[3].tolist()) and counts(want)[want[3] == EXACT].min() > ladder(LDS_EF)[LDS_R_END - 1]
+    check(rc.hnsw(ida).search_range(rc.q, rad, ida.Search(), counters=True), want, "the whole ladder")
+    lds_rung0_refused(ida, rc.c, lambda hb: hb.search_range(rc.q, rad, ida.Search()))
