@@ -14,8 +14,9 @@
 //   allowed_pending_kernel  the pending queries in ascending order (a wave per 64 queries: the set flags in front of its chunk are
 //                           counted, not scanned — no atomics, the same list whatever the schedule), and their prepared rows
 //                           gathered into a contiguous buffer for the next rung's launch.
-//   allowed_scan_kernel     the exact step: bruteforce_kernel's machinery (dist_rounds, w_rank / w_insert with ef = k) over one
-//                           contiguous segment of the ascending id list of A per wave; grid = pending queries x S segments.  Each
+//   allowed_scan_kernel     the exact step: the shared steps of the exact scans (scan_segment, stage_query, scan_rank_batch with
+//                           ef = k, topk_emit_list: idist_device.hpp / idist_kernels.hpp) over one contiguous segment of the
+//                           ascending id list of A per wave; grid = pending queries x S segments.  Each
 //                           wave writes its segment's sorted top-k as list s in merge_topk_kernel's input layout (base 0): the
 //                           merge by (distance bits, id) gives the k best, and ids are distinct, so the result does not depend on S.
 //
@@ -33,8 +34,8 @@
 //                             [0, n).  A wave takes 64 windows at a time (one 64-bit load per lane), skips the all-zero ones by a
 //                             ballot, and compacts the set bits of the others into ascending ids by prefix popcount, in batches of
 //                             64 in act_pid; an id that does not fit the batch stays in its lane's register until the batch has been
-//                             ranked and opens the next one.  Everything after that is allowed_scan_kernel's.  No id list exists,
-//                             on the host or the device; the staging does not depend on the number of sets.
+//                             ranked (scan_rank_batch) and opens the next one.  Staging and output are allowed_scan_kernel's.  No id
+//                             list exists, on the host or the device; the staging does not depend on the number of sets.
 //
 // The partitioned index (idist_partitioned_search_batch_allowed_sets): every part runs the several-sets call on ITS slice of the
 // caller's global bitmaps, and base[p] is no multiple of 32 in general:
@@ -179,47 +180,19 @@ __global__ __launch_bounds__(64) void allowed_scan_kernel(IndexView ix, const fl
     IDIST_DYN_SMEM(smem_raw);
     const Smem sm = carve(smem_raw, ix.stride, wcap, false);
     const int lane = lane_id();
-    const uint32_t nb = NB >= 0 ? (uint32_t)NB : ix.nb;
     const uint64_t items = (uint64_t)np * S;
     for (uint64_t w = blockIdx.x; w < items; w += gridDim.x) {
-        const uint32_t p = (uint32_t)(w / S), s = (uint32_t)(w % S);
-        const uint32_t lo = (uint32_t)((uint64_t)n_ids * s / S), hi = (uint32_t)((uint64_t)n_ids * (s + 1u) / S);
-        wave_sync();
-        for (uint32_t o = lane; o < ix.stride; o += 64) sm.q[o] = 0.0f;
-        wave_sync();
-        for (uint32_t e = lane; e < ix.dim; e += 64) sm.q[blocked_pos(e, nb)] = queries[(size_t)p * ix.dim + e];
-        wave_sync();
+        uint32_t p, lo, hi;
+        scan_segment(n_ids, S, w, &p, &lo, &hi);
+        stage_query<NB>(ix, sm.q, queries + (size_t)p * ix.dim);
         WState st{sm.W, 0, (int)k, 0, 0u};
         for (uint32_t base = lo; base < hi; base += 64u) {
             const int na = hi - base < 64u ? (int)(hi - base) : 64;
-            uint32_t id = kInvalid;
-            if (lane < na) {
-                id = ids[base + (uint32_t)lane];
-                sm.act_pid[lane] = id;
-            }
-            wave_sync();
-            dist_rounds<NB, RS, TAIL>(ix, sm.q, sm.act_pid, sm.act_dist, na);
-            wave_sync();
-            uint64_t key = kMaxKey;
-            if (lane < na) key = ((uint64_t)sm.act_dist[lane] << 32) | id;
-            const uint64_t thr = st.plen >= st.ef ? (st.W[st.ef - 1] & kKeyMask) : kMaxKey + 1ull;
-            uint64_t pm = __ballot(lane < na && key < thr);
-            while (pm) {
-                const int i = __builtin_ctzll(pm);
-                pm &= pm - 1ull;
-                const uint64_t kk = bcast_u64(key, i);
-                const int idx = w_rank(st, kk);
-                if (idx < st.ef) w_insert(st, idx, kk);
-            }
-            if (st.plen > st.ef) st.plen = st.ef;   // plain truncate (no candidates here)
-            wave_sync();
+            if (lane < na) sm.act_pid[lane] = ids[base + (uint32_t)lane];
+            scan_rank_batch<NB, RS, TAIL>(ix, sm, st, na);
         }
-        const size_t row = ((size_t)s * np + p) * k;
-        for (uint32_t i = lane; i < (uint32_t)st.plen; i += 64) {
-            out_pid[row + i] = (uint32_t)st.W[i];
-            out_dist[row + i] = (uint32_t)((st.W[i] & kKeyMask) >> 32);
-        }
-        if (lane == 0) out_count[(size_t)s * np + p] = (uint32_t)st.plen;
+        const size_t slot = (size_t)(w % S) * np + p;
+        topk_emit_list(st, slot * k, slot, out_pid, out_dist, out_count);
     }
 }
 
@@ -269,28 +242,6 @@ __device__ __forceinline__ uint64_t allowed_window(const uint32_t* __restrict__ 
     return m;
 }
 
-// One batch of the exact step: the na ids in act_pid measured and ranked into the wave's top-k (allowed_scan_kernel's loop body).
-template <int NB, int RS, int TAIL>
-__device__ __forceinline__ void allowed_rank_batch(const IndexView& ix, const Smem& sm, WState& st, int na) {
-    const int lane = lane_id();
-    wave_sync();
-    dist_rounds<NB, RS, TAIL>(ix, sm.q, sm.act_pid, sm.act_dist, na);
-    wave_sync();
-    uint64_t key = kMaxKey;
-    if (lane < na) key = ((uint64_t)sm.act_dist[lane] << 32) | sm.act_pid[lane];
-    const uint64_t thr = st.plen >= st.ef ? (st.W[st.ef - 1] & kKeyMask) : kMaxKey + 1ull;
-    uint64_t pm = __ballot(lane < na && key < thr);
-    while (pm) {
-        const int i = __builtin_ctzll(pm);
-        pm &= pm - 1ull;
-        const uint64_t kk = bcast_u64(key, i);
-        const int idx = w_rank(st, kk);
-        if (idx < st.ef) w_insert(st, idx, kk);
-    }
-    if (st.plen > st.ef) st.plen = st.ef;   // plain truncate (no candidates here)
-    wave_sync();
-}
-
 // The exact step of the several-sets call, straight from the bitmaps.  bits [n_sets][words]; list [np] (nullptr: the identity): the
 // original query index of pending row p, set_of [nq]: its set.  The n_win = ceil(n / 64) windows of [0, n) are cut into S contiguous
 // segments [n_win s / S, n_win (s + 1) / S) (an empty one yields an empty list).  Work item w = p * S + s; the outputs as
@@ -305,18 +256,13 @@ __global__ __launch_bounds__(64) void allowed_scan_bits_kernel(IndexView ix, con
     const Smem sm = carve(smem_raw, ix.stride, wcap, false);
     const int lane = lane_id();
     const uint64_t below = (1ull << lane) - 1ull;
-    const uint32_t nb = NB >= 0 ? (uint32_t)NB : ix.nb;
     const uint32_t n_win = (uint32_t)(((uint64_t)n + 63u) / 64u);
     const uint64_t items = (uint64_t)np * S;
     for (uint64_t w = blockIdx.x; w < items; w += gridDim.x) {
-        const uint32_t p = (uint32_t)(w / S), s = (uint32_t)(w % S);
-        const uint32_t lo = (uint32_t)((uint64_t)n_win * s / S), hi = (uint32_t)((uint64_t)n_win * (s + 1u) / S);
+        uint32_t p, lo, hi;
+        scan_segment(n_win, S, w, &p, &lo, &hi);
         const uint32_t* b = bits + (size_t)set_of[list ? list[p] : p] * words;
-        wave_sync();
-        for (uint32_t o = lane; o < ix.stride; o += 64) sm.q[o] = 0.0f;
-        wave_sync();
-        for (uint32_t e = lane; e < ix.dim; e += 64) sm.q[blocked_pos(e, nb)] = queries[(size_t)p * ix.dim + e];
-        wave_sync();
+        stage_query<NB>(ix, sm.q, queries + (size_t)p * ix.dim);
         WState st{sm.W, 0, (int)k, 0, 0u};
         uint32_t fill = 0;                                    // ids waiting in act_pid, < 64 between windows
         for (uint32_t g = lo; g < hi; g += 64u) {
@@ -334,19 +280,15 @@ __global__ __launch_bounds__(64) void allowed_scan_bits_kernel(IndexView ix, con
                 if (ok && pos < 64u) sm.act_pid[pos] = id;
                 fill += (uint32_t)__popcll(m);
                 if (fill >= 64u) {
-                    allowed_rank_batch<NB, RS, TAIL>(ix, sm, st, 64);
+                    scan_rank_batch<NB, RS, TAIL>(ix, sm, st, 64);
                     if (ok && pos >= 64u) sm.act_pid[pos - 64u] = id;     // carried over in the lane's register
                     fill -= 64u;
                 }
             }
         }
-        if (fill) allowed_rank_batch<NB, RS, TAIL>(ix, sm, st, (int)fill);
-        const size_t row = ((size_t)s * np + p) * k;
-        for (uint32_t i = lane; i < (uint32_t)st.plen; i += 64) {
-            out_pid[row + i] = (uint32_t)st.W[i];
-            out_dist[row + i] = (uint32_t)((st.W[i] & kKeyMask) >> 32);
-        }
-        if (lane == 0) out_count[(size_t)s * np + p] = (uint32_t)st.plen;
+        if (fill) scan_rank_batch<NB, RS, TAIL>(ix, sm, st, (int)fill);
+        const size_t slot = (size_t)(w % S) * np + p;
+        topk_emit_list(st, slot * k, slot, out_pid, out_dist, out_count);
     }
 }
 

@@ -3013,7 +3013,7 @@ static idist_status bruteforce_scan(const idist_index* idx, const float* queries
     HIPCHK(hipMemcpy(d_q, queries, qb, hipMemcpyHostToDevice));
     const float *d_qk = nullptr, *d_sq = nullptr;                        // what the kernel reads: [nq][kdim]
     CHK(metric.prepare_own(d_q, mem, nq, nullptr, &d_qk, &d_sq));
-    const uint32_t wcap = k + 64 + 8;
+    const uint32_t wcap = topk_wcap(k);
     const size_t smem = smem_bytes(idx->L.stride, wcap, false);
     const uint32_t grid = std::min<uint32_t>(nq, (uint32_t)idx->n_cu * 16);
     IndexView view = idx->view();
@@ -3103,7 +3103,7 @@ static idist_status bruteforce_mfma(const idist_index* idx, const float* queries
         a.mode = 1; a.p_begin = 0; a.p_end = n;
         IDIST_LAUNCH(mfma_dist_kernel, nqt * ((n + kTN - 1) / kTN), 256, smem_g, st, a);
         // pass 3: canonical re-rank of the candidates
-        const uint32_t wcap = k + 64 + 8;
+        const uint32_t wcap = topk_wcap(k);
         const size_t smem_r = (size_t)stride * 4 + (size_t)wcap * 8 + 2 * 64 * 4;
         const uint32_t gridr = std::min<uint32_t>(qc, (uint32_t)idx->n_cu * 16);
 #define LAUNCH_RR(NB_, RS_, TAIL_)                                                                                   \
@@ -3310,7 +3310,7 @@ idist_status allowed_exact_step(const idist_index* idx, idist_search_ctx* ctx, c
     CHK(grow(ctx->al_mpid.p, ctx->al_mpid.cap, mb));
     CHK(grow(ctx->al_mdist.p, ctx->al_mdist.cap, mb));
     CHK(grow(ctx->al_mcnt.p, ctx->al_mcnt.cap, (size_t)np * 4));
-    const uint32_t wcap = k + 64 + 8;
+    const uint32_t wcap = topk_wcap(k);
     const size_t smem = smem_bytes(idx->L.stride, wcap, false);
     if (smem > 64 * 1024) return fail(IDIST_ERR_INVALID_ARG, "dim/k need %zu B of LDS per wave (> 64 KiB)", smem);
     auto scan_and_merge = [&]() -> idist_status {

@@ -940,6 +940,76 @@ __device__ __forceinline__ void w_insert(WState& st, int idx, uint64_t k) {
     if (idx < st.cursor) st.cursor = idx;
 }
 
+// ---------------------------------------------------------------------------
+// The exact scans (brute force, rerank, the exact steps of the restricted and the range search) are built from the
+// routines below, so that they agree bit for bit: one staging of the query, one ranking, one writer per output form.
+// ---------------------------------------------------------------------------
+// Row `src` ([dim] floats, natural order) into q[0..stride) in the blocked order of the point rows, the padding zero.
+// Barriers: on entry every LDS read of the previous query by this wave is done before q is overwritten; the zeroes land
+// before the scatter (a padding position and an element never race); on exit the row is visible to the whole wave.
+// A caller needs no wave_sync of its own around the call.
+template <int NB>
+__device__ __forceinline__ void stage_query(const IndexView& ix, float* q, const float* __restrict__ src) {
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint32_t nb = NB >= 0 ? (uint32_t)NB : ix.nb;
+    wave_sync();
+    for (uint32_t o = lane; o < ix.stride; o += 64) q[o] = 0.0f;
+    wave_sync();
+    for (uint32_t e = lane; e < ix.dim; e += 64) q[blocked_pos(e, nb)] = src[e];
+    wave_sync();
+}
+
+// One batch of up to 64 keys (dist_bits << 32 | id, one per lane where `on`) ranked into the wave's sorted top-k st (ef = k):
+// a key enters iff it is below the k-th (Vec::binary_search + insert as in `push`, core/lib.rs:712-719: equal distances in id
+// order), then the plain truncate — there are no candidates here.  Ends with a wave_sync: st.W is settled for the next batch.
+__device__ __forceinline__ void topk_rank(WState& st, uint64_t key, bool on) {
+    const uint64_t thr = st.plen >= st.ef ? (st.W[st.ef - 1] & kKeyMask) : kMaxKey + 1ull;
+    uint64_t pm = __ballot(on && key < thr);
+    while (pm) {
+        const int i = __builtin_ctzll(pm);
+        pm &= pm - 1ull;
+        const uint64_t kk = bcast_u64(key, i);
+        const int idx = w_rank(st, kk);
+        if (idx < st.ef) w_insert(st, idx, kk);
+    }
+    if (st.plen > st.ef) st.plen = st.ef;
+    wave_sync();
+}
+
+// The top-k as one padded result row: out_pid / out_dist [k], kInvalid / +inf behind the st.plen entries found.
+__device__ __forceinline__ void topk_emit_row(const WState& st, uint32_t k, uint32_t* out_pid, float* out_dist) {
+    for (uint32_t i = (uint32_t)lane_id(); i < k; i += 64) {
+        uint32_t pid = kInvalid;
+        float d = __uint_as_float(0x7f800000u);
+        if ((int)i < st.plen) {
+            pid = (uint32_t)st.W[i];
+            d = __uint_as_float((uint32_t)((st.W[i] & kKeyMask) >> 32));
+        }
+        out_pid[i] = pid;
+        out_dist[i] = d;
+    }
+}
+
+// The top-k as one input list of merge_topk_kernel: the st.plen entries from out_pid / out_dist + row on (nothing behind them
+// is written), their number in out_count[slot].
+__device__ __forceinline__ void topk_emit_list(const WState& st, size_t row, size_t slot, uint32_t* out_pid, uint32_t* out_dist,
+                                               uint32_t* out_count) {
+    const int lane = lane_id();
+    for (uint32_t i = (uint32_t)lane; i < (uint32_t)st.plen; i += 64) {
+        out_pid[row + i] = (uint32_t)st.W[i];
+        out_dist[row + i] = (uint32_t)((st.W[i] & kKeyMask) >> 32);
+    }
+    if (lane == 0) out_count[slot] = (uint32_t)st.plen;
+}
+
+// Work item w = p * S + s of a segmented scan: query row p and segment s = [units s / S, units (s + 1) / S) of `units` items.
+__device__ __forceinline__ void scan_segment(uint32_t units, uint32_t S, uint64_t w, uint32_t* p, uint32_t* lo, uint32_t* hi) {
+    const uint32_t s = (uint32_t)(w % S);
+    *p = (uint32_t)(w / S);
+    *lo = (uint32_t)((uint64_t)units * s / S);
+    *hi = (uint32_t)((uint64_t)units * (s + 1u) / S);
+}
+
 // first un-expanded entry at or after cursor, -1 if none (== candidates.pop() of the
 // minimum LIVE candidate, core/lib.rs:599; dead ones would only trigger the break)
 __device__ __forceinline__ int w_pop(WState& st) {

@@ -167,6 +167,22 @@ __device__ __forceinline__ Smem carve(uint8_t* base, uint32_t stride, uint32_t w
     return s;
 }
 
+// W capacity of a wave's top-k in the exact scans (topk_rank with ef = k): k entries, the batch of 64 that w_insert may put on top of
+// them before the truncate, 8 spare.
+constexpr uint32_t topk_wcap(uint32_t k) { return k + 64u + 8u; }
+// One batch of an exact scan: the na (<= 64) ids the wave has put into sm.act_pid measured against the staged query (canonical
+// distance, dist_rounds) and ranked into its top-k (topk_rank).  The barriers around the distance pass are in here.
+template <int NB, int RS, int TAIL>
+__device__ __forceinline__ void scan_rank_batch(const IndexView& ix, const Smem& sm, WState& st, int na) {
+    const int lane = lane_id();
+    wave_sync();
+    dist_rounds<NB, RS, TAIL>(ix, sm.q, sm.act_pid, sm.act_dist, na);
+    wave_sync();
+    uint64_t key = kMaxKey;
+    if (lane < na) key = ((uint64_t)sm.act_dist[lane] << 32) | sm.act_pid[lane];
+    topk_rank(st, key, lane < na);
+}
+
 // ---------------------------------------------------------------------------
 // Hnsw::search (core/lib.rs:352-383) for a batch: persistent slots pull queries.
 // ---------------------------------------------------------------------------
@@ -266,7 +282,7 @@ __global__ __launch_bounds__(walk_quad(LAT) ? 256 : 64) IDIST_WAVES_ATTR(LAT) vo
         first_pull = false;
         if (qi >= a.nq) break;
 
-        // stage the query tile in LDS in the blocked order of the point rows
+        // the query tile in LDS, in the blocked order of the point rows: stage_query's steps, kept open (the walk kernels' ISA stays as it is)
         for (uint32_t o = lane; o < ix.stride; o += 64) sm.q[o] = 0.0f;
         wave_sync();
         const float* qsrc = a.queries + (size_t)qi * ix.dim;
@@ -355,13 +371,9 @@ __global__ __launch_bounds__(64) void distance_batch_kernel(IndexView ix, const 
     const Smem sm = carve(smem_raw, ix.stride, 0, false);
     const int lane = lane_id();
     const uint32_t chunks = (n_ids + 63u) / 64u;
-    const uint32_t nb = NB >= 0 ? (uint32_t)NB : ix.nb;
     for (uint32_t w = blockIdx.x; w < nq * chunks; w += gridDim.x) {
         const uint32_t qi = w / chunks, c0 = (w % chunks) * 64u;
-        wave_sync();
-        for (uint32_t o = lane; o < ix.stride; o += 64) sm.q[o] = 0.0f;
-        wave_sync();
-        for (uint32_t e = lane; e < ix.dim; e += 64) sm.q[blocked_pos(e, nb)] = queries[(size_t)qi * ix.dim + e];
+        stage_query<NB>(ix, sm.q, queries + (size_t)qi * ix.dim);
         const uint32_t i = c0 + lane;
         uint32_t id = kInvalid;
         if (i < n_ids) id = ids[(size_t)qi * n_ids + i];
@@ -385,16 +397,11 @@ __global__ __launch_bounds__(64) void filter_bound_kernel(IndexView ix, const fl
     const Smem sm = carve(smem_raw, ix.stride, 0, false);
     const int lane = lane_id();
     const uint32_t chunks = (n_ids + 63u) / 64u;
-    const uint32_t nb = NB >= 0 ? (uint32_t)NB : ix.nb;
     constexpr int NCH = filt_chunks<NB, RS, TAIL, kWalkFilterBit>();       // (runtime geometries: the larger tile)
     constexpr bool T8 = filt_tail8<NB, RS, TAIL>();
     for (uint32_t w = blockIdx.x; w < nq * chunks; w += gridDim.x) {
         const uint32_t qi = w / chunks, c0 = (w % chunks) * 64u;
-        wave_sync();
-        for (uint32_t o = lane; o < ix.stride; o += 64) sm.q[o] = 0.0f;
-        wave_sync();
-        for (uint32_t e = lane; e < ix.dim; e += 64) sm.q[blocked_pos(e, nb)] = queries[(size_t)qi * ix.dim + e];
-        wave_sync();
+        stage_query<NB>(ix, sm.q, queries + (size_t)qi * ix.dim);
         FilterQ<NCH, T8> fq;
         filter_stage_query(ix, sm.q, fq);
         const uint32_t i = c0 + lane;
@@ -422,48 +429,19 @@ __global__ __launch_bounds__(64) void bruteforce_kernel(IndexView ix, const floa
     IDIST_DYN_SMEM(smem_raw);
     const Smem sm = carve(smem_raw, ix.stride, wcap, false);
     const int lane = lane_id();
-    const uint32_t nb = NB >= 0 ? (uint32_t)NB : ix.nb;
     for (;;) {
         uint32_t qi = 0;
         if (lane == 0) qi = atomicAdd(next, 1u);
         qi = uniform_u32(qi);
         if (qi >= nq) break;
-        wave_sync();
-        for (uint32_t o = lane; o < ix.stride; o += 64) sm.q[o] = 0.0f;
-        wave_sync();
-        for (uint32_t e = lane; e < ix.dim; e += 64) sm.q[blocked_pos(e, nb)] = queries[(size_t)qi * ix.dim + e];
-        wave_sync();
+        stage_query<NB>(ix, sm.q, queries + (size_t)qi * ix.dim);
         WState st{sm.W, 0, (int)k, 0, 0u};
         for (uint32_t base = 0; base < ix.n; base += 64) {
             const int na = ix.n - base < 64u ? (int)(ix.n - base) : 64;
             if (lane < na) sm.act_pid[lane] = base + lane;
-            wave_sync();
-            dist_rounds<NB, RS, TAIL>(ix, sm.q, sm.act_pid, sm.act_dist, na);
-            wave_sync();
-            uint64_t key = kMaxKey;
-            if (lane < na) key = ((uint64_t)sm.act_dist[lane] << 32) | (base + lane);
-            const uint64_t thr = st.plen >= st.ef ? (st.W[st.ef - 1] & kKeyMask) : kMaxKey + 1ull;
-            uint64_t pm = __ballot(lane < na && key < thr);
-            while (pm) {
-                const int i = __builtin_ctzll(pm);
-                pm &= pm - 1ull;
-                const uint64_t kk = bcast_u64(key, i);
-                const int idx = w_rank(st, kk);
-                if (idx < st.ef) w_insert(st, idx, kk);
-            }
-            if (st.plen > st.ef) st.plen = st.ef;   // plain truncate (no candidates here)
-            wave_sync();
+            scan_rank_batch<NB, RS, TAIL>(ix, sm, st, na);
         }
-        for (uint32_t i = lane; i < k; i += 64) {
-            uint32_t pid = kInvalid;
-            float d = __uint_as_float(0x7f800000u);
-            if ((int)i < st.plen) {
-                pid = (uint32_t)st.W[i];
-                d = __uint_as_float((uint32_t)((st.W[i] & kKeyMask) >> 32));
-            }
-            out_pid[(size_t)qi * k + i] = pid;
-            out_dist[(size_t)qi * k + i] = d;
-        }
+        topk_emit_row(st, k, out_pid + (size_t)qi * k, out_dist + (size_t)qi * k);
     }
 }
 

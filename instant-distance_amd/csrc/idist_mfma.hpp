@@ -184,17 +184,7 @@ __global__ __launch_bounds__(64) void kth_threshold_kernel(const float* __restri
             const uint32_t c = base + lane;
             uint64_t key = kMaxKey;
             if (c < ncols) key = ((uint64_t)__float_as_uint(dense[(size_t)q * dense_ld + c]) << 32) | c;
-            const uint64_t t = st.plen >= st.ef ? (st.W[st.ef - 1] & kKeyMask) : kMaxKey + 1ull;
-            uint64_t pm = __ballot(c < ncols && key < t);
-            while (pm) {
-                const int i = __builtin_ctzll(pm);
-                pm &= pm - 1ull;
-                const uint64_t kk = bcast_u64(key, i);
-                const int idx = w_rank(st, kk);
-                if (idx < st.ef) w_insert(st, idx, kk);
-            }
-            if (st.plen > st.ef) st.plen = st.ef;
-            wave_sync();
+            topk_rank(st, key, c < ncols);
         }
         if (lane == 0) {
             // fewer than k sample points: no bound.  Slack covers |d~ - d*| of both the sample's k-th and the candidate.
@@ -206,57 +196,30 @@ __global__ __launch_bounds__(64) void kth_threshold_kernel(const float* __restri
     }
 }
 
-// exact canonical top-k of each query's candidate list (same machinery as bruteforce_kernel)
+// exact canonical top-k of each query's candidate list: bruteforce_kernel's steps (stage_query, scan_rank_batch, topk_emit_row) over
+// cand[qi][0..cnt) instead of every id.  Its own, smaller LDS carve (no hand-over block): q, W, act_pid, act_dist.
 template <int NB, int RS, int TAIL>
 __global__ __launch_bounds__(64) void rerank_kernel(IndexView ix, const float* __restrict__ queries, uint32_t nq, uint32_t k,
                                                    uint32_t wcap, const uint32_t* __restrict__ cand, const uint32_t* __restrict__ cnt,
                                                    uint32_t cap, uint32_t* out_pid, float* out_dist, uint32_t* overflow) {
     IDIST_DYN_SMEM(smem_raw);
-    float* q = reinterpret_cast<float*>(smem_raw);
-    uint64_t* W = reinterpret_cast<uint64_t*>(q + ix.stride);
-    uint32_t* act_pid = reinterpret_cast<uint32_t*>(W + wcap);
-    uint32_t* act_dist = act_pid + 64;
+    Smem sm{};
+    sm.q = reinterpret_cast<float*>(smem_raw);
+    sm.W = reinterpret_cast<uint64_t*>(sm.q + ix.stride);
+    sm.act_pid = reinterpret_cast<uint32_t*>(sm.W + wcap);
+    sm.act_dist = sm.act_pid + 64;
     const int lane = lane_id();
-    const uint32_t nb = NB >= 0 ? (uint32_t)NB : ix.nb;
     for (uint32_t qi = blockIdx.x; qi < nq; qi += gridDim.x) {
-        wave_sync();
-        for (uint32_t o = lane; o < ix.stride; o += 64) q[o] = 0.0f;
-        wave_sync();
-        for (uint32_t e = lane; e < ix.dim; e += 64) q[blocked_pos(e, nb)] = queries[(size_t)qi * ix.dim + e];
-        wave_sync();
+        stage_query<NB>(ix, sm.q, queries + (size_t)qi * ix.dim);
         uint32_t nc = cnt[qi];
         if (nc > cap) { nc = cap; if (lane == 0) atomicAdd(overflow, 1u); }
-        WState st{W, 0, (int)k, 0, 0u};
+        WState st{sm.W, 0, (int)k, 0, 0u};
         for (uint32_t base = 0; base < nc; base += 64) {
             const int na = nc - base < 64u ? (int)(nc - base) : 64;
-            if (lane < na) act_pid[lane] = cand[(size_t)qi * cap + base + lane];
-            wave_sync();
-            dist_rounds<NB, RS, TAIL>(ix, q, act_pid, act_dist, na);
-            wave_sync();
-            uint64_t key = kMaxKey;
-            if (lane < na) key = ((uint64_t)act_dist[lane] << 32) | act_pid[lane];
-            const uint64_t t = st.plen >= st.ef ? (st.W[st.ef - 1] & kKeyMask) : kMaxKey + 1ull;
-            uint64_t pm = __ballot(lane < na && key < t);
-            while (pm) {
-                const int i = __builtin_ctzll(pm);
-                pm &= pm - 1ull;
-                const uint64_t kk = bcast_u64(key, i);
-                const int idx = w_rank(st, kk);
-                if (idx < st.ef) w_insert(st, idx, kk);
-            }
-            if (st.plen > st.ef) st.plen = st.ef;
-            wave_sync();
+            if (lane < na) sm.act_pid[lane] = cand[(size_t)qi * cap + base + lane];
+            scan_rank_batch<NB, RS, TAIL>(ix, sm, st, na);
         }
-        for (uint32_t i = lane; i < k; i += 64) {
-            uint32_t pid = kInvalid;
-            float d = __uint_as_float(0x7f800000u);
-            if ((int)i < st.plen) {
-                pid = (uint32_t)st.W[i];
-                d = __uint_as_float((uint32_t)((st.W[i] & kKeyMask) >> 32));
-            }
-            out_pid[(size_t)qi * k + i] = pid;
-            out_dist[(size_t)qi * k + i] = d;
-        }
+        topk_emit_row(st, k, out_pid + (size_t)qi * k, out_dist + (size_t)qi * k);
     }
 }
 

@@ -13,9 +13,10 @@
 //   range_chunk_sums_kernel  \ an exclusive u64 prefix sum over u32 counts in two levels: the sum of every chunk of 64 items, then
 //   range_offsets_kernel     / per chunk the chunk sums in front of it are counted (allowed_pending_kernel's scheme: no look-back).
 //   range_copy_kernel        the prefixes closed in this step as keys dist_bits << 32 | pid at their offsets in the result buffer.
-//   range_scan_kernel        the exact step: grid = pending queries x S contiguous segments of [0, n), dist_rounds on 64 consecutive
-//                            ids at a time.  Run twice: the first run stores the number of hits per (query, segment), the second
-//                            writes the keys at the offsets the prefix sum gave, ascending id within a segment.  No top-k.
+//   range_scan_kernel        the exact step: grid = pending queries x S contiguous segments of [0, n) (scan_segment, stage_query: the
+//                            exact scans' shared steps, idist_device.hpp), dist_rounds on 64 consecutive ids at a time.  Run twice:
+//                            the first run stores the number of hits per (query, segment), the second writes the keys at the offsets
+//                            the prefix sum gave, ascending id within a segment.  No top-k.
 //   range_close_kernel       the exact queries closed: count, offset, rung EXACT.
 //   range_sort_kernel        every exact query's keys ascending, in place: a bitonic network of ASCENDING comparators only (a merge
 //                            level = one "flip" i <-> k - 1 - i, then half-cleaners i <-> i + j), so a comparator whose upper end lies
@@ -190,17 +191,12 @@ __global__ __launch_bounds__(64) void range_scan_kernel(IndexView ix, const floa
     const Smem sm = carve(smem_raw, ix.stride, 0, false);
     const int lane = lane_id();
     const uint64_t below = (1ull << lane) - 1ull;
-    const uint32_t nb = NB >= 0 ? (uint32_t)NB : ix.nb;
     const uint64_t items = (uint64_t)np * S;
     for (uint64_t w = blockIdx.x; w < items; w += gridDim.x) {
-        const uint32_t p = (uint32_t)(w / S), s = (uint32_t)(w % S);
-        const uint32_t lo = (uint32_t)((uint64_t)ix.n * s / S), hi = (uint32_t)((uint64_t)ix.n * (s + 1u) / S);
+        uint32_t p, lo, hi;
+        scan_segment(ix.n, S, w, &p, &lo, &hi);
         const uint32_t q = list ? list[p] : p;
-        wave_sync();
-        for (uint32_t o = lane; o < ix.stride; o += 64) sm.q[o] = 0.0f;
-        wave_sync();
-        for (uint32_t e = lane; e < ix.dim; e += 64) sm.q[blocked_pos(e, nb)] = queries[(size_t)p * ix.dim + e];
-        wave_sync();
+        stage_query<NB>(ix, sm.q, queries + (size_t)p * ix.dim);
         const uint64_t dst = keys ? seg_off[w] : 0ull;
         uint32_t taken = 0;
         for (uint32_t base = lo; base < hi; base += 64u) {
