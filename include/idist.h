@@ -150,7 +150,13 @@ typedef struct idist_index_info {
     uint32_t layer_len[IDIST_MAX_LAYERS]; /* layer_len[l-1] = rows of layers[l-1], l = 1..n_upper */
     uint32_t tie_capacity;      /* the tie region the build ended up using (see idist_config.tie_capacity) */
     float dot_bound;            /* IDIST_METRIC_DOT: the bound S in use (given or derived); 0 for every other metric */
+    int32_t filter_format;      /* the reject filter's compact rows a wide search of this index reads:
+                                   IDIST_FILTER_FORMAT_NONE / _IDENTITY (one byte per stored float) / _PRINCIPAL (64-byte rows in a
+                                   principal basis: thin search walks of low-rank data).  One deterministic choice per index. */
+    uint64_t filter_bytes;           /* device memory of the identity table (0: this index runs unfiltered) ... */
+    uint64_t filter_principal_bytes; /* ... and of the principal one, 64 B per row on top (0: not made, or dropped by the policy) */
 } idist_index_info;
+enum { IDIST_FILTER_FORMAT_NONE = 0, IDIST_FILTER_FORMAT_IDENTITY = 1, IDIST_FILTER_FORMAT_PRINCIPAL = 2 };
 
 /* Raw device views (for RCCL replication by the host: torch.distributed / ncclBroadcast). */
 typedef struct idist_device_buffers {
@@ -289,6 +295,10 @@ idist_status idist_search_ctx_tie_overflowed(idist_search_ctx* ctx, int32_t* out
  * candidates the filter examined and how many f32 rows it spared, summed over the searches of this context since the last
  * reset (bench.py derives the bytes a launch really requests from them).  Synchronise the context's stream first. */
 idist_status idist_search_ctx_filter_counts(idist_search_ctx* ctx, uint64_t* examined, uint64_t* rejected, int32_t reset);
+/* ... and the part of both that the walks read from the 64-byte principal rows (idist_index_info.filter_format): a query whose energy
+ * lies mostly outside the index's basis is served from the identity rows inside the same launch, so what a launch requested is
+ * principal_examined * 64 + (examined - principal_examined) * identity row bytes + (pushes - rejected) * 4 * dim.  Own reset. */
+idist_status idist_search_ctx_filter_principal_counts(idist_search_ctx* ctx, uint64_t* examined, uint64_t* rejected, int32_t reset);
 /* HIP-event duration of the last search kernel launched through ctx, milliseconds. */
 idist_status idist_search_ctx_last_kernel_ms(idist_search_ctx* ctx, float* ms);
 /* Durations (ms) of the most recent search-kernel launches through ctx, oldest first, measured

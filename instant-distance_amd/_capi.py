@@ -61,7 +61,13 @@ class IndexInfo(C.Structure):
         ("layer_len", C.c_uint32 * MAX_LAYERS),
         ("tie_capacity", C.c_uint32),
         ("dot_bound", C.c_float),
+        ("filter_format", C.c_int32),            # FILTER_FORMAT_NONE / _IDENTITY / _PRINCIPAL
+        ("filter_bytes", C.c_uint64),
+        ("filter_principal_bytes", C.c_uint64),
     ]
+
+
+FILTER_FORMAT_NONE, FILTER_FORMAT_IDENTITY, FILTER_FORMAT_PRINCIPAL = 0, 1, 2
 
 
 class DeviceBuffers(C.Structure):
@@ -124,6 +130,7 @@ SYMBOLS = {
     "idist_search_ctx_status": (C.c_int32, [_vp]),
     "idist_search_ctx_tie_overflowed": (C.c_int32, [_vp, C.POINTER(C.c_int32)]),
     "idist_search_ctx_filter_counts": (C.c_int32, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int32]),
+    "idist_search_ctx_filter_principal_counts": (C.c_int32, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int32]),
     "idist_search_ctx_last_kernel_ms": (C.c_int32, [_vp, C.POINTER(C.c_float)]),
     "idist_search_ctx_kernel_times": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p]),
     "idist_replicate": (C.c_int32, [_vp, C.POINTER(C.c_int32), C.c_uint32, C.POINTER(_vp)]),

@@ -293,6 +293,15 @@ class Search:
         _lib().check(_lib().idist_search_ctx_filter_counts(self._ctx, C.byref(a), C.byref(b), 1 if reset else 0))
         return int(a.value), int(b.value)
 
+    def filter_principal_counts(self, reset: bool = True) -> tuple[int, int]:
+        """The part of `filter_counts()` that was read from the 64-byte principal rows (`Hnsw.info().filter_format`): queries the
+        index's basis does not fit are served from the identity rows in the same launch.  Its own reset.  Synchronise first."""
+        if self._ctx is None:
+            return 0, 0
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        _lib().check(_lib().idist_search_ctx_filter_principal_counts(self._ctx, C.byref(a), C.byref(b), 1 if reset else 0))
+        return int(a.value), int(b.value)
+
     def check_status(self):
         """Raise if a device-side guard tripped during the launches so far (after a stream sync)."""
         _lib().check(_lib().idist_search_ctx_status(self._ctx))

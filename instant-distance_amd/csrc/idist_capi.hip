@@ -10,6 +10,7 @@
 #include "idist_dot.hpp"
 #include "idist_allowed.hpp"
 #include "idist_range.hpp"
+#include "idist_basis.hpp"
 
 #ifndef IDIST_EMU
 #include <hip/hip_runtime.h>
@@ -265,6 +266,13 @@ struct idist_index {
     mutable std::mutex filt_mu;
     mutable std::atomic<int> filt_state{0};    // 0 not made yet, 1 ready, 2 not available (no memory: the walks run without it)
     mutable idist::FilterView filt{};
+    // ... and its second table, the 64-byte rows in a principal basis (filter_ensure: eligibility, basis, policy).  filt_format says
+    // which of the two a thin wide search reads — one deterministic choice per index; everything else reads `filt`.
+    mutable idist::FilterView filt_p{};        // rows == nullptr: this index has no principal table
+    mutable std::atomic<int> filt_format{IDIST_FILTER_FORMAT_NONE};   // stored ONCE, when filt_p_state goes to 1 (readers: after that)
+    mutable bool filt_p_turned_down = false;   // the policy chose the identity rows and no knob asked to keep the other table
+    mutable std::atomic<int> filt_p_state{0};  // 0: basis, policy and principal table still to come (a build makes the identity table only:
+                                               // the basis is 0.1 s of host time, which belongs to the first wide search, not to the build), 1: done
 
     IndexView view() const {
         IndexView v;
@@ -292,6 +300,7 @@ struct idist_progress {
 
 // Knobs read from the environment (see test_env above: three in the product, the rest in the test / measurement builds),
 // sampled once per context or build — not per launch.
+inline int filter_basis_knob(const char* e) { return e[0] == 'p' ? IDIST_FILTER_FORMAT_PRINCIPAL : (e[0] == 'i' ? IDIST_FILTER_FORMAT_IDENTITY : 0); }
 struct Knobs {
     uint32_t latency_nq = 1024;   // IDIST_LATENCY_NQ: batches up to this many queries run the latency walk (0 = never)
     bool classic = false;         // IDIST_WALK=classic
@@ -305,6 +314,9 @@ struct Knobs {
     bool tie_spill_first = false; // IDIST_TIE_SPILL=1: strict ties go to the HBM bags at the first overflow instead of growing the LDS region first (test knob)
     bool events = true;           // IDIST_KERNEL_EVENTS=0: no HIP events around the search kernels (idist_search_ctx_kernel_times then has nothing)
     bool filter = true;           // IDIST_FILTER=0: wide on-chip walks without the reject filter (test / A-B knob)
+    uint32_t filter_waves = 0;    // IDIST_FILTER_WAVES=2|3: thin waves per SIMD of a walk on the principal rows (A/B knob; 0: kFilterWavesPrincipal)
+    int basis = 0;                // IDIST_FILTER_BASIS=identity|principal: the compact rows thin wide searches read, whatever the index's
+                                  // policy chose (principal: where the index is eligible for that table) (test / A-B knob)
     bool tab_ids = false;         // IDIST_TAB_FORMAT=ids: the on-chip set always keeps full ids (4 per bucket, frozen at 7/8), never
                                   // 16-bit quotients (8 per bucket, single ids overflow) (test / A-B knob)
     bool tab_q16 = false;         // IDIST_TAB_FORMAT=q16: quotients wherever they apply, also where the policy would keep ids
@@ -334,6 +346,8 @@ struct Knobs {
         if (const char* e = test_env("IDIST_WALK")) k.classic = e[0] == 'c';      // (honoured by the test build only, see variants_check)
         if (const char* e = test_env("IDIST_BLOOM")) k.bloom = e[0] != '0';
         if (const char* e = test_env("IDIST_FILTER")) k.filter = e[0] != '0';
+        if (const char* e = test_env("IDIST_FILTER_BASIS")) k.basis = filter_basis_knob(e);
+        if (const char* e = test_env("IDIST_FILTER_WAVES")) k.filter_waves = atoi(e) == 3 ? 3u : 2u;
         if (const char* e = test_env("IDIST_VISITED")) { k.vis_bitmap = e[0] == 'b'; k.vis_onchip = e[0] == 'o'; }
         if (const char* e = test_env("IDIST_NO_ZERO_COPY")) k.no_zero_copy = e[0] != '0';
         if (const char* e = test_env("IDIST_TAB_FORMAT")) { k.tab_ids = e[0] == 'i'; k.tab_q16 = e[0] == 'q'; }
@@ -496,8 +510,8 @@ inline bool has_template_geometry(const Layout& L) {
 
 // Which filtered kernels a row geometry can ever be given (launch_search / run_build): instantiating only those keeps the build of
 // this translation unit at three minutes.  The thin filtered walk serves compact rows of up to five chunks (128-d, 300-d, runtime
-// geometries), one fat filtered wave per SIMD the longer ones (768-d, runtime geometries); fat filtered DESCENTS exist for runtime
-// geometries only.  A launch the policy asks for and the geometry has no kernel for is an internal error, never a silent no-op.
+// geometries) — on the identity rows, and a second instantiation on the 64-byte principal rows (walk_thin_filter_principal) — one fat
+// filtered wave per SIMD the longer ones (768-d, runtime geometries); descents are filtered on thin waves only.  A launch the policy asks for and the geometry has no kernel for is an internal error, never a silent no-op.
 template <int NB> struct GeoKernels {
     static constexpr bool thin_search = NB != 24;
     static constexpr bool fat_filtered_search = NB == 24 || NB < 0;
@@ -509,6 +523,12 @@ template <int NB> struct GeoKernels {
     static constexpr bool thin_descent = NB != 4;
 #endif
 };
+// (the third wave per SIMD of a principal walk is an A/B: instantiated where the knob exists, or where it is the default)
+#if defined(IDIST_VARIANTS) || defined(IDIST_EMU) || defined(IDIST_PROBE)
+constexpr bool kPrincipalWaves3 = true;
+#else
+constexpr bool kPrincipalWaves3 = false;
+#endif
 template <int NB, int RS, int TAIL, int WALK, bool ON> struct SearchLaunch {
     static bool go(uint32_t grid, size_t smem, hipStream_t stream, const IndexView& view, const SearchArgs& a) {
         auto kS = search_kernel<NB, RS, TAIL, WALK>;
@@ -518,6 +538,16 @@ template <int NB, int RS, int TAIL, int WALK, bool ON> struct SearchLaunch {
 };
 template <int NB, int RS, int TAIL, int WALK> struct SearchLaunch<NB, RS, TAIL, WALK, false> {
     static bool go(uint32_t, size_t, hipStream_t, const IndexView&, const SearchArgs&) { return false; }
+};
+template <int NB, int RS, int TAIL, bool ON> struct BoundLaunch {       // filter_bound_kernel on the principal rows
+    static bool go(uint32_t grid, size_t smem, const IndexView& view, const float* q, uint32_t nq, const uint32_t* ids, uint32_t n_ids, float* out) {
+        auto kD = filter_bound_kernel<NB, RS, TAIL, true>;
+        IDIST_LAUNCH(kD, grid, 64, smem, (hipStream_t) nullptr, view, q, nq, ids, n_ids, out);
+        return true;
+    }
+};
+template <int NB, int RS, int TAIL> struct BoundLaunch<NB, RS, TAIL, false> {
+    static bool go(uint32_t, size_t, const IndexView&, const float*, uint32_t, const uint32_t*, uint32_t, float*) { return false; }
 };
 template <int NB, int RS, int TAIL, int WALK, bool ON> struct DescentLaunch {
     static bool go(uint32_t grid, size_t smem, hipStream_t stream, const IndexView& view, const BuildArgs& a) {
@@ -786,7 +816,7 @@ idist_status device_status_to_code(uint32_t st, int32_t tie_policy) {
 
 // ---- build driver: the per-layer insertion schedule of Hnsw::new, core/lib.rs:304-329 ----
 bool filter_applies(const idist_index* ix);
-idist_status filter_ensure(const idist_index* ix);
+idist_status filter_ensure(const idist_index* ix, bool with_principal = true);
 
 idist_status run_build(idist_index* ix, idist_progress* prog, bool tie_spill) {
     const uint32_t n = ix->n;
@@ -1040,7 +1070,7 @@ idist_status run_build(idist_index* ix, idist_progress* prog, bool tie_spill) {
                         (has_template_geometry(ix->L) || filt_stride(ix->L.stride) <= 128u * (uint32_t)kFiltRtChunks) &&   // (the thin tile)
                         (bf_env ? bf_env[0] != '0' : ix->L.stride >= 192u);
     if (build_filter) {
-        CHK(filter_ensure(ix));
+        CHK(filter_ensure(ix, false));      // (the descents read the identity table; basis and policy wait for the first wide search)
         build_filter = ix->filt_state.load(std::memory_order_acquire) == 1;
     }
     // (fat filtered descents for runtime-geometry rows beyond the thin tile: 500k x 1024 / 1536-d 2.04 / 2.78 against 2.10 / 3.13 s —
@@ -1425,6 +1455,14 @@ constexpr size_t kShortRowBitmapBytes = (size_t)320 << 20;
 // ... and long rows by the on-chip walk from this size on (below it nothing was measured: the round-2 rule stands)
 constexpr size_t kLongRowOnChipBytes = (size_t)96 << 20;
 constexpr uint32_t kFilterWaves = 2u;    // waves per SIMD of a filtered wide walk (launch_search)
+constexpr uint32_t kFilterWavesPrincipal = 2u;   // ... on the principal rows (three: measured)
+// a forced format that cannot be served is an error, never a quiet run on the other table
+idist_status filter_basis_forced_check(const idist_index* ix, int knob) {
+    if (knob == IDIST_FILTER_FORMAT_PRINCIPAL && ix->filt_state.load(std::memory_order_acquire) == 1 && ix->filt_p_turned_down)
+        return fail(IDIST_ERR_INVALID_ARG, "the principal format was asked for by name, but this index's policy turned that table down and freed it before "
+                                           "the knob was set (set it before the index's first wide search)");
+    return IDIST_OK;
+}
 constexpr uint32_t kLongWalkEf = 512u;   // ef_search from which wide on-chip batches run two thinner waves per SIMD (see launch_search)
 
 // Long walks and where the visited bitmaps land (round 5, measured, nothing kept): ef_search 800 at 1M points test-and-sets the HBM
@@ -1438,8 +1476,8 @@ constexpr uint32_t kLongWalkEf = 512u;   // ef_search from which wide on-chip ba
 // kept.  Gathering the rows with the non-temporal hint (leaving the cache to the bitmaps) costs 11-15 % at every ef_search and 30 % of
 // the build (`make nt`, profiles/r05/probe_r05e_rows_nontemporal_ab_c3.jsonl): the row gathers live on Infinity-Cache hits too.
 // The compact copy of the rows behind the walk's reject filter (FilterView): made once per index, here.  The lattice [lo, lo + 255
-// step] comes from a sample of up to 2048 rows: mean +- 5 sigma of the central 98 % of the sampled coordinates (sigma rescaled to
-// the whole of a Gaussian), clipped to the sample's range + a quarter sigma.  Its choice decides how many candidates the filter can
+// step] comes from a sample of up to 2048 rows (filter_robust_range): mean and sigma are those of the central 98 % of the sampled
+// coordinates (sigma rescaled to the whole of a Gaussian), the range is mean +- 5 sigma clipped to the sample's range + a quarter sigma.  Its choice decides how many candidates the filter can
 // reject, never a result — a coordinate outside it is clamped and its error is part of the row's recorded |p - p^|.  Runs on the
 // null stream and waits for it (an index is immutable once it is searched; its rows are in place).
 // Geometries the search kernels have no filter tile for (no compile-time instantiation and a compact row beyond the fat tile's
@@ -1463,31 +1501,10 @@ constexpr uint32_t kLongWalkEf = 512u;   // ef_search from which wide on-chip ba
 // and 2^76 (7.6e22), wherever the data sits — and such data is ordinary: at the lower end typical squared distances are dim 1e-26,
 // at the upper end they overflow.  Outside it every walk is the unfiltered one (tests/test_data_scale.py runs both sides).
 constexpr float kFilterMinStep256 = 0x1p-58f, kFilterMaxStep256 = 0x1p60f;
-bool filter_applies(const idist_index* ix) {
-    return ix->n > 0 && (has_template_geometry(ix->L) || filt_stride(ix->L.stride) <= 128u * (uint32_t)kFiltRtChunksFat);
-}
-idist_status filter_ensure(const idist_index* ix) {
-    if (ix->filt_state.load(std::memory_order_acquire) != 0) return IDIST_OK;
-    std::lock_guard<std::mutex> lk(ix->filt_mu);
-    if (ix->filt_state.load(std::memory_order_acquire) != 0) return IDIST_OK;
-    if (!filter_applies(ix)) { ix->filt_state.store(2, std::memory_order_release); return IDIST_OK; }
-    HIPCHK(hipSetDevice(ix->device));
-    const uint32_t stride = ix->L.stride, fs = filt_stride(stride);
-    // sample: up to 2048 rows, evenly spaced
-    const uint32_t ns = std::min<uint32_t>(ix->n, 2048u), every = ix->n / ns;
-    std::vector<float> smp((size_t)ns * stride);
-    HIPCHK(hipMemcpy2D(smp.data(), (size_t)stride * 4, ix->d_points, (size_t)every * stride * 4, (size_t)stride * 4, ns, hipMemcpyDeviceToHost));
-    // robust range: mean and sigma of the central 98 % of the sampled coordinates (a few wild values — or heavy tails — must not
-    // stretch the lattice: they are clamped, and only their own rows pay for it), sigma rescaled to the whole of a Gaussian
-    std::vector<float> vals;
-    vals.reserve((size_t)ns * ix->kdim);
-    for (uint32_t r = 0; r < ns; r++)
-        for (uint32_t pos = 0; pos < stride; pos++) {
-            if (natural_pos(pos, ix->L.nb) >= ix->kdim) continue;
-            const float v = smp[(size_t)r * stride + pos];
-            if (std::fabs(v) <= 3.0e38f) vals.push_back(v);
-        }
-    double lo = 0.0, hi = 1.0;
+// the robust range of filter_ensure (reorders `vals`)
+void filter_robust_range(std::vector<float>& vals, double& lo, double& hi) {
+    lo = 0.0;
+    hi = 1.0;
     if (!vals.empty()) {
         const size_t cnt = vals.size(), k0 = cnt / 100, k1 = cnt - 1 - cnt / 100;
         std::nth_element(vals.begin(), vals.begin() + k0, vals.end());
@@ -1506,6 +1523,247 @@ idist_status filter_ensure(const idist_index* ix) {
         hi = std::min(mx + 0.25 * sd, mean + 5.0 * sd);
     }
     if (!(hi > lo) || !((hi - lo) / 65280.0 > 1e-30)) hi = lo + 1.0;      // degenerate data: any lattice is as good
+}
+
+// ---- the principal format: a second compact table, 64 bytes per row (FilterView::basis) ----
+// For data whose variance sits in a few dozen directions, 56 coordinates y = B (p - mu) in a principal basis prove "this candidate is
+// farther than nearest[ef-1]" almost as often as all the coordinates in the natural basis do — at one 64-B fabric request per examined
+// candidate instead of three (320 B at 300-d).  The bound is the identity format's chain with one more line in front:
+//     |q - p| s  >=  |B (q - p)|  =  |B (q - mu) - B (p - mu)|  >=  |q^' - p^'| - E_q - E_p
+//   * B is the f32 matrix as stored; s >= sigma_max(B) is computed from those very values in f64 (principal_basis), so the first
+//     step needs nothing of B but what was measured.  mu cancels exactly: both sides subtract the same f32 values.
+//   * q^', p^' are lattice points lo + step256 Q (Q = 256 u for a row) of the y the kernels EVALUATE (filter_project: f64, one fma
+//     per stored position); E_q, E_p = |fl(y) - y^| + the evaluation error of y, at most sqrt(56) (stride + 2) 2^-53 s |x - mu|
+//     (`slack`, with a per cent to spare) + that of the subtraction itself (filter_principal_error).  All in f64, rounded up to f32.
+//   * from there on it is filter_rounds' test unchanged, dh = (float)I dscale > ((st + E) up)^2, with `up` = the identity format's
+//     (the float steps of the test and the canonical chain of the f32 row, which the bound still speaks about) times s.
+// The lattice's range is the robust range of the LEADING component of the sample — taken over all 56 it would clamp the components
+// that carry the distance.  The same step range applies; outside it, or if anything here fails, the index simply has no principal table.
+//
+// Policy: one deterministic choice per index, from the sample alone (a pure function of the rows: replicas and re-imports agree).
+// For each format the bytes an examined candidate costs are predicted as row_bytes + (1 - share) 4 dim: 64 sample rows act as
+// queries, the threshold is the distance of their 32nd nearest sample row, the candidates are the sample rows beyond it, and `share`
+// is what that format's bound (the formula above, f64 on the host) rejects.  The format with fewer predicted bytes is in force
+// (the principal one only while it leaves at most twice the identity rows' survivors: see `take` below);
+// a principal table the policy turns down is freed again.  Beneath it the per-walk switch-off of dist_pass_filtered stays.
+bool filter_principal_eligible(const idist_index* ix) {
+    // thin search walks only (compact identity row within the thin tile's five chunks), rows of at least 128 coordinates; DOT's
+    // extra coordinate is left alone
+    return ix->n > 0 && !is_dot(ix->cfg) && ix->kdim >= 128u && filt_stride(ix->L.stride) <= 128u * (uint32_t)kFiltRtChunks &&
+           (GeoKernels<-1>::thin_search || has_template_geometry(ix->L));
+}
+// share of (query, candidate) sample pairs a format's bound rejects.  v: [ns][c] the rows in the format's coordinates (identity: the
+// coordinates themselves; principal: y), ex [ns]: what a row's E carries beside its lattice error, st [nq]: the thresholds (L2),
+// far [nq][*]: the candidates of query row qrow[i]
+double filter_policy_share(const std::vector<double>& v, uint32_t ns, uint32_t c, const FilterView& f, const std::vector<double>& ex_row,
+                           const std::vector<double>& ex_query, const std::vector<uint32_t>& qrow, const std::vector<double>& st,
+                           const std::vector<std::vector<uint32_t>>& far) {
+    const double lo = f.lo, s256 = f.step256, step = 256.0 * s256;
+    std::vector<int32_t> code((size_t)ns * c);
+    std::vector<double> ep(ns);
+    for (uint32_t r = 0; r < ns; r++) {
+        double e2 = 0.0;
+        for (uint32_t k = 0; k < c; k++) {
+            const double x = v[(size_t)r * c + k];
+            const double u = std::nearbyint(std::min(std::max((x - lo) / step, 0.0), 255.0));
+            const double e = x - (lo + u * step);
+            e2 += e * e;
+            code[(size_t)r * c + k] = (int32_t)u * 256;
+        }
+        ep[r] = std::sqrt(e2) + ex_row[r];
+    }
+    uint64_t pairs = 0, rejected = 0;
+    std::vector<int32_t> Q(c);
+    for (size_t i = 0; i < qrow.size(); i++) {
+        const uint32_t r = qrow[i];
+        double e2 = 0.0;
+        for (uint32_t k = 0; k < c; k++) {
+            const double x = v[(size_t)r * c + k];
+            const double q = std::nearbyint(std::min(std::max((x - lo) / s256, 0.0), 65535.0));
+            const double e = x - (lo + q * s256);
+            e2 += e * e;
+            Q[k] = (int32_t)q;
+        }
+        const double eq = std::max(std::sqrt(e2) + ex_query[r], f.basis ? 16.0 * s256 : 0.0);
+        for (const uint32_t p : far[i]) {
+            double I = 0.0;
+            const int32_t* cp = &code[(size_t)p * c];
+            for (uint32_t k = 0; k < c; k++) { const double d = (double)(Q[k] - cp[k]); I += d * d; }
+            const double t = (st[i] + eq + ep[p]) * (double)f.up;
+            pairs++;
+            if (I * s256 * s256 > t * t) rejected++;
+        }
+    }
+    return pairs ? (double)rejected / (double)pairs : 0.0;
+}
+// smp: the sample of filter_ensure, [ns][stride] blocked rows; ident: the identity table's view (made).  Leaves ix->filt_p and
+// ix->filt_format set; nothing it fails at is an error of the index.
+idist_status filter_principal_ensure(const idist_index* ix, const std::vector<float>& smp, uint32_t ns, const FilterView& ident) {
+    ix->filt_format.store(IDIST_FILTER_FORMAT_IDENTITY, std::memory_order_relaxed);     // (published by the caller's store to filt_p_state)
+    if (!filter_principal_eligible(ix)) return IDIST_OK;
+    constexpr int m = idist::kBasisM;
+    const uint32_t stride = ix->L.stride, d = ix->kdim, nb = ix->L.nb;
+    std::vector<float> xs((size_t)ns * d);
+    for (uint32_t r = 0; r < ns; r++)
+        for (uint32_t e = 0; e < d; e++) xs[(size_t)r * d + e] = smp[(size_t)r * stride + blocked_pos(e, nb)];
+    const idist::PrincipalBasis pb = idist::principal_basis(xs.data(), ns, d, d);
+    // the sample in the basis (f64), and |x - mu|; rows with a non-finite coordinate take no part in range or policy
+    std::vector<double> y((size_t)ns * m), xn(ns);
+    std::vector<uint8_t> finite(ns, 1);
+    std::vector<float> lead;
+    std::vector<double> rho;             // share of |x - mu|^2 a finite row leaves outside the basis
+    for (uint32_t r = 0; r < ns; r++) {
+        double d2 = 0.0;
+        for (uint32_t e = 0; e < d; e++) {
+            if (!(std::fabs(xs[(size_t)r * d + e]) <= 3.0e38f)) finite[r] = 0;
+            const double c = (double)xs[(size_t)r * d + e] - (double)pb.mu[e];
+            d2 += c * c;
+        }
+        xn[r] = std::sqrt(d2);
+        if (!finite[r]) continue;
+        double y2 = 0.0;
+        for (int i = 0; i < m; i++) {
+            double acc = 0.0;
+            for (uint32_t e = 0; e < d; e++) acc += (double)pb.B[(size_t)i * d + e] * ((double)xs[(size_t)r * d + e] - (double)pb.mu[e]);
+            y[(size_t)r * m + i] = acc;
+            y2 += acc * acc;
+        }
+        if (d2 > 0.0) rho.push_back(std::min(1.0, std::max(0.0, 1.0 - y2 / d2)));
+        const double y0 = y[(size_t)r * m];
+        if (std::fabs(y0) <= 3.0e38) lead.push_back((float)y0);
+    }
+    double lo = 0.0, hi = 1.0;
+    filter_robust_range(lead, lo, hi);
+    FilterView f{};
+    f.fstride = 64u;
+    f.lo = (float)lo;
+    f.step256 = (float)((hi - lo) / 65280.0);
+    if (!(f.step256 >= kFilterMinStep256 && f.step256 <= kFilterMaxStep256) || !(std::fabs(f.lo) <= 3.0e38f)) return IDIST_OK;
+    f.qscale = 1.0f / f.step256;
+    f.dscale = f.step256 * f.step256;
+    f.up = std::nextafter((float)((double)ident.up * pb.s * (1.0 + 1e-6)), 2.0f * ident.up * (float)pb.s);
+    // queries take the principal rows while they leave at most twice the rows' 99th percentile outside the basis (+ 0.1 %)
+    double rho99 = 0.0;
+    if (!rho.empty()) {
+        std::sort(rho.begin(), rho.end());
+        rho99 = rho[std::min(rho.size() - 1, rho.size() * 99 / 100)];
+    }
+    f.rho_max = (float)std::min(1.0, 2.0 * rho99 + 1e-3);
+    f.slack = std::nextafter((float)(std::sqrt((double)m) * (double)(stride + 2u) * 0x1p-53 * pb.s * 1.01), 1.0f);
+
+    // policy first (host only): a table the policy turns down is never made — unless a test asks for either format by name
+    std::vector<uint32_t> rows_ok;
+    for (uint32_t r = 0; r < ns; r++)
+        if (finite[r]) rows_ok.push_back(r);
+    std::vector<uint32_t> qrow;
+    std::vector<double> st;
+    std::vector<std::vector<uint32_t>> far;
+    const uint32_t nq = std::min<uint32_t>(64u, (uint32_t)rows_ok.size());
+    for (uint32_t i = 0; i < nq; i++) {
+        const uint32_t r = rows_ok[(size_t)i * rows_ok.size() / nq];
+        std::vector<std::pair<double, uint32_t>> dist;
+        dist.reserve(rows_ok.size());
+        for (const uint32_t p : rows_ok) {
+            if (p == r) continue;
+            double d2 = 0.0;
+            for (uint32_t e = 0; e < d; e++) { const double c = (double)xs[(size_t)r * d + e] - (double)xs[(size_t)p * d + e]; d2 += c * c; }
+            dist.emplace_back(d2, p);
+        }
+        if (dist.size() <= 32u) continue;
+        std::sort(dist.begin(), dist.end());
+        qrow.push_back(r);
+        st.push_back(std::sqrt(dist[31].first));
+        far.emplace_back();
+        for (size_t k = 32; k < dist.size(); k++) far.back().push_back(dist[k].second);
+    }
+    std::vector<double> xi((size_t)ns * d, 0.0), zero(ns, 0.0), ex_qi(ns, 0.0), ex_p(ns, 0.0);
+    for (uint32_t r = 0; r < ns; r++) {
+        if (!finite[r]) continue;
+        double mx = 0.0;
+        for (uint32_t e = 0; e < d; e++) { xi[(size_t)r * d + e] = xs[(size_t)r * d + e]; mx = std::max(mx, std::fabs((double)xs[(size_t)r * d + e])); }
+        ex_qi[r] = (double)ident.slack * (mx + std::fabs((double)ident.lo) + 65536.0 * (double)ident.step256);
+        ex_p[r] = (double)f.slack * xn[r];
+    }
+    FilterView fpol = f;
+    fpol.basis = ix->d_points;      // (any non-null value: filter_policy_share only asks whether the view is the principal one)
+    const double share_i = filter_policy_share(xi, ns, d, ident, zero, ex_qi, qrow, st, far);
+    const double share_p = filter_policy_share(y, ns, (uint32_t)m, fpol, ex_p, ex_p, qrow, st, far);
+    const double bytes_i = (double)ident.fstride + (1.0 - share_i) * 4.0 * (double)d;
+    const double bytes_p = 64.0 + (1.0 - share_p) * 4.0 * (double)d;
+    // ... and no more than twice the identity rows' survivors (+ 1 %): a survivor costs the walk a dependent round trip for its f32 row,
+    // which bytes under-price on a walk bound by round trips — by bytes alone 1M x 300 rows with a 64-d latent or a 1/k^2 spectrum take
+    // the principal rows (0.85 / 0.61 rejected against 0.92 / 0.90) and search 5 % / 25 % slower than on the identity rows
+    const bool take = bytes_p < bytes_i && (1.0 - share_p) <= 2.0 * (1.0 - share_i) + 0.01;
+    if (!take && !test_env("IDIST_FILTER_BASIS")) { ix->filt_p_turned_down = true; return IDIST_OK; }
+
+    // the table: B^T and mu in the rows' stored order, then one wave per row
+    std::vector<float> bt((size_t)stride * 64u, 0.0f), mu(stride, 0.0f);
+    for (uint32_t e = 0; e < d; e++) {
+        const uint32_t pos = blocked_pos(e, nb);
+        mu[pos] = pb.mu[e];
+        for (int i = 0; i < m; i++) bt[(size_t)pos * 64u + (uint32_t)i] = pb.B[(size_t)i * d + e];
+    }
+    float *d_bt = nullptr, *d_mu = nullptr;
+    uint8_t* rows = nullptr;
+    auto drop = [&]() { (void)hipGetLastError(); hipFree(d_bt); hipFree(d_mu); hipFree(rows); };
+    if (hipMalloc((void**)&d_bt, bt.size() * 4) != hipSuccess || hipMalloc((void**)&d_mu, mu.size() * 4) != hipSuccess ||
+        hipMalloc((void**)&rows, (size_t)ix->n * 64u) != hipSuccess ||
+        hipMemcpy(d_bt, bt.data(), bt.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_mu, mu.data(), mu.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        drop();
+        return IDIST_OK;                                                  // no memory: the identity table serves
+    }
+    f.basis = d_bt;
+    f.mu = d_mu;
+    IndexView view = ix->view();
+    view.f = f;
+    const uint32_t grid = std::min<uint32_t>(ix->n, (uint32_t)ix->n_cu * 32u);
+    IDIST_LAUNCH(filter_rows_principal_kernel, grid, 64, 0, nullptr, view, rows);
+    if (hipDeviceSynchronize() != hipSuccess) {
+        const hipError_t e = hipGetLastError();
+        drop();
+        return fail(IDIST_ERR_HIP, "filter_rows_principal_kernel failed: %s", hipGetErrorString(e));
+    }
+    f.rows = rows;
+    ix->filt_p = f;
+    if (take) ix->filt_format.store(IDIST_FILTER_FORMAT_PRINCIPAL, std::memory_order_relaxed);
+    return IDIST_OK;
+}
+bool filter_applies(const idist_index* ix) {
+    return ix->n > 0 && (has_template_geometry(ix->L) || filt_stride(ix->L.stride) <= 128u * (uint32_t)kFiltRtChunksFat);
+}
+idist_status filter_ensure(const idist_index* ix, bool with_principal) {
+    auto settled = [&]() {
+        const int st = ix->filt_state.load(std::memory_order_acquire);
+        return st == 2 || (st == 1 && (!with_principal || ix->filt_p_state.load(std::memory_order_acquire) == 1));
+    };
+    if (settled()) return IDIST_OK;
+    std::lock_guard<std::mutex> lk(ix->filt_mu);
+    if (settled()) return IDIST_OK;
+    if (!filter_applies(ix)) { ix->filt_state.store(2, std::memory_order_release); return IDIST_OK; }
+    HIPCHK(hipSetDevice(ix->device));
+    const uint32_t stride = ix->L.stride, fs = filt_stride(stride);
+    // sample: up to 2048 rows, evenly spaced
+    const uint32_t ns = std::min<uint32_t>(ix->n, 2048u), every = ix->n / ns;
+    std::vector<float> smp((size_t)ns * stride);
+    HIPCHK(hipMemcpy2D(smp.data(), (size_t)stride * 4, ix->d_points, (size_t)every * stride * 4, (size_t)stride * 4, ns, hipMemcpyDeviceToHost));
+    if (ix->filt_state.load(std::memory_order_acquire) == 1) {          // the identity table stands (a build made it): the second one now
+        CHK(filter_principal_ensure(ix, smp, ns, ix->filt));
+        ix->filt_p_state.store(1, std::memory_order_release);
+        return IDIST_OK;
+    }
+    // robust range: mean and sigma of the central 98 % of the sampled coordinates (a few wild values — or heavy tails — must not
+    // stretch the lattice: they are clamped, and only their own rows pay for it), sigma rescaled to the whole of a Gaussian
+    std::vector<float> vals;
+    vals.reserve((size_t)ns * ix->kdim);
+    for (uint32_t r = 0; r < ns; r++)
+        for (uint32_t pos = 0; pos < stride; pos++) {
+            if (natural_pos(pos, ix->L.nb) >= ix->kdim) continue;
+            const float v = smp[(size_t)r * stride + pos];
+            if (std::fabs(v) <= 3.0e38f) vals.push_back(v);
+        }
+    double lo = 0.0, hi = 1.0;
+    filter_robust_range(vals, lo, hi);
     FilterView f{};
     f.fstride = fs;
     f.lo = (float)lo;
@@ -1534,6 +1792,14 @@ idist_status filter_ensure(const idist_index* ix) {
     }
     f.rows = rows;
     ix->filt = f;
+    if (with_principal) {
+        if (const idist_status ps = filter_principal_ensure(ix, smp, ns, f); ps != IDIST_OK) {
+            hipFree(rows);
+            ix->filt = FilterView{};
+            return ps;
+        }
+        ix->filt_p_state.store(1, std::memory_order_release);
+    }
     ix->filt_state.store(1, std::memory_order_release);
     return IDIST_OK;
 }
@@ -1607,7 +1873,7 @@ idist_status launch_search(const idist_index* ix, idist_search_ctx* ctx, const f
     const bool filtered = use_filter && ix->filt_state.load(std::memory_order_acquire) == 1;
     // (every other wide walk — unfiltered indexes, IDIST_TAB_FORMAT=ids, the classic test walks, n beyond the quotient form's reach —
     //  runs the round-5 kernels, compiled WITHOUT the filter: carrying its registers cost the 1024-d search 15 %)
-    // Long rows (compact rows beyond four chunks: 768-d) keep ONE fat wave per SIMD with the filter: a thin wave's registers hold 16
+    // Long rows (compact rows beyond the thin tile's five chunks: 768-d) keep ONE fat wave per SIMD with the filter: a thin wave's registers hold 16
     // of their compact rows and a quarter of an f32 row at a time — six or seven dependent round trips per expansion where the fat
     // wave makes two (C5, ef 200: 162 ms fat against 213 ms thin per 65,536 queries; C4 a tie at 78-83 ms).
     // (always on the quotient form of the set — the id form's cheaper probe was worth 1-2 % and another two large kernels to compile)
@@ -1616,7 +1882,12 @@ idist_status launch_search(const idist_index* ix, idist_search_ctx* ctx, const f
     // ... except the 768-d instantiation while the id form of the set cannot fill up (ef_search <= ~120: C4)
     const bool fat_ids = fat_filtered && ix->L.nb == 24 && ix->L.rs == 0 && ix->L.tail == 0;
     uint32_t fw = 1;
-    if (filtered && !fat_filtered && !ctx->knobs.classic && !ctx->knobs.tab_ids) fw = kFilterWaves;
+    if (filtered) CHK(filter_basis_forced_check(ix, ctx->knobs.basis));
+    // thin walks read the table the index's policy chose (filter_principal_ensure) — the 64-byte principal rows have their own instantiation
+    const bool principal_rows = filtered && !fat_filtered && ix->filt_p.rows &&
+                                (ctx->knobs.basis ? ctx->knobs.basis : ix->filt_format.load(std::memory_order_relaxed)) == IDIST_FILTER_FORMAT_PRINCIPAL;
+    if (filtered && !fat_filtered && !ctx->knobs.classic && !ctx->knobs.tab_ids)
+        fw = principal_rows ? (ctx->knobs.filter_waves ? ctx->knobs.filter_waves : kFilterWavesPrincipal) : kFilterWaves;
     if (fw > 1) {
         uint32_t l = ctx->knobs.tab_log2 ? std::min(tab_fit, ctx->knobs.tab_log2) : tab_fit;
         // (a smaller set addresses fewer ids in its 16-bit quotients: 10M points need the 16-KB set — C5 runs six or seven thin
@@ -1690,11 +1961,13 @@ idist_status launch_search(const idist_index* ix, idist_search_ctx* ctx, const f
     [[maybe_unused]] const bool classic = ctx->knobs.classic;   // (test build: IDIST_VARIANT_SEARCH_*)
     IndexView view = ix->view();
     if (!thin && !fat_filtered) view.f = FilterView{};
+    const bool principal = thin && principal_rows;
+    if (principal) { view.f2 = view.f; view.f = ix->filt_p; }       // (f2: the identity rows, for the queries the basis does not fit)
     a.queue_base = ctx->queue_base;
     a.status_host = status_host && grid <= idist_search_ctx::kIoStatusSlots ? status_host : nullptr;
     a.done_host = done_host;
     a.done_count = ctx->d_next + 2;
-    a.filt_counts = reinterpret_cast<unsigned long long*>(ctx->d_next + 16);
+    a.filt_counts = reinterpret_cast<unsigned long long*>(ctx->d_next + 16);       // [4]: + the share of both on the principal rows
     a.done_seq = done_seq;
     if (grid_out) *grid_out = grid;
     const uint32_t slot = (uint32_t)(ctx->n_launch % IDIST_EVENT_RING);
@@ -1732,6 +2005,10 @@ idist_status launch_search(const idist_index* ix, idist_search_ctx* ctx, const f
         } else if (quad) {                                                                         \
             auto kS = search_kernel<NB_, RS_, TAIL_, walk_code(kWalkOverlap, 0, false, 1, true, true)>; \
             IDIST_LAUNCH(kS, grid, 256, smem, stream, view, a);                                    \
+        } else if (thin && principal && fw == 3u) {                                                \
+            launched = SearchLaunch<NB_, RS_, TAIL_, walk_thin_filter_principal(3), GeoKernels<NB_>::thin_search && kPrincipalWaves3>::go(grid, smem, stream, view, a); \
+        } else if (thin && principal) {                                                            \
+            launched = SearchLaunch<NB_, RS_, TAIL_, walk_thin_filter_principal(2), GeoKernels<NB_>::thin_search>::go(grid, smem, stream, view, a); \
         } else if (thin) {                                                                         \
             launched = SearchLaunch<NB_, RS_, TAIL_, walk_thin_filter(2), GeoKernels<NB_>::thin_search>::go(grid, smem, stream, view, a); \
         } IDIST_VARIANT_SEARCH_ONCHIP_Q16(NB_, RS_, TAIL_) else if (w2) {                          \
@@ -2003,6 +2280,15 @@ idist_status idist_index_get_info(const idist_index* idx, idist_index_info* out)
     out->tie_capacity = tie_capacity(idx->cfg);
     out->dot_bound = is_dot(idx->cfg) ? idx->dot_S : 0.0f;
     for (uint32_t l = 0; l < idx->n_upper; l++) out->layer_len[l] = idx->layer_len[l];
+    // the reject filter's tables are made on first use (a wide search, idist_filter_bound_batch, a build): NONE / 0 / 0 until then —
+    // asking must not make them, the rows of a replication target may not have arrived yet
+    if (idx->filt_state.load(std::memory_order_acquire) == 1) {
+        out->filter_bytes = (uint64_t)idx->n * idx->filt.fstride;
+        if (idx->filt_p_state.load(std::memory_order_acquire) == 1) {       // (the format is decided: nothing below is written again)
+            out->filter_format = idx->filt_format.load(std::memory_order_relaxed);
+            out->filter_principal_bytes = idx->filt_p.rows ? (uint64_t)idx->n * idx->filt_p.fstride : 0u;
+        }
+    }
     return IDIST_OK;
 }
 
@@ -2033,6 +2319,9 @@ void idist_index_free(idist_index* idx) {
     hipFree(idx->d_upper);
     hipFree(idx->d_layer_off);
     hipFree(const_cast<uint8_t*>(idx->filt.rows));
+    hipFree(const_cast<uint8_t*>(idx->filt_p.rows));
+    hipFree(const_cast<float*>(idx->filt_p.basis));
+    hipFree(const_cast<float*>(idx->filt_p.mu));
     delete idx;
 }
 
@@ -2158,6 +2447,16 @@ idist_status idist_search_ctx_status(idist_search_ctx* ctx) {
         g_tie_cap_msg = cap;
     }
     return device_status_to_code(st, ctx->tie_policy);
+}
+
+idist_status idist_search_ctx_filter_principal_counts(idist_search_ctx* ctx, uint64_t* examined, uint64_t* rejected, int32_t reset) {
+    if (!ctx) return fail(IDIST_ERR_INVALID_ARG, "ctx is null");
+    unsigned long long c[2] = {0, 0};
+    HIPCHK(hipMemcpy(c, ctx->d_next + 20, sizeof(c), hipMemcpyDeviceToHost));
+    if (reset) HIPCHK(hipMemset(ctx->d_next + 20, 0, sizeof(c)));
+    if (examined) *examined = c[0];
+    if (rejected) *rejected = c[1];
+    return IDIST_OK;
 }
 
 idist_status idist_search_ctx_filter_counts(idist_search_ctx* ctx, uint64_t* examined, uint64_t* rejected, int32_t reset) {
@@ -2964,17 +3263,29 @@ static idist_status pairs_batch(const idist_index* idx, const float* queries, ui
     const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)nq * chunks, 1u << 20);
     const size_t smem = smem_bytes(idx->L.stride, 0, false);
     IndexView view = idx->view();
+    // the bound of the format wide searches of this index use
+    int basis = idx->filt_format.load(std::memory_order_relaxed);
+    if (const char* e = test_env("IDIST_FILTER_BASIS")) {               // (no context here: the knob as a new context would sample it)
+        if (bound && have_filter) CHK(filter_basis_forced_check(idx, filter_basis_knob(e)));
+        basis = filter_basis_knob(e) ? filter_basis_knob(e) : basis;
+    }
+    const bool principal = bound && have_filter && idx->filt_p.rows && basis == IDIST_FILTER_FORMAT_PRINCIPAL;
+    if (principal) { view.f2 = view.f; view.f = idx->filt_p; }
 #define LAUNCH_PAIRS(NB_, RS_, TAIL_)                                                                 \
-    if (bound) {                                                                                      \
+    if (bound && principal) {                                                                         \
+        launched = BoundLaunch<NB_, RS_, TAIL_, GeoKernels<NB_>::thin_search>::go(grid, smem, view, d_qk, nq, d_ids, n_ids, d_out); \
+    } else if (bound) {                                                                               \
         auto kD = filter_bound_kernel<NB_, RS_, TAIL_>;                                               \
         IDIST_LAUNCH(kD, grid, 64, smem, (hipStream_t) nullptr, view, d_qk, nq, d_ids, n_ids, d_out); \
     } else {                                                                                          \
         auto kD = distance_batch_kernel<NB_, RS_, TAIL_>;                                             \
         IDIST_LAUNCH(kD, grid, 64, smem, (hipStream_t) nullptr, view, d_qk, nq, d_ids, n_ids, d_out); \
     }
+    bool launched = true;
     if (have_filter || !bound) IDIST_DISPATCH(idx->L, LAUNCH_PAIRS);
     else HIPCHK(hipMemset(d_out, 0, ib));
 #undef LAUNCH_PAIRS
+    if (!launched) return fail(IDIST_ERR_INTERNAL, "no principal bound kernel for this row geometry (stride %u)", idx->L.stride);
     HIPCHK(hipGetLastError());
     CHK(metric.report(d_out, d_sq, nq, n_ids, nullptr));
     HIPCHK(hipMemcpy(out, d_out, ib, hipMemcpyDeviceToHost));

@@ -22,6 +22,7 @@
 //                           the ids in the same LDS); what it cannot hold goes to
 //                           one bit per point and slot in HBM.
 #pragma once
+#include <type_traits>
 #ifdef IDIST_EMU
 #include "hip_emu.hpp"   // tests/simt: CPU lockstep emulation of one wave (test infrastructure)
 #else
@@ -64,7 +65,17 @@ struct FilterView {
     float dscale = 0.0f;             // step256^2: |q^ - p^|^2 = I * dscale (a normal float: filter_ensure refuses lattices outside 2^-58 <= step256 <= 2^60)
     float up = 1.0f;                 // safety factor > 1 on the threshold side (rounding of every float step, of the canonical sum)
     float slack = 0.0f;              // absolute slack of a query's own lattice error (f32 evaluation), per sqrt(dim) * magnitude
+    // The PRINCIPAL format (thin search walks of eligible indexes; filter_ensure has the argument): a row is 56 one-byte codes of
+    // y = B (p - mu) on the lattice + the same 8 bytes of metadata = 64 B, one fabric request.  B: 56 orthonormal directions of largest
+    // sample variance, stored transposed [stride][64] in the rows' own (blocked) element order so that lane i reads component i of
+    // every position from consecutive addresses (columns 56..63 and the padding positions are zero); mu [stride] likewise.
+    // `slack` is then the f64 evaluation error of y per |x - mu|, and `up` carries s >= sigma_max(B) on top of the identity terms.
+    const float* basis = nullptr;    // nullptr: the identity format above
+    const float* mu = nullptr;
+    float rho_max = 0.0f;            // a query takes the principal rows while the share of |q - mu|^2 OUTSIDE the basis is at most this
+                                     // (twice what the sample's rows leave outside: the policy's prediction holds for such queries only)
 };
+constexpr int kFiltPrincipalM = 56;  // (= kBasisM, idist_basis.hpp)
 constexpr uint32_t filt_stride(uint32_t stride_floats) { return (stride_floats + 8u + 63u) & ~63u; }
 constexpr int kFiltRtChunks = 5;     // runtime-geometry rows on THIN filtered waves: a compact row of at most five 128-B chunks (dim <= 624: 512-d)
 constexpr int kFiltRtChunksFat = 13; // ... on one fat filtered wave per SIMD (longer rows, like 768-d): thirteen chunks (dim <= 1656: 512-d, 1024-d, 1536-d)
@@ -82,6 +93,7 @@ struct IndexView {
     uint32_t n_upper;
     uint32_t metric;          // 0 = squared L2, 1 = L2
     FilterView f;             // compact copy of the rows for the walk's reject filter (search kernels only)
+    FilterView f2;            // principal walks: f is the principal table, f2 the identity one for the queries the basis does not fit
 };
 
 // natural element of stored position `pos` (inverse of blocked_pos)
@@ -637,10 +649,16 @@ constexpr bool walk_thin(int code) { return (code & kWalkThinBit) != 0; }
 constexpr int walk_thin_filter(int waves = 2) {  // the walk code of a thin filtered walk at `waves` per SIMD: quotient set, one f32 round in flight
     return walk_code(kWalkOverlap, 1, true, waves, true, false, true) | kWalkFilterBit | kWalkThinBit;
 }
+// Thin filtered SEARCH walks on the principal format (bit 21): the compact row is the 64-B one of FilterView::basis — FilterQ<1, true>,
+// the 8-byte-per-lane tail alone: 2 registers per row in flight instead of 10 at 300-d, 4 of staged query instead of 20.
+constexpr int kWalkPrincipalBit = 1 << 21;
+constexpr bool walk_principal(int code) { return (code & kWalkPrincipalBit) != 0; }
+constexpr int walk_thin_filter_principal(int waves = 2) { return walk_thin_filter(waves) | kWalkPrincipalBit; }
 // 128-B chunks of a compact row (8 lanes x 16 B each; the last one may be half a chunk)
 // WALK: the walk code of the kernel (runtime geometries only: the fat filtered walk's tile is larger than the thin one's)
 template <int NB, int RS, int TAIL, int WALK = 0>
 constexpr int filt_chunks() {
+    if (walk_principal(WALK)) return 1;
     if (NB < 0) return walk_is_thin(WALK) || ((WALK >> 19) & 1) == 0 ? kFiltRtChunks : kFiltRtChunksFat;
     const uint32_t used = 32u * (uint32_t)NB + 8u * (uint32_t)RS + 4u * (uint32_t)TAIL;
     const uint32_t stride = used < 16u ? 16u : ((used + 15u) & ~15u);
@@ -649,8 +667,9 @@ constexpr int filt_chunks() {
 // The compile-time geometries' compact rows all end in HALF a chunk (320 = 2 x 128 + 64, 192, 832): that half is read as 8 bytes
 // per lane by all 8 lanes of a group (T8) instead of 16 bytes by four of them — two registers of row data per lane and round less,
 // which is what lets a thin wave keep all 64 rows of an expansion in flight at 300-d (8 x 10 registers).
-template <int NB, int RS, int TAIL>
+template <int NB, int RS, int TAIL, int WALK = 0>
 constexpr bool filt_tail8() {
+    if (walk_principal(WALK)) return true;           // (every geometry: the principal row is half a chunk)
     if (NB < 0) return false;
     const uint32_t used = 32u * (uint32_t)NB + 8u * (uint32_t)RS + 4u * (uint32_t)TAIL;
     const uint32_t stride = used < 16u ? 16u : ((used + 15u) & ~15u);
@@ -685,13 +704,91 @@ struct FilterQ {
     uint2 ht, lt;
     float eq = 0.0f;        // |q - q^|_2, rounded up (NaN for a query with a NaN coordinate: nothing is ever rejected)
     uint64_t sq = 0;        // sum Q^2
+    bool fits = true;       // principal staging: the query lies close enough to the basis (FilterView::rho_max)
     mutable bool on = false; // (a walk switches its own filter off when it is not paying, dist_pass_filtered)
     mutable uint32_t seen = 0, rejected = 0;   // per walk; search_kernel adds them to the context's counters when the query ends
 };
+__device__ __forceinline__ double shfl_xor_f64(double v, int m) {
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)b, m, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(b >> 32), m, 64);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+// y_i = sum_k B[i][k] (x[k] - mu[k]) in f64, component i in lane i (i < 56; the other lanes hold 0), and |x - mu|^2 in every lane: the
+// ONE evaluation both sides of the principal format use (filter_rows_principal_kernel for the rows, filter_stage_query for a query),
+// so that E_p and E_q speak about the same arithmetic.  x: a blocked row (padding zero), global or LDS.
+__device__ __forceinline__ double filter_project(const IndexView& ix, const float* x, double& d2) {
+    const int lane = lane_id();
+    const float* bt = ix.f.basis + lane;
+    double y = 0.0;
+    d2 = 0.0;
+    for (uint32_t pos = 0; pos < ix.stride; pos++) {
+        const double d = (double)x[pos] - (double)ix.f.mu[pos];
+        y = __builtin_fma((double)bt[(size_t)pos * 64u], d, y);
+        d2 = __builtin_fma(d, d, d2);
+    }
+    return lane < kFiltPrincipalM ? y : 0.0;         // (lanes 56..63 read zeros of B: 0 * inf would be NaN)
+}
+// |fl(y) - y^|-side error of a principal row or query, rounded up to f32: the lattice error e2 = sum e_i^2 as evaluated, the f64
+// evaluation slack of y (FilterView::slack per |x - mu|) and that of e_i itself (2^-52 of the magnitudes, sqrt(56) < 7.5 components)
+__device__ __forceinline__ float filter_principal_error(const IndexView& ix, double e2, double d2, double ymax) {
+    const double mag = ymax + __builtin_fabs((double)ix.f.lo) + 65536.0 * (double)ix.f.step256;
+    const double E = (__builtin_sqrt(e2) + (double)ix.f.slack * __builtin_sqrt(d2)) * (1.0 + 1e-6) + 7.5 * 0x1p-51 * mag;
+    float f = (float)E;
+    if (f < 3.0e38f) f = __uint_as_float(__float_as_uint(f) + 1u);      // one more ulp up: the cast rounded to nearest (NaN, inf: as they are)
+    return f;
+}
+// fv: the table the query is staged for — ix.f, or ix.f2 (the identity rows beside a principal walk)
 template <int NCH, bool T8>
-__device__ __forceinline__ void filter_stage_query(const IndexView& ix, const float* q, FilterQ<NCH, T8>& fq) {
+__device__ __forceinline__ void filter_stage_query(const IndexView& ix, const float* q, FilterQ<NCH, T8>& fq, const FilterView& fv) {
     constexpr int NCF = FilterQ<NCH, T8>::NCF;
-    fq.on = ix.f.rows != nullptr && ix.f.fstride <= 128u * (uint32_t)NCH && (!T8 || ix.f.fstride == 128u * (uint32_t)NCF + 64u);
+    if constexpr (NCH == 1 && T8) {
+        // The principal format (the only 64-B row with an 8-byte-per-lane tail: identity rows that short belong to runtime geometries,
+        // which read 16 bytes per lane).  Lane i holds y_i = (B (q - mu))_i and its 16-bit lattice coordinate; lane j of every group
+        // then collects the byte planes of components 8 j .. 8 j + 7 — lane 7's are the row's metadata: zero.
+        fq.on = ix.f.rows != nullptr && ix.f.basis != nullptr && ix.f.fstride == 64u;
+        fq.ht = make_uint2(0u, 0u);
+        fq.lt = make_uint2(0u, 0u);
+        fq.h[0] = fq.l[0] = make_uint4(0u, 0u, 0u, 0u);
+        if (!fq.on) return;
+        const int lane = lane_id();
+        double d2;
+        const double y = filter_project(ix, q, d2);
+        uint32_t Q = 0u;
+        double e = 0.0;
+        if (lane < kFiltPrincipalM) {
+            const double t = (y - (double)ix.f.lo) * (double)ix.f.qscale;
+            Q = (uint32_t)__builtin_rint(__builtin_fmin(__builtin_fmax(t, 0.0), 65535.0));     // fmax(NaN, 0) = 0
+            e = y - __builtin_fma((double)Q, (double)ix.f.step256, (double)ix.f.lo);            // NaN / inf for such a y
+        }
+        double e2 = e * e, ymax = __builtin_fabs(y), y2 = y * y;
+        unsigned long long sq = (unsigned long long)Q * Q;
+        for (int m = 1; m < 64; m <<= 1) {
+            e2 += shfl_xor_f64(e2, m);
+            y2 += shfl_xor_f64(y2, m);
+            ymax = __builtin_fmax(ymax, shfl_xor_f64(ymax, m));
+            const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)sq, m, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(sq >> 32), m, 64);
+            sq += ((unsigned long long)hi << 32) | lo;
+        }
+        fq.sq = sq;
+        const int j = lane & 7;
+        uint32_t hw[2] = {0u, 0u}, lw[2] = {0u, 0u};
+#pragma unroll
+        for (int b = 0; b < 8; b++) {
+            const uint32_t Qb = (uint32_t)__shfl((int)Q, 8 * j + b, 64);
+            hw[b >> 2] |= (Qb >> 8) << (8 * (b & 3));
+            lw[b >> 2] |= (Qb & 255u) << (8 * (b & 3));
+        }
+        fq.ht = make_uint2(hw[0], hw[1]);
+        fq.lt = make_uint2(lw[0], lw[1]);
+        // E_q, never below 16 sub-steps (a 16th of a code step: nothing beside a row's own lattice error) — what keeps the right-hand
+        // side of the test a normal float and the canonical chain's underflow out of reach (filter_ensure, "The scale range")
+        float eq = filter_principal_error(ix, e2, d2, ymax);
+        const float floor_ = 16.0f * ix.f.step256;
+        fq.eq = eq < floor_ ? floor_ : eq;                                                      // (NaN stays NaN: nothing is rejected)
+        fq.fits = d2 - y2 <= (double)ix.f.rho_max * d2;                                         // (NaN: false — the identity rows' staging deals with it)
+        return;
+    }
+    fq.on = fv.rows != nullptr && fv.fstride <= 128u * (uint32_t)NCH && (!T8 || fv.fstride == 128u * (uint32_t)NCF + 64u);
     fq.ht = make_uint2(0u, 0u);
     fq.lt = make_uint2(0u, 0u);
 #pragma unroll
@@ -710,10 +807,10 @@ __device__ __forceinline__ void filter_stage_query(const IndexView& ix, const fl
             const uint32_t pos = 128u * (uint32_t)c + (tail ? 8u : 16u) * (uint32_t)j + (uint32_t)b;
             if (pos < ix.stride && natural_pos(pos, ix.nb) < ix.dim) {       // (padding: Q = u = 0 by construction, no error either side)
                 const float v = q[pos];
-                const float t = (v - ix.f.lo) * ix.f.qscale;
+                const float t = (v - fv.lo) * fv.qscale;
                 const float r = __builtin_rintf(__builtin_fminf(__builtin_fmaxf(t, 0.0f), 65535.0f));   // fmax(NaN, 0) = 0
                 const uint32_t Q = (uint32_t)r;
-                const float e = v - __builtin_fmaf((float)Q, ix.f.step256, ix.f.lo);                     // NaN / inf for such a v
+                const float e = v - __builtin_fmaf((float)Q, fv.step256, fv.lo);                     // NaN / inf for such a v
                 e2 = __builtin_fmaf(e, e, e2);
                 mx = __builtin_fmaxf(mx, __builtin_fabsf(v));
                 const uint32_t qq = Q * Q;
@@ -742,8 +839,31 @@ __device__ __forceinline__ void filter_stage_query(const IndexView& ix, const fl
     }
     fq.sq = sq;
     // |q - q^| as evaluated in f32: each term is off by at most ~2^-22 of the magnitudes involved
-    const float mag = mx + __builtin_fabsf(ix.f.lo) + 65536.0f * ix.f.step256;
-    fq.eq = __builtin_sqrtf(e2) * 1.001f + ix.f.slack * mag;
+    const float mag = mx + __builtin_fabsf(fv.lo) + 65536.0f * fv.step256;
+    fq.eq = __builtin_sqrtf(e2) * 1.001f + fv.slack * mag;
+}
+template <int NCH, bool T8>
+__device__ __forceinline__ void filter_stage_query(const IndexView& ix, const float* q, FilterQ<NCH, T8>& fq) { filter_stage_query(ix, q, fq, ix.f); }
+// The staged query of a thin search walk on the principal format: its 64-byte form, and — only for a query the basis does not fit,
+// e.g. one from another subspace than the rows, for which 56 coordinates prove little — the identity form on ix.f2 instead.  One choice
+// per query, wave-uniform, a function of the query and the index: deterministic.  on / seen / rejected are the base's, whichever serves.
+template <int NCH, bool T8>
+struct FilterQDual : FilterQ<NCH, T8> {
+    FilterQ<1, true> p;
+    bool principal = false;
+};
+template <int NCH, bool T8>
+__device__ __forceinline__ void filter_stage_query(const IndexView& ix, const float* q, FilterQDual<NCH, T8>& fq) {
+    filter_stage_query(ix, q, fq.p, ix.f);
+    fq.principal = fq.p.on && fq.p.fits;
+    if (fq.principal) {
+        fq.on = true;
+        fq.ht = fq.lt = make_uint2(0u, 0u);
+#pragma unroll
+        for (int c = 0; c < (FilterQ<NCH, T8>::NCF > 0 ? FilterQ<NCH, T8>::NCF : 1); c++) fq.h[c] = fq.l[c] = make_uint4(0u, 0u, 0u, 0u);
+    } else {
+        filter_stage_query(ix, q, static_cast<FilterQ<NCH, T8>&>(fq), ix.f2);
+    }
 }
 
 // One filter pass over act_pid[0..na): act_dist[k] = kAbandoned where the compact row PROVES that the canonical distance
@@ -760,7 +880,7 @@ __device__ __forceinline__ uint32_t group_total_u32(uint32_t v) {           // s
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, true);   // row_half_mirror: the other quad's sum
     return v;
 }
-template <int NCH, bool T8, int FR, class Mid = NoMid, bool BOUND = false>
+template <int NCH, bool T8, int FR, class Mid = NoMid, bool BOUND = false, bool SECOND = false>     // SECOND: the rows of ix.f2
 __device__ __forceinline__ void filter_rounds(const IndexView& ix, const FilterQ<NCH, T8>& fq, const uint32_t* act_pid, uint32_t* act_dist,
                                               int na, float st, Mid mid = Mid()) {
     static_assert(FR >= 1 && FR <= 8, "lane j of a group finishes round j");
@@ -768,14 +888,15 @@ __device__ __forceinline__ void filter_rounds(const IndexView& ix, const FilterQ
     constexpr int NCA = NCF > 0 ? NCF : 1;
     const int lane = lane_id();
     const int g = lane >> 3, j = lane & 7;
-    const uint32_t fs = ix.f.fstride;
+    const FilterView& fv = SECOND ? ix.f2 : ix.f;
+    const uint32_t fs = fv.fstride;
     for (int base = 0; base < na; base += 8 * FR) {
         uint4 p[FR][NCA];
         uint2 pt[FR];
 #pragma unroll
         for (int r = 0; r < FR; r++) {
             const int k = base + 8 * r + g;
-            const uint8_t* rowb = ix.f.rows + (size_t)act_pid[k < na ? k : 0] * fs;
+            const uint8_t* rowb = fv.rows + (size_t)act_pid[k < na ? k : 0] * fs;
             const uint8_t* row = rowb + 16u * (uint32_t)j;
 #pragma unroll
             for (int c = 0; c < NCF; c++) {
@@ -790,7 +911,7 @@ __device__ __forceinline__ void filter_rounds(const IndexView& ix, const FilterQ
         const bool fin = j < FR && kf < na;
         uint32_t ep = 0u, su = 0u;
         if (fin) {
-            const uint32_t* m = reinterpret_cast<const uint32_t*>(ix.f.rows + (size_t)act_pid[kf] * fs + (fs - 8u));
+            const uint32_t* m = reinterpret_cast<const uint32_t*>(fv.rows + (size_t)act_pid[kf] * fs + (fs - 8u));
             ep = m[0];
             su = m[1];
         }
@@ -819,16 +940,16 @@ __device__ __forceinline__ void filter_rounds(const IndexView& ix, const FilterQ
             // I = sum (Q - 256 u)^2 = sum Q^2 - 512 sum Q u + 65536 sum u^2, exact
             const uint64_t A = ((uint64_t)ah_f << 8) + (uint64_t)al_f;
             const uint64_t I = fq.sq + ((uint64_t)su << 16) - (A << 9);
-            const float dh = (float)I * ix.f.dscale;                      // |q^ - p^|^2
+            const float dh = (float)I * fv.dscale;                      // |q^ - p^|^2
             if constexpr (BOUND) {
                 // rejected iff dh > ((st + E) up)^2  <=>  st < sqrt(dh) / up - E: that supremum, rounded down
                 // (dh = +inf: the exact product is beyond FLT_MAX, any finite value is below it; NaN stays NaN)
                 const float dhb = dh > 3.0e38f ? 3.0e38f : dh;
-                float b = __builtin_sqrtf(dhb) * 0.999999f / ix.f.up - (__uint_as_float(ep) + fq.eq) * 1.000001f;
+                float b = __builtin_sqrtf(dhb) * 0.999999f / fv.up - (__uint_as_float(ep) + fq.eq) * 1.000001f;
                 b = b > 0.0f ? b : 0.0f;                                  // (NaN: 0 — no bound)
                 act_dist[kf] = __float_as_uint(ix.metric ? b : b * b * 0.999999f);
             } else {
-                const float t = (st + (__uint_as_float(ep) + fq.eq)) * ix.f.up;
+                const float t = (st + (__uint_as_float(ep) + fq.eq)) * fv.up;
                 act_dist[kf] = dh > t * t ? kAbandoned : 0u;              // (NaN anywhere: not rejected)
             }
         }
@@ -839,19 +960,34 @@ __device__ __forceinline__ void filter_rounds(const IndexView& ix, const FilterQ
 // its visited-set inserts — runs while they are in flight), then the f32 rows of the ids that were not rejected, through the
 // walk's ordinary pass.  act_dist[k] ends up as the canonical distance bits of id k, or kAbandoned — above every key of a full
 // `nearest`, so `push` turns it down exactly as it would have turned down the distance itself (core/lib.rs:712-714).
-// thr_bits = 0xFFFFFFFF (nearest not full yet, or a build descent: its distance log needs every distance): no filter.
-template <int NB, int RS, int TAIL, int WALK> using FilterQFor = FilterQ<filt_chunks<NB, RS, TAIL, WALK>(), filt_tail8<NB, RS, TAIL>()>;
+// thr_bits = 0xFFFFFFFF (nearest not full yet): no filter.  Build descents run filtered too: a rejected candidate's entry in their
+// distance log is its bound, marked as one (kDlogBound), and dlog_resolve fetches the distance of the few the build asks for.
+template <int NB, int RS, int TAIL, int WALK> struct FilterQPick {
+    using type = FilterQ<filt_chunks<NB, RS, TAIL, WALK>(), filt_tail8<NB, RS, TAIL, WALK>()>;
+};
+template <int NB, int RS, int TAIL, int WALK> using FilterQFor =
+    std::conditional_t<walk_principal(WALK), FilterQDual<filt_chunks<NB, RS, TAIL, WALK & ~kWalkPrincipalBit>(), filt_tail8<NB, RS, TAIL, WALK & ~kWalkPrincipalBit>()>,
+                       typename FilterQPick<NB, RS, TAIL, WALK>::type>;
 template <int NB, int RS, int TAIL, int WALK, class Mid = NoMid>
 __device__ __forceinline__ void dist_pass_filtered(const IndexView& ix, const float* q, const FilterQFor<NB, RS, TAIL, WALK>& fq,
                                                    uint32_t* act_pid, uint32_t* act_dist, int na, Mid mid, uint32_t thr_bits) {
     if constexpr (walk_filter(WALK)) {
         if (fq.on && thr_bits != 0xFFFFFFFFu && na > 0) {
-            constexpr int NCH = filt_chunks<NB, RS, TAIL, WALK>();
-            constexpr bool T8 = filt_tail8<NB, RS, TAIL>();
+            constexpr int kIdWalk = WALK & ~kWalkPrincipalBit;
+            constexpr int NCH = filt_chunks<NB, RS, TAIL, kIdWalk>();
+            constexpr bool T8 = filt_tail8<NB, RS, TAIL, kIdWalk>();
             const int lane = lane_id();
             const float thr = __uint_as_float(thr_bits);
             const float st = ix.metric ? thr : __builtin_sqrtf(thr);
-            filter_rounds<NCH, T8, filt_rounds<NCH, T8, WALK>()>(ix, fq, act_pid, act_dist, na, st, mid);
+            if constexpr (walk_principal(WALK)) {
+                if (fq.principal) filter_rounds<1, true, filt_rounds<1, true, WALK>()>(ix, fq.p, act_pid, act_dist, na, st, mid);
+                // (the identity rows of the exceptional query two rounds of 8 rows at a time — one for the runtime geometries' five-chunk
+                //  tile — instead of the identity walk's eight: with all of them in flight the kernel needs 76 B of scratch at 300-d, which
+                //  every query pays for; as it stands 12 B are left, 96 B on runtime geometries: DESIGN.md §4.5)
+                else filter_rounds<NCH, T8, (NB < 0 ? 1 : 2), Mid, false, true>(ix, fq, act_pid, act_dist, na, st, mid);
+            } else {
+                filter_rounds<NCH, T8, filt_rounds<NCH, T8, WALK>()>(ix, fq, act_pid, act_dist, na, st, mid);
+            }
             wave_sync();
             const bool in = lane < na;
             const uint32_t pid = in ? act_pid[lane] : 0u;

@@ -71,6 +71,45 @@ __global__ __launch_bounds__(64) void filter_rows_kernel(const float* __restrict
     }
 }
 
+// The 64-byte rows of the principal format (FilterView::basis): one wave per row, lane i < 56 evaluates y_i = (B (p - mu))_i exactly
+// as filter_stage_query does for a query (filter_project) and writes its code u_i = round((y_i - lo) / step) clamped to [0, 255];
+// bytes 56..63: {E_p rounded UP as f32, sum u_i^2} with E_p = |fl(y) - p^| + the evaluation slack of y.  A row with a non-finite
+// coordinate gets +inf there: the filter never rejects it.
+__global__ __launch_bounds__(64) void filter_rows_principal_kernel(IndexView ix, uint8_t* __restrict__ rows) {
+    const int lane = lane_id();
+    const double step = 256.0 * (double)ix.f.step256;
+    for (uint32_t r = blockIdx.x; r < ix.n; r += gridDim.x) {
+        const float* src = ix.points + (size_t)r * ix.stride;
+        uint8_t* dst = rows + (size_t)r * 64u;
+        bool bad = false;
+        for (uint32_t pos = (uint32_t)lane; pos < ix.stride; pos += 64u) bad = bad || !(__builtin_fabsf(src[pos]) <= 3.0e38f);
+        double d2;
+        const double y = filter_project(ix, src, d2);
+        uint32_t u = 0u;
+        double e = 0.0;
+        if (lane < kFiltPrincipalM) {
+            const double t = (y - (double)ix.f.lo) / step;
+            u = (uint32_t)__builtin_rint(__builtin_fmin(__builtin_fmax(t, 0.0), 255.0));        // fmax(NaN, 0) = 0
+            e = y - __builtin_fma((double)u, step, (double)ix.f.lo);
+        }
+        double e2 = e * e, ymax = __builtin_fabs(y);
+        uint32_t su = u * u;
+        for (int m = 1; m < 64; m <<= 1) {
+            e2 += shfl_xor_f64(e2, m);
+            ymax = __builtin_fmax(ymax, shfl_xor_f64(ymax, m));
+            su += (uint32_t)__shfl_xor((int)su, m, 64);
+        }
+        const bool any_bad = __ballot(bad) != 0ull;
+        if (lane < kFiltPrincipalM) dst[lane] = (uint8_t)u;
+        if (lane == 0) {
+            float ep = filter_principal_error(ix, e2, d2, ymax);
+            if (any_bad || !(ep <= 3.0e38f)) ep = __uint_as_float(0x7f800000u);
+            reinterpret_cast<uint32_t*>(dst + 56)[0] = __float_as_uint(ep);
+            reinterpret_cast<uint32_t*>(dst + 56)[1] = su;
+        }
+    }
+}
+
 // UpperNode::from_zero for a whole layer, core/lib.rs:323-328, core/types.rs:66-70
 __global__ void snapshot_kernel(const uint32_t* __restrict__ zero, uint32_t* __restrict__ upper_rows, uint32_t rows) {
     const size_t total = (size_t)rows * kM;
@@ -211,7 +250,7 @@ struct SearchArgs {
     uint32_t* done_host;
     uint32_t* done_count;
     uint32_t done_seq;
-    unsigned long long* filt_counts;   // [2] device words of the context: candidates the reject filter examined / rejected
+    unsigned long long* filt_counts;   // [4] device words of the context: candidates the reject filter examined / rejected, and the part of both on principal rows
 };
 // the LDS tail region (after the dirty-block bitmap) holds the Bloom filter or the on-chip visited set
 __device__ __forceinline__ void visited_attach_tab(Visited& v, uint32_t* mem, uint32_t log2_entries) {
@@ -341,6 +380,12 @@ __global__ __launch_bounds__(walk_quad(LAT) ? 256 : 64) IDIST_WAVES_ATTR(LAT) vo
             if (lane == 0 && fq.seen) {
                 atomicAdd(&a.filt_counts[0], (unsigned long long)fq.seen);
                 atomicAdd(&a.filt_counts[1], (unsigned long long)fq.rejected);
+                if constexpr (walk_principal(LAT)) {                   // ... of which on the 64-byte rows (idist_search_ctx_filter_principal_counts)
+                    if (fq.principal) {
+                        atomicAdd(&a.filt_counts[2], (unsigned long long)fq.seen);
+                        atomicAdd(&a.filt_counts[3], (unsigned long long)fq.rejected);
+                    }
+                }
             }
         }
     }
@@ -390,19 +435,23 @@ __global__ __launch_bounds__(64) void distance_batch_kernel(IndexView ix, const 
 
 // The reject filter on its own (idist_filter_bound_batch): for id lists, the lower bound of the canonical distance the compact
 // rows give — what the walk's filter compares with nearest[ef-1] — through the walk's own loads and arithmetic (filter_rounds).
-template <int NB, int RS, int TAIL>
+// PRINCIPAL: the 64-byte rows of FilterView::basis (ix.f is that format's view) — the format thin wide searches of the index use.
+template <int NB, int RS, int TAIL, bool PRINCIPAL = false>
 __global__ __launch_bounds__(64) void filter_bound_kernel(IndexView ix, const float* __restrict__ queries, uint32_t nq,
                                                          const uint32_t* __restrict__ ids, uint32_t n_ids, float* __restrict__ out) {
     IDIST_DYN_SMEM(smem_raw);
     const Smem sm = carve(smem_raw, ix.stride, 0, false);
     const int lane = lane_id();
     const uint32_t chunks = (n_ids + 63u) / 64u;
-    constexpr int NCH = filt_chunks<NB, RS, TAIL, kWalkFilterBit>();       // (runtime geometries: the larger tile)
-    constexpr bool T8 = filt_tail8<NB, RS, TAIL>();
+    constexpr int NCH = filt_chunks<NB, RS, TAIL, kWalkFilterBit | (PRINCIPAL ? kWalkPrincipalBit : 0)>();   // (runtime geometries: the larger tile)
+    constexpr bool T8 = filt_tail8<NB, RS, TAIL, PRINCIPAL ? kWalkPrincipalBit : 0>();
+    constexpr int NCHI = filt_chunks<NB, RS, TAIL, kWalkFilterBit | (PRINCIPAL ? kWalkThinBit : 0)>();      // the identity rows (principal: thin geometries only)
+    constexpr bool T8I = filt_tail8<NB, RS, TAIL>();
     for (uint32_t w = blockIdx.x; w < nq * chunks; w += gridDim.x) {
         const uint32_t qi = w / chunks, c0 = (w % chunks) * 64u;
         stage_query<NB>(ix, sm.q, queries + (size_t)qi * ix.dim);
-        FilterQ<NCH, T8> fq;
+        // (PRINCIPAL: per query the rows its walk would read — the identity ones of ix.f2 for a query the basis does not fit)
+        std::conditional_t<PRINCIPAL, FilterQDual<NCHI, T8I>, FilterQ<NCH, T8>> fq;
         filter_stage_query(ix, sm.q, fq);
         const uint32_t i = c0 + lane;
         uint32_t id = kInvalid;
@@ -412,7 +461,12 @@ __global__ __launch_bounds__(64) void filter_bound_kernel(IndexView ix, const fl
         const int my = __popcll(m & ((1ull << lane) - 1ull));
         if (ok) sm.act_pid[my] = id;
         wave_sync();
-        if (m) filter_rounds<NCH, T8, 2, NoMid, true>(ix, fq, sm.act_pid, sm.act_dist, __popcll(m), 0.0f);
+        if constexpr (PRINCIPAL) {
+            if (m && fq.principal) filter_rounds<1, true, 2, NoMid, true>(ix, fq.p, sm.act_pid, sm.act_dist, __popcll(m), 0.0f);
+            else if (m) filter_rounds<NCHI, T8I, 2, NoMid, true, true>(ix, fq, sm.act_pid, sm.act_dist, __popcll(m), 0.0f);
+        } else {
+            if (m) filter_rounds<NCH, T8, 2, NoMid, true>(ix, fq, sm.act_pid, sm.act_dist, __popcll(m), 0.0f);
+        }
         wave_sync();
         if (i < n_ids) out[(size_t)qi * n_ids + i] = ok ? __uint_as_float(sm.act_dist[my]) : 0.0f;
     }
