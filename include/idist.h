@@ -155,6 +155,9 @@ typedef struct idist_index_info {
                                    principal basis: thin search walks of low-rank data).  One deterministic choice per index. */
     uint64_t filter_bytes;           /* device memory of the identity table (0: this index runs unfiltered) ... */
     uint64_t filter_principal_bytes; /* ... and of the principal one, 64 B per row on top (0: not made, or dropped by the policy) */
+    uint64_t filter_inline_bytes;    /* ... and of the principal rows stored once more with the adjacency, 4096 B per point: made at the first
+                                        wide search of an index in the PRINCIPAL format (0: not made — another format, above the cap of
+                                        8 GiB, or no memory; the walks then read the principal table itself) */
 } idist_index_info;
 enum { IDIST_FILTER_FORMAT_NONE = 0, IDIST_FILTER_FORMAT_IDENTITY = 1, IDIST_FILTER_FORMAT_PRINCIPAL = 2 };
 
@@ -299,6 +302,10 @@ idist_status idist_search_ctx_filter_counts(idist_search_ctx* ctx, uint64_t* exa
  * lies mostly outside the index's basis is served from the identity rows inside the same launch, so what a launch requested is
  * principal_examined * 64 + (examined - principal_examined) * identity row bytes + (pushes - rejected) * 4 * dim.  Own reset. */
 idist_status idist_search_ctx_filter_principal_counts(idist_search_ctx* ctx, uint64_t* examined, uint64_t* rejected, int32_t reset);
+/* ... and, for an index with idist_index_info.filter_inline_bytes: the 4096-byte blocks the walks requested (prefetches for a wrong
+ * guess included) and the blocks they tested.  The candidates counted by filter_principal_counts were then read as part of these blocks:
+ * a launch requested blocks_requested * 4096 bytes of compact rows for them instead of principal_examined * 64.  Own reset. */
+idist_status idist_search_ctx_filter_inline_counts(idist_search_ctx* ctx, uint64_t* blocks_requested, uint64_t* blocks_used, int32_t reset);
 /* HIP-event duration of the last search kernel launched through ctx, milliseconds. */
 idist_status idist_search_ctx_last_kernel_ms(idist_search_ctx* ctx, float* ms);
 /* Durations (ms) of the most recent search-kernel launches through ctx, oldest first, measured

@@ -302,6 +302,15 @@ class Search:
         _lib().check(_lib().idist_search_ctx_filter_principal_counts(self._ctx, C.byref(a), C.byref(b), 1 if reset else 0))
         return int(a.value), int(b.value)
 
+    def filter_inline_counts(self, reset: bool = True) -> tuple[int, int]:
+        """(4096-byte blocks of principal rows stored with the adjacency that the walks requested, blocks they tested) — indexes with
+        `Hnsw.info().filter_inline_bytes` only.  Its own reset.  Synchronise first."""
+        if self._ctx is None:
+            return 0, 0
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        _lib().check(_lib().idist_search_ctx_filter_inline_counts(self._ctx, C.byref(a), C.byref(b), 1 if reset else 0))
+        return int(a.value), int(b.value)
+
     def check_status(self):
         """Raise if a device-side guard tripped during the launches so far (after a stream sync)."""
         _lib().check(_lib().idist_search_ctx_status(self._ctx))

@@ -273,6 +273,9 @@ struct idist_index {
     mutable bool filt_p_turned_down = false;   // the policy chose the identity rows and no knob asked to keep the other table
     mutable std::atomic<int> filt_p_state{0};  // 0: basis, policy and principal table still to come (a build makes the identity table only:
                                                // the basis is 0.1 s of host time, which belongs to the first wide search, not to the build), 1: done
+    // ... and the principal rows once more, stored with the adjacency (IndexView::inl, filter_inline_ensure): 4 KB per point
+    mutable uint8_t* filt_inl = nullptr;
+    mutable std::atomic<int> filt_inl_state{0};   // 0 not tried yet, 1 ready, 2 not available (above the cap, or no memory: the walks read filt_p)
 
     IndexView view() const {
         IndexView v;
@@ -317,6 +320,8 @@ struct Knobs {
     uint32_t filter_waves = 0;    // IDIST_FILTER_WAVES=2|3: thin waves per SIMD of a walk on the principal rows (A/B knob; 0: kFilterWavesPrincipal)
     int basis = 0;                // IDIST_FILTER_BASIS=identity|principal: the compact rows thin wide searches read, whatever the index's
                                   // policy chose (principal: where the index is eligible for that table) (test / A-B knob)
+    int inl = -1;                 // IDIST_FILTER_INLINE=0|1: thin principal walks without / with the principal rows stored with the adjacency
+                                  // (A/B knob; -1: kFilterInlinePolicy)
     bool tab_ids = false;         // IDIST_TAB_FORMAT=ids: the on-chip set always keeps full ids (4 per bucket, frozen at 7/8), never
                                   // 16-bit quotients (8 per bucket, single ids overflow) (test / A-B knob)
     bool tab_q16 = false;         // IDIST_TAB_FORMAT=q16: quotients wherever they apply, also where the policy would keep ids
@@ -347,6 +352,7 @@ struct Knobs {
         if (const char* e = test_env("IDIST_BLOOM")) k.bloom = e[0] != '0';
         if (const char* e = test_env("IDIST_FILTER")) k.filter = e[0] != '0';
         if (const char* e = test_env("IDIST_FILTER_BASIS")) k.basis = filter_basis_knob(e);
+        if (const char* e = test_env("IDIST_FILTER_INLINE")) k.inl = e[0] != '0' ? 1 : 0;
         if (const char* e = test_env("IDIST_FILTER_WAVES")) k.filter_waves = atoi(e) == 3 ? 3u : 2u;
         if (const char* e = test_env("IDIST_VISITED")) { k.vis_bitmap = e[0] == 'b'; k.vis_onchip = e[0] == 'o'; }
         if (const char* e = test_env("IDIST_NO_ZERO_COPY")) k.no_zero_copy = e[0] != '0';
@@ -367,7 +373,7 @@ struct idist_search_ctx {
     uint32_t slots = 0;            // query slots currently backed by a visited bitmap
     VisGeom vis{};
     uint32_t* d_visited = nullptr; // [slots][vis.slot_words], all-zero between launches
-    uint32_t* d_next = nullptr;    // [0] queue head, [1] status, [2] completion count, [16..19] the reject filter's two 64-bit counters
+    uint32_t* d_next = nullptr;    // [0] queue head, [1] status, [2] completion count, [16..27] the reject filter's six 64-bit counters
     uint32_t queue_base = 0;       // value of the queue head before the next launch (it is never reset: each launch of nq queries on
                                    // g workgroups moves it by nq + g, unsigned wrap-around included)
     // narrow host-pointer batches (the reference's one query per call): query and results cross PCIe through one pinned,
@@ -1729,6 +1735,39 @@ idist_status filter_principal_ensure(const idist_index* ix, const std::vector<fl
     if (take) ix->filt_format.store(IDIST_FILTER_FORMAT_PRINCIPAL, std::memory_order_relaxed);
     return IDIST_OK;
 }
+// The principal rows stored with the adjacency (IndexView::inl): block i = filt_p.rows[id] of the ids in zero row i.  Made at the
+// first wide search of an index whose thin walks read the principal rows; 64 times the principal table, so above kFilterInlineCapBytes
+// — or when the allocation fails — the index keeps none and its walks read filt_p as before: not an error.
+// The cap: 1M points take 4.1 GB (the benchmark's index), the 2M an 8-GiB cap admits are where the table still leaves most of a 288-GB
+// card to rows of 1.2 KB each and their graph; beyond it the gain of one round trip per expansion is not worth a memory footprint
+// four times the rows' own.  (IDIST_FILTER_INLINE_CAP=<bytes>: test build.)
+constexpr uint64_t kFilterInlineCapBytes = 8ull << 30;
+constexpr bool kFilterInlinePolicy = true;
+idist_status filter_inline_ensure(const idist_index* ix) {
+    if (ix->filt_inl_state.load(std::memory_order_acquire) != 0) return IDIST_OK;
+    std::lock_guard<std::mutex> lk(ix->filt_mu);
+    if (ix->filt_inl_state.load(std::memory_order_acquire) != 0) return IDIST_OK;
+    HIPCHK(hipSetDevice(ix->device));
+    uint64_t cap = kFilterInlineCapBytes;
+    if (const char* e = test_env("IDIST_FILTER_INLINE_CAP")) cap = strtoull(e, nullptr, 10);
+    const uint64_t bytes = (uint64_t)ix->n * idist::kInlineBlockBytes;
+    uint8_t* blocks = nullptr;
+    if (!ix->filt_p.rows || ix->filt_p.fstride != 64u || bytes > cap || hipMalloc((void**)&blocks, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        ix->filt_inl_state.store(2, std::memory_order_release);
+        return IDIST_OK;
+    }
+    const uint32_t grid = std::min<uint32_t>(ix->n, (uint32_t)ix->n_cu * 32u);
+    IDIST_LAUNCH(filter_inline_kernel, grid, 64, 0, nullptr, ix->d_zero, ix->filt_p.rows, ix->n, blocks);
+    if (hipDeviceSynchronize() != hipSuccess) {
+        const hipError_t e = hipGetLastError();
+        hipFree(blocks);
+        return fail(IDIST_ERR_HIP, "filter_inline_kernel failed: %s", hipGetErrorString(e));
+    }
+    ix->filt_inl = blocks;
+    ix->filt_inl_state.store(1, std::memory_order_release);
+    return IDIST_OK;
+}
 bool filter_applies(const idist_index* ix) {
     return ix->n > 0 && (has_template_geometry(ix->L) || filt_stride(ix->L.stride) <= 128u * (uint32_t)kFiltRtChunksFat);
 }
@@ -1899,6 +1938,10 @@ idist_status launch_search(const idist_index* ix, idist_search_ctx* ctx, const f
         else fw = 1;
     }
     const bool thin = fw > 1;
+    // ... two of them per SIMD on the principal rows read those rows from the blocks stored with the adjacency, where the index has them
+    const bool want_inline = thin && principal_rows && fw == 2u && (ctx->knobs.inl >= 0 ? ctx->knobs.inl == 1 : kFilterInlinePolicy);
+    if (want_inline) CHK(filter_inline_ensure(ix));
+    const bool inlined = want_inline && ix->filt_inl_state.load(std::memory_order_acquire) == 1;
     a.tab_log2 = tab_log2;
     // the set stores 16-bit quotients (twice the ids in the same LDS) whenever n allows it: up to 33M points with 32 KB
     a.ubits = on_chip ? q16_universe_bits(ix->n, tab_log2) : 0u;
@@ -1963,11 +2006,12 @@ idist_status launch_search(const idist_index* ix, idist_search_ctx* ctx, const f
     if (!thin && !fat_filtered) view.f = FilterView{};
     const bool principal = thin && principal_rows;
     if (principal) { view.f2 = view.f; view.f = ix->filt_p; }       // (f2: the identity rows, for the queries the basis does not fit)
+    if (inlined) view.inl = ix->filt_inl;
     a.queue_base = ctx->queue_base;
     a.status_host = status_host && grid <= idist_search_ctx::kIoStatusSlots ? status_host : nullptr;
     a.done_host = done_host;
     a.done_count = ctx->d_next + 2;
-    a.filt_counts = reinterpret_cast<unsigned long long*>(ctx->d_next + 16);       // [4]: + the share of both on the principal rows
+    a.filt_counts = reinterpret_cast<unsigned long long*>(ctx->d_next + 16);       // [6]: + the share of both on the principal rows, + the inlined blocks
     a.done_seq = done_seq;
     if (grid_out) *grid_out = grid;
     const uint32_t slot = (uint32_t)(ctx->n_launch % IDIST_EVENT_RING);
@@ -2007,6 +2051,8 @@ idist_status launch_search(const idist_index* ix, idist_search_ctx* ctx, const f
             IDIST_LAUNCH(kS, grid, 256, smem, stream, view, a);                                    \
         } else if (thin && principal && fw == 3u) {                                                \
             launched = SearchLaunch<NB_, RS_, TAIL_, walk_thin_filter_principal(3), GeoKernels<NB_>::thin_search && kPrincipalWaves3>::go(grid, smem, stream, view, a); \
+        } else if (thin && principal && inlined) {                                                 \
+            launched = SearchLaunch<NB_, RS_, TAIL_, walk_thin_filter_inline(2), GeoKernels<NB_>::thin_search>::go(grid, smem, stream, view, a); \
         } else if (thin && principal) {                                                            \
             launched = SearchLaunch<NB_, RS_, TAIL_, walk_thin_filter_principal(2), GeoKernels<NB_>::thin_search>::go(grid, smem, stream, view, a); \
         } else if (thin) {                                                                         \
@@ -2287,6 +2333,7 @@ idist_status idist_index_get_info(const idist_index* idx, idist_index_info* out)
         if (idx->filt_p_state.load(std::memory_order_acquire) == 1) {       // (the format is decided: nothing below is written again)
             out->filter_format = idx->filt_format.load(std::memory_order_relaxed);
             out->filter_principal_bytes = idx->filt_p.rows ? (uint64_t)idx->n * idx->filt_p.fstride : 0u;
+            if (idx->filt_inl_state.load(std::memory_order_acquire) == 1) out->filter_inline_bytes = (uint64_t)idx->n * idist::kInlineBlockBytes;
         }
     }
     return IDIST_OK;
@@ -2322,6 +2369,7 @@ void idist_index_free(idist_index* idx) {
     hipFree(const_cast<uint8_t*>(idx->filt_p.rows));
     hipFree(const_cast<float*>(idx->filt_p.basis));
     hipFree(const_cast<float*>(idx->filt_p.mu));
+    hipFree(idx->filt_inl);
     delete idx;
 }
 
@@ -2456,6 +2504,16 @@ idist_status idist_search_ctx_filter_principal_counts(idist_search_ctx* ctx, uin
     if (reset) HIPCHK(hipMemset(ctx->d_next + 20, 0, sizeof(c)));
     if (examined) *examined = c[0];
     if (rejected) *rejected = c[1];
+    return IDIST_OK;
+}
+
+idist_status idist_search_ctx_filter_inline_counts(idist_search_ctx* ctx, uint64_t* blocks_requested, uint64_t* blocks_used, int32_t reset) {
+    if (!ctx) return fail(IDIST_ERR_INVALID_ARG, "ctx is null");
+    unsigned long long c[2] = {0, 0};
+    HIPCHK(hipMemcpy(c, ctx->d_next + 24, sizeof(c), hipMemcpyDeviceToHost));
+    if (reset) HIPCHK(hipMemset(ctx->d_next + 24, 0, sizeof(c)));
+    if (blocks_requested) *blocks_requested = c[0];
+    if (blocks_used) *blocks_used = c[1];
     return IDIST_OK;
 }
 

@@ -94,6 +94,8 @@ struct IndexView {
     uint32_t metric;          // 0 = squared L2, 1 = L2
     FilterView f;             // compact copy of the rows for the walk's reject filter (search kernels only)
     FilterView f2;            // principal walks: f is the principal table, f2 the identity one for the queries the basis does not fit
+    const uint8_t* inl = nullptr;   // [n][64][64 B] or nullptr: block i = the principal rows of the ids in zero row i, in slot order — byte copies of
+                                    // f.rows[id], zero at and behind the first INVALID (inlined thin principal walks, kWalkInlineBit)
 };
 
 // natural element of stored position `pos` (inverse of blocked_pos)
@@ -654,6 +656,25 @@ constexpr int walk_thin_filter(int waves = 2) {  // the walk code of a thin filt
 constexpr int kWalkPrincipalBit = 1 << 21;
 constexpr bool walk_principal(int code) { return (code & kWalkPrincipalBit) != 0; }
 constexpr int walk_thin_filter_principal(int waves = 2) { return walk_thin_filter(waves) | kWalkPrincipalBit; }
+// ... with the neighbours' principal rows stored with the adjacency (bit 22, IndexView::inl): the compact rows of an expansion are ONE
+// 4-KB block whose address is known with the candidate's id — requested together with its adjacency row, one dependent round trip less
+constexpr int kWalkInlineBit = 1 << 22;
+constexpr bool walk_inline(int code) { return (code & kWalkInlineBit) != 0; }
+constexpr int walk_thin_filter_inline(int waves = 2) { return walk_thin_filter_principal(waves) | kWalkInlineBit; }
+constexpr uint32_t kInlineBlockBytes = 64u * 64u;
+// An inlined kernel decides ONCE per query which table serves it and runs the layers in one of two instantiations of search_layer
+// (bits 23 / 24, never a kernel's own code): in the principal one the identity form of the query is dead, which is what pays for the
+// prefetched block's sixteen registers (the per-expansion choice of the plain principal kernel keeps both forms live).
+constexpr int kWalkOnlyPrincipalBit = 1 << 23, kWalkOnlyIdentityBit = 1 << 24;
+constexpr bool walk_blocks(int code) { return walk_inline(code) && (code & kWalkOnlyIdentityBit) == 0; }
+template <int WALK, class FQ> __device__ __forceinline__ bool fq_principal(const FQ& fq) {
+    if constexpr ((WALK & kWalkOnlyPrincipalBit) != 0) return true;
+    else if constexpr ((WALK & kWalkOnlyIdentityBit) != 0) return false;
+    else return fq.principal;
+}
+#ifndef IDIST_INLINE_PF_TOP
+#define IDIST_INLINE_PF_TOP 0   // 1: the next block is requested beside the next adjacency row, at the top of an expansion; 0: once this
+#endif                          // expansion's block is consumed, just before its f32 pass (16 registers of block live instead of 32)
 // 128-B chunks of a compact row (8 lanes x 16 B each; the last one may be half a chunk)
 // WALK: the walk code of the kernel (runtime geometries only: the fat filtered walk's tile is larger than the thin one's)
 template <int NB, int RS, int TAIL, int WALK = 0>
@@ -853,6 +874,10 @@ struct FilterQDual : FilterQ<NCH, T8> {
     bool principal = false;
 };
 template <int NCH, bool T8>
+struct FilterQInline : FilterQDual<NCH, T8> {
+    mutable uint32_t blk_req = 0, blk_used = 0;   // inlined walks: blocks of IndexView::inl requested (wasted prefetches included) / tested
+};
+template <int NCH, bool T8>
 __device__ __forceinline__ void filter_stage_query(const IndexView& ix, const float* q, FilterQDual<NCH, T8>& fq) {
     filter_stage_query(ix, q, fq.p, ix.f);
     fq.principal = fq.p.on && fq.p.fits;
@@ -966,8 +991,9 @@ template <int NB, int RS, int TAIL, int WALK> struct FilterQPick {
     using type = FilterQ<filt_chunks<NB, RS, TAIL, WALK>(), filt_tail8<NB, RS, TAIL, WALK>()>;
 };
 template <int NB, int RS, int TAIL, int WALK> using FilterQFor =
+    std::conditional_t<walk_inline(WALK), FilterQInline<filt_chunks<NB, RS, TAIL, WALK & ~kWalkPrincipalBit>(), filt_tail8<NB, RS, TAIL, WALK & ~kWalkPrincipalBit>()>,
     std::conditional_t<walk_principal(WALK), FilterQDual<filt_chunks<NB, RS, TAIL, WALK & ~kWalkPrincipalBit>(), filt_tail8<NB, RS, TAIL, WALK & ~kWalkPrincipalBit>()>,
-                       typename FilterQPick<NB, RS, TAIL, WALK>::type>;
+                       typename FilterQPick<NB, RS, TAIL, WALK>::type>>;
 template <int NB, int RS, int TAIL, int WALK, class Mid = NoMid>
 __device__ __forceinline__ void dist_pass_filtered(const IndexView& ix, const float* q, const FilterQFor<NB, RS, TAIL, WALK>& fq,
                                                    uint32_t* act_pid, uint32_t* act_dist, int na, Mid mid, uint32_t thr_bits) {
@@ -980,7 +1006,7 @@ __device__ __forceinline__ void dist_pass_filtered(const IndexView& ix, const fl
             const float thr = __uint_as_float(thr_bits);
             const float st = ix.metric ? thr : __builtin_sqrtf(thr);
             if constexpr (walk_principal(WALK)) {
-                if (fq.principal) filter_rounds<1, true, filt_rounds<1, true, WALK>()>(ix, fq.p, act_pid, act_dist, na, st, mid);
+                if (fq_principal<WALK>(fq)) filter_rounds<1, true, filt_rounds<1, true, WALK>()>(ix, fq.p, act_pid, act_dist, na, st, mid);
                 // (the identity rows of the exceptional query two rounds of 8 rows at a time — one for the runtime geometries' five-chunk
                 //  tile — instead of the identity walk's eight: with all of them in flight the kernel needs 76 B of scratch at 300-d, which
                 //  every query pays for; as it stands 12 B are left, 96 B on runtime geometries: DESIGN.md §4.5)
@@ -1013,6 +1039,65 @@ __device__ __forceinline__ void dist_pass_filtered(const IndexView& ix, const fl
         }
     }
     dist_rounds_walk<NB, RS, TAIL, WALK>(ix, q, act_pid, act_dist, na, mid, thr_bits);
+}
+
+// One block of IndexView::inl in registers, in the lane mapping of filter_rounds<1, true, 8> with the row index being the slot: lane
+// (g, j) holds bytes 8 j .. 8 j + 7 of slot 8 r + g in r[r].  pid < ix.n (an entry of `nearest`).
+struct InlBlock { uint2 r[8]; };
+__device__ __forceinline__ void inline_block_load(const IndexView& ix, uint32_t pid, InlBlock& b) {
+    const int lane = lane_id();
+    const uint8_t* p = ix.inl + (size_t)pid * kInlineBlockBytes + 8u * (uint32_t)lane;          // (64 g + 8 j = 8 lane)
+#pragma unroll
+    for (int r = 0; r < 8; r++) b.r[r] = *reinterpret_cast<const uint2*>(p + 512u * (uint32_t)r);
+}
+// The verdicts of all 64 slots of a block, filter_rounds' arithmetic on the same bytes: true in lane s where slot s is PROVEN beyond
+// st.  Lane (g, j) finishes slot 8 j + g as there — its metadata are the last 8 bytes of that slot, in lane (g, 7) of round j — and
+// the verdicts are handed to the slots' own lanes through one ballot.  (Zero slots get a verdict nobody asks for.)
+__device__ __forceinline__ bool inline_verdicts(const IndexView& ix, const FilterQ<1, true>& fq, const InlBlock& b, float st) {
+    const int lane = lane_id();
+    const int g = lane >> 3, j = lane & 7;
+    uint32_t ah_f = 0u, al_f = 0u, ep = 0u, su = 0u;
+#pragma unroll
+    for (int r = 0; r < 8; r++) {
+        uint32_t ah = 0u, al = 0u;
+        ah = udot4(fq.ht.x, b.r[r].x, ah); al = udot4(fq.lt.x, b.r[r].x, al);
+        ah = udot4(fq.ht.y, b.r[r].y, ah); al = udot4(fq.lt.y, b.r[r].y, al);
+        ah = group_total_u32(ah);
+        al = group_total_u32(al);
+        const uint32_t m0 = (uint32_t)__shfl((int)b.r[r].x, lane | 7, 64), m1 = (uint32_t)__shfl((int)b.r[r].y, lane | 7, 64);
+        ah_f = j == r ? ah : ah_f;
+        al_f = j == r ? al : al_f;
+        ep = j == r ? m0 : ep;
+        su = j == r ? m1 : su;
+    }
+    const uint64_t A = ((uint64_t)ah_f << 8) + (uint64_t)al_f;
+    const uint64_t I = fq.sq + ((uint64_t)su << 16) - (A << 9);
+    const float dh = (float)I * ix.f.dscale;
+    const float t = (st + (__uint_as_float(ep) + fq.eq)) * ix.f.up;
+    const uint64_t m = __ballot(dh > t * t);                      // bit 8 g + j: slot 8 j + g
+    return ((m >> (8 * j + g)) & 1ull) != 0ull;
+}
+// dist_pass_filtered with the verdicts at hand (`rej`, per slot = per lane): the ids of the lanes in `in` (slot order), less the
+// rejected ones, go through the walk's f32 pass, `mid` runs while their rows are in flight; d = the canonical distance bits or
+// kAbandoned.  Counts and the switch-off test as there.
+template <int NB, int RS, int TAIL, int WALK, class Mid>
+__device__ __forceinline__ uint32_t dist_pass_inline(const IndexView& ix, const float* q, const FilterQFor<NB, RS, TAIL, WALK>& fq, uint32_t* act_pid,
+                                                     uint32_t* act_dist, bool in, uint32_t pid, bool rej, Mid mid) {
+    const int lane = lane_id();
+    const int na = __popcll(__ballot(in));
+    const bool keep = in && !rej;
+    const uint64_t km = __ballot(keep);
+    const int pos = __popcll(km & ((1ull << lane) - 1ull));
+    const int ns = __popcll(km);
+    if (keep) act_pid[pos] = pid;                                  // slot order is kept
+    wave_sync();
+    fq.seen += (uint32_t)na;
+    fq.rejected += (uint32_t)(na - ns);
+    if (fq.seen >= 1024u && fq.rejected * 4u < fq.seen) fq.on = false;
+    if (ns) dist_rounds_walk<NB, RS, TAIL, WALK>(ix, q, act_pid, act_dist, ns, mid);
+    else mid();
+    wave_sync();
+    return keep ? act_dist[pos] : kAbandoned;
 }
 
 // ---------------------------------------------------------------------------
@@ -2068,6 +2153,9 @@ __device__ __forceinline__ void search_layer(const IndexView& ix, const uint32_t
     constexpr bool kSpec = walk_quad(LAT) && walk_vis_lds(LAT) && PFA && NB >= 0;
     [[maybe_unused]] uint32_t sq_pid = kInvalid;          // the candidate whose row the helpers were given (wave-uniform)
     [[maybe_unused]] bool sq_off = false;                 // this layer met an id only the bitmap answers for: no more guesses
+    // inlined walks (kWalkInlineBit): the block of the candidate expected next, requested one expansion ahead like its adjacency row
+    [[maybe_unused]] InlBlock pf_blk{};
+    [[maybe_unused]] uint32_t pf_blk_pid = kInvalid;
     QP_DECL
     for (;;) {
         int ci = w_pop(st);                               // :599-604
@@ -2082,13 +2170,28 @@ __device__ __forceinline__ void search_layer(const IndexView& ix, const uint32_t
 
         // layer.nearest_iter(pid).take(links): stop at first INVALID (core/types.rs:183-187)
         uint32_t nb_pid = kInvalid;
+        // inlined walks: the zero layer of a query staged on the principal rows whose filter is still on reads its compact rows from
+        // the candidate's own block — the prefetched one when the guess was right, otherwise requested here, beside the adjacency row
+        [[maybe_unused]] bool inl_on = false;
+        [[maybe_unused]] InlBlock blk{};
+        if constexpr (walk_blocks(LAT)) inl_on = is_zero && ix.inl != nullptr && fq_principal<LAT>(fq) && fq.on;
         if constexpr (PFA) {
             if (cpid == pf_pid) nb_pid = pf_row;
             else if (row_lane) nb_pid = rows[(size_t)cpid * row_stride + lane];
+            if constexpr (walk_blocks(LAT)) {
+                if (inl_on) {
+                    if (cpid == pf_blk_pid) blk = pf_blk;
+                    else { inline_block_load(ix, cpid, blk); fq.blk_req++; }
+                }
+                pf_blk_pid = kInvalid;
+            }
             const int c2 = w_peek_next(st, ci);
             pf_pid = c2 >= 0 ? (uint32_t)st.W[c2] : kInvalid;
             pf_row = kInvalid;
             if (pf_pid != kInvalid && row_lane) pf_row = rows[(size_t)pf_pid * row_stride + lane];
+            if constexpr (walk_blocks(LAT) && IDIST_INLINE_PF_TOP) {
+                if (inl_on && pf_pid != kInvalid) { inline_block_load(ix, pf_pid, pf_blk); pf_blk_pid = pf_pid; fq.blk_req++; }
+            }
         } else {
             if (row_lane) nb_pid = rows[(size_t)cpid * row_stride + lane];
         }
@@ -2163,34 +2266,68 @@ __device__ __forceinline__ void search_layer(const IndexView& ix, const uint32_t
             const bool sure = ok_nb && stt == kQRoom, maybe = ok_nb && stt == kQFull;
             if constexpr (kSpec) { if (__ballot(maybe)) sq_off = true; }
             const uint64_t sm = __ballot(sure);
+            // inlined walks: the verdicts of all 64 slots from the block's registers, against the threshold as the expansion began —
+            // for both passes below; then the next candidate's block is requested (this one's registers are free)
+            [[maybe_unused]] bool have_v = false, rej = false;
+            if constexpr (walk_blocks(LAT)) {
+                if (inl_on && thr_bits != 0xFFFFFFFFu && __ballot(sure || maybe)) {
+                    const float thr = __uint_as_float(thr_bits);
+                    rej = inline_verdicts(ix, fq.p, blk, ix.metric ? thr : __builtin_sqrtf(thr));
+                    have_v = true;
+                    fq.blk_used++;
+                }
+                if constexpr (!IDIST_INLINE_PF_TOP) {
+                    if (inl_on && pf_pid != kInvalid) { inline_block_load(ix, pf_pid, pf_blk); pf_blk_pid = pf_pid; fq.blk_req++; }
+                }
+            }
             wave_sync();
             if (sm) {
-                const int my = __popcll(sm & ((1ull << lane) - 1ull));
-                if (sure) act_pid[my] = nb_pid;                                         // keeps slot order
-                wave_sync();
                 auto mid = [&]() {
                     if (sure && q16_insert(vis, nb_pid, tab_idx) == kQFull) {           // filled up by this very expansion
                         atomicOr(&vis.bits[nb_pid >> 5], vbit);
                         visited_note(vis, nb_pid);
                     }
                 };
-                if constexpr (walk_quad(LAT)) quad_dist_pass<NB, RS, TAIL>(ix, q, *quad, act_pid, act_dist, __popcll(sm), mid);
-                else dist_pass_filtered<NB, RS, TAIL, LAT>(ix, q, fq, act_pid, act_dist, __popcll(sm), mid, thr_bits);
-                wave_sync();
-                if (sure) my_d = act_dist[my];
+                bool done = false;
+                if constexpr (walk_blocks(LAT)) {
+                    if (have_v && fq.on) {
+                        const uint32_t d = dist_pass_inline<NB, RS, TAIL, LAT>(ix, q, fq, act_pid, act_dist, sure, nb_pid, rej, mid);
+                        if (sure) my_d = d;
+                        done = true;
+                    }
+                }
+                if (!done) {
+                    const int my = __popcll(sm & ((1ull << lane) - 1ull));
+                    if (sure) act_pid[my] = nb_pid;                                     // keeps slot order
+                    wave_sync();
+                    if constexpr (walk_quad(LAT)) quad_dist_pass<NB, RS, TAIL>(ix, q, *quad, act_pid, act_dist, __popcll(sm), mid);
+                    else dist_pass_filtered<NB, RS, TAIL, LAT>(ix, q, fq, act_pid, act_dist, __popcll(sm), mid, thr_bits);
+                    wave_sync();
+                    if (sure) my_d = act_dist[my];
+                }
             }
             const bool late = maybe && (vold & vbit) == 0u;
             if (late) visited_note(vis, nb_pid);
             const uint64_t lm = __ballot(late);
             wave_sync();
             if (lm) {
-                const int my = __popcll(lm & ((1ull << lane) - 1ull));
-                if (late) act_pid[my] = nb_pid;
-                wave_sync();
-                if constexpr (walk_quad(LAT)) quad_dist_pass<NB, RS, TAIL>(ix, q, *quad, act_pid, act_dist, __popcll(lm));
-                else dist_pass_filtered<NB, RS, TAIL, LAT>(ix, q, fq, act_pid, act_dist, __popcll(lm), NoMid(), thr_bits);
-                wave_sync();
-                if (late) my_d = act_dist[my];
+                bool done = false;
+                if constexpr (walk_blocks(LAT)) {
+                    if (have_v && fq.on) {                                              // (the first pass may have switched the filter off)
+                        const uint32_t d = dist_pass_inline<NB, RS, TAIL, LAT>(ix, q, fq, act_pid, act_dist, late, nb_pid, rej, NoMid());
+                        if (late) my_d = d;
+                        done = true;
+                    }
+                }
+                if (!done) {
+                    const int my = __popcll(lm & ((1ull << lane) - 1ull));
+                    if (late) act_pid[my] = nb_pid;
+                    wave_sync();
+                    if constexpr (walk_quad(LAT)) quad_dist_pass<NB, RS, TAIL>(ix, q, *quad, act_pid, act_dist, __popcll(lm));
+                    else dist_pass_filtered<NB, RS, TAIL, LAT>(ix, q, fq, act_pid, act_dist, __popcll(lm), NoMid(), thr_bits);
+                    wave_sync();
+                    if (late) my_d = act_dist[my];
+                }
             }
             fresh = sure || late;                                                       // (ids that went to the bitmap have no index)
             na = __popcll(sm) + __popcll(lm);

@@ -110,6 +110,31 @@ __global__ __launch_bounds__(64) void filter_rows_principal_kernel(IndexView ix,
     }
 }
 
+// IndexView::inl: block i = the 64-byte principal rows of the ids in zero row i, in slot order, zero at and behind the first INVALID
+// (and for an id beyond n, which the walk reports and never looks up).  One wave per block: a 64-B gather per slot, eight slots per
+// lane group in flight, then 4 KB of contiguous stores.
+__global__ __launch_bounds__(64) void filter_inline_kernel(const uint32_t* __restrict__ zero, const uint8_t* __restrict__ rows, uint32_t n,
+                                                           uint8_t* __restrict__ out) {
+    const int lane = lane_id();
+    const int g = lane >> 3;
+    for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
+        const uint32_t id = zero[(size_t)i * kM2 + (uint32_t)lane];
+        const uint64_t inval = __ballot(id == kInvalid);
+        const int nvalid = inval ? __builtin_ctzll(inval) : 64;
+        uint2 v[8];
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            const int slot = 8 * r + g;
+            const uint32_t sid = (uint32_t)__shfl((int)id, slot, 64);
+            v[r] = make_uint2(0u, 0u);
+            if (slot < nvalid && sid < n) v[r] = *reinterpret_cast<const uint2*>(rows + (size_t)sid * 64u + 8u * (uint32_t)(lane & 7));
+        }
+        uint8_t* dst = out + (size_t)i * kInlineBlockBytes + 8u * (uint32_t)lane;
+#pragma unroll
+        for (int r = 0; r < 8; r++) *reinterpret_cast<uint2*>(dst + 512u * (uint32_t)r) = v[r];
+    }
+}
+
 // UpperNode::from_zero for a whole layer, core/lib.rs:323-328, core/types.rs:66-70
 __global__ void snapshot_kernel(const uint32_t* __restrict__ zero, uint32_t* __restrict__ upper_rows, uint32_t rows) {
     const size_t total = (size_t)rows * kM;
@@ -250,7 +275,8 @@ struct SearchArgs {
     uint32_t* done_host;
     uint32_t* done_count;
     uint32_t done_seq;
-    unsigned long long* filt_counts;   // [4] device words of the context: candidates the reject filter examined / rejected, and the part of both on principal rows
+    unsigned long long* filt_counts;   // [6] device words of the context: candidates the reject filter examined / rejected, the part of both on principal rows,
+                                       // blocks of IndexView::inl requested / tested (idist_search_ctx_filter_inline_counts)
 };
 // the LDS tail region (after the dirty-block bitmap) holds the Bloom filter or the on-chip visited set
 __device__ __forceinline__ void visited_attach_tab(Visited& v, uint32_t* mem, uint32_t log2_entries) {
@@ -276,6 +302,32 @@ __device__ __forceinline__ void visited_attach_q16(Visited& v, uint32_t log2_ent
     v.ubits = ubits;
     v.rbits = ubits - (log2_entries - 2u);
     v.tlimit = 0xFFFFFFFFu;                            // never frozen: single ids overflow to the bitmap
+}
+
+// Search::search of one staged query, entry point to zero layer (core/lib.rs:357-379), for the kernels that run it in more than one
+// instantiation of search_layer (kWalkInlineBit): search_kernel's own steps, LAT the instantiation's code.
+template <int NB, int RS, int TAIL, int LAT>
+__device__ __forceinline__ void search_layers(const IndexView& ix, const SearchArgs& a, const Smem& sm, WState& st, Visited& vis, Counters& ctr,
+                                              QuadLead& ql, const FilterQFor<NB, RS, TAIL, LAT>& fq) {
+    const int lane = lane_id();
+    DistLog nolog{nullptr, 0u};
+    push_entry<NB, RS, TAIL>(ix, sm.q, st, vis, sm.act_pid, sm.act_dist, ctr, nolog);
+    for (int cur = (int)ix.n_upper;; cur--) {
+        const bool is_zero = cur == 0;
+        st.ef = is_zero ? (int)a.ef : 1;
+        if (is_zero) {
+            search_layer<NB, RS, TAIL, LAT>(ix, ix.zero, kM2, kM2, sm.q, st, vis, sm.act_pid, sm.act_dist, ctr, true, nolog, &ql, fq);
+            break;
+        }
+        const uint32_t* rows = ix.upper + (size_t)ix.layer_off[cur - 1] * kM;
+        search_layer<NB, RS, TAIL, LAT>(ix, rows, kM, kM, sm.q, st, vis, sm.act_pid, sm.act_dist, ctr, false, nolog, &ql, fq);
+        w_cull(st);
+        visited_clear(vis);
+        visited_begin(vis, (uint32_t)st.plen);
+        for (int i = lane; i < st.plen; i += 64) visited_mark(vis, (uint32_t)st.W[i]);
+        visited_added(vis, (uint32_t)st.plen);
+        wave_sync();
+    }
 }
 
 // LAT: walk mode (kWalkClassic / kWalkLatency / kWalkOverlap, see search_layer).
@@ -337,6 +389,10 @@ __global__ __launch_bounds__(walk_quad(LAT) ? 256 : 64) IDIST_WAVES_ATTR(LAT) vo
         Counters ctr{0, 0, 0};
         DistLog nolog{nullptr, 0u};
         // search.reset(), :357: the visited set was emptied when the slot's previous search ended
+        if constexpr (walk_inline(LAT)) {
+            if (fq.principal) search_layers<NB, RS, TAIL, LAT | kWalkOnlyPrincipalBit>(ix, a, sm, st, vis, ctr, ql, fq);
+            else search_layers<NB, RS, TAIL, LAT | kWalkOnlyIdentityBit>(ix, a, sm, st, vis, ctr, ql, fq);
+        } else {
         push_entry<NB, RS, TAIL>(ix, sm.q, st, vis, sm.act_pid, sm.act_dist, ctr, nolog);  // :364
         for (int cur = (int)ix.n_upper;; cur--) {                      // :365
             const bool is_zero = cur == 0;
@@ -353,6 +409,7 @@ __global__ __launch_bounds__(walk_quad(LAT) ? 256 : 64) IDIST_WAVES_ATTR(LAT) vo
             for (int i = lane; i < st.plen; i += 64) visited_mark(vis, (uint32_t)st.W[i]);
             visited_added(vis, (uint32_t)st.plen);
             wave_sync();
+        }
         }
         const int cnt = st.plen < st.ef ? st.plen : st.ef;             // search.iter(), :382
         for (uint32_t i = lane; i < a.ef; i += 64) {
@@ -385,6 +442,12 @@ __global__ __launch_bounds__(walk_quad(LAT) ? 256 : 64) IDIST_WAVES_ATTR(LAT) vo
                         atomicAdd(&a.filt_counts[2], (unsigned long long)fq.seen);
                         atomicAdd(&a.filt_counts[3], (unsigned long long)fq.rejected);
                     }
+                }
+            }
+            if constexpr (walk_inline(LAT)) {
+                if (lane == 0 && fq.blk_req) {
+                    atomicAdd(&a.filt_counts[4], (unsigned long long)fq.blk_req);
+                    atomicAdd(&a.filt_counts[5], (unsigned long long)fq.blk_used);
                 }
             }
         }

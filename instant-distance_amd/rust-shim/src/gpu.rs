@@ -51,7 +51,7 @@ struct IdistIndexInfo {     // idist_index_info
     n: u32, dim: u32, row_stride: u32, n_upper: u32, ef_search: u32, metric: i32, device: i32,
     layer_len: [u32; IDIST_MAX_LAYERS], tie_capacity: u32,
     dot_bound: f32,   // Metric::Dot: the S in use; 0 otherwise
-    filter_format: i32, filter_bytes: u64, filter_principal_bytes: u64,   // the reject filter's tables
+    filter_format: i32, filter_bytes: u64, filter_principal_bytes: u64, filter_inline_bytes: u64,   // the reject filter's tables
 }
 
 extern "C" {
