@@ -566,6 +566,61 @@ idist_status idist_search_ctx_range_fetch(idist_search_ctx* ctx, uint32_t* out_p
  * IDIST_KERNEL_EVENTS=0.  The rungs' own search kernels are in idist_search_ctx_kernel_times. */
 idist_status idist_search_ctx_range_kernel_ms(idist_search_ctx* ctx, float* select_ms, float* scan_ms, float* sort_ms);
 
+/* Range search over a partitioned index: the range search above on every part, merged on the device.
+ * DEFINITION: row q is the merge, by the u64 key  raw distance bits << 32 | global id, of what idist_search_batch_range returns for
+ * query q on every non-empty part, global id = base[p] + PointId.  Every part gets the same radius[q] and the same max_rungs.  So:
+ *   - every part climbs its own ladder and ends in its own exact scan, as in idist_partitioned_search_batch_allowed_sets; a part's
+ *     list is already ascending in that key and keys of different parts are distinct; "within" is the definition above, unchanged,
+ *     decided by the parts;
+ *   - reported distances are report(d) of the merged raw distances, applied once, after the merge, with that query's own term (DOT:
+ *     s(q) + S, every part holds the same S): the bits equal what the single index reports for the same raw distance;
+ *   - out_lims [nq + 1], lims[0] = 0: query q owns [lims[q], lims[q + 1]) of the flat pid (GLOBAL ids) and distance arrays
+ *     idist_partitioned_range_fetch hands out, nearest first;
+ *   - out_rung[q * n_parts + p] = part p's rung for query q, IDIST_RUNG_NONE for an empty part; out_counters = the parts' counters
+ *     summed (both may be NULL);
+ *   - max_total bounds the merged total lims[nq]; every part is given the same bound (its own total can never legitimately exceed
+ *     it) and the merged total is checked again.  Beyond it: IDIST_ERR_INVALID_ARG, the message says how many results were known
+ *     (a part's message is prefixed "part <p> (device <d>): "), and no results are held;
+ *   - a NaN radius is IDIST_ERR_INVALID_ARG with the query named; nq == 0: lims[0] = 0; no points at all, or ef_search == 0: every count
+ *     0, every rung IDIST_RUNG_NONE, every counter 0;
+ *   - IDIST_ERR_TIE_OVERFLOW never reaches the caller; a part's failure on rung 0 is returned with the prefix above.
+ * With max_rungs == 0 the answer is every point of the whole set within the radius, ordered by (raw distance bits, global id): what
+ * one exact scan over all rows gives.  One part is the identity: every output equals idist_search_batch_range on that part.
+ * The queries are uploaded once per distinct device; the parts' searches block on the host once per rung, so the parts run side by
+ * side, one host thread per non-empty part for the duration of the call.  The merge reads the lists of the parts on the merge device
+ * where their contexts hold them (completion order, a per-query offset and count); parts elsewhere send keys, offsets and counts by
+ * peer copies.  Work is divided by results, not by queries; up to 64 lists; no size cap but max_total.  ONE read-back of the merged
+ * total precedes the merge.  The results are held by p until the next range call through it or until they are fetched.
+ * Host pointers; blocks until done; p is used by one thread at a time.  Out of scope: device-pointer / stream variants,
+ * idist_search_batch_sharded and a restricted range search. */
+idist_status idist_partitioned_search_batch_range(idist_partitioned* p, const float* queries, uint32_t nq,
+                                                  const float* radius, uint32_t n_radius, int32_t max_rungs, uint64_t max_total,
+                                                  uint64_t* out_lims,        /* nq + 1 */
+                                                  uint32_t* out_rung,        /* [nq][n_parts] or NULL */
+                                                  uint32_t* out_counters);   /* nq*3 or NULL */
+/* The results of the last successful idist_partitioned_search_batch_range through p: out_pid (global ids) / out_dist [lims[nq]] each
+ * (may be NULL when that is 0).  The rules of idist_search_ctx_range_fetch: handed out once; a second fetch, or one with nothing held,
+ * is IDIST_ERR_INVALID_ARG. */
+idist_status idist_partitioned_range_fetch(idist_partitioned* p, uint32_t* out_pid, float* out_dist);
+/* HIP-event duration (ms) of the counts, prefix-sum and merge kernels of the last idist_partitioned_search_batch_range through p
+ * (0 when it had nothing to find); IDIST_ERR_INVALID_ARG before the first one.  The parts' own kernels:
+ * idist_partitioned_last_search_kernel_ms. */
+idist_status idist_partitioned_last_range_merge_ms(idist_partitioned* p, float* ms);
+/* The counts and merge kernels behind it on their own, on caller-made lists in the memory of `device` (the role
+ * idist_merge_topk_device plays for the top-k merge).  d_keys / d_off / d_cnt: HOST arrays of n_lists (1..64) device pointers.  List l
+ * holds for query q the d_cnt[l][q] (u32) keys  raw distance bits << 32 | local id  (u64) at d_keys[l] + d_off[l][q] (u64 offsets, in
+ * keys, in any order of the queries), ascending; its global ids are base[l] + local id (< 2^32 - 1), so that the keys of different
+ * lists are distinct.  The counts rule: nothing beyond a list's count is read, and a list that is empty for every query may have a
+ * NULL d_keys[l].  d_lims [nq + 1] (u64) receives the prefix sum of the merged counts, *out_total its last entry; d_out_pid /
+ * d_out_dist [capacity]: query q's merged keys at [lims[q], lims[q + 1]) as global ids and as report(d) for `metric` (IDIST_METRIC_DOT:
+ * d_sq [nq] holds s(q), dot_bound is S; else d_sq may be NULL).  *out_total > capacity: IDIST_ERR_INVALID_ARG and nothing is written
+ * to the output arrays; nothing is ever written beyond lims[nq].  The call waits for `hip_stream` (a hipStream_t, may be NULL) once,
+ * to read the total back; the merge itself is enqueued without synchronising. */
+idist_status idist_range_merge_device(const void* const* d_keys, const void* const* d_off, const void* const* d_cnt,
+                                      uint32_t n_lists, uint32_t nq, const uint32_t* base, int32_t metric, const void* d_sq,
+                                      float dot_bound, uint64_t capacity, void* d_lims, void* d_out_pid, void* d_out_dist,
+                                      uint64_t* out_total, int32_t device, void* hip_stream);
+
 /* Point::distance for id lists (core/lib.rs:780-782 as used at :709-710): out[q][i] =
  * distance(queries[q], points[ids[q][i]]) for i < n_ids; IDIST_INVALID ids give +inf.
  * Host pointers. The batched gather-L2 kernel on its own. */

@@ -156,6 +156,11 @@ SYMBOLS = {
     "idist_search_batch_range": (C.c_int32, [_vp, _vp, _f32p, C.c_uint32, _f32p, C.c_uint32, C.c_int32, C.c_uint64, _u64p, _u32p, _u32p]),
     "idist_search_ctx_range_fetch": (C.c_int32, [_vp, _u32p, _f32p]),
     "idist_search_ctx_range_kernel_ms": (C.c_int32, [_vp, _f32p, _f32p, _f32p]),
+    "idist_partitioned_search_batch_range": (C.c_int32, [_vp, _f32p, C.c_uint32, _f32p, C.c_uint32, C.c_int32, C.c_uint64, _u64p, _u32p, _u32p]),
+    "idist_partitioned_range_fetch": (C.c_int32, [_vp, _u32p, _f32p]),
+    "idist_partitioned_last_range_merge_ms": (C.c_int32, [_vp, C.POINTER(C.c_float)]),
+    "idist_range_merge_device": (C.c_int32, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.c_uint32, C.c_uint32, _u32p, C.c_int32, _vp,
+                                             C.c_float, C.c_uint64, _vp, _vp, _vp, C.POINTER(C.c_uint64), C.c_int32, _vp]),
     "idist_partitioned_search_batch_allowed_sets": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, _u32p, C.c_uint32, C.c_int32,
                                                                 _u32p, _f32p, _u32p, _u32p, _u32p]),
     "idist_partitioned_last_allowed_slice_ms": (C.c_int32, [_vp, C.POINTER(C.c_float)]),

@@ -10,6 +10,7 @@
 #include "idist_dot.hpp"
 #include "idist_allowed.hpp"
 #include "idist_range.hpp"
+#include "idist_range_merge.hpp"
 #include "idist_basis.hpp"
 
 #ifndef IDIST_EMU
@@ -467,6 +468,11 @@ struct idist_partitioned {
         uint32_t *r_pid = nullptr, *r_cnt = nullptr, *r_ctr = nullptr;
         float* r_dist = nullptr;
         size_t r_cap_pid = 0, r_cap_dist = 0, r_cap_cnt = 0, r_cap_ctr = 0;
+        // range search, a part away from the merge device: its keys, offsets, counts and counters ON the merge device (peer copies on
+        // the part's stream); a part on the merge device is read where its context holds them
+        uint64_t *m_keys = nullptr, *m_off = nullptr;
+        uint32_t *m_cnt = nullptr, *m_ctr = nullptr;
+        size_t m_cap_keys = 0, m_cap_off = 0, m_cap_cnt = 0, m_cap_ctr = 0;
     };
     struct Dev {
         int32_t device = 0;
@@ -474,6 +480,8 @@ struct idist_partitioned {
         size_t cap_q = 0;
         uint32_t* d_setof = nullptr;         // restricted search: the set of every query, uploaded once per distinct device
         size_t cap_setof = 0;
+        float* d_sq = nullptr;               // range search over DOT parts: s(q) of the batch's queries (the parts' limits need the report's term)
+        size_t cap_sq = 0;
     };
     std::vector<Part> parts;
     std::vector<Dev> devs;
@@ -490,6 +498,15 @@ struct idist_partitioned {
     uint32_t* s_rung = nullptr;              // restricted search: the parts' rungs [P][nq]
     size_t cap_s_rung = 0;
     float al_slice_ms = 0.0f;                // ... and the host time its last call spent on the bitmaps: upload + slice, every part
+    // range search, on the merge device: the merged counts, lims and the chunk sums of their prefix sum; the merged result, which no
+    // other call writes and idist_partitioned_range_fetch hands out once
+    uint32_t *rm_c = nullptr, *rm_opid = nullptr;
+    uint64_t *rm_lims = nullptr, *rm_chunks = nullptr;
+    float* rm_odist = nullptr;
+    size_t cap_rm_c = 0, cap_rm_lims = 0, cap_rm_chunks = 0, cap_rm_opid = 0, cap_rm_odist = 0;
+    bool rg_valid = false;                   // a successful range call's results are held (until the next one, or the fetch)
+    uint64_t rg_total = 0;
+    float rg_merge_ms = -1.0f;               // the last range call's counts, prefix and merge kernels (-1: none has run)
     hipStream_t stream = nullptr;            // the merge and the copies of its result
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
@@ -3064,8 +3081,10 @@ void idist_partitioned_free(idist_partitioned* p) {
     for (auto& pt : p->parts) {
         idist_search_ctx_free(pt.ctx);
         hipFree(pt.r_pid); hipFree(pt.r_dist); hipFree(pt.r_cnt); hipFree(pt.r_ctr);
+        hipFree(pt.m_keys); hipFree(pt.m_off); hipFree(pt.m_cnt); hipFree(pt.m_ctr);
     }
-    for (auto& dv : p->devs) { hipFree(dv.d_q); hipFree(dv.d_setof); }
+    for (auto& dv : p->devs) { hipFree(dv.d_q); hipFree(dv.d_setof); hipFree(dv.d_sq); }
+    hipFree(p->rm_c); hipFree(p->rm_lims); hipFree(p->rm_chunks); hipFree(p->rm_opid); hipFree(p->rm_odist);
     hipFree(p->d_qm); hipFree(p->d_sq); hipFree(p->s_rung);
     hipFree(p->s_pid); hipFree(p->s_dist); hipFree(p->s_cnt); hipFree(p->s_ctr);
     hipFree(p->o_pid); hipFree(p->o_dist); hipFree(p->o_cnt); hipFree(p->o_ctr);
@@ -3146,8 +3165,8 @@ static idist_status partitioned_merge(idist_partitioned* p, uint32_t nq, uint32_
 
 // The batch's queries, once per distinct device that has something to search, as the parts' launches read them (prepared = true):
 // Dev::d_q holds the [nq][kdim] rows in front (a metric whose prepare cannot run in place: followed by the queries as uploaded).
-// Leaves another device current.
-static idist_status partitioned_upload_queries(idist_partitioned* p, const float* queries, uint32_t nq) {
+// Leaves another device current.  with_sq: a metric with a report term also leaves s(q) in Dev::d_sq (the range search's limits).
+static idist_status partitioned_upload_queries(idist_partitioned* p, const float* queries, uint32_t nq, bool with_sq = false) {
     const MetricPasses metric(p);
     const size_t qb = (size_t)nq * p->dim * 4, qa = metric.in_place() ? 0 : metric.qk_floats(nq) * 4;
     for (size_t d = 0; d < p->devs.size(); d++) {
@@ -3158,8 +3177,10 @@ static idist_status partitioned_upload_queries(idist_partitioned* p, const float
         HIPCHK(hipSetDevice(dv.device));
         CHK(grow(dv.d_q, dv.cap_q, qa + qb));
         HIPCHK(hipMemcpy(dv.d_q + qa / 4, queries, qb, hipMemcpyHostToDevice));
+        const bool sq = with_sq && metric.sq_floats(nq) != 0;
+        if (sq) CHK(grow(dv.d_sq, dv.cap_sq, metric.sq_floats(nq) * 4));
         if (metric.any()) {                              // prepared once per device; the parts' launches take them as they are
-            CHK(metric.prepare(dv.d_q + qa / 4, dv.d_q, nullptr, nq, nullptr, nullptr));
+            CHK(metric.prepare(dv.d_q + qa / 4, dv.d_q, sq ? dv.d_sq : nullptr, nq, nullptr, nullptr));
             HIPCHK(hipStreamSynchronize(nullptr));
         }
     }
@@ -4178,15 +4199,21 @@ idist_status range_grow_keys(idist_search_ctx* ctx, uint64_t used, uint64_t need
 }
 
 // off [N + 1] = base + the exclusive prefix sum of cnt [N] (off[N]: the total), enqueued on the context's stream
+// (chunk_sum: ceil(N / 64) u64 of scratch on the stream's device)
+idist_status range_prefix_on(hipStream_t stream, uint64_t* chunk_sum, const uint32_t* cnt, uint64_t N, uint64_t base, uint64_t* off) {
+    const uint64_t chunks = (N + 63u) / 64u;
+    if (chunks == 0) return IDIST_OK;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(chunks, 65536u);
+    IDIST_LAUNCH(range_chunk_sums_kernel, grid, 64, 0, stream, cnt, N, chunk_sum);
+    IDIST_LAUNCH(range_offsets_kernel, grid, 64, 0, stream, cnt, N, chunk_sum, base, off);
+    HIPCHK(hipGetLastError());
+    return IDIST_OK;
+}
 idist_status range_prefix(idist_search_ctx* ctx, const uint32_t* cnt, uint64_t N, uint64_t base, uint64_t* off) {
     const uint64_t chunks = (N + 63u) / 64u;
     if (chunks == 0) return IDIST_OK;
     CHK(grow(ctx->rg_chunks.p, ctx->rg_chunks.cap, doubled_from(256, (size_t)chunks * 8)));
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(chunks, 65536u);
-    IDIST_LAUNCH(range_chunk_sums_kernel, grid, 64, 0, ctx->stream, cnt, N, ctx->rg_chunks.as<uint64_t>());
-    IDIST_LAUNCH(range_offsets_kernel, grid, 64, 0, ctx->stream, cnt, N, ctx->rg_chunks.as<uint64_t>(), base, off);
-    HIPCHK(hipGetLastError());
-    return IDIST_OK;
+    return range_prefix_on(ctx->stream, ctx->rg_chunks.as<uint64_t>(), cnt, N, base, off);
 }
 
 // every list [ex_off[p], + ex_len[p]) of the result buffer ascending; max_len: the longest of them
@@ -4224,15 +4251,9 @@ idist_status range_too_many(uint64_t known, uint64_t max_total, const char* afte
                 (unsigned long long)known, after, (unsigned long long)max_total);
 }
 
-}  // namespace
-}  // extern "C++"
-
-idist_status idist_search_batch_range(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
-                                      const float* radius, uint32_t n_radius, int32_t max_rungs, uint64_t max_total,
-                                      uint64_t* out_lims, uint32_t* out_rung, uint32_t* out_counters) {
-    CHK(check_ctx(idx, ctx));
-    ctx->rg_valid = false;                                                   // whatever happens next, the previous results are gone
-    const uint32_t n = idx->n, ef0 = idx->cfg.ef_search;
+// the argument checks of a range call, each message once (the single index and the partitioned one)
+idist_status check_range_args(const float* queries, uint32_t nq, const float* radius, uint32_t n_radius, int32_t max_rungs,
+                              const uint64_t* out_lims) {
     CHK(check_max_rungs(max_rungs));
     if (!out_lims) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
     if (nq && n_radius != 1 && n_radius != nq) return fail(IDIST_ERR_INVALID_ARG, "n_radius %u: 1 (one radius for the batch) or nq = %u", n_radius, nq);
@@ -4242,24 +4263,78 @@ idist_status idist_search_batch_range(const idist_index* idx, idist_search_ctx* 
             if (n_radius == 1) return fail(IDIST_ERR_INVALID_ARG, "the radius of the batch (query 0 and every other) is NaN");
             return fail(IDIST_ERR_INVALID_ARG, "the radius of query %u is NaN", i);
         }
+    return IDIST_OK;
+}
+
+// a range call begins: the context holds nothing, times nothing
+void range_begin(const idist_index* idx, idist_search_ctx* ctx, uint32_t nq) {
+    ctx->rg_valid = false;
     ctx->rg_nq = nq;
     ctx->rg_total = 0;
     ctx->rg_metric = idx->cfg.metric;
     ctx->al_ms[3] = ctx->al_ms[4] = ctx->al_ms[5] = 0.0f;
     ctx->al_ev_used = 0;
-    if (nq == 0 || n == 0 || ef0 == 0) {                                     // step 1: nothing to find
+}
+
+idist_status range_search_device(const idist_index* idx, idist_search_ctx* ctx, const float* d_qk, const float* d_sq, uint32_t nq,
+                                 const float* radius, uint32_t n_radius, int32_t max_rungs, uint64_t max_total, bool counters,
+                                 uint64_t* total_out);
+
+}  // namespace
+}  // extern "C++"
+
+idist_status idist_search_batch_range(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
+                                      const float* radius, uint32_t n_radius, int32_t max_rungs, uint64_t max_total,
+                                      uint64_t* out_lims, uint32_t* out_rung, uint32_t* out_counters) {
+    CHK(check_ctx(idx, ctx));
+    ctx->rg_valid = false;                                                   // whatever happens next, the previous results are gone
+    CHK(check_range_args(queries, nq, radius, n_radius, max_rungs, out_lims));
+    range_begin(idx, ctx, nq);
+    if (nq == 0 || idx->n == 0 || idx->cfg.ef_search == 0) {                 // step 1: nothing to find
         std::fill(out_lims, out_lims + nq + 1, (uint64_t)0);
         fill_nothing_found(nq, 0, nullptr, nullptr, nullptr, out_rung, out_counters);
         ctx->rg_valid = true;
         return IDIST_OK;
     }
-    const AllowedLadder lad = make_ladder(ef0, max_rungs);
-
     HIPCHK(hipSetDevice(idx->device));
     hipStream_t stream = ctx->stream;
-    const MetricPasses metric(idx);
-    const uint32_t kdim = idx->kdim, kmetric = (uint32_t)idx->cfg.metric;
     const bool counters = out_counters != nullptr;
+    const float* d_qk = nullptr;                                 // (the metric's report is applied once, to what the fetch hands out)
+    CHK(ladder_upload_queries(idx, ctx, MetricPasses(idx), queries, nq, &d_qk));
+    uint64_t total = 0;
+    CHK(range_search_device(idx, ctx, d_qk, ctx->d_sq, nq, radius, n_radius, max_rungs, max_total, counters, &total));
+    // lims: the prefix sum of the counts, in query order
+    CHK(grow(ctx->rg_lims.p, ctx->rg_lims.cap, ((size_t)nq + 1) * 8));
+    uint64_t* d_lims = ctx->rg_lims.as<uint64_t>();
+    auto lims_pass = [&]() -> idist_status { return range_prefix(ctx, ctx->rg_cnt.as<uint32_t>(), nq, 0, d_lims); };
+    CHK(ladder_timed(ctx, 3, lims_pass));
+    HIPCHK(hipMemcpyAsync(out_lims, d_lims, ((size_t)nq + 1) * 8, hipMemcpyDeviceToHost, stream));
+    if (out_rung) HIPCHK(hipMemcpyAsync(out_rung, ctx->al_orung.p, (size_t)nq * 4, hipMemcpyDeviceToHost, stream));
+    if (counters) HIPCHK(hipMemcpyAsync(out_counters, ctx->al_octr.p, (size_t)nq * 12, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    CHK(ladder_times_resolve(ctx));
+    if (out_lims[nq] != total) return fail(IDIST_ERR_INTERNAL, "range search: the counts sum to %llu, the result buffer holds %llu",
+                                           (unsigned long long)out_lims[nq], (unsigned long long)total);
+    ctx->rg_total = total;
+    ctx->rg_valid = true;
+    return IDIST_OK;
+}
+
+extern "C++" {
+namespace {
+
+// The search itself, for queries that are on the index's device already (d_qk [nq][kdim] as the kernels read them, d_sq: s(q) of a
+// DOT index): the ladder and the exact step of DESIGN.md §4.9 on the context's stream, which is the current device's.  Afterwards
+// the context holds the keys in completion order (rg_keys), every query's offset, count and report term (rg_off, rg_cnt, rg_term),
+// its rung and counters (al_orung, al_octr); *total_out keys in all.  n > 0, ef_search > 0, nq > 0; range_begin has run.  The kernels
+// enqueued last may still be running when this returns.
+idist_status range_search_device(const idist_index* idx, idist_search_ctx* ctx, const float* d_qk, const float* d_sq, uint32_t nq,
+                                 const float* radius, uint32_t n_radius, int32_t max_rungs, uint64_t max_total, bool counters,
+                                 uint64_t* total_out) {
+    const uint32_t n = idx->n;
+    const AllowedLadder lad = make_ladder(idx->cfg.ef_search, max_rungs);
+    hipStream_t stream = ctx->stream;
+    const uint32_t kdim = idx->kdim, kmetric = (uint32_t)idx->cfg.metric;
     CHK(grow(ctx->rg_radius.p, ctx->rg_radius.cap, (size_t)n_radius * 4));
     CHK(grow(ctx->rg_lim.p, ctx->rg_lim.cap, (size_t)nq * 8));
     CHK(grow(ctx->rg_term.p, ctx->rg_term.cap, (size_t)nq * 4));
@@ -4267,7 +4342,6 @@ idist_status idist_search_batch_range(const idist_index* idx, idist_search_ctx* 
     CHK(grow(ctx->rg_off.p, ctx->rg_off.cap, (size_t)nq * 8));
     CHK(grow(ctx->rg_stepcnt.p, ctx->rg_stepcnt.cap, (size_t)nq * 4));
     CHK(grow(ctx->rg_stepoff.p, ctx->rg_stepoff.cap, ((size_t)nq + 1) * 8));
-    CHK(grow(ctx->rg_lims.p, ctx->rg_lims.cap, ((size_t)nq + 1) * 8));
     CHK(grow(ctx->al_flag.p, ctx->al_flag.cap, (size_t)nq * 4));
     CHK(grow(ctx->al_list.p, ctx->al_list.cap, (size_t)nq * 4));
     CHK(grow(ctx->al_npend.p, ctx->al_npend.cap, 256));
@@ -4276,8 +4350,6 @@ idist_status idist_search_batch_range(const idist_index* idx, idist_search_ctx* 
     CHK(grow(ctx->al_orung.p, ctx->al_orung.cap, (size_t)nq * 4));
     CHK(grow(ctx->al_octr.p, ctx->al_octr.cap, (size_t)nq * 12));
     HIPCHK(hipMemcpyAsync(ctx->rg_radius.p, radius, (size_t)n_radius * 4, hipMemcpyHostToDevice, stream));
-    const float* d_qk = nullptr;                                 // (the metric's report is applied once, to what the fetch hands out)
-    CHK(ladder_upload_queries(idx, ctx, metric, queries, nq, &d_qk));
     RangeState st{};
     st.lim = ctx->rg_lim.as<uint32_t>(); st.term = ctx->rg_term.as<float>(); st.count = ctx->rg_cnt.as<uint32_t>();
     st.off = ctx->rg_off.as<uint64_t>(); st.rung = ctx->al_orung.as<uint32_t>(); st.counters = counters ? ctx->al_octr.as<uint32_t>() : nullptr;
@@ -4285,7 +4357,7 @@ idist_status idist_search_batch_range(const idist_index* idx, idist_search_ctx* 
     const uint32_t waves_cap = (uint32_t)std::max(ctx->n_cu, 1) * 64u;
     auto init_pass = [&]() -> idist_status {
         const uint32_t grid = std::min<uint32_t>((nq + 255u) / 256u, (uint32_t)std::max(ctx->n_cu, 1) * 8u);
-        IDIST_LAUNCH(range_init_kernel, grid, 256, 0, stream, st, ctx->rg_radius.as<float>(), n_radius, kmetric, ctx->d_sq, idx->dot_S);
+        IDIST_LAUNCH(range_init_kernel, grid, 256, 0, stream, st, ctx->rg_radius.as<float>(), n_radius, kmetric, d_sq, idx->dot_S);
         HIPCHK(hipGetLastError());
         return IDIST_OK;
     };
@@ -4384,21 +4456,12 @@ idist_status idist_search_batch_range(const idist_index* idx, idist_search_ctx* 
         CHK(ladder_timed(ctx, 5, sort_pass));
         total = new_total;
     }
-    // lims: the prefix sum of the counts, in query order
-    uint64_t* d_lims = ctx->rg_lims.as<uint64_t>();
-    auto lims_pass = [&]() -> idist_status { return range_prefix(ctx, st.count, nq, 0, d_lims); };
-    CHK(ladder_timed(ctx, 3, lims_pass));
-    HIPCHK(hipMemcpyAsync(out_lims, d_lims, ((size_t)nq + 1) * 8, hipMemcpyDeviceToHost, stream));
-    if (out_rung) HIPCHK(hipMemcpyAsync(out_rung, ctx->al_orung.p, (size_t)nq * 4, hipMemcpyDeviceToHost, stream));
-    if (counters) HIPCHK(hipMemcpyAsync(out_counters, ctx->al_octr.p, (size_t)nq * 12, hipMemcpyDeviceToHost, stream));
-    HIPCHK(hipStreamSynchronize(stream));
-    CHK(ladder_times_resolve(ctx));
-    if (out_lims[nq] != total) return fail(IDIST_ERR_INTERNAL, "range search: the counts sum to %llu, the result buffer holds %llu",
-                                           (unsigned long long)out_lims[nq], (unsigned long long)total);
-    ctx->rg_total = total;
-    ctx->rg_valid = true;
+    *total_out = total;
     return IDIST_OK;
 }
+
+}  // namespace
+}  // extern "C++"
 
 idist_status idist_search_ctx_range_fetch(idist_search_ctx* ctx, uint32_t* out_pid, float* out_dist) {
     if (!ctx) return fail(IDIST_ERR_INVALID_ARG, "ctx is null");
@@ -4431,6 +4494,238 @@ idist_status idist_search_ctx_range_kernel_ms(idist_search_ctx* ctx, float* sele
     *select_ms = ctx->al_ms[3];
     *scan_ms = ctx->al_ms[4];
     *sort_ms = ctx->al_ms[5];
+    return IDIST_OK;
+}
+
+// ---- range search over a partitioned index: the parts' lists of any length merged on the device ----
+extern "C++" {
+namespace {
+
+// c [nq] = the lists' counts summed (out_ctr [nq][3] or nullptr: their counters), lims [nq + 1] = its prefix sum; chunks: ceil(nq / 64)
+// u64 of scratch.  Enqueued on `stream`.
+idist_status launch_range_merge_counts(const RangeLists& L, uint32_t* c, uint32_t* out_ctr, uint64_t* chunks, uint64_t* lims, int n_cu,
+                                       hipStream_t stream) {
+    const uint32_t grid = std::min<uint32_t>((L.nq + 255u) / 256u, (uint32_t)std::max(n_cu, 1) * 8u);
+    IDIST_LAUNCH(range_merge_counts_kernel, grid, 256, 0, stream, L, c, out_ctr);
+    HIPCHK(hipGetLastError());
+    return range_prefix_on(stream, chunks, c, L.nq, 0, lims);
+}
+
+// total = lims[nq] > 0 elements, a bounded tile of them per wave however they spread over queries and lists.  Enqueued on `stream`.
+idist_status launch_range_merge(const RangeLists& L, const uint64_t* lims, uint64_t total, int32_t metric, const float* d_sq, float S,
+                                uint32_t* out_pid, float* out_dist, int n_cu, hipStream_t stream) {
+    uint32_t tile = kRangeMergeTile;
+    if (const char* e = test_env("IDIST_RANGE_MERGE_TILE")) {      // test knob: the result must not depend on it
+        const uint32_t t = (uint32_t)std::max(0, atoi(e));
+        if (t >= 64u && t <= 65536u && t % 64u == 0u) tile = t;
+    }
+    const uint64_t tiles = (total + tile - 1u) / tile;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(tiles, (uint64_t)std::max(n_cu, 1) * 32u);   // the kernel strides over the rest
+    IDIST_LAUNCH(range_merge_kernel, grid, 64, 0, stream, L, lims, total, tile, (uint32_t)metric, d_sq, S, out_pid, out_dist);
+    HIPCHK(hipGetLastError());
+    return IDIST_OK;
+}
+
+}  // namespace
+}  // extern "C++"
+
+idist_status idist_range_merge_device(const void* const* d_keys, const void* const* d_off, const void* const* d_cnt, uint32_t n_lists,
+                                      uint32_t nq, const uint32_t* base, int32_t metric, const void* d_sq, float dot_bound,
+                                      uint64_t capacity, void* d_lims, void* d_out_pid, void* d_out_dist, uint64_t* out_total,
+                                      int32_t device, void* hip_stream) {
+    if (n_lists == 0 || n_lists > kMergeMaxLists) return fail(IDIST_ERR_INVALID_ARG, "n_lists %u out of [1,%u]", n_lists, kMergeMaxLists);
+    if (metric != IDIST_METRIC_L2SQ && metric != IDIST_METRIC_L2 && metric != IDIST_METRIC_COSINE && metric != IDIST_METRIC_DOT)
+        return fail(IDIST_ERR_INVALID_ARG, "unknown metric %d", metric);
+    if (!d_keys || !d_off || !d_cnt || !base || !d_lims || !out_total) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    if (nq && metric == IDIST_METRIC_DOT && !d_sq) return fail(IDIST_ERR_INVALID_ARG, "the inner-product metric reports with s(q): d_sq is null");
+    for (uint32_t l = 0; nq && l < n_lists; l++)
+        if (!d_off[l] || !d_cnt[l]) return fail(IDIST_ERR_INVALID_ARG, "list %u: null device pointer", l);
+    *out_total = 0;
+    CHK(check_device(device));
+    HIPCHK(hipSetDevice(device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (nq == 0) {
+        HIPCHK(hipMemsetAsync(d_lims, 0, 8, stream));
+        return IDIST_OK;
+    }
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    RangeLists L{};
+    L.n_lists = n_lists; L.nq = nq;
+    for (uint32_t l = 0; l < n_lists; l++) {
+        L.keys[l] = (const uint64_t*)d_keys[l]; L.off[l] = (const uint64_t*)d_off[l]; L.cnt[l] = (const uint32_t*)d_cnt[l];
+        L.base[l] = base[l];
+    }
+    Scratch mem;
+    uint32_t* c = nullptr;
+    uint64_t* chunks = nullptr;
+    CHK(mem.alloc(&c, nq));
+    CHK(mem.alloc(&chunks, ((size_t)nq + 63u) / 64u));
+    CHK(launch_range_merge_counts(L, c, nullptr, chunks, (uint64_t*)d_lims, prop.multiProcessorCount, stream));
+    uint64_t total = 0;                                          // the one read-back: it checks the capacity
+    HIPCHK(hipMemcpyAsync(&total, (const uint64_t*)d_lims + nq, 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    *out_total = total;
+    if (total > capacity)
+        return fail(IDIST_ERR_INVALID_ARG, "range merge: the lists hold %llu results, the output arrays %llu (nothing is written to them)",
+                    (unsigned long long)total, (unsigned long long)capacity);
+    if (total == 0) return IDIST_OK;
+    if (!d_out_pid || !d_out_dist) return fail(IDIST_ERR_INVALID_ARG, "null device pointer");
+    return launch_range_merge(L, (const uint64_t*)d_lims, total, metric, (const float*)d_sq, dot_bound, (uint32_t*)d_out_pid,
+                              (float*)d_out_dist, prop.multiProcessorCount, stream);
+}
+
+idist_status idist_partitioned_search_batch_range(idist_partitioned* p, const float* queries, uint32_t nq, const float* radius,
+                                                  uint32_t n_radius, int32_t max_rungs, uint64_t max_total, uint64_t* out_lims,
+                                                  uint32_t* out_rung, uint32_t* out_counters) {
+    if (!p) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    p->rg_valid = false;                                                     // whatever happens next, the previous results are gone
+    p->rg_total = 0;
+    uint32_t ef = 0;
+    CHK(partitioned_check(p, &ef));
+    CHK(check_range_args(queries, nq, radius, n_radius, max_rungs, out_lims));
+    const size_t P = p->parts.size();
+    const uint32_t N = p->base[P];
+    if (out_rung) std::fill(out_rung, out_rung + (size_t)nq * P, (uint32_t)IDIST_RUNG_NONE);   // (empty parts keep it)
+    if (nq == 0 || N == 0 || ef == 0) {                                      // nothing to find
+        std::fill(out_lims, out_lims + nq + 1, (uint64_t)0);
+        if (out_counters) memset(out_counters, 0, (size_t)nq * 12);
+        p->rg_merge_ms = 0.0f;
+        p->rg_valid = true;
+        return IDIST_OK;
+    }
+    const bool counters = out_counters != nullptr;
+    HIPCHK(hipSetDevice(p->merge_device));
+    CHK(partitioned_prepare_report(p, queries, nq));
+    // 1. the queries (DOT: and their s(q), the term of the parts' limits), once per distinct device that has something to search
+    CHK(partitioned_upload_queries(p, queries, nq, true));
+    // 2. the parts' searches block on the host once per rung: one thread per non-empty part, each with the part's own context and
+    //    stream (step 3 of idist_partitioned_search_batch_allowed_sets).  Every part gets the caller's bound: its own total can never
+    //    legitimately exceed the merged one.  A part on the merge device leaves its keys, offsets and counts where its context holds
+    //    them; a part elsewhere sends them to the merge device by peer copies on its stream.
+    std::vector<idist_status> st(P, IDIST_OK);
+    std::vector<std::string> msg(P);
+    std::vector<uint32_t> rungs(out_rung ? P * (size_t)nq : 0);
+    auto part = [&](size_t i) -> idist_status {
+        idist_partitioned::Part& pt = p->parts[i];
+        idist_search_ctx* ctx = pt.ctx;
+        const idist_partitioned::Dev& dv = p->devs[pt.dev_slot];
+        const int32_t dev = dv.device;
+        HIPCHK(hipSetDevice(dev));
+        range_begin(pt.idx, ctx, nq);
+        uint64_t total = 0;
+        CHK(range_search_device(pt.idx, ctx, dv.d_q, dv.d_sq, nq, radius, n_radius, max_rungs, max_total, counters, &total));
+        if (out_rung) HIPCHK(hipMemcpyAsync(rungs.data() + i * nq, ctx->al_orung.p, (size_t)nq * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (dev != p->merge_device) {
+            HIPCHK(hipSetDevice(p->merge_device));               // (staging on the merge device only grows)
+            CHK(grow(pt.m_keys, pt.m_cap_keys, doubled_from(4096, (size_t)total * 8)));
+            CHK(grow(pt.m_off, pt.m_cap_off, (size_t)nq * 8));
+            CHK(grow(pt.m_cnt, pt.m_cap_cnt, (size_t)nq * 4));
+            if (counters) CHK(grow(pt.m_ctr, pt.m_cap_ctr, (size_t)nq * 12));
+            HIPCHK(hipSetDevice(dev));
+            if (total) HIPCHK(hipMemcpyPeerAsync(pt.m_keys, p->merge_device, ctx->rg_keys.p, dev, (size_t)total * 8, ctx->stream));
+            HIPCHK(hipMemcpyPeerAsync(pt.m_off, p->merge_device, ctx->rg_off.p, dev, (size_t)nq * 8, ctx->stream));
+            HIPCHK(hipMemcpyPeerAsync(pt.m_cnt, p->merge_device, ctx->rg_cnt.p, dev, (size_t)nq * 4, ctx->stream));
+            if (counters) HIPCHK(hipMemcpyPeerAsync(pt.m_ctr, p->merge_device, ctx->al_octr.p, dev, (size_t)nq * 12, ctx->stream));
+        }
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        return ladder_times_resolve(ctx);
+    };
+    auto work = [&](size_t i) {
+        st[i] = part(i);
+        if (st[i] != IDIST_OK) msg[i] = g_err;               // g_err is thread-local
+    };
+    {
+        std::vector<std::thread> threads;
+        long first = -1;                                     // the first non-empty part runs on the calling thread
+        for (size_t i = 0; i < P; i++) {
+            if (!p->parts[i].ctx) continue;
+            if (first < 0) { first = (long)i; continue; }
+            try {
+                threads.emplace_back(work, i);
+            } catch (...) {                                  // no thread to be had: the part runs here, after the others were started
+                work(i);
+            }
+        }
+        if (first >= 0) work((size_t)first);
+        for (auto& t : threads) t.join();                    // every thread is joined before any return
+    }
+    for (size_t i = 0; i < P; i++)
+        if (st[i] != IDIST_OK) return fail(st[i], "part %zu (device %d): %s", i, p->devs[p->parts[i].dev_slot].device, msg[i].c_str());
+    // 3. the union, on the merge device: the counts and lims, ONE read-back of the total (it checks max_total and sizes the output),
+    //    the merge kernel straight into the flat arrays the fetch hands out
+    HIPCHK(hipSetDevice(p->merge_device));
+    RangeLists L{};
+    L.nq = nq;
+    for (size_t i = 0; i < P; i++) {
+        const idist_partitioned::Part& pt = p->parts[i];
+        if (!pt.ctx) continue;                               // an empty part hands in no list
+        const bool here = p->devs[pt.dev_slot].device == p->merge_device;
+        const uint32_t l = L.n_lists++;
+        L.keys[l] = here ? pt.ctx->rg_keys.as<uint64_t>() : pt.m_keys;
+        L.off[l] = here ? pt.ctx->rg_off.as<uint64_t>() : pt.m_off;
+        L.cnt[l] = here ? pt.ctx->rg_cnt.as<uint32_t>() : pt.m_cnt;
+        L.ctr[l] = !counters ? nullptr : (here ? pt.ctx->al_octr.as<uint32_t>() : pt.m_ctr);
+        L.base[l] = p->base[i];
+    }
+    const int n_cu = p->parts[0].idx->n_cu;
+    CHK(grow(p->rm_c, p->cap_rm_c, (size_t)nq * 4));
+    CHK(grow(p->rm_lims, p->cap_rm_lims, ((size_t)nq + 1) * 8));
+    CHK(grow(p->rm_chunks, p->cap_rm_chunks, doubled_from(256, (((size_t)nq + 63u) / 64u) * 8)));
+    if (counters) CHK(grow(p->o_ctr, p->cap_o_ctr, (size_t)nq * 12));
+    HIPCHK(hipEventRecord(p->ev0, p->stream));
+    CHK(launch_range_merge_counts(L, p->rm_c, counters ? p->o_ctr : nullptr, p->rm_chunks, p->rm_lims, n_cu, p->stream));
+    HIPCHK(hipEventRecord(p->ev1, p->stream));
+    uint64_t total = 0;
+    HIPCHK(hipMemcpyAsync(&total, p->rm_lims + nq, 8, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    float ms_counts = 0.0f, ms_merge = 0.0f;
+    HIPCHK(hipEventElapsedTime(&ms_counts, p->ev0, p->ev1));
+    if (total > max_total) return range_too_many(total, max_total, "the merge");
+    if (total) {
+        CHK(grow(p->rm_opid, p->cap_rm_opid, doubled_from(4096, (size_t)total * 4)));
+        CHK(grow(p->rm_odist, p->cap_rm_odist, doubled_from(4096, (size_t)total * 4)));
+        HIPCHK(hipEventRecord(p->ev0, p->stream));
+        CHK(launch_range_merge(L, p->rm_lims, total, p->metric, p->d_sq, p->dot_S, p->rm_opid, p->rm_odist, n_cu, p->stream));
+        HIPCHK(hipEventRecord(p->ev1, p->stream));
+    }
+    HIPCHK(hipMemcpyAsync(out_lims, p->rm_lims, ((size_t)nq + 1) * 8, hipMemcpyDeviceToHost, p->stream));
+    if (counters) HIPCHK(hipMemcpyAsync(out_counters, p->o_ctr, (size_t)nq * 12, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    if (total) HIPCHK(hipEventElapsedTime(&ms_merge, p->ev0, p->ev1));
+    p->rg_merge_ms = ms_counts + ms_merge;
+    if (out_rung)                                            // the parts' rungs came back [P][nq]
+        for (size_t i = 0; i < P; i++) {
+            if (!p->parts[i].ctx) continue;
+            for (uint32_t q = 0; q < nq; q++) out_rung[(size_t)q * P + i] = rungs[i * nq + q];
+        }
+    p->rg_total = total;
+    p->rg_valid = true;
+    return IDIST_OK;
+}
+
+idist_status idist_partitioned_range_fetch(idist_partitioned* p, uint32_t* out_pid, float* out_dist) {
+    if (!p) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    if (!p->rg_valid)
+        return fail(IDIST_ERR_INVALID_ARG, "no range search results are held: call idist_partitioned_search_batch_range first (a fetch hands them out once)");
+    const uint64_t total = p->rg_total;
+    if (total == 0) {
+        p->rg_valid = false;
+        return IDIST_OK;
+    }
+    if (!out_pid || !out_dist) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    HIPCHK(hipSetDevice(p->merge_device));
+    HIPCHK(hipMemcpyAsync(out_pid, p->rm_opid, (size_t)total * 4, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipMemcpyAsync(out_dist, p->rm_odist, (size_t)total * 4, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    p->rg_valid = false;
+    return IDIST_OK;
+}
+
+idist_status idist_partitioned_last_range_merge_ms(idist_partitioned* p, float* ms) {
+    if (!p || !ms) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    if (p->rg_merge_ms < 0.0f) return fail(IDIST_ERR_INVALID_ARG, "no range search has run through this object yet");
+    *ms = p->rg_merge_ms;
     return IDIST_OK;
 }
 

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import INVALID, METRIC_DOT, RUNG_NONE
-from .api import AllowedResult, BatchResult, Builder, Hnsw, Item, _as_points, allowed_bitmap, allowed_bitmaps
+from .api import AllowedResult, BatchResult, Builder, Hnsw, Item, RangeResult, _as_points, allowed_bitmap, allowed_bitmaps
 from .dist import shard_range
 
 
@@ -226,6 +226,45 @@ class PartitionedHnsw:
         """Host time the last restricted search spent on the bitmaps (the parts' strided uploads + slice kernels), milliseconds."""
         ms = C.c_float(0.0)
         _lib().check(_lib().idist_partitioned_last_allowed_slice_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def search_range(self, queries, radius, max_rungs: int = -1, max_total: int = 64 * 2**20, counters: bool = False) -> RangeResult:
+        """Every point of the whole set within `radius` of each query (idist_partitioned_search_batch_range): `Hnsw.search_range` on
+        every part — each climbs its own ladder and ends in its own exact scan — merged on the GPU by (raw distance bits, global id),
+        the metric's report applied once, after the merge.  `radius`, `max_rungs` and `max_total` as in `Hnsw.search_range`;
+        `max_total` bounds the merged total.  `RangeResult.pid` holds GLOBAL ids, `RangeResult.rung` has shape (nq, n_parts)
+        (RUNG_NONE for an empty part), the counters are summed over the parts."""
+        q = _as_points(queries)
+        info = self.info()
+        P = int(info.n_parts)
+        if q.shape[0] and len(self) and q.shape[1] != info.dim:
+            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
+        nq = q.shape[0]
+        rad = np.ascontiguousarray(np.asarray(radius, dtype=np.float32).reshape(-1))
+        if rad.size != 1 and rad.size != nq:
+            raise ValueError(f"`radius` is one float or an array of nq = {nq}, got {rad.size}")
+        lims = np.zeros(nq + 1, dtype=np.uint64)
+        rung = np.full((nq, P), RUNG_NONE, dtype=np.uint32)
+        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
+        L = _lib()
+        L.check(L.idist_partitioned_search_batch_range(self._h, _capi.f32p(q), nq, _capi.f32p(rad), int(rad.size), int(max_rungs),
+                                                       int(max_total), _capi.u64p(lims), _capi.u32p(rung),
+                                                       _capi.u32p(ctr) if counters else None))
+        total = int(lims[nq])
+        pid = np.zeros(total, dtype=np.uint32)
+        dist = np.zeros(total, dtype=np.float32)
+        L.check(L.idist_partitioned_range_fetch(self._h, _capi.u32p(pid), _capi.f32p(dist)))
+        return RangeResult(lims, pid, dist, rung, ctr)
+
+    def search_one_range(self, point, radius) -> list[Item]:
+        """One query: every item within `radius`, nearest first; `Item.pid` is the global id."""
+        r = self.search_range(np.asarray(point, dtype=np.float32).reshape(1, -1), float(radius))
+        return [Item(float(r.distance[i]), int(r.pid[i]), self[int(r.pid[i])]) for i in range(int(r.lims[1]))]
+
+    def last_range_merge_ms(self) -> float:
+        """HIP-event duration of the last range search's counts, prefix-sum and merge kernels, milliseconds."""
+        ms = C.c_float(0.0)
+        _lib().check(_lib().idist_partitioned_last_range_merge_ms(self._h, C.byref(ms)))
         return float(ms.value)
 
     def bruteforce(self, queries, k: int) -> tuple[np.ndarray, np.ndarray]:
