@@ -557,14 +557,58 @@ idist_status idist_search_ctx_allowed_kernel_ms(idist_search_ctx* ctx, float* se
 idist_status idist_search_batch_range(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
                                       const float* radius, uint32_t n_radius, int32_t max_rungs, uint64_t max_total,
                                       uint64_t* out_lims, uint32_t* out_rung, uint32_t* out_counters);
-/* The results of the last successful idist_search_batch_range through ctx: out_pid / out_dist [lims[nq]] each (may be NULL when that is
- * 0), in query order, reported distances.  They are handed out once: a fetch without a preceding successful range call (or a second
- * one) is IDIST_ERR_INVALID_ARG. */
+/* The results of the last successful idist_search_batch_range or idist_search_batch_range_allowed_sets through ctx: out_pid /
+ * out_dist [lims[nq]] each (may be NULL when that is 0), in query order, reported distances.  They are handed out once: a fetch
+ * without a preceding successful range call (or a second one) is IDIST_ERR_INVALID_ARG. */
 idist_status idist_search_ctx_range_fetch(idist_search_ctx* ctx, uint32_t* out_pid, float* out_dist);
-/* HIP-event durations (ms) of the kernels the last idist_search_batch_range through ctx ran around its searches: the select passes
- * (limits, within-prefixes, offsets, copies, pending lists), the exact step's two scans with their offsets, the sort.  0 with
- * IDIST_KERNEL_EVENTS=0.  The rungs' own search kernels are in idist_search_ctx_kernel_times. */
+/* HIP-event durations (ms) of the kernels the last idist_search_batch_range or idist_search_batch_range_allowed_sets through ctx ran
+ * around its searches: the select passes (limits, within-prefixes, offsets, copies, pending lists; the restricted call's count pass),
+ * the exact step's two scans with their offsets, the sort.  0 with IDIST_KERNEL_EVENTS=0.  The rungs' own search kernels are in
+ * idist_search_ctx_kernel_times. */
 idist_status idist_search_ctx_range_kernel_ms(idist_search_ctx* ctx, float* select_ms, float* scan_ms, float* sort_ms);
+
+/* ---- restricted range search: every point of an allowed set within a radius ------------------------------ */
+/* The composition of the two calls above, one allowed set per query: "every point of my subset within a radius".  Defined through
+ * what is already exact, as they are.
+ *   radius, n_radius, max_rungs, max_total   exactly as idist_search_batch_range.  A NaN radius is IDIST_ERR_INVALID_ARG and the message
+ *               names the query.
+ *   allow_bits, n_sets, set_of               exactly as idist_search_batch_allowed_sets: n_sets bitmaps of (n + 31) / 32 words each;
+ *               bits at positions >= n are ignored; set_of == NULL requires n_sets == nq; the buffer is neither written nor cleaned
+ *               on the host.
+ *   within      idist_search_batch_range's: report(d) <= r_q on the raw canonical distance.
+ *   the ladder  E[0] = ef_search, E[r + 1] = min(4 * E[r], IDIST_MAX_EF).
+ * For one query q with A = its own set:
+ *   1. Nothing to find.  n == 0, ef_search == 0 or |A| == 0: count 0, rung IDIST_RUNG_NONE.
+ *   2. End rule (per query).  Rung r is permitted for q iff max_rungs permits it and E[r] < 2 * |A|, in 64-bit integers: the exact step
+ *      below measures each of A's rows twice, 2 |A| row reads, while a search at E[r] fills a list of E[r] entries and measures at
+ *      least that many rows.  E is increasing, so the permitted rungs are a prefix r < R_q; R_q == 0 sends the query straight to 4.
+ *   3. Rungs.  For r = 0, 1, ... < R_q: L = the result of Hnsw::search at ef_search = E[r], c entries, pre the length of its
+ *      within-prefix.  c == E[r] and pre == c: saturated — judged on the unrestricted list, as in idist_search_batch_range — the next
+ *      rung runs.  Otherwise the answer is the allowed entries of L[0:pre], in L's order; rung = r (a count of 0 is an answer).
+ *   4. Exact.  The query is still unanswered after its last permitted rung, or R_q == 0: every point of A within the radius, ordered by
+ *      (raw distance bits, id); rung IDIST_RUNG_EXACT.
+ *   5. Reported distances are report(d), applied once, at the fetch.  out_counters sums {n_dist, n_exp0, n_expU} over the rungs the
+ *      query ran; the exact step adds nothing.
+ * As in idist_search_batch_range: a later rung that does not fit a wave's LDS ends the ladder for every query still pending (on rung 0
+ * the failure is returned); a strict-tie overflow is retried and never reaches the caller; every row of the batch is what the call
+ * returns for that query alone; max_total bounds the RESTRICTED total known after each step, with that call's message, and nothing is
+ * truncated.  So: row q's ids are idist_search_batch_range's answer of the same rung filtered by A whenever that rung is permitted;
+ * with max_rungs == 0 the answer is the exhaustive one; with every bit set and 2 n > IDIST_MAX_EF every output equals
+ * idist_search_batch_range's.
+ * The sets' sizes and last rungs are counted on the device; the exact step reads the bitmaps themselves and fetches only allowed rows
+ * (no id list is made; the staging does not grow beyond the bitmaps' own bytes).
+ * Host pointers; the call blocks until done.  ctx is the `&mut Search`: it holds the results exactly as after
+ * idist_search_batch_range — idist_search_ctx_range_fetch hands them out once, idist_search_ctx_range_kernel_ms reports the three
+ * times; idx is never mutated.  nq == 0: lims[0] = 0.
+ * IDIST_ERR_INVALID_ARG: the cases of idist_search_batch_range and of idist_search_batch_allowed_sets' sets (n_sets == 0; set_of == NULL
+ * with n_sets != nq; a set_of[q] >= n_sets, the message names q); null pointers.
+ * Out of scope: the partitioned index, device-pointer / stream variants and idist_search_batch_sharded. */
+idist_status idist_search_batch_range_allowed_sets(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
+                                                   const float* radius, uint32_t n_radius,
+                                                   const uint32_t* allow_bits,              /* [n_sets][(n + 31) / 32] */
+                                                   uint32_t n_sets, const uint32_t* set_of, /* [nq] or NULL */
+                                                   int32_t max_rungs, uint64_t max_total,
+                                                   uint64_t* out_lims, uint32_t* out_rung, uint32_t* out_counters);
 
 /* Range search over a partitioned index: the range search above on every part, merged on the device.
  * DEFINITION: row q is the merge, by the u64 key  raw distance bits << 32 | global id, of what idist_search_batch_range returns for
@@ -592,7 +636,7 @@ idist_status idist_search_ctx_range_kernel_ms(idist_search_ctx* ctx, float* sele
  * peer copies.  Work is divided by results, not by queries; up to 64 lists; no size cap but max_total.  ONE read-back of the merged
  * total precedes the merge.  The results are held by p until the next range call through it or until they are fetched.
  * Host pointers; blocks until done; p is used by one thread at a time.  Out of scope: device-pointer / stream variants,
- * idist_search_batch_sharded and a restricted range search. */
+ * idist_search_batch_sharded and a restricted range search over the parts (one index: idist_search_batch_range_allowed_sets). */
 idist_status idist_partitioned_search_batch_range(idist_partitioned* p, const float* queries, uint32_t nq,
                                                   const float* radius, uint32_t n_radius, int32_t max_rungs, uint64_t max_total,
                                                   uint64_t* out_lims,        /* nq + 1 */

@@ -154,6 +154,8 @@ SYMBOLS = {
                                                     _f32p, _u32p, _u32p, _u32p]),
     "idist_search_ctx_allowed_kernel_ms": (C.c_int32, [_vp, _f32p, _f32p, _f32p]),
     "idist_search_batch_range": (C.c_int32, [_vp, _vp, _f32p, C.c_uint32, _f32p, C.c_uint32, C.c_int32, C.c_uint64, _u64p, _u32p, _u32p]),
+    "idist_search_batch_range_allowed_sets": (C.c_int32, [_vp, _vp, _f32p, C.c_uint32, _f32p, C.c_uint32, _u32p, C.c_uint32, _u32p, C.c_int32,
+                                                          C.c_uint64, _u64p, _u32p, _u32p]),
     "idist_search_ctx_range_fetch": (C.c_int32, [_vp, _u32p, _f32p]),
     "idist_search_ctx_range_kernel_ms": (C.c_int32, [_vp, _f32p, _f32p, _f32p]),
     "idist_partitioned_search_batch_range": (C.c_int32, [_vp, _f32p, C.c_uint32, _f32p, C.c_uint32, C.c_int32, C.c_uint64, _u64p, _u32p, _u32p]),

@@ -416,6 +416,22 @@ def allowed_bitmaps(sets, n: int) -> np.ndarray:
     return out
 
 
+def _set_of(set_of, n_sets: int, nq: int):
+    """`set_of` of the several-sets calls as the ABI takes it: uint32 [nq], or None (query q uses set q) when it is None."""
+    if set_of is None:
+        if n_sets != nq:
+            raise ValueError(f"set_of=None means one set per query: {n_sets} sets for {nq} queries")
+        return None
+    so = np.asarray(set_of)
+    if so.size and not np.issubdtype(so.dtype, np.integer):
+        raise TypeError("`set_of` is an integer array of set indices, one per query")
+    if so.shape != (nq,):
+        raise ValueError(f"`set_of` must have one entry per query: shape ({nq},), got {so.shape}")
+    if so.size and (so.min() < 0 or so.max() >= n_sets):
+        raise IndexError(f"`set_of` names a set outside [0, {n_sets})")
+    return np.ascontiguousarray(so.astype(np.uint32))
+
+
 def normalize(points, device: int = 0, return_norm2: bool = False):
     """x / sqrt(s(x)) per row, s = the canonical squared-L2 distance of the row to the origin (idist_normalize_batch): the rows a
     METRIC_COSINE index holds for `points`, bit for bit — an METRIC_L2SQ index over `normalize(points)` searched with
@@ -644,6 +660,51 @@ class Hnsw:
         L.check(L.idist_search_ctx_range_fetch(ctx, _capi.u32p(pid), _capi.f32p(dist)))
         return RangeResult(lims, pid, dist, rung, ctr)
 
+    def search_range_allowed(self, queries, radius, allowed, search: Search, max_rungs: int = -1, max_total: int = 64 * 2**20,
+                             counters: bool = False) -> RangeResult:
+        """Every point of `allowed` within `radius` of each query: `search_range_allowed_sets` with one set for the whole batch.
+        `allowed`: a bool array of length n or an integer array of PointIds (`allowed_bitmap`'s rules), or a ready uint32 bitmap of
+        shape (1, (n + 31) // 32)."""
+        a = allowed
+        if not (isinstance(a, np.ndarray) and a.ndim == 2 and a.dtype == np.uint32):
+            a = allowed_bitmap(a, int(self.info().n))[None, :]
+        nq = _as_points(queries).shape[0]
+        return self.search_range_allowed_sets(queries, radius, a, np.zeros(nq, dtype=np.uint32), search, max_rungs, max_total, counters)
+
+    def search_range_allowed_sets(self, queries, radius, sets, set_of, search: Search, max_rungs: int = -1, max_total: int = 64 * 2**20,
+                                  counters: bool = False) -> RangeResult:
+        """`search_range` restricted to one allowed set per query (idist_search_batch_range_allowed_sets): every point of
+        sets[set_of[q]] within radius[q].  The rungs are `search_range`'s, each answer filtered by the query's set — saturation is
+        judged on the unrestricted list — but a query runs rung r only while ef_search * 4**r < 2 |set| (a longer list costs more than
+        the exact step); where its rungs end, an exact scan of the set's rows answers.  `radius`, `max_rungs`, `max_total`: as
+        `search_range`, `max_total` bounding the restricted total; `sets`, `set_of`: as `search_allowed_sets`."""
+        q = _as_points(queries)
+        info = self.info()
+        if q.shape[0] and info.n and q.shape[1] != info.dim:
+            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
+        nq = q.shape[0]
+        rad = np.ascontiguousarray(np.asarray(radius, dtype=np.float32).reshape(-1))
+        if rad.size != 1 and rad.size != nq:
+            raise ValueError(f"`radius` is one float or an array of nq = {nq}, got {rad.size}")
+        bits = allowed_bitmaps(sets, int(info.n))
+        so = _set_of(set_of, bits.shape[0], nq)
+        lims = np.zeros(nq + 1, dtype=np.uint64)
+        rung = np.full(nq, RUNG_NONE, dtype=np.uint32)
+        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
+        if bits.shape[0] == 0 and nq == 0:
+            return RangeResult(lims, np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.float32), rung, ctr)
+        ctx = search._bind(self)
+        L = _lib()
+        L.check(L.idist_search_batch_range_allowed_sets(self._h, ctx, _capi.f32p(q), nq, _capi.f32p(rad), int(rad.size), _capi.u32p(bits),
+                                                        bits.shape[0], _capi.u32p(so) if so is not None else None, int(max_rungs),
+                                                        int(max_total), _capi.u64p(lims), _capi.u32p(rung),
+                                                        _capi.u32p(ctr) if counters else None))
+        total = int(lims[nq])
+        pid = np.zeros(total, dtype=np.uint32)
+        dist = np.zeros(total, dtype=np.float32)
+        L.check(L.idist_search_ctx_range_fetch(ctx, _capi.u32p(pid), _capi.f32p(dist)))
+        return RangeResult(lims, pid, dist, rung, ctr)
+
     def search_allowed_sets(self, queries, sets, set_of, k: int, search: Search, max_rungs: int = -1, counters: bool = False) -> AllowedResult:
         """`search_allowed` with several allowed sets in one call, one per query (idist_search_batch_allowed_sets): row q is exactly
         what `search_allowed(queries[q], sets[set_of[q]], k, ...)` returns.  `sets`: a sequence of bool masks or of PointId arrays
@@ -656,19 +717,7 @@ class Hnsw:
             raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
         bits = allowed_bitmaps(sets, int(info.n))
         nq, k, n_sets = q.shape[0], int(k), bits.shape[0]
-        if set_of is None:
-            if n_sets != nq:
-                raise ValueError(f"set_of=None means one set per query: {n_sets} sets for {nq} queries")
-            so = None
-        else:
-            so = np.asarray(set_of)
-            if so.size and not np.issubdtype(so.dtype, np.integer):
-                raise TypeError("`set_of` is an integer array of set indices, one per query")
-            if so.shape != (nq,):
-                raise ValueError(f"`set_of` must have one entry per query: shape ({nq},), got {so.shape}")
-            if so.size and (so.min() < 0 or so.max() >= n_sets):
-                raise IndexError(f"`set_of` names a set outside [0, {n_sets})")
-            so = np.ascontiguousarray(so.astype(np.uint32))
+        so = _set_of(set_of, n_sets, nq)
         kk = max(k, 0)
         pid = np.full((nq, kk), INVALID, dtype=np.uint32)
         dist = np.full((nq, kk), np.inf, dtype=np.float32)
@@ -806,9 +855,21 @@ class HnswMap:
 
     def search_range(self, queries, radius, search: Search, max_rungs: int = -1, max_total: int = 64 * 2**20) -> list[list[MapItem]]:
         """`Hnsw.search_range` with the values: per query every result within its radius as `MapItem`s, nearest first."""
-        r = self.hnsw.search_range(queries, radius, search, max_rungs, max_total)
+        return self._range_items(self.hnsw.search_range(queries, radius, search, max_rungs, max_total))
+
+    def _range_items(self, r: RangeResult) -> list[list[MapItem]]:
         return [[MapItem(float(r.distance[j]), int(r.pid[j]), self.hnsw.points[int(r.pid[j])], self.values[int(r.pid[j])])
                  for j in range(int(r.lims[i]), int(r.lims[i + 1]))] for i in range(len(r.lims) - 1)]
+
+    def search_range_allowed(self, queries, radius, allowed, search: Search, max_rungs: int = -1,
+                             max_total: int = 64 * 2**20) -> list[list[MapItem]]:
+        """`Hnsw.search_range_allowed` with the values: per query every allowed result within its radius as `MapItem`s, nearest first."""
+        return self._range_items(self.hnsw.search_range_allowed(queries, radius, allowed, search, max_rungs, max_total))
+
+    def search_range_allowed_sets(self, queries, radius, sets, set_of, search: Search, max_rungs: int = -1,
+                                  max_total: int = 64 * 2**20) -> list[list[MapItem]]:
+        """`Hnsw.search_range_allowed_sets` with the values: per query every result of its set within its radius as `MapItem`s."""
+        return self._range_items(self.hnsw.search_range_allowed_sets(queries, radius, sets, set_of, search, max_rungs, max_total))
 
     def search_allowed_sets(self, queries, sets, set_of, k: int, search: Search, max_rungs: int = -1) -> list[list[MapItem]]:
         """`Hnsw.search_allowed_sets` with the values: per query its min(k, points of its set) results as `MapItem`s, nearest first."""

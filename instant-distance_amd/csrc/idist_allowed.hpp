@@ -30,6 +30,7 @@
 //   allowed_select_kernel     with set_of: the row is filtered by the bitmap of the query's own set.
 //   allowed_pending_kernel    with first / rung: a query is gathered iff it is pending and first[q] <= rung — a query waits,
 //                             unlaunched, until its start rung comes up; rung = kRungExact gathers everything still pending.
+//                             With last (the restricted range search, idist_range_allowed.hpp): ... and rung < last[q].
 //   allowed_scan_bits_kernel  the exact step straight from the bitmap: grid = pending queries x S segments of the 64-id windows of
 //                             [0, n).  A wave takes 64 windows at a time (one 64-bit load per lane), skips the all-zero ones by a
 //                             ballot, and compacts the set bits of the others into ascending ids by prefix popcount, in batches of
@@ -143,18 +144,22 @@ __global__ __launch_bounds__(64) void allowed_select_kernel(AllowedOut o, const 
 // pending [nq] -> list: the pending query indices, ascending; pend_q [np][kdim]: their rows of `queries` [nq][kdim]; *n_pending = np.
 // grid = ceil(nq / 64) waves EXACTLY: wave b owns the queries [64 b, 64 b + 64) and the last one writes the total.
 // first [nq] (nullptr: every pending query is gathered): only the pending queries with first[q] <= rung are — the others wait.
+// last [nq] (nullptr: no bound; the restricted range search, idist_range_allowed.hpp): only those with rung < last[q] are — the
+// others have run their last rung and wait for the exact step.
 __global__ __launch_bounds__(64) void allowed_pending_kernel(const uint32_t* __restrict__ pending, uint32_t nq,
                                                              const float* __restrict__ queries, uint32_t kdim,
                                                              uint32_t* __restrict__ list, float* __restrict__ pend_q,
                                                              uint32_t* __restrict__ n_pending,
-                                                             const uint32_t* __restrict__ first_rung = nullptr, uint32_t rung = 0) {
+                                                             const uint32_t* __restrict__ first_rung = nullptr, uint32_t rung = 0,
+                                                             const uint32_t* __restrict__ last_rung = nullptr) {
     const int lane = lane_id();
     const uint32_t first = blockIdx.x * 64u;
+    auto due = [&](uint32_t i) { return pending[i] != 0u && (!first_rung || first_rung[i] <= rung) && (!last_rung || rung < last_rung[i]); };
     uint32_t before = 0;
-    for (uint32_t i = (uint32_t)lane; i < first; i += 64u) before += pending[i] && (!first_rung || first_rung[i] <= rung) ? 1u : 0u;
+    for (uint32_t i = (uint32_t)lane; i < first; i += 64u) before += due(i) ? 1u : 0u;
     before = wave_sum_u32(before);
     const uint32_t q = first + (uint32_t)lane;
-    const bool on = q < nq && pending[q] != 0u && (!first_rung || first_rung[q] <= rung);
+    const bool on = q < nq && due(q);
     const uint64_t m = __ballot(on);
     if (on) list[before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = q;
     uint64_t rest = m;
@@ -203,6 +208,18 @@ struct AllowedLadder {
     uint32_t n_rungs;     // (max_rungs applied)
 };
 
+// |A| of one bitmap of `words` words over n points (bits at positions >= n not counted), in every lane: a sum of popcounts, the same
+// whatever the schedule.  <= n.
+__device__ __forceinline__ uint32_t allowed_set_size(const uint32_t* __restrict__ b, uint32_t n, uint32_t words) {
+    const uint32_t last_mask = n % 32u ? (1u << (n % 32u)) - 1u : 0xFFFFFFFFu;
+    uint32_t c = 0;
+    for (uint32_t w = (uint32_t)lane_id(); w < words; w += 64u) {
+        const uint32_t v = b[w] & (w + 1u == words ? last_mask : 0xFFFFFFFFu);
+        c += (uint32_t)__popcll((uint64_t)v);
+    }
+    return wave_sum_u32(c);
+}
+
 // bits [n_sets][words] -> size [n_sets] = |A_s| (bits at positions >= n not counted), start [n_sets]: the first permitted rung r
 // with E[r] |A_s| >= k n (64-bit), kRungExact when |A_s| <= k or no rung qualifies, kRungNone for the empty set.  One wave per set
 // (the grid strides over the rest): a sum of popcounts, the same whatever the schedule.
@@ -210,15 +227,8 @@ __global__ __launch_bounds__(64) void allowed_count_kernel(const uint32_t* __res
                                                            uint32_t k, AllowedLadder lad, uint32_t* __restrict__ size,
                                                            uint32_t* __restrict__ start) {
     const int lane = lane_id();
-    const uint32_t last_mask = n % 32u ? (1u << (n % 32u)) - 1u : 0xFFFFFFFFu;
     for (uint32_t s = blockIdx.x; s < n_sets; s += gridDim.x) {
-        const uint32_t* b = bits + (size_t)s * words;
-        uint32_t c = 0;
-        for (uint32_t w = (uint32_t)lane; w < words; w += 64u) {
-            const uint32_t v = b[w] & (w + 1u == words ? last_mask : 0xFFFFFFFFu);
-            c += (uint32_t)__popcll((uint64_t)v);
-        }
-        c = wave_sum_u32(c);                                  // <= n
+        const uint32_t c = allowed_set_size(bits + (size_t)s * words, n, words);
         uint32_t r0 = kRungExact;
         if (c == 0u) r0 = kRungNone;
         else if (c > k)

@@ -10,6 +10,7 @@
 #include "idist_dot.hpp"
 #include "idist_allowed.hpp"
 #include "idist_range.hpp"
+#include "idist_range_allowed.hpp"
 #include "idist_range_merge.hpp"
 #include "idist_basis.hpp"
 
@@ -419,7 +420,8 @@ struct idist_search_ctx {
     //    the words of the caller's global bitmaps that hold its bits, as uploaded (al_raw: allowed_slice_kernel cuts al_bits out of them).
     //  * The range search's: rg_*.  What idist_search_ctx_range_fetch needs lives in buffers no other call writes: the keys in
     //    completion order, every query's count, offset and report term.  rg_list: the second pending list (a rung's copy pass still
-    //    reads the list that the next rung's pending pass replaces).
+    //    reads the list that the next rung's pending pass replaces).  The restricted range search stages its sets in the restricted
+    //    search's buffers: al_bits, al_setof, |A_s| (al_size), the permitted rungs per set (al_start) and per query (al_first).
     struct Buf {
         void* p = nullptr;
         size_t cap = 0;
@@ -3652,13 +3654,15 @@ idist_status ladder_rung(const idist_index* idx, idist_search_ctx* ctx, const fl
     }
 }
 
-// The pending pass, enqueued only: the pending queries (d_first: whose first rung is <= rung) ascending into list_out, their rows
-// into ctx->al_pq, their number into ctx->al_npend — which the caller reads back (the range search: with its new total, in one wait)
+// The pending pass, enqueued only: the pending queries (d_first: whose first rung is <= rung; d_last: whose last rung is > rung)
+// ascending into list_out, their rows into ctx->al_pq, their number into ctx->al_npend — which the caller reads back (the range
+// searches: with their new total, in one wait)
 idist_status ladder_pending(idist_search_ctx* ctx, const uint32_t* pending, uint32_t nq, const float* d_qk, uint32_t kdim,
-                            uint32_t* list_out, int which_timer, const uint32_t* d_first = nullptr, uint32_t rung = 0) {
+                            uint32_t* list_out, int which_timer, const uint32_t* d_first = nullptr, uint32_t rung = 0,
+                            const uint32_t* d_last = nullptr) {
     auto pending_pass = [&]() -> idist_status {
         IDIST_LAUNCH(allowed_pending_kernel, (nq + 63u) / 64u, 64, 0, ctx->stream, pending, nq, d_qk, kdim, list_out, ctx->al_pq.as<float>(),
-                     ctx->al_npend.as<uint32_t>(), d_first, rung);
+                     ctx->al_npend.as<uint32_t>(), d_first, rung, d_last);
         HIPCHK(hipGetLastError());
         return IDIST_OK;
     };
@@ -4276,9 +4280,17 @@ void range_begin(const idist_index* idx, idist_search_ctx* ctx, uint32_t nq) {
     ctx->al_ev_used = 0;
 }
 
+// the allowed sets of a restricted range search, on the device: bits [n_sets][words], set_of [nq]
+struct RangeSets {
+    const uint32_t* bits;
+    const uint32_t* set_of;
+    uint32_t n_sets, words;
+};
+
 idist_status range_search_device(const idist_index* idx, idist_search_ctx* ctx, const float* d_qk, const float* d_sq, uint32_t nq,
                                  const float* radius, uint32_t n_radius, int32_t max_rungs, uint64_t max_total, bool counters,
-                                 uint64_t* total_out);
+                                 uint64_t* total_out, const RangeSets* sets = nullptr);
+idist_status range_finish(idist_search_ctx* ctx, uint32_t nq, uint64_t total, uint64_t* out_lims, uint32_t* out_rung, uint32_t* out_counters);
 
 }  // namespace
 }  // extern "C++"
@@ -4297,20 +4309,70 @@ idist_status idist_search_batch_range(const idist_index* idx, idist_search_ctx* 
         return IDIST_OK;
     }
     HIPCHK(hipSetDevice(idx->device));
-    hipStream_t stream = ctx->stream;
     const bool counters = out_counters != nullptr;
     const float* d_qk = nullptr;                                 // (the metric's report is applied once, to what the fetch hands out)
     CHK(ladder_upload_queries(idx, ctx, MetricPasses(idx), queries, nq, &d_qk));
     uint64_t total = 0;
     CHK(range_search_device(idx, ctx, d_qk, ctx->d_sq, nq, radius, n_radius, max_rungs, max_total, counters, &total));
-    // lims: the prefix sum of the counts, in query order
+    return range_finish(ctx, nq, total, out_lims, out_rung, out_counters);
+}
+
+// ---- restricted range search: every point of a query's own allowed set within its radius ----
+idist_status idist_search_batch_range_allowed_sets(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
+                                                   const float* radius, uint32_t n_radius, const uint32_t* allow_bits, uint32_t n_sets,
+                                                   const uint32_t* set_of, int32_t max_rungs, uint64_t max_total, uint64_t* out_lims,
+                                                   uint32_t* out_rung, uint32_t* out_counters) {
+    CHK(check_ctx(idx, ctx));
+    ctx->rg_valid = false;                                                   // whatever happens next, the previous results are gone
+    CHK(check_range_args(queries, nq, radius, n_radius, max_rungs, out_lims));
+    CHK(check_sets_args(n_sets, set_of, nq));
+    const uint32_t n = idx->n;
+    if (nq && n && !allow_bits) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    range_begin(idx, ctx, nq);
+    if (nq == 0 || n == 0 || idx->cfg.ef_search == 0) {                      // step 1: nothing to find, whatever the sets
+        std::fill(out_lims, out_lims + nq + 1, (uint64_t)0);
+        fill_nothing_found(nq, 0, nullptr, nullptr, nullptr, out_rung, out_counters);
+        ctx->rg_valid = true;
+        return IDIST_OK;
+    }
+    HIPCHK(hipSetDevice(idx->device));
+    hipStream_t stream = ctx->stream;
+    // the bitmaps and set_of as idist_search_batch_allowed_sets stages them: as the caller has them, padding bits are masked where
+    // they are read
+    const uint32_t words = (n + 31u) / 32u;
+    const size_t bb = (size_t)n_sets * words * 4;
+    CHK(grow(ctx->al_bits.p, ctx->al_bits.cap, bb));
+    CHK(grow(ctx->al_setof.p, ctx->al_setof.cap, (size_t)nq * 4));
+    std::vector<uint32_t> own_set;                               // set_of == NULL: query q uses set q
+    if (!set_of) {
+        own_set.resize(nq);
+        for (uint32_t q = 0; q < nq; q++) own_set[q] = q;
+        set_of = own_set.data();
+    }
+    HIPCHK(hipMemcpyAsync(ctx->al_bits.p, allow_bits, bb, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(ctx->al_setof.p, set_of, (size_t)nq * 4, hipMemcpyHostToDevice, stream));
+    const float* d_qk = nullptr;
+    CHK(ladder_upload_queries(idx, ctx, MetricPasses(idx), queries, nq, &d_qk));
+    const RangeSets sets{ctx->al_bits.as<uint32_t>(), ctx->al_setof.as<uint32_t>(), n_sets, words};
+    uint64_t total = 0;
+    CHK(range_search_device(idx, ctx, d_qk, ctx->d_sq, nq, radius, n_radius, max_rungs, max_total, out_counters != nullptr, &total, &sets));
+    return range_finish(ctx, nq, total, out_lims, out_rung, out_counters);
+}
+
+extern "C++" {
+namespace {
+
+// The end of a range call on one index: lims, the prefix sum of the counts in query order, with the rungs and counters on their way
+// back to the caller; the call's last synchronisation; the context holds the results from here on.
+idist_status range_finish(idist_search_ctx* ctx, uint32_t nq, uint64_t total, uint64_t* out_lims, uint32_t* out_rung, uint32_t* out_counters) {
+    hipStream_t stream = ctx->stream;
     CHK(grow(ctx->rg_lims.p, ctx->rg_lims.cap, ((size_t)nq + 1) * 8));
     uint64_t* d_lims = ctx->rg_lims.as<uint64_t>();
     auto lims_pass = [&]() -> idist_status { return range_prefix(ctx, ctx->rg_cnt.as<uint32_t>(), nq, 0, d_lims); };
     CHK(ladder_timed(ctx, 3, lims_pass));
     HIPCHK(hipMemcpyAsync(out_lims, d_lims, ((size_t)nq + 1) * 8, hipMemcpyDeviceToHost, stream));
     if (out_rung) HIPCHK(hipMemcpyAsync(out_rung, ctx->al_orung.p, (size_t)nq * 4, hipMemcpyDeviceToHost, stream));
-    if (counters) HIPCHK(hipMemcpyAsync(out_counters, ctx->al_octr.p, (size_t)nq * 12, hipMemcpyDeviceToHost, stream));
+    if (out_counters) HIPCHK(hipMemcpyAsync(out_counters, ctx->al_octr.p, (size_t)nq * 12, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
     CHK(ladder_times_resolve(ctx));
     if (out_lims[nq] != total) return fail(IDIST_ERR_INTERNAL, "range search: the counts sum to %llu, the result buffer holds %llu",
@@ -4320,17 +4382,18 @@ idist_status idist_search_batch_range(const idist_index* idx, idist_search_ctx* 
     return IDIST_OK;
 }
 
-extern "C++" {
-namespace {
-
 // The search itself, for queries that are on the index's device already (d_qk [nq][kdim] as the kernels read them, d_sq: s(q) of a
 // DOT index): the ladder and the exact step of DESIGN.md §4.9 on the context's stream, which is the current device's.  Afterwards
 // the context holds the keys in completion order (rg_keys), every query's offset, count and report term (rg_off, rg_cnt, rg_term),
 // its rung and counters (al_orung, al_octr); *total_out keys in all.  n > 0, ef_search > 0, nq > 0; range_begin has run.  The kernels
 // enqueued last may still be running when this returns.
+// sets != nullptr: the restricted range search of §4.10 — the same schedule with the bitmap in the select and copy passes and in the
+// exact scan, a count pass in front, and pending lists that know every query's last rung: a query is gathered for rung r iff it is
+// pending and r < last[q], so the batch is gathered once before rung 0 (a small set skips the ladder) and once more, whole, before
+// the exact step.  sets == nullptr launches exactly what the plain call always launched.
 idist_status range_search_device(const idist_index* idx, idist_search_ctx* ctx, const float* d_qk, const float* d_sq, uint32_t nq,
                                  const float* radius, uint32_t n_radius, int32_t max_rungs, uint64_t max_total, bool counters,
-                                 uint64_t* total_out) {
+                                 uint64_t* total_out, const RangeSets* sets) {
     const uint32_t n = idx->n;
     const AllowedLadder lad = make_ladder(idx->cfg.ef_search, max_rungs);
     hipStream_t stream = ctx->stream;
@@ -4368,6 +4431,37 @@ idist_status range_search_device(const idist_index* idx, idist_search_ctx* ctx, 
     const float* d_pq = d_qk;
     uint32_t* step_cnt = ctx->rg_stepcnt.as<uint32_t>();
     uint64_t* step_off = ctx->rg_stepoff.as<uint64_t>();
+    const uint32_t* d_last = nullptr;                            // restricted: the rungs query q may run are r < last[q]
+    const uint32_t *s_bits = sets ? sets->bits : nullptr, *s_setof = sets ? sets->set_of : nullptr;
+    const uint32_t s_words = sets ? sets->words : 0u, n_sets = sets ? sets->n_sets : 0u;
+    // restricted: the queries of rung `rung` (d_last) or everything still pending (nullptr) into al_list / al_pq, their number read back
+    auto gather = [&](uint32_t rung, const uint32_t* last) -> idist_status {
+        CHK(ladder_pending(ctx, st.pending, nq, d_qk, kdim, ctx->al_list.as<uint32_t>(), 3, nullptr, rung, last));
+        HIPCHK(hipMemcpyAsync(&np, ctx->al_npend.p, 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        d_list = ctx->al_list.as<uint32_t>();
+        d_pq = ctx->al_pq.as<float>();
+        return IDIST_OK;
+    };
+    if (sets) {
+        CHK(grow(ctx->al_size.p, ctx->al_size.cap, (size_t)n_sets * 4));
+        CHK(grow(ctx->al_start.p, ctx->al_start.cap, (size_t)n_sets * 4));
+        CHK(grow(ctx->al_first.p, ctx->al_first.cap, (size_t)nq * 4));
+        d_last = ctx->al_first.as<uint32_t>();
+        auto count_pass = [&]() -> idist_status {
+            const uint32_t grid_c = std::min<uint32_t>(n_sets, (uint32_t)std::max(ctx->n_cu, 1) * 32u);
+            IDIST_LAUNCH(range_allowed_count_kernel, grid_c, 64, 0, stream, s_bits, n, s_words, n_sets, lad,
+                         ctx->al_size.as<uint32_t>(), ctx->al_start.as<uint32_t>());
+            const uint32_t grid_i = std::min<uint32_t>((nq + 255u) / 256u, (uint32_t)std::max(ctx->n_cu, 1) * 8u);
+            IDIST_LAUNCH(range_allowed_init_kernel, grid_i, 256, 0, stream, st, ctx->al_size.as<uint32_t>(), ctx->al_start.as<uint32_t>(),
+                         s_setof, ctx->al_first.as<uint32_t>());
+            HIPCHK(hipGetLastError());
+            return IDIST_OK;
+        };
+        CHK(ladder_timed(ctx, 3, count_pass));
+        np = 0;
+        if (lad.n_rungs) { CHK(gather(0, d_last)); }
+    }
     for (uint32_t r = 0; r < lad.n_rungs && np; r++) {
         const uint32_t ef = lad.E[r];
         bool ended = false;
@@ -4375,8 +4469,13 @@ idist_status range_search_device(const idist_index* idx, idist_search_ctx* ctx, 
         if (ended) break;
         const uint32_t np_step = np;
         auto select_pass = [&]() -> idist_status {
-            IDIST_LAUNCH(range_select_kernel, std::min(np_step, 65536u), 64, 0, stream, st, reinterpret_cast<const uint32_t*>(ctx->d_dist),
-                         ctx->d_cnt, counters ? ctx->d_ctr : nullptr, ef, d_list, np_step, r, step_cnt);
+            if (sets)
+                IDIST_LAUNCH(range_allowed_select_kernel, std::min(np_step, 65536u), 64, 0, stream, st, s_bits, n, s_words, s_setof,
+                             ctx->d_pid, reinterpret_cast<const uint32_t*>(ctx->d_dist), ctx->d_cnt, counters ? ctx->d_ctr : nullptr, ef,
+                             d_list, np_step, r, step_cnt);
+            else
+                IDIST_LAUNCH(range_select_kernel, std::min(np_step, 65536u), 64, 0, stream, st, reinterpret_cast<const uint32_t*>(ctx->d_dist),
+                             ctx->d_cnt, counters ? ctx->d_ctr : nullptr, ef, d_list, np_step, r, step_cnt);
             HIPCHK(hipGetLastError());
             return range_prefix(ctx, step_cnt, np_step, total, step_off);
         };
@@ -4385,7 +4484,7 @@ idist_status range_search_device(const idist_index* idx, idist_search_ctx* ctx, 
         // number: the copy still needs this rung's list, so the lists alternate between two buffers (the rows of this rung stay
         // where they are until the copy has run; the next rows go to al_pq)
         uint32_t* next_list = d_list == ctx->al_list.as<uint32_t>() ? ctx->rg_list.as<uint32_t>() : ctx->al_list.as<uint32_t>();
-        CHK(ladder_pending(ctx, st.pending, nq, d_qk, kdim, next_list, 3));
+        CHK(ladder_pending(ctx, st.pending, nq, d_qk, kdim, next_list, 3, nullptr, r + 1u, d_last));
         uint64_t new_total = 0;
         HIPCHK(hipMemcpyAsync(&new_total, step_off + np_step, 8, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipMemcpyAsync(&np, ctx->al_npend.p, 4, hipMemcpyDeviceToHost, stream));
@@ -4397,8 +4496,13 @@ idist_status range_search_device(const idist_index* idx, idist_search_ctx* ctx, 
         }
         CHK(range_grow_keys(ctx, total, new_total));
         auto copy_pass = [&]() -> idist_status {
-            IDIST_LAUNCH(range_copy_kernel, std::min(np_step, 65536u), 64, 0, stream, st, ctx->d_pid, reinterpret_cast<const uint32_t*>(ctx->d_dist),
-                         ef, d_list, np_step, step_cnt, step_off, ctx->rg_keys.as<uint64_t>());
+            if (sets)
+                IDIST_LAUNCH(range_allowed_copy_kernel, std::min(np_step, 65536u), 64, 0, stream, st, s_bits, n, s_words, s_setof,
+                             ctx->d_pid, reinterpret_cast<const uint32_t*>(ctx->d_dist), ef, d_list, np_step, step_cnt, step_off,
+                             ctx->rg_keys.as<uint64_t>());
+            else
+                IDIST_LAUNCH(range_copy_kernel, std::min(np_step, 65536u), 64, 0, stream, st, ctx->d_pid, reinterpret_cast<const uint32_t*>(ctx->d_dist),
+                             ef, d_list, np_step, step_cnt, step_off, ctx->rg_keys.as<uint64_t>());
             HIPCHK(hipGetLastError());
             return IDIST_OK;
         };
@@ -4407,8 +4511,10 @@ idist_status range_search_device(const idist_index* idx, idist_search_ctx* ctx, 
         d_list = next_list;
         d_pq = ctx->al_pq.as<float>();
     }
+    if (sets) { CHK(gather(kRungExact, nullptr)); }               // whoever is still pending: past its last rung, or the ladder ended
     if (np) {
-        // step 3, exact: [0, n) cut into S segments, one wave per (pending query, segment)
+        // step 3, exact: [0, n) cut into S segments, one wave per (pending query, segment); restricted: the 64-id windows of [0, n),
+        // never narrower than one window
         const uint32_t S = exact_segments(ctx, np, n, ctx->knobs.range_segments);
         const uint64_t items = (uint64_t)np * S;
         CHK(grow(ctx->d_cnt, ctx->cap_cnt, (size_t)items * 4));
@@ -4428,7 +4534,15 @@ idist_status range_search_device(const idist_index* idx, idist_search_ctx* ctx, 
         auto kR = range_scan_kernel<NB_, RS_, TAIL_>;                                                            \
         IDIST_LAUNCH(kR, grid, 64, smem, stream, view, d_pq, np, d_list, d_lim, S, seg_cnt, seg_off, keys);      \
     }
-            IDIST_DISPATCH(idx->L, LAUNCH_AS);
+#define LAUNCH_AS_SETS(NB_, RS_, TAIL_)                                                                          \
+    {                                                                                                            \
+        auto kA = range_allowed_scan_kernel<NB_, RS_, TAIL_>;                                                    \
+        IDIST_LAUNCH(kA, grid, 64, smem, stream, view, d_pq, np, s_bits, n, s_words, d_list, s_setof, d_lim, S, seg_cnt, \
+                     seg_off, keys);                                                                             \
+    }
+            if (sets) IDIST_DISPATCH(idx->L, LAUNCH_AS_SETS);
+            else IDIST_DISPATCH(idx->L, LAUNCH_AS);
+#undef LAUNCH_AS_SETS
 #undef LAUNCH_AS
             HIPCHK(hipGetLastError());
             return IDIST_OK;
