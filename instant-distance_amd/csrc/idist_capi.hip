@@ -1379,6 +1379,16 @@ extern "C" int idist_probe_quad(unsigned long long* out24, int reset) {
     }
     return 0;
 }
+// ... and the inlined thin principal walk's zero layer: the second half of g_quad_probe (mark i in out24[i])
+extern "C" int idist_probe_thin(unsigned long long* out24, int reset) {
+    if (hipDeviceSynchronize() != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(out24, HIP_SYMBOL(g_quad_probe), 24 * sizeof(unsigned long long), 24 * sizeof(unsigned long long)) != hipSuccess) return -2;
+    if (reset) {
+        unsigned long long z[24] = {};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_quad_probe), z, sizeof(z), sizeof(z)) != hipSuccess) return -3;
+    }
+    return 0;
+}
 #endif
 
 idist_status build_common(const void* points, bool on_device, uint32_t n, uint32_t dim, const idist_config* cfg,

@@ -208,6 +208,25 @@ __device__ __forceinline__ float fold_chains(float acc, bool has_tail, float tq,
 // mid(): work of the caller that does not depend on the distances — it runs once, after the first batch of row loads
 // has been issued and before anything waits for them (the walk inserts the new ids into its visited set there).
 struct NoMid { __device__ __forceinline__ void operator()() const {} };
+#ifdef IDIST_PROBE
+// measurement build: a `mid` that also wants to know when the rows it ran beside have arrived — the pass waits for all of its
+// loads right after mid() and calls arrived() (the first rows' arithmetic no longer overlaps the last rows' arrival: a pass of
+// the thin walks is a single batch, and the stamp needs one moment)
+template <class F, class G> struct MidStamped {
+    F f; G g;
+    __device__ __forceinline__ void operator()() const { f(); }
+    __device__ __forceinline__ void arrived() const { g(); }
+};
+template <class F, class G> __device__ __forceinline__ MidStamped<F, G> mid_stamped(F f, G g) { return MidStamped<F, G>{f, g}; }
+template <class M> __device__ __forceinline__ auto mid_arrived(const M& m, int) -> decltype(m.arrived(), void()) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    m.arrived();
+}
+template <class M> __device__ __forceinline__ void mid_arrived(const M&, long) {}
+#define MID_ARRIVED(m) mid_arrived(m, 0)
+#else
+#define MID_ARRIVED(m)
+#endif
 constexpr uint32_t kAbandoned = 0xFFFFFFFFu;   // act_dist of a row given up early: above every canonical distance pattern
 // EAK > 0 (measurement builds, `make probe`): partial-distance early abandon.  Only the first EAK blocks of every row are
 // requested at first; the canonical fold of the partial chains is a LOWER bound of the row's canonical distance (every
@@ -327,7 +346,7 @@ __device__ __forceinline__ void dist_rounds_inflight(const IndexView& ix, const 
                 if (TAIL) pt[r] = row[NB * 32 + RS * 8 + (j & 3)];
             }
         }
-        if (base == first) mid();
+        if (base == first) { mid(); MID_ARRIVED(mid); }
         float acc[RIF];
 #pragma unroll
         for (int r = 0; r < RIF; r++) {
@@ -1613,6 +1632,26 @@ __device__ __forceinline__ int q16_insert(const Visited& v, uint32_t pid) {
     int idx;
     return q16_insert(v, pid, idx);
 }
+// q16_insert of an id the caller KNOWS to be absent (its own q16_lookup said kQRoom, nothing was inserted since but the other ids of
+// the same adjacency row, and a row holds no id twice): the same entry in the same place, without the two membership tests per try
+__device__ __forceinline__ int q16_insert_new(const Visited& v, uint32_t pid, int& idx) {
+    idx = -1;
+    const Q16Keys k = q16_keys(v, pid);
+    for (;;) {
+        const uint4 e1 = *reinterpret_cast<const uint4*>(v.tab + 4u * k.b1);
+        const uint4 e2 = *reinterpret_cast<const uint4*>(v.tab + 4u * k.b2);
+        const int f1 = q16_fill(e1), f2 = q16_fill(e2);
+        if (f1 == 8 && f2 == 8) return kQFull;
+        const bool second = f2 < f1;
+        const uint4 e = second ? e2 : e1;
+        const int f = second ? f2 : f1;
+        const uint32_t t = second ? k.t2 : k.t1, b = second ? k.b2 : k.b1;
+        const int wi = f >> 1;
+        const uint32_t cur = wi == 0 ? e.x : (wi == 1 ? e.y : (wi == 2 ? e.z : e.w));
+        const uint32_t nw = (f & 1) ? ((cur & 0x0000FFFFu) | (t << 16)) : ((cur & 0xFFFF0000u) | t);
+        if (atomicCAS(&v.tab[4u * b + (uint32_t)wi], cur, nw) == cur) { idx = (int)(8u * b) + f; return kQRoom; }
+    }
+}
 // index of pid in the on-chip set, whichever form it has (-1: not there)
 __device__ __forceinline__ int vis_index(const Visited& v, uint32_t pid) {
     return v.q16 ? q16_index(v, pid) : (v.tab ? tab_index(v, pid) : -1);
@@ -1889,16 +1928,19 @@ struct Counters {
 // Measurement build (make probe): where the leader of a four-wave walk and its helpers spend a zero-layer walk — 10-ns ticks
 // per segment, summed over all walks since the last reset (idist_probe_quad in idist_capi.hip).
 #ifdef IDIST_PROBE
-__device__ unsigned long long g_quad_probe[24];
-#define QP_DECL unsigned long long qp[12] = {}; unsigned long long qp_t = wall_clock64();
-#define QP_MARK(i) { const unsigned long long t_ = wall_clock64(); qp[i] += t_ - qp_t; qp_t = t_; }
-#define QP_CNT(i, v) { qp[i] += (unsigned long long)(v); }
-#define QP_FLUSH(on) { if ((on) && lane_id() == 0) for (int i_ = 0; i_ < 12; i_++) atomicAdd(&g_quad_probe[i_], qp[i_]); }
+// [0, 24): the four-wave walk (leader 0..11, helpers 12..20); [24, 48): the zero layer of the inlined thin principal walk, slot 24 + i
+// = mark i (idist_probe_thin; scripts/probe_thin_phases.py names the segments)
+__device__ unsigned long long g_quad_probe[48];
+// (32-bit accumulators per layer walk — 43 s of ticks — so that the stamps' own registers stay few)
+#define QP_DECL uint32_t qp[24] = {}; uint32_t qp_t = (uint32_t)wall_clock64();
+#define QP_MARK(i) { const uint32_t t_ = (uint32_t)wall_clock64(); qp[i] += t_ - qp_t; qp_t = t_; }
+#define QP_CNT(i, v) { qp[i] += (uint32_t)(v); }
+#define QP_FLUSH(on, base, n) { if ((on) && lane_id() == 0) for (int i_ = 0; i_ < (n); i_++) atomicAdd(&g_quad_probe[(base) + i_], (unsigned long long)qp[i_]); }
 #else
 #define QP_DECL
 #define QP_MARK(i)
 #define QP_CNT(i, v)
-#define QP_FLUSH(on)
+#define QP_FLUSH(on, base, n)
 #endif
 enum : uint32_t { kQuadPass = 0, kQuadSpec = 1, kQuadTake = 2, kQuadExit = 3 };
 constexpr uint32_t kSpecAbort = 0xFFFFFFFFu;            // spec_n: the row holds an id only the bitmap can answer for
@@ -2266,6 +2308,7 @@ __device__ __forceinline__ void search_layer(const IndexView& ix, const uint32_t
             const bool sure = ok_nb && stt == kQRoom, maybe = ok_nb && stt == kQFull;
             if constexpr (kSpec) { if (__ballot(maybe)) sq_off = true; }
             const uint64_t sm = __ballot(sure);
+            QP_MARK(12)
             // inlined walks: the verdicts of all 64 slots from the block's registers, against the threshold as the expansion began —
             // for both passes below; then the next candidate's block is requested (this one's registers are free)
             [[maybe_unused]] bool have_v = false, rej = false;
@@ -2281,13 +2324,25 @@ __device__ __forceinline__ void search_layer(const IndexView& ix, const uint32_t
                 }
             }
             wave_sync();
+            QP_MARK(13)
             if (sm) {
-                auto mid = [&]() {
-                    if (sure && q16_insert(vis, nb_pid, tab_idx) == kQFull) {           // filled up by this very expansion
+                auto mid_work = [&]() {
+                    QP_MARK(14)
+                    int ins = kQFound;
+                    // (inlined walks: the lookup above found these ids absent, and a row holds none twice — no membership tests)
+                    if constexpr (walk_blocks(LAT)) { if (sure) ins = q16_insert_new(vis, nb_pid, tab_idx); }
+                    else { if (sure) ins = q16_insert(vis, nb_pid, tab_idx); }
+                    if (ins == kQFull) {                                                // filled up by this very expansion
                         atomicOr(&vis.bits[nb_pid >> 5], vbit);
                         visited_note(vis, nb_pid);
                     }
+                    QP_MARK(15)
                 };
+#ifdef IDIST_PROBE
+                auto mid = mid_stamped(mid_work, [&]() { QP_MARK(16) QP_CNT(17, 1) });
+#else
+                auto& mid = mid_work;
+#endif
                 bool done = false;
                 if constexpr (walk_blocks(LAT)) {
                     if (have_v && fq.on) {
@@ -2424,7 +2479,8 @@ __device__ __forceinline__ void search_layer(const IndexView& ix, const uint32_t
         QP_MARK(5) QP_CNT(10, na)
         if (++guard > ix.n + 64u) { st.status |= kStGuard; break; }
     }
-    QP_FLUSH(kSpec && is_zero)
+    QP_FLUSH(kSpec && is_zero, 0, 12)
+    if constexpr (walk_blocks(LAT)) { QP_FLUSH(is_zero && ix.inl != nullptr && fq_principal<LAT>(fq), 24, 24) }
 }
 
 // n_dist / n_rows: work as executed here.  n_ref: distance calls as the REFERENCE makes them — `any` stops at the first
