@@ -1379,13 +1379,14 @@ extern "C" int idist_probe_quad(unsigned long long* out24, int reset) {
     }
     return 0;
 }
-// ... and the inlined thin principal walk's zero layer: the second half of g_quad_probe (mark i in out24[i])
-extern "C" int idist_probe_thin(unsigned long long* out24, int reset) {
+// ... and the inlined thin principal walk: its zero layer (mark i in out40[i], i < 24) and the whole query slot of the inlined
+// kernels (slot mark i in out40[24 + i], i < 16: QS_* in idist_device.hpp) — the rest of g_quad_probe
+extern "C" int idist_probe_thin(unsigned long long* out40, int reset) {
     if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out24, HIP_SYMBOL(g_quad_probe), 24 * sizeof(unsigned long long), 24 * sizeof(unsigned long long)) != hipSuccess) return -2;
+    if (hipMemcpyFromSymbol(out40, HIP_SYMBOL(g_quad_probe), 40 * sizeof(unsigned long long), 24 * sizeof(unsigned long long)) != hipSuccess) return -2;
     if (reset) {
-        unsigned long long z[24] = {};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_quad_probe), z, sizeof(z), sizeof(z)) != hipSuccess) return -3;
+        unsigned long long z[40] = {};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_quad_probe), z, sizeof(z), 24 * sizeof(unsigned long long)) != hipSuccess) return -3;
     }
     return 0;
 }

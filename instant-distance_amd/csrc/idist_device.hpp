@@ -756,16 +756,85 @@ __device__ __forceinline__ double shfl_xor_f64(double v, int m) {
 // y_i = sum_k B[i][k] (x[k] - mu[k]) in f64, component i in lane i (i < 56; the other lanes hold 0), and |x - mu|^2 in every lane: the
 // ONE evaluation both sides of the principal format use (filter_rows_principal_kernel for the rows, filter_stage_query for a query),
 // so that E_p and E_q speak about the same arithmetic.  x: a blocked row (padding zero), global or LDS.
+//
+// The chain of FMAs is the result (pos ascending, y then d2, one accumulator each); the order of the LOADS is not.  Written as one
+// loop the device compiler — at its register limit inside the walks — issued one basis load per position and waited for each: `stride`
+// dependent L2 round trips per query.  So the loop goes in blocks of kProjectK positions, two blocks in flight: the loads of the next
+// block (its kProjectK basis values per lane, and x - mu of position p in lane p & 31, one load each) are issued, a scheduling
+// barrier pins them there, and only then the current block's FMAs run, each taking its d from that lane (v_readlane_b32: d is the
+// same number in every lane).  Strides are multiples of 16: a block's upper half may lie past the row; it then loads the lower half
+// once more (in bounds, unused) and its FMAs are skipped.  The emulator build takes the plain loop (IDIST_PROJECT_BLOCKED: the blocks
+// there too, tests/host/project.cpp compares the two bit for bit); -DIDIST_PROJECT_PLAIN gives a measurement build the plain loop.
+constexpr uint32_t kProjectK = 32;
+struct ProjectBlock {
+    float b[kProjectK];     // B[p][lane] of the block's positions
+    float x, mu;            // x[p], mu[p] of position p = lane & 31 of the block, as loaded (widened and subtracted once they are used)
+};
+__device__ __forceinline__ double readlane_f64(double v, int src) {
+    const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+    const uint32_t lo = readlane_u32((uint32_t)b, src), hi = readlane_u32((uint32_t)(b >> 32), src);
+    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+// requests block p0 (a multiple of kProjectK; past the row: the last granule again, never used)
+__device__ __forceinline__ void project_load(const IndexView& ix, const float* x, uint32_t p0, int lane, ProjectBlock& blk) {
+    const uint32_t last = ix.stride - 16u;
+    const uint32_t lo = p0 < last ? p0 : last, hi = p0 + 16u < last ? p0 + 16u : last;
+    // (a wave-uniform base per half and lane + 64 k behind it: one address register for the 32 loads, the rest immediate offsets)
+    const float* blo = ix.f.basis + (size_t)lo * 64u;
+    const float* bhi = ix.f.basis + (size_t)hi * 64u;
+#pragma unroll
+    for (uint32_t k = 0; k < 16u; k++) blk.b[k] = blo[(uint32_t)lane + 64u * k];
+#pragma unroll
+    for (uint32_t k = 0; k < 16u; k++) blk.b[16u + k] = bhi[(uint32_t)lane + 64u * k];
+    const uint32_t pl = ((lane & 16) ? hi : lo) + (uint32_t)(lane & 15);
+    blk.x = x[pl];
+    blk.mu = ix.f.mu[pl];
+}
+__device__ __forceinline__ void project_fma(const IndexView& ix, uint32_t p0, const ProjectBlock& blk, double& y, double& d2) {
+#ifndef IDIST_EMU
+    __builtin_amdgcn_sched_barrier(0);               // the next block's loads stay above, this block's arithmetic below
+#endif
+    const double dl = (double)blk.x - (double)blk.mu;
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        const double d = readlane_f64(dl, k);
+        y = __builtin_fma((double)blk.b[k], d, y);
+        d2 = __builtin_fma(d, d, d2);
+    }
+    if (p0 + 16u >= ix.stride) return;               // (wave-uniform)
+#pragma unroll
+    for (int k = 16; k < 32; k++) {
+        const double d = readlane_f64(dl, k);
+        y = __builtin_fma((double)blk.b[k], d, y);
+        d2 = __builtin_fma(d, d, d2);
+    }
+}
 __device__ __forceinline__ double filter_project(const IndexView& ix, const float* x, double& d2) {
     const int lane = lane_id();
-    const float* bt = ix.f.basis + lane;
     double y = 0.0;
     d2 = 0.0;
+#if defined(IDIST_EMU) ? !defined(IDIST_PROJECT_BLOCKED) : defined(IDIST_PROJECT_PLAIN)
+    const float* bt = ix.f.basis + lane;
     for (uint32_t pos = 0; pos < ix.stride; pos++) {
         const double d = (double)x[pos] - (double)ix.f.mu[pos];
         y = __builtin_fma((double)bt[(size_t)pos * 64u], d, y);
         d2 = __builtin_fma(d, d, d2);
     }
+#else
+    ProjectBlock a, b;
+    uint32_t p0 = 0;
+#ifndef IDIST_EMU
+    asm volatile("" : "+s"(p0));                     // (the first block's addresses are made here, not kept in registers across a walk)
+#endif
+    project_load(ix, x, p0, lane, a);
+    for (; p0 < ix.stride; p0 += 2u * kProjectK) {
+        project_load(ix, x, p0 + kProjectK, lane, b);
+        project_fma(ix, p0, a, y, d2);
+        if (p0 + kProjectK >= ix.stride) break;      // (wave-uniform)
+        project_load(ix, x, p0 + 2u * kProjectK, lane, a);
+        project_fma(ix, p0 + kProjectK, b, y, d2);
+    }
+#endif
     return lane < kFiltPrincipalM ? y : 0.0;         // (lanes 56..63 read zeros of B: 0 * inf would be NaN)
 }
 // |fl(y) - y^|-side error of a principal row or query, rounded up to f32: the lattice error e2 = sum e_i^2 as evaluated, the f64
@@ -1930,17 +1999,39 @@ struct Counters {
 #ifdef IDIST_PROBE
 // [0, 24): the four-wave walk (leader 0..11, helpers 12..20); [24, 48): the zero layer of the inlined thin principal walk, slot 24 + i
 // = mark i (idist_probe_thin; scripts/probe_thin_phases.py names the segments)
-__device__ unsigned long long g_quad_probe[48];
+// [48, 64): the whole query slot of the inlined kernels, slot 48 + i = mark i of search_kernel / search_layers (QS_*, below)
+__device__ unsigned long long g_quad_probe[64];
 // (32-bit accumulators per layer walk — 43 s of ticks — so that the stamps' own registers stay few)
 #define QP_DECL uint32_t qp[24] = {}; uint32_t qp_t = (uint32_t)wall_clock64();
 #define QP_MARK(i) { const uint32_t t_ = (uint32_t)wall_clock64(); qp[i] += t_ - qp_t; qp_t = t_; }
 #define QP_CNT(i, v) { qp[i] += (uint32_t)(v); }
 #define QP_FLUSH(on, base, n) { if ((on) && lane_id() == 0) for (int i_ = 0; i_ < (n); i_++) atomicAdd(&g_quad_probe[(base) + i_], (unsigned long long)qp[i_]); }
+// One query's stay in a slot of an inlined kernel, from one queue pull to the next: 0 queue pull (with the previous query's flush of
+// these very words), 1 query into LDS, 2 filter_stage_query, 3 push_entry, 4 upper layers, 5 layer transitions (w_cull + visited_clear
+// + re-mark), 6 zero layer (the QP marks above split its expansions), 7 emit + clear + the counter atomics; counts: 8 upper-layer
+// expansions, 9 queries; once per slot: 10 slots, 11 ticks from a slot's first pull to its exit.  What a launch's slots spend beyond
+// these — kernel time x slots less the segments — is their wait for the last walks of the launch (and for their own start).
+constexpr int kSlotMarks = 10;
+struct SlotStamps { uint32_t t[kSlotMarks] = {}; uint32_t last = 0, born = 0; };
+#define QS_DECL SlotStamps qs; qs.last = qs.born = (uint32_t)wall_clock64();
+#define QS_END() { if (lane_id() == 0) { atomicAdd(&g_quad_probe[58], 1ull); atomicAdd(&g_quad_probe[59], (unsigned long long)((uint32_t)wall_clock64() - qs.born)); } }
+#define QS_PARAM , SlotStamps& qs
+#define QS_ARG , qs
+#define QS_MARK(i) { const uint32_t t_ = (uint32_t)wall_clock64(); qs.t[i] += t_ - qs.last; qs.last = t_; }
+#define QS_CNT(i, v) { qs.t[i] += (uint32_t)(v); }
+#define QS_FLUSH() { if (lane_id() == 0) for (int i_ = 0; i_ < kSlotMarks; i_++) { atomicAdd(&g_quad_probe[48 + i_], (unsigned long long)qs.t[i_]); qs.t[i_] = 0u; } }
 #else
 #define QP_DECL
 #define QP_MARK(i)
 #define QP_CNT(i, v)
 #define QP_FLUSH(on, base, n)
+#define QS_DECL
+#define QS_PARAM
+#define QS_ARG
+#define QS_MARK(i)
+#define QS_CNT(i, v)
+#define QS_FLUSH()
+#define QS_END()
 #endif
 enum : uint32_t { kQuadPass = 0, kQuadSpec = 1, kQuadTake = 2, kQuadExit = 3 };
 constexpr uint32_t kSpecAbort = 0xFFFFFFFFu;            // spec_n: the row holds an id only the bitmap can answer for

@@ -308,26 +308,31 @@ __device__ __forceinline__ void visited_attach_q16(Visited& v, uint32_t log2_ent
 // instantiation of search_layer (kWalkInlineBit): search_kernel's own steps, LAT the instantiation's code.
 template <int NB, int RS, int TAIL, int LAT>
 __device__ __forceinline__ void search_layers(const IndexView& ix, const SearchArgs& a, const Smem& sm, WState& st, Visited& vis, Counters& ctr,
-                                              QuadLead& ql, const FilterQFor<NB, RS, TAIL, LAT>& fq) {
+                                              QuadLead& ql, const FilterQFor<NB, RS, TAIL, LAT>& fq QS_PARAM) {
     const int lane = lane_id();
     DistLog nolog{nullptr, 0u};
     push_entry<NB, RS, TAIL>(ix, sm.q, st, vis, sm.act_pid, sm.act_dist, ctr, nolog);
+    QS_MARK(3)
     for (int cur = (int)ix.n_upper;; cur--) {
         const bool is_zero = cur == 0;
         st.ef = is_zero ? (int)a.ef : 1;
         if (is_zero) {
             search_layer<NB, RS, TAIL, LAT>(ix, ix.zero, kM2, kM2, sm.q, st, vis, sm.act_pid, sm.act_dist, ctr, true, nolog, &ql, fq);
+            QS_MARK(6)
             break;
         }
         const uint32_t* rows = ix.upper + (size_t)ix.layer_off[cur - 1] * kM;
         search_layer<NB, RS, TAIL, LAT>(ix, rows, kM, kM, sm.q, st, vis, sm.act_pid, sm.act_dist, ctr, false, nolog, &ql, fq);
+        QS_MARK(4)
         w_cull(st);
         visited_clear(vis);
         visited_begin(vis, (uint32_t)st.plen);
         for (int i = lane; i < st.plen; i += 64) visited_mark(vis, (uint32_t)st.W[i]);
         visited_added(vis, (uint32_t)st.plen);
         wave_sync();
+        QS_MARK(5)
     }
+    QS_CNT(8, ctr.n_expU)
 }
 
 // LAT: walk mode (kWalkClassic / kWalkLatency / kWalkOverlap, see search_layer).
@@ -362,10 +367,12 @@ __global__ __launch_bounds__(walk_quad(LAT) ? 256 : 64) IDIST_WAVES_ATTR(LAT) vo
     for (uint32_t i = lane; i < a.vis.dirty_words; i += 64) sm.dirty[i] = 0u;
     visited_clear(vis);                                                // LDS side; the slot's bitmap is clean between launches
     bool first_pull = true;
+    QS_DECL
     for (;;) {
         uint32_t qi = 0;
         if (lane == 0) qi = atomicAdd(a.next, 1u) - a.queue_base;
         qi = uniform_u32(qi);
+        QS_MARK(0)
         // the head counts on from launch to launch: a launch that does not find it inside its own window [queue_base,
         // queue_base + nq + gridDim.x) was replayed (graph) or interleaved with another launch of the same context —
         // it would write nothing and the caller would read stale results: say so
@@ -379,10 +386,12 @@ __global__ __launch_bounds__(walk_quad(LAT) ? 256 : 64) IDIST_WAVES_ATTR(LAT) vo
         const float* qsrc = a.queries + (size_t)qi * ix.dim;
         for (uint32_t e = lane; e < ix.dim; e += 64) sm.q[blocked_pos(e, nb)] = qsrc[e];
         wave_sync();
+        QS_MARK(1)
 
         // the query on the reject filter's lattice (walks compiled with it): registers, for the whole walk
         FilterQFor<NB, RS, TAIL, LAT> fq;
         if constexpr (walk_filter(LAT)) filter_stage_query(ix, sm.q, fq);
+        QS_MARK(2)
 
         WState st{sm.W, 0, 1, 0, 0u, (int)a.tie_cap};
         if (a.tie_spill) { st.spill = a.tie_spill + (size_t)slot * a.tie_spill_cap; st.spill_cap = a.tie_spill_cap; }
@@ -390,8 +399,8 @@ __global__ __launch_bounds__(walk_quad(LAT) ? 256 : 64) IDIST_WAVES_ATTR(LAT) vo
         DistLog nolog{nullptr, 0u};
         // search.reset(), :357: the visited set was emptied when the slot's previous search ended
         if constexpr (walk_inline(LAT)) {
-            if (fq.principal) search_layers<NB, RS, TAIL, LAT | kWalkOnlyPrincipalBit>(ix, a, sm, st, vis, ctr, ql, fq);
-            else search_layers<NB, RS, TAIL, LAT | kWalkOnlyIdentityBit>(ix, a, sm, st, vis, ctr, ql, fq);
+            if (fq.principal) search_layers<NB, RS, TAIL, LAT | kWalkOnlyPrincipalBit>(ix, a, sm, st, vis, ctr, ql, fq QS_ARG);
+            else search_layers<NB, RS, TAIL, LAT | kWalkOnlyIdentityBit>(ix, a, sm, st, vis, ctr, ql, fq QS_ARG);
         } else {
         push_entry<NB, RS, TAIL>(ix, sm.q, st, vis, sm.act_pid, sm.act_dist, ctr, nolog);  // :364
         for (int cur = (int)ix.n_upper;; cur--) {                      // :365
@@ -451,7 +460,9 @@ __global__ __launch_bounds__(walk_quad(LAT) ? 256 : 64) IDIST_WAVES_ATTR(LAT) vo
                 }
             }
         }
+        if constexpr (walk_inline(LAT)) { QS_MARK(7) QS_CNT(9, 1) QS_FLUSH() }
     }
+    if constexpr (walk_inline(LAT)) { QS_END() }
     if constexpr (walk_quad(LAT)) quad_release_helpers(ql);
     if (lane == 0 && status) {
         atomicOr(a.status, status);
