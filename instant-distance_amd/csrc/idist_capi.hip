@@ -126,17 +126,29 @@ struct Scratch {
     }
 };
 
-// Grow-only staging: p holds at least `need` bytes afterwards, exactly `need` if it had to grow (hipFree waits for the device).
-// After a failed allocation p is null and cap 0, so the *_free functions and the next call stay safe.
-template <typename T> idist_status grow(T*& p, size_t& cap, size_t need) {
-    if (need <= cap) return IDIST_OK;
-    hipFree(p);
-    p = nullptr;
-    cap = 0;
-    HIPCHK(hipMalloc((void**)&p, need));
-    cap = need;
-    return IDIST_OK;
-}
+// Grow-only device staging that frees itself: what a search context or a partitioned index keeps between calls.  Reads as the T* it
+// holds; T = void for the few buffers that are read as two types (as<U>()).  Movable, so that it can live in a std::vector.
+template <typename T = void> struct DevBuf {
+    T* p = nullptr;
+    size_t cap = 0;                                      // bytes
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~DevBuf() { hipFree(p); }
+    operator T*() const { return p; }
+    template <typename U> U* as() const { return static_cast<U*>(p); }
+    // p holds at least `need` BYTES afterwards, exactly `need` if it had to grow (hipFree waits for the device).  The device the
+    // memory belongs on is current.  After a failed allocation p is null and cap 0, so the next call and the destructor stay safe.
+    idist_status grow(size_t need) {
+        if (need <= cap) return IDIST_OK;
+        hipFree(p);
+        p = nullptr;
+        cap = 0;
+        HIPCHK(hipMalloc((void**)&p, need));
+        cap = need;
+        return IDIST_OK;
+    }
+};
 // `need` for the buffers that grow by doubling from `lo` bytes (0 stays 0)
 inline size_t doubled_from(size_t lo, size_t need) {
     if (!need) return 0;
@@ -399,18 +411,16 @@ struct idist_search_ctx {
     int32_t device = 0;            // copies of what growing the context needs: nothing is read through `idx` after creation
     int n_cu = 256;
     Knobs knobs;
+    // Every DevBuf below is staging the context owns: it only grows (byte capacities), and it frees itself when idist_search_ctx_free
+    // deletes the context.  d_visited, d_next, d_tie_spill and the pinned h_io above carry state between launches and are replaced,
+    // not grown; idist_search_ctx_free releases those by hand.
     // staging for the host-pointer API
-    float* d_q = nullptr;
-    uint32_t* d_pid = nullptr;
-    float* d_dist = nullptr;
-    uint32_t* d_cnt = nullptr;
-    uint32_t* d_ctr = nullptr;
-    size_t cap_q = 0, cap_pid = 0, cap_dist = 0, cap_cnt = 0, cap_ctr = 0;   // bytes, as every cap_* below
-    float* d_qn = nullptr;         // what MetricPasses::prepare writes for a launch (launch_search): the queries the kernel reads
-    size_t cap_qn = 0;             // (cosine: normalised; DOT: with the trailing 0, [nq][kdim])
-    float* d_sq = nullptr;         // DOT indexes: s(q) per query of the launch, for the report pass
-    size_t cap_sq = 0;
-    // Staging of the ladder searches (grow-only, freed with the context), by role.
+    DevBuf<float> d_q, d_dist;
+    DevBuf<uint32_t> d_pid, d_cnt, d_ctr;
+    DevBuf<float> d_qn;            // what MetricPasses::prepare writes for a launch (launch_search): the queries the kernel reads
+                                   // (cosine: normalised; DOT: with the trailing 0, [nq][kdim])
+    DevBuf<float> d_sq;            // DOT indexes: s(q) per query of the launch, for the report pass
+    // Staging of the ladder searches (owned and freed as above), by role.
     //  * The ladder's, shared by the restricted and the range search: the pending flags, the ascending list of the pending queries,
     //    their number and their gathered rows (al_flag, al_list, al_npend, al_pq), every query's rung and counters (al_orung, al_octr).
     //    A rung's result rows and an exact scan's segment lists use d_pid / d_dist / d_cnt / d_ctr above, the queries d_q / d_qn / d_sq.
@@ -422,13 +432,10 @@ struct idist_search_ctx {
     //    completion order, every query's count, offset and report term.  rg_list: the second pending list (a rung's copy pass still
     //    reads the list that the next rung's pending pass replaces).  The restricted range search stages its sets in the restricted
     //    search's buffers: al_bits, al_setof, |A_s| (al_size), the permitted rungs per set (al_start) and per query (al_first).
-    struct Buf {
-        void* p = nullptr;
-        size_t cap = 0;
-        template <typename T> T* as() const { return static_cast<T*>(p); }
-    };
-    Buf al_flag, al_list, al_npend, al_pq, al_orung, al_octr;
-    Buf al_bits, al_ids, al_opid, al_odist, al_ocnt, al_mpid, al_mdist, al_mcnt, al_setof, al_size, al_start, al_first, al_raw;
+    DevBuf<uint32_t> al_flag, al_list, al_npend, al_orung, al_octr;
+    DevBuf<float> al_pq;
+    DevBuf<uint32_t> al_bits, al_ids, al_opid, al_ocnt, al_mpid, al_mcnt, al_setof, al_size, al_start, al_first, al_raw;
+    DevBuf<> al_odist, al_mdist;   // distances: f32 to the report pass, their bits to the ranking kernels
     // The passes a call times (ladder_timed): a pair of events each, created on first use, resolved when the call has synchronised its
     // stream.  A restricted search: a pair per select and pending pass of at most seven rungs + the exact step's two; several sets: + the
     // count pass and a pending pass in front of every launch.  A range search: three pairs per rung (select, pending, copy) + five
@@ -441,7 +448,9 @@ struct idist_search_ctx {
     // (idist_search_ctx_allowed_kernel_ms); [3..5]: the last range search's select (+ init, prefix, pending, copy, lims), exact scan
     // and sort kernels (idist_search_ctx_range_kernel_ms)
     float al_ms[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    Buf rg_radius, rg_lim, rg_term, rg_cnt, rg_off, rg_stepcnt, rg_stepoff, rg_chunks, rg_keys, rg_exoff, rg_exlen, rg_lims, rg_opid, rg_odist, rg_list;
+    DevBuf<float> rg_radius, rg_term, rg_odist;
+    DevBuf<uint32_t> rg_lim, rg_cnt, rg_stepcnt, rg_exlen, rg_opid, rg_list;
+    DevBuf<uint64_t> rg_off, rg_stepoff, rg_chunks, rg_keys, rg_exoff, rg_lims;
     bool rg_valid = false;         // a successful range call's results are held (until the next one, or the fetch)
     uint32_t rg_nq = 0;
     uint64_t rg_total = 0;
@@ -459,7 +468,8 @@ struct idist_search_ctx {
 };
 
 // A partitioned index (include/idist.h): borrowed parts + everything one caller needs to search them as one — the role of one
-// `&mut Search` over all parts.  Staging memory only grows.
+// `&mut Search` over all parts.  The indexes are borrowed.  The object owns a search context per non-empty part (freed by
+// idist_partitioned_free), its stream and events, and every DevBuf below: staging that only grows and frees itself with the object.
 struct idist_partitioned {
     struct Part {
         const idist_index* idx = nullptr;
@@ -467,23 +477,18 @@ struct idist_partitioned {
         idist_search_ctx* ctx = nullptr;     // nullptr: empty part (nothing to search); its stream is the part's stream
         int dev_slot = 0;                    // index into `devs`
         // parts away from the merge device write here first, then one peer copy per array
-        uint32_t *r_pid = nullptr, *r_cnt = nullptr, *r_ctr = nullptr;
-        float* r_dist = nullptr;
-        size_t r_cap_pid = 0, r_cap_dist = 0, r_cap_cnt = 0, r_cap_ctr = 0;
+        DevBuf<uint32_t> r_pid, r_cnt, r_ctr;
+        DevBuf<float> r_dist;
         // range search, a part away from the merge device: its keys, offsets, counts and counters ON the merge device (peer copies on
-        // the part's stream); a part on the merge device is read where its context holds them
-        uint64_t *m_keys = nullptr, *m_off = nullptr;
-        uint32_t *m_cnt = nullptr, *m_ctr = nullptr;
-        size_t m_cap_keys = 0, m_cap_off = 0, m_cap_cnt = 0, m_cap_ctr = 0;
+        // the part's stream; grown with the merge device current); a part on the merge device is read where its context holds them
+        DevBuf<uint64_t> m_keys, m_off;
+        DevBuf<uint32_t> m_cnt, m_ctr;
     };
     struct Dev {
         int32_t device = 0;
-        float* d_q = nullptr;                // the batch's queries, uploaded once per distinct device
-        size_t cap_q = 0;
-        uint32_t* d_setof = nullptr;         // restricted search: the set of every query, uploaded once per distinct device
-        size_t cap_setof = 0;
-        float* d_sq = nullptr;               // range search over DOT parts: s(q) of the batch's queries (the parts' limits need the report's term)
-        size_t cap_sq = 0;
+        DevBuf<float> d_q;                   // the batch's queries, uploaded once per distinct device
+        DevBuf<uint32_t> d_setof;            // restricted search: the set of every query, uploaded once per distinct device
+        DevBuf<float> d_sq;                  // range search over DOT parts: s(q) of the batch's queries (the parts' limits need the report's term)
     };
     std::vector<Part> parts;
     std::vector<Dev> devs;
@@ -491,21 +496,17 @@ struct idist_partitioned {
     uint32_t dim = 0;
     int32_t metric = 0, merge_device = 0;
     float dot_S = 0.0f;                      // DOT: the bound every part holds
-    float *d_qm = nullptr, *d_sq = nullptr;  // DOT, on the merge device: the batch's queries and their s(q), for the report after the merge
-    size_t cap_qm = 0, cap_sq = 0;
+    DevBuf<float> d_qm, d_sq;                // DOT, on the merge device: the batch's queries and their s(q), for the report after the merge
     // on the merge device: the parts' lists [P][nq][width] and the merged result [nq][out_width]
-    uint32_t *s_pid = nullptr, *s_cnt = nullptr, *s_ctr = nullptr, *o_pid = nullptr, *o_cnt = nullptr, *o_ctr = nullptr;
-    float *s_dist = nullptr, *o_dist = nullptr;
-    size_t cap_s_pid = 0, cap_s_dist = 0, cap_s_cnt = 0, cap_s_ctr = 0, cap_o_pid = 0, cap_o_dist = 0, cap_o_cnt = 0, cap_o_ctr = 0;
-    uint32_t* s_rung = nullptr;              // restricted search: the parts' rungs [P][nq]
-    size_t cap_s_rung = 0;
+    DevBuf<uint32_t> s_pid, s_cnt, s_ctr, o_pid, o_cnt, o_ctr;
+    DevBuf<float> s_dist, o_dist;
+    DevBuf<uint32_t> s_rung;                 // restricted search: the parts' rungs [P][nq]
     float al_slice_ms = 0.0f;                // ... and the host time its last call spent on the bitmaps: upload + slice, every part
     // range search, on the merge device: the merged counts, lims and the chunk sums of their prefix sum; the merged result, which no
     // other call writes and idist_partitioned_range_fetch hands out once
-    uint32_t *rm_c = nullptr, *rm_opid = nullptr;
-    uint64_t *rm_lims = nullptr, *rm_chunks = nullptr;
-    float* rm_odist = nullptr;
-    size_t cap_rm_c = 0, cap_rm_lims = 0, cap_rm_chunks = 0, cap_rm_opid = 0, cap_rm_odist = 0;
+    DevBuf<uint32_t> rm_c, rm_opid;
+    DevBuf<uint64_t> rm_lims, rm_chunks;
+    DevBuf<float> rm_odist;
     bool rg_valid = false;                   // a successful range call's results are held (until the next one, or the fetch)
     uint64_t rg_total = 0;
     float rg_merge_ms = -1.0f;               // the last range call's counts, prefix and merge kernels (-1: none has run)
@@ -1889,8 +1890,8 @@ idist_status launch_search(const idist_index* ix, idist_search_ctx* ctx, const f
     const MetricPasses metric(ix);
     const bool passes = metric.any() && !prepared;
     if (passes) {
-        CHK(grow(ctx->d_qn, ctx->cap_qn, doubled_from(4096, metric.qk_floats(nq) * 4)));
-        CHK(grow(ctx->d_sq, ctx->cap_sq, doubled_from(256, metric.sq_floats(nq) * 4)));
+        CHK(ctx->d_qn.grow(doubled_from(4096, metric.qk_floats(nq) * 4)));
+        CHK(ctx->d_sq.grow(doubled_from(256, metric.sq_floats(nq) * 4)));
         CHK(metric.prepare(d_q, ctx->d_qn, ctx->d_sq, nq, stream, &d_q));
     }
     SearchArgs a{};
@@ -2447,19 +2448,6 @@ void idist_search_ctx_free(idist_search_ctx* c) {
     hipFree(c->d_tie_spill);
     hipFree(c->d_next);
     if (c->h_io) hipHostFree(c->h_io);
-    hipFree(c->d_q);
-    hipFree(c->d_qn);
-    hipFree(c->d_sq);
-    hipFree(c->d_pid);
-    hipFree(c->d_dist);
-    hipFree(c->d_cnt);
-    hipFree(c->d_ctr);
-    for (idist_search_ctx::Buf* b : {&c->al_bits, &c->al_ids, &c->al_flag, &c->al_list, &c->al_npend, &c->al_pq, &c->al_opid, &c->al_odist,
-                                     &c->al_ocnt, &c->al_orung, &c->al_octr, &c->al_mpid, &c->al_mdist, &c->al_mcnt, &c->al_setof, &c->al_size,
-                                     &c->al_start, &c->al_first, &c->al_raw, &c->rg_radius, &c->rg_lim, &c->rg_term,
-                                     &c->rg_cnt, &c->rg_off, &c->rg_stepcnt, &c->rg_stepoff, &c->rg_chunks, &c->rg_keys, &c->rg_exoff, &c->rg_exlen,
-                                     &c->rg_lims, &c->rg_opid, &c->rg_odist, &c->rg_list})
-        hipFree(b->p);
     for (hipEvent_t e : c->al_ev)
         if (e) hipEventDestroy(e);
     for (uint32_t i = 0; i < IDIST_EVENT_RING; i++) {
@@ -2467,7 +2455,7 @@ void idist_search_ctx_free(idist_search_ctx* c) {
         if (c->ev1[i]) hipEventDestroy(c->ev1[i]);
     }
     if (c->stream) hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                      // the staging (every DevBuf) goes here, after its stream: hipFree synchronises the device
 }
 
 idist_status idist_search_ctx_reserve(idist_search_ctx* ctx, uint32_t slots) {
@@ -2744,14 +2732,14 @@ static idist_status search_batch_impl(const idist_index* idx, idist_search_ctx* 
             return IDIST_OK;
         }
     }
-    CHK(grow(ctx->d_q, ctx->cap_q, qb));
-    CHK(grow(ctx->d_pid, ctx->cap_pid, ob));
-    CHK(grow(ctx->d_dist, ctx->cap_dist, ob));
-    CHK(grow(ctx->d_cnt, ctx->cap_cnt, (size_t)nq * 4));
-    CHK(grow(ctx->d_ctr, ctx->cap_ctr, (size_t)nq * 12));
+    CHK(ctx->d_q.grow(qb));
+    CHK(ctx->d_pid.grow(ob));
+    CHK(ctx->d_dist.grow(ob));
+    CHK(ctx->d_cnt.grow((size_t)nq * 4));
+    CHK(ctx->d_ctr.grow((size_t)nq * 12));
     HIPCHK(hipMemcpyAsync(ctx->d_q, queries, qb, hipMemcpyHostToDevice, ctx->stream));
     for (;;) {
-        CHK(launch_search(idx, ctx, ctx->d_q, nq, ctx->d_pid, ctx->d_dist, ctx->d_cnt, out_counters ? ctx->d_ctr : nullptr,
+        CHK(launch_search(idx, ctx, ctx->d_q, nq, ctx->d_pid, ctx->d_dist, ctx->d_cnt, out_counters ? ctx->d_ctr.p : nullptr,
                           ctx->stream));
         HIPCHK(hipMemcpyAsync(out_pid, ctx->d_pid, ob, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipMemcpyAsync(out_dist, ctx->d_dist, ob, hipMemcpyDeviceToHost, ctx->stream));
@@ -2943,6 +2931,42 @@ idist_status idist_replicate_rccl(const idist_index* root, const int32_t* device
 #endif
 }
 
+extern "C++" {
+namespace {
+// Calls that block on the host side by side (shards, the parts of a partitioned index): work(i) for every i < n with runs(i).  The
+// first runs on the calling thread, every other on a thread of its own — or here, after the others were started, when no thread is
+// to be had.  Every thread is joined before this returns.  True when one failed: *f is the first such i, with its status and
+// message (g_err is thread-local: a worker's message is kept where it ran).
+struct Failure { size_t i = 0; idist_status status = IDIST_OK; std::string msg; };
+template <typename Runs, typename Work> bool fan_out(size_t n, Runs&& runs, Work&& work, Failure* f) {
+    std::vector<idist_status> st(n, IDIST_OK);
+    std::vector<std::string> msg(n);
+    auto one = [&](size_t i) {
+        st[i] = work(i);
+        if (st[i] != IDIST_OK) msg[i] = g_err;
+    };
+    {
+        std::vector<std::thread> threads;
+        size_t first = n;
+        for (size_t i = 0; i < n; i++) {
+            if (!runs(i)) continue;
+            if (first == n) { first = i; continue; }
+            try {
+                threads.emplace_back(one, i);
+            } catch (...) {
+                one(i);
+            }
+        }
+        if (first < n) one(first);
+        for (auto& t : threads) t.join();
+    }
+    for (size_t i = 0; i < n; i++)
+        if (st[i] != IDIST_OK) { *f = Failure{i, st[i], msg[i]}; return true; }
+    return false;
+}
+}  // namespace
+}  // extern "C++"
+
 idist_status idist_search_batch_sharded(const idist_index* const* replicas, idist_search_ctx* const* ctxs, uint32_t n_shards,
                                         const float* queries, uint32_t nq, uint32_t* out_pid, float* out_dist,
                                         uint32_t* out_count, uint32_t* out_counters) {
@@ -2958,23 +2982,17 @@ idist_status idist_search_batch_sharded(const idist_index* const* replicas, idis
     if (nq == 0) return IDIST_OK;
     if (!queries || !out_count) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
     const uint32_t ef = replicas[0]->cfg.ef_search, dim = replicas[0]->dim;
-    std::vector<idist_status> st(n_shards, IDIST_OK);
-    std::vector<std::string> msg(n_shards);
-    auto work = [&](uint32_t i) {
-        // contiguous block partition, the reference's own concurrency model (callers split queries over threads)
-        const uint32_t lo = (uint32_t)((uint64_t)nq * i / n_shards), hi = (uint32_t)((uint64_t)nq * (i + 1) / n_shards);
-        if (hi == lo) return;
-        st[i] = idist_search_batch(replicas[i], ctxs[i], queries + (size_t)lo * dim, hi - lo,
-                                   out_pid ? out_pid + (size_t)lo * ef : nullptr, out_dist ? out_dist + (size_t)lo * ef : nullptr,
-                                   out_count + lo, out_counters ? out_counters + (size_t)lo * 3 : nullptr);
-        if (st[i] != IDIST_OK) msg[i] = g_err;                 // g_err is thread-local
+    // contiguous block partition, the reference's own concurrency model (callers split queries over threads)
+    auto lo_of = [&](size_t i) { return (uint32_t)((uint64_t)nq * i / n_shards); };
+    auto shard = [&](size_t i) {
+        const uint32_t lo = lo_of(i), hi = lo_of(i + 1);
+        return idist_search_batch(replicas[i], ctxs[i], queries + (size_t)lo * dim, hi - lo,
+                                  out_pid ? out_pid + (size_t)lo * ef : nullptr, out_dist ? out_dist + (size_t)lo * ef : nullptr,
+                                  out_count + lo, out_counters ? out_counters + (size_t)lo * 3 : nullptr);
     };
-    std::vector<std::thread> threads;
-    for (uint32_t i = 1; i < n_shards; i++) threads.emplace_back(work, i);
-    work(0);
-    for (auto& t : threads) t.join();
-    for (uint32_t i = 0; i < n_shards; i++)
-        if (st[i] != IDIST_OK) return fail(st[i], "shard %u (device %d): %s", i, replicas[i]->device, msg[i].c_str());
+    Failure f;
+    if (fan_out(n_shards, [&](size_t i) { return lo_of(i + 1) != lo_of(i); }, shard, &f))
+        return fail(f.status, "shard %u (device %d): %s", (uint32_t)f.i, replicas[f.i]->device, f.msg.c_str());
     return IDIST_OK;
 }
 
@@ -3072,9 +3090,8 @@ idist_status idist_partitioned_new(const idist_index* const* parts, uint32_t n_p
         int slot = -1;
         for (size_t d = 0; d < p->devs.size(); d++) if (p->devs[d].device == parts[i]->device) slot = (int)d;
         if (slot < 0) {
-            idist_partitioned::Dev dv;
-            dv.device = parts[i]->device;
-            p->devs.push_back(dv);
+            p->devs.emplace_back();
+            p->devs.back().device = parts[i]->device;
             slot = (int)p->devs.size() - 1;
         }
         pt.dev_slot = slot;
@@ -3091,20 +3108,11 @@ idist_status idist_partitioned_new(const idist_index* const* parts, uint32_t n_p
 void idist_partitioned_free(idist_partitioned* p) {
     if (!p) return;
     // (the parts are borrowed and may already be gone: nothing of them is touched here)
-    for (auto& pt : p->parts) {
-        idist_search_ctx_free(pt.ctx);
-        hipFree(pt.r_pid); hipFree(pt.r_dist); hipFree(pt.r_cnt); hipFree(pt.r_ctr);
-        hipFree(pt.m_keys); hipFree(pt.m_off); hipFree(pt.m_cnt); hipFree(pt.m_ctr);
-    }
-    for (auto& dv : p->devs) { hipFree(dv.d_q); hipFree(dv.d_setof); hipFree(dv.d_sq); }
-    hipFree(p->rm_c); hipFree(p->rm_lims); hipFree(p->rm_chunks); hipFree(p->rm_opid); hipFree(p->rm_odist);
-    hipFree(p->d_qm); hipFree(p->d_sq); hipFree(p->s_rung);
-    hipFree(p->s_pid); hipFree(p->s_dist); hipFree(p->s_cnt); hipFree(p->s_ctr);
-    hipFree(p->o_pid); hipFree(p->o_dist); hipFree(p->o_cnt); hipFree(p->o_ctr);
+    for (auto& pt : p->parts) idist_search_ctx_free(pt.ctx);
     if (p->ev0) hipEventDestroy(p->ev0);
     if (p->ev1) hipEventDestroy(p->ev1);
     if (p->stream) hipStreamDestroy(p->stream);
-    delete p;
+    delete p;                      // (the staging of the object, its parts and devices: as in idist_search_ctx_free)
 }
 
 idist_status idist_partitioned_get_info(const idist_partitioned* p, idist_partitioned_info* out) {
@@ -3125,14 +3133,14 @@ idist_status idist_partitioned_get_info(const idist_partitioned* p, idist_partit
 // staging on the merge device for P lists of `width` per query and a result of `out_width` (the merge device is current)
 static idist_status partitioned_reserve(idist_partitioned* p, uint32_t nq, uint32_t width, uint32_t out_width) {
     const size_t P = p->parts.size(), slab = P * nq * width, o = (size_t)nq * out_width;
-    CHK(grow(p->s_pid, p->cap_s_pid, slab * 4));
-    CHK(grow(p->s_dist, p->cap_s_dist, slab * 4));
-    CHK(grow(p->s_cnt, p->cap_s_cnt, P * nq * 4));
-    CHK(grow(p->s_ctr, p->cap_s_ctr, P * nq * 12));
-    CHK(grow(p->o_cnt, p->cap_o_cnt, (size_t)nq * 4));
-    CHK(grow(p->o_ctr, p->cap_o_ctr, (size_t)nq * 12));
-    CHK(grow(p->o_pid, p->cap_o_pid, o * 4));
-    CHK(grow(p->o_dist, p->cap_o_dist, o * 4));
+    CHK(p->s_pid.grow(slab * 4));
+    CHK(p->s_dist.grow(slab * 4));
+    CHK(p->s_cnt.grow(P * nq * 4));
+    CHK(p->s_ctr.grow(P * nq * 12));
+    CHK(p->o_cnt.grow((size_t)nq * 4));
+    CHK(p->o_ctr.grow((size_t)nq * 12));
+    CHK(p->o_pid.grow(o * 4));
+    CHK(p->o_dist.grow(o * 4));
     return IDIST_OK;
 }
 
@@ -3145,8 +3153,8 @@ static idist_status partitioned_prepare_report(idist_partitioned* p, const float
     const MetricPasses metric(p);
     if (!metric.sq_floats(nq)) return IDIST_OK;
     const size_t qb = (size_t)nq * p->dim * 4;
-    CHK(grow(p->d_qm, p->cap_qm, qb));
-    CHK(grow(p->d_sq, p->cap_sq, metric.sq_floats(nq) * 4));
+    CHK(p->d_qm.grow(qb));
+    CHK(p->d_sq.grow(metric.sq_floats(nq) * 4));
     HIPCHK(hipMemcpyAsync(p->d_qm, queries, qb, hipMemcpyHostToDevice, p->stream));
     return metric.prepare(p->d_qm, nullptr, p->d_sq, nq, p->stream, nullptr);
 }
@@ -3158,9 +3166,9 @@ static idist_status partitioned_prepare_report(idist_partitioned* p, const float
 static idist_status partitioned_merge(idist_partitioned* p, uint32_t nq, uint32_t width, uint32_t out_width, bool counters,
                                       uint32_t* out_pid, float* out_dist, uint32_t* out_count, uint32_t* out_counters) {
     MergeArgs a{};
-    a.pid = p->s_pid; a.dist = (const uint32_t*)p->s_dist; a.count = p->s_cnt; a.counters = counters ? p->s_ctr : nullptr;
+    a.pid = p->s_pid; a.dist = (const uint32_t*)p->s_dist.p; a.count = p->s_cnt; a.counters = counters ? p->s_ctr.p : nullptr;
     a.n_lists = (uint32_t)p->parts.size(); a.nq = nq; a.width = width; a.out_width = out_width;
-    a.out_pid = p->o_pid; a.out_dist = (uint32_t*)p->o_dist; a.out_count = p->o_cnt; a.out_counters = counters ? p->o_ctr : nullptr;
+    a.out_pid = p->o_pid; a.out_dist = (uint32_t*)p->o_dist.p; a.out_count = p->o_cnt; a.out_counters = counters ? p->o_ctr.p : nullptr;
     for (uint32_t l = 0; l < a.n_lists; l++) a.base[l] = p->base[l];
     HIPCHK(hipEventRecord(p->ev0, p->stream));
     CHK(launch_merge(a, p->stream));
@@ -3176,28 +3184,89 @@ static idist_status partitioned_merge(idist_partitioned* p, uint32_t nq, uint32_
     return IDIST_OK;
 }
 
+// ---- the steps the partitioned calls share ----
+static int32_t part_device(const idist_partitioned* p, size_t i) { return p->devs[p->parts[i].dev_slot].device; }
+
+// a part's failure as the caller sees it (msg by value: it may be g_err itself, which fail() writes)
+static idist_status part_failed(const idist_partitioned* p, size_t i, idist_status s, std::string msg) {
+    return fail(s, "part %zu (device %d): %s", i, part_device(p, i), msg.c_str());
+}
+
+extern "C++" {
+namespace {
+// part(i) for every non-empty part, side by side (fan_out); the first failure comes back as the part's
+template <typename Work> idist_status partitioned_fan_out(idist_partitioned* p, Work&& part) {
+    Failure f;
+    if (fan_out(p->parts.size(), [&](size_t i) { return p->parts[i].ctx != nullptr; }, part, &f)) return part_failed(p, f.i, f.status, f.msg);
+    return IDIST_OK;
+}
+
+// fn(dv) for every device that has something to search, with that device current (it stays current)
+template <typename Fn> idist_status for_each_used_device(idist_partitioned* p, Fn&& fn) {
+    for (size_t d = 0; d < p->devs.size(); d++) {
+        bool used = false;
+        for (auto& pt : p->parts) used |= pt.ctx && pt.dev_slot == (int)d;
+        if (!used) continue;
+        HIPCHK(hipSetDevice(p->devs[d].device));
+        CHK(fn(p->devs[d]));
+    }
+    return IDIST_OK;
+}
+}  // namespace
+}  // extern "C++"
+
 // The batch's queries, once per distinct device that has something to search, as the parts' launches read them (prepared = true):
 // Dev::d_q holds the [nq][kdim] rows in front (a metric whose prepare cannot run in place: followed by the queries as uploaded).
 // Leaves another device current.  with_sq: a metric with a report term also leaves s(q) in Dev::d_sq (the range search's limits).
 static idist_status partitioned_upload_queries(idist_partitioned* p, const float* queries, uint32_t nq, bool with_sq = false) {
     const MetricPasses metric(p);
     const size_t qb = (size_t)nq * p->dim * 4, qa = metric.in_place() ? 0 : metric.qk_floats(nq) * 4;
-    for (size_t d = 0; d < p->devs.size(); d++) {
-        idist_partitioned::Dev& dv = p->devs[d];
-        bool used = false;
-        for (auto& pt : p->parts) used |= pt.ctx && pt.dev_slot == (int)d;
-        if (!used) continue;
-        HIPCHK(hipSetDevice(dv.device));
-        CHK(grow(dv.d_q, dv.cap_q, qa + qb));
+    return for_each_used_device(p, [&](idist_partitioned::Dev& dv) -> idist_status {
+        CHK(dv.d_q.grow(qa + qb));
         HIPCHK(hipMemcpy(dv.d_q + qa / 4, queries, qb, hipMemcpyHostToDevice));
         const bool sq = with_sq && metric.sq_floats(nq) != 0;
-        if (sq) CHK(grow(dv.d_sq, dv.cap_sq, metric.sq_floats(nq) * 4));
+        if (sq) CHK(dv.d_sq.grow(metric.sq_floats(nq) * 4));
         if (metric.any()) {                              // prepared once per device; the parts' launches take them as they are
-            CHK(metric.prepare(dv.d_q + qa / 4, dv.d_q, sq ? dv.d_sq : nullptr, nq, nullptr, nullptr));
+            CHK(metric.prepare(dv.d_q + qa / 4, dv.d_q, sq ? dv.d_sq.p : nullptr, nq, nullptr, nullptr));
             HIPCHK(hipStreamSynchronize(nullptr));
         }
+        return IDIST_OK;
+    });
+}
+
+// A part away from the merge device: its (pid, dist, count[, rung][, counters]) arrays, [nq] rows of `width`, to slice i of the
+// staging memory on the merge device, one peer copy per array on the part's stream (the part's device is current)
+static idist_status partitioned_send(idist_partitioned* p, size_t i, uint32_t nq, uint32_t width, const uint32_t* pid, const void* dist,
+                                     const uint32_t* cnt, const uint32_t* rung, const uint32_t* ctr) {
+    const int32_t dev = part_device(p, i), to = p->merge_device;
+    hipStream_t stream = p->parts[i].ctx->stream;
+    const size_t row = (size_t)nq * width;
+    HIPCHK(hipMemcpyPeerAsync(p->s_pid + i * row, to, pid, dev, row * 4, stream));
+    HIPCHK(hipMemcpyPeerAsync(p->s_dist + i * row, to, dist, dev, row * 4, stream));
+    HIPCHK(hipMemcpyPeerAsync(p->s_cnt + i * nq, to, cnt, dev, (size_t)nq * 4, stream));
+    if (rung) HIPCHK(hipMemcpyPeerAsync(p->s_rung + i * nq, to, rung, dev, (size_t)nq * 4, stream));
+    if (ctr) HIPCHK(hipMemcpyPeerAsync(p->s_ctr + i * nq * 3, to, ctr, dev, (size_t)nq * 12, stream));
+    return IDIST_OK;
+}
+
+// an empty part hands in lists of length 0 and has done no work: its counts and counters in the staging memory, on p->stream (the
+// merge device is current)
+static idist_status partitioned_zero_empty_parts(idist_partitioned* p, uint32_t nq, bool counters) {
+    for (size_t i = 0; i < p->parts.size(); i++) {
+        if (p->parts[i].ctx) continue;
+        HIPCHK(hipMemsetAsync(p->s_cnt + i * nq, 0, (size_t)nq * 4, p->stream));
+        if (counters) HIPCHK(hipMemsetAsync(p->s_ctr + i * nq * 3, 0, (size_t)nq * 12, p->stream));
     }
     return IDIST_OK;
+}
+
+// the parts' rungs [P][nq] as the caller has them, [nq][P]; an empty part's column keeps the IDIST_RUNG_NONE written up front
+static void partitioned_transpose_rungs(const idist_partitioned* p, const std::vector<uint32_t>& rungs, uint32_t nq, uint32_t* out_rung) {
+    const size_t P = p->parts.size();
+    for (size_t i = 0; out_rung && i < P; i++) {
+        if (!p->parts[i].ctx) continue;
+        for (uint32_t q = 0; q < nq; q++) out_rung[(size_t)q * P + i] = rungs[i * nq + q];
+    }
 }
 
 idist_status idist_partitioned_search_batch(idist_partitioned* p, const float* queries, uint32_t nq, uint32_t* out_pid,
@@ -3231,23 +3300,18 @@ idist_status idist_partitioned_search_batch(idist_partitioned* p, const float* q
         HIPCHK(hipSetDevice(dev));
         if (dev == p->merge_device)
             return search_batch_device_impl(pt.idx, pt.ctx, p->devs[pt.dev_slot].d_q, nq, s_pid, s_dist, s_cnt, counters ? s_ctr : nullptr, pt.ctx->stream, true);
-        CHK(grow(pt.r_pid, pt.r_cap_pid, row * 4));
-        CHK(grow(pt.r_dist, pt.r_cap_dist, row * 4));
-        CHK(grow(pt.r_cnt, pt.r_cap_cnt, (size_t)nq * 4));
-        CHK(grow(pt.r_ctr, pt.r_cap_ctr, (size_t)nq * 12));
-        CHK(search_batch_device_impl(pt.idx, pt.ctx, p->devs[pt.dev_slot].d_q, nq, pt.r_pid, pt.r_dist, pt.r_cnt, counters ? pt.r_ctr : nullptr, pt.ctx->stream, true));
-        HIPCHK(hipMemcpyPeerAsync(s_pid, p->merge_device, pt.r_pid, dev, row * 4, pt.ctx->stream));
-        HIPCHK(hipMemcpyPeerAsync(s_dist, p->merge_device, pt.r_dist, dev, row * 4, pt.ctx->stream));
-        HIPCHK(hipMemcpyPeerAsync(s_cnt, p->merge_device, pt.r_cnt, dev, (size_t)nq * 4, pt.ctx->stream));
-        if (counters) HIPCHK(hipMemcpyPeerAsync(s_ctr, p->merge_device, pt.r_ctr, dev, (size_t)nq * 12, pt.ctx->stream));
-        return IDIST_OK;
+        CHK(pt.r_pid.grow(row * 4));
+        CHK(pt.r_dist.grow(row * 4));
+        CHK(pt.r_cnt.grow((size_t)nq * 4));
+        CHK(pt.r_ctr.grow((size_t)nq * 12));
+        uint32_t* r_ctr = counters ? pt.r_ctr.p : nullptr;
+        CHK(search_batch_device_impl(pt.idx, pt.ctx, p->devs[pt.dev_slot].d_q, nq, pt.r_pid, pt.r_dist, pt.r_cnt, r_ctr, pt.ctx->stream, true));
+        return partitioned_send(p, i, nq, ef, pt.r_pid, pt.r_dist, pt.r_cnt, nullptr, r_ctr);
     };
-    for (size_t i = 0; i < P; i++) {
-        if (p->parts[i].ctx) { CHK(enqueue(i)); continue; }
-        HIPCHK(hipSetDevice(p->merge_device));           // an empty part: lists of length 0, no work done
-        HIPCHK(hipMemsetAsync(p->s_cnt + i * nq, 0, (size_t)nq * 4, p->stream));
-        if (counters) HIPCHK(hipMemsetAsync(p->s_ctr + i * nq * 3, 0, (size_t)nq * 12, p->stream));
-    }
+    for (size_t i = 0; i < P; i++)
+        if (p->parts[i].ctx) CHK(enqueue(i));
+    HIPCHK(hipSetDevice(p->merge_device));
+    CHK(partitioned_zero_empty_parts(p, nq, counters));
     // 3. wait for every part and read its device-side status.  Strict ties: a part whose tie region overflowed now has the larger
     //    region (or the HBM bags) and is searched again — for as long as the escalation makes progress, the bound idist_search_batch
     //    puts on its own loop; the merge never sees a list from an overflowed launch
@@ -3263,8 +3327,7 @@ idist_status idist_partitioned_search_batch(idist_partitioned* p, const float* q
                 continue;
             }
             if (s == IDIST_OK) break;
-            const std::string msg = g_err;
-            return fail(s, "part %zu (device %d): %s", i, p->devs[pt.dev_slot].device, msg.c_str());
+            return part_failed(p, i, s, g_err);
         }
     }
     // 4. the union
@@ -3290,7 +3353,7 @@ idist_status idist_partitioned_bruteforce(idist_partitioned* p, const float* que
         const uint32_t kp = std::min(k, ix->n);                   // what this part contributes per query
         if (kp) {
             const idist_status s = bruteforce_impl(ix, queries, nq, kp, h_pid.data(), h_dist.data(), true);
-            if (s != IDIST_OK) { const std::string msg = g_err; return fail(s, "part %zu (device %d): %s", i, ix->device, msg.c_str()); }
+            if (s != IDIST_OK) return part_failed(p, i, s, g_err);
             HIPCHK(hipSetDevice(p->merge_device));
             HIPCHK(hipMemcpy2D(p->s_pid + i * row, (size_t)k * 4, h_pid.data(), (size_t)kp * 4, (size_t)kp * 4, nq, hipMemcpyHostToDevice));
             HIPCHK(hipMemcpy2D(p->s_dist + i * row, (size_t)k * 4, h_dist.data(), (size_t)kp * 4, (size_t)kp * 4, nq, hipMemcpyHostToDevice));
@@ -3628,12 +3691,12 @@ AllowedLadder make_ladder(uint32_t ef0, int32_t max_rungs) {
 idist_status ladder_upload_queries(const idist_index* idx, idist_search_ctx* ctx, const MetricPasses& metric, const float* queries,
                                    uint32_t nq, const float** d_qk) {
     const size_t qb = (size_t)nq * idx->dim * 4;
-    CHK(grow(ctx->d_q, ctx->cap_q, qb));
+    CHK(ctx->d_q.grow(qb));
     HIPCHK(hipMemcpyAsync(ctx->d_q, queries, qb, hipMemcpyHostToDevice, ctx->stream));
     *d_qk = ctx->d_q;
     if (metric.any()) {
-        CHK(grow(ctx->d_qn, ctx->cap_qn, doubled_from(4096, metric.qk_floats(nq) * 4)));
-        CHK(grow(ctx->d_sq, ctx->cap_sq, doubled_from(256, metric.sq_floats(nq) * 4)));
+        CHK(ctx->d_qn.grow(doubled_from(4096, metric.qk_floats(nq) * 4)));
+        CHK(ctx->d_sq.grow(doubled_from(256, metric.sq_floats(nq) * 4)));
         CHK(metric.prepare(ctx->d_q, ctx->d_qn, ctx->d_sq, nq, ctx->stream, d_qk));
     }
     return IDIST_OK;
@@ -3645,13 +3708,13 @@ idist_status ladder_rung(const idist_index* idx, idist_search_ctx* ctx, const fl
                          bool counters, bool* ended) {
     *ended = false;
     const size_t rb = (size_t)np * ef * 4;
-    CHK(grow(ctx->d_pid, ctx->cap_pid, rb));
-    CHK(grow(ctx->d_dist, ctx->cap_dist, rb));
-    CHK(grow(ctx->d_cnt, ctx->cap_cnt, (size_t)np * 4));
-    CHK(grow(ctx->d_ctr, ctx->cap_ctr, (size_t)np * 12));
+    CHK(ctx->d_pid.grow(rb));
+    CHK(ctx->d_dist.grow(rb));
+    CHK(ctx->d_cnt.grow((size_t)np * 4));
+    CHK(ctx->d_ctr.grow((size_t)np * 12));
     for (;;) {
         bool lds_short = false;
-        const idist_status ls = launch_search(idx, ctx, d_pq, np, ctx->d_pid, ctx->d_dist, ctx->d_cnt, counters ? ctx->d_ctr : nullptr,
+        const idist_status ls = launch_search(idx, ctx, d_pq, np, ctx->d_pid, ctx->d_dist, ctx->d_cnt, counters ? ctx->d_ctr.p : nullptr,
                                               ctx->stream, nullptr, nullptr, nullptr, 0, true, ef, &lds_short);
         if (ls != IDIST_OK) {
             // a later rung that does not fit a wave's LDS ends the ladder as max_rungs would; rung 0 fails as idist_search_batch does
@@ -3672,8 +3735,8 @@ idist_status ladder_pending(idist_search_ctx* ctx, const uint32_t* pending, uint
                             uint32_t* list_out, int which_timer, const uint32_t* d_first = nullptr, uint32_t rung = 0,
                             const uint32_t* d_last = nullptr) {
     auto pending_pass = [&]() -> idist_status {
-        IDIST_LAUNCH(allowed_pending_kernel, (nq + 63u) / 64u, 64, 0, ctx->stream, pending, nq, d_qk, kdim, list_out, ctx->al_pq.as<float>(),
-                     ctx->al_npend.as<uint32_t>(), d_first, rung, d_last);
+        IDIST_LAUNCH(allowed_pending_kernel, (nq + 63u) / 64u, 64, 0, ctx->stream, pending, nq, d_qk, kdim, list_out, ctx->al_pq,
+                     ctx->al_npend, d_first, rung, d_last);
         HIPCHK(hipGetLastError());
         return IDIST_OK;
     };
@@ -3694,7 +3757,7 @@ idist_status allowed_select(idist_search_ctx* ctx, const AllowedOut& o, uint32_t
                             uint32_t rung, bool exact, const uint32_t* set_of = nullptr, uint32_t words = 0) {
     auto select_pass = [&]() -> idist_status {
         const uint32_t grid = std::min<uint32_t>(np, 65536u);                 // one wave per pending query; the kernel strides over the rest
-        IDIST_LAUNCH(allowed_select_kernel, grid, 64, 0, ctx->stream, o, ctx->al_bits.as<uint32_t>(), n, r_pid,
+        IDIST_LAUNCH(allowed_select_kernel, grid, 64, 0, ctx->stream, o, ctx->al_bits, n, r_pid,
                      reinterpret_cast<const uint32_t*>(r_dist), r_cnt, r_ctr, width, list, np, rung, exact ? 1u : 0u, set_of,
                      words);
         HIPCHK(hipGetLastError());
@@ -3709,42 +3772,42 @@ template <typename F>
 idist_status allowed_exact_step(const idist_index* idx, idist_search_ctx* ctx, const AllowedOut& o, uint32_t np, uint32_t k, uint32_t S,
                                 const uint32_t* d_list, const uint32_t* d_setof, uint32_t words, F launch_scan) {
     const size_t sb = (size_t)S * np * k * 4, mb = (size_t)np * k * 4;
-    CHK(grow(ctx->d_pid, ctx->cap_pid, sb));
-    CHK(grow(ctx->d_dist, ctx->cap_dist, sb));
-    CHK(grow(ctx->d_cnt, ctx->cap_cnt, (size_t)S * np * 4));
-    CHK(grow(ctx->al_mpid.p, ctx->al_mpid.cap, mb));
-    CHK(grow(ctx->al_mdist.p, ctx->al_mdist.cap, mb));
-    CHK(grow(ctx->al_mcnt.p, ctx->al_mcnt.cap, (size_t)np * 4));
+    CHK(ctx->d_pid.grow(sb));
+    CHK(ctx->d_dist.grow(sb));
+    CHK(ctx->d_cnt.grow((size_t)S * np * 4));
+    CHK(ctx->al_mpid.grow(mb));
+    CHK(ctx->al_mdist.grow(mb));
+    CHK(ctx->al_mcnt.grow((size_t)np * 4));
     const uint32_t wcap = topk_wcap(k);
     const size_t smem = smem_bytes(idx->L.stride, wcap, false);
     if (smem > 64 * 1024) return fail(IDIST_ERR_INVALID_ARG, "dim/k need %zu B of LDS per wave (> 64 KiB)", smem);
     auto scan_and_merge = [&]() -> idist_status {
         const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)np * S, (uint64_t)std::max(ctx->n_cu, 1) * 64u);
-        uint32_t *s_pid = ctx->d_pid, *s_dist = reinterpret_cast<uint32_t*>(ctx->d_dist), *s_cnt = ctx->d_cnt;
+        uint32_t *s_pid = ctx->d_pid, *s_dist = reinterpret_cast<uint32_t*>(ctx->d_dist.p), *s_cnt = ctx->d_cnt;
         launch_scan(grid, smem, S, wcap, s_pid, s_dist, s_cnt);
         HIPCHK(hipGetLastError());
         MergeArgs a{};
         a.pid = s_pid; a.dist = s_dist; a.count = s_cnt; a.counters = nullptr;
         a.n_lists = S; a.nq = np; a.width = k; a.out_width = k;
-        a.out_pid = ctx->al_mpid.as<uint32_t>(); a.out_dist = ctx->al_mdist.as<uint32_t>(); a.out_count = ctx->al_mcnt.as<uint32_t>();
+        a.out_pid = ctx->al_mpid; a.out_dist = ctx->al_mdist.as<uint32_t>(); a.out_count = ctx->al_mcnt;
         a.out_counters = nullptr;
         return launch_merge(a, ctx->stream);
     };
     CHK(ladder_timed(ctx, 2, scan_and_merge));
-    return allowed_select(ctx, o, idx->n, ctx->al_mpid.as<uint32_t>(), ctx->al_mdist.as<float>(), ctx->al_mcnt.as<uint32_t>(), nullptr, k,
+    return allowed_select(ctx, o, idx->n, ctx->al_mpid, ctx->al_mdist.as<float>(), ctx->al_mcnt, nullptr, k,
                           d_list, np, IDIST_RUNG_EXACT, true, d_setof, words);
 }
 
 // a call's [nq][k] result with its counts, rungs and counters in the context's own memory
 idist_status allowed_out_in_ctx(idist_search_ctx* ctx, uint32_t nq, uint32_t k, bool counters, AllowedOut* o) {
     const size_t ob = (size_t)nq * k * 4;
-    CHK(grow(ctx->al_opid.p, ctx->al_opid.cap, ob));
-    CHK(grow(ctx->al_odist.p, ctx->al_odist.cap, ob));
-    CHK(grow(ctx->al_ocnt.p, ctx->al_ocnt.cap, (size_t)nq * 4));
-    CHK(grow(ctx->al_orung.p, ctx->al_orung.cap, (size_t)nq * 4));
-    CHK(grow(ctx->al_octr.p, ctx->al_octr.cap, (size_t)nq * 12));
-    o->pid = ctx->al_opid.as<uint32_t>(); o->dist = ctx->al_odist.as<uint32_t>(); o->count = ctx->al_ocnt.as<uint32_t>();
-    o->rung = ctx->al_orung.as<uint32_t>(); o->counters = counters ? ctx->al_octr.as<uint32_t>() : nullptr;
+    CHK(ctx->al_opid.grow(ob));
+    CHK(ctx->al_odist.grow(ob));
+    CHK(ctx->al_ocnt.grow((size_t)nq * 4));
+    CHK(ctx->al_orung.grow((size_t)nq * 4));
+    CHK(ctx->al_octr.grow((size_t)nq * 12));
+    o->pid = ctx->al_opid; o->dist = ctx->al_odist.as<uint32_t>(); o->count = ctx->al_ocnt;
+    o->rung = ctx->al_orung; o->counters = counters ? ctx->al_octr.p : nullptr;
     return IDIST_OK;
 }
 // ... and its way back to the caller, enqueued: the caller synchronises the stream and calls ladder_times_resolve
@@ -3796,14 +3859,14 @@ idist_status idist_search_batch_allowed(const idist_index* idx, idist_search_ctx
     const bool counters = out_counters != nullptr;
     ctx->al_ms[0] = ctx->al_ms[1] = ctx->al_ms[2] = 0.0f;
     ctx->al_ev_used = 0;
-    CHK(grow(ctx->al_bits.p, ctx->al_bits.cap, (size_t)words * 4));
-    CHK(grow(ctx->al_flag.p, ctx->al_flag.cap, (size_t)nq * 4));
-    CHK(grow(ctx->al_list.p, ctx->al_list.cap, (size_t)nq * 4));
-    CHK(grow(ctx->al_npend.p, ctx->al_npend.cap, 256));
-    CHK(grow(ctx->al_pq.p, ctx->al_pq.cap, (size_t)nq * kdim * 4));
+    CHK(ctx->al_bits.grow((size_t)words * 4));
+    CHK(ctx->al_flag.grow((size_t)nq * 4));
+    CHK(ctx->al_list.grow((size_t)nq * 4));
+    CHK(ctx->al_npend.grow(256));
+    CHK(ctx->al_pq.grow((size_t)nq * kdim * 4));
     AllowedOut o{};
     CHK(allowed_out_in_ctx(ctx, nq, k, counters, &o));
-    o.pending = ctx->al_flag.as<uint32_t>(); o.nq = nq; o.k = k;
+    o.pending = ctx->al_flag; o.nq = nq; o.k = k;
     HIPCHK(hipMemcpyAsync(ctx->al_bits.p, bits.data(), (size_t)words * 4, hipMemcpyHostToDevice, stream));
     const float* d_qk = nullptr;
     CHK(ladder_upload_queries(idx, ctx, metric, queries, nq, &d_qk));
@@ -3822,12 +3885,12 @@ idist_status idist_search_batch_allowed(const idist_index* idx, idist_search_ctx
         bool ended = false;
         CHK(ladder_rung(idx, ctx, d_pq, np, ef, r, counters, &ended));
         if (ended) break;
-        CHK(allowed_select(ctx, o, n, ctx->d_pid, ctx->d_dist, ctx->d_cnt, counters ? ctx->d_ctr : nullptr, ef, d_list, np, r, false));
-        CHK(ladder_pending(ctx, o.pending, nq, d_qk, kdim, ctx->al_list.as<uint32_t>(), 1));
+        CHK(allowed_select(ctx, o, n, ctx->d_pid, ctx->d_dist, ctx->d_cnt, counters ? ctx->d_ctr.p : nullptr, ef, d_list, np, r, false));
+        CHK(ladder_pending(ctx, o.pending, nq, d_qk, kdim, ctx->al_list, 1));
         HIPCHK(hipMemcpyAsync(&np, ctx->al_npend.p, 4, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
-        d_list = ctx->al_list.as<uint32_t>();
-        d_pq = ctx->al_pq.as<float>();
+        d_list = ctx->al_list;
+        d_pq = ctx->al_pq;
     }
     if (np) {
         // step 5, exact: the ascending id list of A cut into S segments, the segments' top-k lists merged
@@ -3835,9 +3898,9 @@ idist_status idist_search_batch_allowed(const idist_index* idx, idist_search_ctx
         for (uint32_t w = 0; w < words; w++)
             for (uint32_t m = bits[w]; m; m &= m - 1u) ids.push_back(32u * w + (uint32_t)__builtin_ctz(m));
         const uint32_t n_ids = (uint32_t)ids.size();
-        CHK(grow(ctx->al_ids.p, ctx->al_ids.cap, (size_t)n_ids * 4));
+        CHK(ctx->al_ids.grow((size_t)n_ids * 4));
         HIPCHK(hipMemcpyAsync(ctx->al_ids.p, ids.data(), (size_t)n_ids * 4, hipMemcpyHostToDevice, stream));
-        const uint32_t* d_ids = ctx->al_ids.as<uint32_t>();
+        const uint32_t* d_ids = ctx->al_ids;
         const IndexView view = idx->view();
         auto scan_ids = [&](uint32_t grid, size_t smem, uint32_t S, uint32_t wcap, uint32_t* s_pid, uint32_t* s_dist, uint32_t* s_cnt) {
 #define LAUNCH_AS(NB_, RS_, TAIL_)                                                                                        \
@@ -3878,19 +3941,19 @@ idist_status allowed_sets_device(const idist_index* idx, idist_search_ctx* ctx, 
     const bool counters = o.counters != nullptr;
     ctx->al_ms[0] = ctx->al_ms[1] = ctx->al_ms[2] = 0.0f;
     ctx->al_ev_used = 0;
-    CHK(grow(ctx->al_size.p, ctx->al_size.cap, (size_t)n_sets * 4));
-    CHK(grow(ctx->al_start.p, ctx->al_start.cap, (size_t)n_sets * 4));
-    CHK(grow(ctx->al_first.p, ctx->al_first.cap, (size_t)nq * 4));
-    CHK(grow(ctx->al_flag.p, ctx->al_flag.cap, (size_t)nq * 4));
-    CHK(grow(ctx->al_list.p, ctx->al_list.cap, (size_t)nq * 4));
-    CHK(grow(ctx->al_npend.p, ctx->al_npend.cap, 256));
-    CHK(grow(ctx->al_pq.p, ctx->al_pq.cap, (size_t)nq * kdim * 4));
-    o.pending = ctx->al_flag.as<uint32_t>(); o.nq = nq; o.k = k;
-    const uint32_t* d_first = ctx->al_first.as<uint32_t>();
+    CHK(ctx->al_size.grow((size_t)n_sets * 4));
+    CHK(ctx->al_start.grow((size_t)n_sets * 4));
+    CHK(ctx->al_first.grow((size_t)nq * 4));
+    CHK(ctx->al_flag.grow((size_t)nq * 4));
+    CHK(ctx->al_list.grow((size_t)nq * 4));
+    CHK(ctx->al_npend.grow(256));
+    CHK(ctx->al_pq.grow((size_t)nq * kdim * 4));
+    o.pending = ctx->al_flag; o.nq = nq; o.k = k;
+    const uint32_t* d_first = ctx->al_first;
     auto count_pass = [&]() -> idist_status {
         const uint32_t grid = std::min<uint32_t>(n_sets, (uint32_t)std::max(ctx->n_cu, 1) * 32u);
-        IDIST_LAUNCH(allowed_count_kernel, grid, 64, 0, stream, d_bits, n, words, n_sets, k, lad, ctx->al_size.as<uint32_t>(),
-                     ctx->al_start.as<uint32_t>());
+        IDIST_LAUNCH(allowed_count_kernel, grid, 64, 0, stream, d_bits, n, words, n_sets, k, lad, ctx->al_size,
+                     ctx->al_start);
         HIPCHK(hipGetLastError());
         return IDIST_OK;
     };
@@ -3899,7 +3962,7 @@ idist_status allowed_sets_device(const idist_index* idx, idist_search_ctx* ctx, 
     HIPCHK(hipMemcpyAsync(start.data(), ctx->al_start.p, (size_t)n_sets * 4, hipMemcpyDeviceToHost, stream));
     {
         const uint32_t grid = (uint32_t)std::min<size_t>(((size_t)nq * k + 255) / 256, (size_t)std::max(ctx->n_cu, 1) * 8u);
-        IDIST_LAUNCH(allowed_init_kernel, grid, 256, 0, stream, o, ctx->al_start.as<uint32_t>(), d_setof, ctx->al_first.as<uint32_t>());
+        IDIST_LAUNCH(allowed_init_kernel, grid, 256, 0, stream, o, ctx->al_start, d_setof, ctx->al_first);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(stream));
@@ -3924,11 +3987,11 @@ idist_status allowed_sets_device(const idist_index* idx, idist_search_ctx* ctx, 
     const uint32_t* d_list = nullptr;
     const float* d_pq = d_qk;
     auto gather = [&](uint32_t rung) -> idist_status {
-        CHK(ladder_pending(ctx, o.pending, nq, d_qk, kdim, ctx->al_list.as<uint32_t>(), 1, d_first, rung));
+        CHK(ladder_pending(ctx, o.pending, nq, d_qk, kdim, ctx->al_list, 1, d_first, rung));
         HIPCHK(hipMemcpyAsync(&np, ctx->al_npend.p, 4, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
-        d_list = ctx->al_list.as<uint32_t>();
-        d_pq = ctx->al_pq.as<float>();
+        d_list = ctx->al_list;
+        d_pq = ctx->al_pq;
         return IDIST_OK;
     };
     uint32_t r = next_start(0);
@@ -3950,7 +4013,7 @@ idist_status allowed_sets_device(const idist_index* idx, idist_search_ctx* ctx, 
         bool ended = false;
         CHK(ladder_rung(idx, ctx, d_pq, np, ef, r, counters, &ended));
         if (ended) break;
-        CHK(allowed_select(ctx, o, n, ctx->d_pid, ctx->d_dist, ctx->d_cnt, counters ? ctx->d_ctr : nullptr, ef, d_list, np, r, false,
+        CHK(allowed_select(ctx, o, n, ctx->d_pid, ctx->d_dist, ctx->d_cnt, counters ? ctx->d_ctr.p : nullptr, ef, d_list, np, r, false,
                            d_setof, words));
         r++;
     }
@@ -3975,6 +4038,14 @@ idist_status allowed_sets_device(const idist_index* idx, idist_search_ctx* ctx, 
 }  // namespace
 }  // extern "C++"
 
+// set_of == NULL: query q uses set q — the call's own_set, kept in *keep for its duration
+static const uint32_t* set_of_or_identity(const uint32_t* set_of, uint32_t nq, std::vector<uint32_t>* keep) {
+    if (set_of) return set_of;
+    keep->resize(nq);
+    for (uint32_t q = 0; q < nq; q++) (*keep)[q] = q;
+    return keep->data();
+}
+
 idist_status idist_search_batch_allowed_sets(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
                                              const uint32_t* allow_bits, uint32_t n_sets, const uint32_t* set_of, uint32_t k,
                                              int32_t max_rungs, uint32_t* out_pid, float* out_dist, uint32_t* out_count,
@@ -3995,21 +4066,17 @@ idist_status idist_search_batch_allowed_sets(const idist_index* idx, idist_searc
     hipStream_t stream = ctx->stream;
     const MetricPasses metric(idx);
     const size_t bb = (size_t)n_sets * words * 4;
-    CHK(grow(ctx->al_bits.p, ctx->al_bits.cap, bb));
-    CHK(grow(ctx->al_setof.p, ctx->al_setof.cap, (size_t)nq * 4));
+    CHK(ctx->al_bits.grow(bb));
+    CHK(ctx->al_setof.grow((size_t)nq * 4));
     AllowedOut o{};
     CHK(allowed_out_in_ctx(ctx, nq, k, out_counters != nullptr, &o));
-    std::vector<uint32_t> own_set;                               // set_of == NULL: query q uses set q
-    if (!set_of) {
-        own_set.resize(nq);
-        for (uint32_t q = 0; q < nq; q++) own_set[q] = q;
-        set_of = own_set.data();
-    }
+    std::vector<uint32_t> identity;
+    set_of = set_of_or_identity(set_of, nq, &identity);
     HIPCHK(hipMemcpyAsync(ctx->al_bits.p, allow_bits, bb, hipMemcpyHostToDevice, stream));     // as the caller has them: padding bits are masked where they are read
     HIPCHK(hipMemcpyAsync(ctx->al_setof.p, set_of, (size_t)nq * 4, hipMemcpyHostToDevice, stream));
     const float* d_qk = nullptr;
     CHK(ladder_upload_queries(idx, ctx, metric, queries, nq, &d_qk));
-    CHK(allowed_sets_device(idx, ctx, d_qk, nq, ctx->al_bits.as<uint32_t>(), n_sets, ctx->al_setof.as<uint32_t>(), set_of, k, max_rungs, o));
+    CHK(allowed_sets_device(idx, ctx, d_qk, nq, ctx->al_bits, n_sets, ctx->al_setof, set_of, k, max_rungs, o));
     CHK(metric.report(ctx->al_odist.as<float>(), ctx->d_sq, nq, k, stream));
     CHK(allowed_download(ctx, nq, k, out_pid, out_dist, out_count, out_rung, out_counters));
     HIPCHK(hipStreamSynchronize(stream));
@@ -4057,27 +4124,19 @@ idist_status idist_partitioned_search_batch_allowed_sets(idist_partitioned* p, c
     }
     const bool counters = out_counters != nullptr;
     const size_t W = ((size_t)N + 31u) / 32u, row = (size_t)nq * k;
-    std::vector<uint32_t> own_set;                               // set_of == NULL: query q uses set q
-    if (!set_of) {
-        own_set.resize(nq);
-        for (uint32_t q = 0; q < nq; q++) own_set[q] = q;
-        set_of = own_set.data();
-    }
+    std::vector<uint32_t> identity;
+    set_of = set_of_or_identity(set_of, nq, &identity);
     HIPCHK(hipSetDevice(p->merge_device));
     CHK(partitioned_reserve(p, nq, k, k));
-    CHK(grow(p->s_rung, p->cap_s_rung, P * nq * 4));
+    CHK(p->s_rung.grow(P * nq * 4));
     CHK(partitioned_prepare_report(p, queries, nq));
     // 1. the queries and the set of every query, once per distinct device that has something to search
     CHK(partitioned_upload_queries(p, queries, nq));
-    for (size_t d = 0; d < p->devs.size(); d++) {
-        idist_partitioned::Dev& dv = p->devs[d];
-        bool used = false;
-        for (auto& pt : p->parts) used |= pt.ctx && pt.dev_slot == (int)d;
-        if (!used) continue;
-        HIPCHK(hipSetDevice(dv.device));
-        CHK(grow(dv.d_setof, dv.cap_setof, (size_t)nq * 4));
+    CHK(for_each_used_device(p, [&](idist_partitioned::Dev& dv) -> idist_status {
+        CHK(dv.d_setof.grow((size_t)nq * 4));
         HIPCHK(hipMemcpy(dv.d_setof, set_of, (size_t)nq * 4, hipMemcpyHostToDevice));
-    }
+        return IDIST_OK;
+    }));
     // 2. every part's bitmaps: the words [base / 32, ceil((base + n_p) / 32)) of every set in ONE strided copy out of the caller's
     //    buffer (which is only read), then the slice kernel shifts them by base % 32 on the part's stream — the part's own
     //    [n_sets][(n_p + 31) / 32], the bits behind n_p cleared
@@ -4088,14 +4147,15 @@ idist_status idist_partitioned_search_batch_allowed_sets(idist_partitioned* p, c
         const uint32_t n_p = pt.idx->n, w0 = p->base[i] / 32u, sh = p->base[i] % 32u;
         const size_t nw = ((size_t)sh + n_p + 31u) / 32u, words = ((size_t)n_p + 31u) / 32u;
         HIPCHK(hipSetDevice(p->devs[pt.dev_slot].device));
-        CHK(grow(pt.ctx->al_raw.p, pt.ctx->al_raw.cap, (size_t)n_sets * nw * 4));
-        CHK(grow(pt.ctx->al_bits.p, pt.ctx->al_bits.cap, (size_t)n_sets * words * 4));
+        CHK(pt.ctx->al_raw.grow((size_t)n_sets * nw * 4));
+        CHK(pt.ctx->al_bits.grow((size_t)n_sets * words * 4));
         if (n_sets == 1) HIPCHK(hipMemcpy(pt.ctx->al_raw.p, allow_bits + w0, nw * 4, hipMemcpyHostToDevice));
         else HIPCHK(hipMemcpy2D(pt.ctx->al_raw.p, nw * 4, allow_bits + w0, W * 4, nw * 4, n_sets, hipMemcpyHostToDevice));
         const size_t total = (size_t)n_sets * words;
         const uint32_t grid = (uint32_t)std::min<size_t>((total + 255u) / 256u, (size_t)std::max(pt.ctx->n_cu, 1) * 8u);
-        IDIST_LAUNCH(allowed_slice_kernel, grid, 256, 0, pt.ctx->stream, pt.ctx->al_raw.as<uint32_t>(), n_sets, (uint32_t)nw, (uint64_t)sh, n_p,
-                     pt.ctx->al_bits.as<uint32_t>());
+        const uint32_t* raw = pt.ctx->al_raw;
+        uint32_t* bits = pt.ctx->al_bits;
+        IDIST_LAUNCH(allowed_slice_kernel, grid, 256, 0, pt.ctx->stream, raw, n_sets, (uint32_t)nw, (uint64_t)sh, n_p, bits);
         HIPCHK(hipGetLastError());
     }
     for (size_t i = 0; i < P; i++) {                     // (waited for only to be timed: the ladders run on the same streams)
@@ -4107,10 +4167,8 @@ idist_status idist_partitioned_search_batch_allowed_sets(idist_partitioned* p, c
     p->al_slice_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     // 3. the ladders block on the host, one synchronisation per rung: one thread per non-empty part, each with the part's own context
     //    and stream.  On the merge device straight into the part's slice of the staging memory, elsewhere into memory of the part's
-    //    device followed by one peer copy per array.  A worker keeps its status and message (g_err is thread-local).
-    std::vector<idist_status> st(P, IDIST_OK);
-    std::vector<std::string> msg(P);
-    auto part = [&](size_t i) -> idist_status {
+    //    device followed by one peer copy per array (partitioned_fan_out, partitioned_send).
+    CHK(partitioned_fan_out(p, [&](size_t i) -> idist_status {
         idist_partitioned::Part& pt = p->parts[i];
         idist_search_ctx* ctx = pt.ctx;
         const idist_partitioned::Dev& dv = p->devs[pt.dev_slot];
@@ -4124,56 +4182,21 @@ idist_status idist_partitioned_search_batch_allowed_sets(idist_partitioned* p, c
         } else {
             CHK(allowed_out_in_ctx(ctx, nq, k, counters, &o));
         }
-        CHK(allowed_sets_device(pt.idx, ctx, dv.d_q, nq, ctx->al_bits.as<uint32_t>(), n_sets, dv.d_setof, set_of, k, max_rungs, o));
-        if (dev != p->merge_device) {
-            HIPCHK(hipMemcpyPeerAsync(s_pid, p->merge_device, o.pid, dev, row * 4, ctx->stream));
-            HIPCHK(hipMemcpyPeerAsync(s_dist, p->merge_device, o.dist, dev, row * 4, ctx->stream));
-            HIPCHK(hipMemcpyPeerAsync(s_cnt, p->merge_device, o.count, dev, (size_t)nq * 4, ctx->stream));
-            HIPCHK(hipMemcpyPeerAsync(s_rung, p->merge_device, o.rung, dev, (size_t)nq * 4, ctx->stream));
-            if (counters) HIPCHK(hipMemcpyPeerAsync(s_ctr, p->merge_device, o.counters, dev, (size_t)nq * 12, ctx->stream));
-        }
+        CHK(allowed_sets_device(pt.idx, ctx, dv.d_q, nq, ctx->al_bits, n_sets, dv.d_setof, set_of, k, max_rungs, o));
+        if (dev != p->merge_device) CHK(partitioned_send(p, i, nq, k, o.pid, o.dist, o.count, o.rung, counters ? o.counters : nullptr));
         HIPCHK(hipStreamSynchronize(ctx->stream));
         return ladder_times_resolve(ctx);
-    };
-    auto work = [&](size_t i) {
-        st[i] = part(i);
-        if (st[i] != IDIST_OK) msg[i] = g_err;
-    };
-    {
-        std::vector<std::thread> threads;
-        long first = -1;                                 // the first non-empty part runs on the calling thread
-        for (size_t i = 0; i < P; i++) {
-            if (!p->parts[i].ctx) continue;
-            if (first < 0) { first = (long)i; continue; }
-            try {
-                threads.emplace_back(work, i);
-            } catch (...) {                              // no thread to be had: the part runs here, after the others were started
-                work(i);
-            }
-        }
-        if (first >= 0) work((size_t)first);
-        for (auto& t : threads) t.join();                // every thread is joined before any return
-    }
-    for (size_t i = 0; i < P; i++)
-        if (st[i] != IDIST_OK) return fail(st[i], "part %zu (device %d): %s", i, p->devs[p->parts[i].dev_slot].device, msg[i].c_str());
+    }));
     // 4. the union: empty parts hand in lists of length 0; the parts' rungs come back [P][nq] and are transposed on the host
     HIPCHK(hipSetDevice(p->merge_device));
-    for (size_t i = 0; i < P; i++) {
-        if (p->parts[i].ctx) continue;
-        HIPCHK(hipMemsetAsync(p->s_cnt + i * nq, 0, (size_t)nq * 4, p->stream));
-        if (counters) HIPCHK(hipMemsetAsync(p->s_ctr + i * nq * 3, 0, (size_t)nq * 12, p->stream));
-    }
+    CHK(partitioned_zero_empty_parts(p, nq, counters));
     std::vector<uint32_t> rungs;
     if (out_rung) {
         rungs.resize(P * nq);
         HIPCHK(hipMemcpyAsync(rungs.data(), p->s_rung, P * nq * 4, hipMemcpyDeviceToHost, p->stream));
     }
     CHK(partitioned_merge(p, nq, k, k, counters, out_pid, out_dist, out_count, out_counters));
-    if (out_rung)
-        for (size_t i = 0; i < P; i++) {
-            if (!p->parts[i].ctx) continue;
-            for (uint32_t q = 0; q < nq; q++) out_rung[(size_t)q * P + i] = rungs[i * nq + q];
-        }
+    partitioned_transpose_rungs(p, rungs, nq, out_rung);
     return IDIST_OK;
 }
 
@@ -4195,21 +4218,15 @@ idist_status idist_search_ctx_allowed_kernel_ms(idist_search_ctx* ctx, float* se
 extern "C++" {
 namespace {
 
-// the result buffer keeps what it holds when it grows (grow() alone frees first)
+// the result buffer keeps what it holds when it grows (DevBuf::grow alone frees first)
 idist_status range_grow_keys(idist_search_ctx* ctx, uint64_t used, uint64_t need) {
     const size_t need_b = (size_t)need * 8;
     if (need_b <= ctx->rg_keys.cap) return IDIST_OK;
-    void* fresh = nullptr;
-    size_t cap = 0;
-    CHK(grow(fresh, cap, doubled_from(4096, need_b)));
-    if (used) {
-        const hipError_t e = hipMemcpyAsync(fresh, ctx->rg_keys.p, (size_t)used * 8, hipMemcpyDeviceToDevice, ctx->stream);
-        if (e != hipSuccess) { hipFree(fresh); HIPCHK(e); }
-    }
+    DevBuf<uint64_t> fresh;
+    CHK(fresh.grow(doubled_from(4096, need_b)));
+    if (used) HIPCHK(hipMemcpyAsync(fresh, ctx->rg_keys, (size_t)used * 8, hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    hipFree(ctx->rg_keys.p);
-    ctx->rg_keys.p = fresh;
-    ctx->rg_keys.cap = cap;
+    ctx->rg_keys = std::move(fresh);                     // (a swap: the old buffer leaves with `fresh`)
     return IDIST_OK;
 }
 
@@ -4227,8 +4244,8 @@ idist_status range_prefix_on(hipStream_t stream, uint64_t* chunk_sum, const uint
 idist_status range_prefix(idist_search_ctx* ctx, const uint32_t* cnt, uint64_t N, uint64_t base, uint64_t* off) {
     const uint64_t chunks = (N + 63u) / 64u;
     if (chunks == 0) return IDIST_OK;
-    CHK(grow(ctx->rg_chunks.p, ctx->rg_chunks.cap, doubled_from(256, (size_t)chunks * 8)));
-    return range_prefix_on(ctx->stream, ctx->rg_chunks.as<uint64_t>(), cnt, N, base, off);
+    CHK(ctx->rg_chunks.grow(doubled_from(256, (size_t)chunks * 8)));
+    return range_prefix_on(ctx->stream, ctx->rg_chunks, cnt, N, base, off);
 }
 
 // every list [ex_off[p], + ex_len[p]) of the result buffer ascending; max_len: the longest of them
@@ -4239,9 +4256,9 @@ idist_status range_sort(idist_search_ctx* ctx, uint32_t np, uint64_t max_len) {
     const uint32_t chunk = ctx->knobs.range_sort_chunk ? ctx->knobs.range_sort_chunk : 2048u;
     const uint32_t chunks_max = (uint32_t)std::max<uint64_t>(P / chunk, 1u);
     const uint64_t pairs_max = P / 2u;
-    uint64_t* keys = ctx->rg_keys.as<uint64_t>();
-    const uint64_t* off = ctx->rg_exoff.as<uint64_t>();
-    const uint32_t* len = ctx->rg_exlen.as<uint32_t>();
+    uint64_t* keys = ctx->rg_keys;
+    const uint64_t* off = ctx->rg_exoff;
+    const uint32_t* len = ctx->rg_exlen;
     const uint64_t cap = (uint64_t)std::max(ctx->n_cu, 1) * 64u;
     const uint32_t grid_l = (uint32_t)std::min<uint64_t>((uint64_t)np * chunks_max, cap);
     const uint32_t grid_g = (uint32_t)std::min<uint64_t>((uint64_t)np * ((pairs_max + 63u) / 64u), cap);
@@ -4352,19 +4369,15 @@ idist_status idist_search_batch_range_allowed_sets(const idist_index* idx, idist
     // they are read
     const uint32_t words = (n + 31u) / 32u;
     const size_t bb = (size_t)n_sets * words * 4;
-    CHK(grow(ctx->al_bits.p, ctx->al_bits.cap, bb));
-    CHK(grow(ctx->al_setof.p, ctx->al_setof.cap, (size_t)nq * 4));
-    std::vector<uint32_t> own_set;                               // set_of == NULL: query q uses set q
-    if (!set_of) {
-        own_set.resize(nq);
-        for (uint32_t q = 0; q < nq; q++) own_set[q] = q;
-        set_of = own_set.data();
-    }
+    CHK(ctx->al_bits.grow(bb));
+    CHK(ctx->al_setof.grow((size_t)nq * 4));
+    std::vector<uint32_t> identity;
+    set_of = set_of_or_identity(set_of, nq, &identity);
     HIPCHK(hipMemcpyAsync(ctx->al_bits.p, allow_bits, bb, hipMemcpyHostToDevice, stream));
     HIPCHK(hipMemcpyAsync(ctx->al_setof.p, set_of, (size_t)nq * 4, hipMemcpyHostToDevice, stream));
     const float* d_qk = nullptr;
     CHK(ladder_upload_queries(idx, ctx, MetricPasses(idx), queries, nq, &d_qk));
-    const RangeSets sets{ctx->al_bits.as<uint32_t>(), ctx->al_setof.as<uint32_t>(), n_sets, words};
+    const RangeSets sets{ctx->al_bits, ctx->al_setof, n_sets, words};
     uint64_t total = 0;
     CHK(range_search_device(idx, ctx, d_qk, ctx->d_sq, nq, radius, n_radius, max_rungs, max_total, out_counters != nullptr, &total, &sets));
     return range_finish(ctx, nq, total, out_lims, out_rung, out_counters);
@@ -4377,9 +4390,9 @@ namespace {
 // back to the caller; the call's last synchronisation; the context holds the results from here on.
 idist_status range_finish(idist_search_ctx* ctx, uint32_t nq, uint64_t total, uint64_t* out_lims, uint32_t* out_rung, uint32_t* out_counters) {
     hipStream_t stream = ctx->stream;
-    CHK(grow(ctx->rg_lims.p, ctx->rg_lims.cap, ((size_t)nq + 1) * 8));
-    uint64_t* d_lims = ctx->rg_lims.as<uint64_t>();
-    auto lims_pass = [&]() -> idist_status { return range_prefix(ctx, ctx->rg_cnt.as<uint32_t>(), nq, 0, d_lims); };
+    CHK(ctx->rg_lims.grow(((size_t)nq + 1) * 8));
+    uint64_t* d_lims = ctx->rg_lims;
+    auto lims_pass = [&]() -> idist_status { return range_prefix(ctx, ctx->rg_cnt, nq, 0, d_lims); };
     CHK(ladder_timed(ctx, 3, lims_pass));
     HIPCHK(hipMemcpyAsync(out_lims, d_lims, ((size_t)nq + 1) * 8, hipMemcpyDeviceToHost, stream));
     if (out_rung) HIPCHK(hipMemcpyAsync(out_rung, ctx->al_orung.p, (size_t)nq * 4, hipMemcpyDeviceToHost, stream));
@@ -4409,29 +4422,29 @@ idist_status range_search_device(const idist_index* idx, idist_search_ctx* ctx, 
     const AllowedLadder lad = make_ladder(idx->cfg.ef_search, max_rungs);
     hipStream_t stream = ctx->stream;
     const uint32_t kdim = idx->kdim, kmetric = (uint32_t)idx->cfg.metric;
-    CHK(grow(ctx->rg_radius.p, ctx->rg_radius.cap, (size_t)n_radius * 4));
-    CHK(grow(ctx->rg_lim.p, ctx->rg_lim.cap, (size_t)nq * 8));
-    CHK(grow(ctx->rg_term.p, ctx->rg_term.cap, (size_t)nq * 4));
-    CHK(grow(ctx->rg_cnt.p, ctx->rg_cnt.cap, (size_t)nq * 4));
-    CHK(grow(ctx->rg_off.p, ctx->rg_off.cap, (size_t)nq * 8));
-    CHK(grow(ctx->rg_stepcnt.p, ctx->rg_stepcnt.cap, (size_t)nq * 4));
-    CHK(grow(ctx->rg_stepoff.p, ctx->rg_stepoff.cap, ((size_t)nq + 1) * 8));
-    CHK(grow(ctx->al_flag.p, ctx->al_flag.cap, (size_t)nq * 4));
-    CHK(grow(ctx->al_list.p, ctx->al_list.cap, (size_t)nq * 4));
-    CHK(grow(ctx->al_npend.p, ctx->al_npend.cap, 256));
-    CHK(grow(ctx->al_pq.p, ctx->al_pq.cap, (size_t)nq * kdim * 4));
-    CHK(grow(ctx->rg_list.p, ctx->rg_list.cap, (size_t)nq * 4));
-    CHK(grow(ctx->al_orung.p, ctx->al_orung.cap, (size_t)nq * 4));
-    CHK(grow(ctx->al_octr.p, ctx->al_octr.cap, (size_t)nq * 12));
+    CHK(ctx->rg_radius.grow((size_t)n_radius * 4));
+    CHK(ctx->rg_lim.grow((size_t)nq * 8));
+    CHK(ctx->rg_term.grow((size_t)nq * 4));
+    CHK(ctx->rg_cnt.grow((size_t)nq * 4));
+    CHK(ctx->rg_off.grow((size_t)nq * 8));
+    CHK(ctx->rg_stepcnt.grow((size_t)nq * 4));
+    CHK(ctx->rg_stepoff.grow(((size_t)nq + 1) * 8));
+    CHK(ctx->al_flag.grow((size_t)nq * 4));
+    CHK(ctx->al_list.grow((size_t)nq * 4));
+    CHK(ctx->al_npend.grow(256));
+    CHK(ctx->al_pq.grow((size_t)nq * kdim * 4));
+    CHK(ctx->rg_list.grow((size_t)nq * 4));
+    CHK(ctx->al_orung.grow((size_t)nq * 4));
+    CHK(ctx->al_octr.grow((size_t)nq * 12));
     HIPCHK(hipMemcpyAsync(ctx->rg_radius.p, radius, (size_t)n_radius * 4, hipMemcpyHostToDevice, stream));
     RangeState st{};
-    st.lim = ctx->rg_lim.as<uint32_t>(); st.term = ctx->rg_term.as<float>(); st.count = ctx->rg_cnt.as<uint32_t>();
-    st.off = ctx->rg_off.as<uint64_t>(); st.rung = ctx->al_orung.as<uint32_t>(); st.counters = counters ? ctx->al_octr.as<uint32_t>() : nullptr;
-    st.pending = ctx->al_flag.as<uint32_t>(); st.nq = nq;
+    st.lim = ctx->rg_lim; st.term = ctx->rg_term; st.count = ctx->rg_cnt;
+    st.off = ctx->rg_off; st.rung = ctx->al_orung; st.counters = counters ? ctx->al_octr.p : nullptr;
+    st.pending = ctx->al_flag; st.nq = nq;
     const uint32_t waves_cap = (uint32_t)std::max(ctx->n_cu, 1) * 64u;
     auto init_pass = [&]() -> idist_status {
         const uint32_t grid = std::min<uint32_t>((nq + 255u) / 256u, (uint32_t)std::max(ctx->n_cu, 1) * 8u);
-        IDIST_LAUNCH(range_init_kernel, grid, 256, 0, stream, st, ctx->rg_radius.as<float>(), n_radius, kmetric, d_sq, idx->dot_S);
+        IDIST_LAUNCH(range_init_kernel, grid, 256, 0, stream, st, ctx->rg_radius, n_radius, kmetric, d_sq, idx->dot_S);
         HIPCHK(hipGetLastError());
         return IDIST_OK;
     };
@@ -4440,32 +4453,32 @@ idist_status range_search_device(const idist_index* idx, idist_search_ctx* ctx, 
     uint64_t total = 0;                                          // keys in the result buffer so far
     const uint32_t* d_list = nullptr;
     const float* d_pq = d_qk;
-    uint32_t* step_cnt = ctx->rg_stepcnt.as<uint32_t>();
-    uint64_t* step_off = ctx->rg_stepoff.as<uint64_t>();
+    uint32_t* step_cnt = ctx->rg_stepcnt;
+    uint64_t* step_off = ctx->rg_stepoff;
     const uint32_t* d_last = nullptr;                            // restricted: the rungs query q may run are r < last[q]
     const uint32_t *s_bits = sets ? sets->bits : nullptr, *s_setof = sets ? sets->set_of : nullptr;
     const uint32_t s_words = sets ? sets->words : 0u, n_sets = sets ? sets->n_sets : 0u;
     // restricted: the queries of rung `rung` (d_last) or everything still pending (nullptr) into al_list / al_pq, their number read back
     auto gather = [&](uint32_t rung, const uint32_t* last) -> idist_status {
-        CHK(ladder_pending(ctx, st.pending, nq, d_qk, kdim, ctx->al_list.as<uint32_t>(), 3, nullptr, rung, last));
+        CHK(ladder_pending(ctx, st.pending, nq, d_qk, kdim, ctx->al_list, 3, nullptr, rung, last));
         HIPCHK(hipMemcpyAsync(&np, ctx->al_npend.p, 4, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
-        d_list = ctx->al_list.as<uint32_t>();
-        d_pq = ctx->al_pq.as<float>();
+        d_list = ctx->al_list;
+        d_pq = ctx->al_pq;
         return IDIST_OK;
     };
     if (sets) {
-        CHK(grow(ctx->al_size.p, ctx->al_size.cap, (size_t)n_sets * 4));
-        CHK(grow(ctx->al_start.p, ctx->al_start.cap, (size_t)n_sets * 4));
-        CHK(grow(ctx->al_first.p, ctx->al_first.cap, (size_t)nq * 4));
-        d_last = ctx->al_first.as<uint32_t>();
+        CHK(ctx->al_size.grow((size_t)n_sets * 4));
+        CHK(ctx->al_start.grow((size_t)n_sets * 4));
+        CHK(ctx->al_first.grow((size_t)nq * 4));
+        d_last = ctx->al_first;
         auto count_pass = [&]() -> idist_status {
             const uint32_t grid_c = std::min<uint32_t>(n_sets, (uint32_t)std::max(ctx->n_cu, 1) * 32u);
             IDIST_LAUNCH(range_allowed_count_kernel, grid_c, 64, 0, stream, s_bits, n, s_words, n_sets, lad,
-                         ctx->al_size.as<uint32_t>(), ctx->al_start.as<uint32_t>());
+                         ctx->al_size, ctx->al_start);
             const uint32_t grid_i = std::min<uint32_t>((nq + 255u) / 256u, (uint32_t)std::max(ctx->n_cu, 1) * 8u);
-            IDIST_LAUNCH(range_allowed_init_kernel, grid_i, 256, 0, stream, st, ctx->al_size.as<uint32_t>(), ctx->al_start.as<uint32_t>(),
-                         s_setof, ctx->al_first.as<uint32_t>());
+            IDIST_LAUNCH(range_allowed_init_kernel, grid_i, 256, 0, stream, st, ctx->al_size, ctx->al_start,
+                         s_setof, ctx->al_first);
             HIPCHK(hipGetLastError());
             return IDIST_OK;
         };
@@ -4482,11 +4495,11 @@ idist_status range_search_device(const idist_index* idx, idist_search_ctx* ctx, 
         auto select_pass = [&]() -> idist_status {
             if (sets)
                 IDIST_LAUNCH(range_allowed_select_kernel, std::min(np_step, 65536u), 64, 0, stream, st, s_bits, n, s_words, s_setof,
-                             ctx->d_pid, reinterpret_cast<const uint32_t*>(ctx->d_dist), ctx->d_cnt, counters ? ctx->d_ctr : nullptr, ef,
+                             ctx->d_pid, reinterpret_cast<const uint32_t*>(ctx->d_dist.p), ctx->d_cnt, counters ? ctx->d_ctr.p : nullptr, ef,
                              d_list, np_step, r, step_cnt);
             else
-                IDIST_LAUNCH(range_select_kernel, std::min(np_step, 65536u), 64, 0, stream, st, reinterpret_cast<const uint32_t*>(ctx->d_dist),
-                             ctx->d_cnt, counters ? ctx->d_ctr : nullptr, ef, d_list, np_step, r, step_cnt);
+                IDIST_LAUNCH(range_select_kernel, std::min(np_step, 65536u), 64, 0, stream, st, reinterpret_cast<const uint32_t*>(ctx->d_dist.p),
+                             ctx->d_cnt, counters ? ctx->d_ctr.p : nullptr, ef, d_list, np_step, r, step_cnt);
             HIPCHK(hipGetLastError());
             return range_prefix(ctx, step_cnt, np_step, total, step_off);
         };
@@ -4494,7 +4507,7 @@ idist_status range_search_device(const idist_index* idx, idist_search_ctx* ctx, 
         // the pending queries of the next rung, gathered BEFORE the copy so that one synchronisation reads the new total and their
         // number: the copy still needs this rung's list, so the lists alternate between two buffers (the rows of this rung stay
         // where they are until the copy has run; the next rows go to al_pq)
-        uint32_t* next_list = d_list == ctx->al_list.as<uint32_t>() ? ctx->rg_list.as<uint32_t>() : ctx->al_list.as<uint32_t>();
+        uint32_t* next_list = d_list == ctx->al_list ? ctx->rg_list : ctx->al_list;
         CHK(ladder_pending(ctx, st.pending, nq, d_qk, kdim, next_list, 3, nullptr, r + 1u, d_last));
         uint64_t new_total = 0;
         HIPCHK(hipMemcpyAsync(&new_total, step_off + np_step, 8, hipMemcpyDeviceToHost, stream));
@@ -4509,18 +4522,18 @@ idist_status range_search_device(const idist_index* idx, idist_search_ctx* ctx, 
         auto copy_pass = [&]() -> idist_status {
             if (sets)
                 IDIST_LAUNCH(range_allowed_copy_kernel, std::min(np_step, 65536u), 64, 0, stream, st, s_bits, n, s_words, s_setof,
-                             ctx->d_pid, reinterpret_cast<const uint32_t*>(ctx->d_dist), ef, d_list, np_step, step_cnt, step_off,
-                             ctx->rg_keys.as<uint64_t>());
+                             ctx->d_pid, reinterpret_cast<const uint32_t*>(ctx->d_dist.p), ef, d_list, np_step, step_cnt, step_off,
+                             ctx->rg_keys);
             else
-                IDIST_LAUNCH(range_copy_kernel, std::min(np_step, 65536u), 64, 0, stream, st, ctx->d_pid, reinterpret_cast<const uint32_t*>(ctx->d_dist),
-                             ef, d_list, np_step, step_cnt, step_off, ctx->rg_keys.as<uint64_t>());
+                IDIST_LAUNCH(range_copy_kernel, std::min(np_step, 65536u), 64, 0, stream, st, ctx->d_pid, reinterpret_cast<const uint32_t*>(ctx->d_dist.p),
+                             ef, d_list, np_step, step_cnt, step_off, ctx->rg_keys);
             HIPCHK(hipGetLastError());
             return IDIST_OK;
         };
         CHK(ladder_timed(ctx, 3, copy_pass));                  // (enqueued, not waited for: the next launch follows it in stream order)
         total = new_total;
         d_list = next_list;
-        d_pq = ctx->al_pq.as<float>();
+        d_pq = ctx->al_pq;
     }
     if (sets) { CHK(gather(kRungExact, nullptr)); }               // whoever is still pending: past its last rung, or the ladder ended
     if (np) {
@@ -4528,12 +4541,12 @@ idist_status range_search_device(const idist_index* idx, idist_search_ctx* ctx, 
         // never narrower than one window
         const uint32_t S = exact_segments(ctx, np, n, ctx->knobs.range_segments);
         const uint64_t items = (uint64_t)np * S;
-        CHK(grow(ctx->d_cnt, ctx->cap_cnt, (size_t)items * 4));
-        CHK(grow(ctx->rg_stepoff.p, ctx->rg_stepoff.cap, (size_t)(items + 1) * 8));
-        CHK(grow(ctx->rg_exoff.p, ctx->rg_exoff.cap, (size_t)np * 8));
-        CHK(grow(ctx->rg_exlen.p, ctx->rg_exlen.cap, (size_t)np * 4));
+        CHK(ctx->d_cnt.grow((size_t)items * 4));
+        CHK(ctx->rg_stepoff.grow((size_t)(items + 1) * 8));
+        CHK(ctx->rg_exoff.grow((size_t)np * 8));
+        CHK(ctx->rg_exlen.grow((size_t)np * 4));
         uint32_t* seg_cnt = ctx->d_cnt;
-        uint64_t* seg_off = ctx->rg_stepoff.as<uint64_t>();
+        uint64_t* seg_off = ctx->rg_stepoff;
         const size_t smem = smem_bytes(idx->L.stride, 0, false);
         if (smem > 64 * 1024) return fail(IDIST_ERR_INVALID_ARG, "dim needs %zu B of LDS per wave (> 64 KiB)", smem);
         const uint32_t grid = (uint32_t)std::min<uint64_t>(items, waves_cap);
@@ -4562,7 +4575,7 @@ idist_status range_search_device(const idist_index* idx, idist_search_ctx* ctx, 
             CHK(scan_pass(nullptr));
             CHK(range_prefix(ctx, seg_cnt, items, total, seg_off));
             IDIST_LAUNCH(range_close_kernel, std::min<uint32_t>((np + 255u) / 256u, 1024u), 256, 0, stream, st, d_list, np, S, seg_off,
-                         ctx->rg_exoff.as<uint64_t>(), ctx->rg_exlen.as<uint32_t>());
+                         ctx->rg_exoff, ctx->rg_exlen);
             HIPCHK(hipGetLastError());
             return IDIST_OK;
         };
@@ -4574,7 +4587,7 @@ idist_status range_search_device(const idist_index* idx, idist_search_ctx* ctx, 
         HIPCHK(hipStreamSynchronize(stream));
         if (new_total > max_total) return range_too_many(new_total, max_total, "the exact step");
         CHK(range_grow_keys(ctx, total, new_total));
-        auto write_pass = [&]() -> idist_status { return scan_pass(ctx->rg_keys.as<uint64_t>()); };
+        auto write_pass = [&]() -> idist_status { return scan_pass(ctx->rg_keys); };
         CHK(ladder_timed(ctx, 4, write_pass));
         const uint64_t max_len = *std::max_element(ex_len.begin(), ex_len.end());
         auto sort_pass = [&]() -> idist_status { return range_sort(ctx, np, max_len); };
@@ -4599,13 +4612,13 @@ idist_status idist_search_ctx_range_fetch(idist_search_ctx* ctx, uint32_t* out_p
     if (!out_pid || !out_dist) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
     HIPCHK(hipSetDevice(ctx->device));
     hipStream_t stream = ctx->stream;
-    CHK(grow(ctx->rg_opid.p, ctx->rg_opid.cap, doubled_from(4096, (size_t)total * 4)));
-    CHK(grow(ctx->rg_odist.p, ctx->rg_odist.cap, doubled_from(4096, (size_t)total * 4)));
+    CHK(ctx->rg_opid.grow(doubled_from(4096, (size_t)total * 4)));
+    CHK(ctx->rg_odist.grow(doubled_from(4096, (size_t)total * 4)));
     RangeState st{};
-    st.term = ctx->rg_term.as<float>(); st.count = ctx->rg_cnt.as<uint32_t>(); st.off = ctx->rg_off.as<uint64_t>(); st.nq = ctx->rg_nq;
+    st.term = ctx->rg_term; st.count = ctx->rg_cnt; st.off = ctx->rg_off; st.nq = ctx->rg_nq;
     const uint32_t grid = std::min<uint32_t>(ctx->rg_nq, (uint32_t)std::max(ctx->n_cu, 1) * 64u);
-    IDIST_LAUNCH(range_gather_kernel, grid, 64, 0, stream, st, ctx->rg_keys.as<uint64_t>(), ctx->rg_lims.as<uint64_t>(), (uint32_t)ctx->rg_metric,
-                 ctx->rg_opid.as<uint32_t>(), ctx->rg_odist.as<float>());
+    IDIST_LAUNCH(range_gather_kernel, grid, 64, 0, stream, st, ctx->rg_keys, ctx->rg_lims, (uint32_t)ctx->rg_metric,
+                 ctx->rg_opid, ctx->rg_odist);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out_pid, ctx->rg_opid.p, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipMemcpyAsync(out_dist, ctx->rg_odist.p, (size_t)total * 4, hipMemcpyDeviceToHost, stream));
@@ -4728,10 +4741,8 @@ idist_status idist_partitioned_search_batch_range(idist_partitioned* p, const fl
     //    stream (step 3 of idist_partitioned_search_batch_allowed_sets).  Every part gets the caller's bound: its own total can never
     //    legitimately exceed the merged one.  A part on the merge device leaves its keys, offsets and counts where its context holds
     //    them; a part elsewhere sends them to the merge device by peer copies on its stream.
-    std::vector<idist_status> st(P, IDIST_OK);
-    std::vector<std::string> msg(P);
     std::vector<uint32_t> rungs(out_rung ? P * (size_t)nq : 0);
-    auto part = [&](size_t i) -> idist_status {
+    CHK(partitioned_fan_out(p, [&](size_t i) -> idist_status {
         idist_partitioned::Part& pt = p->parts[i];
         idist_search_ctx* ctx = pt.ctx;
         const idist_partitioned::Dev& dv = p->devs[pt.dev_slot];
@@ -4743,10 +4754,10 @@ idist_status idist_partitioned_search_batch_range(idist_partitioned* p, const fl
         if (out_rung) HIPCHK(hipMemcpyAsync(rungs.data() + i * nq, ctx->al_orung.p, (size_t)nq * 4, hipMemcpyDeviceToHost, ctx->stream));
         if (dev != p->merge_device) {
             HIPCHK(hipSetDevice(p->merge_device));               // (staging on the merge device only grows)
-            CHK(grow(pt.m_keys, pt.m_cap_keys, doubled_from(4096, (size_t)total * 8)));
-            CHK(grow(pt.m_off, pt.m_cap_off, (size_t)nq * 8));
-            CHK(grow(pt.m_cnt, pt.m_cap_cnt, (size_t)nq * 4));
-            if (counters) CHK(grow(pt.m_ctr, pt.m_cap_ctr, (size_t)nq * 12));
+            CHK(pt.m_keys.grow(doubled_from(4096, (size_t)total * 8)));
+            CHK(pt.m_off.grow((size_t)nq * 8));
+            CHK(pt.m_cnt.grow((size_t)nq * 4));
+            if (counters) CHK(pt.m_ctr.grow((size_t)nq * 12));
             HIPCHK(hipSetDevice(dev));
             if (total) HIPCHK(hipMemcpyPeerAsync(pt.m_keys, p->merge_device, ctx->rg_keys.p, dev, (size_t)total * 8, ctx->stream));
             HIPCHK(hipMemcpyPeerAsync(pt.m_off, p->merge_device, ctx->rg_off.p, dev, (size_t)nq * 8, ctx->stream));
@@ -4755,28 +4766,7 @@ idist_status idist_partitioned_search_batch_range(idist_partitioned* p, const fl
         }
         HIPCHK(hipStreamSynchronize(ctx->stream));
         return ladder_times_resolve(ctx);
-    };
-    auto work = [&](size_t i) {
-        st[i] = part(i);
-        if (st[i] != IDIST_OK) msg[i] = g_err;               // g_err is thread-local
-    };
-    {
-        std::vector<std::thread> threads;
-        long first = -1;                                     // the first non-empty part runs on the calling thread
-        for (size_t i = 0; i < P; i++) {
-            if (!p->parts[i].ctx) continue;
-            if (first < 0) { first = (long)i; continue; }
-            try {
-                threads.emplace_back(work, i);
-            } catch (...) {                                  // no thread to be had: the part runs here, after the others were started
-                work(i);
-            }
-        }
-        if (first >= 0) work((size_t)first);
-        for (auto& t : threads) t.join();                    // every thread is joined before any return
-    }
-    for (size_t i = 0; i < P; i++)
-        if (st[i] != IDIST_OK) return fail(st[i], "part %zu (device %d): %s", i, p->devs[p->parts[i].dev_slot].device, msg[i].c_str());
+    }));
     // 3. the union, on the merge device: the counts and lims, ONE read-back of the total (it checks max_total and sizes the output),
     //    the merge kernel straight into the flat arrays the fetch hands out
     HIPCHK(hipSetDevice(p->merge_device));
@@ -4787,19 +4777,19 @@ idist_status idist_partitioned_search_batch_range(idist_partitioned* p, const fl
         if (!pt.ctx) continue;                               // an empty part hands in no list
         const bool here = p->devs[pt.dev_slot].device == p->merge_device;
         const uint32_t l = L.n_lists++;
-        L.keys[l] = here ? pt.ctx->rg_keys.as<uint64_t>() : pt.m_keys;
-        L.off[l] = here ? pt.ctx->rg_off.as<uint64_t>() : pt.m_off;
-        L.cnt[l] = here ? pt.ctx->rg_cnt.as<uint32_t>() : pt.m_cnt;
-        L.ctr[l] = !counters ? nullptr : (here ? pt.ctx->al_octr.as<uint32_t>() : pt.m_ctr);
+        L.keys[l] = here ? pt.ctx->rg_keys.p : pt.m_keys.p;
+        L.off[l] = here ? pt.ctx->rg_off.p : pt.m_off.p;
+        L.cnt[l] = here ? pt.ctx->rg_cnt.p : pt.m_cnt.p;
+        L.ctr[l] = !counters ? nullptr : (here ? pt.ctx->al_octr.p : pt.m_ctr.p);
         L.base[l] = p->base[i];
     }
     const int n_cu = p->parts[0].idx->n_cu;
-    CHK(grow(p->rm_c, p->cap_rm_c, (size_t)nq * 4));
-    CHK(grow(p->rm_lims, p->cap_rm_lims, ((size_t)nq + 1) * 8));
-    CHK(grow(p->rm_chunks, p->cap_rm_chunks, doubled_from(256, (((size_t)nq + 63u) / 64u) * 8)));
-    if (counters) CHK(grow(p->o_ctr, p->cap_o_ctr, (size_t)nq * 12));
+    CHK(p->rm_c.grow((size_t)nq * 4));
+    CHK(p->rm_lims.grow(((size_t)nq + 1) * 8));
+    CHK(p->rm_chunks.grow(doubled_from(256, (((size_t)nq + 63u) / 64u) * 8)));
+    if (counters) CHK(p->o_ctr.grow((size_t)nq * 12));
     HIPCHK(hipEventRecord(p->ev0, p->stream));
-    CHK(launch_range_merge_counts(L, p->rm_c, counters ? p->o_ctr : nullptr, p->rm_chunks, p->rm_lims, n_cu, p->stream));
+    CHK(launch_range_merge_counts(L, p->rm_c, counters ? p->o_ctr.p : nullptr, p->rm_chunks, p->rm_lims, n_cu, p->stream));
     HIPCHK(hipEventRecord(p->ev1, p->stream));
     uint64_t total = 0;
     HIPCHK(hipMemcpyAsync(&total, p->rm_lims + nq, 8, hipMemcpyDeviceToHost, p->stream));
@@ -4808,8 +4798,8 @@ idist_status idist_partitioned_search_batch_range(idist_partitioned* p, const fl
     HIPCHK(hipEventElapsedTime(&ms_counts, p->ev0, p->ev1));
     if (total > max_total) return range_too_many(total, max_total, "the merge");
     if (total) {
-        CHK(grow(p->rm_opid, p->cap_rm_opid, doubled_from(4096, (size_t)total * 4)));
-        CHK(grow(p->rm_odist, p->cap_rm_odist, doubled_from(4096, (size_t)total * 4)));
+        CHK(p->rm_opid.grow(doubled_from(4096, (size_t)total * 4)));
+        CHK(p->rm_odist.grow(doubled_from(4096, (size_t)total * 4)));
         HIPCHK(hipEventRecord(p->ev0, p->stream));
         CHK(launch_range_merge(L, p->rm_lims, total, p->metric, p->d_sq, p->dot_S, p->rm_opid, p->rm_odist, n_cu, p->stream));
         HIPCHK(hipEventRecord(p->ev1, p->stream));
@@ -4819,11 +4809,7 @@ idist_status idist_partitioned_search_batch_range(idist_partitioned* p, const fl
     HIPCHK(hipStreamSynchronize(p->stream));
     if (total) HIPCHK(hipEventElapsedTime(&ms_merge, p->ev0, p->ev1));
     p->rg_merge_ms = ms_counts + ms_merge;
-    if (out_rung)                                            // the parts' rungs came back [P][nq]
-        for (size_t i = 0; i < P; i++) {
-            if (!p->parts[i].ctx) continue;
-            for (uint32_t q = 0; q < nq; q++) out_rung[(size_t)q * P + i] = rungs[i * nq + q];
-        }
+    partitioned_transpose_rungs(p, rungs, nq, out_rung);
     p->rg_total = total;
     p->rg_valid = true;
     return IDIST_OK;

@@ -30,6 +30,27 @@ def test_host_cpp_gpu(tmp_path):
     _build_and_run(os.path.join(ROOT, "instant-distance_amd", "csrc", "libidist.so"), 1024, tmp_path)
 
 
+def _build_and_run_partitioned(lib_path, tmp_path):
+    exe = str(tmp_path / "host_partitioned")
+    libdir, libname = os.path.dirname(lib_path), os.path.basename(lib_path)[3:-3]
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", os.path.join(ROOT, "tests", "host", "partitioned.cpp"), "-o", exe,
+                           f"-L{libdir}", f"-l{libname}", f"-Wl,-rpath,{libdir}", "-pthread"])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "partitioned ok" in out.stdout
+
+
+def test_partitioned_life_cycle_emulated(tmp_path):
+    """tests/host/partitioned.cpp: one idist_partitioned through every search call with 5, 300 and 5 queries again (its staging
+    grows and is reused), a refused range call, and the object freed after the indexes it borrowed."""
+    _build_and_run_partitioned(engines.build_emu(), tmp_path)
+
+
+@pytest.mark.gpu
+def test_partitioned_life_cycle_gpu(tmp_path):
+    _build_and_run_partitioned(os.path.join(ROOT, "instant-distance_amd", "csrc", "libidist.so"), tmp_path)
+
+
 def _build_and_run_threads(lib_path, args, tmp_path):
     exe = str(tmp_path / "host_threads")
     libdir, libname = os.path.dirname(lib_path), os.path.basename(lib_path)[3:-3]
