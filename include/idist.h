@@ -508,8 +508,10 @@ idist_status idist_partitioned_search_batch_allowed_sets(idist_partitioned* p, c
                                                          uint32_t* out_count,                     /* nq */
                                                          uint32_t* out_rung,                      /* [nq][n_parts] or NULL */
                                                          uint32_t* out_counters);                 /* nq*3 or NULL */
-/* Host time (ms) the last idist_partitioned_search_batch_allowed_sets through p spent on the bitmaps: the strided uploads and the
- * slice kernels of all parts (waited for, to be timed, unless IDIST_KERNEL_EVENTS=0).  0 before the first call. */
+/* Host time (ms) the last idist_partitioned_search_batch_allowed_sets or idist_partitioned_search_batch_range_allowed_sets through p
+ * spent on the bitmaps: the strided uploads and the slice kernels of all parts (waited for, to be timed, unless
+ * IDIST_KERNEL_EVENTS=0).  After an attribute call (idist_partitioned_search_batch_attr / _range_attr): the HIP-event durations of the
+ * parts' bitmap kernels, summed, instead.  0 before the first call. */
 idist_status idist_partitioned_last_allowed_slice_ms(idist_partitioned* p, float* ms);
 /* The slice on its own: d_bits holds n_sets rows of pitch_words u32 words, d_out n_sets rows of (n_out + 31) / 32 words, both in the
  * memory of `device`.  out[s] bit i = in[s] bit bit_offset + i for i < n_out; the bits at positions >= n_out of a row's last word are
@@ -557,9 +559,9 @@ idist_status idist_search_ctx_allowed_kernel_ms(idist_search_ctx* ctx, float* se
 idist_status idist_search_batch_range(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
                                       const float* radius, uint32_t n_radius, int32_t max_rungs, uint64_t max_total,
                                       uint64_t* out_lims, uint32_t* out_rung, uint32_t* out_counters);
-/* The results of the last successful idist_search_batch_range or idist_search_batch_range_allowed_sets through ctx: out_pid /
- * out_dist [lims[nq]] each (may be NULL when that is 0), in query order, reported distances.  They are handed out once: a fetch
- * without a preceding successful range call (or a second one) is IDIST_ERR_INVALID_ARG. */
+/* The results of the last successful idist_search_batch_range, idist_search_batch_range_allowed_sets or idist_search_batch_range_attr
+ * through ctx: out_pid / out_dist [lims[nq]] each (may be NULL when that is 0), in query order, reported distances.  They are handed
+ * out once: a fetch without a preceding successful range call (or a second one) is IDIST_ERR_INVALID_ARG. */
 idist_status idist_search_ctx_range_fetch(idist_search_ctx* ctx, uint32_t* out_pid, float* out_dist);
 /* HIP-event durations (ms) of the kernels the last idist_search_batch_range or idist_search_batch_range_allowed_sets through ctx ran
  * around its searches: the select passes (limits, within-prefixes, offsets, copies, pending lists; the restricted call's count pass),
@@ -602,7 +604,8 @@ idist_status idist_search_ctx_range_kernel_ms(idist_search_ctx* ctx, float* sele
  * times; idx is never mutated.  nq == 0: lims[0] = 0.
  * IDIST_ERR_INVALID_ARG: the cases of idist_search_batch_range and of idist_search_batch_allowed_sets' sets (n_sets == 0; set_of == NULL
  * with n_sets != nq; a set_of[q] >= n_sets, the message names q); null pointers.
- * Out of scope: the partitioned index, device-pointer / stream variants and idist_search_batch_sharded. */
+ * Out of scope: device-pointer / stream variants and idist_search_batch_sharded.  The partitioned index:
+ * idist_partitioned_search_batch_range_allowed_sets below. */
 idist_status idist_search_batch_range_allowed_sets(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
                                                    const float* radius, uint32_t n_radius,
                                                    const uint32_t* allow_bits,              /* [n_sets][(n + 31) / 32] */
@@ -635,14 +638,47 @@ idist_status idist_search_batch_range_allowed_sets(const idist_index* idx, idist
  * where their contexts hold them (completion order, a per-query offset and count); parts elsewhere send keys, offsets and counts by
  * peer copies.  Work is divided by results, not by queries; up to 64 lists; no size cap but max_total.  ONE read-back of the merged
  * total precedes the merge.  The results are held by p until the next range call through it or until they are fetched.
- * Host pointers; blocks until done; p is used by one thread at a time.  Out of scope: device-pointer / stream variants,
- * idist_search_batch_sharded and a restricted range search over the parts (one index: idist_search_batch_range_allowed_sets). */
+ * Host pointers; blocks until done; p is used by one thread at a time.  Out of scope: device-pointer / stream variants and
+ * idist_search_batch_sharded.  Restricted to one allowed set per query: idist_partitioned_search_batch_range_allowed_sets below. */
 idist_status idist_partitioned_search_batch_range(idist_partitioned* p, const float* queries, uint32_t nq,
                                                   const float* radius, uint32_t n_radius, int32_t max_rungs, uint64_t max_total,
                                                   uint64_t* out_lims,        /* nq + 1 */
                                                   uint32_t* out_rung,        /* [nq][n_parts] or NULL */
                                                   uint32_t* out_counters);   /* nq*3 or NULL */
-/* The results of the last successful idist_partitioned_search_batch_range through p: out_pid (global ids) / out_dist [lims[nq]] each
+/* Restricted range search over a partitioned index: the two calls above, composed (DESIGN.md sections 4.10 and 8.1).
+ *   allow_bits, n_sets, set_of   exactly as idist_partitioned_search_batch_allowed_sets: n_sets bitmaps over the GLOBAL ids, (N + 31) / 32
+ *                                words each, bits at positions >= N ignored, the buffer neither written nor cleaned on the host;
+ *                                set_of == NULL requires n_sets == nq.
+ *   radius, n_radius, max_rungs, max_total, out_lims, out_rung, out_counters   exactly as idist_partitioned_search_batch_range.
+ * DEFINITION: A_p = the slice of query q's set that falls into part p (bit i of A_p = bit base[p] + i of the set, i < n_p).  Row q is the
+ * merge, by the u64 key  raw distance bits << 32 | global id, of what
+ *   idist_search_batch_range_allowed_sets(part p, ctx, &queries[q * dim], 1, &radius[q], 1, A_p, 1, NULL, max_rungs, ...)
+ * returns on every non-empty part.  So:
+ *   - every part applies its own end rule E[r] < 2 |A_p|, climbs its own ladder and ends in its own exact scan of A_p's rows; a part
+ *     that holds none of a query's allowed points answers IDIST_RUNG_NONE at once;
+ *   - the metric's report runs once, after the merge, with the query's own term;
+ *   - max_total bounds the merged RESTRICTED total: it is passed to every part and checked again after the merge, with the messages
+ *     and the "holds nothing" rule of idist_partitioned_search_batch_range;
+ *   - the results are held by p and handed out once by idist_partitioned_range_fetch; idist_partitioned_last_range_merge_ms and
+ *     idist_partitioned_last_allowed_slice_ms report the merge and the bitmaps' upload + slice;
+ *   - with max_rungs == 0 the answer is every allowed point within the radius, ordered by (raw distance bits, global id).
+ * One part is the identity: every output equals idist_search_batch_range_allowed_sets on that part.  With every bit set and
+ * 2 n_p > IDIST_MAX_EF in every part, every output equals idist_partitioned_search_batch_range's.
+ * IDIST_ERR_INVALID_ARG: the cases of idist_partitioned_search_batch_range and of idist_search_batch_allowed_sets' sets.
+ * The bitmaps reach the parts as in idist_partitioned_search_batch_allowed_sets (one strided copy + the slice kernel per part);
+ * everything else is idist_partitioned_search_batch_range's schedule, which the plain call still launches unchanged.
+ * Host pointers; blocks until done; p is used by one thread at a time.  Out of scope: device-pointer / stream variants and
+ * idist_search_batch_sharded. */
+idist_status idist_partitioned_search_batch_range_allowed_sets(idist_partitioned* p, const float* queries, uint32_t nq,
+                                                               const float* radius, uint32_t n_radius,
+                                                               const uint32_t* allow_bits,              /* [n_sets][(N + 31) / 32], global ids */
+                                                               uint32_t n_sets, const uint32_t* set_of, /* [nq] or NULL */
+                                                               int32_t max_rungs, uint64_t max_total,
+                                                               uint64_t* out_lims,        /* nq + 1 */
+                                                               uint32_t* out_rung,        /* [nq][n_parts] or NULL */
+                                                               uint32_t* out_counters);   /* nq*3 or NULL */
+/* The results of the last successful idist_partitioned_search_batch_range, idist_partitioned_search_batch_range_allowed_sets or
+ * idist_partitioned_search_batch_range_attr through p: out_pid (global ids) / out_dist [lims[nq]] each
  * (may be NULL when that is 0).  The rules of idist_search_ctx_range_fetch: handed out once; a second fetch, or one with nothing held,
  * is IDIST_ERR_INVALID_ARG. */
 idist_status idist_partitioned_range_fetch(idist_partitioned* p, uint32_t* out_pid, float* out_dist);
@@ -664,6 +700,81 @@ idist_status idist_range_merge_device(const void* const* d_keys, const void* con
                                       uint32_t n_lists, uint32_t nq, const uint32_t* base, int32_t metric, const void* d_sq,
                                       float dot_bound, uint64_t capacity, void* d_lims, void* d_out_pid, void* d_out_dist,
                                       uint64_t* out_total, int32_t device, void* hip_stream);
+
+/* ---- attribute filters: a u32 per point, an interval per query, the bitmaps made on the device -------------- */
+/* The allowed sets above are for "tenants, ACL groups, categories and date ranges mixed in one batch": the caller holds one small
+ * integer per point and one condition per query.  An idist_attr keeps that integer on the device, next to the rows; the four calls
+ * below take an interval per query instead of bitmaps and make the bitmaps where they are read.
+ *   values      one u32 per point: PointId order for an index, global-id order (N of them) for a partitioned index.
+ *   an attr     a device copy of the values — on the index's device; for a partitioned index every non-empty part's slice
+ *               values[base[p] .. base[p] + n_p) on that part's own device.  Immutable after creation, may be shared by any number of
+ *               threads and contexts.  Bound to the handle it was made for by identity, not by address, as a search context is: with any
+ *               other index or partitioned index, with an index's attribute in a partitioned call or the reverse, every call below is
+ *               IDIST_ERR_INVALID_ARG.  The index is not touched and stays immutable.  n == 0 is legal (values may be NULL).  Free it
+ *               with idist_attr_free, before or after the handle it was made for.
+ *   lo, hi      n_cond intervals: point i satisfies interval c iff lo[c] <= values[i] && values[i] <= hi[c], UNSIGNED comparisons
+ *               (lo == hi: equality; lo > hi: the empty set, legal; (0, 0xFFFFFFFF): every point).
+ *   n_cond      1: one condition for the whole batch; nq: one per query — as n_radius.  Anything else is IDIST_ERR_INVALID_ARG.
+ * DEFINITION: let D be the distinct (lo, hi) pairs of the call, bits[s] the bitmap of pair s (bit i = the condition on values[i], the
+ * bits at positions >= n zero) and set_of[q] the index of query q's pair.  Every output of a call below equals, bit for bit, the output
+ * of the call it is listed with, given (bits, |D|, set_of):
+ *   idist_search_batch_attr                     idist_search_batch_allowed_sets
+ *   idist_search_batch_range_attr               idist_search_batch_range_allowed_sets       (results: idist_search_ctx_range_fetch)
+ *   idist_partitioned_search_batch_attr         idist_partitioned_search_batch_allowed_sets, bitmaps over the global ids
+ *   idist_partitioned_search_batch_range_attr   idist_partitioned_search_batch_range_allowed_sets  (idist_partitioned_range_fetch)
+ * and everything else comes from those calls: the other arguments and their errors (a NaN radius names its query), the trivial cases
+ * (nq == 0, no points, ef_search == 0), max_total, the strict-tie retry, the LDS rule for later rungs, out_rung [nq][n_parts] for the
+ * parts.  Null lo / hi / attr: IDIST_ERR_INVALID_ARG.
+ * The conditions are grouped on the host (nq entries); lo / hi / set_of are uploaded; one kernel on the context's stream writes the
+ * |D| bitmaps where the restricted search reads them, and the call goes on exactly as the bitmap call does.  On a partitioned index
+ * every part makes its own bitmaps from its own slice of the values, on its own stream: no strided upload, no slice kernel — by
+ * construction the slice of the global bitmap.  Staging: |D| * ((n + 31) / 32) * 4 bytes per context (per part: n_p for n), nothing
+ * of the size of n crosses PCIe; an allocation that fails is returned as IDIST_ERR_HIP, nothing is truncated.
+ * Host pointers; blocks until done; ctx / p are the `&mut Search` as in the bitmap calls.
+ * Out of scope: conditions over several attributes or unions of intervals (make the bitmaps and use the bitmap calls), testing the
+ * attribute inside the select / scan kernels instead of through bitmaps, device-pointer / stream variants and
+ * idist_search_batch_sharded. */
+typedef struct idist_attr idist_attr;
+idist_status idist_attr_new(const idist_index* idx, const uint32_t* values /* [n], PointId order */, idist_attr** out);
+idist_status idist_partitioned_attr_new(const idist_partitioned* p, const uint32_t* values /* [N], global-id order */, idist_attr** out);
+void idist_attr_free(idist_attr* a);
+idist_status idist_search_batch_attr(const idist_index* idx, idist_search_ctx* ctx, const idist_attr* attr, const float* queries, uint32_t nq,
+                                     const uint32_t* lo, const uint32_t* hi, uint32_t n_cond, /* 1 or nq */
+                                     uint32_t k, int32_t max_rungs,
+                                     uint32_t* out_pid, float* out_dist,      /* nq*k */
+                                     uint32_t* out_count, uint32_t* out_rung, /* nq; out_rung may be NULL */
+                                     uint32_t* out_counters);                 /* nq*3 or NULL */
+idist_status idist_search_batch_range_attr(const idist_index* idx, idist_search_ctx* ctx, const idist_attr* attr, const float* queries,
+                                           uint32_t nq, const float* radius, uint32_t n_radius,
+                                           const uint32_t* lo, const uint32_t* hi, uint32_t n_cond, /* 1 or nq */
+                                           int32_t max_rungs, uint64_t max_total,
+                                           uint64_t* out_lims, uint32_t* out_rung, uint32_t* out_counters);
+idist_status idist_partitioned_search_batch_attr(idist_partitioned* p, const idist_attr* attr, const float* queries, uint32_t nq,
+                                                 const uint32_t* lo, const uint32_t* hi, uint32_t n_cond, /* 1 or nq */
+                                                 uint32_t k, int32_t max_rungs,
+                                                 uint32_t* out_pid, float* out_dist,      /* nq*k, global ids */
+                                                 uint32_t* out_count,                     /* nq */
+                                                 uint32_t* out_rung,                      /* [nq][n_parts] or NULL */
+                                                 uint32_t* out_counters);                 /* nq*3 or NULL */
+idist_status idist_partitioned_search_batch_range_attr(idist_partitioned* p, const idist_attr* attr, const float* queries, uint32_t nq,
+                                                       const float* radius, uint32_t n_radius,
+                                                       const uint32_t* lo, const uint32_t* hi, uint32_t n_cond, /* 1 or nq */
+                                                       int32_t max_rungs, uint64_t max_total,
+                                                       uint64_t* out_lims,        /* nq + 1 */
+                                                       uint32_t* out_rung,        /* [nq][n_parts] or NULL */
+                                                       uint32_t* out_counters);   /* nq*3 or NULL */
+/* HIP-event duration (ms) of the bitmap kernel of the last idist_search_batch_attr / idist_search_batch_range_attr through ctx;
+ * 0 before the first one, when that call had nothing to find, and with IDIST_KERNEL_EVENTS=0.  After a partitioned attribute call
+ * idist_partitioned_last_allowed_slice_ms reports the parts' bitmap kernels, summed, instead of uploads plus slices. */
+idist_status idist_search_ctx_attr_bitmap_ms(idist_search_ctx* ctx, float* ms);
+/* The bitmap kernel on its own (the role idist_allowed_slice_device plays for the slice): d_values [n], d_lo / d_hi [n_sets], d_out
+ * [n_sets][(n + 31) / 32], all u32 in the memory of `device`.  Bit i of out[s] = d_lo[s] <= d_values[i] && d_values[i] <= d_hi[s],
+ * unsigned, for i < n; the bits at positions >= n of a row's last word are written as 0.  Every output word is written exactly once
+ * (no atomics, nothing to clear first, the same bytes whatever the grid); nothing is read past d_values[n - 1], nothing is written
+ * past a row's last word.  n == 0 or n_sets == 0: nothing is done.  Enqueued on `hip_stream` (a hipStream_t, may be NULL) without
+ * synchronising. */
+idist_status idist_attr_bitmaps_device(const void* d_values, uint32_t n, const void* d_lo, const void* d_hi, uint32_t n_sets,
+                                       void* d_out, int32_t device, void* hip_stream);
 
 /* Point::distance for id lists (core/lib.rs:780-782 as used at :709-710): out[q][i] =
  * distance(queries[q], points[ids[q][i]]) for i < n_ids; IDIST_INVALID ids give +inf.

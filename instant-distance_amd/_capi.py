@@ -167,6 +167,21 @@ SYMBOLS = {
                                                                 _u32p, _f32p, _u32p, _u32p, _u32p]),
     "idist_partitioned_last_allowed_slice_ms": (C.c_int32, [_vp, C.POINTER(C.c_float)]),
     "idist_allowed_slice_device": (C.c_int32, [_vp, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, _vp, C.c_int32, _vp]),
+    "idist_partitioned_search_batch_range_allowed_sets": (C.c_int32, [_vp, _f32p, C.c_uint32, _f32p, C.c_uint32, _u32p, C.c_uint32, _u32p,
+                                                                      C.c_int32, C.c_uint64, _u64p, _u32p, _u32p]),
+    "idist_attr_new": (C.c_int32, [_vp, _u32p, C.POINTER(_vp)]),
+    "idist_partitioned_attr_new": (C.c_int32, [_vp, _u32p, C.POINTER(_vp)]),
+    "idist_attr_free": (None, [_vp]),
+    "idist_search_batch_attr": (C.c_int32, [_vp, _vp, _vp, _f32p, C.c_uint32, _u32p, _u32p, C.c_uint32, C.c_uint32, C.c_int32, _u32p, _f32p,
+                                            _u32p, _u32p, _u32p]),
+    "idist_search_batch_range_attr": (C.c_int32, [_vp, _vp, _vp, _f32p, C.c_uint32, _f32p, C.c_uint32, _u32p, _u32p, C.c_uint32, C.c_int32,
+                                                  C.c_uint64, _u64p, _u32p, _u32p]),
+    "idist_partitioned_search_batch_attr": (C.c_int32, [_vp, _vp, _f32p, C.c_uint32, _u32p, _u32p, C.c_uint32, C.c_uint32, C.c_int32, _u32p,
+                                                        _f32p, _u32p, _u32p, _u32p]),
+    "idist_partitioned_search_batch_range_attr": (C.c_int32, [_vp, _vp, _f32p, C.c_uint32, _f32p, C.c_uint32, _u32p, _u32p, C.c_uint32,
+                                                              C.c_int32, C.c_uint64, _u64p, _u32p, _u32p]),
+    "idist_search_ctx_attr_bitmap_ms": (C.c_int32, [_vp, C.POINTER(C.c_float)]),
+    "idist_attr_bitmaps_device": (C.c_int32, [_vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, C.c_int32, _vp]),
     "idist_distance_batch": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, _f32p]),
     "idist_filter_bound_batch": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, _f32p]),
     "idist_bruteforce": (C.c_int32, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),

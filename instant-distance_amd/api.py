@@ -264,6 +264,12 @@ class Search:
         _lib().check(_lib().idist_search_ctx_allowed_kernel_ms(self._ctx, C.byref(a), C.byref(b), C.byref(c)))
         return float(a.value), float(b.value), float(c.value)
 
+    def attr_bitmap_ms(self) -> float:
+        """HIP-event time (ms) of the bitmap kernel of the last `search_where` / `search_range_where` through this Search."""
+        ms = C.c_float(0)
+        _lib().check(_lib().idist_search_ctx_attr_bitmap_ms(self._ctx, C.byref(ms)))
+        return float(ms.value)
+
     def range_kernel_ms(self) -> tuple[float, float, float]:
         """HIP-event time (ms) of the select passes (limits, within-prefixes, offsets, copies, pending lists), the exact step's two
         scans and the sort of the last `search_range` through this Search; the rungs' own search kernels are in `kernel_times_ms`."""
@@ -430,6 +436,65 @@ def _set_of(set_of, n_sets: int, nq: int):
     if so.size and (so.min() < 0 or so.max() >= n_sets):
         raise IndexError(f"`set_of` names a set outside [0, {n_sets})")
     return np.ascontiguousarray(so.astype(np.uint32))
+
+
+def _as_u32(x, what: str) -> np.ndarray:
+    """integers as the ABI's uint32, shape kept; anything outside [0, 2**32) raises instead of wrapping"""
+    a = np.asarray(x)
+    if a.dtype == object:                                  # Python ints beyond int64
+        flat = [v for v in a.reshape(-1)]
+        if not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in flat):
+            raise TypeError(f"`{what}` holds integers")
+        if any(not 0 <= int(v) <= 0xFFFFFFFF for v in flat):
+            raise ValueError(f"`{what}` holds a value outside the uint32 range [0, 2**32)")
+        return np.array([int(v) for v in flat], dtype=np.uint32).reshape(a.shape)
+    if a.size and (a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer)):
+        raise TypeError(f"`{what}` holds integers, got {a.dtype}")
+    if a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+        raise ValueError(f"`{what}` holds a value outside the uint32 range [0, 2**32)")
+    return a.astype(np.uint32)
+
+
+def _conditions(lo, hi, nq: int) -> tuple[np.ndarray, np.ndarray, int]:
+    """The intervals of a `search_where` call as the ABI takes them: (lo, hi, n_cond).  `lo` / `hi`: scalars (one condition for the
+    batch) or arrays of nq (one per query; a scalar next to an array is repeated); hi=None means equality."""
+    lo_a = _as_u32(lo, "lo")
+    hi_a = lo_a if hi is None else _as_u32(hi, "hi")
+    for a, what in ((lo_a, "lo"), (hi_a, "hi")):
+        if a.ndim > 1 or (a.ndim == 1 and a.shape[0] != nq):
+            raise ValueError(f"`{what}` is one integer or an array of nq = {nq}, got shape {a.shape}")
+    if lo_a.ndim == 0 and hi_a.ndim == 0:
+        return lo_a.reshape(1).copy(), hi_a.reshape(1).copy(), 1
+    return (np.ascontiguousarray(np.broadcast_to(lo_a, (nq,))), np.ascontiguousarray(np.broadcast_to(hi_a, (nq,))), nq)
+
+
+class Attr:
+    """One uint32 per point, on the device next to the rows (idist_attr): what `search_where` / `search_range_where` compare a
+    query's interval with.  Made by `Hnsw.attributes` / `PartitionedHnsw.attributes` and bound to that index: any other raises
+    IdistError.  Immutable; `values` keeps the host copy."""
+
+    def __init__(self, handle, owner, values: np.ndarray):
+        self._h = handle
+        self._owner = owner           # (kept alive: the handle names it)
+        self.values = values
+
+    def __len__(self):
+        return self.values.shape[0]
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) is not None:
+                _lib().idist_attr_free(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+def _attr_values(values, n: int) -> np.ndarray:
+    v = _as_u32(values, "values")
+    if v.shape != (n,):
+        raise ValueError(f"`values` must have one entry per point: shape ({n},), got {v.shape}")
+    return np.ascontiguousarray(v)
 
 
 def normalize(points, device: int = 0, return_norm2: bool = False):
@@ -733,6 +798,72 @@ class Hnsw:
                                                   _capi.u32p(ctr) if counters else None))
         return AllowedResult(pid, dist, cnt, rung, ctr)
 
+    def attributes(self, values) -> Attr:
+        """One uint32 per point (a tenant id, a category, a day number), in PointId order — the order of a bool `allowed` mask —
+        copied to the index's device once (idist_attr_new) for `search_where` / `search_range_where`.  Values outside uint32
+        raise."""
+        v = _attr_values(values, int(self.info().n))
+        h = C.c_void_p()
+        L = _lib()
+        L.check(L.idist_attr_new(self._h, _capi.u32p(v), C.byref(h)))
+        return Attr(h, self, v)
+
+    def search_where(self, queries, attr: Attr, lo, hi=None, k: int = 10, search: Search | None = None, max_rungs: int = -1,
+                     counters: bool = False) -> AllowedResult:
+        """The k nearest among the points whose attribute lies in the query's interval: lo <= attr <= hi, unsigned
+        (idist_search_batch_attr).  `lo` / `hi`: one integer for the batch or an array of one per query; hi=None means equality;
+        lo > hi is the empty set.  Row q is exactly what `search_allowed_sets` returns for the mask
+        `(attr.values >= lo[q]) & (attr.values <= hi[q])` — but the masks are made on the device from the attribute that already
+        lives there: nothing of the size of n is computed on the host or uploaded."""
+        q = _as_points(queries)
+        info = self.info()
+        if q.shape[0] and info.n and q.shape[1] != info.dim:
+            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
+        nq, k = q.shape[0], int(k)
+        lo_a, hi_a, n_cond = _conditions(lo, hi, nq)
+        kk = max(k, 0)
+        pid = np.full((nq, kk), INVALID, dtype=np.uint32)
+        dist = np.full((nq, kk), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        rung = np.full(nq, RUNG_NONE, dtype=np.uint32)
+        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
+        search = search if search is not None else Search()
+        ctx = search._bind(self)
+        L = _lib()
+        L.check(L.idist_search_batch_attr(self._h, ctx, attr._h, _capi.f32p(q), nq, _capi.u32p(lo_a), _capi.u32p(hi_a), n_cond, kk,
+                                          int(max_rungs), _capi.u32p(pid), _capi.f32p(dist), _capi.u32p(cnt), _capi.u32p(rung),
+                                          _capi.u32p(ctr) if counters else None))
+        return AllowedResult(pid, dist, cnt, rung, ctr)
+
+    def search_range_where(self, queries, radius, attr: Attr, lo, hi=None, search: Search | None = None, max_rungs: int = -1,
+                           max_total: int = 64 * 2**20, counters: bool = False) -> RangeResult:
+        """Every point within `radius` whose attribute lies in the query's interval (idist_search_batch_range_attr): row q is
+        exactly what `search_range_allowed_sets` returns for the mask of `search_where`; `radius`, `max_rungs`, `max_total` as in
+        `search_range`, `lo` / `hi` as in `search_where`."""
+        q = _as_points(queries)
+        info = self.info()
+        if q.shape[0] and info.n and q.shape[1] != info.dim:
+            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
+        nq = q.shape[0]
+        rad = np.ascontiguousarray(np.asarray(radius, dtype=np.float32).reshape(-1))
+        if rad.size != 1 and rad.size != nq:
+            raise ValueError(f"`radius` is one float or an array of nq = {nq}, got {rad.size}")
+        lo_a, hi_a, n_cond = _conditions(lo, hi, nq)
+        lims = np.zeros(nq + 1, dtype=np.uint64)
+        rung = np.full(nq, RUNG_NONE, dtype=np.uint32)
+        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
+        search = search if search is not None else Search()
+        ctx = search._bind(self)
+        L = _lib()
+        L.check(L.idist_search_batch_range_attr(self._h, ctx, attr._h, _capi.f32p(q), nq, _capi.f32p(rad), int(rad.size), _capi.u32p(lo_a),
+                                                _capi.u32p(hi_a), n_cond, int(max_rungs), int(max_total), _capi.u64p(lims),
+                                                _capi.u32p(rung), _capi.u32p(ctr) if counters else None))
+        total = int(lims[nq])
+        pid = np.zeros(total, dtype=np.uint32)
+        dist = np.zeros(total, dtype=np.float32)
+        L.check(L.idist_search_ctx_range_fetch(ctx, _capi.u32p(pid), _capi.f32p(dist)))
+        return RangeResult(lims, pid, dist, rung, ctr)
+
     def search_batch_device(self, search: Search, d_queries: int, nq: int, d_pid: int, d_dist: int, d_count: int,
                             d_counters: int = 0, stream: int = 0):
         """Device-pointer variant: inputs/outputs stay in HBM, enqueued on `stream` without a sync."""
@@ -876,6 +1007,22 @@ class HnswMap:
         r = self.hnsw.search_allowed_sets(queries, sets, set_of, k, search, max_rungs)
         return [[MapItem(float(r.distance[i, j]), int(r.pid[i, j]), self.hnsw.points[int(r.pid[i, j])], self.values[int(r.pid[i, j])])
                  for j in range(int(r.count[i]))] for i in range(r.pid.shape[0])]
+
+    def attributes(self, values) -> Attr:
+        """`Hnsw.attributes`: one uint32 per point in PointId order (the order of `self.values`)."""
+        return self.hnsw.attributes(values)
+
+    def search_where(self, queries, attr: Attr, lo, hi=None, k: int = 10, search: Search | None = None,
+                     max_rungs: int = -1) -> list[list[MapItem]]:
+        """`Hnsw.search_where` with the values: per query its results as `MapItem`s, nearest first."""
+        r = self.hnsw.search_where(queries, attr, lo, hi, k, search, max_rungs)
+        return [[MapItem(float(r.distance[i, j]), int(r.pid[i, j]), self.hnsw.points[int(r.pid[i, j])], self.values[int(r.pid[i, j])])
+                 for j in range(int(r.count[i]))] for i in range(r.pid.shape[0])]
+
+    def search_range_where(self, queries, radius, attr: Attr, lo, hi=None, search: Search | None = None, max_rungs: int = -1,
+                           max_total: int = 64 * 2**20) -> list[list[MapItem]]:
+        """`Hnsw.search_range_where` with the values: per query every result of its interval within its radius as `MapItem`s."""
+        return self._range_items(self.hnsw.search_range_where(queries, radius, attr, lo, hi, search, max_rungs, max_total))
 
     def iter(self):
         return self.hnsw.iter()

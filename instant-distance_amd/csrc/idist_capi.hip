@@ -12,6 +12,7 @@
 #include "idist_range.hpp"
 #include "idist_range_allowed.hpp"
 #include "idist_range_merge.hpp"
+#include "idist_attr.hpp"
 #include "idist_basis.hpp"
 
 #ifndef IDIST_EMU
@@ -26,6 +27,7 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <memory>
 #include <mutex>
 #include <cmath>
 #include <cstdarg>
@@ -73,8 +75,15 @@ inline void warn_ignored_knobs() {
 }
 #endif
 
-char g_err_anchor;                                       // (its address identifies this loaded library, see index_alloc)
+char g_err_anchor;                                       // (its address identifies this loaded library, see fresh_uid)
 thread_local std::string g_err;
+// The identity of an index or a partitioned index, never reused.  uids are unique across the libraries of one process too
+// (libidist.so and the test build libidist_variants.so share handles in tests/): the counter starts at a value derived from where
+// THIS library was mapped
+uint64_t fresh_uid() {
+    static std::atomic<uint64_t> next_uid{(((uint64_t)(uintptr_t)&g_err_anchor >> 12) << 28) | 1u};
+    return next_uid.fetch_add(1);
+}
 thread_local struct idist_progress* g_watch = nullptr;   // armed by idist_progress_watch_next_build
 
 inline void cpu_relax() {
@@ -448,6 +457,12 @@ struct idist_search_ctx {
     // (idist_search_ctx_allowed_kernel_ms); [3..5]: the last range search's select (+ init, prefix, pending, copy, lims), exact scan
     // and sort kernels (idist_search_ctx_range_kernel_ms)
     float al_ms[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    // An attribute call: the call's distinct intervals next to al_bits, which attr_bitmaps_kernel fills instead of
+    // an upload; its own pair of events (created on first use) and the time they gave (idist_search_ctx_attr_bitmap_ms)
+    DevBuf<uint32_t> at_lo, at_hi;
+    hipEvent_t at_ev[2] = {nullptr, nullptr};
+    bool at_timed = false;
+    float at_ms = 0.0f;
     DevBuf<float> rg_radius, rg_term, rg_odist;
     DevBuf<uint32_t> rg_lim, rg_cnt, rg_stepcnt, rg_exlen, rg_opid, rg_list;
     DevBuf<uint64_t> rg_off, rg_stepoff, rg_chunks, rg_keys, rg_exoff, rg_lims;
@@ -471,6 +486,7 @@ struct idist_search_ctx {
 // `&mut Search` over all parts.  The indexes are borrowed.  The object owns a search context per non-empty part (freed by
 // idist_partitioned_free), its stream and events, and every DevBuf below: staging that only grows and frees itself with the object.
 struct idist_partitioned {
+    uint64_t uid = 0;                        // never reused (fresh_uid): an idist_attr is bound to it, not to the address
     struct Part {
         const idist_index* idx = nullptr;
         uint64_t uid = 0;
@@ -502,6 +518,7 @@ struct idist_partitioned {
     DevBuf<float> s_dist, o_dist;
     DevBuf<uint32_t> s_rung;                 // restricted search: the parts' rungs [P][nq]
     float al_slice_ms = 0.0f;                // ... and the host time its last call spent on the bitmaps: upload + slice, every part
+                                             // (an attribute call: the parts' bitmap kernels, HIP events, summed)
     // range search, on the merge device: the merged counts, lims and the chunk sums of their prefix sum; the merged result, which no
     // other call writes and idist_partitioned_range_fetch hands out once
     DevBuf<uint32_t> rm_c, rm_opid;
@@ -513,6 +530,20 @@ struct idist_partitioned {
     hipStream_t stream = nullptr;            // the merge and the copies of its result
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
+};
+
+// One u32 per point on the device, next to the rows (include/idist.h): immutable after creation.  Bound to the
+// handle it was made for by that handle's uid.  An index: one slice on its device; a partitioned index: one per part, empty parts
+// included (n == 0, no memory), each on its part's device.  The slices free themselves.
+struct idist_attr {
+    uint64_t owner_uid = 0;
+    bool partitioned = false;
+    struct Slice {
+        uint32_t n = 0;
+        int32_t device = 0;
+        DevBuf<uint32_t> v;
+    };
+    std::vector<Slice> parts;
 };
 
 namespace {
@@ -595,11 +626,8 @@ idist_status index_alloc(uint32_t n, uint32_t dim, const idist_config* cfg, cons
     if (n == 0xFFFFFFFFu) return fail(IDIST_ERR_INVALID_ARG, "n must be < u32::MAX (core/lib.rs:256)");
     if (n_upper >= IDIST_MAX_LAYERS) return fail(IDIST_ERR_INVALID_ARG, "more than %u layers", IDIST_MAX_LAYERS);
     CHK(check_device(device));
-    // uids are unique across the libraries of one process too (libidist.so and the test build libidist_variants.so share handles in
-    // tests/): the counter starts at a value derived from where THIS library was mapped
-    static std::atomic<uint64_t> next_uid{(((uint64_t)(uintptr_t)&g_err_anchor >> 12) << 28) | 1u};
     idist_index* ix = new idist_index();
-    ix->uid = next_uid.fetch_add(1);
+    ix->uid = fresh_uid();
     ix->device = device;
     ix->cfg = *cfg;
     ix->n = n;
@@ -2450,6 +2478,8 @@ void idist_search_ctx_free(idist_search_ctx* c) {
     if (c->h_io) hipHostFree(c->h_io);
     for (hipEvent_t e : c->al_ev)
         if (e) hipEventDestroy(e);
+    for (hipEvent_t e : c->at_ev)
+        if (e) hipEventDestroy(e);
     for (uint32_t i = 0; i < IDIST_EVENT_RING; i++) {
         if (c->ev0[i]) hipEventDestroy(c->ev0[i]);
         if (c->ev1[i]) hipEventDestroy(c->ev1[i]);
@@ -3071,6 +3101,7 @@ idist_status idist_partitioned_new(const idist_index* const* parts, uint32_t n_p
     for (uint32_t i = 0; i < n_parts; i++)
         if (!parts[i]) return fail(IDIST_ERR_INVALID_ARG, "part %u is null", i);
     idist_partitioned* p = new idist_partitioned();
+    p->uid = fresh_uid();
     auto bail = [&](idist_status s) {
         const std::string keep = g_err;
         idist_partitioned_free(p);
@@ -3664,6 +3695,118 @@ idist_status check_sets_args(uint32_t n_sets, const uint32_t* set_of, uint32_t n
     return IDIST_OK;
 }
 
+// ---- attribute filters: the sets of a restricted call made on the device ----
+// Where a restricted call's sets come from: the caller's bitmaps (over the ids of an index, or the global ids of a partitioned
+// one), or an attribute and the call's distinct intervals.  set_of [nq] is never null once a call has resolved it.
+struct SetsSource {
+    const uint32_t* bits = nullptr;                      // HOST bitmaps [n_sets][(n + 31) / 32] ...
+    const idist_attr* attr = nullptr;                    // ... or the values on the device and
+    const uint32_t *lo = nullptr, *hi = nullptr;         //     the distinct intervals, HOST [n_sets]
+    uint32_t n_sets = 0;
+    const uint32_t* set_of = nullptr;
+};
+
+// the conditions of an attribute call: one for the batch or one per query, as a radius (nq == 0 is no error)
+idist_status check_cond_args(const uint32_t* lo, const uint32_t* hi, uint32_t n_cond, uint32_t nq) {
+    if (nq == 0) return IDIST_OK;
+    if (n_cond != 1 && n_cond != nq) return fail(IDIST_ERR_INVALID_ARG, "n_cond %u: 1 (one condition for the batch) or nq = %u", n_cond, nq);
+    if (!lo || !hi) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    return IDIST_OK;
+}
+
+// D, the distinct (lo, hi) pairs of a call in ascending order, and every query's index into it.  nq entries: host work.
+struct AttrConds {
+    std::vector<uint32_t> lo, hi, set_of;
+    SetsSource source(const idist_attr* attr) const {
+        SetsSource s;
+        s.attr = attr; s.lo = lo.data(); s.hi = hi.data(); s.n_sets = (uint32_t)lo.size(); s.set_of = set_of.data();
+        return s;
+    }
+};
+void attr_group(const uint32_t* lo, const uint32_t* hi, uint32_t n_cond, uint32_t nq, AttrConds* g) {
+    g->set_of.assign(nq, 0u);
+    std::vector<std::pair<uint64_t, uint32_t>> keyed(n_cond);
+    for (uint32_t i = 0; i < n_cond; i++) keyed[i] = {(uint64_t)lo[i] << 32 | hi[i], i};
+    std::sort(keyed.begin(), keyed.end());
+    for (uint32_t i = 0; i < n_cond; i++) {
+        if (i == 0 || keyed[i].first != keyed[i - 1].first) {
+            g->lo.push_back((uint32_t)(keyed[i].first >> 32));
+            g->hi.push_back((uint32_t)keyed[i].first);
+        }
+        if (n_cond == nq) g->set_of[keyed[i].second] = (uint32_t)g->lo.size() - 1u;
+    }
+}
+
+// an attribute belongs to ONE handle, as a context does: the index (partitioned == false) or the partitioned index with this uid
+idist_status check_attr(const idist_attr* a, uint64_t uid, bool partitioned) {
+    if (!a) return fail(IDIST_ERR_INVALID_ARG, "attr is null");
+    if (a->partitioned != partitioned)
+        return fail(IDIST_ERR_INVALID_ARG, partitioned ? "attr was made for an index, not for a partitioned index (idist_partitioned_attr_new)"
+                                                       : "attr was made for a partitioned index, not for an index (idist_attr_new)");
+    if (a->owner_uid != uid) return fail(IDIST_ERR_INVALID_ARG, partitioned ? "attr does not belong to this partitioned index" : "attr does not belong to idx");
+    return IDIST_OK;
+}
+
+// attr_bitmaps_kernel on `stream` (its device is current): n >= 1, n_sets >= 1.  Work item = (tile of 4096 points, chunk of sets): one
+// chunk — v read once — as soon as the tiles alone give every CU eight waves; never chunks of fewer than eight sets.
+idist_status launch_attr_bitmaps(const uint32_t* d_v, uint32_t n, const uint32_t* d_lo, const uint32_t* d_hi, uint32_t n_sets, uint32_t* d_out,
+                                 int n_cu, hipStream_t stream) {
+    const uint64_t tiles = ((uint64_t)n + kAttrTile - 1u) / kAttrTile, want = (uint64_t)std::max(n_cu, 1) * 8u;
+    const uint64_t chunks_wanted = std::max<uint64_t>((want + tiles - 1u) / tiles, 1u);
+    const uint32_t set_chunk = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n_sets + chunks_wanted - 1u) / chunks_wanted, 8u), n_sets);
+    const uint64_t items = tiles * ((n_sets + set_chunk - 1u) / set_chunk);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(items, (uint64_t)std::max(n_cu, 1) * 32u);
+    IDIST_LAUNCH(attr_bitmaps_kernel, grid, 64, 0, stream, d_v, n, d_lo, d_hi, n_sets, set_chunk, d_out);
+    HIPCHK(hipGetLastError());
+    return IDIST_OK;
+}
+
+// The bitmaps of an attribute call into ctx->al_bits, on the context's stream (its device is current): the distinct intervals go
+// up, the kernel runs between the context's own pair of events.  d_values [n], n >= 1.  Staging: n_sets * ((n + 31) / 32) * 4 bytes.
+idist_status attr_stage_bitmaps(idist_search_ctx* ctx, const uint32_t* d_values, uint32_t n, const SetsSource& src) {
+    const size_t words = ((size_t)n + 31u) / 32u;
+    hipStream_t stream = ctx->stream;
+    CHK(ctx->al_bits.grow((size_t)src.n_sets * words * 4));
+    CHK(ctx->at_lo.grow((size_t)src.n_sets * 4));
+    CHK(ctx->at_hi.grow((size_t)src.n_sets * 4));
+    HIPCHK(hipMemcpyAsync(ctx->at_lo.p, src.lo, (size_t)src.n_sets * 4, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipMemcpyAsync(ctx->at_hi.p, src.hi, (size_t)src.n_sets * 4, hipMemcpyHostToDevice, stream));
+    ctx->at_timed = false;
+    if (ctx->knobs.events) {
+        for (hipEvent_t& e : ctx->at_ev)
+            if (!e) HIPCHK(hipEventCreate(&e));
+        HIPCHK(hipEventRecord(ctx->at_ev[0], stream));
+    }
+    CHK(launch_attr_bitmaps(d_values, n, ctx->at_lo, ctx->at_hi, src.n_sets, ctx->al_bits, ctx->n_cu, stream));
+    if (ctx->knobs.events) {
+        HIPCHK(hipEventRecord(ctx->at_ev[1], stream));
+        ctx->at_timed = true;                            // (both recorded: attr_time_resolve may ask for their distance)
+    }
+    return IDIST_OK;
+}
+// ... and its time, once the call has synchronised the stream
+idist_status attr_time_resolve(idist_search_ctx* ctx) {
+    if (!ctx->at_timed) return IDIST_OK;
+    ctx->at_timed = false;
+    HIPCHK(hipEventElapsedTime(&ctx->at_ms, ctx->at_ev[0], ctx->at_ev[1]));
+    return IDIST_OK;
+}
+
+// The sets of a several-sets call on ONE index, on the context's stream: al_bits — the caller's bitmaps as they are (padding bits are
+// masked where they are read), or the attribute's, made here — and al_setof.  n >= 1.
+idist_status stage_sets(idist_search_ctx* ctx, uint32_t n, uint32_t nq, const SetsSource& src) {
+    const size_t bb = (size_t)src.n_sets * (((size_t)n + 31u) / 32u) * 4;
+    CHK(ctx->al_setof.grow((size_t)nq * 4));
+    if (src.attr) {
+        CHK(attr_stage_bitmaps(ctx, src.attr->parts[0].v, n, src));
+    } else {
+        CHK(ctx->al_bits.grow(bb));
+        HIPCHK(hipMemcpyAsync(ctx->al_bits.p, src.bits, bb, hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIPCHK(hipMemcpyAsync(ctx->al_setof.p, src.set_of, (size_t)nq * 4, hipMemcpyHostToDevice, ctx->stream));
+    return IDIST_OK;
+}
+
 // step 1, nothing to find: every output array the caller hands in (null: it has none, or fills it its own way)
 void fill_nothing_found(uint32_t nq, uint32_t k, uint32_t* out_pid, float* out_dist, uint32_t* out_count, uint32_t* out_rung,
                         uint32_t* out_counters) {
@@ -4046,41 +4189,123 @@ static const uint32_t* set_of_or_identity(const uint32_t* set_of, uint32_t nq, s
     return keep->data();
 }
 
+// The several-sets call behind its argument checks, for sets from either source: stage, the call on the device, report, download.
+// nq > 0; the trivial cases (n == 0, ef_search == 0) are answered here.
+static idist_status allowed_sets_call(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq, const SetsSource& src,
+                                      uint32_t k, int32_t max_rungs, uint32_t* out_pid, float* out_dist, uint32_t* out_count,
+                                      uint32_t* out_rung, uint32_t* out_counters) {
+    const uint32_t n = idx->n;
+    if (n == 0 || idx->cfg.ef_search == 0) {                                 // step 1: nothing to find, whatever the sets
+        fill_nothing_found(nq, k, out_pid, out_dist, out_count, out_rung, out_counters);
+        return IDIST_OK;
+    }
+    HIPCHK(hipSetDevice(idx->device));
+    hipStream_t stream = ctx->stream;
+    const MetricPasses metric(idx);
+    AllowedOut o{};
+    CHK(allowed_out_in_ctx(ctx, nq, k, out_counters != nullptr, &o));
+    CHK(stage_sets(ctx, n, nq, src));
+    const float* d_qk = nullptr;
+    CHK(ladder_upload_queries(idx, ctx, metric, queries, nq, &d_qk));
+    CHK(allowed_sets_device(idx, ctx, d_qk, nq, ctx->al_bits, src.n_sets, ctx->al_setof, src.set_of, k, max_rungs, o));
+    CHK(metric.report(ctx->al_odist.as<float>(), ctx->d_sq, nq, k, stream));
+    CHK(allowed_download(ctx, nq, k, out_pid, out_dist, out_count, out_rung, out_counters));
+    HIPCHK(hipStreamSynchronize(stream));
+    CHK(attr_time_resolve(ctx));
+    return ladder_times_resolve(ctx);
+}
+
 idist_status idist_search_batch_allowed_sets(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
                                              const uint32_t* allow_bits, uint32_t n_sets, const uint32_t* set_of, uint32_t k,
                                              int32_t max_rungs, uint32_t* out_pid, float* out_dist, uint32_t* out_count,
                                              uint32_t* out_rung, uint32_t* out_counters) {
     CHK(check_ctx(idx, ctx));
-    const uint32_t n = idx->n, ef0 = idx->cfg.ef_search;
-    CHK(check_ladder_args(max_rungs, k, ef0));
+    CHK(check_ladder_args(max_rungs, k, idx->cfg.ef_search));
     CHK(check_sets_args(n_sets, set_of, nq));
     if (nq == 0) return IDIST_OK;
-    if (!queries || !out_pid || !out_dist || !out_count || (n && !allow_bits)) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
-    if (n == 0 || ef0 == 0) {                                                // step 1: nothing to find, whatever the sets
-        fill_nothing_found(nq, k, out_pid, out_dist, out_count, out_rung, out_counters);
-        return IDIST_OK;
-    }
-    // upload, the call on the device, report, download
-    const uint32_t words = (n + 31u) / 32u;
-    HIPCHK(hipSetDevice(idx->device));
-    hipStream_t stream = ctx->stream;
-    const MetricPasses metric(idx);
-    const size_t bb = (size_t)n_sets * words * 4;
-    CHK(ctx->al_bits.grow(bb));
-    CHK(ctx->al_setof.grow((size_t)nq * 4));
-    AllowedOut o{};
-    CHK(allowed_out_in_ctx(ctx, nq, k, out_counters != nullptr, &o));
+    if (!queries || !out_pid || !out_dist || !out_count || (idx->n && !allow_bits)) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
     std::vector<uint32_t> identity;
-    set_of = set_of_or_identity(set_of, nq, &identity);
-    HIPCHK(hipMemcpyAsync(ctx->al_bits.p, allow_bits, bb, hipMemcpyHostToDevice, stream));     // as the caller has them: padding bits are masked where they are read
-    HIPCHK(hipMemcpyAsync(ctx->al_setof.p, set_of, (size_t)nq * 4, hipMemcpyHostToDevice, stream));
-    const float* d_qk = nullptr;
-    CHK(ladder_upload_queries(idx, ctx, metric, queries, nq, &d_qk));
-    CHK(allowed_sets_device(idx, ctx, d_qk, nq, ctx->al_bits, n_sets, ctx->al_setof, set_of, k, max_rungs, o));
-    CHK(metric.report(ctx->al_odist.as<float>(), ctx->d_sq, nq, k, stream));
-    CHK(allowed_download(ctx, nq, k, out_pid, out_dist, out_count, out_rung, out_counters));
-    HIPCHK(hipStreamSynchronize(stream));
-    return ladder_times_resolve(ctx);
+    SetsSource src;
+    src.bits = allow_bits; src.n_sets = n_sets; src.set_of = set_of_or_identity(set_of, nq, &identity);
+    return allowed_sets_call(idx, ctx, queries, nq, src, k, max_rungs, out_pid, out_dist, out_count, out_rung, out_counters);
+}
+
+// ---- the attribute on the device and the calls that read it ----
+idist_status idist_attr_new(const idist_index* idx, const uint32_t* values, idist_attr** out) {
+    if (!idx || !out) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    if (idx->n && !values) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    std::unique_ptr<idist_attr> a(new idist_attr());
+    a->owner_uid = idx->uid;
+    a->parts.resize(1);
+    idist_attr::Slice& sl = a->parts[0];
+    sl.n = idx->n;
+    sl.device = idx->device;
+    if (sl.n) {
+        HIPCHK(hipSetDevice(sl.device));
+        CHK(sl.v.grow((size_t)sl.n * 4));
+        HIPCHK(hipMemcpy(sl.v.p, values, (size_t)sl.n * 4, hipMemcpyHostToDevice));
+    }
+    *out = a.release();
+    return IDIST_OK;
+}
+
+idist_status idist_partitioned_attr_new(const idist_partitioned* p, const uint32_t* values, idist_attr** out) {
+    if (!p || !out) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    *out = nullptr;
+    CHK(partitioned_check(const_cast<idist_partitioned*>(p), nullptr));
+    const size_t P = p->parts.size();
+    if (p->base[P] && !values) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    std::unique_ptr<idist_attr> a(new idist_attr());
+    a->owner_uid = p->uid;
+    a->partitioned = true;
+    a->parts.resize(P);
+    for (size_t i = 0; i < P; i++) {
+        idist_attr::Slice& sl = a->parts[i];
+        sl.n = p->parts[i].idx->n;
+        sl.device = part_device(p, i);
+        if (!sl.n) continue;
+        HIPCHK(hipSetDevice(sl.device));
+        CHK(sl.v.grow((size_t)sl.n * 4));
+        HIPCHK(hipMemcpy(sl.v.p, values + p->base[i], (size_t)sl.n * 4, hipMemcpyHostToDevice));
+    }
+    *out = a.release();
+    return IDIST_OK;
+}
+
+void idist_attr_free(idist_attr* a) { delete a; }
+
+idist_status idist_attr_bitmaps_device(const void* d_values, uint32_t n, const void* d_lo, const void* d_hi, uint32_t n_sets, void* d_out,
+                                       int32_t device, void* hip_stream) {
+    if (n == 0 || n_sets == 0) return IDIST_OK;
+    if (!d_values || !d_lo || !d_hi || !d_out) return fail(IDIST_ERR_INVALID_ARG, "null device pointer");
+    CHK(check_device(device));
+    HIPCHK(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    return launch_attr_bitmaps((const uint32_t*)d_values, n, (const uint32_t*)d_lo, (const uint32_t*)d_hi, n_sets, (uint32_t*)d_out,
+                               prop.multiProcessorCount, (hipStream_t)hip_stream);
+}
+
+idist_status idist_search_batch_attr(const idist_index* idx, idist_search_ctx* ctx, const idist_attr* attr, const float* queries, uint32_t nq,
+                                     const uint32_t* lo, const uint32_t* hi, uint32_t n_cond, uint32_t k, int32_t max_rungs,
+                                     uint32_t* out_pid, float* out_dist, uint32_t* out_count, uint32_t* out_rung, uint32_t* out_counters) {
+    CHK(check_ctx(idx, ctx));
+    CHK(check_attr(attr, idx->uid, false));
+    ctx->at_ms = 0.0f;
+    CHK(check_ladder_args(max_rungs, k, idx->cfg.ef_search));
+    CHK(check_cond_args(lo, hi, n_cond, nq));
+    if (nq == 0) return IDIST_OK;
+    if (!queries || !out_pid || !out_dist || !out_count) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    AttrConds g;
+    attr_group(lo, hi, n_cond, nq, &g);
+    return allowed_sets_call(idx, ctx, queries, nq, g.source(attr), k, max_rungs, out_pid, out_dist, out_count, out_rung, out_counters);
+}
+
+idist_status idist_search_ctx_attr_bitmap_ms(idist_search_ctx* ctx, float* ms) {
+    if (!ctx || !ms) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    *ms = ctx->at_ms;
+    return IDIST_OK;
 }
 
 idist_status idist_allowed_slice_device(const void* d_bits, uint32_t n_sets, uint32_t pitch_words, uint64_t bit_offset, uint32_t n_out,
@@ -4103,43 +4328,35 @@ idist_status idist_allowed_slice_device(const void* d_bits, uint32_t n_sets, uin
     return IDIST_OK;
 }
 
-idist_status idist_partitioned_search_batch_allowed_sets(idist_partitioned* p, const float* queries, uint32_t nq,
-                                                         const uint32_t* allow_bits, uint32_t n_sets, const uint32_t* set_of, uint32_t k,
-                                                         int32_t max_rungs, uint32_t* out_pid, float* out_dist, uint32_t* out_count,
-                                                         uint32_t* out_rung, uint32_t* out_counters) {
-    if (!p) return fail(IDIST_ERR_INVALID_ARG, "null argument");
-    uint32_t ef = 0;
-    CHK(partitioned_check(p, &ef));
+// The sets of a restricted call over the parts (the sets name GLOBAL ids), every part's in its context's al_bits, its device's
+// Dev::d_setof filled.  N > 0, nq > 0.
+//   1. the set of every query, once per distinct device that has something to search;
+//   2. the caller's bitmaps: the words [base / 32, ceil((base + n_p) / 32)) of every set in ONE strided copy out of the caller's
+//      buffer (which is only read), then the slice kernel shifts them by base % 32 on the part's stream — the part's own
+//      [n_sets][(n_p + 31) / 32], the bits behind n_p cleared.  p->al_slice_ms: the host time of it;
+//      an attribute: every part makes its bitmaps from ITS slice of the values with attr_bitmaps_kernel on its own stream — no
+//      upload of n bits, no slice kernel, and by construction the slice of the global bitmap.  p->al_slice_ms comes from the
+//      parts' events once their streams have been synchronised (partitioned_attr_times).
+static idist_status partitioned_stage_sets(idist_partitioned* p, uint32_t nq, const SetsSource& src) {
     const size_t P = p->parts.size();
-    const uint32_t N = p->base[P];
-    CHK(check_ladder_args(max_rungs, k, ef));
-    CHK(check_sets_args(n_sets, set_of, nq));
-    if (nq == 0) return IDIST_OK;
-    if (!queries || !out_pid || !out_dist || !out_count || (N && !allow_bits)) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
-    if (out_rung) std::fill(out_rung, out_rung + (size_t)nq * P, (uint32_t)IDIST_RUNG_NONE);   // (empty parts keep it)
-    p->al_slice_ms = 0.0f;
-    if (N == 0 || ef == 0) {                                                 // nothing to find, whatever the sets
-        fill_nothing_found(nq, k, out_pid, out_dist, out_count, nullptr, out_counters);     // (out_rung [nq][P] is filled above)
-        return IDIST_OK;
-    }
-    const bool counters = out_counters != nullptr;
-    const size_t W = ((size_t)N + 31u) / 32u, row = (size_t)nq * k;
-    std::vector<uint32_t> identity;
-    set_of = set_of_or_identity(set_of, nq, &identity);
-    HIPCHK(hipSetDevice(p->merge_device));
-    CHK(partitioned_reserve(p, nq, k, k));
-    CHK(p->s_rung.grow(P * nq * 4));
-    CHK(partitioned_prepare_report(p, queries, nq));
-    // 1. the queries and the set of every query, once per distinct device that has something to search
-    CHK(partitioned_upload_queries(p, queries, nq));
+    const size_t W = ((size_t)p->base[P] + 31u) / 32u;
+    const uint32_t n_sets = src.n_sets;
     CHK(for_each_used_device(p, [&](idist_partitioned::Dev& dv) -> idist_status {
         CHK(dv.d_setof.grow((size_t)nq * 4));
-        HIPCHK(hipMemcpy(dv.d_setof, set_of, (size_t)nq * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(dv.d_setof, src.set_of, (size_t)nq * 4, hipMemcpyHostToDevice));
         return IDIST_OK;
     }));
-    // 2. every part's bitmaps: the words [base / 32, ceil((base + n_p) / 32)) of every set in ONE strided copy out of the caller's
-    //    buffer (which is only read), then the slice kernel shifts them by base % 32 on the part's stream — the part's own
-    //    [n_sets][(n_p + 31) / 32], the bits behind n_p cleared
+    if (src.attr) {
+        for (size_t i = 0; i < P; i++) {
+            idist_partitioned::Part& pt = p->parts[i];
+            if (!pt.ctx) continue;
+            HIPCHK(hipSetDevice(p->devs[pt.dev_slot].device));
+            pt.ctx->at_ms = 0.0f;
+            CHK(attr_stage_bitmaps(pt.ctx, src.attr->parts[i].v, pt.idx->n, src));
+        }
+        return IDIST_OK;
+    }
+    const uint32_t* allow_bits = src.bits;
     const auto t0 = std::chrono::steady_clock::now();
     for (size_t i = 0; i < P; i++) {
         idist_partitioned::Part& pt = p->parts[i];
@@ -4165,6 +4382,47 @@ idist_status idist_partitioned_search_batch_allowed_sets(idist_partitioned* p, c
         HIPCHK(hipStreamSynchronize(pt.ctx->stream));
     }
     p->al_slice_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return IDIST_OK;
+}
+// an attribute call, after the parts' streams have been synchronised: the parts' bitmap kernels, summed
+static void partitioned_attr_times(idist_partitioned* p, const SetsSource& src) {
+    if (!src.attr) return;
+    p->al_slice_ms = 0.0f;
+    for (auto& pt : p->parts)
+        if (pt.ctx) p->al_slice_ms += pt.ctx->at_ms;
+}
+
+// an attribute of a partitioned call: made for p, and the parts are still the sizes its slices were cut for (partitioned_check ran)
+static idist_status check_partitioned_attr(const idist_partitioned* p, const idist_attr* attr) {
+    CHK(check_attr(attr, p->uid, true));
+    for (size_t i = 0; i < p->parts.size(); i++)
+        if (attr->parts.size() != p->parts.size() || attr->parts[i].n != p->parts[i].idx->n)
+            return fail(IDIST_ERR_INVALID_ARG, "attr does not belong to this partitioned index");
+    return IDIST_OK;
+}
+
+// The restricted search over the parts behind its argument checks, for sets from either source.  nq > 0.
+static idist_status partitioned_allowed_sets_call(idist_partitioned* p, uint32_t ef, const float* queries, uint32_t nq, const SetsSource& src,
+                                                  uint32_t k, int32_t max_rungs, uint32_t* out_pid, float* out_dist, uint32_t* out_count,
+                                                  uint32_t* out_rung, uint32_t* out_counters) {
+    const size_t P = p->parts.size();
+    const uint32_t N = p->base[P], n_sets = src.n_sets;
+    const uint32_t* set_of = src.set_of;
+    if (out_rung) std::fill(out_rung, out_rung + (size_t)nq * P, (uint32_t)IDIST_RUNG_NONE);   // (empty parts keep it)
+    p->al_slice_ms = 0.0f;
+    if (N == 0 || ef == 0) {                                                 // nothing to find, whatever the sets
+        fill_nothing_found(nq, k, out_pid, out_dist, out_count, nullptr, out_counters);     // (out_rung [nq][P] is filled above)
+        return IDIST_OK;
+    }
+    const bool counters = out_counters != nullptr;
+    const size_t row = (size_t)nq * k;
+    HIPCHK(hipSetDevice(p->merge_device));
+    CHK(partitioned_reserve(p, nq, k, k));
+    CHK(p->s_rung.grow(P * nq * 4));
+    CHK(partitioned_prepare_report(p, queries, nq));
+    // 1. the queries and the set of every query, once per distinct device that has something to search; 2. every part's bitmaps
+    CHK(partitioned_upload_queries(p, queries, nq));
+    CHK(partitioned_stage_sets(p, nq, src));
     // 3. the ladders block on the host, one synchronisation per rung: one thread per non-empty part, each with the part's own context
     //    and stream.  On the merge device straight into the part's slice of the staging memory, elsewhere into memory of the part's
     //    device followed by one peer copy per array (partitioned_fan_out, partitioned_send).
@@ -4185,8 +4443,10 @@ idist_status idist_partitioned_search_batch_allowed_sets(idist_partitioned* p, c
         CHK(allowed_sets_device(pt.idx, ctx, dv.d_q, nq, ctx->al_bits, n_sets, dv.d_setof, set_of, k, max_rungs, o));
         if (dev != p->merge_device) CHK(partitioned_send(p, i, nq, k, o.pid, o.dist, o.count, o.rung, counters ? o.counters : nullptr));
         HIPCHK(hipStreamSynchronize(ctx->stream));
+        CHK(attr_time_resolve(ctx));
         return ladder_times_resolve(ctx);
     }));
+    partitioned_attr_times(p, src);
     // 4. the union: empty parts hand in lists of length 0; the parts' rungs come back [P][nq] and are transposed on the host
     HIPCHK(hipSetDevice(p->merge_device));
     CHK(partitioned_zero_empty_parts(p, nq, counters));
@@ -4198,6 +4458,40 @@ idist_status idist_partitioned_search_batch_allowed_sets(idist_partitioned* p, c
     CHK(partitioned_merge(p, nq, k, k, counters, out_pid, out_dist, out_count, out_counters));
     partitioned_transpose_rungs(p, rungs, nq, out_rung);
     return IDIST_OK;
+}
+
+idist_status idist_partitioned_search_batch_allowed_sets(idist_partitioned* p, const float* queries, uint32_t nq,
+                                                         const uint32_t* allow_bits, uint32_t n_sets, const uint32_t* set_of, uint32_t k,
+                                                         int32_t max_rungs, uint32_t* out_pid, float* out_dist, uint32_t* out_count,
+                                                         uint32_t* out_rung, uint32_t* out_counters) {
+    if (!p) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    uint32_t ef = 0;
+    CHK(partitioned_check(p, &ef));
+    CHK(check_ladder_args(max_rungs, k, ef));
+    CHK(check_sets_args(n_sets, set_of, nq));
+    if (nq == 0) return IDIST_OK;
+    if (!queries || !out_pid || !out_dist || !out_count || (p->base[p->parts.size()] && !allow_bits)) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    std::vector<uint32_t> identity;
+    SetsSource src;
+    src.bits = allow_bits; src.n_sets = n_sets; src.set_of = set_of_or_identity(set_of, nq, &identity);
+    return partitioned_allowed_sets_call(p, ef, queries, nq, src, k, max_rungs, out_pid, out_dist, out_count, out_rung, out_counters);
+}
+
+idist_status idist_partitioned_search_batch_attr(idist_partitioned* p, const idist_attr* attr, const float* queries, uint32_t nq,
+                                                 const uint32_t* lo, const uint32_t* hi, uint32_t n_cond, uint32_t k, int32_t max_rungs,
+                                                 uint32_t* out_pid, float* out_dist, uint32_t* out_count, uint32_t* out_rung,
+                                                 uint32_t* out_counters) {
+    if (!p) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    uint32_t ef = 0;
+    CHK(partitioned_check(p, &ef));
+    CHK(check_partitioned_attr(p, attr));
+    CHK(check_ladder_args(max_rungs, k, ef));
+    CHK(check_cond_args(lo, hi, n_cond, nq));
+    if (nq == 0) return IDIST_OK;
+    if (!queries || !out_pid || !out_dist || !out_count) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    AttrConds g;
+    attr_group(lo, hi, n_cond, nq, &g);
+    return partitioned_allowed_sets_call(p, ef, queries, nq, g.source(attr), k, max_rungs, out_pid, out_dist, out_count, out_rung, out_counters);
 }
 
 idist_status idist_partitioned_last_allowed_slice_ms(idist_partitioned* p, float* ms) {
@@ -4346,16 +4640,11 @@ idist_status idist_search_batch_range(const idist_index* idx, idist_search_ctx* 
 }
 
 // ---- restricted range search: every point of a query's own allowed set within its radius ----
-idist_status idist_search_batch_range_allowed_sets(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
-                                                   const float* radius, uint32_t n_radius, const uint32_t* allow_bits, uint32_t n_sets,
-                                                   const uint32_t* set_of, int32_t max_rungs, uint64_t max_total, uint64_t* out_lims,
-                                                   uint32_t* out_rung, uint32_t* out_counters) {
-    CHK(check_ctx(idx, ctx));
-    ctx->rg_valid = false;                                                   // whatever happens next, the previous results are gone
-    CHK(check_range_args(queries, nq, radius, n_radius, max_rungs, out_lims));
-    CHK(check_sets_args(n_sets, set_of, nq));
+// The call behind its argument checks, for sets from either source.  The previous results are gone already.
+static idist_status range_allowed_sets_call(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq, const float* radius,
+                                            uint32_t n_radius, const SetsSource& src, int32_t max_rungs, uint64_t max_total, uint64_t* out_lims,
+                                            uint32_t* out_rung, uint32_t* out_counters) {
     const uint32_t n = idx->n;
-    if (nq && n && !allow_bits) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
     range_begin(idx, ctx, nq);
     if (nq == 0 || n == 0 || idx->cfg.ef_search == 0) {                      // step 1: nothing to find, whatever the sets
         std::fill(out_lims, out_lims + nq + 1, (uint64_t)0);
@@ -4364,23 +4653,44 @@ idist_status idist_search_batch_range_allowed_sets(const idist_index* idx, idist
         return IDIST_OK;
     }
     HIPCHK(hipSetDevice(idx->device));
-    hipStream_t stream = ctx->stream;
-    // the bitmaps and set_of as idist_search_batch_allowed_sets stages them: as the caller has them, padding bits are masked where
-    // they are read
-    const uint32_t words = (n + 31u) / 32u;
-    const size_t bb = (size_t)n_sets * words * 4;
-    CHK(ctx->al_bits.grow(bb));
-    CHK(ctx->al_setof.grow((size_t)nq * 4));
-    std::vector<uint32_t> identity;
-    set_of = set_of_or_identity(set_of, nq, &identity);
-    HIPCHK(hipMemcpyAsync(ctx->al_bits.p, allow_bits, bb, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(ctx->al_setof.p, set_of, (size_t)nq * 4, hipMemcpyHostToDevice, stream));
+    // the bitmaps and set_of as idist_search_batch_allowed_sets stages them
+    CHK(stage_sets(ctx, n, nq, src));
     const float* d_qk = nullptr;
     CHK(ladder_upload_queries(idx, ctx, MetricPasses(idx), queries, nq, &d_qk));
-    const RangeSets sets{ctx->al_bits, ctx->al_setof, n_sets, words};
+    const RangeSets sets{ctx->al_bits, ctx->al_setof, src.n_sets, (n + 31u) / 32u};
     uint64_t total = 0;
     CHK(range_search_device(idx, ctx, d_qk, ctx->d_sq, nq, radius, n_radius, max_rungs, max_total, out_counters != nullptr, &total, &sets));
-    return range_finish(ctx, nq, total, out_lims, out_rung, out_counters);
+    CHK(range_finish(ctx, nq, total, out_lims, out_rung, out_counters));
+    return attr_time_resolve(ctx);
+}
+
+idist_status idist_search_batch_range_allowed_sets(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
+                                                   const float* radius, uint32_t n_radius, const uint32_t* allow_bits, uint32_t n_sets,
+                                                   const uint32_t* set_of, int32_t max_rungs, uint64_t max_total, uint64_t* out_lims,
+                                                   uint32_t* out_rung, uint32_t* out_counters) {
+    CHK(check_ctx(idx, ctx));
+    ctx->rg_valid = false;                                                   // whatever happens next, the previous results are gone
+    CHK(check_range_args(queries, nq, radius, n_radius, max_rungs, out_lims));
+    CHK(check_sets_args(n_sets, set_of, nq));
+    if (nq && idx->n && !allow_bits) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    std::vector<uint32_t> identity;
+    SetsSource src;
+    src.bits = allow_bits; src.n_sets = n_sets; src.set_of = set_of_or_identity(set_of, nq, &identity);
+    return range_allowed_sets_call(idx, ctx, queries, nq, radius, n_radius, src, max_rungs, max_total, out_lims, out_rung, out_counters);
+}
+
+idist_status idist_search_batch_range_attr(const idist_index* idx, idist_search_ctx* ctx, const idist_attr* attr, const float* queries, uint32_t nq,
+                                           const float* radius, uint32_t n_radius, const uint32_t* lo, const uint32_t* hi, uint32_t n_cond,
+                                           int32_t max_rungs, uint64_t max_total, uint64_t* out_lims, uint32_t* out_rung, uint32_t* out_counters) {
+    CHK(check_ctx(idx, ctx));
+    ctx->rg_valid = false;                                                   // whatever happens next, the previous results are gone
+    CHK(check_attr(attr, idx->uid, false));
+    ctx->at_ms = 0.0f;
+    CHK(check_range_args(queries, nq, radius, n_radius, max_rungs, out_lims));
+    CHK(check_cond_args(lo, hi, n_cond, nq));
+    AttrConds g;
+    attr_group(lo, hi, nq ? n_cond : 0u, nq, &g);
+    return range_allowed_sets_call(idx, ctx, queries, nq, radius, n_radius, g.source(attr), max_rungs, max_total, out_lims, out_rung, out_counters);
 }
 
 extern "C++" {
@@ -4713,15 +5023,12 @@ idist_status idist_range_merge_device(const void* const* d_keys, const void* con
                               (float*)d_out_dist, prop.multiProcessorCount, stream);
 }
 
-idist_status idist_partitioned_search_batch_range(idist_partitioned* p, const float* queries, uint32_t nq, const float* radius,
-                                                  uint32_t n_radius, int32_t max_rungs, uint64_t max_total, uint64_t* out_lims,
-                                                  uint32_t* out_rung, uint32_t* out_counters) {
-    if (!p) return fail(IDIST_ERR_INVALID_ARG, "null argument");
-    p->rg_valid = false;                                                     // whatever happens next, the previous results are gone
-    p->rg_total = 0;
-    uint32_t ef = 0;
-    CHK(partitioned_check(p, &ef));
-    CHK(check_range_args(queries, nq, radius, n_radius, max_rungs, out_lims));
+// The range search over the parts behind its argument checks (p->rg_valid is false already).  src == nullptr: the plain call, which
+// launches exactly what it always launched.  src: the restricted one — the sets staged per part as the restricted top-k call stages
+// them (partitioned_stage_sets), every part's range_search_device given its own slice of them.
+static idist_status partitioned_range_call(idist_partitioned* p, uint32_t ef, const float* queries, uint32_t nq, const float* radius,
+                                           uint32_t n_radius, const SetsSource* src, int32_t max_rungs, uint64_t max_total, uint64_t* out_lims,
+                                           uint32_t* out_rung, uint32_t* out_counters) {
     const size_t P = p->parts.size();
     const uint32_t N = p->base[P];
     if (out_rung) std::fill(out_rung, out_rung + (size_t)nq * P, (uint32_t)IDIST_RUNG_NONE);   // (empty parts keep it)
@@ -4737,6 +5044,10 @@ idist_status idist_partitioned_search_batch_range(idist_partitioned* p, const fl
     CHK(partitioned_prepare_report(p, queries, nq));
     // 1. the queries (DOT: and their s(q), the term of the parts' limits), once per distinct device that has something to search
     CHK(partitioned_upload_queries(p, queries, nq, true));
+    if (src) {                                                   // ... and the restricted call's sets, every part's slice on its device
+        p->al_slice_ms = 0.0f;
+        CHK(partitioned_stage_sets(p, nq, *src));
+    }
     // 2. the parts' searches block on the host once per rung: one thread per non-empty part, each with the part's own context and
     //    stream (step 3 of idist_partitioned_search_batch_allowed_sets).  Every part gets the caller's bound: its own total can never
     //    legitimately exceed the merged one.  A part on the merge device leaves its keys, offsets and counts where its context holds
@@ -4750,7 +5061,8 @@ idist_status idist_partitioned_search_batch_range(idist_partitioned* p, const fl
         HIPCHK(hipSetDevice(dev));
         range_begin(pt.idx, ctx, nq);
         uint64_t total = 0;
-        CHK(range_search_device(pt.idx, ctx, dv.d_q, dv.d_sq, nq, radius, n_radius, max_rungs, max_total, counters, &total));
+        const RangeSets sets{ctx->al_bits, dv.d_setof, src ? src->n_sets : 0u, (pt.idx->n + 31u) / 32u};
+        CHK(range_search_device(pt.idx, ctx, dv.d_q, dv.d_sq, nq, radius, n_radius, max_rungs, max_total, counters, &total, src ? &sets : nullptr));
         if (out_rung) HIPCHK(hipMemcpyAsync(rungs.data() + i * nq, ctx->al_orung.p, (size_t)nq * 4, hipMemcpyDeviceToHost, ctx->stream));
         if (dev != p->merge_device) {
             HIPCHK(hipSetDevice(p->merge_device));               // (staging on the merge device only grows)
@@ -4765,8 +5077,10 @@ idist_status idist_partitioned_search_batch_range(idist_partitioned* p, const fl
             if (counters) HIPCHK(hipMemcpyPeerAsync(pt.m_ctr, p->merge_device, ctx->al_octr.p, dev, (size_t)nq * 12, ctx->stream));
         }
         HIPCHK(hipStreamSynchronize(ctx->stream));
+        CHK(attr_time_resolve(ctx));
         return ladder_times_resolve(ctx);
     }));
+    if (src) partitioned_attr_times(p, *src);
     // 3. the union, on the merge device: the counts and lims, ONE read-back of the total (it checks max_total and sizes the output),
     //    the merge kernel straight into the flat arrays the fetch hands out
     HIPCHK(hipSetDevice(p->merge_device));
@@ -4813,6 +5127,55 @@ idist_status idist_partitioned_search_batch_range(idist_partitioned* p, const fl
     p->rg_total = total;
     p->rg_valid = true;
     return IDIST_OK;
+}
+
+idist_status idist_partitioned_search_batch_range(idist_partitioned* p, const float* queries, uint32_t nq, const float* radius,
+                                                  uint32_t n_radius, int32_t max_rungs, uint64_t max_total, uint64_t* out_lims,
+                                                  uint32_t* out_rung, uint32_t* out_counters) {
+    if (!p) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    p->rg_valid = false;                                                     // whatever happens next, the previous results are gone
+    p->rg_total = 0;
+    uint32_t ef = 0;
+    CHK(partitioned_check(p, &ef));
+    CHK(check_range_args(queries, nq, radius, n_radius, max_rungs, out_lims));
+    return partitioned_range_call(p, ef, queries, nq, radius, n_radius, nullptr, max_rungs, max_total, out_lims, out_rung, out_counters);
+}
+
+// ---- restricted range search over the parts: the missing cell ----
+idist_status idist_partitioned_search_batch_range_allowed_sets(idist_partitioned* p, const float* queries, uint32_t nq, const float* radius,
+                                                               uint32_t n_radius, const uint32_t* allow_bits, uint32_t n_sets,
+                                                               const uint32_t* set_of, int32_t max_rungs, uint64_t max_total,
+                                                               uint64_t* out_lims, uint32_t* out_rung, uint32_t* out_counters) {
+    if (!p) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    p->rg_valid = false;                                                     // whatever happens next, the previous results are gone
+    p->rg_total = 0;
+    uint32_t ef = 0;
+    CHK(partitioned_check(p, &ef));
+    CHK(check_range_args(queries, nq, radius, n_radius, max_rungs, out_lims));
+    CHK(check_sets_args(n_sets, set_of, nq));
+    if (nq && p->base[p->parts.size()] && !allow_bits) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    std::vector<uint32_t> identity;
+    SetsSource src;
+    src.bits = allow_bits; src.n_sets = n_sets; src.set_of = set_of_or_identity(set_of, nq, &identity);
+    return partitioned_range_call(p, ef, queries, nq, radius, n_radius, &src, max_rungs, max_total, out_lims, out_rung, out_counters);
+}
+
+idist_status idist_partitioned_search_batch_range_attr(idist_partitioned* p, const idist_attr* attr, const float* queries, uint32_t nq,
+                                                       const float* radius, uint32_t n_radius, const uint32_t* lo, const uint32_t* hi,
+                                                       uint32_t n_cond, int32_t max_rungs, uint64_t max_total, uint64_t* out_lims,
+                                                       uint32_t* out_rung, uint32_t* out_counters) {
+    if (!p) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    p->rg_valid = false;                                                     // whatever happens next, the previous results are gone
+    p->rg_total = 0;
+    uint32_t ef = 0;
+    CHK(partitioned_check(p, &ef));
+    CHK(check_partitioned_attr(p, attr));
+    CHK(check_range_args(queries, nq, radius, n_radius, max_rungs, out_lims));
+    CHK(check_cond_args(lo, hi, n_cond, nq));
+    AttrConds g;
+    attr_group(lo, hi, nq ? n_cond : 0u, nq, &g);
+    const SetsSource src = g.source(attr);
+    return partitioned_range_call(p, ef, queries, nq, radius, n_radius, &src, max_rungs, max_total, out_lims, out_rung, out_counters);
 }
 
 idist_status idist_partitioned_range_fetch(idist_partitioned* p, uint32_t* out_pid, float* out_dist) {

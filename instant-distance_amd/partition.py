@@ -20,7 +20,8 @@ import numpy as np
 
 from . import _capi
 from ._capi import INVALID, METRIC_DOT, RUNG_NONE
-from .api import AllowedResult, BatchResult, Builder, Hnsw, Item, RangeResult, _as_points, allowed_bitmap, allowed_bitmaps
+from .api import (AllowedResult, Attr, BatchResult, Builder, Hnsw, Item, RangeResult, _as_points, _attr_values, _conditions, _set_of, allowed_bitmap,
+                  allowed_bitmaps)
 from .dist import shard_range
 
 
@@ -223,7 +224,8 @@ class PartitionedHnsw:
         return [Item(float(r.distance[0, i]), int(r.pid[0, i]), self[int(r.pid[0, i])]) for i in range(int(r.count[0]))]
 
     def last_allowed_slice_ms(self) -> float:
-        """Host time the last restricted search spent on the bitmaps (the parts' strided uploads + slice kernels), milliseconds."""
+        """Host time the last restricted search spent on the bitmaps (the parts' strided uploads + slice kernels), milliseconds;
+        after `search_where` / `search_range_where`: the HIP-event time of the parts' bitmap kernels, summed."""
         ms = C.c_float(0.0)
         _lib().check(_lib().idist_partitioned_last_allowed_slice_ms(self._h, C.byref(ms)))
         return float(ms.value)
@@ -255,6 +257,105 @@ class PartitionedHnsw:
         dist = np.zeros(total, dtype=np.float32)
         L.check(L.idist_partitioned_range_fetch(self._h, _capi.u32p(pid), _capi.f32p(dist)))
         return RangeResult(lims, pid, dist, rung, ctr)
+
+    def _range_outputs(self, queries, radius, counters: bool):
+        q = _as_points(queries)
+        info = self.info()
+        if q.shape[0] and len(self) and q.shape[1] != info.dim:
+            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
+        nq = q.shape[0]
+        rad = np.ascontiguousarray(np.asarray(radius, dtype=np.float32).reshape(-1))
+        if rad.size != 1 and rad.size != nq:
+            raise ValueError(f"`radius` is one float or an array of nq = {nq}, got {rad.size}")
+        lims = np.zeros(nq + 1, dtype=np.uint64)
+        rung = np.full((nq, int(info.n_parts)), RUNG_NONE, dtype=np.uint32)
+        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
+        return q, rad, lims, rung, ctr
+
+    def _range_fetch(self, lims, rung, ctr) -> RangeResult:
+        total = int(lims[-1])
+        pid = np.zeros(total, dtype=np.uint32)
+        dist = np.zeros(total, dtype=np.float32)
+        L = _lib()
+        L.check(L.idist_partitioned_range_fetch(self._h, _capi.u32p(pid), _capi.f32p(dist)))
+        return RangeResult(lims, pid, dist, rung, ctr)
+
+    def search_range_allowed_sets(self, queries, radius, sets, set_of, max_rungs: int = -1, max_total: int = 64 * 2**20,
+                                  counters: bool = False) -> RangeResult:
+        """`search_range` restricted to one allowed set per query (idist_partitioned_search_batch_range_allowed_sets):
+        `Hnsw.search_range_allowed_sets` on every part with the slice of each set that falls into it — every part applies its own
+        end rule, climbs its own ladder and ends in its own exact scan — merged on the GPU by (raw distance bits, global id), the
+        metric's report applied once, after the merge.  `sets` / `set_of` name GLOBAL ids as in `search_allowed_sets`; `radius`,
+        `max_rungs`, `max_total` as in `search_range`, `max_total` bounding the merged restricted total.  `RangeResult.rung` has
+        shape (nq, n_parts): RUNG_NONE for an empty part or an empty slice."""
+        q, rad, lims, rung, ctr = self._range_outputs(queries, radius, counters)
+        nq = q.shape[0]
+        bits = allowed_bitmaps(sets, len(self))
+        so = _set_of(set_of, bits.shape[0], nq)
+        if bits.shape[0] == 0 and nq == 0:
+            return RangeResult(lims, np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.float32), rung, ctr)
+        L = _lib()
+        L.check(L.idist_partitioned_search_batch_range_allowed_sets(self._h, _capi.f32p(q), nq, _capi.f32p(rad), int(rad.size),
+                                                                    _capi.u32p(bits), bits.shape[0],
+                                                                    _capi.u32p(so) if so is not None else None, int(max_rungs),
+                                                                    int(max_total), _capi.u64p(lims), _capi.u32p(rung),
+                                                                    _capi.u32p(ctr) if counters else None))
+        return self._range_fetch(lims, rung, ctr)
+
+    def search_range_allowed(self, queries, radius, allowed, max_rungs: int = -1, max_total: int = 64 * 2**20,
+                             counters: bool = False) -> RangeResult:
+        """`search_range_allowed_sets` with ONE set shared by the batch: `allowed` is a bool mask of length len(self) or an integer
+        array of global ids (`allowed_bitmap`'s rules)."""
+        q = _as_points(queries)
+        bits = allowed_bitmap(allowed, len(self)).reshape(1, -1)
+        return self.search_range_allowed_sets(q, radius, bits, np.zeros(q.shape[0], dtype=np.uint32), max_rungs, max_total, counters)
+
+    # -- attribute filters --
+    def attributes(self, values) -> Attr:
+        """One uint32 per point in GLOBAL-id order (the order of a bool `allowed` mask of this index): every non-empty part's slice
+        goes to that part's own device, once (idist_partitioned_attr_new).  Values outside uint32 raise."""
+        v = _attr_values(values, len(self))
+        h = C.c_void_p()
+        L = _lib()
+        L.check(L.idist_partitioned_attr_new(self._h, _capi.u32p(v), C.byref(h)))
+        return Attr(h, self, v)
+
+    def search_where(self, queries, attr: Attr, lo, hi=None, k: int = 10, max_rungs: int = -1, counters: bool = False) -> AllowedResult:
+        """The k nearest among the points whose attribute lies in the query's interval lo <= attr <= hi
+        (idist_partitioned_search_batch_attr): row q is exactly what `search_allowed_sets` returns for the mask
+        `(attr.values >= lo[q]) & (attr.values <= hi[q])` over the global ids; every part makes its bitmaps from its own slice of the
+        values on its own device.  `lo` / `hi`: one integer for the batch or an array of one per query; hi=None means equality."""
+        q = _as_points(queries)
+        info = self.info()
+        n, P = int(info.n), int(info.n_parts)
+        if q.shape[0] and n and q.shape[1] != info.dim:
+            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
+        nq, k = q.shape[0], int(k)
+        lo_a, hi_a, n_cond = _conditions(lo, hi, nq)
+        kk = max(k, 0)
+        pid = np.full((nq, kk), INVALID, dtype=np.uint32)
+        dist = np.full((nq, kk), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        rung = np.full((nq, P), RUNG_NONE, dtype=np.uint32)
+        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
+        L = _lib()
+        L.check(L.idist_partitioned_search_batch_attr(self._h, attr._h, _capi.f32p(q), nq, _capi.u32p(lo_a), _capi.u32p(hi_a), n_cond, kk,
+                                                      int(max_rungs), _capi.u32p(pid), _capi.f32p(dist), _capi.u32p(cnt), _capi.u32p(rung),
+                                                      _capi.u32p(ctr) if counters else None))
+        return AllowedResult(pid, dist, cnt, rung, ctr)
+
+    def search_range_where(self, queries, radius, attr: Attr, lo, hi=None, max_rungs: int = -1, max_total: int = 64 * 2**20,
+                           counters: bool = False) -> RangeResult:
+        """Every point within `radius` whose attribute lies in the query's interval (idist_partitioned_search_batch_range_attr): row q
+        is exactly what `search_range_allowed_sets` returns for the mask of `search_where`."""
+        q, rad, lims, rung, ctr = self._range_outputs(queries, radius, counters)
+        nq = q.shape[0]
+        lo_a, hi_a, n_cond = _conditions(lo, hi, nq)
+        L = _lib()
+        L.check(L.idist_partitioned_search_batch_range_attr(self._h, attr._h, _capi.f32p(q), nq, _capi.f32p(rad), int(rad.size),
+                                                            _capi.u32p(lo_a), _capi.u32p(hi_a), n_cond, int(max_rungs), int(max_total),
+                                                            _capi.u64p(lims), _capi.u32p(rung), _capi.u32p(ctr) if counters else None))
+        return self._range_fetch(lims, rung, ctr)
 
     def search_one_range(self, point, radius) -> list[Item]:
         """One query: every item within `radius`, nearest first; `Item.pid` is the global id."""
