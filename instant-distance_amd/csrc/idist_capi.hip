@@ -3594,7 +3594,7 @@ static idist_status bruteforce_mfma(const idist_index* idx, const float* queries
         a.mode = 0; a.p_begin = 0; a.p_end = S;
         IDIST_LAUNCH(mfma_dist_kernel, nqt * (S_pad / kTN), 256, smem_g, st, a);
         IDIST_LAUNCH(kth_threshold_kernel, std::min<uint32_t>(qc, 8192), 64, (size_t)(k + 72) * 8, st, d_dense, S_pad, S, qc, k,
-                     k + 72, d_qn, pn_max, d_thr);
+                     k + 72, d_qn, pn_max, stride, d_thr);
         // pass 2: all points, keep those under the threshold
         HIPCHK(hipMemsetAsync(d_cnt, 0, (size_t)qpad * 4, st));
         a.mode = 1; a.p_begin = 0; a.p_end = n;

@@ -13,7 +13,11 @@
 //   4. the candidates (a superset of the true top-k, typically k*n/S + k of them) are re-ranked
 //      with the canonical distance by the same top-k machinery as the scan kernel.
 //
-// The result is bit-identical to bruteforce_kernel's (tests/test_parity.py::test_bruteforce_mfma*).
+// The slack is a worst-case bound in the stored row length K (product_form_eps below; kth_threshold_kernel has the argument), so
+// the candidates hold the true top-k at every K and on any data, and the result is bit-identical to bruteforce_kernel's as long
+// as no candidate list overflows — an overflow is reported, and the caller answers with the scan kernel instead
+// (tests/test_parity.py::test_bruteforce_mfma*, tests/test_long_rows.py).  The slack grows with K: the longer the rows, the more
+// candidates are re-ranked and the sooner structured data (coordinates on a few levels) takes the scan fallback.
 #pragma once
 #include "idist_device.hpp"
 #include "idist_kernels.hpp"
@@ -23,6 +27,26 @@ namespace idist {
 #ifndef IDIST_EMU
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 #endif
+
+// How far a product-form squared distance d~(a,b) = |a|^2 + |b|^2 - 2 a.b, every sum an f32 fma chain over the K stored floats of a
+// row, can lie from the canonical distance d*(a,b) (eight interleaved chains of fma((a-b), (a-b), .)):
+//      |d~ - d*| <= E(a,b) = product_form_eps(K) * (|a|^2 + |b|^2)          (+ 1e-30 where a flushed denormal could matter)
+// Budget, u = 2^-24 the rounding unit: a sum of K products in which no term passes through more than K roundings is off by at most
+// K u sum|x_k y_k| <= K u |x||y|, WHATEVER the order of the additions (to first order; the (K u)^2 / 2 term is < 0.2 % of it at the
+// longest row, K u = 2^-8).  So a.b is within K u |a||b| <= K u (|a|^2 + |b|^2) / 2, -2 a.b within K u (|a|^2 + |b|^2), the two norms
+// within K u |a|^2 and K u |b|^2: the three chains of d~ within 2 K u (|a|^2 + |b|^2) of the true value, and the two additions that
+// combine them add 2 u (...) at most.  The canonical sum (eight chains of K/8 fmas on rounded differences, then their tree) is
+// within (K/8 + 8) u d <= (K/4 + 16) u (|a|^2 + |b|^2) of it (d <= 2 (|a|^2 + |b|^2)).  Together (2.25 K + 18) u <= 3.4 K u for
+// K >= 16, the shortest stored row, and <= 2.3 K u from K = 512; the factor is 4 K u:
+//   * the order of the sum is free: mfma_dist_kernel's and build_select_mfma_kernel's k-ordered chains, whatever order the
+//     matrix core adds the two products of one v_mfma_f32_32x32x2_f32 in, and row_norms_kernel's — 64 lane chains of <= K/64 + 4
+//     fmas, then a butterfly of 6 additions: no term sees more than K/64 + 10 <= K roundings;
+//   * the norms the bound is evaluated with are the computed ones, short of the true ones by a factor >= 1 - K u >= 1 - 2^-8;
+//   * even a matrix core that rounded each product before adding it (two roundings per step: 2 K u on a.b) would stay inside
+//     from K = 32: (3.25 K + 18) u <= 3.82 K u.
+// Both MFMA filters take their margin from here: the build's Gram filter uses E itself, the brute force's threshold 2 E.
+constexpr float kGramEps = 4.0f * 5.9604645e-8f;    // 4 * 2^-24 per stored element, times the row length at run time
+__host__ __device__ inline float product_form_eps(uint32_t K) { return kGramEps * (float)K; }
 
 // tile, K chunk, LDS pitch: 36 floats = 16-B aligned rows, and 36 = 4 * 9 with 9 odd, so 16 lanes reading float4s of rows
 // that differ mod 16 hit 64 distinct banks (ds_read_b128 / ds_write_b128 conflict-free)
@@ -169,10 +193,15 @@ __global__ __launch_bounds__(256) void mfma_dist_kernel(MfmaArgs a) {
     }
 }
 
-// threshold of query q = k-th smallest of its dense sample row (+ slack): one wave per query
+// threshold of query q = k-th smallest of its dense sample row (+ slack): one wave per query.
+// The slack is 2 E with E = product_form_eps(stride) * (|q|^2 + max |p|^2) >= |d~ - d*| of every pair of this query.  Why 2: let
+// t~ be the k-th smallest d~ of the sample.  The k sample points at or below it have d* <= t~ + E (one E: the sample's k-th value),
+// so the k-th smallest d* over ALL points is <= t~ + E, and a true top-k member p, d*(p) at most that, has d~(p) <= d*(p) + E
+// <= t~ + 2 E (the other E: the candidate).  (Clamping d~ at 0 moves it towards d* >= 0; the roundings of this sum itself are
+// u-sized beside a margin of (4 - 3.4) K u at least.)  The floor covers inputs so small that a flushed denormal could matter.
 __global__ __launch_bounds__(64) void kth_threshold_kernel(const float* __restrict__ dense, uint32_t dense_ld, uint32_t ncols,
                                                           uint32_t nq, uint32_t k, uint32_t wcap, const float* __restrict__ qn,
-                                                          float pn_max, float* __restrict__ thr) {
+                                                          float pn_max, uint32_t stride, float* __restrict__ thr) {
     IDIST_DYN_SMEM(smem_raw);
     uint64_t* W = reinterpret_cast<uint64_t*>(smem_raw);
     const int lane = lane_id();
@@ -189,7 +218,8 @@ __global__ __launch_bounds__(64) void kth_threshold_kernel(const float* __restri
         if (lane == 0) {
             // fewer than k sample points: no bound.  Slack covers |d~ - d*| of both the sample's k-th and the candidate.
             float t = __uint_as_float(0x7f800000u);
-            if (st.plen >= (int)k) t = __uint_as_float((uint32_t)((st.W[k - 1] & kKeyMask) >> 32)) + 1e-4f * (qn[q] + pn_max) + 1e-30f;
+            if (st.plen >= (int)k)
+                t = __uint_as_float((uint32_t)((st.W[k - 1] & kKeyMask) >> 32)) + 2.0f * product_form_eps(stride) * (qn[q] + pn_max) + 1e-30f;
             thr[q] = t;
         }
         wave_sync();
@@ -232,11 +262,9 @@ __global__ __launch_bounds__(64) void rerank_kernel(IndexView ix, const float* _
 //
 // The order-defining comparison is `d(c_i, c_j) < d(c_i, q)` (:676-679) with the CANONICAL distance; a product-form
 // distance |c_i|^2 + |c_j|^2 - 2 c_i.c_j rounds differently, so it is used as a filter with a margin, never as the
-// answer: with G~ from v_mfma_f32_32x32x2_f32 and eps_ij = kGramEps * K * (|c_i|^2 + |c_j|^2) (K = stored row length).
-// Error budget: a K-term fma chain is off by at most ~K u sum|a_k b_k| <= K u |a||b| (u = 2^-24), so the three chains of G~
-// are within 2 K u (|c_i|^2 + |c_j|^2) of the true value, the canonical 8-chain sum within (K/8 + 3) u d <= 0.3 K u (...)
-// of it: |G~ - canonical| <= 2.3 K u (|c_i|^2 + |c_j|^2), and eps is 4 K u (...) plus an absolute floor of 1e-30 for
-// inputs so small that a flushed denormal could matter.  With it,
+// answer: with G~ from v_mfma_f32_32x32x2_f32 and eps_ij = product_form_eps(K) * (|c_i|^2 + |c_j|^2) (K = stored row length):
+// the bound on |G~ - canonical| derived above product_form_eps — 2.3 K u (|c_i|^2 + |c_j|^2) for long rows, eps is 4 K u (...) —
+// plus an absolute floor of 1e-30 for inputs so small that a flushed denormal could matter.  With it,
 //      G~ + eps <  d(c_i,q)   =>  c_j is closer for certain          (bit in closer[i])
 //      G~ - eps >= d(c_i,q)   =>  it is not, for certain
 //      otherwise              =>  uncertain: the canonical distance is computed for that pair (bit in unsure[i]).
@@ -250,7 +278,6 @@ __global__ __launch_bounds__(64) void rerank_kernel(IndexView ix, const float* _
 // pitch 36 floats: 16-B aligned rows, and 36 = 4 * 9 with 9 odd => any 16 lanes reading float4s of rows that differ mod 16 hit
 // 64 distinct banks (ds_read_b128 / ds_write_b128 without conflicts)
 constexpr int kGramRows = 128, kGramChunk = 32, kGramPitch = 36;
-constexpr float kGramEps = 4.0f * 5.9604645e-8f;    // 4 * 2^-24 per stored element, times the row length at run time
 
 __host__ __device__ inline size_t smem_bytes_select_mfma(uint32_t stride) {
     return (size_t)kGramRows * kGramPitch * 4 + 2 * kGramRows * 4 * 4 + 2 * kGramRows * 4 + kGramRows * 8 + kGramRows * 4 +
@@ -292,7 +319,7 @@ __global__ __launch_bounds__(256) IDIST_A2M_ATTR void build_select_mfma_kernel(I
     int kTi[3], kTj[3];
 #pragma unroll
     for (int t = 0; t < 3; t++) { kTi[t] = (int)((ti_pack >> (4 * t)) & 15u); kTj[t] = (int)((tj_pack >> (4 * t)) & 15u); }
-    const float eps_k = kGramEps * (float)ix.stride;
+    const float eps_k = product_form_eps(ix.stride);
     HeurCounters hc{0, 0};
     for (;;) {
         if (tid == 0) ctl[0] = atomicAdd(&a.queue[4], 1u);

@@ -42,10 +42,21 @@ class Counters(C.Structure):
 
 
 def build_lib(force: bool = False) -> str:
-    """Compile the oracle with its committed Makefile (gcc)."""
-    src = os.path.join(_HERE, "idist_oracle.c")
-    if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < os.path.getmtime(src):
-        subprocess.check_call(["make", "-C", _HERE, "-s"])
+    """Compile the oracle with its committed Makefile (gcc).  Safe when several processes call it at once (pytest-xdist workers, each
+    with a session of its own): one builds under a lock, the others wait and find the library up to date; the Makefile moves the
+    finished file into place, so nobody ever loads a half-written one."""
+    srcs = [os.path.join(_HERE, f) for f in ("idist_oracle.c", "idist_oracle.h")]
+
+    def stale():
+        return not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(s) for s in srcs)
+
+    if force or stale():
+        import fcntl
+
+        with open(_SO + ".lock", "w") as lk:
+            fcntl.flock(lk, fcntl.LOCK_EX)
+            if force or stale():
+                subprocess.check_call(["make", "-C", _HERE, "-s"])
     return _SO
 
 

@@ -158,7 +158,26 @@ def gen_points(rng, n, dim, kind="uniform", scale=0):
         a = rng.standard_normal((8, dim)).astype(np.float32)
         x = z @ a + 0.05 * rng.standard_normal((n, dim)).astype(np.float32)
         return (x / np.linalg.norm(x, axis=1, keepdims=True)).astype(np.float32)
+    if kind == "levels":         # constant rows: the roundings of a product-form f32 chain all go one way (tests/test_long_rows.py)
+        return np.repeat(levels_table(rng, n, dim)[:, None], dim, axis=1)
     raise ValueError(kind)
+
+
+def half_ulp(dim):
+    """h: half an ulp of the top binade a running f32 sum of `dim` terms of ~1 passes through, 2^(ceil(log2 dim) - 25)"""
+    return float(np.ldexp(1.0, int(np.ceil(np.log2(dim))) - 25))
+
+
+def levels_table(rng, n, dim):
+    """n f32 levels 1 + h (1 + t), t in +-1/8, drawn without repetition from the f32 values in that interval (there are 2^(c-4) + 1
+    for 2^(c-1) < dim <= 2^c; a longer list starts over).  A term 1 * level added to a sum in the top binade loses its h (1 + t)
+    for t < 0 and gains 2 h in its place for t > 0."""
+    c = int(np.ceil(np.log2(dim)))
+    if c < 5:
+        raise ValueError("levels: dim > 16")
+    m = np.arange(7 << (c - 5), (9 << (c - 5)) + 1)              # h (1 + t) in units of 2^-23, the f32 spacing above 1
+    m = rng.permutation(m)[np.arange(n) % len(m)]
+    return (1.0 + np.ldexp(m.astype(np.float64), -23)).astype(np.float32)
 
 
 def check_distance_batch(ida, oracle, n, dim, metric, seed=0, nq=5, n_ids=70):

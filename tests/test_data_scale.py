@@ -4,7 +4,7 @@ The data is always `ldexp(gen_points(...), s)` with the queries scaled by the sa
 exact rescaling until something under- or overflows, so the oracle's answer at s is its answer at 0 with the distances `ldexp`-ed
 (asserted here on the oracle alone, for the scales at which nothing saturates) — and the product has to follow the oracle bit for
 bit at EVERY scale: where its own constants (the reject filter's lattice step and its square, the `+ 1e-30f` floors and the
-`1e-4f * (qn + pn_max)` slack of the MFMA filters, the row norms behind METRIC_DOT) become denormal, zero or inf long before the
+`product_form_eps(K) * (|a|^2 + |b|^2)` margins of the MFMA filters, the row norms behind METRIC_DOT) become denormal, zero or inf long before the
 canonical distances do.
 
   normal            s = -40, +40, +60         nothing saturates; the reject filter must still be at work
