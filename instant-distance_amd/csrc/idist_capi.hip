@@ -3,6 +3,7 @@
 // of the build (Hnsw::new, core/lib.rs:209-345) and of the batched search.
 #include "../../include/idist.h"
 #include "idist_kernels.hpp"
+#include "idist_search_plan.hpp"
 #include "idist_mfma.hpp"
 #include "idist_combine.hpp"
 #include "idist_merge.hpp"
@@ -41,6 +42,8 @@
 using namespace idist;
 static_assert(kRangeCosine == IDIST_METRIC_COSINE && kRangeDot == IDIST_METRIC_DOT && kRungNone == IDIST_RUNG_NONE && kRungExact == IDIST_RUNG_EXACT,
               "idist_range.hpp / idist_allowed.hpp restate constants of include/idist.h");
+static_assert(kFilterFormatNone == IDIST_FILTER_FORMAT_NONE && kFilterFormatIdentity == IDIST_FILTER_FORMAT_IDENTITY && kFilterFormatPrincipal == IDIST_FILTER_FORMAT_PRINCIPAL,
+              "idist_search_plan.hpp restates constants of include/idist.h");
 
 // (The HIP runtime multiplexes a process's streams onto GPU_MAX_HW_QUEUES hardware queues — default 4, read once when the
 // runtime starts.  One `Search` per host thread = one stream per thread: a host that runs more than four of them sets
@@ -163,21 +166,6 @@ inline size_t doubled_from(size_t lo, size_t need) {
     if (!need) return 0;
     while (lo < need) lo <<= 1;
     return lo;
-}
-
-struct Layout {
-    uint32_t stride, nb, rs, tail;
-};
-Layout make_layout(uint32_t dim) {
-    const uint32_t dp = (dim + 3u) & ~3u;      // zero padding is a bitwise no-op (fma(0,0,acc) == acc)
-    const uint32_t steps = dp / 8u;            // chunks_exact(8), instant-distance-py/src/lib.rs:391
-    Layout L;
-    L.tail = (dp % 8u) == 4u ? 1u : 0u;        // :402-405
-    L.nb = steps / 4u;
-    L.rs = steps % 4u;
-    const uint32_t used = 32u * L.nb + 8u * L.rs + 4u * L.tail;
-    L.stride = std::max(16u, (used + 15u) & ~15u);
-    return L;
 }
 
 // Layer sizing of Hnsw::new, core/lib.rs:238-250 (f32 multiply + truncation, `as usize` saturates)
@@ -324,70 +312,38 @@ struct idist_progress {
     unsigned long long total = 0;
 };
 
-// Knobs read from the environment (see test_env above: three in the product, the rest in the test / measurement builds),
-// sampled once per context or build — not per launch.
+// The knobs (struct Knobs, idist_search_plan.hpp) as the environment sets them (see test_env above: three in the product, the rest in
+// the test / measurement builds), sampled once per context or build — not per launch.
 inline int filter_basis_knob(const char* e) { return e[0] == 'p' ? IDIST_FILTER_FORMAT_PRINCIPAL : (e[0] == 'i' ? IDIST_FILTER_FORMAT_IDENTITY : 0); }
-struct Knobs {
-    uint32_t latency_nq = 1024;   // IDIST_LATENCY_NQ: batches up to this many queries run the latency walk (0 = never)
-    bool classic = false;         // IDIST_WALK=classic
-    bool bloom = true;            // IDIST_BLOOM=0 disables the LDS Bloom filter in front of the visited bitmap
-    uint32_t tab_log2 = 0;        // IDIST_TAB_LOG2=<5..13>: size of the on-chip visited set (test knob: small sets exercise the overflow path)
-    bool vis_bitmap = false;      // IDIST_VISITED=bitmap: search with bitmap + Bloom filter (16 waves per CU) instead of the on-chip set
-    bool vis_onchip = false;      // IDIST_VISITED=onchip: the on-chip set whatever the policy says (test / A-B knob)
-    bool combine = true;          // IDIST_COMBINE=0: every scalar host-pointer call makes its own launch, however many are in flight
-    bool sync_flag = true;        // IDIST_SYNC=stream: narrow host-pointer calls wait with hipStreamSynchronize instead of for the completion
-                                  // word the kernel writes to the context's pinned buffer (A/B knob)
-    bool tie_spill_first = false; // IDIST_TIE_SPILL=1: strict ties go to the HBM bags at the first overflow instead of growing the LDS region first (test knob)
-    bool events = true;           // IDIST_KERNEL_EVENTS=0: no HIP events around the search kernels (idist_search_ctx_kernel_times then has nothing)
-    bool filter = true;           // IDIST_FILTER=0: wide on-chip walks without the reject filter (test / A-B knob)
-    uint32_t filter_waves = 0;    // IDIST_FILTER_WAVES=2|3: thin waves per SIMD of a walk on the principal rows (A/B knob; 0: kFilterWavesPrincipal)
-    int basis = 0;                // IDIST_FILTER_BASIS=identity|principal: the compact rows thin wide searches read, whatever the index's
-                                  // policy chose (principal: where the index is eligible for that table) (test / A-B knob)
-    int inl = -1;                 // IDIST_FILTER_INLINE=0|1: thin principal walks without / with the principal rows stored with the adjacency
-                                  // (A/B knob; -1: kFilterInlinePolicy)
-    bool tab_ids = false;         // IDIST_TAB_FORMAT=ids: the on-chip set always keeps full ids (4 per bucket, frozen at 7/8), never
-                                  // 16-bit quotients (8 per bucket, single ids overflow) (test / A-B knob)
-    bool tab_q16 = false;         // IDIST_TAB_FORMAT=q16: quotients wherever they apply, also where the policy would keep ids
-    bool no_zero_copy = false;    // IDIST_NO_ZERO_COPY=1: narrow host-pointer batches take the general (staged) path too (test / A-B knob)
-    int ea = 0;                   // IDIST_EA=<k> (measurement builds only, -DIDIST_EA_PROBE): early abandon after k blocks of a 300-d row
-    uint32_t w2_ef = 0xFFFFFFFFu; // IDIST_W2_EF=<ef>: from this ef_search on, wide on-chip batches run two 256-register waves per SIMD (A/B knob; default: policy)
-    uint32_t allowed_segments = 0;    // IDIST_ALLOWED_SEGMENTS=<1..64>: segments of the exact step of a restricted search (test knob: the result
-                                      // must not depend on it; default: by the number of pending queries)
-    uint32_t range_segments = 0;      // IDIST_RANGE_SEGMENTS=<1..64>: segments of the exact step of a range search (test knob, as allowed_segments)
-    uint32_t range_sort_chunk = 0;    // IDIST_RANGE_SORT_CHUNK=<128..4096, a power of two>: keys a wave of the range search's sort holds in
-                                      // LDS (test knob: small chunks send short lists through the global-memory strides; default 2048)
-    uint32_t quad_nq = 0xFFFFFFFFu;   // IDIST_QUAD_NQ: batches up to this many queries run four waves per query (default: two
-                                      // workgroups per CU, one for 768-d rows; 0 = never)
-    static Knobs from_env() {
-        Knobs k;
-        warn_ignored_knobs();
-        if (const char* e = test_env("IDIST_EA")) k.ea = atoi(e);
-        if (const char* e = test_env("IDIST_W2_EF")) k.w2_ef = (uint32_t)strtoul(e, nullptr, 10);
-        if (const char* e = test_env("IDIST_ALLOWED_SEGMENTS")) k.allowed_segments = std::min(64u, (uint32_t)std::max(0, atoi(e)));
-        if (const char* e = test_env("IDIST_RANGE_SEGMENTS")) k.range_segments = std::min(64u, (uint32_t)std::max(0, atoi(e)));
-        if (const char* e = test_env("IDIST_RANGE_SORT_CHUNK")) {
-            const uint32_t c = (uint32_t)std::max(0, atoi(e));
-            if (c >= 128u && c <= 4096u && (c & (c - 1u)) == 0u) k.range_sort_chunk = c;
-        }
-        if (const char* e = test_env("IDIST_LATENCY_NQ")) k.latency_nq = (uint32_t)strtoul(e, nullptr, 10);
-        if (const char* e = test_env("IDIST_QUAD_NQ")) k.quad_nq = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 0xFFFFFFFEul);
-        if (const char* e = test_env("IDIST_WALK")) k.classic = e[0] == 'c';      // (honoured by the test build only, see variants_check)
-        if (const char* e = test_env("IDIST_BLOOM")) k.bloom = e[0] != '0';
-        if (const char* e = test_env("IDIST_FILTER")) k.filter = e[0] != '0';
-        if (const char* e = test_env("IDIST_FILTER_BASIS")) k.basis = filter_basis_knob(e);
-        if (const char* e = test_env("IDIST_FILTER_INLINE")) k.inl = e[0] != '0' ? 1 : 0;
-        if (const char* e = test_env("IDIST_FILTER_WAVES")) k.filter_waves = atoi(e) == 3 ? 3u : 2u;
-        if (const char* e = test_env("IDIST_VISITED")) { k.vis_bitmap = e[0] == 'b'; k.vis_onchip = e[0] == 'o'; }
-        if (const char* e = test_env("IDIST_NO_ZERO_COPY")) k.no_zero_copy = e[0] != '0';
-        if (const char* e = test_env("IDIST_TAB_FORMAT")) { k.tab_ids = e[0] == 'i'; k.tab_q16 = e[0] == 'q'; }
-        if (const char* e = getenv("IDIST_KERNEL_EVENTS")) k.events = e[0] != '0';
-        if (const char* e = test_env("IDIST_TIE_SPILL")) k.tie_spill_first = e[0] == '1';
-        if (const char* e = getenv("IDIST_SYNC")) k.sync_flag = e[0] != 's';
-        if (const char* e = getenv("IDIST_COMBINE")) k.combine = e[0] != '0';
-        if (const char* e = test_env("IDIST_TAB_LOG2")) k.tab_log2 = std::min(13u, std::max(5u, (uint32_t)atoi(e)));
-        return k;
+inline Knobs knobs_from_env() {
+    Knobs k;
+    warn_ignored_knobs();
+    if (const char* e = test_env("IDIST_EA")) k.ea = atoi(e);
+    if (const char* e = test_env("IDIST_W2_EF")) k.w2_ef = (uint32_t)strtoul(e, nullptr, 10);
+    if (const char* e = test_env("IDIST_ALLOWED_SEGMENTS")) k.allowed_segments = std::min(64u, (uint32_t)std::max(0, atoi(e)));
+    if (const char* e = test_env("IDIST_RANGE_SEGMENTS")) k.range_segments = std::min(64u, (uint32_t)std::max(0, atoi(e)));
+    if (const char* e = test_env("IDIST_RANGE_SORT_CHUNK")) {
+        const uint32_t c = (uint32_t)std::max(0, atoi(e));
+        if (c >= 128u && c <= 4096u && (c & (c - 1u)) == 0u) k.range_sort_chunk = c;
     }
-};
+    if (const char* e = test_env("IDIST_LATENCY_NQ")) k.latency_nq = (uint32_t)strtoul(e, nullptr, 10);
+    if (const char* e = test_env("IDIST_QUAD_NQ")) k.quad_nq = (uint32_t)std::min<unsigned long>(strtoul(e, nullptr, 10), 0xFFFFFFFEul);
+    if (const char* e = test_env("IDIST_WALK")) k.classic = e[0] == 'c';      // (honoured by the test build only, see variants_check)
+    if (const char* e = test_env("IDIST_BLOOM")) k.bloom = e[0] != '0';
+    if (const char* e = test_env("IDIST_FILTER")) k.filter = e[0] != '0';
+    if (const char* e = test_env("IDIST_FILTER_BASIS")) k.basis = filter_basis_knob(e);
+    if (const char* e = test_env("IDIST_FILTER_INLINE")) k.inl = e[0] != '0' ? 1 : 0;
+    if (const char* e = test_env("IDIST_FILTER_WAVES")) k.filter_waves = atoi(e) == 3 ? 3u : 2u;
+    if (const char* e = test_env("IDIST_VISITED")) { k.vis_bitmap = e[0] == 'b'; k.vis_onchip = e[0] == 'o'; }
+    if (const char* e = test_env("IDIST_NO_ZERO_COPY")) k.no_zero_copy = e[0] != '0';
+    if (const char* e = test_env("IDIST_TAB_FORMAT")) { k.tab_ids = e[0] == 'i'; k.tab_q16 = e[0] == 'q'; }
+    if (const char* e = getenv("IDIST_KERNEL_EVENTS")) k.events = e[0] != '0';
+    if (const char* e = test_env("IDIST_TIE_SPILL")) k.tie_spill_first = e[0] == '1';
+    if (const char* e = getenv("IDIST_SYNC")) k.sync_flag = e[0] != 's';
+    if (const char* e = getenv("IDIST_COMBINE")) k.combine = e[0] != '0';
+    if (const char* e = test_env("IDIST_TAB_LOG2")) k.tab_log2 = std::min(13u, std::max(5u, (uint32_t)atoi(e)));
+    return k;
+}
 
 struct idist_search_ctx {
     const idist_index* idx = nullptr;
@@ -548,38 +504,6 @@ struct idist_attr {
 
 namespace {
 
-// The row geometries the kernels are instantiated for at compile time — ONE list: IDIST_DISPATCH instantiates them, and every
-// policy that asks "is this a runtime-geometry index?" (launch_search, run_build, filter_applies) asks has_template_geometry().
-#define IDIST_GEO_LIST(X, L, CALL) X(L, CALL, 4, 0, 0) /* dim 128 */ X(L, CALL, 9, 1, 1) /* dim 300 */ X(L, CALL, 24, 0, 0) /* dim 768 */
-#define IDIST_GEO_TEST(L, CALL, NB_, RS_, TAIL_) if ((L).nb == (NB_) && (L).rs == (RS_) && (L).tail == (TAIL_)) return true;
-inline bool has_template_geometry(const Layout& L) {
-    IDIST_GEO_LIST(IDIST_GEO_TEST, L, _)
-    return false;
-}
-#define IDIST_GEO_CASE(L, CALL, NB_, RS_, TAIL_) \
-    if (!idist_geo_hit_ && (L).nb == (NB_) && (L).rs == (RS_) && (L).tail == (TAIL_)) { idist_geo_hit_ = true; CALL(NB_, RS_, TAIL_); }
-#define IDIST_DISPATCH(L, CALL)                                         \
-    do {                                                                \
-        bool idist_geo_hit_ = false;                                    \
-        IDIST_GEO_LIST(IDIST_GEO_CASE, L, CALL)                         \
-        if (!idist_geo_hit_) { CALL(-1, -1, -1); }                      \
-    } while (0)
-
-// Which filtered kernels a row geometry can ever be given (launch_search / run_build): instantiating only those keeps the build of
-// this translation unit at three minutes.  The thin filtered walk serves compact rows of up to five chunks (128-d, 300-d, runtime
-// geometries) — on the identity rows, and a second instantiation on the 64-byte principal rows (walk_thin_filter_principal) — one fat
-// filtered wave per SIMD the longer ones (768-d, runtime geometries); descents are filtered on thin waves only.  A launch the policy asks for and the geometry has no kernel for is an internal error, never a silent no-op.
-template <int NB> struct GeoKernels {
-    static constexpr bool thin_search = NB != 24;
-    static constexpr bool fat_filtered_search = NB == 24 || NB < 0;
-    static constexpr bool fat_filtered_search_ids = NB == 24;      // (the id form of the set, cheaper to probe while a walk cannot fill it: C4)
-    // thin filtered descents: rows of at least 192 floats by policy — 128-d rows only under the test knob IDIST_BUILD_FILTER=1
-#if defined(IDIST_VARIANTS) || defined(IDIST_EMU) || defined(IDIST_PROBE)
-    static constexpr bool thin_descent = true;
-#else
-    static constexpr bool thin_descent = NB != 4;
-#endif
-};
 // (the third wave per SIMD of a principal walk is an A/B: instantiated where the knob exists, or where it is the default)
 #if defined(IDIST_VARIANTS) || defined(IDIST_EMU) || defined(IDIST_PROBE)
 constexpr bool kPrincipalWaves3 = true;
@@ -587,14 +511,14 @@ constexpr bool kPrincipalWaves3 = true;
 constexpr bool kPrincipalWaves3 = false;
 #endif
 template <int NB, int RS, int TAIL, int WALK, bool ON> struct SearchLaunch {
-    static bool go(uint32_t grid, size_t smem, hipStream_t stream, const IndexView& view, const SearchArgs& a) {
+    static bool go(uint32_t grid, uint32_t block, size_t smem, hipStream_t stream, const IndexView& view, const SearchArgs& a) {
         auto kS = search_kernel<NB, RS, TAIL, WALK>;
-        IDIST_LAUNCH(kS, grid, 64, smem, stream, view, a);
+        IDIST_LAUNCH(kS, grid, block, smem, stream, view, a);
         return true;
     }
 };
 template <int NB, int RS, int TAIL, int WALK> struct SearchLaunch<NB, RS, TAIL, WALK, false> {
-    static bool go(uint32_t, size_t, hipStream_t, const IndexView&, const SearchArgs&) { return false; }
+    static bool go(uint32_t, uint32_t, size_t, hipStream_t, const IndexView&, const SearchArgs&) { return false; }
 };
 template <int NB, int RS, int TAIL, bool ON> struct BoundLaunch {       // filter_bound_kernel on the principal rows
     static bool go(uint32_t grid, size_t smem, const IndexView& view, const float* q, uint32_t nq, const uint32_t* ids, uint32_t n_ids, float* out) {
@@ -711,7 +635,7 @@ idist_status launch_dot_report(float* d, const float* d_sq, float S, uint32_t nq
 // The host side of the metrics that are reductions onto the squared-L2 index (cosine: idist_normalize.hpp, DOT: idist_dot.hpp):
 // ONE pass over a launch's queries in front of the kernels, ONE over the reported distances behind them — the kernels never learn
 // about the metric (kernel_metric, IndexView).  Every entry point goes through this pair; one that is handed prepared queries or
-// reports later itself (launch_search's `prepared`, the brute force's `raw`) skips the call.  L2SQ and L2 enqueue nothing.
+// reports later itself (SearchOpts::prepared of launch_search, the brute force's `raw`) skips the call.  L2SQ and L2 enqueue nothing.
 struct MetricPasses {
     int32_t metric;
     uint32_t dim, kdim;     // coordinates of a caller's query, of the row the kernels read
@@ -840,9 +764,6 @@ uint32_t default_slots(uint32_t n_points, int n_cu) {
     return (uint32_t)std::max<size_t>(s, 1);
 }
 
-// LDS one wave of the on-chip walk may use: one wave per SIMD, four per CU, out of 160 KiB
-constexpr size_t kOnChipLdsPerWave = 40 * 1024;
-
 thread_local uint32_t g_tie_cap_msg = kTieCap;
 uint32_t tie_capacity(const idist_config& cfg) { return g_tie_cap_msg = cfg.tie_capacity ? cfg.tie_capacity : (uint32_t)kTieCap; }
 
@@ -888,7 +809,7 @@ idist_status run_build(idist_index* ix, idist_progress* prog, bool tie_spill) {
     uint32_t slots = std::min(cap, (uint32_t)ix->n_cu * 8u);
     if (tie_spill) slots = std::min<uint32_t>(slots, (uint32_t)std::max<size_t>(1, ((size_t)1 << 30) / ((size_t)n * 8)));
     const VisGeom vg = vis_geometry(n);
-    const Knobs knobs = Knobs::from_env();
+    const Knobs knobs = knobs_from_env();
     CHK(variants_check(knobs.classic));
     // no compile-time instantiation of the row geometry (IDIST_DISPATCH): the runtime-geometry kernels
     const bool rt_geometry = !has_template_geometry(ix->L);
@@ -1260,10 +1181,10 @@ idist_status run_build(idist_index* ix, idist_progress* prog, bool tie_spill) {
 #ifdef IDIST_VARIANTS
 #define IDIST_VARIANT_BUILD(NB_, RS_, TAIL_)                                                                          \
     else if (classic && tab16) {                                                                                      \
-        auto kA16 = build_insert_kernel<NB_, RS_, TAIL_, walk_code(kWalkClassic, 0, false, 1, true, false, true)>;    \
+        auto kA16 = build_insert_kernel<NB_, RS_, TAIL_, kWalkClassicOnChipQ16>;                                         \
         IDIST_LAUNCH(kA16, gridA, 64, smem, sA, viewA, aA);                                                           \
     } else if (classic) {                                                                                             \
-        auto kA = build_insert_kernel<NB_, RS_, TAIL_, walk_code(kWalkClassic, 0, false, 1, true)>;                   \
+        auto kA = build_insert_kernel<NB_, RS_, TAIL_, kWalkClassicOnChipIds>;                                           \
         IDIST_LAUNCH(kA, gridA, 64, smem, sA, viewA, aA);                                                             \
     }
 #else
@@ -1271,12 +1192,12 @@ idist_status run_build(idist_index* ix, idist_progress* prog, bool tie_spill) {
 #endif
 #define LAUNCH_BUILD(NB_, RS_, TAIL_)                                                              \
     {                                                                                              \
-        auto kAo = build_insert_kernel<NB_, RS_, TAIL_, walk_code(kWalkOverlap, 0, false, 1, true)>; \
-        auto kAo16 = build_insert_kernel<NB_, RS_, TAIL_, walk_code(kWalkOverlap, 0, false, 1, true, false, true)>; \
+        auto kAo = build_insert_kernel<NB_, RS_, TAIL_, kWalkFatIds>;                        \
+        auto kAo16 = build_insert_kernel<NB_, RS_, TAIL_, kWalkFatQ16>;                      \
         /* two descent waves per SIMD: 256 registers each, fewer rounds in flight per wave, more waves */ \
         /* narrow steps (the growth phase of a layer, max_batch = 1): four waves per insertion, like narrow search batches */ \
-        auto kAq16 = build_insert_kernel<NB_, RS_, TAIL_, walk_code(kWalkOverlap, 0, false, 1, true, true, true)>; \
-        auto kAo16w2 = build_insert_kernel<NB_, RS_, TAIL_, walk_code(kWalkOverlap, (NB_) == 24 ? 1 : ((NB_) == 4 ? 6 : 3), false, 2, true, false, true)>; \
+        auto kAq16 = build_insert_kernel<NB_, RS_, TAIL_, kWalkFourWaveQ16>;                 \
+        auto kAo16w2 = build_insert_kernel<NB_, RS_, TAIL_, walk_two_per_simd(NB_)>;          \
         /* ... and with the reject filter in front of the distance passes (thin: one f32 round in flight, query fragment from LDS) */ \
         auto kF = build_update_fast_kernel<NB_, RS_, TAIL_>;                                       \
         auto kB = build_update_kernel<NB_, RS_, TAIL_>;                                            \
@@ -1483,44 +1404,6 @@ idist_status ensure_slots(idist_search_ctx* ctx, uint32_t want, hipStream_t stre
     return IDIST_OK;
 }
 
-// Which walk serves a wide batch (profiles/r02/probe_r02_ef_paths_onchip_vs_bitmap.jsonl, probe_r02_configs_c2_c4_c5.jsonl):
-//   * a search visits ~53 * ef_search + 600 nodes; the 8192-id on-chip set is frozen at 7168 and the rest of the walk
-//     test-and-sets the bitmap.  The fat on-chip waves still win while a row fetch outweighs that extra round trip:
-//     up to ef_search ~ 180 at 128-d, ~ 550 at 300-d (id set; ~ 600 with the quotient set), beyond 200 at 768-d;
-//   * an index that sits in the Infinity Cache (100k x 128: 51 MB) is served faster by 16 small waves per CU
-//     (4.2 vs 5.0 ms per 10k queries): the on-chip walk is for HBM-resident indexes.
-//   * round 4 (profiles/r04/probe_r04f_ef_crossover_c3.jsonl, probe_r04i_ef_paths_wide_merge_c3.jsonl): with the quotient set the
-//     crossover at 300-d moved from ~1.5 to ~2 x row floats, and once the fat waves merged a `nearest` of up to 1024 entries in
-//     one pass (w_push_merge<16>) the on-chip walk stayed ahead of the bitmap walk up to ef_search 1000 (0.651 / 0.637 / 0.625
-//     vs 0.628 / 0.620 / 0.611 of spec at 650 / 800 / 1000; beyond the merge's reach too: 0.628 vs 0.565 at ef 1000 in
-//     probe_r04k).  Rows of >= 256 floats: on chip as far as LDS allows; shorter rows: the line through the 128-d (~180) and
-//     300-d (~600) crossovers.
-//   * round 5 (profiles/r05/probe_r05m_walk_policy_cache_resident.jsonl, probe_r05n_walk_policy_by_size_and_row.jsonl: on-chip walk vs
-//     bitmap walk at 9 more shapes): which walk wins near the Infinity Cache depends on the ROW LENGTH, not on residency alone.
-//     Rows of >= 256 floats: the on-chip walk wins by 5-8 % also where the index sits in the cache (100k x 300: 7.97 vs 8.51 ms,
-//     40k x 768: 17.2 vs 18.1 ms per 10k queries at ef 100; the same at ef 150-800).  Shorter rows: the bitmap walk wins well BEYOND
-//     the 128-MB mark — 300k x 128 (154 MB): 4.39 vs 4.69 ms at ef 100, 6.03 vs 7.50 at ef 150; 400k x 200-d (320 MB): 7.49 vs 8.76 and
-//     13.2 vs 17.8; 1M x 64-d (256 MB): 4.96 vs 6.84 — and loses from ~512 MB on (1M x 128: 6.73 vs 5.29 ms); and once such an index
-//     is far beyond the cache the on-chip walk stays ahead to higher ef_search (1M / 2M x 128 at ef 200: 10.6 / 10.9 against 11.8 /
-//     15.0 ms; 2M x 128 at ef 400: 23.0 against 27.5; 1M x 128 at ef 400: a tie).
-//     Runtime-geometry rows shorter than 128 floats are different again: the fat waves' register tile (<8 blocks, 4 rounds>) keeps only
-//     4 x 8 rows x 256 B = 8 KB on the wire per wave at 64-d, and the bitmap walk wins at EVERY size — 4M x 64 (1 GB): 5.93 / 10.7 /
-//     20.1 ms against 7.13 / 14.9 / 31.0 ms at ef 100 / 200 / 400; at 100-d (3 blocks) it wins from ef ~150 on (3M x 100: 14.9 / 27.3
-//     against 16.3 / 34.0 ms at ef 200 / 400, a tie at ef 100); 200-d rows behave like the 128-d instantiation (2M x 200: on chip 9.83 /
-//     19.3 against 11.5 / 21.1 ms) — profiles/r05/probe_r05u_walk_policy_short_rt_rows_large.jsonl.
-inline uint32_t on_chip_max_ef(uint32_t stride_floats, size_t index_bytes, bool runtime_geometry) {
-    if (stride_floats >= 256u) return 1536u;       // (as far as W and the set fit a wave's LDS: tab_fit in launch_search)
-    if (runtime_geometry && stride_floats <= 64u) return 0u;         // never: see above
-    if (runtime_geometry && stride_floats < 128u) return 160u;
-    const int ef = (int)stride_floats * 61 / 25 - 132;
-    return (uint32_t)std::min(1536, std::max(index_bytes >= ((size_t)512 << 20) ? 400 : 160, ef));
-}
-// short rows (< 256 floats) are served by the bitmap walk up to this many bytes of point rows (see above)
-constexpr size_t kShortRowBitmapBytes = (size_t)320 << 20;
-// ... and long rows by the on-chip walk from this size on (below it nothing was measured: the round-2 rule stands)
-constexpr size_t kLongRowOnChipBytes = (size_t)96 << 20;
-constexpr uint32_t kFilterWaves = 2u;    // waves per SIMD of a filtered wide walk (launch_search)
-constexpr uint32_t kFilterWavesPrincipal = 2u;   // ... on the principal rows (three: measured)
 // a forced format that cannot be served is an error, never a quiet run on the other table
 idist_status filter_basis_forced_check(const idist_index* ix, int knob) {
     if (knob == IDIST_FILTER_FORMAT_PRINCIPAL && ix->filt_state.load(std::memory_order_acquire) == 1 && ix->filt_p_turned_down)
@@ -1528,7 +1411,6 @@ idist_status filter_basis_forced_check(const idist_index* ix, int knob) {
                                            "the knob was set (set it before the index's first wide search)");
     return IDIST_OK;
 }
-constexpr uint32_t kLongWalkEf = 512u;   // ef_search from which wide on-chip batches run two thinner waves per SIMD (see launch_search)
 
 // Long walks and where the visited bitmaps land (round 5, measured, nothing kept): ef_search 800 at 1M points test-and-sets the HBM
 // bitmaps ~36k times per query, and five fresh contexts on ONE index in one process answer the same 10k queries in 72.5 / 72.9 / 79.1 /
@@ -1801,7 +1683,6 @@ idist_status filter_principal_ensure(const idist_index* ix, const std::vector<fl
 // card to rows of 1.2 KB each and their graph; beyond it the gain of one round trip per expansion is not worth a memory footprint
 // four times the rows' own.  (IDIST_FILTER_INLINE_CAP=<bytes>: test build.)
 constexpr uint64_t kFilterInlineCapBytes = 8ull << 30;
-constexpr bool kFilterInlinePolicy = true;
 idist_status filter_inline_ensure(const idist_index* ix) {
     if (ix->filt_inl_state.load(std::memory_order_acquire) != 0) return IDIST_OK;
     std::lock_guard<std::mutex> lk(ix->filt_mu);
@@ -1827,9 +1708,7 @@ idist_status filter_inline_ensure(const idist_index* ix) {
     ix->filt_inl_state.store(1, std::memory_order_release);
     return IDIST_OK;
 }
-bool filter_applies(const idist_index* ix) {
-    return ix->n > 0 && (has_template_geometry(ix->L) || filt_stride(ix->L.stride) <= 128u * (uint32_t)kFiltRtChunksFat);
-}
+bool filter_applies(const idist_index* ix) { return idist::filter_applies(ix->n, ix->L); }
 idist_status filter_ensure(const idist_index* ix, bool with_principal) {
     auto settled = [&]() {
         const int st = ix->filt_state.load(std::memory_order_acquire);
@@ -1902,129 +1781,84 @@ idist_status filter_ensure(const idist_index* ix, bool with_principal) {
     return IDIST_OK;
 }
 
+// What a caller may add to a plain launch of the index's own ef_search
+struct SearchOpts {
+    uint32_t* status_host = nullptr;   // pinned words the kernel writes its slots' status to (narrow host-pointer batches)
+    uint32_t* grid_out = nullptr;      // the launch's grid
+    uint32_t* done_host = nullptr;     // pinned completion word, written with done_seq
+    uint32_t done_seq = 0;
+    bool prepared = false;             // d_q already holds what the kernels read and the caller reports later (the partitioned search: after its merge)
+    uint32_t ef = 0;                   // the ef_search of this launch when it is not the index's (the rungs of a restricted search: the index
+                                       // is shared and never mutated)
+    bool* lds_short = nullptr;         // set when the launch was refused because this ef_search does not fit a wave's LDS
+};
+// the state of the lazily made tables into the facts; true when one of them differs from what `f` held
+bool table_facts(const idist_index* ix, SearchFacts& f) {
+    const bool ready = ix->filt_state.load(std::memory_order_acquire) == 1;
+    const bool table = ready && ix->filt_p_state.load(std::memory_order_acquire) == 1 && ix->filt_p.rows;   // (filt_p is written before its state)
+    const int format = table ? ix->filt_format.load(std::memory_order_relaxed) : IDIST_FILTER_FORMAT_NONE;
+    const bool inl = ix->filt_inl_state.load(std::memory_order_acquire) == 1;
+    const bool changed = ready != f.filter_ready || table != f.principal_table || format != f.filt_format || inl != f.inline_ready;
+    f.filter_ready = ready;
+    f.principal_table = table;
+    f.filt_format = format;
+    f.inline_ready = inl;
+    return changed;
+}
+
+// One search launch: the facts of this index, context and call -> the plan (plan_search, idist_search_plan.hpp: which kernel, which
+// visited set, how much LDS, how many resident walks) -> the tables the plan wants -> the launch.
 idist_status launch_search(const idist_index* ix, idist_search_ctx* ctx, const float* d_q, uint32_t nq,
                            uint32_t* d_pid, float* d_dist, uint32_t* d_cnt, uint32_t* d_ctr, hipStream_t stream,
-                           uint32_t* status_host = nullptr, uint32_t* grid_out = nullptr, uint32_t* done_host = nullptr, uint32_t done_seq = 0,
-                           bool prepared = false, uint32_t ef_arg = 0, bool* lds_short = nullptr) {
-    // ef_arg: the ef_search of this launch when it is not the index's (the rungs of a restricted search: the index is shared and
-    // never mutated).  *lds_short: set when the launch was refused because this ef_search does not fit a wave's LDS.
-    const uint32_t ef = ef_arg ? ef_arg : ix->cfg.ef_search;
-    if (lds_short) *lds_short = false;
-    CHK(variants_check(ctx->knobs.classic));
+                           const SearchOpts& o = SearchOpts()) {
+    const uint32_t ef = o.ef ? o.ef : ix->cfg.ef_search;
+    if (o.lds_short) *o.lds_short = false;
+    const Knobs& knobs = ctx->knobs;
+    CHK(variants_check(knobs.classic));
     // Cosine and DOT: the walk reads the queries MetricPasses::prepare wrote into buffers this context owns (the caller's are only
     // read), and the distances it wrote are reported behind it — both on the launch's stream, outside the events that time the
-    // search kernel.  `prepared`: d_q already holds what the kernels read and the caller reports later (the partitioned search:
-    // after its merge).
+    // search kernel.
     const MetricPasses metric(ix);
-    const bool passes = metric.any() && !prepared;
+    const bool passes = metric.any() && !o.prepared;
     if (passes) {
         CHK(ctx->d_qn.grow(doubled_from(4096, metric.qk_floats(nq) * 4)));
         CHK(ctx->d_sq.grow(doubled_from(256, metric.sq_floats(nq) * 4)));
         CHK(metric.prepare(d_q, ctx->d_qn, ctx->d_sq, nq, stream, &d_q));
     }
+    // ---- facts
+    SearchFacts facts;
+    facts.n = ix->n;
+    facts.L = ix->L;
+    facts.n_cu = ix->n_cu;
+    facts.template_geometry = has_template_geometry(ix->L);
+    facts.filter_applies = filter_applies(ix);
+    facts.ef = ef;
+    facts.nq = nq;
+    facts.tie_cap = std::max(tie_capacity(ix->cfg), ctx->tie_cap);
+    facts.dirty_words = ctx->vis.dirty_words;
+    table_facts(ix, facts);
+    // ---- plan, and the tables it wants (made on first use; once they stand or are turned down the first plan is the launch's)
+    SearchPlan plan = plan_search(facts, knobs);
+    if (plan.wants_filter) {
+        CHK(filter_ensure(ix));
+        if (table_facts(ix, facts)) plan = plan_search(facts, knobs);
+    }
+    if (plan.wants_filter && facts.filter_ready) CHK(filter_basis_forced_check(ix, knobs.basis));
+    if (plan.wants_inline) {
+        CHK(filter_inline_ensure(ix));
+        if (table_facts(ix, facts)) plan = plan_search(facts, knobs);
+    }
+    // ---- launch
     SearchArgs a{};
     a.queries = d_q;
     a.nq = nq;
     a.ef = ef;
-    a.tie_cap = std::max(tie_capacity(ix->cfg), ctx->tie_cap);
-    a.wcap = ef + 64 + a.tie_cap + 8;
+    a.tie_cap = facts.tie_cap;
+    a.wcap = plan.wcap;
     a.vis = ctx->vis;
-    // Default walk: the visited set lives in LDS (an exact hash set of 2^tab_log2 ids per query, the HBM bitmap only
-    // takes what does not fit), one wave per SIMD with up to 512 registers for rows in flight.  The largest set that
-    // fits a quarter of the CU's LDS next to the query tile and W is used; none fits (huge ef_search) -> bitmap walk.
-    uint32_t tab_fit = 0;                                               // largest set that fits at all
-    for (uint32_t l = 13; l >= 10 && !tab_fit; l--)
-        if (smem_bytes(ix->L.stride, a.wcap, false, 1u << l, a.vis.dirty_words) <= kOnChipLdsPerWave) tab_fit = l;
-    if (tab_fit && ctx->knobs.tab_log2) tab_fit = std::min(tab_fit, ctx->knobs.tab_log2);
-    if (ctx->knobs.vis_bitmap) tab_fit = 0;
-    // Narrow batches (the reference's call pattern is ONE query per Hnsw::search): a four-wave workgroup per query,
-    // one workgroup per CU — the rows of an expansion are fetched by all four SIMDs in one round trip.
-    // Two such workgroups share a CU where the kernel's registers allow it (all but the 768-d instantiation): up to two
-    // queries per CU the four-wave walk beats the single-wave one (512 queries: 0.65 vs 0.81 ms at C3), beyond it loses.
-    const uint32_t quad_per_cu = (ix->L.nb == 24 && ix->L.rs == 0 && ix->L.tail == 0) ? 1u : 2u;
-    const uint32_t quad_nq = ctx->knobs.quad_nq == 0xFFFFFFFFu ? (uint32_t)ix->n_cu * quad_per_cu : ctx->knobs.quad_nq;
-    const bool quad = tab_fit && !ctx->knobs.classic && nq <= quad_nq;
-    const size_t row_bytes = (size_t)ix->n * ix->L.stride * 4;
-    const bool long_rows = ix->L.stride >= 256u;
-    const bool rt_rows = !has_template_geometry(ix->L);   // no compile-time instantiation of the row geometry
-    const bool cache_resident = long_rows ? row_bytes < kLongRowOnChipBytes : row_bytes <= kShortRowBitmapBytes;   // "served best by many small waves"
-    // With the reject filter in front (round 6) the on-chip walk stays ahead at every ef_search the set fits — 1M x 128 at ef 200 / 400:
-    // 8.5 / 15.4 ms against 10.6 / 20.8 ms on the bitmap walk, 4M x 64-d at ef 100 / 200: 5.1 / 10.3 against 5.9 / 11.8 — and the ef
-    // caps of on_chip_max_ef only bind for unfiltered indexes (compact rows beyond the filter's tiles, IDIST_FILTER=0).  The
-    // cache-residency rule shrinks too: filtered long rows take it at every size (20k x 300: 3.46 against 5.87 ms; 40k x 768 did before),
-    // filtered short rows from the L2's reach on (8 x 4 MB: 100k x 128 = C2 3.44 against 3.80 ms at ef 100, 6.56 against 6.64 at ef 200,
-    // a tie at 400; 300k x 128 3.65 against 4.45; 400k x 200-d 4.71 against 7.48) — below it the bitmap walk's sixteen small waves per
-    // CU win (10k x 128: 1.98 against 2.83 ms, 50k x 64-d: 2.85 against 3.75) — profiles/probe_r06f_filter_policy.jsonl,
-    // probe_r06l_c2_policy.jsonl.
-    const bool filter_ok = ctx->knobs.filter && filter_applies(ix);
-    const bool small_for_filter = !long_rows && row_bytes < ((size_t)32 << 20);
-    const bool wide_on_chip = tab_fit && (ctx->knobs.vis_onchip || ctx->knobs.tab_log2 ||
-                                          (filter_ok ? !small_for_filter : (ef <= on_chip_max_ef(ix->L.stride, row_bytes, rt_rows) && !cache_resident)));
-    const bool on_chip = quad || wide_on_chip;
-    uint32_t tab_log2 = on_chip ? tab_fit : 0u;
-    // The reject filter in front of the wide on-chip walks' distance passes (its compact rows are made on first use).  A filtered
-    // walk is bound by its dependent round trips, so it runs as `fw` thin waves per SIMD (walk_thin_filter, idist_device.hpp) with
-    // the largest quotient set that lets 4 * fw of them share a CU's LDS — where the quotient form applies (n <= 33M) and the
-    // caller did not pin the set's form or size.
-    const bool use_filter = wide_on_chip && !quad && filter_ok;
-    if (use_filter) CHK(filter_ensure(ix));
-    const bool filtered = use_filter && ix->filt_state.load(std::memory_order_acquire) == 1;
-    // (every other wide walk — unfiltered indexes, IDIST_TAB_FORMAT=ids, the classic test walks, n beyond the quotient form's reach —
-    //  runs the round-5 kernels, compiled WITHOUT the filter: carrying its registers cost the 1024-d search 15 %)
-    // Long rows (compact rows beyond the thin tile's five chunks: 768-d) keep ONE fat wave per SIMD with the filter: a thin wave's registers hold 16
-    // of their compact rows and a quarter of an f32 row at a time — six or seven dependent round trips per expansion where the fat
-    // wave makes two (C5, ef 200: 162 ms fat against 213 ms thin per 65,536 queries; C4 a tie at 78-83 ms).
-    // (always on the quotient form of the set — the id form's cheaper probe was worth 1-2 % and another two large kernels to compile)
-    const bool fat_filtered = filtered && !ctx->knobs.classic && !ctx->knobs.tab_ids && filt_stride(ix->L.stride) > 128u * (uint32_t)kFiltRtChunks &&
-                              q16_applies(tab_fit, q16_universe_bits(ix->n, tab_fit));
-    // ... except the 768-d instantiation while the id form of the set cannot fill up (ef_search <= ~120: C4)
-    const bool fat_ids = fat_filtered && ix->L.nb == 24 && ix->L.rs == 0 && ix->L.tail == 0;
-    uint32_t fw = 1;
-    if (filtered) CHK(filter_basis_forced_check(ix, ctx->knobs.basis));
-    // thin walks read the table the index's policy chose (filter_principal_ensure) — the 64-byte principal rows have their own instantiation
-    const bool principal_rows = filtered && !fat_filtered && ix->filt_p.rows &&
-                                (ctx->knobs.basis ? ctx->knobs.basis : ix->filt_format.load(std::memory_order_relaxed)) == IDIST_FILTER_FORMAT_PRINCIPAL;
-    if (filtered && !fat_filtered && !ctx->knobs.classic && !ctx->knobs.tab_ids)
-        fw = principal_rows ? (ctx->knobs.filter_waves ? ctx->knobs.filter_waves : kFilterWavesPrincipal) : kFilterWaves;
-    if (fw > 1) {
-        uint32_t l = ctx->knobs.tab_log2 ? std::min(tab_fit, ctx->knobs.tab_log2) : tab_fit;
-        // (a smaller set addresses fewer ids in its 16-bit quotients: 10M points need the 16-KB set — C5 runs six or seven thin
-        //  waves per CU on it rather than eight on a set it cannot use)
-        while (l > 10u && smem_bytes(ix->L.stride, a.wcap, false, 1u << l, a.vis.dirty_words, false) * 4u * fw > (size_t)160 * 1024 &&
-               q16_applies(l - 1u, q16_universe_bits(ix->n, l - 1u)))
-            l--;
-        if (q16_applies(l, q16_universe_bits(ix->n, l))) tab_log2 = l;
-        else fw = 1;
-    }
-    const bool thin = fw > 1;
-    // ... two of them per SIMD on the principal rows read those rows from the blocks stored with the adjacency, where the index has them
-    const bool want_inline = thin && principal_rows && fw == 2u && (ctx->knobs.inl >= 0 ? ctx->knobs.inl == 1 : kFilterInlinePolicy);
-    if (want_inline) CHK(filter_inline_ensure(ix));
-    const bool inlined = want_inline && ix->filt_inl_state.load(std::memory_order_acquire) == 1;
-    a.tab_log2 = tab_log2;
-    // the set stores 16-bit quotients (twice the ids in the same LDS) whenever n allows it: up to 33M points with 32 KB
-    a.ubits = on_chip ? q16_universe_bits(ix->n, tab_log2) : 0u;
-    // ... and the walk can outgrow the id form: a search visits ~53 * ef_search + 600 nodes (C3 / C4 / C5 data alike); while that
-    // stays below the 7/8 * 2^tab_log2 ids the plain set takes, the plain set never spills and its cheaper probe wins by
-    // 1-2 % (ef_search = 100: 10.25 vs 10.42 ms per 10k queries at C3, profiles/r03/probe_r03a_ef_paths_*)
-    const bool ids_suffice = 53u * ef + 600u <= (7u << tab_log2) / 8u;
-    const bool q16 = on_chip && !ctx->knobs.tab_ids && q16_applies(tab_log2, a.ubits) &&
-                     (thin || (fat_filtered && !(fat_ids && ids_suffice && !ctx->knobs.tab_q16 && !ctx->knobs.tab_log2)) || ctx->knobs.tab_q16 || ctx->knobs.tab_log2 || !ids_suffice);
-    // Long walks (ef_search in the hundreds): an expansion costs a wave 9-10 us whatever it fetches, and it fetches fewer new rows
-    // the longer the walk runs — more, thinner waves (two 256-register waves per SIMD, as many as the CU's LDS holds) keep more
-    // expansions in flight than one fat wave per SIMD.
-    // Measured at 300-d (profiles/r04/probe_r04k_ef_paths_two_waves_per_simd_c3.jsonl: ef 650 / 800 / 1000 at 0.704 / 0.690 / 0.651 of
-    // spec against 0.653 / 0.639 / 0.628 for the fat waves, 0.787 against 0.795 at ef 400): from ef_search 512 on, for that row
-    // geometry; other geometries keep the fat waves until they are measured (IDIST_W2_EF forces either way).
-    // Round 5 (profiles/r05/probe_r05r_long_walks_two_waves_other_geometries.jsonl): the same holds for runtime-geometry rows the
-    // 256-register tile keeps whole in flight (1M x 384-d: ef 600 / 800 at 79.1 / 105.1 ms against 88.5 / 114.6 ms, ef 400 within
-    // 2 %); not for 768-d (fat waves 1 % ahead at ef 400-800) and not for 128-d (thin waves 43 % slower at ef 400).
-    const bool w2_geometry = (ix->L.nb == 9 && ix->L.rs == 1 && ix->L.tail == 1) || (rt_rows && ix->L.stride >= 256u && ix->L.nb <= 12u);
-    const uint32_t w2_from = ctx->knobs.w2_ef != 0xFFFFFFFFu ? ctx->knobs.w2_ef : (w2_geometry ? kLongWalkEf : 0xFFFFFFFFu);
-    const bool w2 = on_chip && q16 && !quad && !thin && !ctx->knobs.classic && ef >= w2_from;
-    const uint32_t w2_per_cu = (uint32_t)std::min<size_t>(8, (size_t)160 * 1024 / smem_bytes(ix->L.stride, a.wcap, false, 1u << std::max(tab_log2, 5u), a.vis.dirty_words));
-    const uint32_t thin_per_cu = (uint32_t)std::min<size_t>(4u * fw, (size_t)160 * 1024 / smem_bytes(ix->L.stride, a.wcap, false, 1u << std::max(tab_log2, 5u), a.vis.dirty_words, false));
-    uint32_t resident = (uint32_t)ix->n_cu * (quad ? 2u : (thin ? std::max(thin_per_cu, 4u) : (w2 ? std::max(w2_per_cu, 4u) : (on_chip ? 4u : 16u))));   // quad: two workgroups per CU where registers allow
+    a.tab_log2 = plan.tab_log2;
+    a.ubits = plan.ubits;
+    uint32_t resident = plan.resident;
     if (ctx->tie_spill) {
         // one bag of n keys per slot (a walk can hold every point as a tie at most once); the slots that fit 1 GiB
         const uint32_t fit = (uint32_t)std::max<size_t>(1, ((size_t)1 << 30) / ((size_t)std::max(ix->n, 1u) * 8));
@@ -2049,113 +1883,79 @@ idist_status launch_search(const idist_index* ix, idist_search_ctx* ctx, const f
     a.visited = ctx->d_visited;
     a.next = ctx->d_next;
     a.status = ctx->d_next + 1;
-    a.use_bloom = ctx->knobs.bloom ? 1u : 0u;
-    // bitmap walk only: narrow batches cannot fill the chip and run its latency variant (same results)
-    const bool lat = !on_chip && nq <= ctx->knobs.latency_nq &&
-                     smem_bytes(ix->L.stride, a.wcap, false, kBloomLatWords, a.vis.dirty_words) <= 64 * 1024;
-    const size_t smem = smem_bytes(ix->L.stride, a.wcap, false, on_chip ? (1u << tab_log2) : (lat ? kBloomLatWords : kBloomWords),
-                                   a.vis.dirty_words, !thin);
-    if (smem > 64 * 1024) {
-        if (lds_short) *lds_short = true;
+    a.use_bloom = knobs.bloom ? 1u : 0u;
+    const size_t smem = plan.smem;
+    if (plan.lds_short) {
+        if (o.lds_short) *o.lds_short = true;
         return fail(IDIST_ERR_INVALID_ARG, "dim/ef_search need %zu B of LDS per wave (> 64 KiB)", smem);
     }
     const uint32_t grid = std::min(std::min(nq, ctx->slots), resident);
-    [[maybe_unused]] const bool classic = ctx->knobs.classic;   // (test build: IDIST_VARIANT_SEARCH_*)
     IndexView view = ix->view();
-    if (!thin && !fat_filtered) view.f = FilterView{};
-    const bool principal = thin && principal_rows;
-    if (principal) { view.f2 = view.f; view.f = ix->filt_p; }       // (f2: the identity rows, for the queries the basis does not fit)
-    if (inlined) view.inl = ix->filt_inl;
+    if (plan.filter == PlanFilter::None) view.f = FilterView{};
+    if (plan.filter == PlanFilter::Principal) { view.f2 = view.f; view.f = ix->filt_p; }       // (f2: the identity rows, for the queries the basis does not fit)
+    if (plan.inl) view.inl = ix->filt_inl;
     a.queue_base = ctx->queue_base;
-    a.status_host = status_host && grid <= idist_search_ctx::kIoStatusSlots ? status_host : nullptr;
-    a.done_host = done_host;
+    a.status_host = o.status_host && grid <= idist_search_ctx::kIoStatusSlots ? o.status_host : nullptr;
+    a.done_host = o.done_host;
     a.done_count = ctx->d_next + 2;
     a.filt_counts = reinterpret_cast<unsigned long long*>(ctx->d_next + 16);       // [6]: + the share of both on the principal rows, + the inlined blocks
-    a.done_seq = done_seq;
-    if (grid_out) *grid_out = grid;
+    a.done_seq = o.done_seq;
+    if (o.grid_out) *o.grid_out = grid;
     const uint32_t slot = (uint32_t)(ctx->n_launch % IDIST_EVENT_RING);
-    if (ctx->knobs.events) HIPCHK(hipEventRecord(ctx->ev0[slot], stream));
+    if (knobs.events) HIPCHK(hipEventRecord(ctx->ev0[slot], stream));
 // The `classic` walks (one distance round in flight, no adjacency prefetch) are selected by no policy: they exist as
 // independent implementations of the same decisions for the parity tests and are compiled into the TEST build only
 // (`make variants` -> libidist_variants.so, -DIDIST_VARIANTS; the CPU emulator build defines it too).
 #ifdef IDIST_VARIANTS
-#define IDIST_VARIANT_SEARCH_ONCHIP_Q16(NB_, RS_, TAIL_)                                                    \
-    else if (on_chip && classic && q16) {                                                                   \
-        auto kS = search_kernel<NB_, RS_, TAIL_, walk_code(kWalkClassic, 0, false, 1, true, false, true)>;  \
-        IDIST_LAUNCH(kS, grid, 64, smem, stream, view, a);                                                  \
-    }
-#define IDIST_VARIANT_SEARCH_ONCHIP_IDS(NB_, RS_, TAIL_)                                                    \
-    else if (on_chip && classic) {                                                                          \
-        auto kS = search_kernel<NB_, RS_, TAIL_, walk_code(kWalkClassic, 0, false, 1, true)>;               \
-        IDIST_LAUNCH(kS, grid, 64, smem, stream, view, a);                                                  \
-    }
-#define IDIST_VARIANT_SEARCH_BITMAP(NB_, RS_, TAIL_)                                                        \
-    else if (classic) {                                                                                     \
-        auto kS = search_kernel<NB_, RS_, TAIL_, kWalkClassic>;                                             \
-        IDIST_LAUNCH(kS, grid, 64, smem, stream, view, a);                                                  \
-    }
+#define IDIST_VARIANT_SEARCH_CASES(NB_, RS_, TAIL_)                                                                  \
+    case SearchWalk::ClassicOnChipQ16: SEARCH_CASE(NB_, RS_, TAIL_, kWalkClassicOnChipQ16, true); break;             \
+    case SearchWalk::ClassicOnChipIds: SEARCH_CASE(NB_, RS_, TAIL_, kWalkClassicOnChipIds, true); break;             \
+    case SearchWalk::ClassicBitmap: SEARCH_CASE(NB_, RS_, TAIL_, kWalkClassic, true); break;
 #else
-#define IDIST_VARIANT_SEARCH_ONCHIP_Q16(NB_, RS_, TAIL_)
-#define IDIST_VARIANT_SEARCH_ONCHIP_IDS(NB_, RS_, TAIL_)
-#define IDIST_VARIANT_SEARCH_BITMAP(NB_, RS_, TAIL_)
+#define IDIST_VARIANT_SEARCH_CASES(NB_, RS_, TAIL_)
 #endif
     bool launched = true;
-#define LAUNCH_SEARCH(NB_, RS_, TAIL_)                                                             \
-    {                                                                                              \
-        if (quad && q16) {                                                                         \
-            auto kS = search_kernel<NB_, RS_, TAIL_, walk_code(kWalkOverlap, 0, false, 1, true, true, true)>; \
-            IDIST_LAUNCH(kS, grid, 256, smem, stream, view, a);                                    \
-        } else if (quad) {                                                                         \
-            auto kS = search_kernel<NB_, RS_, TAIL_, walk_code(kWalkOverlap, 0, false, 1, true, true)>; \
-            IDIST_LAUNCH(kS, grid, 256, smem, stream, view, a);                                    \
-        } else if (thin && principal && fw == 3u) {                                                \
-            launched = SearchLaunch<NB_, RS_, TAIL_, walk_thin_filter_principal(3), GeoKernels<NB_>::thin_search && kPrincipalWaves3>::go(grid, smem, stream, view, a); \
-        } else if (thin && principal && inlined) {                                                 \
-            launched = SearchLaunch<NB_, RS_, TAIL_, walk_thin_filter_inline(2), GeoKernels<NB_>::thin_search>::go(grid, smem, stream, view, a); \
-        } else if (thin && principal) {                                                            \
-            launched = SearchLaunch<NB_, RS_, TAIL_, walk_thin_filter_principal(2), GeoKernels<NB_>::thin_search>::go(grid, smem, stream, view, a); \
-        } else if (thin) {                                                                         \
-            launched = SearchLaunch<NB_, RS_, TAIL_, walk_thin_filter(2), GeoKernels<NB_>::thin_search>::go(grid, smem, stream, view, a); \
-        } IDIST_VARIANT_SEARCH_ONCHIP_Q16(NB_, RS_, TAIL_) else if (w2) {                          \
-            auto kS = search_kernel<NB_, RS_, TAIL_, walk_code(kWalkOverlap, (NB_) == 24 ? 1 : ((NB_) == 4 ? 6 : 3), false, 2, true, false, true)>; \
-            IDIST_LAUNCH(kS, grid, 64, smem, stream, view, a);                                     \
-        } else if (on_chip && fat_filtered && !q16) {                                              \
-            launched = SearchLaunch<NB_, RS_, TAIL_, walk_with_filter(walk_code(kWalkOverlap, 0, false, 1, true)), GeoKernels<NB_>::fat_filtered_search_ids>::go(grid, smem, stream, view, a); \
-        } else if (on_chip && fat_filtered) {                                                      \
-            launched = SearchLaunch<NB_, RS_, TAIL_, walk_with_filter(walk_code(kWalkOverlap, 0, false, 1, true, false, true)), GeoKernels<NB_>::fat_filtered_search>::go(grid, smem, stream, view, a); \
-        } else if (on_chip && q16) {                                                               \
-            auto kS = search_kernel<NB_, RS_, TAIL_, walk_code(kWalkOverlap, 0, false, 1, true, false, true)>; \
-            IDIST_LAUNCH(kS, grid, 64, smem, stream, view, a);                                     \
-        } IDIST_VARIANT_SEARCH_ONCHIP_IDS(NB_, RS_, TAIL_) else if (on_chip) {                     \
-            auto kS = search_kernel<NB_, RS_, TAIL_, walk_code(kWalkOverlap, 0, false, 1, true)>;  \
-            IDIST_LAUNCH(kS, grid, 64, smem, stream, view, a);                                     \
-        } else if (lat) {                                                                          \
-            auto kS = search_kernel<NB_, RS_, TAIL_, kWalkLatency>;                                \
-            IDIST_LAUNCH(kS, grid, 64, smem, stream, view, a);                                     \
-        } IDIST_VARIANT_SEARCH_BITMAP(NB_, RS_, TAIL_) else {                                      \
-            auto kS = search_kernel<NB_, RS_, TAIL_, kWalkOverlap>;                                \
-            IDIST_LAUNCH(kS, grid, 64, smem, stream, view, a);                                     \
-        }                                                                                          \
+    // (ON_ = false: this geometry is never given that walk and has no instantiation of it — reaching it is the internal error below)
+#define SEARCH_CASE(NB_, RS_, TAIL_, WALK_, ON_) launched = SearchLaunch<NB_, RS_, TAIL_, WALK_, ON_>::go(grid, plan.block, smem, stream, view, a)
+#define LAUNCH_SEARCH(NB_, RS_, TAIL_)                                                                                                 \
+    switch (plan.walk) {                                                                                                               \
+        case SearchWalk::QuadQ16: SEARCH_CASE(NB_, RS_, TAIL_, kWalkFourWaveQ16, true); break;                                         \
+        case SearchWalk::QuadIds: SEARCH_CASE(NB_, RS_, TAIL_, kWalkFourWaveIds, true); break;                                         \
+        case SearchWalk::ThinPrincipal3: SEARCH_CASE(NB_, RS_, TAIL_, walk_thin_filter_principal(3), GeoKernels<NB_>::thin_search && kPrincipalWaves3); break; \
+        case SearchWalk::ThinInline: SEARCH_CASE(NB_, RS_, TAIL_, walk_thin_filter_inline(2), GeoKernels<NB_>::thin_search); break;    \
+        case SearchWalk::ThinPrincipal: SEARCH_CASE(NB_, RS_, TAIL_, walk_thin_filter_principal(2), GeoKernels<NB_>::thin_search); break; \
+        case SearchWalk::ThinIdentity: SEARCH_CASE(NB_, RS_, TAIL_, walk_thin_filter(2), GeoKernels<NB_>::thin_search); break;         \
+        case SearchWalk::TwoPerSimd: SEARCH_CASE(NB_, RS_, TAIL_, walk_two_per_simd(NB_), true); break;                                \
+        case SearchWalk::FatFilteredIds: SEARCH_CASE(NB_, RS_, TAIL_, walk_with_filter(kWalkFatIds), GeoKernels<NB_>::fat_filtered_search_ids); break; \
+        case SearchWalk::FatFilteredQ16: SEARCH_CASE(NB_, RS_, TAIL_, walk_with_filter(kWalkFatQ16), GeoKernels<NB_>::fat_filtered_search); break; \
+        case SearchWalk::OnChipQ16: SEARCH_CASE(NB_, RS_, TAIL_, kWalkFatQ16, true); break;                                            \
+        case SearchWalk::OnChipIds: SEARCH_CASE(NB_, RS_, TAIL_, kWalkFatIds, true); break;                                            \
+        case SearchWalk::Latency: SEARCH_CASE(NB_, RS_, TAIL_, kWalkLatency, true); break;                                             \
+        case SearchWalk::OverlapBitmap: SEARCH_CASE(NB_, RS_, TAIL_, kWalkOverlap, true); break;                                       \
+        IDIST_VARIANT_SEARCH_CASES(NB_, RS_, TAIL_)                                                                                    \
+        default: launched = false; break;                                                                                              \
     }
 #ifdef IDIST_EA_PROBE
     // measurement build: wide 300-d batches on the id set with partial-distance early abandon after k blocks (dist_rounds_inflight)
-    if (on_chip && !quad && !q16 && !classic && ctx->knobs.ea > 0 && ix->L.nb == 9 && ix->L.rs == 1 && ix->L.tail == 1) {
+    if (plan.walk == SearchWalk::OnChipIds && knobs.ea > 0 && ix->L.nb == 9 && ix->L.rs == 1 && ix->L.tail == 1) {
 #define EA_CASE(K_)                                                                                   \
     case K_: {                                                                                        \
-        auto kS = search_kernel<9, 1, 1, walk_with_ea(walk_code(kWalkOverlap, 0, false, 1, true), K_)>; \
+        auto kS = search_kernel<9, 1, 1, walk_with_ea(kWalkFatIds, K_)>;                              \
         IDIST_LAUNCH(kS, grid, 64, smem, stream, view, a);                                            \
         break;                                                                                        \
     }
-        switch (ctx->knobs.ea) {
+        switch (knobs.ea) {
             EA_CASE(4) EA_CASE(5) EA_CASE(6) EA_CASE(7)
-            default: return fail(IDIST_ERR_INVALID_ARG, "IDIST_EA=%d: 4..7", ctx->knobs.ea);
+            default: return fail(IDIST_ERR_INVALID_ARG, "IDIST_EA=%d: 4..7", knobs.ea);
         }
 #undef EA_CASE
     } else
 #endif
     IDIST_DISPATCH(ix->L, LAUNCH_SEARCH);
 #undef LAUNCH_SEARCH
-    if (!launched) return fail(IDIST_ERR_INTERNAL, "no filtered search kernel for this row geometry (stride %u)", ix->L.stride);
+#undef SEARCH_CASE
+#undef IDIST_VARIANT_SEARCH_CASES
+    if (!launched) return fail(IDIST_ERR_INTERNAL, "no search kernel for the walk %s at this row geometry (stride %u)", walk_name(plan.walk), ix->L.stride);
     if (const hipError_t le = hipGetLastError(); le != hipSuccess) {
         // nothing ran: put the queue head back where a fresh context has it
         hipMemsetAsync(ctx->d_next, 0, 4, stream);
@@ -2163,7 +1963,7 @@ idist_status launch_search(const idist_index* ix, idist_search_ctx* ctx, const f
         return fail(IDIST_ERR_HIP, "search launch failed: %s", hipGetErrorString(le));
     }
     ctx->queue_base += nq + grid;
-    if (ctx->knobs.events) {
+    if (knobs.events) {
         HIPCHK(hipEventRecord(ctx->ev1[slot], stream));
         ctx->n_launch++;
         ctx->recs[ctx->n_rec++ % IDIST_EVENT_RING] = {(int32_t)slot, 0.0f};
@@ -2441,7 +2241,7 @@ idist_status idist_search_ctx_new(const idist_index* idx, uint32_t slots, idist_
     c->idx_uid = idx->uid;
     c->slots_req = slots;
     c->vis = vis_geometry(idx->n);
-    c->knobs = Knobs::from_env();
+    c->knobs = knobs_from_env();
     c->tie_policy = idx->cfg.tie_policy;
     c->base_tie_cap = tie_capacity(idx->cfg);
     c->n_points = idx->n;
@@ -2499,7 +2299,7 @@ idist_status idist_search_ctx_reserve(idist_search_ctx* ctx, uint32_t slots) {
     return IDIST_OK;
 }
 
-// prepared: see launch_search (the partitioned search hands in what the kernels read and reports the distances after its merge)
+// prepared: see SearchOpts (the partitioned search hands in what the kernels read and reports the distances after its merge)
 static idist_status search_batch_device_impl(const idist_index* idx, idist_search_ctx* ctx, const void* d_queries,
                                              uint32_t nq, void* d_out_pid, void* d_out_dist, void* d_out_count,
                                              void* d_out_counters, void* hip_stream, bool prepared) {
@@ -2513,8 +2313,10 @@ static idist_status search_batch_device_impl(const idist_index* idx, idist_searc
         return IDIST_OK;
     }
     if (!d_out_pid || !d_out_dist) return fail(IDIST_ERR_INVALID_ARG, "null device pointer");
+    SearchOpts opts;
+    opts.prepared = prepared;
     return launch_search(idx, ctx, (const float*)d_queries, nq, (uint32_t*)d_out_pid, (float*)d_out_dist,
-                         (uint32_t*)d_out_count, (uint32_t*)d_out_counters, stream, nullptr, nullptr, nullptr, 0, prepared);
+                         (uint32_t*)d_out_count, (uint32_t*)d_out_counters, stream, opts);
 }
 
 idist_status idist_search_batch_device(const idist_index* idx, idist_search_ctx* ctx, const void* d_queries,
@@ -2718,10 +2520,14 @@ static idist_status search_batch_impl(const idist_index* idx, idist_search_ctx* 
             const bool flag = ctx->knobs.sync_flag;
             const uint32_t seq = ++ctx->done_seq ? ctx->done_seq : ++ctx->done_seq;       // never 0: a fresh buffer reads 0
             const auto t0 = std::chrono::steady_clock::now();
+            SearchOpts opts;
+            opts.status_host = (uint32_t*)((uint8_t*)h_status + dv);
+            opts.grid_out = &grid;
+            opts.done_host = flag ? (uint32_t*)((uint8_t*)h_done + dv) : nullptr;
+            opts.done_seq = seq;
             CHK(launch_search(idx, ctx, (const float*)((uint8_t*)h_q + dv), nq, (uint32_t*)((uint8_t*)h_pid + dv),
                               (float*)((uint8_t*)h_dist + dv), (uint32_t*)((uint8_t*)h_cnt + dv),
-                              out_counters ? (uint32_t*)((uint8_t*)h_ctr + dv) : nullptr, ctx->stream,
-                              (uint32_t*)((uint8_t*)h_status + dv), &grid, flag ? (uint32_t*)((uint8_t*)h_done + dv) : nullptr, seq));
+                              out_counters ? (uint32_t*)((uint8_t*)h_ctr + dv) : nullptr, ctx->stream, opts));
             if (flag) {
                 // The kernel's last workgroup writes `seq` into the pinned buffer behind its results.  One Search per thread
                 // is the reference's model, so waiting must not burn a core per thread: sleep through the first half of what
@@ -3857,8 +3663,12 @@ idist_status ladder_rung(const idist_index* idx, idist_search_ctx* ctx, const fl
     CHK(ctx->d_ctr.grow((size_t)np * 12));
     for (;;) {
         bool lds_short = false;
+        SearchOpts opts;
+        opts.prepared = true;
+        opts.ef = ef;
+        opts.lds_short = &lds_short;
         const idist_status ls = launch_search(idx, ctx, d_pq, np, ctx->d_pid, ctx->d_dist, ctx->d_cnt, counters ? ctx->d_ctr.p : nullptr,
-                                              ctx->stream, nullptr, nullptr, nullptr, 0, true, ef, &lds_short);
+                                              ctx->stream, opts);
         if (ls != IDIST_OK) {
             // a later rung that does not fit a wave's LDS ends the ladder as max_rungs would; rung 0 fails as idist_search_batch does
             if (lds_short && r != 0) { *ended = true; return IDIST_OK; }

@@ -680,6 +680,21 @@ constexpr int walk_thin_filter_principal(int waves = 2) { return walk_thin_filte
 constexpr int kWalkInlineBit = 1 << 22;
 constexpr bool walk_inline(int code) { return (code & kWalkInlineBit) != 0; }
 constexpr int walk_thin_filter_inline(int waves = 2) { return walk_thin_filter_principal(waves) | kWalkInlineBit; }
+// The unfiltered walks on the on-chip set, by name (the policy that picks among them: idist_search_plan.hpp; the descents: run_build).
+// One wave per SIMD unless the name says otherwise; Ids / Q16: the set keeps full ids / 16-bit quotients.
+constexpr int kWalkFatIds = walk_code(kWalkOverlap, 0, false, 1, true);
+constexpr int kWalkFatQ16 = walk_code(kWalkOverlap, 0, false, 1, true, false, true);
+constexpr int kWalkFourWaveIds = walk_code(kWalkOverlap, 0, false, 1, true, true);             // a four-wave workgroup per walk
+constexpr int kWalkFourWaveQ16 = walk_code(kWalkOverlap, 0, false, 1, true, true, true);
+constexpr int kWalkClassicOnChipIds = walk_code(kWalkClassic, 0, false, 1, true);              // (test builds, build_extend_kernel)
+constexpr int kWalkClassicOnChipQ16 = walk_code(kWalkClassic, 0, false, 1, true, false, true);
+// two 256-register waves per SIMD on the quotient set, rounds in flight by what the registers of geometry NB leave
+constexpr int walk_two_per_simd(int NB) { return walk_code(kWalkOverlap, NB == 24 ? 1 : (NB == 4 ? 6 : 3), false, 2, true, false, true); }
+// (a walk code is a template argument of its kernel: these integers are part of the kernels' symbols, as profiles/ names them)
+static_assert(kWalkFatIds == 4610 && kWalkFatQ16 == 6658 && kWalkFourWaveIds == 5634 && kWalkFourWaveQ16 == 7682 &&
+              kWalkClassicOnChipIds == 4608 && kWalkClassicOnChipQ16 == 6656, "walk codes changed: other kernel symbols");
+static_assert(walk_two_per_simd(24) == 10770 && walk_two_per_simd(4) == 10850 && walk_two_per_simd(9) == 10802 && walk_two_per_simd(-1) == 10802,
+              "walk codes changed: other kernel symbols");
 constexpr uint32_t kInlineBlockBytes = 64u * 64u;
 // An inlined kernel decides ONCE per query which table serves it and runs the layers in one of two instantiations of search_layer
 // (bits 23 / 24, never a kernel's own code): in the principal one the identity form of the query is dead, which is what pays for the

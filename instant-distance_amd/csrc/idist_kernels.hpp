@@ -905,7 +905,7 @@ __global__ __launch_bounds__(64) void build_extend_kernel(IndexView ix, BuildArg
     uint64_t* W2 = reinterpret_cast<uint64_t*>(q2 + ix.stride);                      // the `insertion` Search's nearest
     uint64_t* own = W2 + ((a.wcap + 1u) & ~1u);                                      // `found`, :465-472
     const int lane = lane_id();
-    constexpr int LAT = walk_code(kWalkClassic, 0, false, 1, true);
+    constexpr int LAT = kWalkClassicOnChipIds;
     Visited vis{a.visited, ix.n, sm.dirty, a.vis.shift, a.vis.dirty_words, nullptr, 0};
     visited_attach_tab(vis, sm.bloom, a.tab_log2);
     for (uint32_t i = lane; i < a.vis.dirty_words; i += 64) sm.dirty[i] = 0u;
