@@ -731,9 +731,9 @@ idist_status idist_range_merge_device(const void* const* d_keys, const void* con
  * construction the slice of the global bitmap.  Staging: |D| * ((n + 31) / 32) * 4 bytes per context (per part: n_p for n), nothing
  * of the size of n crosses PCIe; an allocation that fails is returned as IDIST_ERR_HIP, nothing is truncated.
  * Host pointers; blocks until done; ctx / p are the `&mut Search` as in the bitmap calls.
- * Out of scope: conditions over several attributes or unions of intervals (make the bitmaps and use the bitmap calls), testing the
- * attribute inside the select / scan kernels instead of through bitmaps, device-pointer / stream variants and
- * idist_search_batch_sharded. */
+ * Conditions over several attributes and unions of intervals: the attribute tables below.
+ * Out of scope: testing the attribute inside the select / scan kernels instead of through bitmaps, device-pointer / stream variants
+ * and idist_search_batch_sharded. */
 typedef struct idist_attr idist_attr;
 idist_status idist_attr_new(const idist_index* idx, const uint32_t* values /* [n], PointId order */, idist_attr** out);
 idist_status idist_partitioned_attr_new(const idist_partitioned* p, const uint32_t* values /* [N], global-id order */, idist_attr** out);
@@ -775,6 +775,80 @@ idist_status idist_search_ctx_attr_bitmap_ms(idist_search_ctx* ctx, float* ms);
  * synchronising. */
 idist_status idist_attr_bitmaps_device(const void* d_values, uint32_t n, const void* d_lo, const void* d_hi, uint32_t n_sets,
                                        void* d_out, int32_t device, void* hip_stream);
+
+/* ---- attribute tables: several u32 columns per point, AND / OR conditions per query ------------------------- */
+/* Real filters are "tenant = 7 AND day in [100, 200]" or "category in {3, 17, 42}": several attributes, unions of intervals.  An
+ * idist_attr is a TABLE of n_cols columns (1 to 64; anything else is IDIST_ERR_INVALID_ARG); idist_attr_new is its n_cols == 1 case.
+ *   values      [n_cols][n] u32, column after column, column 0 first: column c is values + c * n, in PointId order (partitioned:
+ *               [n_cols][N], global-id order; every non-empty part holds [n_cols][n_p], its slice of every column, on its own device).
+ *               n == 0 stays legal (values may be NULL).  Binding, immutability, sharing and idist_attr_free: as above.
+ *   the interval calls above accept a table and test COLUMN 0; given a one-column attribute they launch exactly what they launched.
+ *   a clause    {col, lo, hi}: lo <= values[col][i] && values[col][i] <= hi, UNSIGNED (lo > hi: the empty clause).
+ *   a condition an OR of conjunctions, a conjunction an AND of clauses (DNF): conjunction j = the clauses [and_lims[j], and_lims[j + 1])
+ *               — none: TRUE; condition c = the conjunctions [or_lims[c], or_lims[c + 1]) — none: FALSE.  The same column may appear
+ *               more than once in a conjunction (an intersection), conjunctions may overlap, "not equal to x" is the two conjunctions
+ *               [0, x - 1] and [x + 1, 0xFFFFFFFF]: there is no NOT.  No cap on clauses or conjunctions beyond the u32 limits.
+ *   n_cond      1: one condition for the whole batch; nq: one per query — as n_radius.  nq == 0 is no error.
+ * IDIST_ERR_INVALID_ARG: n_cond neither 1 nor nq; a null conds, and_lims or or_lims (clauses may be NULL when there is none);
+ * and_lims[0] or or_lims[0] not 0; a lims array that decreases (the message names the entry); a clause whose col >= n_cols (the
+ * message names the condition and the clause).
+ * DEFINITION: let bits[c] be the bitmap of condition c (bit i = the condition evaluated on point i, the bits at positions >= n
+ * zero).  Every output of a call below equals, bit for bit, the output of the bitmap call it is listed with given
+ * (bits, n_cond, set_of = NULL) — with n_cond == 1: one set and set_of all zero:
+ *   idist_search_batch_match                     idist_search_batch_allowed_sets
+ *   idist_search_batch_range_match               idist_search_batch_range_allowed_sets       (results: idist_search_ctx_range_fetch)
+ *   idist_partitioned_search_batch_match         idist_partitioned_search_batch_allowed_sets, bitmaps over the global ids
+ *   idist_partitioned_search_batch_range_match   idist_partitioned_search_batch_range_allowed_sets  (idist_partitioned_range_fetch)
+ * and everything else comes from those calls, as for the interval calls, which are the special case of one conjunction of one
+ * clause {0, lo, hi}.
+ * The conditions are grouped on the host: conditions that are equal as encoded — and those that differ only in the order of the
+ * clauses within a conjunction — share one bitmap, D being the distinct ones; set_of and D as one flat program are uploaded; one
+ * kernel on the context's stream evaluates the program over the columns into the |D| bitmaps where the restricted search reads
+ * them (idist_search_ctx_attr_bitmap_ms; the parts, summed: idist_partitioned_last_allowed_slice_ms), every part over its own
+ * slice on its own stream.  Staging: |D| * ((n + 31) / 32) * 4 bytes per context, never nq bitmaps when the conditions repeat; an
+ * allocation that fails is IDIST_ERR_HIP, nothing is truncated.  Host pointers; blocks until done.
+ * Out of scope: NOT, testing the attributes inside the select / scan kernels, device-pointer / stream variants and
+ * idist_search_batch_sharded. */
+typedef struct idist_attr_clause { uint32_t col, lo, hi; } idist_attr_clause;   /* lo <= v[col][i] && v[col][i] <= hi, UNSIGNED */
+typedef struct idist_attr_conds {
+    const idist_attr_clause* clauses; /* [and_lims[n_and]]; may be NULL when there is none */
+    const uint32_t* and_lims;         /* [n_and + 1], and_lims[0] = 0, non-decreasing: conjunction j = AND of clauses [and_lims[j], and_lims[j + 1]); none: TRUE */
+    const uint32_t* or_lims;          /* [n_cond + 1], or_lims[0] = 0, non-decreasing; n_and = or_lims[n_cond]: condition c = OR of conjunctions [or_lims[c], or_lims[c + 1]); none: FALSE */
+    uint32_t n_cond;                  /* 1: one condition for the batch; nq: one per query (as n_radius) */
+} idist_attr_conds;
+/* values [n_cols][n]: column c is values + c * n, PointId order (partitioned: [n_cols][N], global-id order) */
+idist_status idist_attr_new_columns(const idist_index* idx, const uint32_t* values, uint32_t n_cols, idist_attr** out);
+idist_status idist_partitioned_attr_new_columns(const idist_partitioned* p, const uint32_t* values, uint32_t n_cols, idist_attr** out);
+idist_status idist_search_batch_match(const idist_index* idx, idist_search_ctx* ctx, const idist_attr* attr, const float* queries, uint32_t nq,
+                                      const idist_attr_conds* conds, uint32_t k, int32_t max_rungs,
+                                      uint32_t* out_pid, float* out_dist,      /* nq*k */
+                                      uint32_t* out_count, uint32_t* out_rung, /* nq; out_rung may be NULL */
+                                      uint32_t* out_counters);                 /* nq*3 or NULL */
+idist_status idist_search_batch_range_match(const idist_index* idx, idist_search_ctx* ctx, const idist_attr* attr, const float* queries,
+                                            uint32_t nq, const float* radius, uint32_t n_radius, const idist_attr_conds* conds,
+                                            int32_t max_rungs, uint64_t max_total,
+                                            uint64_t* out_lims, uint32_t* out_rung, uint32_t* out_counters);
+idist_status idist_partitioned_search_batch_match(idist_partitioned* p, const idist_attr* attr, const float* queries, uint32_t nq,
+                                                  const idist_attr_conds* conds, uint32_t k, int32_t max_rungs,
+                                                  uint32_t* out_pid, float* out_dist,      /* nq*k, global ids */
+                                                  uint32_t* out_count,                     /* nq */
+                                                  uint32_t* out_rung,                      /* [nq][n_parts] or NULL */
+                                                  uint32_t* out_counters);                 /* nq*3 or NULL */
+idist_status idist_partitioned_search_batch_range_match(idist_partitioned* p, const idist_attr* attr, const float* queries, uint32_t nq,
+                                                        const float* radius, uint32_t n_radius, const idist_attr_conds* conds,
+                                                        int32_t max_rungs, uint64_t max_total,
+                                                        uint64_t* out_lims,        /* nq + 1 */
+                                                        uint32_t* out_rung,        /* [nq][n_parts] or NULL */
+                                                        uint32_t* out_counters);   /* nq*3 or NULL */
+/* The kernel on its own: d_values [n_cols][col_pitch] (col_pitch >= n: elements between columns), the program of n_sets conditions in
+ * device memory (d_clauses [.][3] u32 as idist_attr_clause, d_and_lims, d_or_lims [n_sets + 1]; d_clauses may be NULL for a program
+ * without clauses), d_out [n_sets][(n + 31) / 32].  The contract of idist_attr_bitmaps_device: every output word written exactly
+ * once, the same bytes whatever the grid, the bits at positions >= n zero, no column read past its element n - 1, nothing written
+ * past a row's last word; n == 0 or n_sets == 0: nothing is done.  The program is the caller's: its limits are not checked, and a
+ * clause whose col >= n_cols matches nothing.  Enqueued on hip_stream without synchronising, as idist_attr_bitmaps_device. */
+idist_status idist_attr_match_bitmaps_device(const void* d_values, uint32_t n, uint32_t n_cols, uint64_t col_pitch,
+                                             const void* d_clauses, const void* d_and_lims, const void* d_or_lims, uint32_t n_sets,
+                                             void* d_out, int32_t device, void* hip_stream);
 
 /* Point::distance for id lists (core/lib.rs:780-782 as used at :709-710): out[q][i] =
  * distance(queries[q], points[ids[q][i]]) for i < n_ids; IDIST_INVALID ids give +inf.

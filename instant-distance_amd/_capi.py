@@ -96,11 +96,20 @@ class PartitionedInfo(C.Structure):
     ]
 
 
+class AttrConds(C.Structure):
+    """idist_attr_conds: `clauses` is [n][3] uint32 (col, lo, hi), the layout of idist_attr_clause"""
+    _fields_ = [
+        ("clauses", C.POINTER(C.c_uint32)), ("and_lims", C.POINTER(C.c_uint32)), ("or_lims", C.POINTER(C.c_uint32)),
+        ("n_cond", C.c_uint32),
+    ]
+
+
 # every symbol include/idist.h declares: name -> (restype, argtypes)
 _f32p = C.POINTER(C.c_float)
 _u32p = C.POINTER(C.c_uint32)
 _u64p = C.POINTER(C.c_uint64)
 _vp = C.c_void_p
+_condsp = C.POINTER(AttrConds)
 SYMBOLS = {
     "idist_last_error": (C.c_char_p, []),
     "idist_version": (C.c_char_p, []),
@@ -182,6 +191,16 @@ SYMBOLS = {
                                                               C.c_int32, C.c_uint64, _u64p, _u32p, _u32p]),
     "idist_search_ctx_attr_bitmap_ms": (C.c_int32, [_vp, C.POINTER(C.c_float)]),
     "idist_attr_bitmaps_device": (C.c_int32, [_vp, C.c_uint32, _vp, _vp, C.c_uint32, _vp, C.c_int32, _vp]),
+    "idist_attr_new_columns": (C.c_int32, [_vp, _u32p, C.c_uint32, C.POINTER(_vp)]),
+    "idist_partitioned_attr_new_columns": (C.c_int32, [_vp, _u32p, C.c_uint32, C.POINTER(_vp)]),
+    "idist_search_batch_match": (C.c_int32, [_vp, _vp, _vp, _f32p, C.c_uint32, _condsp, C.c_uint32, C.c_int32, _u32p, _f32p, _u32p, _u32p, _u32p]),
+    "idist_search_batch_range_match": (C.c_int32, [_vp, _vp, _vp, _f32p, C.c_uint32, _f32p, C.c_uint32, _condsp, C.c_int32, C.c_uint64, _u64p,
+                                                   _u32p, _u32p]),
+    "idist_partitioned_search_batch_match": (C.c_int32, [_vp, _vp, _f32p, C.c_uint32, _condsp, C.c_uint32, C.c_int32, _u32p, _f32p, _u32p, _u32p,
+                                                         _u32p]),
+    "idist_partitioned_search_batch_range_match": (C.c_int32, [_vp, _vp, _f32p, C.c_uint32, _f32p, C.c_uint32, _condsp, C.c_int32, C.c_uint64,
+                                                               _u64p, _u32p, _u32p]),
+    "idist_attr_match_bitmaps_device": (C.c_int32, [_vp, C.c_uint32, C.c_uint32, C.c_uint64, _vp, _vp, _vp, C.c_uint32, _vp, C.c_int32, _vp]),
     "idist_distance_batch": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, _f32p]),
     "idist_filter_bound_batch": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, _f32p]),
     "idist_bruteforce": (C.c_int32, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),

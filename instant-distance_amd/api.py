@@ -21,6 +21,7 @@ All compute goes through the C ABI (include/idist.h); there is no CPU path.
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 import secrets
 from dataclasses import dataclass
 from typing import Any, Iterator, Sequence
@@ -497,6 +498,140 @@ def _attr_values(values, n: int) -> np.ndarray:
     return np.ascontiguousarray(v)
 
 
+class AttrTable(Attr):
+    """Several uint32 columns per point on the device (idist_attr_new_columns): what `search_match` / `search_range_match` evaluate
+    a query's condition over.  Made by `attribute_table`.  `names`: the columns in order; `columns`: name -> the uint32 host copy
+    [n]; `values`: column 0, the one `search_where` / `search_range_where` read when they are given a table."""
+
+    def __init__(self, handle, owner, names: list, cols: np.ndarray):
+        super().__init__(handle, owner, cols[0] if len(names) else np.zeros(cols.shape[1], np.uint32))
+        self.names = list(names)
+        self.n_cols = len(self.names)
+        self.columns = {name: cols[i] for i, name in enumerate(self.names)}
+        self._n = int(cols.shape[1])
+
+    def __len__(self):
+        return self._n
+
+
+def _table_columns(columns, n: int) -> tuple[list, np.ndarray]:
+    """`columns` of `attribute_table` as (names, uint32 [n_cols][n], column after column): a dict name -> integer array [n], or an
+    integer array [n, n_cols] whose columns are named "0", "1", ...; the checks of `attributes()` per column."""
+    if isinstance(columns, dict):
+        names = list(columns)
+        if not all(isinstance(name, str) for name in names):
+            raise TypeError("the columns of an attribute table are named by strings")
+        cols = [_attr_values(columns[name], n) for name in names]
+        return names, (np.ascontiguousarray(np.stack(cols)) if cols else np.zeros((0, n), np.uint32))
+    a = _as_u32(columns, "columns")
+    if a.ndim != 2 or a.shape[0] != n:
+        raise ValueError(f"`columns` is a dict of arrays [{n}] or one array [{n}, n_cols], got shape {a.shape}")
+    return [str(i) for i in range(a.shape[1])], np.ascontiguousarray(a.T)
+
+
+class AnyOf:
+    """The OR of conjunctions in a `search_match` condition: AnyOf(d1, d2, ...) with every d a dict as `search_match` takes it.
+    AnyOf() is FALSE; a plain dict d is AnyOf(d); {} is TRUE."""
+
+    def __init__(self, *conjunctions):
+        if not all(isinstance(d, dict) for d in conjunctions):
+            raise TypeError("AnyOf takes dicts: column name -> an int, a (lo, hi) tuple or a list / set / array of values")
+        self.conjunctions = tuple(conjunctions)
+
+    def __repr__(self):
+        return "AnyOf(" + ", ".join(repr(d) for d in self.conjunctions) + ")"
+
+
+MAX_CONJUNCTIONS = 4096      # of one condition, after its membership lists have been multiplied out
+
+
+def _is_int(x) -> bool:
+    return isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
+
+
+def _u32_scalar(x, what: str) -> int:
+    if not _is_int(x):
+        raise TypeError(f"`{what}` is an integer, got {type(x).__name__}")
+    if not 0 <= int(x) <= 0xFFFFFFFF:
+        raise ValueError(f"`{what}` = {x} is outside the uint32 range [0, 2**32)")
+    return int(x)
+
+
+def _intervals(spec, name) -> list[tuple[int, int]]:
+    """what a column of a conjunction maps to, as intervals: an int (equality), a (lo, hi) tuple, or a list / set / integer array
+    (membership: sorted, duplicates dropped, runs of consecutive values merged)"""
+    if _is_int(spec):
+        v = _u32_scalar(spec, name)
+        return [(v, v)]
+    if isinstance(spec, tuple):
+        if len(spec) != 2:
+            raise ValueError(f"column {name!r}: an interval is a tuple (lo, hi); a list or set is a membership test")
+        return [(_u32_scalar(spec[0], f"{name} lo"), _u32_scalar(spec[1], f"{name} hi"))]
+    if isinstance(spec, (list, set, frozenset, np.ndarray)):
+        a = _as_u32(list(spec) if not isinstance(spec, np.ndarray) else spec, name)
+        if a.ndim != 1:
+            raise ValueError(f"column {name!r}: a membership test is a flat list of values, got shape {a.shape}")
+        u = np.unique(a).astype(np.int64)
+        if u.size == 0:
+            return []
+        cut = np.flatnonzero(np.diff(u) > 1)
+        first, last = np.concatenate(([0], cut + 1)), np.concatenate((cut, [u.size - 1]))
+        return [(int(u[i]), int(u[j])) for i, j in zip(first, last)]
+    raise TypeError(f"column {name!r}: an int, a (lo, hi) tuple or a list / set / array of values, got {type(spec).__name__}")
+
+
+def encode_conds(conds, names, nq: int) -> tuple[np.ndarray, np.ndarray, np.ndarray, int]:
+    """The conditions of `search_match` as idist_attr_conds takes them: (clauses uint32 [m, 3] of (col, lo, hi), and_lims, or_lims,
+    n_cond).  `conds`: one dict / AnyOf for the batch (n_cond 1) or a list / tuple of nq of them; `names`: the table's column names in
+    order.  A dict is one conjunction, column name -> an int (equality), a (lo, hi) tuple, or a list / set / integer array
+    (membership, as merged intervals); several memberships in one dict expand to their Cartesian product, at most MAX_CONJUNCTIONS
+    conjunctions per condition.  A pure function of its arguments: no index, no device."""
+    col_of = {name: i for i, name in enumerate(names)}
+    if isinstance(conds, (dict, AnyOf)):
+        per_query, n_cond = [conds], 1
+    elif isinstance(conds, (list, tuple)):
+        if len(conds) != nq:
+            raise ValueError(f"`conds` is one dict / AnyOf for the batch or a list of nq = {nq} of them, got {len(conds)}")
+        per_query, n_cond = list(conds), nq
+    else:
+        raise TypeError(f"`conds` is a dict, an AnyOf or a list of them, got {type(conds).__name__}")
+    clauses, and_lims, or_lims = [], [0], [0]
+    done = {}                                              # the same object again (a list that repeats a few conditions): encoded once
+    for cond in per_query:
+        if id(cond) not in done:
+            if not isinstance(cond, (dict, AnyOf)):
+                raise TypeError(f"a condition is a dict or an AnyOf, got {type(cond).__name__}")
+            conjs = []
+            for d in (cond,) if isinstance(cond, dict) else cond.conjunctions:
+                cols, lists, count = [], [], 1
+                for name, spec in d.items():
+                    if name not in col_of:
+                        raise KeyError(name)
+                    cols.append(col_of[name])
+                    lists.append(_intervals(spec, name))
+                    count *= len(lists[-1])
+                if len(conjs) + count > MAX_CONJUNCTIONS:
+                    raise ValueError(f"a condition expands to more than {MAX_CONJUNCTIONS} conjunctions")
+                conjs += [[(c, lo, hi) for c, (lo, hi) in zip(cols, pick)] for pick in itertools.product(*lists)]
+            done[id(cond)] = conjs
+        for conj in done[id(cond)]:
+            clauses += conj
+            and_lims.append(len(clauses))
+        or_lims.append(len(and_lims) - 1)
+    if max(len(clauses), len(and_lims)) > 0xFFFFFFFF:
+        raise ValueError("the conditions of one call hold at most 2**32 - 1 clauses")
+    return (np.array(clauses, dtype=np.uint32).reshape(-1, 3), np.array(and_lims, dtype=np.uint32), np.array(or_lims, dtype=np.uint32), n_cond)
+
+
+def _conds_arg(table: "AttrTable", conds, nq: int):
+    """(the idist_attr_conds of a call, the arrays it points into)"""
+    if not isinstance(table, AttrTable):
+        raise TypeError("`table` is an AttrTable (attribute_table); for an Attr use search_where")
+    clauses, and_lims, or_lims, n_cond = encode_conds(conds, table.names, nq)
+    keep = (clauses, and_lims, or_lims)
+    return _capi.AttrConds(_capi.u32p(clauses), _capi.u32p(and_lims), _capi.u32p(or_lims), n_cond), keep
+
+
 def normalize(points, device: int = 0, return_norm2: bool = False):
     """x / sqrt(s(x)) per row, s = the canonical squared-L2 distance of the row to the origin (idist_normalize_batch): the rows a
     METRIC_COSINE index holds for `points`, bit for bit — an METRIC_L2SQ index over `normalize(points)` searched with
@@ -864,6 +999,71 @@ class Hnsw:
         L.check(L.idist_search_ctx_range_fetch(ctx, _capi.u32p(pid), _capi.f32p(dist)))
         return RangeResult(lims, pid, dist, rung, ctr)
 
+    def attribute_table(self, columns) -> AttrTable:
+        """Several uint32 columns per point (tenant, category, day ...), in PointId order, copied to the index's device once
+        (idist_attr_new_columns) for `search_match` / `search_range_match`.  `columns`: a dict name -> integer array [n], or an
+        integer array [n, n_cols] whose columns are named "0", "1", ...; the checks of `attributes()`."""
+        names, cols = _table_columns(columns, int(self.info().n))
+        h = C.c_void_p()
+        L = _lib()
+        L.check(L.idist_attr_new_columns(self._h, _capi.u32p(cols), len(names), C.byref(h)))
+        return AttrTable(h, self, names, cols)
+
+    def search_match(self, queries, table: AttrTable, conds, k: int = 10, search: Search | None = None, max_rungs: int = -1,
+                     counters: bool = False) -> AllowedResult:
+        """The k nearest among the points that satisfy the query's condition over the table's columns (idist_search_batch_match).
+        `conds`: one condition for the batch or a list of one per query.  A condition is a dict — one conjunction, column name ->
+        an int (equality), a (lo, hi) tuple (an interval, unsigned, lo > hi empty) or a list / set / integer array (membership) —
+        or `AnyOf(d1, d2, ...)`, the OR of such dicts; {} is TRUE, AnyOf() FALSE.  Row q is exactly what `search_allowed_sets`
+        returns for the mask of its condition, but the masks are made on the device from the columns that already live there."""
+        q = _as_points(queries)
+        info = self.info()
+        if q.shape[0] and info.n and q.shape[1] != info.dim:
+            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
+        nq, k = q.shape[0], int(k)
+        cs, _keep = _conds_arg(table, conds, nq)
+        kk = max(k, 0)
+        pid = np.full((nq, kk), INVALID, dtype=np.uint32)
+        dist = np.full((nq, kk), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        rung = np.full(nq, RUNG_NONE, dtype=np.uint32)
+        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
+        search = search if search is not None else Search()
+        ctx = search._bind(self)
+        L = _lib()
+        L.check(L.idist_search_batch_match(self._h, ctx, table._h, _capi.f32p(q), nq, C.byref(cs), kk, int(max_rungs), _capi.u32p(pid),
+                                           _capi.f32p(dist), _capi.u32p(cnt), _capi.u32p(rung), _capi.u32p(ctr) if counters else None))
+        return AllowedResult(pid, dist, cnt, rung, ctr)
+
+    def search_range_match(self, queries, radius, table: AttrTable, conds, search: Search | None = None, max_rungs: int = -1,
+                           max_total: int = 64 * 2**20, counters: bool = False) -> RangeResult:
+        """Every point within `radius` that satisfies the query's condition (idist_search_batch_range_match): row q is exactly what
+        `search_range_allowed_sets` returns for the mask of its condition; `radius`, `max_rungs`, `max_total` as in `search_range`,
+        `conds` as in `search_match`."""
+        q = _as_points(queries)
+        info = self.info()
+        if q.shape[0] and info.n and q.shape[1] != info.dim:
+            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
+        nq = q.shape[0]
+        rad = np.ascontiguousarray(np.asarray(radius, dtype=np.float32).reshape(-1))
+        if rad.size != 1 and rad.size != nq:
+            raise ValueError(f"`radius` is one float or an array of nq = {nq}, got {rad.size}")
+        cs, _keep = _conds_arg(table, conds, nq)
+        lims = np.zeros(nq + 1, dtype=np.uint64)
+        rung = np.full(nq, RUNG_NONE, dtype=np.uint32)
+        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
+        search = search if search is not None else Search()
+        ctx = search._bind(self)
+        L = _lib()
+        L.check(L.idist_search_batch_range_match(self._h, ctx, table._h, _capi.f32p(q), nq, _capi.f32p(rad), int(rad.size), C.byref(cs),
+                                                 int(max_rungs), int(max_total), _capi.u64p(lims), _capi.u32p(rung),
+                                                 _capi.u32p(ctr) if counters else None))
+        total = int(lims[nq])
+        pid = np.zeros(total, dtype=np.uint32)
+        dist = np.zeros(total, dtype=np.float32)
+        L.check(L.idist_search_ctx_range_fetch(ctx, _capi.u32p(pid), _capi.f32p(dist)))
+        return RangeResult(lims, pid, dist, rung, ctr)
+
     def search_batch_device(self, search: Search, d_queries: int, nq: int, d_pid: int, d_dist: int, d_count: int,
                             d_counters: int = 0, stream: int = 0):
         """Device-pointer variant: inputs/outputs stay in HBM, enqueued on `stream` without a sync."""
@@ -1023,6 +1223,22 @@ class HnswMap:
                            max_total: int = 64 * 2**20) -> list[list[MapItem]]:
         """`Hnsw.search_range_where` with the values: per query every result of its interval within its radius as `MapItem`s."""
         return self._range_items(self.hnsw.search_range_where(queries, radius, attr, lo, hi, search, max_rungs, max_total))
+
+    def attribute_table(self, columns) -> AttrTable:
+        """`Hnsw.attribute_table`: the columns in PointId order (the order of `self.values`)."""
+        return self.hnsw.attribute_table(columns)
+
+    def search_match(self, queries, table: AttrTable, conds, k: int = 10, search: Search | None = None,
+                     max_rungs: int = -1) -> list[list[MapItem]]:
+        """`Hnsw.search_match` with the values: per query its results as `MapItem`s, nearest first."""
+        r = self.hnsw.search_match(queries, table, conds, k, search, max_rungs)
+        return [[MapItem(float(r.distance[i, j]), int(r.pid[i, j]), self.hnsw.points[int(r.pid[i, j])], self.values[int(r.pid[i, j])])
+                 for j in range(int(r.count[i]))] for i in range(r.pid.shape[0])]
+
+    def search_range_match(self, queries, radius, table: AttrTable, conds, search: Search | None = None, max_rungs: int = -1,
+                           max_total: int = 64 * 2**20) -> list[list[MapItem]]:
+        """`Hnsw.search_range_match` with the values: per query every result of its condition within its radius as `MapItem`s."""
+        return self._range_items(self.hnsw.search_range_match(queries, radius, table, conds, search, max_rungs, max_total))
 
     def iter(self):
         return self.hnsw.iter()

@@ -416,6 +416,9 @@ struct idist_search_ctx {
     // An attribute call: the call's distinct intervals next to al_bits, which attr_bitmaps_kernel fills instead of
     // an upload; its own pair of events (created on first use) and the time they gave (idist_search_ctx_attr_bitmap_ms)
     DevBuf<uint32_t> at_lo, at_hi;
+    // ... or, for a call with conditions over a table, its distinct conditions as one flat program for
+    // attr_match_kernel: the clauses [n_clauses][3], then and_lims [n_and + 1], then or_lims [n_sets + 1], one upload
+    DevBuf<uint32_t> at_prog;
     hipEvent_t at_ev[2] = {nullptr, nullptr};
     bool at_timed = false;
     float at_ms = 0.0f;
@@ -488,12 +491,14 @@ struct idist_partitioned {
     bool timed = false;
 };
 
-// One u32 per point on the device, next to the rows (include/idist.h): immutable after creation.  Bound to the
-// handle it was made for by that handle's uid.  An index: one slice on its device; a partitioned index: one per part, empty parts
-// included (n == 0, no memory), each on its part's device.  The slices free themselves.
+// n_cols u32 per point on the device, next to the rows (include/idist.h): immutable after creation.  Bound to
+// the handle it was made for by that handle's uid.  An index: one slice on its device; a partitioned index: one per part, empty
+// parts included (n == 0, no memory), each on its part's device.  A slice holds its points of every column, column after column:
+// v [n_cols][n], so that v starts with the n values of column 0 the interval calls read.  The slices free themselves.
 struct idist_attr {
     uint64_t owner_uid = 0;
     bool partitioned = false;
+    uint32_t n_cols = 1;
     struct Slice {
         uint32_t n = 0;
         int32_t device = 0;
@@ -3508,8 +3513,11 @@ struct SetsSource {
     const uint32_t* bits = nullptr;                      // HOST bitmaps [n_sets][(n + 31) / 32] ...
     const idist_attr* attr = nullptr;                    // ... or the values on the device and
     const uint32_t *lo = nullptr, *hi = nullptr;         //     the distinct intervals, HOST [n_sets]
+    const uint32_t* prog = nullptr;                      // ... or the table on the device (attr) and the distinct conditions as a flat
+    uint32_t n_clauses = 0, n_and = 0;                   //     program, HOST: clauses [n_clauses][3], and_lims [n_and + 1], or_lims [n_sets + 1]
     uint32_t n_sets = 0;
     const uint32_t* set_of = nullptr;
+    size_t prog_words() const { return (size_t)n_clauses * 3u + n_and + 1u + n_sets + 1u; }
 };
 
 // the conditions of an attribute call: one for the batch or one per query, as a radius (nq == 0 is no error)
@@ -3543,6 +3551,102 @@ void attr_group(const uint32_t* lo, const uint32_t* hi, uint32_t n_cond, uint32_
     }
 }
 
+// ---- conditions over a table: an OR of ANDs of interval clauses per query ----
+// lims [count + 1]: starts at 0 and never decreases
+idist_status check_lims(const char* what, const uint32_t* lims, uint32_t count) {
+    if (lims[0] != 0) return fail(IDIST_ERR_INVALID_ARG, "%s[0] = %u: the first limit is 0", what, lims[0]);
+    for (uint32_t i = 0; i < count; i++)
+        if (lims[i + 1] < lims[i])
+            return fail(IDIST_ERR_INVALID_ARG, "%s[%u] = %u is below %s[%u] = %u: the limits never decrease", what, i + 1u, lims[i + 1], what, i, lims[i]);
+    return IDIST_OK;
+}
+
+// the conditions of a match call: one for the batch or one per query, as a radius (nq == 0 is no error); every clause names a column
+// of the table
+idist_status check_match_args(const idist_attr_conds* conds, uint32_t nq, uint32_t n_cols) {
+    if (nq == 0) return IDIST_OK;
+    if (!conds) return fail(IDIST_ERR_INVALID_ARG, "conds is null");
+    const uint32_t n_cond = conds->n_cond;
+    if (n_cond != 1 && n_cond != nq) return fail(IDIST_ERR_INVALID_ARG, "n_cond %u: 1 (one condition for the batch) or nq = %u", n_cond, nq);
+    if (!conds->and_lims || !conds->or_lims) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    CHK(check_lims("or_lims", conds->or_lims, n_cond));
+    const uint32_t n_and = conds->or_lims[n_cond];
+    CHK(check_lims("and_lims", conds->and_lims, n_and));
+    if (conds->and_lims[n_and] && !conds->clauses) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    for (uint32_t c = 0; c < n_cond; c++)
+        for (uint32_t i = conds->and_lims[conds->or_lims[c]]; i < conds->and_lims[conds->or_lims[c + 1]]; i++)
+            if (conds->clauses[i].col >= n_cols)
+                return fail(IDIST_ERR_INVALID_ARG, "condition %u, clause %u: col %u, but the table has %u column%s", c, i, conds->clauses[i].col, n_cols,
+                            n_cols == 1 ? "" : "s");
+    return IDIST_OK;
+}
+
+// D, the distinct conditions of a call, as the flat program attr_match_kernel reads, and every query's index into it.  The clauses
+// of a conjunction are ordered by (col, lo, hi) first — AND commutes, and the kernel keeps a column's tile while consecutive clauses
+// name it — and the ordered forms are what is compared: conditions equal as encoded are equal here, and share one bitmap.  In the
+// program every other conjunction is written with its columns downwards, so that it starts on the column the last one ended on.
+struct MatchConds {
+    std::vector<uint32_t> prog, set_of;                  // prog: clauses [n_clauses][3], and_lims [n_and + 1], or_lims [n_sets + 1]
+    uint32_t n_clauses = 0, n_and = 0, n_sets = 0;
+    SetsSource source(const idist_attr* attr) const {
+        SetsSource s;
+        s.attr = attr; s.prog = prog.data(); s.n_clauses = n_clauses; s.n_and = n_and; s.n_sets = n_sets; s.set_of = set_of.data();
+        return s;
+    }
+};
+void match_group(const idist_attr_conds* conds, uint32_t n_cond, uint32_t nq, MatchConds* g) {
+    g->set_of.assign(nq, 0u);
+    const uint32_t *al = n_cond ? conds->and_lims : nullptr, *ol = n_cond ? conds->or_lims : nullptr;
+    std::vector<idist_attr_clause> cl;
+    if (n_cond && al[ol[n_cond]]) cl.assign(conds->clauses, conds->clauses + al[ol[n_cond]]);
+    auto clause_less = [](const idist_attr_clause& a, const idist_attr_clause& b) {
+        return a.col != b.col ? a.col < b.col : a.lo != b.lo ? a.lo < b.lo : a.hi < b.hi;
+    };
+    for (uint32_t j = 0; n_cond && j < ol[n_cond]; j++) std::sort(cl.begin() + al[j], cl.begin() + al[j + 1], clause_less);
+    // a total order of the conditions: the number of conjunctions, their lengths, then their ordered clauses
+    auto compare = [&](uint32_t a, uint32_t b) -> int {
+        const uint32_t na = ol[a + 1] - ol[a], nb = ol[b + 1] - ol[b];
+        if (na != nb) return na < nb ? -1 : 1;
+        for (uint32_t j = 0; j < na; j++) {
+            const uint32_t la = al[ol[a] + j + 1] - al[ol[a] + j], lb = al[ol[b] + j + 1] - al[ol[b] + j];
+            if (la != lb) return la < lb ? -1 : 1;
+        }
+        const idist_attr_clause *pa = cl.data() + al[ol[a]], *pb = cl.data() + al[ol[b]];
+        for (uint32_t i = 0, m = al[ol[a + 1]] - al[ol[a]]; i < m; i++) {
+            if (clause_less(pa[i], pb[i])) return -1;
+            if (clause_less(pb[i], pa[i])) return 1;
+        }
+        return 0;
+    };
+    std::vector<uint32_t> order(n_cond);
+    for (uint32_t i = 0; i < n_cond; i++) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return compare(a, b) < 0; });
+    std::vector<uint32_t> clauses, and_lims(1, 0u), or_lims(1, 0u);
+    for (uint32_t i = 0; i < n_cond; i++) {
+        const uint32_t c = order[i];
+        if (i == 0 || compare(order[i - 1], c) != 0) {
+            for (uint32_t j = ol[c]; j < ol[c + 1]; j++) {
+                // every other conjunction of the program names its columns downwards: it starts on the column the one before it
+                // ended on, whose tile the kernel still holds ("tenant = t AND day in [a, b]" per query: three loads per two conditions)
+                const bool down = (and_lims.size() & 1u) == 0;
+                for (uint32_t x = 0, m = al[j + 1] - al[j]; x < m; x++) {
+                    const idist_attr_clause& k = cl[down ? al[j + 1] - 1u - x : al[j] + x];
+                    clauses.insert(clauses.end(), {k.col, k.lo, k.hi});
+                }
+                and_lims.push_back((uint32_t)(clauses.size() / 3u));
+            }
+            or_lims.push_back((uint32_t)and_lims.size() - 1u);
+        }
+        if (n_cond == nq) g->set_of[c] = (uint32_t)or_lims.size() - 2u;
+    }
+    g->n_clauses = (uint32_t)(clauses.size() / 3u);
+    g->n_and = (uint32_t)and_lims.size() - 1u;
+    g->n_sets = (uint32_t)or_lims.size() - 1u;
+    g->prog = std::move(clauses);
+    g->prog.insert(g->prog.end(), and_lims.begin(), and_lims.end());
+    g->prog.insert(g->prog.end(), or_lims.begin(), or_lims.end());
+}
+
 // an attribute belongs to ONE handle, as a context does: the index (partitioned == false) or the partitioned index with this uid
 idist_status check_attr(const idist_attr* a, uint64_t uid, bool partitioned) {
     if (!a) return fail(IDIST_ERR_INVALID_ARG, "attr is null");
@@ -3555,35 +3659,63 @@ idist_status check_attr(const idist_attr* a, uint64_t uid, bool partitioned) {
 
 // attr_bitmaps_kernel on `stream` (its device is current): n >= 1, n_sets >= 1.  Work item = (tile of 4096 points, chunk of sets): one
 // chunk — v read once — as soon as the tiles alone give every CU eight waves; never chunks of fewer than eight sets.
-idist_status launch_attr_bitmaps(const uint32_t* d_v, uint32_t n, const uint32_t* d_lo, const uint32_t* d_hi, uint32_t n_sets, uint32_t* d_out,
-                                 int n_cu, hipStream_t stream) {
+struct AttrGrid {
+    uint32_t set_chunk, grid;
+};
+AttrGrid attr_grid(uint32_t n, uint32_t n_sets, int n_cu) {
     const uint64_t tiles = ((uint64_t)n + kAttrTile - 1u) / kAttrTile, want = (uint64_t)std::max(n_cu, 1) * 8u;
     const uint64_t chunks_wanted = std::max<uint64_t>((want + tiles - 1u) / tiles, 1u);
     const uint32_t set_chunk = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n_sets + chunks_wanted - 1u) / chunks_wanted, 8u), n_sets);
     const uint64_t items = tiles * ((n_sets + set_chunk - 1u) / set_chunk);
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(items, (uint64_t)std::max(n_cu, 1) * 32u);
-    IDIST_LAUNCH(attr_bitmaps_kernel, grid, 64, 0, stream, d_v, n, d_lo, d_hi, n_sets, set_chunk, d_out);
+    return {set_chunk, (uint32_t)std::min<uint64_t>(items, (uint64_t)std::max(n_cu, 1) * 32u)};
+}
+idist_status launch_attr_bitmaps(const uint32_t* d_v, uint32_t n, const uint32_t* d_lo, const uint32_t* d_hi, uint32_t n_sets, uint32_t* d_out,
+                                 int n_cu, hipStream_t stream) {
+    const AttrGrid g = attr_grid(n, n_sets, n_cu);
+    IDIST_LAUNCH(attr_bitmaps_kernel, g.grid, 64, 0, stream, d_v, n, d_lo, d_hi, n_sets, g.set_chunk, d_out);
+    HIPCHK(hipGetLastError());
+    return IDIST_OK;
+}
+// attr_match_kernel on `stream`, divided as launch_attr_bitmaps divides: d_v [n_cols][col_pitch], the program of n_sets conditions
+// in device memory.  n >= 1, n_sets >= 1, col_pitch >= n.
+idist_status launch_attr_match(const uint32_t* d_v, uint32_t n, uint32_t n_cols, uint64_t col_pitch, const AttrClause* d_clauses,
+                               const uint32_t* d_and_lims, const uint32_t* d_or_lims, uint32_t n_sets, uint32_t* d_out, int n_cu,
+                               hipStream_t stream) {
+    const AttrGrid g = attr_grid(n, n_sets, n_cu);
+    IDIST_LAUNCH(attr_match_kernel, g.grid, 64, 0, stream, d_v, n, n_cols, col_pitch, d_clauses, d_and_lims, d_or_lims, n_sets, g.set_chunk, d_out);
     HIPCHK(hipGetLastError());
     return IDIST_OK;
 }
 
 // The bitmaps of an attribute call into ctx->al_bits, on the context's stream (its device is current): the distinct intervals go
-// up, the kernel runs between the context's own pair of events.  d_values [n], n >= 1.  Staging: n_sets * ((n + 31) / 32) * 4 bytes.
+// up (or the distinct conditions over a table, as one program), the kernel runs between the context's own pair of events.  d_values
+// [n_cols][n], n >= 1: the interval kernel reads column 0.  Staging: n_sets * ((n + 31) / 32) * 4 bytes.
 idist_status attr_stage_bitmaps(idist_search_ctx* ctx, const uint32_t* d_values, uint32_t n, const SetsSource& src) {
     const size_t words = ((size_t)n + 31u) / 32u;
     hipStream_t stream = ctx->stream;
     CHK(ctx->al_bits.grow((size_t)src.n_sets * words * 4));
-    CHK(ctx->at_lo.grow((size_t)src.n_sets * 4));
-    CHK(ctx->at_hi.grow((size_t)src.n_sets * 4));
-    HIPCHK(hipMemcpyAsync(ctx->at_lo.p, src.lo, (size_t)src.n_sets * 4, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(ctx->at_hi.p, src.hi, (size_t)src.n_sets * 4, hipMemcpyHostToDevice, stream));
+    if (src.prog) {
+        CHK(ctx->at_prog.grow(src.prog_words() * 4));
+        HIPCHK(hipMemcpyAsync(ctx->at_prog.p, src.prog, src.prog_words() * 4, hipMemcpyHostToDevice, stream));
+    } else {
+        CHK(ctx->at_lo.grow((size_t)src.n_sets * 4));
+        CHK(ctx->at_hi.grow((size_t)src.n_sets * 4));
+        HIPCHK(hipMemcpyAsync(ctx->at_lo.p, src.lo, (size_t)src.n_sets * 4, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(ctx->at_hi.p, src.hi, (size_t)src.n_sets * 4, hipMemcpyHostToDevice, stream));
+    }
     ctx->at_timed = false;
     if (ctx->knobs.events) {
         for (hipEvent_t& e : ctx->at_ev)
             if (!e) HIPCHK(hipEventCreate(&e));
         HIPCHK(hipEventRecord(ctx->at_ev[0], stream));
     }
-    CHK(launch_attr_bitmaps(d_values, n, ctx->at_lo, ctx->at_hi, src.n_sets, ctx->al_bits, ctx->n_cu, stream));
+    if (src.prog) {
+        const uint32_t *d_and = ctx->at_prog + (size_t)src.n_clauses * 3u, *d_or = d_and + src.n_and + 1u;
+        CHK(launch_attr_match(d_values, n, src.attr->n_cols, n, reinterpret_cast<const AttrClause*>(ctx->at_prog.p), d_and, d_or, src.n_sets,
+                              ctx->al_bits, ctx->n_cu, stream));
+    } else {
+        CHK(launch_attr_bitmaps(d_values, n, ctx->at_lo, ctx->at_hi, src.n_sets, ctx->al_bits, ctx->n_cu, stream));
+    }
     if (ctx->knobs.events) {
         HIPCHK(hipEventRecord(ctx->at_ev[1], stream));
         ctx->at_timed = true;                            // (both recorded: attr_time_resolve may ask for their distance)
@@ -4040,47 +4172,62 @@ idist_status idist_search_batch_allowed_sets(const idist_index* idx, idist_searc
     return allowed_sets_call(idx, ctx, queries, nq, src, k, max_rungs, out_pid, out_dist, out_count, out_rung, out_counters);
 }
 
-// ---- the attribute on the device and the calls that read it (DESIGN.md §4.11) ----
-idist_status idist_attr_new(const idist_index* idx, const uint32_t* values, idist_attr** out) {
+// ---- the attribute on the device and the calls that read it (DESIGN.md §4.11, §4.12) ----
+static idist_status check_n_cols(uint32_t n_cols) {
+    if (n_cols < 1 || n_cols > 64) return fail(IDIST_ERR_INVALID_ARG, "n_cols %u: a table has 1 to 64 columns", n_cols);
+    return IDIST_OK;
+}
+// a slice's points [first, first + sl.n) of every column of values [n_cols][n_total] -> sl.v [n_cols][sl.n], on the slice's device
+static idist_status attr_upload_slice(idist_attr::Slice& sl, const uint32_t* values, uint32_t n_cols, size_t n_total, size_t first) {
+    if (!sl.n) return IDIST_OK;
+    HIPCHK(hipSetDevice(sl.device));
+    CHK(sl.v.grow((size_t)n_cols * sl.n * 4));
+    if (n_cols == 1) HIPCHK(hipMemcpy(sl.v.p, values + first, (size_t)sl.n * 4, hipMemcpyHostToDevice));
+    else HIPCHK(hipMemcpy2D(sl.v.p, (size_t)sl.n * 4, values + first, n_total * 4, (size_t)sl.n * 4, n_cols, hipMemcpyHostToDevice));
+    return IDIST_OK;
+}
+
+idist_status idist_attr_new_columns(const idist_index* idx, const uint32_t* values, uint32_t n_cols, idist_attr** out) {
     if (!idx || !out) return fail(IDIST_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
+    CHK(check_n_cols(n_cols));
     if (idx->n && !values) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
     std::unique_ptr<idist_attr> a(new idist_attr());
     a->owner_uid = idx->uid;
+    a->n_cols = n_cols;
     a->parts.resize(1);
     idist_attr::Slice& sl = a->parts[0];
     sl.n = idx->n;
     sl.device = idx->device;
-    if (sl.n) {
-        HIPCHK(hipSetDevice(sl.device));
-        CHK(sl.v.grow((size_t)sl.n * 4));
-        HIPCHK(hipMemcpy(sl.v.p, values, (size_t)sl.n * 4, hipMemcpyHostToDevice));
-    }
+    CHK(attr_upload_slice(sl, values, n_cols, sl.n, 0));
     *out = a.release();
     return IDIST_OK;
 }
+idist_status idist_attr_new(const idist_index* idx, const uint32_t* values, idist_attr** out) { return idist_attr_new_columns(idx, values, 1, out); }
 
-idist_status idist_partitioned_attr_new(const idist_partitioned* p, const uint32_t* values, idist_attr** out) {
+idist_status idist_partitioned_attr_new_columns(const idist_partitioned* p, const uint32_t* values, uint32_t n_cols, idist_attr** out) {
     if (!p || !out) return fail(IDIST_ERR_INVALID_ARG, "null argument");
     *out = nullptr;
+    CHK(check_n_cols(n_cols));
     CHK(partitioned_check(const_cast<idist_partitioned*>(p), nullptr));
     const size_t P = p->parts.size();
     if (p->base[P] && !values) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
     std::unique_ptr<idist_attr> a(new idist_attr());
     a->owner_uid = p->uid;
     a->partitioned = true;
+    a->n_cols = n_cols;
     a->parts.resize(P);
     for (size_t i = 0; i < P; i++) {
         idist_attr::Slice& sl = a->parts[i];
         sl.n = p->parts[i].idx->n;
         sl.device = part_device(p, i);
-        if (!sl.n) continue;
-        HIPCHK(hipSetDevice(sl.device));
-        CHK(sl.v.grow((size_t)sl.n * 4));
-        HIPCHK(hipMemcpy(sl.v.p, values + p->base[i], (size_t)sl.n * 4, hipMemcpyHostToDevice));
+        CHK(attr_upload_slice(sl, values, n_cols, p->base[P], p->base[i]));
     }
     *out = a.release();
     return IDIST_OK;
+}
+idist_status idist_partitioned_attr_new(const idist_partitioned* p, const uint32_t* values, idist_attr** out) {
+    return idist_partitioned_attr_new_columns(p, values, 1, out);
 }
 
 void idist_attr_free(idist_attr* a) { delete a; }
@@ -4097,6 +4244,21 @@ idist_status idist_attr_bitmaps_device(const void* d_values, uint32_t n, const v
                                prop.multiProcessorCount, (hipStream_t)hip_stream);
 }
 
+idist_status idist_attr_match_bitmaps_device(const void* d_values, uint32_t n, uint32_t n_cols, uint64_t col_pitch, const void* d_clauses,
+                                             const void* d_and_lims, const void* d_or_lims, uint32_t n_sets, void* d_out, int32_t device,
+                                             void* hip_stream) {
+    if (n == 0 || n_sets == 0) return IDIST_OK;
+    if (!d_values || !d_and_lims || !d_or_lims || !d_out) return fail(IDIST_ERR_INVALID_ARG, "null device pointer");   // (d_clauses: a program may have none)
+    CHK(check_n_cols(n_cols));
+    if (col_pitch < n) return fail(IDIST_ERR_INVALID_ARG, "col_pitch %llu: a column holds n = %u values", (unsigned long long)col_pitch, n);
+    CHK(check_device(device));
+    HIPCHK(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    return launch_attr_match((const uint32_t*)d_values, n, n_cols, col_pitch, (const AttrClause*)d_clauses, (const uint32_t*)d_and_lims,
+                             (const uint32_t*)d_or_lims, n_sets, (uint32_t*)d_out, prop.multiProcessorCount, (hipStream_t)hip_stream);
+}
+
 idist_status idist_search_batch_attr(const idist_index* idx, idist_search_ctx* ctx, const idist_attr* attr, const float* queries, uint32_t nq,
                                      const uint32_t* lo, const uint32_t* hi, uint32_t n_cond, uint32_t k, int32_t max_rungs,
                                      uint32_t* out_pid, float* out_dist, uint32_t* out_count, uint32_t* out_rung, uint32_t* out_counters) {
@@ -4109,6 +4271,21 @@ idist_status idist_search_batch_attr(const idist_index* idx, idist_search_ctx* c
     if (!queries || !out_pid || !out_dist || !out_count) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
     AttrConds g;
     attr_group(lo, hi, n_cond, nq, &g);
+    return allowed_sets_call(idx, ctx, queries, nq, g.source(attr), k, max_rungs, out_pid, out_dist, out_count, out_rung, out_counters);
+}
+
+idist_status idist_search_batch_match(const idist_index* idx, idist_search_ctx* ctx, const idist_attr* attr, const float* queries, uint32_t nq,
+                                      const idist_attr_conds* conds, uint32_t k, int32_t max_rungs, uint32_t* out_pid, float* out_dist,
+                                      uint32_t* out_count, uint32_t* out_rung, uint32_t* out_counters) {
+    CHK(check_ctx(idx, ctx));
+    CHK(check_attr(attr, idx->uid, false));
+    ctx->at_ms = 0.0f;
+    CHK(check_ladder_args(max_rungs, k, idx->cfg.ef_search));
+    CHK(check_match_args(conds, nq, attr->n_cols));
+    if (nq == 0) return IDIST_OK;
+    if (!queries || !out_pid || !out_dist || !out_count) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    MatchConds g;
+    match_group(conds, conds->n_cond, nq, &g);
     return allowed_sets_call(idx, ctx, queries, nq, g.source(attr), k, max_rungs, out_pid, out_dist, out_count, out_rung, out_counters);
 }
 
@@ -4301,6 +4478,22 @@ idist_status idist_partitioned_search_batch_attr(idist_partitioned* p, const idi
     if (!queries || !out_pid || !out_dist || !out_count) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
     AttrConds g;
     attr_group(lo, hi, n_cond, nq, &g);
+    return partitioned_allowed_sets_call(p, ef, queries, nq, g.source(attr), k, max_rungs, out_pid, out_dist, out_count, out_rung, out_counters);
+}
+
+idist_status idist_partitioned_search_batch_match(idist_partitioned* p, const idist_attr* attr, const float* queries, uint32_t nq,
+                                                  const idist_attr_conds* conds, uint32_t k, int32_t max_rungs, uint32_t* out_pid,
+                                                  float* out_dist, uint32_t* out_count, uint32_t* out_rung, uint32_t* out_counters) {
+    if (!p) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    uint32_t ef = 0;
+    CHK(partitioned_check(p, &ef));
+    CHK(check_partitioned_attr(p, attr));
+    CHK(check_ladder_args(max_rungs, k, ef));
+    CHK(check_match_args(conds, nq, attr->n_cols));
+    if (nq == 0) return IDIST_OK;
+    if (!queries || !out_pid || !out_dist || !out_count) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    MatchConds g;
+    match_group(conds, conds->n_cond, nq, &g);
     return partitioned_allowed_sets_call(p, ef, queries, nq, g.source(attr), k, max_rungs, out_pid, out_dist, out_count, out_rung, out_counters);
 }
 
@@ -4500,6 +4693,20 @@ idist_status idist_search_batch_range_attr(const idist_index* idx, idist_search_
     CHK(check_cond_args(lo, hi, n_cond, nq));
     AttrConds g;
     attr_group(lo, hi, nq ? n_cond : 0u, nq, &g);
+    return range_allowed_sets_call(idx, ctx, queries, nq, radius, n_radius, g.source(attr), max_rungs, max_total, out_lims, out_rung, out_counters);
+}
+
+idist_status idist_search_batch_range_match(const idist_index* idx, idist_search_ctx* ctx, const idist_attr* attr, const float* queries, uint32_t nq,
+                                            const float* radius, uint32_t n_radius, const idist_attr_conds* conds, int32_t max_rungs,
+                                            uint64_t max_total, uint64_t* out_lims, uint32_t* out_rung, uint32_t* out_counters) {
+    CHK(check_ctx(idx, ctx));
+    ctx->rg_valid = false;                                                   // whatever happens next, the previous results are gone
+    CHK(check_attr(attr, idx->uid, false));
+    ctx->at_ms = 0.0f;
+    CHK(check_range_args(queries, nq, radius, n_radius, max_rungs, out_lims));
+    CHK(check_match_args(conds, nq, attr->n_cols));
+    MatchConds g;
+    match_group(conds, nq ? conds->n_cond : 0u, nq, &g);
     return range_allowed_sets_call(idx, ctx, queries, nq, radius, n_radius, g.source(attr), max_rungs, max_total, out_lims, out_rung, out_counters);
 }
 
@@ -4984,6 +5191,24 @@ idist_status idist_partitioned_search_batch_range_attr(idist_partitioned* p, con
     CHK(check_cond_args(lo, hi, n_cond, nq));
     AttrConds g;
     attr_group(lo, hi, nq ? n_cond : 0u, nq, &g);
+    const SetsSource src = g.source(attr);
+    return partitioned_range_call(p, ef, queries, nq, radius, n_radius, &src, max_rungs, max_total, out_lims, out_rung, out_counters);
+}
+
+idist_status idist_partitioned_search_batch_range_match(idist_partitioned* p, const idist_attr* attr, const float* queries, uint32_t nq,
+                                                        const float* radius, uint32_t n_radius, const idist_attr_conds* conds,
+                                                        int32_t max_rungs, uint64_t max_total, uint64_t* out_lims, uint32_t* out_rung,
+                                                        uint32_t* out_counters) {
+    if (!p) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    p->rg_valid = false;                                                     // whatever happens next, the previous results are gone
+    p->rg_total = 0;
+    uint32_t ef = 0;
+    CHK(partitioned_check(p, &ef));
+    CHK(check_partitioned_attr(p, attr));
+    CHK(check_range_args(queries, nq, radius, n_radius, max_rungs, out_lims));
+    CHK(check_match_args(conds, nq, attr->n_cols));
+    MatchConds g;
+    match_group(conds, nq ? conds->n_cond : 0u, nq, &g);
     const SetsSource src = g.source(attr);
     return partitioned_range_call(p, ef, queries, nq, radius, n_radius, &src, max_rungs, max_total, out_lims, out_rung, out_counters);
 }

@@ -20,8 +20,8 @@ import numpy as np
 
 from . import _capi
 from ._capi import INVALID, METRIC_DOT, RUNG_NONE
-from .api import (AllowedResult, Attr, BatchResult, Builder, Hnsw, Item, RangeResult, _as_points, _attr_values, _conditions, _set_of, allowed_bitmap,
-                  allowed_bitmaps)
+from .api import (AllowedResult, Attr, AttrTable, BatchResult, Builder, Hnsw, Item, RangeResult, _as_points, _attr_values, _conditions, _conds_arg,
+                  _set_of, _table_columns, allowed_bitmap, allowed_bitmaps)
 from .dist import shard_range
 
 
@@ -355,6 +355,53 @@ class PartitionedHnsw:
         L.check(L.idist_partitioned_search_batch_range_attr(self._h, attr._h, _capi.f32p(q), nq, _capi.f32p(rad), int(rad.size),
                                                             _capi.u32p(lo_a), _capi.u32p(hi_a), n_cond, int(max_rungs), int(max_total),
                                                             _capi.u64p(lims), _capi.u32p(rung), _capi.u32p(ctr) if counters else None))
+        return self._range_fetch(lims, rung, ctr)
+
+    # -- attribute tables --
+    def attribute_table(self, columns) -> AttrTable:
+        """Several uint32 columns per point in GLOBAL-id order (idist_partitioned_attr_new_columns): every non-empty part's slice of
+        every column goes to that part's own device, once.  `columns` as in `Hnsw.attribute_table`."""
+        names, cols = _table_columns(columns, len(self))
+        h = C.c_void_p()
+        L = _lib()
+        L.check(L.idist_partitioned_attr_new_columns(self._h, _capi.u32p(cols), len(names), C.byref(h)))
+        return AttrTable(h, self, names, cols)
+
+    def search_match(self, queries, table: AttrTable, conds, k: int = 10, max_rungs: int = -1, counters: bool = False) -> AllowedResult:
+        """The k nearest among the points that satisfy the query's condition over the table's columns
+        (idist_partitioned_search_batch_match): row q is exactly what `search_allowed_sets` returns for the mask of its condition over
+        the global ids; every part evaluates the conditions over its own slice of the columns on its own device.  `conds` as in
+        `Hnsw.search_match`."""
+        q = _as_points(queries)
+        info = self.info()
+        n, P = int(info.n), int(info.n_parts)
+        if q.shape[0] and n and q.shape[1] != info.dim:
+            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
+        nq, k = q.shape[0], int(k)
+        cs, _keep = _conds_arg(table, conds, nq)
+        kk = max(k, 0)
+        pid = np.full((nq, kk), INVALID, dtype=np.uint32)
+        dist = np.full((nq, kk), np.inf, dtype=np.float32)
+        cnt = np.zeros(nq, dtype=np.uint32)
+        rung = np.full((nq, P), RUNG_NONE, dtype=np.uint32)
+        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
+        L = _lib()
+        L.check(L.idist_partitioned_search_batch_match(self._h, table._h, _capi.f32p(q), nq, C.byref(cs), kk, int(max_rungs), _capi.u32p(pid),
+                                                       _capi.f32p(dist), _capi.u32p(cnt), _capi.u32p(rung),
+                                                       _capi.u32p(ctr) if counters else None))
+        return AllowedResult(pid, dist, cnt, rung, ctr)
+
+    def search_range_match(self, queries, radius, table: AttrTable, conds, max_rungs: int = -1, max_total: int = 64 * 2**20,
+                           counters: bool = False) -> RangeResult:
+        """Every point within `radius` that satisfies the query's condition (idist_partitioned_search_batch_range_match): row q is
+        exactly what `search_range_allowed_sets` returns for the mask of its condition."""
+        q, rad, lims, rung, ctr = self._range_outputs(queries, radius, counters)
+        nq = q.shape[0]
+        cs, _keep = _conds_arg(table, conds, nq)
+        L = _lib()
+        L.check(L.idist_partitioned_search_batch_range_match(self._h, table._h, _capi.f32p(q), nq, _capi.f32p(rad), int(rad.size), C.byref(cs),
+                                                             int(max_rungs), int(max_total), _capi.u64p(lims), _capi.u32p(rung),
+                                                             _capi.u32p(ctr) if counters else None))
         return self._range_fetch(lims, rung, ctr)
 
     def search_one_range(self, point, radius) -> list[Item]:
