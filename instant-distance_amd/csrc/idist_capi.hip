@@ -4,6 +4,7 @@
 #include "../../include/idist.h"
 #include "idist_kernels.hpp"
 #include "idist_search_plan.hpp"
+#include "idist_build_plan.hpp"
 #include "idist_mfma.hpp"
 #include "idist_combine.hpp"
 #include "idist_merge.hpp"
@@ -168,25 +169,6 @@ inline size_t doubled_from(size_t lo, size_t need) {
     return lo;
 }
 
-// Layer sizing of Hnsw::new, core/lib.rs:238-250 (f32 multiply + truncation, `as usize` saturates)
-uint32_t layer_sizes(uint32_t n, float ml, uint32_t* cum, uint32_t cap) {
-    uint32_t cnt = 0;
-    size_t num = n;
-    for (;;) {
-        volatile float prod = (float)num * ml;
-        size_t next;
-        if (!(prod > 0.0f)) next = 0;
-        else if (prod >= 18446744073709551616.0f) next = (size_t)-1;
-        else next = (size_t)prod;
-        if (next < IDIST_M) break;
-        if (cnt + 1 >= cap) return 0;  // too many layers
-        cum[cnt++] = (uint32_t)num;
-        num = next;
-    }
-    cum[cnt++] = (uint32_t)num;
-    return cnt;
-}
-
 idist_status check_device(int32_t device) {
     int cnt = 0;
     hipError_t e = hipGetDeviceCount(&cnt);
@@ -342,6 +324,20 @@ inline Knobs knobs_from_env() {
     if (const char* e = getenv("IDIST_SYNC")) k.sync_flag = e[0] != 's';
     if (const char* e = getenv("IDIST_COMBINE")) k.combine = e[0] != '0';
     if (const char* e = test_env("IDIST_TAB_LOG2")) k.tab_log2 = std::min(13u, std::max(5u, (uint32_t)atoi(e)));
+    if (const char* e = test_env("IDIST_BUILD_RT")) k.build_rt = (uint32_t)atoi(e);
+    if (const char* e = test_env("IDIST_BUILD_RT2")) k.build_rt2 = (uint32_t)atoi(e);
+    if (const char* e = test_env("IDIST_BUILD_A2")) k.build_a2_tile = e[0] == 't';
+    if (const char* e = test_env("IDIST_BUILD_PIPELINE")) k.build_pipeline = e[0] != '0';
+    if (const char* e = test_env("IDIST_BUILD_A_WAVES")) k.build_a_waves = (uint32_t)std::min(8, std::max(1, atoi(e)));
+    if (const char* e = test_env("IDIST_BUILD_A_REGS")) k.build_a_regs = atoi(e) == 256 ? 256 : 512;
+    if (const char* e = test_env("IDIST_BUILD_QUAD")) k.build_quad = e[0] != '0';
+    if (const char* e = test_env("IDIST_BUILD_GROWTH")) k.build_growth = (uint32_t)std::min(32, std::max(8, atoi(e)));
+    if (const char* e = test_env("IDIST_BUILD_STREAMS")) k.build_streams = e[0] == 'o' ? 0 : (e[0] == 'a' ? 2 : 1);
+    if (const char* e = test_env("IDIST_BUILD_FILTER")) k.build_filter = e[0] != '0' ? 1 : 0;
+    if (test_env("IDIST_BUILD_NO_DLOG")) k.build_dlog = false;
+    if (const char* e = test_env("IDIST_BUILD_CHUNK")) k.build_chunk = (uint32_t)atoi(e);
+    if (test_env("IDIST_BUILD_NO_FAST")) k.build_no_fast = true;
+    if (test_env("IDIST_BUILD_CHECK")) k.build_check = true;
     return k;
 }
 
@@ -798,271 +794,234 @@ idist_status device_status_to_code(uint32_t st, int32_t tie_policy) {
 bool filter_applies(const idist_index* ix);
 idist_status filter_ensure(const idist_index* ix, bool with_principal = true);
 
+// a stream / an event of a one-shot entry point: destroyed when the function returns, whichever way it returns (null: never made)
+struct OwnedStream {
+    hipStream_t s = nullptr;
+    OwnedStream() = default;
+    OwnedStream(const OwnedStream&) = delete;
+    OwnedStream& operator=(const OwnedStream&) = delete;
+    ~OwnedStream() { if (s) hipStreamDestroy(s); }
+    idist_status create() { HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); return IDIST_OK; }
+    operator hipStream_t() const { return s; }
+};
+struct OwnedEvent {
+    hipEvent_t e = nullptr;
+    OwnedEvent() = default;
+    OwnedEvent(const OwnedEvent&) = delete;
+    OwnedEvent& operator=(const OwnedEvent&) = delete;
+    ~OwnedEvent() { if (e) hipEventDestroy(e); }
+    idist_status create() { HIPCHK(hipEventCreate(&e)); return IDIST_OK; }
+    operator hipEvent_t() const { return e; }
+};
+
+// The build's 64 words of counters (d_small), by who writes what.  A counter block is 8 words a step clears before its selection:
+// [0] n_touched, [1..5] queue heads (A, B, n_slow, B2, A2) — [3] is n_slow.
+enum : uint32_t {
+    kSmallCounters = 0,         // sequential schedule: the one counter block; the descents' queue head is its word 1
+    kSmallQueueA = 1,           // the descents' queue head (pipelined: descent stream 0's, cleared on its own)
+    kSmallStatus = 8,           // sequential schedule: the status word every kernel ORs into
+    kSmallCountersPipe = 16,    // pipelined: the update stream's counter block; odd steps with inboxes of their own take the next one (24)
+    kSmallStatusPipe = 32,      // pipelined: the status word
+    kSmallMismatch = 40,        // IDIST_BUILD_CHECK: rows on which the two copies of the zero layer differ
+    kSmallQueueA1 = 48,         // pipelined: descent stream 1's queue head
+    kSmallBlock = 8, kSmallNSlow = 3, kSmallWords = 64
+};
+
+// What one step launches on, reads and writes: run_build fills it, launch_build_step<geometry> launches from it.
+struct BuildStepIo {
+    uint64_t k = 0;                       // step number, 1-based
+    IndexView viewA, viewS;               // the zero layer the descents read / the selection and the updates write
+    BuildArgs aA, aS, af;                 // descents; selection and updates (same step-A outputs, own counters); the fast update
+    hipStream_t sA = nullptr, sA2 = nullptr, s2 = nullptr;   // descents, selection, updates
+    hipEvent_t evA = nullptr, evA2 = nullptr, evC = nullptr; // this parity's descents / selection done; the carry-over has read its touched list
+    bool own_a2 = false;
+    uint32_t* cnt = nullptr;              // this step's counter block
+    uint64_t* ext_work = nullptr;
+    // the carry-over of the previous step's rows into this step's copy of the zero layer
+    const uint32_t* z_prev = nullptr;
+    uint32_t* z_cur = nullptr;
+    const uint32_t *prev_touched = nullptr, *prev_cnt = nullptr;
+    uint32_t prev_start = 0, prev_count = 0;
+};
+
+template <int NB, int RS, int TAIL>
+idist_status launch_build_step(const BuildStep& st, const BuildPlan& p, const BuildStepIo& io) {
+    const hipStream_t sA = io.sA, sA2 = io.sA2, s2 = io.s2;
+    const bool own_selection = st.select_stream == SelectStream::Selection;   // (pipelined only)
+    auto kAo = build_insert_kernel<NB, RS, TAIL, kWalkFatIds>;
+    auto kAo16 = build_insert_kernel<NB, RS, TAIL, kWalkFatQ16>;
+    auto kAq16 = build_insert_kernel<NB, RS, TAIL, kWalkFourWaveQ16>;
+    auto kAo16w2 = build_insert_kernel<NB, RS, TAIL, walk_two_per_simd(NB)>;
+    auto kF = build_update_fast_kernel<NB, RS, TAIL>;
+    auto kB = build_update_kernel<NB, RS, TAIL>;
+    auto kP = build_update_simple_kernel<NB, RS, TAIL>;
+    auto kA2 = build_select_kernel<NB, RS, TAIL>;
+    auto kX = build_extend_kernel<NB, RS, TAIL>;
+    auto kA2m = build_select_mfma_kernel<NB, RS, TAIL>;
+    switch (st.descent) {
+        case BuildDescent::Extend: IDIST_LAUNCH(kX, 1, 64, p.smem_extend, sA, io.viewA, io.aA, io.ext_work, p.ext_cap); break;
+#ifdef IDIST_VARIANTS
+        case BuildDescent::ClassicQ16: {
+            auto kA16 = build_insert_kernel<NB, RS, TAIL, kWalkClassicOnChipQ16>;
+            IDIST_LAUNCH(kA16, st.gridA, 64, p.smem, sA, io.viewA, io.aA);
+            break;
+        }
+        case BuildDescent::ClassicIds: {
+            auto kA = build_insert_kernel<NB, RS, TAIL, kWalkClassicOnChipIds>;
+            IDIST_LAUNCH(kA, st.gridA, 64, p.smem, sA, io.viewA, io.aA);
+            break;
+        }
+#else
+        case BuildDescent::ClassicQ16:
+        case BuildDescent::ClassicIds: return fail(IDIST_ERR_INTERNAL, "the classic descents exist in the test build only");
+#endif
+        case BuildDescent::FourWaveQ16: IDIST_LAUNCH(kAq16, std::min(st.B, p.slots), 256, p.smem, sA, io.viewA, io.aA); break;
+        case BuildDescent::ThinFiltered:
+            if (!DescentLaunch<NB, RS, TAIL, walk_thin_filter(2), GeoKernels<NB>::thin_descent>::go(st.gridA, p.smem, sA, io.viewA, io.aA))
+                return fail(IDIST_ERR_INTERNAL, "no filtered descent kernel for this row geometry");
+            break;
+        case BuildDescent::TwoPerSimd: IDIST_LAUNCH(kAo16w2, st.gridA, 64, p.smem, sA, io.viewA, io.aA); break;
+        case BuildDescent::FatQ16: IDIST_LAUNCH(kAo16, st.gridA, 64, p.smem, sA, io.viewA, io.aA); break;
+        case BuildDescent::FatIds: IDIST_LAUNCH(kAo, st.gridA, 64, p.smem, sA, io.viewA, io.aA); break;
+        case BuildDescent::kCount: break;
+    }
+    if (p.pipe) {
+        HIPCHK(hipEventRecord(io.evA, sA));
+        HIPCHK(hipStreamWaitEvent(sA2, io.evA, 0));
+        /* this step's inbox set is the one step k - 1's carry-over reads its touched list from (evC, recorded below) */
+        if (own_selection && io.k > 1) HIPCHK(hipStreamWaitEvent(sA2, io.evC, 0));
+        if (!own_selection) {
+            IDIST_LAUNCH(copy_rows_kernel, 1024, 64, 0, s2, io.z_prev, io.z_cur, io.prev_touched, io.prev_cnt, io.prev_start, io.prev_count);
+            if (io.own_a2) HIPCHK(hipEventRecord(io.evC, s2));
+        }
+        HIPCHK(hipMemsetAsync(io.cnt, 0, 32, sA2));
+    }
+    if (p.ext) {
+    } else if (p.has_heuristic) {
+        if (p.a2_mfma) IDIST_LAUNCH(kA2m, st.gridA2m, 256, p.smem_select_mfma, sA2, io.viewS, io.aS);
+        else IDIST_LAUNCH(kA2, st.gridA2, 64, p.smem_select, sA2, io.viewS, io.aS);
+        if (p.pipe && own_selection) {
+            HIPCHK(hipEventRecord(io.evA2, sA2));
+            HIPCHK(hipStreamWaitEvent(s2, io.evA2, 0));
+            IDIST_LAUNCH(copy_rows_kernel, 1024, 64, 0, s2, io.z_prev, io.z_cur, io.prev_touched, io.prev_cnt, io.prev_start, io.prev_count);
+            HIPCHK(hipEventRecord(io.evC, s2));
+        }
+        IDIST_LAUNCH(kF, st.gridB, 64, p.smem_update_fast, s2, io.viewS, io.af);
+        IDIST_LAUNCH(kB, st.gridS, 64, p.smem_update, s2, io.viewS, io.aS);
+    } else {
+        IDIST_LAUNCH(kP, st.gridB, 64, (size_t)(72 * 8 + 64 * 4), s2, io.viewS, io.aS);
+    }
+    return IDIST_OK;
+}
+
 idist_status run_build(idist_index* ix, idist_progress* prog, bool tie_spill) {
     const uint32_t n = ix->n;
     if (prog) { prog->total = n; prog->slot[0] = n ? 1 : 0; prog->slot[1] = 0; }   // pid 0 is in from the start
     if (n <= 1) return IDIST_OK;   // pid 0 is never inserted (core/lib.rs:279-280)
     const idist_config& cfg = ix->cfg;
     const uint32_t top = ix->n_upper;
-    // a step never holds more than 1/32 of the points already inserted, so scratch is sized by that
-    // Heuristic::extend_candidates: defined by the oracle's lock-free restatement (it deadlocks in the reference,
-    // core/lib.rs:649 vs :438), one whole insertion per launch in program order — always the sequential schedule
-    const bool ext = cfg.has_heuristic && cfg.extend_candidates;
-    const uint32_t cap = ext ? 1u : std::min<uint32_t>(cfg.max_batch == 0 ? 8192u : cfg.max_batch, std::max<uint32_t>(1u, n / 32u));
-    // the descents keep their visited set on chip, one fat wave per SIMD (up to 8 per CU with the 16-KB quotient set);
-    // with the HBM tie bags (one of n keys per slot) as many slots as fit 1 GiB
-    uint32_t slots = std::min(cap, (uint32_t)ix->n_cu * 8u);
-    if (tie_spill) slots = std::min<uint32_t>(slots, (uint32_t)std::max<size_t>(1, ((size_t)1 << 30) / ((size_t)n * 8)));
+
+    // ---- the facts
     const VisGeom vg = vis_geometry(n);
     const Knobs knobs = knobs_from_env();
     CHK(variants_check(knobs.classic));
-    // no compile-time instantiation of the row geometry (IDIST_DISPATCH): the runtime-geometry kernels
-    const bool rt_geometry = !has_template_geometry(ix->L);
+    BuildFacts f;
+    f.n = n;
+    f.L = ix->L;
+    f.n_cu = ix->n_cu;
+    f.ef_construction = cfg.ef_construction;
+    f.max_batch = cfg.max_batch;
+    f.has_heuristic = cfg.has_heuristic;
+    f.extend_candidates = cfg.extend_candidates;
+    f.metric_l2sq = kernel_metric(cfg) == IDIST_METRIC_L2SQ;
+    f.tie_cap = tie_capacity(cfg);
+    f.tie_spill = tie_spill;
+    f.template_geometry = has_template_geometry(ix->L);
+    f.filter_applies = filter_applies(ix);
+    f.dirty_words = vg.dirty_words;
 
-    const uint32_t tie_cap = tie_capacity(cfg);
-    const uint32_t wcap = cfg.ef_construction + 64 + tie_cap + 64;
-    // The descents' on-chip visited set.  Quotient form (16-bit entries, idist_device.hpp q16_*) where n allows it: 16 KB hold
-    // 8192 ids — an ef_construction = 100 descent visits ~6k — so a descent wave takes ~22 KB of LDS instead of ~39 KB
-    // and four or five of them leave half the CU's LDS to the update stream.  Otherwise (and IDIST_TAB_FORMAT=ids, ext):
-    // full ids, the largest set that leaves room for four waves per CU, or the largest that fits at all.
-    uint32_t tab_log2 = 0;
-    bool tab16 = false;
-    if (!ext && !knobs.tab_ids) {
-        const uint32_t want = knobs.tab_log2 ? std::max(8u, std::min(13u, knobs.tab_log2))
-                                             : (cfg.ef_construction <= 128 ? 12u : 13u);
-        for (uint32_t l = want; l <= 13 && !tab16; l++)
-            if (q16_applies(l, q16_universe_bits(n, l)) && smem_bytes(ix->L.stride, wcap, true, 1u << l, vg.dirty_words) <= kOnChipLdsPerWave) {
-                tab_log2 = l;
-                tab16 = true;
-            }
+    // ---- the plan
+    BuildPlan p = plan_build(f, knobs);
+    switch (p.error) {
+        case BuildPlanError::DescentLds: return fail(IDIST_ERR_INVALID_ARG, "dim/ef_construction need more than 64 KiB of LDS per wave");
+        case BuildPlanError::UpdateTileLds: return fail(IDIST_ERR_INVALID_ARG, "dim %u needs %zu B of LDS per wave in the build (> 64 KiB)", ix->dim, p.smem_update);
+        case BuildPlanError::SelectTileLds: return fail(IDIST_ERR_INVALID_ARG, "dim %u / ef_construction %u need %zu B of LDS per wave in the build (> 64 KiB)", ix->dim, cfg.ef_construction, p.smem_select);
+        case BuildPlanError::ExtendLds: return fail(IDIST_ERR_INVALID_ARG, "dim/ef_construction need %zu B of LDS per wave with extend_candidates (> 64 KiB)", p.smem_extend);
+        default: break;
     }
-    if (!tab16) {
-        for (uint32_t l = 13; l >= 8 && !tab_log2; l--)
-            if (smem_bytes(ix->L.stride, wcap, true, 1u << l, vg.dirty_words) <= kOnChipLdsPerWave) tab_log2 = l;
-        for (uint32_t l = 13; l >= 8 && !tab_log2; l--)
-            if (smem_bytes(ix->L.stride, wcap, true, 1u << l, vg.dirty_words) <= 64 * 1024) tab_log2 = l;
-        if (!tab_log2) return fail(IDIST_ERR_INVALID_ARG, "dim/ef_construction need more than 64 KiB of LDS per wave");
-        if (knobs.tab_log2) tab_log2 = std::max(8u, std::min(tab_log2, knobs.tab_log2));
-    }
-    const uint32_t dl_shift = tab_log2 + (tab16 ? 1u : 0u);
-    const size_t smem = smem_bytes(ix->L.stride, wcap, true, 1u << tab_log2, vg.dirty_words);
+    const bool pipe = p.pipe, two_a = p.two_a, own_a2 = p.own_a2;
+    const uint32_t cap = p.cap;
 
-    // Tiles of steps B2 / A2 (tile kernel): selected rows kept on chip next to the staging slots.  A tile wave has to find LDS
-    // BESIDE the descents of the next step (four waves per CU of `smem` bytes each, resident for a whole launch): a tile that
-    // does not fit waits for that launch to drain and the pipeline runs serially — measured at 1024-d, where a 63-KB tile
-    // missed the 62 KB left by 1 KB and the full re-selections took 7.4 s of a 9.5-s build.  So: at most what is left of the
-    // CU's 160 KiB, at most 64 KiB; long runtime-geometry rows stage four candidates per round instead of eight.
-    const bool generic_geo = rt_geometry;
-    const size_t lds_beside = (size_t)160 * 1024 > 4 * smem + 8 * 1024 ? (size_t)160 * 1024 - 4 * smem : 8 * 1024;
-    const size_t tile_budget = cap > 1 ? std::min<size_t>(64 * 1024, std::max<size_t>(lds_beside, 24 * 1024)) : 64 * 1024;
-    uint32_t fc = 8;
-    if (generic_geo && smem_bytes_update(ix->L.nb, 4, 8) > tile_budget) fc = 4;
-    uint32_t rt = 8;
-    if (const char* e = test_env("IDIST_BUILD_RT")) rt = (uint32_t)atoi(e);
-    while (rt > 0 && smem_bytes_update(ix->L.nb, rt, fc) > tile_budget) rt--;
-    size_t smemB = smem_bytes_update(ix->L.nb, rt, fc);
-    if (smemB > tile_budget) {                                   // does not fit beside the descents: take what a CU alone allows
-        rt = 8;
-        while (rt > 0 && smem_bytes_update(ix->L.nb, rt, fc) > 64 * 1024) rt--;
-        smemB = smem_bytes_update(ix->L.nb, rt, fc);
-    }
-    if (smemB > 64 * 1024) return fail(IDIST_ERR_INVALID_ARG, "dim %u needs %zu B of LDS per wave in the build (> 64 KiB)", ix->dim, smemB);
-
-    // step A2 tile: the new point's selected set (up to 64 rows) — it is not memory bound, so favour rows on chip
-    uint32_t rt2 = 16;
-    if (const char* e = test_env("IDIST_BUILD_RT2")) rt2 = (uint32_t)atoi(e);
-    while (rt2 > 0 && smem_bytes_select(ix->L.nb, rt2, cfg.ef_construction, fc) > tile_budget) rt2--;
-    size_t smemA2 = smem_bytes_select(ix->L.nb, rt2, cfg.ef_construction, fc);
-    if (smemA2 > tile_budget) {
-        rt2 = 16;
-        while (rt2 > 0 && smem_bytes_select(ix->L.nb, rt2, cfg.ef_construction, fc) > 64 * 1024) rt2--;
-        smemA2 = smem_bytes_select(ix->L.nb, rt2, cfg.ef_construction, fc);
-    }
-    if (smemA2 > 64 * 1024) return fail(IDIST_ERR_INVALID_ARG, "dim %u / ef_construction %u need %zu B of LDS per wave in the build (> 64 KiB)", ix->dim, cfg.ef_construction, smemA2);
-
+    // ---- scratch (all of it on the null stream)
+    Scratch sc;
+    DevBuf<uint32_t> zero2;                // pipelined: the second copy of the zero layer (or, after the final swap, the first)
+    OwnedStream s1, s2, s3, s4;            // descents, updates; narrow steps: odd steps' descents, selection
+    OwnedEvent evA[2], evS[2], evA2[2], evC, e0, e1;
     uint64_t* d_ext_work = nullptr;
-    uint32_t ext_cap = 1;
-    // a selection's working set, padded for the sort: nearest (<= ef_construction for the new point, <= 65 = new + a full
-    // row for a neighbour's re-selection, whatever ef_construction is) plus up to 64 extensions per member
-    while (ext_cap < (std::max(cfg.ef_construction, 65u) + 1u) * 65u + 64u) ext_cap <<= 1;
-    const size_t smemX = smem_bytes_extend(ix->L.stride, wcap, 1u << tab_log2, vg.dirty_words);
-    if (ext && smemX > 64 * 1024) return fail(IDIST_ERR_INVALID_ARG, "dim/ef_construction need %zu B of LDS per wave with extend_candidates (> 64 KiB)", smemX);
-    // step A2 on the matrix cores (Gram matrix of the candidates as a filter, idist_mfma.hpp) where it applies
-    const bool a2_mfma = cfg.has_heuristic && kernel_metric(cfg) == IDIST_METRIC_L2SQ && cfg.ef_construction <= 128 &&
-                         !(test_env("IDIST_BUILD_A2") && test_env("IDIST_BUILD_A2")[0] == 't');
-    const size_t smemA2m = smem_bytes_select_mfma(ix->L.stride);
     uint32_t* d_vis = nullptr;
     uint64_t* d_tie_spill = nullptr;
-    uint32_t* d_nbr_dist = nullptr;
+    uint32_t *d_nbr_dist = nullptr, *d_nbr_aux = nullptr, *d_row_nsel = nullptr, *d_slow = nullptr;
     uint32_t *d_edge_pid = nullptr, *d_edge_dist = nullptr, *d_head = nullptr, *d_next = nullptr, *d_touched = nullptr;
-    uint32_t* d_small = nullptr;           // [0] n_touched, [1..5] queue (A, B, n_slow, B2, A2), [8] status
+    uint32_t* d_small = nullptr;           // kSmall*
     uint64_t *d_wbuf = nullptr, *d_dlog_log = nullptr;
-    uint32_t* d_dlog_pd = nullptr;
-    uint32_t* d_wcount = nullptr;
-    uint32_t *d_row_nsel = nullptr, *d_slow = nullptr, *d_nbr_aux = nullptr;
+    uint32_t *d_dlog_pd = nullptr, *d_wcount = nullptr;
     unsigned long long* d_stats = nullptr; // [32]
     const size_t n_edges = (size_t)cap * IDIST_M2;
     const size_t n_touch = std::min<size_t>(n_edges, n);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    // Pipelined schedule (default for concurrent builds with the heuristic): the descents of step k+1 (HBM-bound)
-    // run on one stream while the selections / neighbour updates of step k (LDS- and latency-bound) run on another.
-    // Step k's descents read the graph as of step k-2, so nothing they read is being written: the zero layer is
-    // kept in two copies, copy k&1 receiving the state after step k.  Deterministic like the sequential schedule;
-    // a new point then misses the last two steps' points (<= 1/16 of the graph) instead of the last one's.
-    bool pipe = cap > 1 && cfg.has_heuristic;
-    if (const char* e = test_env("IDIST_BUILD_PIPELINE")) pipe = pipe && e[0] != '0';
-    // the descents (8-12 waves per CU saturate their HBM stream) leave wave slots and LDS to the other stream
-    uint32_t a_waves = tab16 ? 4u : 3u;
-    if (const char* e = test_env("IDIST_BUILD_A_WAVES")) a_waves = (uint32_t)std::min(8, std::max(1, atoi(e)));
-    // the descent's register budget (quotient set only): 256 registers per wave (two waves fit a SIMD: the update stream's
-    // waves find room on every SIMD) or 512 (IDIST_BUILD_A_REGS=512, more rounds in flight per wave).  C3: 1.26 vs 1.29-1.32 s
-    // Runtime-geometry rows (any dimension without a compile-time instantiation): the register tile, not the row, bounds what a
-    // wave keeps on the wire, and the 256-register tile (2 x 3 rounds x 4 blocks = 24 KB) is too little at four waves per
-    // CU: one 512-register wave per SIMD (2 x 4 x 8 = 64 KB each) builds 1M x 1024-d in 4.35 s instead of 9.6 s and 1M x 384-d
-    // in 1.98 s instead of 2.66 s (profiles/r04/probe_r04d_build_dim*.jsonl) although the update stream then only runs where a
-    // descent wave has retired.
-    // Which register budget the descents take (same graphs either way; round 5):
-    //   * the 128-d instantiation (4 blocks): one fat wave per SIMD at EVERY size — C2 100k x 128: 0.110 against 0.121 s (five to
-    //     eight thin waves per CU: 0.117-0.122 s); 300k / 600k / 1M x 128: 0.245 / 0.449 / 0.713 s against 0.286 / 0.550 / 0.915 s
-    //     (profiles/r05/probe_r05c_build_descent_waves_c2.jsonl, probe_r05p_build_regs_mid_size_short_rows.jsonl);
-    //   * 300-d and 768-d rows: two 256-register waves per SIMD, also where the index sits in the Infinity Cache (C3 1.26 against
-    //     1.29-1.32 s, C4 2.78-2.83 against 3.00-3.06 s; 40k x 768: 0.139 against 0.153 s; 60k-200k x 300: within 2 %,
-    //     probe_r05q_build_regs_cache_resident_long_rows.jsonl);
-    //   * runtime-geometry rows of at most 12 blocks (<= 384-d) fit the 256-register tile whole (<6 blocks, 3 rounds>, two groups in
-    //     flight) and build faster on it — 1M x 64 / 100 / 200 / 384-d: 0.91 / 1.11 / 1.30 / 1.75 s against 1.18 / 1.38 / 1.55 / 1.96 s;
-    //     longer rows keep the fat waves (512-d: 2.35 against 3.12 s, 500k x 1024-d: 2.26 against 4.19 s; probe_r05g_*, probe_r05p_*).
-    const bool rows128 = ix->L.nb == 4 && ix->L.rs == 0 && ix->L.tail == 0;
-    bool a_regs256 = tab16 && !rows128 && (!rt_geometry || ix->L.nb <= 12u);
-    if (const char* e = test_env("IDIST_BUILD_A_REGS")) a_regs256 = tab16 && atoi(e) == 256;
-    // (Fat descent waves take a SIMD's whole register file: where four of them sit on a CU, nothing of the update stream runs until
-    //  one retires — at 1024-d the selection's launches stretch to the descents' 13 ms and a step's period is 16.5 ms for 12.9 ms of
-    //  descents, profiles/r05/trace_chain_r05i_build_500k_dim1024.json.  Measured and not kept: fewer descent waves per step, so that some
-    //  SIMDs stay free — 960 / 896 / 768 waves build 500k x 1024-d in 2.25 / 2.31 / 2.51 s against 2.20 s, probe_r05j; the update
-    //  streams at the highest priority — no difference at 1024 / 512 / 768 / 300-d, probe_r05k.)
-    // steps of at most two insertions per CU run four waves per insertion (IDIST_BUILD_QUAD=0: never)
-    const bool a_quad = !(test_env("IDIST_BUILD_QUAD") && test_env("IDIST_BUILD_QUAD")[0] == '0');
-    const uint32_t quad_B = (uint32_t)ix->n_cu * 2u;
-    // Narrow steps (four waves per insertion: their time does not depend on their width — one descent ≈ 0.45 ms) hold g / 8
-    // insertions until they stop being narrow, wide ones g / 32: the first 16k points of a build take ≈ 60 steps instead of
-    // ≈ 180 (100k x 128: 0.156 -> 0.122 s, 20k x 128: 0.078 -> 0.043 s, C3 -2.6 %; recall@10 unchanged to the fourth digit at
-    // 5k / 20k / 100k / 1M points, profiles/r04/probe_r04_build_growth_*.jsonl).  IDIST_BUILD_GROWTH=<d> (A/B knob, 8..32): g / d.
-    uint32_t growth_div = 8u;
-    if (const char* e = test_env("IDIST_BUILD_GROWTH")) growth_div = (uint32_t)std::min(32, std::max(8, atoi(e)));
-    // what one CU's LDS holds of them (the sequential schedule runs nothing beside the descents)
-    const uint32_t a_waves_max = std::max<uint32_t>(1u, std::min<uint32_t>(8u, (uint32_t)((160u * 1024u) / smem)));
-    a_waves = std::min(a_waves, a_waves_max);
-    uint32_t* d_zero2 = nullptr;
-    hipStream_t s1 = nullptr, s2 = nullptr, s3 = nullptr, s4 = nullptr;
-    hipEvent_t evA[2] = {nullptr, nullptr}, evS[2] = {nullptr, nullptr}, evA2[2] = {nullptr, nullptr}, evC = nullptr;
-    // Narrow steps (the growth phase of every layer: fewer insertions than the chip has room for) are bound by the latency of
-    // one descent plus five dependent launches, not by throughput, so there the two parity chains of the pipeline
-    //     descents(k) -> selection(k) -> updates(k) -> descents(k + 2)
-    // get streams of their own: the descents of odd steps (s3) run beside those of even steps (s1), and the new points'
-    // selection (s4: matrix cores and LDS) beside the previous step's neighbour updates (s2: dependent gathers).  Everything
-    // a launch owns is kept per parity for that — visited bitmaps, work-queue heads, step-A outputs, the inboxes the selection
-    // hands to the updates.  Wide steps saturate the memory system whatever the layout (profiles/r04/probe_r04_build_schedule:
-    // the extra overlap costs 2 %), so they keep one descent stream and one update stream.
-    // IDIST_BUILD_STREAMS=off | narrow (default) | all.
-    int stream_mode = 1;
-    if (const char* e = test_env("IDIST_BUILD_STREAMS")) stream_mode = e[0] == 'o' ? 0 : (e[0] == 'a' ? 2 : 1);
-    bool two_a = !tie_spill && stream_mode != 0;
-    bool own_a2 = stream_mode != 0;
-    auto release = [&]() {
-        hipFree(d_zero2);
-        hipFree(d_ext_work);
-        if (s1) hipStreamDestroy(s1);
-        if (s2) hipStreamDestroy(s2);
-        if (s3) hipStreamDestroy(s3);
-        if (s4) hipStreamDestroy(s4);
-        for (int i = 0; i < 2; i++) { if (evA[i]) hipEventDestroy(evA[i]); if (evS[i]) hipEventDestroy(evS[i]); if (evA2[i]) hipEventDestroy(evA2[i]); }
-        if (evC) hipEventDestroy(evC);
-        hipFree(d_nbr_dist); hipFree(d_row_nsel); hipFree(d_slow); hipFree(d_nbr_aux); hipFree(d_wbuf); hipFree(d_wcount); hipFree(d_dlog_log); hipFree(d_dlog_pd);
-        hipFree(d_vis); hipFree(d_tie_spill); hipFree(d_edge_pid); hipFree(d_edge_dist); hipFree(d_head);
-        hipFree(d_next); hipFree(d_touched); hipFree(d_small); hipFree(d_stats);
-        if (e0) hipEventDestroy(e0);
-        if (e1) hipEventDestroy(e1);
-    };
-#define BCHK(expr)                                                                                  \
-    do {                                                                                            \
-        hipError_t _e = (expr);                                                                     \
-        if (_e != hipSuccess) {                                                                     \
-            release();                                                                              \
-            return fail(IDIST_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-        }                                                                                           \
-    } while (0)
-    if (ext) BCHK(hipMalloc((void**)&d_ext_work, (size_t)ext_cap * 8));
-    two_a = two_a && pipe;
-    const size_t vis_words = (size_t)slots * vg.slot_words;            // one set of visited bitmaps per descent stream
-    BCHK(hipMalloc((void**)&d_vis, vis_words * 4 * (two_a ? 2 : 1)));
-    BCHK(hipMemset(d_vis, 0, vis_words * 4 * (two_a ? 2 : 1)));
-    if (tie_spill) BCHK(hipMalloc((void**)&d_tie_spill, (size_t)slots * n * 8));
-    BCHK(hipMalloc((void**)&d_nbr_dist, (size_t)n * IDIST_M2 * 4));
-    BCHK(hipMemset(d_nbr_dist, 0, (size_t)n * IDIST_M2 * 4));
-    BCHK(hipMalloc((void**)&d_nbr_aux, (size_t)n * IDIST_M2 * 4));
-    BCHK(hipMemset(d_nbr_aux, 0, (size_t)n * IDIST_M2 * 4));
-    BCHK(hipMalloc((void**)&d_row_nsel, (size_t)n * 4));
-    BCHK(hipMemset(d_row_nsel, 0, (size_t)n * 4));
-    own_a2 = own_a2 && pipe;
+    if (p.ext) CHK(sc.alloc(&d_ext_work, p.ext_cap));
+    const size_t vis_words = (size_t)p.slots * vg.slot_words;            // one set of visited bitmaps per descent stream
+    CHK(sc.alloc(&d_vis, vis_words * (two_a ? 2 : 1)));
+    HIPCHK(hipMemset(d_vis, 0, vis_words * 4 * (two_a ? 2 : 1)));
+    if (tie_spill) CHK(sc.alloc(&d_tie_spill, (size_t)p.slots * n));
+    CHK(sc.alloc(&d_nbr_dist, (size_t)n * IDIST_M2));
+    HIPCHK(hipMemset(d_nbr_dist, 0, (size_t)n * IDIST_M2 * 4));
+    CHK(sc.alloc(&d_nbr_aux, (size_t)n * IDIST_M2));
+    HIPCHK(hipMemset(d_nbr_aux, 0, (size_t)n * IDIST_M2 * 4));
+    CHK(sc.alloc(&d_row_nsel, (size_t)n));
+    HIPCHK(hipMemset(d_row_nsel, 0, (size_t)n * 4));
     const size_t nib = own_a2 ? 2 : 1;                                   // inbox sets
-    BCHK(hipMalloc((void**)&d_slow, nib * n_touch * 4));
+    CHK(sc.alloc(&d_slow, nib * n_touch));
     const size_t np = pipe ? 2 : 1;       // step-A outputs are double-buffered in the pipelined schedule
-    BCHK(hipMalloc((void**)&d_wbuf, np * cap * cfg.ef_construction * 8));
-    BCHK(hipMalloc((void**)&d_wcount, np * cap * 4));
-    const size_t dl_n = cfg.has_heuristic ? (np * cap) << dl_shift : 64;   // the simple splice looks nothing up
-    BCHK(hipMalloc((void**)&d_dlog_log, dl_n * 8));
-    BCHK(hipMalloc((void**)&d_dlog_pd, dl_n * 8));
+    CHK(sc.alloc(&d_wbuf, np * cap * cfg.ef_construction));
+    CHK(sc.alloc(&d_wcount, np * cap));
+    const size_t dl_n = cfg.has_heuristic ? (np * cap) << p.dl_shift : 64;   // the simple splice looks nothing up
+    CHK(sc.alloc(&d_dlog_log, dl_n));
+    CHK(sc.alloc(&d_dlog_pd, dl_n * 2));
     if (pipe) {
-        BCHK(hipMalloc((void**)&d_zero2, (size_t)n * IDIST_M2 * 4));
-        BCHK(hipMemset(d_zero2, 0xFF, (size_t)n * IDIST_M2 * 4));
-        BCHK(hipStreamCreateWithFlags(&s1, hipStreamNonBlocking));
-        BCHK(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
-        if (two_a) BCHK(hipStreamCreateWithFlags(&s3, hipStreamNonBlocking));
+        CHK(zero2.grow((size_t)n * IDIST_M2 * 4));
+        HIPCHK(hipMemset(zero2, 0xFF, (size_t)n * IDIST_M2 * 4));
+        CHK(s1.create());
+        CHK(s2.create());
+        if (two_a) CHK(s3.create());
         if (own_a2) {
-            BCHK(hipStreamCreateWithFlags(&s4, hipStreamNonBlocking));
-            for (int i = 0; i < 2; i++) BCHK(hipEventCreate(&evA2[i]));
-            BCHK(hipEventCreate(&evC));
+            CHK(s4.create());
+            for (int i = 0; i < 2; i++) CHK(evA2[i].create());
+            CHK(evC.create());
         }
-        for (int i = 0; i < 2; i++) { BCHK(hipEventCreate(&evA[i])); BCHK(hipEventCreate(&evS[i])); }
+        for (int i = 0; i < 2; i++) { CHK(evA[i].create()); CHK(evS[i].create()); }
     }
-    BCHK(hipMalloc((void**)&d_edge_pid, nib * n_edges * 4));
-    BCHK(hipMalloc((void**)&d_edge_dist, nib * n_edges * 4));
-    BCHK(hipMalloc((void**)&d_next, nib * n_edges * 4));
-    BCHK(hipMalloc((void**)&d_head, nib * (size_t)n * 4));
-    BCHK(hipMemset(d_head, 0xFF, nib * (size_t)n * 4));
-    BCHK(hipMalloc((void**)&d_touched, nib * n_touch * 4));
-    BCHK(hipMalloc((void**)&d_small, 256));
-    BCHK(hipMemset(d_small, 0, 256));
-    BCHK(hipMalloc((void**)&d_stats, 256));
-    BCHK(hipMemset(d_stats, 0, 256));
-    BCHK(hipEventCreate(&e0));
-    BCHK(hipEventCreate(&e1));
-
-    // Round 6: the descents of concurrent steps run with the reject filter in front of their distance passes (§4.5) — the compact
-    // copy of the rows is made now (every row is in place before the first insertion), the log takes bound-form entries for the
-    // candidates the filter turned down, step B resolves them (dlog_resolve).  IDIST_BUILD_FILTER=0 (test knob): without.
-    // Rows of at least 192 floats: C3 1.20 -> 1.03 s, 1M x 768 2.82 -> 2.01 s, 1M x 384 1.71 -> 1.29 s, 1M x 200 1.22 -> 1.12 s
-    // (probe_r06v_build_filter_128_recheck.jsonl); 128-d rows lose (a 192-B compact
-    // row saves little of a 512-B one and their fat unfiltered descents are faster: 1M x 128 0.70 -> 0.85 s, C2 0.107 -> 0.118 s) and
-    // keep the unfiltered descents (profiles/probe_r06g_build_filter_c3.jsonl, probe_r06h_build_filter_dims.jsonl; same graphs).
-    // IDIST_BUILD_FILTER=1 (test knob) forces it for every geometry the filter applies to.
-    const char* bf_env = test_env("IDIST_BUILD_FILTER");
-    bool build_filter = cfg.has_heuristic && !ext && tab16 && knobs.filter && filter_applies(ix) &&
-                        (has_template_geometry(ix->L) || filt_stride(ix->L.stride) <= 128u * (uint32_t)kFiltRtChunks) &&   // (the thin tile)
-                        (bf_env ? bf_env[0] != '0' : ix->L.stride >= 192u);
-    if (build_filter) {
-        CHK(filter_ensure(ix, false));      // (the descents read the identity table; basis and policy wait for the first wide search)
-        build_filter = ix->filt_state.load(std::memory_order_acquire) == 1;
-    }
-    // (fat filtered descents for runtime-geometry rows beyond the thin tile: 500k x 1024 / 1536-d 2.04 / 2.78 against 2.10 / 3.13 s —
-    //  profiles/probe_r06r_build_fat_filtered_1024.jsonl — not worth their compile time: those descents stay unfiltered)
+    CHK(sc.alloc(&d_edge_pid, nib * n_edges));
+    CHK(sc.alloc(&d_edge_dist, nib * n_edges));
+    CHK(sc.alloc(&d_next, nib * n_edges));
+    CHK(sc.alloc(&d_head, nib * (size_t)n));
+    HIPCHK(hipMemset(d_head, 0xFF, nib * (size_t)n * 4));
+    CHK(sc.alloc(&d_touched, nib * n_touch));
+    CHK(sc.alloc(&d_small, (size_t)kSmallWords));
+    HIPCHK(hipMemset(d_small, 0, kSmallWords * 4));
+    CHK(sc.alloc(&d_stats, 32));
+    HIPCHK(hipMemset(d_stats, 0, 256));
+    CHK(e0.create());
+    CHK(e1.create());
+    if (p.wants_filter) CHK(filter_ensure(ix, false));      // (the descents read the identity table; basis and policy wait for the first wide search)
+    resolve_build_filter(p, ix->filt_state.load(std::memory_order_acquire) == 1);
     IndexView view = ix->view();
-    if (!build_filter) view.f = FilterView{};
-    // (one FAT filtered descent wave per SIMD, the search's layout for 768-d rows, builds 1M x 768 in 2.56 s against 2.37 s on the thin
-    //  ones: the update stream needs the registers — profiles/probe_r06n_build_fat_768.jsonl)
+    if (!p.filtered) view.f = FilterView{};
+    uint32_t* const smallS = d_small + (pipe ? kSmallCountersPipe : kSmallCounters);   // step A2/B/B2 counters (own stream)
+    uint32_t* const d_status = d_small + (pipe ? kSmallStatusPipe : kSmallStatus);
     BuildArgs a{};
     a.top = top;
     a.efc = cfg.ef_construction;
-    a.wcap = wcap;
+    a.wcap = p.wcap;
     a.keep_pruned = cfg.keep_pruned ? 1u : 0u;
     a.has_heuristic = cfg.has_heuristic ? 1u : 0u;
     a.use_bloom = knobs.bloom ? 1u : 0u;
@@ -1077,226 +1036,147 @@ idist_status run_build(idist_index* ix, idist_progress* prog, bool tie_spill) {
     a.row_nsel = d_row_nsel;
     a.nbr_aux = d_nbr_aux;
     a.slow = d_slow;
-    a.rt = rt;
-    a.n_touched = d_small;
-    a.queue = d_small + 1;
-    a.n_slow = d_small + 3;      // == &queue[2]
-    a.status = d_small + 8;
+    a.rt = p.rt;
+    a.n_touched = smallS;
+    a.queue = d_small + kSmallQueueA;
+    a.n_slow = d_small + kSmallCounters + kSmallNSlow;
+    a.status = d_status;
     a.dlog_log = d_dlog_log;
     a.dlog_pd = d_dlog_pd;
-    a.tab_log2 = tab_log2;
-    a.tab16 = tab16 ? 1u : 0u;
-    a.ubits = tab16 ? q16_universe_bits(n, tab_log2) : 0u;
-    a.dl_shift = dl_shift;
-    a.use_dlog = test_env("IDIST_BUILD_NO_DLOG") ? 0u : 1u;
+    a.tab_log2 = p.tab_log2;
+    a.tab16 = p.tab16 ? 1u : 0u;
+    a.ubits = p.ubits;
+    a.dl_shift = p.dl_shift;
+    a.use_dlog = p.use_dlog ? 1u : 0u;
     a.wbuf = d_wbuf;
     a.wcount = d_wcount;
-    a.rt2 = rt2;
-    a.fc = fc;
-    a.tie_cap = tie_cap;
+    a.rt2 = p.rt2;
+    a.fc = p.fc;
+    a.tie_cap = f.tie_cap;
     a.tie_spill = d_tie_spill;
     a.tie_spill_cap = tie_spill ? n : 0u;
-    if (const char* e = test_env("IDIST_BUILD_CHUNK")) a.chunk = (uint32_t)atoi(e);
-    const size_t smemF = smem_bytes_update_fast(ix->L.stride);
-    [[maybe_unused]] const bool classic = knobs.classic;   // (test build: IDIST_VARIANT_BUILD)
-    const bool no_fast = test_env("IDIST_BUILD_NO_FAST") != nullptr;   // test knob: route every update through B2
+    a.chunk = p.chunk;
     a.stats = d_stats;
-
     uint32_t cum[IDIST_MAX_LAYERS + 1];
     cum[0] = n;
     for (uint32_t l = 1; l <= top; l++) cum[l] = ix->layer_len[l - 1];
-
     // the set-up above ran on the null stream, which the pipeline's non-blocking streams do not wait for
-    if (pipe) BCHK(hipDeviceSynchronize());
-    hipStream_t stream = pipe ? s1 : nullptr;
-    uint32_t* zbuf[2] = {ix->d_zero, pipe ? d_zero2 : ix->d_zero};     // copy k&1 holds the state after step k
-    uint32_t* const smallS = d_small + (pipe ? 16 : 0);                // step A2/B/B2 counters (own stream)
-    uint32_t* const d_status = d_small + (pipe ? 32 : 8);
-    a.n_touched = smallS;
-    a.status = d_status;
+    if (pipe) HIPCHK(hipDeviceSynchronize());
+
+    // ---- the loop (a build that is not pipelined has made no stream: every role below is the null stream)
+    const hipStream_t stream = s1;
+    const hipStream_t descent_streams[3] = {s1, s3, s2}, select_streams[2] = {s2, s4};   // by DescentStream / SelectStream
+    uint32_t* zbuf[2] = {ix->d_zero, pipe ? zero2.p : ix->d_zero};     // copy k&1 holds the state after step k
     uint64_t n_batches = 0;
     uint32_t prev_start = 0, prev_count = 0;
-    BCHK(hipEventRecord(e0, stream));
+    HIPCHK(hipEventRecord(e0, stream));
     for (int layer = (int)top; layer >= 0; layer--) {                    // core/lib.rs:304
         const uint32_t end = cum[layer];
         uint32_t g = (uint32_t)layer == top ? 1u : std::max(cum[layer + 1], 1u);   // ranges, :275-281
         a.layer = (uint32_t)layer;
         bool first_of_layer = true;
         while (g < end) {
-            // top layer is sequential in the reference (:313-314); below, at most `cap` inserts run
-            // concurrently (:316-318) and never more than 1/32 of the graph they search (1/8 while the step is narrow).
-            uint32_t B = 1;
-            if (cap > 1 && (uint32_t)layer != top && g >= 64) B = std::min(cap, std::max(std::min(g / growth_div, quad_B), g / 32u));
-            B = std::min(B, end - g);
+            const uint64_t k = n_batches + 1;                              // step number, 1-based
+            const BuildStep st = plan_build_step(p, top, (uint32_t)layer, g, end, k, first_of_layer);
+            const uint32_t B = st.B;
+            const int par = st.par;
             a.start = g;
             a.count = B;
-            const uint64_t k = n_batches + 1;                              // step number, 1-based
-            const int par = (int)(k & 1u);
-            const bool alt = stream_mode == 2 || (stream_mode == 1 && B <= quad_B);   // this step on the extra streams
-            // a sequential step (B = 1: the top layer, the first 63 points) depends on the whole previous step anyway: all of its
-            // launches go to the update stream — same-stream boundaries (~2 us) instead of three cross-stream event hops (~27 us each
-            // in the trace of profiles/r05/trace_chain_r05b_build_c2.json: 74 of the 179 us such a step took)
-            // Only where every descent stream has its own queue head, visited bitmaps and tie bags (two_a): with ONE set of them (a build
-            // on the HBM tie bags, IDIST_BUILD_STREAMS=off) the last sequential step's descent on s2 and the next, concurrent step's
-            // descent on s1 — which waits for the step BEFORE it only — would share them.
-            const bool seq1 = pipe && two_a && B == 1;
-            hipStream_t sA = pipe ? (seq1 ? s2 : (two_a && alt && par ? s3 : s1)) : stream, sS = pipe ? s2 : stream;
-            IndexView viewA = view, viewS = view;
-            BuildArgs aA = a;
+            BuildStepIo io;
+            io.k = k;
+            io.sA = descent_streams[(int)st.descent_stream];
+            io.sA2 = select_streams[(int)st.select_stream];
+            io.s2 = s2;
+            io.own_a2 = own_a2;
+            io.ext_work = d_ext_work;
+            io.viewA = io.viewS = view;
+            BuildArgs& aA = io.aA;
+            aA = a;
             if (pipe) {
-                // a sequential (B = 1) step reads the previous step's state, a concurrent one the state before that.
-                // The first step of a layer reads the previous step's state too: the snapshot of the layer above was
-                // taken from it (s1 has waited for it already), and a descent that enters the zero layer through a
-                // node of that last step must find its row, not the all-INVALID one of the older copy.
-                const int lag = B > 1 && !first_of_layer ? 2 : 1;
-                if (k > (uint64_t)lag) BCHK(hipStreamWaitEvent(sA, evS[(k - lag) & 1u], 0));
-                viewA.zero = zbuf[(k - lag) & 1u];
-                viewS.zero = zbuf[par];
-                aA.queue = d_small + (two_a && par ? 48 : 1);             // step A queue head, one per descent stream
+                if (k > (uint64_t)st.lag) HIPCHK(hipStreamWaitEvent(io.sA, evS[(k - st.lag) & 1u], 0));
+                io.viewA.zero = zbuf[(k - st.lag) & 1u];
+                io.viewS.zero = zbuf[par];
+                aA.queue = d_small + (two_a && par ? kSmallQueueA1 : kSmallQueueA);   // step A queue head, one per descent stream
                 if (two_a && par) aA.visited = d_vis + vis_words;
-                aA.dlog_log = d_dlog_log + (((size_t)par * cap) << dl_shift);
-                aA.dlog_pd = d_dlog_pd + (((size_t)par * cap) << (dl_shift + 1u));
+                aA.dlog_log = d_dlog_log + (((size_t)par * cap) << p.dl_shift);
+                aA.dlog_pd = d_dlog_pd + (((size_t)par * cap) << (p.dl_shift + 1u));
                 aA.wbuf = d_wbuf + (size_t)par * cap * cfg.ef_construction;
                 aA.wcount = d_wcount + (size_t)par * cap;
-                BCHK(hipMemsetAsync(aA.queue, 0, 4, sA));
+                HIPCHK(hipMemsetAsync(aA.queue, 0, 4, io.sA));
+                io.evA = evA[par];
+                io.evA2 = evA2[par];
+                io.evC = evC;
             } else {
-                BCHK(hipMemsetAsync(d_small, 0, 32, sA));                 // n_touched, queue heads, n_slow
+                HIPCHK(hipMemsetAsync(d_small, 0, 32, io.sA));            // n_touched, queue heads, n_slow
             }
-            const uint32_t gridA = std::min(B, std::min<uint32_t>(slots, (uint32_t)ix->n_cu * (pipe ? a_waves : std::min(a_waves_max, a_regs256 ? 8u : 4u))));
-            const uint32_t gridB = (uint32_t)std::min<size_t>(std::min<size_t>((size_t)B * IDIST_M2, g), (size_t)ix->n_cu * 16);
-            const uint32_t gridS = std::min<uint32_t>(gridB, (uint32_t)ix->n_cu * 6);
-            const uint32_t gridA2 = std::min<uint32_t>(B, (uint32_t)ix->n_cu * 4);
-            const uint32_t gridA2m = std::min<uint32_t>(B, (uint32_t)ix->n_cu * 2);
-            BuildArgs aS = aA;                                             // same step-A outputs, own counters
-            uint32_t* const cnt = smallS + (own_a2 && par ? 8 : 0);        // this step's n_touched / queue heads / n_slow
+            BuildArgs& aS = io.aS;
+            aS = aA;                                                       // same step-A outputs, own counters
+            uint32_t* const cnt = smallS + (own_a2 && par ? kSmallBlock : 0);   // this step's n_touched / queue heads / n_slow
+            io.cnt = cnt;
             aS.n_touched = cnt;
             aS.queue = cnt + 1;
-            aS.n_slow = cnt + 3;
+            aS.n_slow = cnt + kSmallNSlow;
             aS.visited = d_vis;
             if (own_a2 && par) {                                           // this step's inboxes
                 aS.edge_pid = d_edge_pid + n_edges; aS.edge_dist = d_edge_dist + n_edges; aS.next = d_next + n_edges;
                 aS.head = d_head + n; aS.touched = d_touched + n_touch; aS.slow = d_slow + n_touch;
             }
             // (carry-over of the previous step's rows: its touched list)
-            const uint32_t* const prev_touched = own_a2 ? d_touched + (par ? 0 : n_touch) : a.touched;
-            const uint32_t* const prev_cnt = own_a2 ? smallS + (par ? 0 : 8) : smallS;
-            hipStream_t sA2 = own_a2 && alt && !seq1 ? s4 : sS;
-            BuildArgs af = aS;
-            af.efc = no_fast ? 0u : cfg.ef_construction;                  // efc = 0 makes the fast kernel defer everything
-#ifdef IDIST_VARIANTS
-#define IDIST_VARIANT_BUILD(NB_, RS_, TAIL_)                                                                          \
-    else if (classic && tab16) {                                                                                      \
-        auto kA16 = build_insert_kernel<NB_, RS_, TAIL_, kWalkClassicOnChipQ16>;                                         \
-        IDIST_LAUNCH(kA16, gridA, 64, smem, sA, viewA, aA);                                                           \
-    } else if (classic) {                                                                                             \
-        auto kA = build_insert_kernel<NB_, RS_, TAIL_, kWalkClassicOnChipIds>;                                           \
-        IDIST_LAUNCH(kA, gridA, 64, smem, sA, viewA, aA);                                                             \
-    }
-#else
-#define IDIST_VARIANT_BUILD(NB_, RS_, TAIL_)
-#endif
-#define LAUNCH_BUILD(NB_, RS_, TAIL_)                                                              \
-    {                                                                                              \
-        auto kAo = build_insert_kernel<NB_, RS_, TAIL_, kWalkFatIds>;                        \
-        auto kAo16 = build_insert_kernel<NB_, RS_, TAIL_, kWalkFatQ16>;                      \
-        /* two descent waves per SIMD: 256 registers each, fewer rounds in flight per wave, more waves */ \
-        /* narrow steps (the growth phase of a layer, max_batch = 1): four waves per insertion, like narrow search batches */ \
-        auto kAq16 = build_insert_kernel<NB_, RS_, TAIL_, kWalkFourWaveQ16>;                 \
-        auto kAo16w2 = build_insert_kernel<NB_, RS_, TAIL_, walk_two_per_simd(NB_)>;          \
-        /* ... and with the reject filter in front of the distance passes (thin: one f32 round in flight, query fragment from LDS) */ \
-        auto kF = build_update_fast_kernel<NB_, RS_, TAIL_>;                                       \
-        auto kB = build_update_kernel<NB_, RS_, TAIL_>;                                            \
-        auto kP = build_update_simple_kernel<NB_, RS_, TAIL_>;                                     \
-        auto kA2 = build_select_kernel<NB_, RS_, TAIL_>;                                           \
-        auto kX = build_extend_kernel<NB_, RS_, TAIL_>;                                            \
-        auto kA2m = build_select_mfma_kernel<NB_, RS_, TAIL_>;                                     \
-        if (ext) { IDIST_LAUNCH(kX, 1, 64, smemX, sA, viewA, aA, d_ext_work, ext_cap); }           \
-        IDIST_VARIANT_BUILD(NB_, RS_, TAIL_)                                                       \
-        else if (tab16 && a_quad && B <= quad_B) { IDIST_LAUNCH(kAq16, std::min(B, slots), 256, smem, sA, viewA, aA); } \
-        else if (tab16 && build_filter) { launched_a = DescentLaunch<NB_, RS_, TAIL_, walk_thin_filter(2), GeoKernels<NB_>::thin_descent>::go(gridA, smem, sA, viewA, aA); } \
-        else if (tab16 && a_regs256) { IDIST_LAUNCH(kAo16w2, gridA, 64, smem, sA, viewA, aA); }    \
-        else if (tab16) { IDIST_LAUNCH(kAo16, gridA, 64, smem, sA, viewA, aA); }                   \
-        else { IDIST_LAUNCH(kAo, gridA, 64, smem, sA, viewA, aA); }                                \
-        if (pipe) {                                                                                \
-            BCHK(hipEventRecord(evA[par], sA));                                                    \
-            BCHK(hipStreamWaitEvent(sA2, evA[par], 0));                                            \
-            /* this step's inbox set is the one step k - 1's carry-over reads its touched list from (evC, recorded below) */ \
-            if (sA2 != s2 && k > 1) BCHK(hipStreamWaitEvent(sA2, evC, 0));                         \
-            if (sA2 == s2) {                                                                       \
-                IDIST_LAUNCH(copy_rows_kernel, 1024, 64, 0, s2, zbuf[par ^ 1], zbuf[par], prev_touched, prev_cnt, prev_start, prev_count); \
-                if (own_a2) BCHK(hipEventRecord(evC, s2));                                         \
-            }                                                                                      \
-            BCHK(hipMemsetAsync(cnt, 0, 32, sA2));                                                 \
-        }                                                                                          \
-        if (ext) {                                                                                 \
-        } else if (cfg.has_heuristic) {                                                            \
-            if (a2_mfma) { IDIST_LAUNCH(kA2m, gridA2m, 256, smemA2m, sA2, viewS, aS); }            \
-            else { IDIST_LAUNCH(kA2, gridA2, 64, smemA2, sA2, viewS, aS); }                        \
-            if (pipe && sA2 != s2) {                                                               \
-                BCHK(hipEventRecord(evA2[par], s4));                                               \
-                BCHK(hipStreamWaitEvent(s2, evA2[par], 0));                                        \
-                IDIST_LAUNCH(copy_rows_kernel, 1024, 64, 0, s2, zbuf[par ^ 1], zbuf[par], prev_touched, prev_cnt, prev_start, prev_count); \
-                BCHK(hipEventRecord(evC, s2));                                                     \
-            }                                                                                      \
-            IDIST_LAUNCH(kF, gridB, 64, smemF, sS, viewS, af);                                     \
-            IDIST_LAUNCH(kB, gridS, 64, smemB, sS, viewS, aS);                                     \
-        } else {                                                                                   \
-            IDIST_LAUNCH(kP, gridB, 64, (size_t)(72 * 8 + 64 * 4), sS, viewS, aS);                 \
-        }                                                                                          \
-    }
-            bool launched_a = true;
+            io.prev_touched = own_a2 ? d_touched + (par ? 0 : n_touch) : a.touched;
+            io.prev_cnt = own_a2 ? smallS + (par ? 0 : kSmallBlock) : smallS;
+            io.prev_start = prev_start;
+            io.prev_count = prev_count;
+            io.z_prev = zbuf[par ^ 1];
+            io.z_cur = zbuf[par];
+            io.af = aS;
+            io.af.efc = p.no_fast ? 0u : cfg.ef_construction;             // efc = 0 makes the fast kernel defer everything
+#define LAUNCH_BUILD(NB_, RS_, TAIL_) CHK((launch_build_step<NB_, RS_, TAIL_>(st, p, io)))
             IDIST_DISPATCH(ix->L, LAUNCH_BUILD);
-            if (!launched_a) { release(); return fail(IDIST_ERR_INTERNAL, "no filtered descent kernel for this row geometry"); }
 #undef LAUNCH_BUILD
             prev_start = g;
             prev_count = B;
             g += B;
             n_batches++;
             first_of_layer = false;
-            if (prog) IDIST_LAUNCH(progress_kernel, 1, 1, 0, sS, prog->slot, (unsigned long long)g, (unsigned long long)layer + 1ull);
-            if (pipe) BCHK(hipEventRecord(evS[par], s2));
-            if ((n_batches & 1023u) == 0) BCHK(hipGetLastError());
+            if (prog) IDIST_LAUNCH(progress_kernel, 1, 1, 0, io.s2, prog->slot, (unsigned long long)g, (unsigned long long)layer + 1ull);
+            if (pipe) HIPCHK(hipEventRecord(evS[par], s2));
+            if ((n_batches & 1023u) == 0) HIPCHK(hipGetLastError());
         }
         if (layer > 0) {                                                 // UpperNode::from_zero, :323-328
             const size_t total = (size_t)end * IDIST_M;
             const int grid = (int)std::min<size_t>((total + 255) / 256, 65536);
             // pipelined: behind the layer's last step on the update stream; the event the next steps' descents wait for
             // (the last step's) is recorded again behind it, so whichever stream they run on finds the snapshot taken
-            IDIST_LAUNCH(snapshot_kernel, grid, 256, 0, pipe ? s2 : stream, zbuf[n_batches & 1u], ix->d_upper + ix->layer_off[layer - 1] * IDIST_M, end);
-            if (pipe) BCHK(hipEventRecord(evS[n_batches & 1u], s2));       // (both the first and the second step of the next layer wait for this one)
+            IDIST_LAUNCH(snapshot_kernel, grid, 256, 0, (hipStream_t)s2, zbuf[n_batches & 1u], ix->d_upper + ix->layer_off[layer - 1] * IDIST_M, end);
+            if (pipe) HIPCHK(hipEventRecord(evS[n_batches & 1u], s2));     // (both the first and the second step of the next layer wait for this one)
         }
     }
     if (pipe) {
-        if (n_batches) BCHK(hipStreamWaitEvent(s1, evS[n_batches & 1u], 0));
-        if (test_env("IDIST_BUILD_CHECK")) {
+        if (n_batches) HIPCHK(hipStreamWaitEvent(s1, evS[n_batches & 1u], 0));
+        if (knobs.build_check) {
             // self-check: carry the last step over as well; now the two copies must agree on every row, or some
             // step's carry-over missed a row
             const int par = (int)(n_batches & 1u);
-            IDIST_LAUNCH(copy_rows_kernel, 1024, 64, 0, s1, zbuf[par], zbuf[par ^ 1], own_a2 && par ? d_touched + n_touch : a.touched,
-                         smallS + (own_a2 && par ? 8 : 0), prev_start, prev_count);
-            BCHK(hipMemsetAsync(d_small + 40, 0, 4, s1));
-            IDIST_LAUNCH(count_row_mismatch_kernel, 1024, 256, 0, s1, zbuf[0], zbuf[1], n, d_small + 40);
+            IDIST_LAUNCH(copy_rows_kernel, 1024, 64, 0, (hipStream_t)s1, zbuf[par], zbuf[par ^ 1], own_a2 && par ? d_touched + n_touch : a.touched,
+                         smallS + (own_a2 && par ? kSmallBlock : 0), prev_start, prev_count);
+            HIPCHK(hipMemsetAsync(d_small + kSmallMismatch, 0, 4, s1));
+            IDIST_LAUNCH(count_row_mismatch_kernel, 1024, 256, 0, (hipStream_t)s1, zbuf[0], zbuf[1], n, d_small + kSmallMismatch);
             uint32_t bad = 0;
-            BCHK(hipStreamSynchronize(s1));
-            BCHK(hipMemcpy(&bad, d_small + 40, 4, hipMemcpyDeviceToHost));
-            if (bad) {
-                release();
-                return fail(IDIST_ERR_INTERNAL, "pipelined build: the two copies of the zero layer differ on %u rows", bad);
-            }
+            HIPCHK(hipStreamSynchronize(s1));
+            HIPCHK(hipMemcpy(&bad, d_small + kSmallMismatch, 4, hipMemcpyDeviceToHost));
+            if (bad) return fail(IDIST_ERR_INTERNAL, "pipelined build: the two copies of the zero layer differ on %u rows", bad);
         }
-        if (n_batches & 1u) std::swap(ix->d_zero, d_zero2);              // the final state lives in copy (last step)&1
+        if (n_batches & 1u) std::swap(ix->d_zero, zero2.p);              // the final state lives in copy (last step)&1; zero2 frees the other
     }
-    BCHK(hipEventRecord(e1, stream));
-    BCHK(hipGetLastError());
-    BCHK(hipEventSynchronize(e1));
+    HIPCHK(hipEventRecord(e1, stream));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventSynchronize(e1));
     float ms = 0;
-    BCHK(hipEventElapsedTime(&ms, e0, e1));
-    uint32_t small[8] = {0};
+    HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+    uint32_t status = 0;
     unsigned long long stats[32] = {0};
-    BCHK(hipMemcpy(&small[6], d_status, 4, hipMemcpyDeviceToHost));
-    BCHK(hipMemcpy(stats, d_stats, 256, hipMemcpyDeviceToHost));
-#undef BCHK
-    release();
+    HIPCHK(hipMemcpy(&status, d_status, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(stats, d_stats, 256, hipMemcpyDeviceToHost));
     ix->stats.n_dist = stats[0];
     ix->stats.n_exp0 = stats[1];
     ix->stats.n_expU = stats[2];
@@ -1309,9 +1189,9 @@ idist_status run_build(idist_index* ix, idist_progress* prog, bool tie_spill) {
     ix->stats.n_updates_full = stats[7];
     ix->stats.n_filter_examined = stats[16];
     ix->stats.n_filter_rejected = stats[17];
-    ix->stats.filter_row_bytes = build_filter ? filt_stride(ix->L.stride) : 0u;
+    ix->stats.filter_row_bytes = p.filtered ? filt_stride(ix->L.stride) : 0u;
     // the reference's own count exists only where every selection ran in the reference's order
-    ix->stats.n_heur_ref = (ext || (cfg.has_heuristic && no_fast && !a2_mfma && cap == 1)) ? stats[8] : 0;
+    ix->stats.n_heur_ref = (p.ext || (cfg.has_heuristic && p.no_fast && !p.a2_mfma && cap == 1)) ? stats[8] : 0;
     if (prog) { prog->slot[0] = n; prog->slot[1] = 0; }
 #ifdef IDIST_PROBE
     fprintf(stderr, "{\"probe\": \"step_B_lookups\", \"n\": %u, \"updates_single_new\": %llu, \"updates_general\": %llu, \"lookups\": %llu, "
@@ -1319,8 +1199,8 @@ idist_status run_build(idist_index* ix, idist_progress* prog, bool tie_spill) {
             "\"n_updates\": %llu, \"n_updates_full\": %llu, \"n_sel_pairs\": %llu, \"n_heur_rows\": %llu}\n",
             n, stats[9], stats[10], stats[11], stats[12], stats[13], stats[14], stats[15], stats[5], stats[7], stats[3], stats[4]);
 #endif
-    ix->stats.tie_overflow = (small[6] & kStTieOverflow) ? 1 : 0;
-    return device_status_to_code(small[6], cfg.tie_policy);
+    ix->stats.tie_overflow = (status & kStTieOverflow) ? 1 : 0;
+    return device_status_to_code(status, cfg.tie_policy);
 }
 
 #ifdef IDIST_PROBE

@@ -94,6 +94,21 @@ struct Knobs {
                                       // LDS (test knob: small chunks send short lists through the global-memory strides; default 2048)
     uint32_t quad_nq = 0xFFFFFFFFu;   // IDIST_QUAD_NQ: batches up to this many queries run four waves per query (default: two
                                       // workgroups per CU, one for 768-d rows; 0 = never)
+    // the build's (plan_build, idist_build_plan.hpp; all test / A-B knobs: every variant builds the same graph)
+    uint32_t build_rt = 8;            // IDIST_BUILD_RT=<rows>: rows of the update tile (step B2) before the LDS budget trims them
+    uint32_t build_rt2 = 16;          // IDIST_BUILD_RT2=<rows>: ... of the select tile (step A2)
+    bool build_a2_tile = false;       // IDIST_BUILD_A2=tile: step A2 with the LDS-tile kernel, never the Gram matrix on MFMA
+    bool build_pipeline = true;       // IDIST_BUILD_PIPELINE=0: the sequential schedule
+    uint32_t build_a_waves = 0;       // IDIST_BUILD_A_WAVES=<1..8>: descent waves per CU of a pipelined step (0: policy)
+    int build_a_regs = -1;            // IDIST_BUILD_A_REGS=256|512: the descents' register budget (-1: policy)
+    bool build_quad = true;           // IDIST_BUILD_QUAD=0: narrow steps never run four waves per insertion
+    uint32_t build_growth = 8;        // IDIST_BUILD_GROWTH=<8..32>: narrow steps hold g / this many insertions
+    int build_streams = 1;            // IDIST_BUILD_STREAMS=off (0) | narrow (1) | all (2): which steps take the extra streams
+    int build_filter = -1;            // IDIST_BUILD_FILTER=0|1: descents never / wherever it applies with the reject filter (-1: policy)
+    bool build_dlog = true;           // IDIST_BUILD_NO_DLOG: the descents log no distances for step B
+    uint32_t build_chunk = 0;         // IDIST_BUILD_CHUNK=<items>: step B's items per dequeue (0: by load)
+    bool build_no_fast = false;       // IDIST_BUILD_NO_FAST: every update through B2
+    bool build_check = false;         // IDIST_BUILD_CHECK: a pipelined build ends by comparing the two copies of the zero layer
 };
 
 // the compact rows' formats as an index records them (SearchFacts::filt_format, Knobs::basis); include/idist.h's IDIST_FILTER_FORMAT_*

@@ -234,8 +234,9 @@ def test_build_batched_is_schedule_independent(eng, oracle, monkeypatch):
             {"IDIST_LATENCY_NQ": "0", "IDIST_WALK": "classic"}]
     if kind == "gpu":
         # (IDIST_BUILD_STREAMS=off: ONE descent stream with one queue head / visited region — the sequential steps of the growth phase
-        #  must then stay on it, run_build's `seq1`)
-        envs += [{"IDIST_BUILD_CHUNK": "1"}, {"IDIST_BUILD_CHUNK": "16"}, {"IDIST_LATENCY_NQ": "4000000000"}, {"IDIST_BUILD_STREAMS": "off"}]
+        #  must then stay on it, plan_build_step's `seq1`; =all: wide steps on the extra streams too)
+        envs += [{"IDIST_BUILD_CHUNK": "1"}, {"IDIST_BUILD_CHUNK": "16"}, {"IDIST_LATENCY_NQ": "4000000000"}, {"IDIST_BUILD_STREAMS": "off"},
+                 {"IDIST_BUILD_STREAMS": "all"}]
     else:
         # which kernel selects for the new points (Gram matrix on MFMA / LDS tile), whether step B finds its distances in
         # the published log, how early the descents' visited set spills: none of it may show in the graph
