@@ -673,7 +673,156 @@ def _as_points(points) -> np.ndarray:
     return pts
 
 
-class Hnsw:
+# -- the restricted and range searches: what `Hnsw`, `HnswMap` and `PartitionedHnsw` share --
+def _queries(queries, info) -> np.ndarray:
+    """The queries of a search call as the ABI takes them, f32 [nq, dim]; `info`: the index's IndexInfo / PartitionedInfo."""
+    q = _as_points(queries)
+    if q.shape[0] and info.n and q.shape[1] != info.dim:
+        raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
+    return q
+
+
+def _radius(radius, nq: int) -> np.ndarray:
+    """`radius` of a range call as the ABI takes it: f32 [1] (one for the batch) or [nq]."""
+    rad = np.ascontiguousarray(np.asarray(radius, dtype=np.float32).reshape(-1))
+    if rad.size != 1 and rad.size != nq:
+        raise ValueError(f"`radius` is one float or an array of nq = {nq}, got {rad.size}")
+    return rad
+
+
+def _topk_outputs(nq: int, k: int, rung_shape: tuple, counters: bool) -> tuple:
+    """The fields of an `AllowedResult`, in order, as a top-k call hands them to C; `rung_shape`: (nq,), or (nq, n_parts) of a
+    partitioned index."""
+    return (np.full((nq, k), INVALID, dtype=np.uint32), np.full((nq, k), np.inf, dtype=np.float32), np.zeros(nq, dtype=np.uint32),
+            np.full(rung_shape, RUNG_NONE, dtype=np.uint32), np.zeros((nq, 3), dtype=np.uint32) if counters else None)
+
+
+def _topk_pointers(pid, dist, cnt, rung, ctr) -> tuple:
+    return _capi.u32p(pid), _capi.f32p(dist), _capi.u32p(cnt), _capi.u32p(rung), _capi.u32p(ctr) if ctr is not None else None
+
+
+def _range_outputs(nq: int, rung_shape: tuple, counters: bool) -> tuple:
+    """(lims, rung, counters) as a range call hands them to C; `pid` and `distance` follow from `_range_fetch`."""
+    return (np.zeros(nq + 1, dtype=np.uint64), np.full(rung_shape, RUNG_NONE, dtype=np.uint32),
+            np.zeros((nq, 3), dtype=np.uint32) if counters else None)
+
+
+def _range_fetch(fetch, handle, lims, rung, ctr) -> RangeResult:
+    """The results the range call before it left behind `handle`, sized by `lims`; called for an empty total too."""
+    total = int(lims[-1])
+    pid = np.zeros(total, dtype=np.uint32)
+    dist = np.zeros(total, dtype=np.float32)
+    _lib().check(fetch(handle, _capi.u32p(pid), _capi.f32p(dist)))
+    return RangeResult(lims, pid, dist, rung, ctr)
+
+
+def _rows(r, item) -> list[list]:
+    """`item(distance, id)` of every result of an `AllowedResult` / `BatchResult`: one row per query, nearest first."""
+    return [[item(float(r.distance[i, j]), int(r.pid[i, j])) for j in range(int(r.count[i]))] for i in range(r.pid.shape[0])]
+
+
+def _range_rows(r: RangeResult, item) -> list[list]:
+    """`item(distance, id)` of every result of a `RangeResult`: one row per query, nearest first."""
+    return [[item(float(r.distance[j]), int(r.pid[j])) for j in range(int(r.lims[i]), int(r.lims[i + 1]))] for i in range(len(r.lims) - 1)]
+
+
+# A restriction is what narrows a search to some of the points.  A form knows its validation and the ctypes arguments it becomes
+# (`args(n, nq)`, which also keeps what they point into alive for as long as the form lives), its `attr` (whose handle follows the
+# leading handles of the call, or None) and whether there is `nothing` to do (read after `args`).
+class _Everything:
+    """no restriction: `search_range`"""
+    attr = None
+    nothing = False
+
+    def args(self, n: int, nq: int) -> tuple:
+        return ()
+
+
+class _Sets:
+    """one allowed set per query: (bits, n_sets, set_of)"""
+    attr = None
+
+    def __init__(self, sets, set_of):
+        self.sets, self.set_of = sets, set_of
+
+    def args(self, n: int, nq: int) -> tuple:
+        bits = allowed_bitmaps(self.sets, n)
+        so = _set_of(self.set_of, bits.shape[0], nq)
+        self._keep = (bits, so)
+        self.nothing = bits.shape[0] == 0 and nq == 0    # only then: sets with no queries still reach C, as every other form does
+        return _capi.u32p(bits), bits.shape[0], _capi.u32p(so) if so is not None else None
+
+
+class _Where:
+    """an interval of an `Attr` per query: (lo, hi, n_cond)"""
+    nothing = False
+
+    def __init__(self, attr, lo, hi):
+        self.attr, self.lo, self.hi = attr, lo, hi
+
+    def args(self, n: int, nq: int) -> tuple:
+        lo, hi, n_cond = _conditions(self.lo, self.hi, nq)
+        self._keep = (lo, hi)
+        return _capi.u32p(lo), _capi.u32p(hi), n_cond
+
+
+class _Match:
+    """a condition over the columns of an `AttrTable` per query: (idist_attr_conds *,)"""
+    nothing = False
+
+    def __init__(self, table, conds):
+        self.attr, self.conds = table, conds
+
+    def args(self, n: int, nq: int) -> tuple:
+        self._keep = _conds_arg(self.attr, self.conds, nq)    # (the struct, the arrays it points into): encoded once
+        return (C.byref(self._keep[0]),)
+
+
+class _RestrictedSearch:
+    """The two drivers behind the restricted and range searches of `Hnsw` and `PartitionedHnsw`.  The index class supplies what
+    differs: `_SEARCH`, the C symbol per (range?, restriction form); `_FETCH`, the symbol that fetches a range call's results;
+    `_lead(search)`, the handles that lead every call — the last one is the handle the fetch reads from; `_rung_shape(nq, info)`.
+    Every symbol takes: leading handles, [attr,] queries, nq, [radius, n_radius,] restriction, (k, max_rungs | max_rungs, max_total),
+    outputs.  Arguments are judged in the order queries, radius, restriction."""
+
+    def _topk(self, queries, restriction, k: int, max_rungs: int, counters: bool, search=None) -> AllowedResult:
+        info = self.info()
+        q = _queries(queries, info)
+        nq, k = q.shape[0], max(int(k), 0)                  # a negative k is clamped: for the shapes, and for C
+        rargs = restriction.args(int(info.n), nq)
+        out = _topk_outputs(nq, k, self._rung_shape(nq, info), counters)
+        if not restriction.nothing:                         # (only `_Sets` ever has: the other forms reach C with no queries too,
+            L = _lib()                                      #  where the attribute is checked against the index)
+            lead = self._lead(search)
+            attr = () if restriction.attr is None else (restriction.attr._h,)
+            L.check(getattr(L, self._SEARCH[False, type(restriction)])(*lead, *attr, _capi.f32p(q), nq, *rargs, k, int(max_rungs),
+                                                                       *_topk_pointers(*out)))
+        return AllowedResult(*out)
+
+    def _range(self, queries, radius, restriction, max_rungs: int, max_total: int, counters: bool, search=None) -> RangeResult:
+        info = self.info()
+        q = _queries(queries, info)
+        nq = q.shape[0]
+        rad = _radius(radius, nq)
+        rargs = restriction.args(int(info.n), nq)
+        lims, rung, ctr = _range_outputs(nq, self._rung_shape(nq, info), counters)
+        if restriction.nothing:
+            return RangeResult(lims, np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.float32), rung, ctr)
+        L = _lib()
+        lead = self._lead(search)
+        attr = () if restriction.attr is None else (restriction.attr._h,)
+        L.check(getattr(L, self._SEARCH[True, type(restriction)])(*lead, *attr, _capi.f32p(q), nq, _capi.f32p(rad), int(rad.size), *rargs,
+                                                                  int(max_rungs), int(max_total), _capi.u64p(lims), _capi.u32p(rung),
+                                                                  _capi.u32p(ctr) if counters else None))
+        return _range_fetch(getattr(L, self._FETCH), lead[-1], lims, rung, ctr)
+
+
+def _or_fresh(search: "Search | None") -> "Search":
+    """search=None of the `where` / `match` calls: a Search of the call's own (the sets and range calls require one)"""
+    return search if search is not None else Search()
+
+
+class Hnsw(_RestrictedSearch):
     """core/lib.rs:194-397.  Owns the points in PointId order and the device index."""
 
     def __init__(self, handle, points: np.ndarray, ef_search: int):
@@ -806,6 +955,22 @@ class Hnsw:
                                          _capi.u32p(cnt), _capi.u32p(ctr) if counters else None))
         return BatchResult(pid, dist, cnt, ctr)
 
+    # what `_RestrictedSearch` asks of the index class
+    _SEARCH = {(False, _Sets): "idist_search_batch_allowed_sets",
+               (False, _Where): "idist_search_batch_attr",
+               (False, _Match): "idist_search_batch_match",
+               (True, _Everything): "idist_search_batch_range",
+               (True, _Sets): "idist_search_batch_range_allowed_sets",
+               (True, _Where): "idist_search_batch_range_attr",
+               (True, _Match): "idist_search_batch_range_match"}
+    _FETCH = "idist_search_ctx_range_fetch"
+
+    def _lead(self, search: Search) -> tuple:
+        return self._h, search._bind(self)
+
+    def _rung_shape(self, nq: int, info) -> tuple:
+        return (nq,)
+
     def search_allowed(self, queries, allowed, k: int, search: Search, max_rungs: int = -1, counters: bool = False) -> AllowedResult:
         """The k nearest among the points of `allowed` (idist_search_batch_allowed; 1 <= k <= ef_search): `Hnsw::search` at
         ef_search, 4 ef_search, ... 4096, filtered — the first rung that holds k allowed points answers — and an exact scan of the
@@ -813,23 +978,16 @@ class Hnsw:
         order or an integer array of PointIds, one set for the whole batch.  `max_rungs`: -1 the whole ladder, m only its first m
         rungs, 0 the exact scan alone (the ground truth for recall).  A query that climbs the whole ladder costs about 1.3 searches
         at ef_search 4096 plus a scan of the allowed rows."""
-        q = _as_points(queries)
         info = self.info()
-        if q.shape[0] and info.n and q.shape[1] != info.dim:
-            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
+        q = _queries(queries, info)
         bits = allowed_bitmap(allowed, int(info.n))
-        nq, k = q.shape[0], int(k)
-        kk = max(k, 0)
-        pid = np.full((nq, kk), INVALID, dtype=np.uint32)
-        dist = np.full((nq, kk), np.inf, dtype=np.float32)
-        cnt = np.zeros(nq, dtype=np.uint32)
-        rung = np.full(nq, RUNG_NONE, dtype=np.uint32)
-        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
-        ctx = search._bind(self)
+        nq, k = q.shape[0], max(int(k), 0)                  # a negative k is clamped: for the shapes, and for C
+        out = _topk_outputs(nq, k, (nq,), counters)
         L = _lib()
-        L.check(L.idist_search_batch_allowed(self._h, ctx, _capi.f32p(q), nq, _capi.u32p(bits), kk, int(max_rungs), _capi.u32p(pid),
-                                             _capi.f32p(dist), _capi.u32p(cnt), _capi.u32p(rung), _capi.u32p(ctr) if counters else None))
-        return AllowedResult(pid, dist, cnt, rung, ctr)
+        # one bitmap and no set_of: a symbol of its own; always binds and calls C, with no queries too
+        L.check(L.idist_search_batch_allowed(self._h, search._bind(self), _capi.f32p(q), nq, _capi.u32p(bits), k, int(max_rungs),
+                                             *_topk_pointers(*out)))
+        return AllowedResult(*out)
 
     def search_range(self, queries, radius, search: Search, max_rungs: int = -1, max_total: int = 64 * 2**20,
                      counters: bool = False) -> RangeResult:
@@ -839,26 +997,7 @@ class Hnsw:
         distances the metric reports (`<=`); NaN is refused.  `max_rungs`: -1 the whole ladder, m only its first m rungs, 0 the exact
         scan alone (the ground truth for recall).  `max_total` bounds the number of results of the whole batch: beyond it the call
         raises instead of truncating (the default, 64 Mi results = 512 MB of keys on the device, is a choice, not a measurement)."""
-        q = _as_points(queries)
-        info = self.info()
-        if q.shape[0] and info.n and q.shape[1] != info.dim:
-            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
-        nq = q.shape[0]
-        rad = np.ascontiguousarray(np.asarray(radius, dtype=np.float32).reshape(-1))
-        if rad.size != 1 and rad.size != nq:
-            raise ValueError(f"`radius` is one float or an array of nq = {nq}, got {rad.size}")
-        lims = np.zeros(nq + 1, dtype=np.uint64)
-        rung = np.full(nq, RUNG_NONE, dtype=np.uint32)
-        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
-        ctx = search._bind(self)
-        L = _lib()
-        L.check(L.idist_search_batch_range(self._h, ctx, _capi.f32p(q), nq, _capi.f32p(rad), int(rad.size), int(max_rungs), int(max_total),
-                                           _capi.u64p(lims), _capi.u32p(rung), _capi.u32p(ctr) if counters else None))
-        total = int(lims[nq])
-        pid = np.zeros(total, dtype=np.uint32)
-        dist = np.zeros(total, dtype=np.float32)
-        L.check(L.idist_search_ctx_range_fetch(ctx, _capi.u32p(pid), _capi.f32p(dist)))
-        return RangeResult(lims, pid, dist, rung, ctr)
+        return self._range(queries, radius, _Everything(), max_rungs, max_total, counters, search)
 
     def search_range_allowed(self, queries, radius, allowed, search: Search, max_rungs: int = -1, max_total: int = 64 * 2**20,
                              counters: bool = False) -> RangeResult:
@@ -866,7 +1005,7 @@ class Hnsw:
         `allowed`: a bool array of length n or an integer array of PointIds (`allowed_bitmap`'s rules), or a ready uint32 bitmap of
         shape (1, (n + 31) // 32)."""
         a = allowed
-        if not (isinstance(a, np.ndarray) and a.ndim == 2 and a.dtype == np.uint32):
+        if not (isinstance(a, np.ndarray) and a.ndim == 2 and a.dtype == np.uint32):    # (a ready bitmap: this class only)
             a = allowed_bitmap(a, int(self.info().n))[None, :]
         nq = _as_points(queries).shape[0]
         return self.search_range_allowed_sets(queries, radius, a, np.zeros(nq, dtype=np.uint32), search, max_rungs, max_total, counters)
@@ -878,32 +1017,7 @@ class Hnsw:
         judged on the unrestricted list — but a query runs rung r only while ef_search * 4**r < 2 |set| (a longer list costs more than
         the exact step); where its rungs end, an exact scan of the set's rows answers.  `radius`, `max_rungs`, `max_total`: as
         `search_range`, `max_total` bounding the restricted total; `sets`, `set_of`: as `search_allowed_sets`."""
-        q = _as_points(queries)
-        info = self.info()
-        if q.shape[0] and info.n and q.shape[1] != info.dim:
-            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
-        nq = q.shape[0]
-        rad = np.ascontiguousarray(np.asarray(radius, dtype=np.float32).reshape(-1))
-        if rad.size != 1 and rad.size != nq:
-            raise ValueError(f"`radius` is one float or an array of nq = {nq}, got {rad.size}")
-        bits = allowed_bitmaps(sets, int(info.n))
-        so = _set_of(set_of, bits.shape[0], nq)
-        lims = np.zeros(nq + 1, dtype=np.uint64)
-        rung = np.full(nq, RUNG_NONE, dtype=np.uint32)
-        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
-        if bits.shape[0] == 0 and nq == 0:
-            return RangeResult(lims, np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.float32), rung, ctr)
-        ctx = search._bind(self)
-        L = _lib()
-        L.check(L.idist_search_batch_range_allowed_sets(self._h, ctx, _capi.f32p(q), nq, _capi.f32p(rad), int(rad.size), _capi.u32p(bits),
-                                                        bits.shape[0], _capi.u32p(so) if so is not None else None, int(max_rungs),
-                                                        int(max_total), _capi.u64p(lims), _capi.u32p(rung),
-                                                        _capi.u32p(ctr) if counters else None))
-        total = int(lims[nq])
-        pid = np.zeros(total, dtype=np.uint32)
-        dist = np.zeros(total, dtype=np.float32)
-        L.check(L.idist_search_ctx_range_fetch(ctx, _capi.u32p(pid), _capi.f32p(dist)))
-        return RangeResult(lims, pid, dist, rung, ctr)
+        return self._range(queries, radius, _Sets(sets, set_of), max_rungs, max_total, counters, search)
 
     def search_allowed_sets(self, queries, sets, set_of, k: int, search: Search, max_rungs: int = -1, counters: bool = False) -> AllowedResult:
         """`search_allowed` with several allowed sets in one call, one per query (idist_search_batch_allowed_sets): row q is exactly
@@ -911,27 +1025,7 @@ class Hnsw:
         (`allowed_bitmap`'s rules), a 2-D bool array [n_sets][n] or a ready uint32 bitmap [n_sets][(n + 31) // 32].  `set_of`: the set
         index of every query; None: query q uses set q (one set per query).  Queries start on the rung their own set's size calls
         for; the exact step reads n / 8 bytes of its set's bitmap per query on top of the allowed rows."""
-        q = _as_points(queries)
-        info = self.info()
-        if q.shape[0] and info.n and q.shape[1] != info.dim:
-            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
-        bits = allowed_bitmaps(sets, int(info.n))
-        nq, k, n_sets = q.shape[0], int(k), bits.shape[0]
-        so = _set_of(set_of, n_sets, nq)
-        kk = max(k, 0)
-        pid = np.full((nq, kk), INVALID, dtype=np.uint32)
-        dist = np.full((nq, kk), np.inf, dtype=np.float32)
-        cnt = np.zeros(nq, dtype=np.uint32)
-        rung = np.full(nq, RUNG_NONE, dtype=np.uint32)
-        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
-        if n_sets == 0 and nq == 0:
-            return AllowedResult(pid, dist, cnt, rung, ctr)
-        ctx = search._bind(self)
-        L = _lib()
-        L.check(L.idist_search_batch_allowed_sets(self._h, ctx, _capi.f32p(q), nq, _capi.u32p(bits), n_sets, _capi.u32p(so) if so is not None else None,
-                                                  kk, int(max_rungs), _capi.u32p(pid), _capi.f32p(dist), _capi.u32p(cnt), _capi.u32p(rung),
-                                                  _capi.u32p(ctr) if counters else None))
-        return AllowedResult(pid, dist, cnt, rung, ctr)
+        return self._topk(queries, _Sets(sets, set_of), k, max_rungs, counters, search)
 
     def attributes(self, values) -> Attr:
         """One uint32 per point (a tenant id, a category, a day number), in PointId order — the order of a bool `allowed` mask —
@@ -950,54 +1044,14 @@ class Hnsw:
         lo > hi is the empty set.  Row q is exactly what `search_allowed_sets` returns for the mask
         `(attr.values >= lo[q]) & (attr.values <= hi[q])` — but the masks are made on the device from the attribute that already
         lives there: nothing of the size of n is computed on the host or uploaded."""
-        q = _as_points(queries)
-        info = self.info()
-        if q.shape[0] and info.n and q.shape[1] != info.dim:
-            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
-        nq, k = q.shape[0], int(k)
-        lo_a, hi_a, n_cond = _conditions(lo, hi, nq)
-        kk = max(k, 0)
-        pid = np.full((nq, kk), INVALID, dtype=np.uint32)
-        dist = np.full((nq, kk), np.inf, dtype=np.float32)
-        cnt = np.zeros(nq, dtype=np.uint32)
-        rung = np.full(nq, RUNG_NONE, dtype=np.uint32)
-        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
-        search = search if search is not None else Search()
-        ctx = search._bind(self)
-        L = _lib()
-        L.check(L.idist_search_batch_attr(self._h, ctx, attr._h, _capi.f32p(q), nq, _capi.u32p(lo_a), _capi.u32p(hi_a), n_cond, kk,
-                                          int(max_rungs), _capi.u32p(pid), _capi.f32p(dist), _capi.u32p(cnt), _capi.u32p(rung),
-                                          _capi.u32p(ctr) if counters else None))
-        return AllowedResult(pid, dist, cnt, rung, ctr)
+        return self._topk(queries, _Where(attr, lo, hi), k, max_rungs, counters, _or_fresh(search))
 
     def search_range_where(self, queries, radius, attr: Attr, lo, hi=None, search: Search | None = None, max_rungs: int = -1,
                            max_total: int = 64 * 2**20, counters: bool = False) -> RangeResult:
         """Every point within `radius` whose attribute lies in the query's interval (idist_search_batch_range_attr): row q is
         exactly what `search_range_allowed_sets` returns for the mask of `search_where`; `radius`, `max_rungs`, `max_total` as in
         `search_range`, `lo` / `hi` as in `search_where`."""
-        q = _as_points(queries)
-        info = self.info()
-        if q.shape[0] and info.n and q.shape[1] != info.dim:
-            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
-        nq = q.shape[0]
-        rad = np.ascontiguousarray(np.asarray(radius, dtype=np.float32).reshape(-1))
-        if rad.size != 1 and rad.size != nq:
-            raise ValueError(f"`radius` is one float or an array of nq = {nq}, got {rad.size}")
-        lo_a, hi_a, n_cond = _conditions(lo, hi, nq)
-        lims = np.zeros(nq + 1, dtype=np.uint64)
-        rung = np.full(nq, RUNG_NONE, dtype=np.uint32)
-        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
-        search = search if search is not None else Search()
-        ctx = search._bind(self)
-        L = _lib()
-        L.check(L.idist_search_batch_range_attr(self._h, ctx, attr._h, _capi.f32p(q), nq, _capi.f32p(rad), int(rad.size), _capi.u32p(lo_a),
-                                                _capi.u32p(hi_a), n_cond, int(max_rungs), int(max_total), _capi.u64p(lims),
-                                                _capi.u32p(rung), _capi.u32p(ctr) if counters else None))
-        total = int(lims[nq])
-        pid = np.zeros(total, dtype=np.uint32)
-        dist = np.zeros(total, dtype=np.float32)
-        L.check(L.idist_search_ctx_range_fetch(ctx, _capi.u32p(pid), _capi.f32p(dist)))
-        return RangeResult(lims, pid, dist, rung, ctr)
+        return self._range(queries, radius, _Where(attr, lo, hi), max_rungs, max_total, counters, _or_fresh(search))
 
     def attribute_table(self, columns) -> AttrTable:
         """Several uint32 columns per point (tenant, category, day ...), in PointId order, copied to the index's device once
@@ -1016,53 +1070,14 @@ class Hnsw:
         an int (equality), a (lo, hi) tuple (an interval, unsigned, lo > hi empty) or a list / set / integer array (membership) —
         or `AnyOf(d1, d2, ...)`, the OR of such dicts; {} is TRUE, AnyOf() FALSE.  Row q is exactly what `search_allowed_sets`
         returns for the mask of its condition, but the masks are made on the device from the columns that already live there."""
-        q = _as_points(queries)
-        info = self.info()
-        if q.shape[0] and info.n and q.shape[1] != info.dim:
-            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
-        nq, k = q.shape[0], int(k)
-        cs, _keep = _conds_arg(table, conds, nq)
-        kk = max(k, 0)
-        pid = np.full((nq, kk), INVALID, dtype=np.uint32)
-        dist = np.full((nq, kk), np.inf, dtype=np.float32)
-        cnt = np.zeros(nq, dtype=np.uint32)
-        rung = np.full(nq, RUNG_NONE, dtype=np.uint32)
-        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
-        search = search if search is not None else Search()
-        ctx = search._bind(self)
-        L = _lib()
-        L.check(L.idist_search_batch_match(self._h, ctx, table._h, _capi.f32p(q), nq, C.byref(cs), kk, int(max_rungs), _capi.u32p(pid),
-                                           _capi.f32p(dist), _capi.u32p(cnt), _capi.u32p(rung), _capi.u32p(ctr) if counters else None))
-        return AllowedResult(pid, dist, cnt, rung, ctr)
+        return self._topk(queries, _Match(table, conds), k, max_rungs, counters, _or_fresh(search))
 
     def search_range_match(self, queries, radius, table: AttrTable, conds, search: Search | None = None, max_rungs: int = -1,
                            max_total: int = 64 * 2**20, counters: bool = False) -> RangeResult:
         """Every point within `radius` that satisfies the query's condition (idist_search_batch_range_match): row q is exactly what
         `search_range_allowed_sets` returns for the mask of its condition; `radius`, `max_rungs`, `max_total` as in `search_range`,
         `conds` as in `search_match`."""
-        q = _as_points(queries)
-        info = self.info()
-        if q.shape[0] and info.n and q.shape[1] != info.dim:
-            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
-        nq = q.shape[0]
-        rad = np.ascontiguousarray(np.asarray(radius, dtype=np.float32).reshape(-1))
-        if rad.size != 1 and rad.size != nq:
-            raise ValueError(f"`radius` is one float or an array of nq = {nq}, got {rad.size}")
-        cs, _keep = _conds_arg(table, conds, nq)
-        lims = np.zeros(nq + 1, dtype=np.uint64)
-        rung = np.full(nq, RUNG_NONE, dtype=np.uint32)
-        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
-        search = search if search is not None else Search()
-        ctx = search._bind(self)
-        L = _lib()
-        L.check(L.idist_search_batch_range_match(self._h, ctx, table._h, _capi.f32p(q), nq, _capi.f32p(rad), int(rad.size), C.byref(cs),
-                                                 int(max_rungs), int(max_total), _capi.u64p(lims), _capi.u32p(rung),
-                                                 _capi.u32p(ctr) if counters else None))
-        total = int(lims[nq])
-        pid = np.zeros(total, dtype=np.uint32)
-        dist = np.zeros(total, dtype=np.float32)
-        L.check(L.idist_search_ctx_range_fetch(ctx, _capi.u32p(pid), _capi.f32p(dist)))
-        return RangeResult(lims, pid, dist, rung, ctr)
+        return self._range(queries, radius, _Match(table, conds), max_rungs, max_total, counters, _or_fresh(search))
 
     def search_batch_device(self, search: Search, d_queries: int, nq: int, d_pid: int, d_dist: int, d_count: int,
                             d_counters: int = 0, stream: int = 0):
@@ -1180,17 +1195,20 @@ class HnswMap:
 
     def search_allowed(self, queries, allowed, k: int, search: Search, max_rungs: int = -1) -> list[list[MapItem]]:
         """`Hnsw.search_allowed` with the values: per query its min(k, allowed points) results as `MapItem`s, nearest first."""
-        r = self.hnsw.search_allowed(queries, allowed, k, search, max_rungs)
-        return [[MapItem(float(r.distance[i, j]), int(r.pid[i, j]), self.hnsw.points[int(r.pid[i, j])], self.values[int(r.pid[i, j])])
-                 for j in range(int(r.count[i]))] for i in range(r.pid.shape[0])]
+        return self._items(self.hnsw.search_allowed(queries, allowed, k, search, max_rungs))
+
+    def _item(self, distance: float, pid: PointId) -> MapItem:
+        return MapItem(distance, pid, self.hnsw.points[pid], self.values[pid])
+
+    def _items(self, r: AllowedResult) -> list[list[MapItem]]:
+        return _rows(r, self._item)
 
     def search_range(self, queries, radius, search: Search, max_rungs: int = -1, max_total: int = 64 * 2**20) -> list[list[MapItem]]:
         """`Hnsw.search_range` with the values: per query every result within its radius as `MapItem`s, nearest first."""
         return self._range_items(self.hnsw.search_range(queries, radius, search, max_rungs, max_total))
 
     def _range_items(self, r: RangeResult) -> list[list[MapItem]]:
-        return [[MapItem(float(r.distance[j]), int(r.pid[j]), self.hnsw.points[int(r.pid[j])], self.values[int(r.pid[j])])
-                 for j in range(int(r.lims[i]), int(r.lims[i + 1]))] for i in range(len(r.lims) - 1)]
+        return _range_rows(r, self._item)
 
     def search_range_allowed(self, queries, radius, allowed, search: Search, max_rungs: int = -1,
                              max_total: int = 64 * 2**20) -> list[list[MapItem]]:
@@ -1204,9 +1222,7 @@ class HnswMap:
 
     def search_allowed_sets(self, queries, sets, set_of, k: int, search: Search, max_rungs: int = -1) -> list[list[MapItem]]:
         """`Hnsw.search_allowed_sets` with the values: per query its min(k, points of its set) results as `MapItem`s, nearest first."""
-        r = self.hnsw.search_allowed_sets(queries, sets, set_of, k, search, max_rungs)
-        return [[MapItem(float(r.distance[i, j]), int(r.pid[i, j]), self.hnsw.points[int(r.pid[i, j])], self.values[int(r.pid[i, j])])
-                 for j in range(int(r.count[i]))] for i in range(r.pid.shape[0])]
+        return self._items(self.hnsw.search_allowed_sets(queries, sets, set_of, k, search, max_rungs))
 
     def attributes(self, values) -> Attr:
         """`Hnsw.attributes`: one uint32 per point in PointId order (the order of `self.values`)."""
@@ -1215,9 +1231,7 @@ class HnswMap:
     def search_where(self, queries, attr: Attr, lo, hi=None, k: int = 10, search: Search | None = None,
                      max_rungs: int = -1) -> list[list[MapItem]]:
         """`Hnsw.search_where` with the values: per query its results as `MapItem`s, nearest first."""
-        r = self.hnsw.search_where(queries, attr, lo, hi, k, search, max_rungs)
-        return [[MapItem(float(r.distance[i, j]), int(r.pid[i, j]), self.hnsw.points[int(r.pid[i, j])], self.values[int(r.pid[i, j])])
-                 for j in range(int(r.count[i]))] for i in range(r.pid.shape[0])]
+        return self._items(self.hnsw.search_where(queries, attr, lo, hi, k, search, max_rungs))
 
     def search_range_where(self, queries, radius, attr: Attr, lo, hi=None, search: Search | None = None, max_rungs: int = -1,
                            max_total: int = 64 * 2**20) -> list[list[MapItem]]:
@@ -1231,9 +1245,7 @@ class HnswMap:
     def search_match(self, queries, table: AttrTable, conds, k: int = 10, search: Search | None = None,
                      max_rungs: int = -1) -> list[list[MapItem]]:
         """`Hnsw.search_match` with the values: per query its results as `MapItem`s, nearest first."""
-        r = self.hnsw.search_match(queries, table, conds, k, search, max_rungs)
-        return [[MapItem(float(r.distance[i, j]), int(r.pid[i, j]), self.hnsw.points[int(r.pid[i, j])], self.values[int(r.pid[i, j])])
-                 for j in range(int(r.count[i]))] for i in range(r.pid.shape[0])]
+        return self._items(self.hnsw.search_match(queries, table, conds, k, search, max_rungs))
 
     def search_range_match(self, queries, radius, table: AttrTable, conds, search: Search | None = None, max_rungs: int = -1,
                            max_total: int = 64 * 2**20) -> list[list[MapItem]]:

@@ -19,9 +19,9 @@ from typing import Sequence
 import numpy as np
 
 from . import _capi
-from ._capi import INVALID, METRIC_DOT, RUNG_NONE
-from .api import (AllowedResult, Attr, AttrTable, BatchResult, Builder, Hnsw, Item, RangeResult, _as_points, _attr_values, _conditions, _conds_arg,
-                  _set_of, _table_columns, allowed_bitmap, allowed_bitmaps)
+from ._capi import INVALID, METRIC_DOT
+from .api import (AllowedResult, Attr, AttrTable, BatchResult, Builder, Hnsw, Item, RangeResult, _as_points, _attr_values, _Everything, _Match,
+                  _range_rows, _RestrictedSearch, _rows, _Sets, _table_columns, _Where, allowed_bitmap)
 from .dist import shard_range
 
 
@@ -29,7 +29,7 @@ def _lib():
     return _capi.lib()
 
 
-class PartitionedHnsw:
+class PartitionedHnsw(_RestrictedSearch):
     """An ordered list of `Hnsw` parts with the same dim, metric and ef_search (METRIC_DOT: and the same dot_bound) behind one
     search call."""
 
@@ -165,8 +165,26 @@ class PartitionedHnsw:
 
     def search(self, point) -> list[Item]:
         """One query: the merged items, nearest first; `Item.pid` is the global id."""
-        r = self.search_batch(np.asarray(point, dtype=np.float32).reshape(1, -1))
-        return [Item(float(r.distance[0, i]), int(r.pid[0, i]), self[int(r.pid[0, i])]) for i in range(int(r.count[0]))]
+        return _rows(self.search_batch(np.asarray(point, dtype=np.float32).reshape(1, -1)), self._item)[0]
+
+    def _item(self, distance: float, gid: int) -> Item:
+        return Item(distance, gid, self[gid])
+
+    # what `_RestrictedSearch` asks of the index class
+    _SEARCH = {(False, _Sets): "idist_partitioned_search_batch_allowed_sets",
+               (False, _Where): "idist_partitioned_search_batch_attr",
+               (False, _Match): "idist_partitioned_search_batch_match",
+               (True, _Everything): "idist_partitioned_search_batch_range",
+               (True, _Sets): "idist_partitioned_search_batch_range_allowed_sets",
+               (True, _Where): "idist_partitioned_search_batch_range_attr",
+               (True, _Match): "idist_partitioned_search_batch_range_match"}
+    _FETCH = "idist_partitioned_range_fetch"
+
+    def _lead(self, search=None) -> tuple:
+        return (self._h,)
+
+    def _rung_shape(self, nq: int, info) -> tuple:
+        return nq, int(info.n_parts)
 
     def search_allowed_sets(self, queries, sets, set_of, k: int, max_rungs: int = -1, counters: bool = False) -> AllowedResult:
         """The k nearest among an allowed subset, several sets in one call, one per query
@@ -176,52 +194,18 @@ class PartitionedHnsw:
         [n_sets][(len(self) + 31) // 32].  `set_of`: the set index of every query; None: query q uses set q.  `AllowedResult.rung` has
         shape (nq, n_parts): every part climbs its own ladder (a part that holds none of a query's allowed points answers RUNG_NONE
         at once; one where they are rare scans them exactly)."""
-        q = _as_points(queries)
-        info = self.info()
-        n, P = int(info.n), int(info.n_parts)
-        if q.shape[0] and n and q.shape[1] != info.dim:
-            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
-        bits = allowed_bitmaps(sets, n)
-        nq, k, n_sets = q.shape[0], int(k), bits.shape[0]
-        if set_of is None:
-            if n_sets != nq:
-                raise ValueError(f"set_of=None means one set per query: {n_sets} sets for {nq} queries")
-            so = None
-        else:
-            so = np.asarray(set_of)
-            if so.size and not np.issubdtype(so.dtype, np.integer):
-                raise TypeError("`set_of` is an integer array of set indices, one per query")
-            if so.shape != (nq,):
-                raise ValueError(f"`set_of` must have one entry per query: shape ({nq},), got {so.shape}")
-            if so.size and (so.min() < 0 or so.max() >= n_sets):
-                raise IndexError(f"`set_of` names a set outside [0, {n_sets})")
-            so = np.ascontiguousarray(so.astype(np.uint32))
-        kk = max(k, 0)
-        pid = np.full((nq, kk), INVALID, dtype=np.uint32)
-        dist = np.full((nq, kk), np.inf, dtype=np.float32)
-        cnt = np.zeros(nq, dtype=np.uint32)
-        rung = np.full((nq, P), RUNG_NONE, dtype=np.uint32)
-        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
-        if n_sets == 0 and nq == 0:
-            return AllowedResult(pid, dist, cnt, rung, ctr)
-        L = _lib()
-        L.check(L.idist_partitioned_search_batch_allowed_sets(self._h, _capi.f32p(q), nq, _capi.u32p(bits), n_sets,
-                                                              _capi.u32p(so) if so is not None else None, kk, int(max_rungs),
-                                                              _capi.u32p(pid), _capi.f32p(dist), _capi.u32p(cnt), _capi.u32p(rung),
-                                                              _capi.u32p(ctr) if counters else None))
-        return AllowedResult(pid, dist, cnt, rung, ctr)
+        return self._topk(queries, _Sets(sets, set_of), k, max_rungs, counters)
 
     def search_allowed(self, queries, allowed, k: int, max_rungs: int = -1, counters: bool = False) -> AllowedResult:
         """`search_allowed_sets` with ONE set shared by the batch: `allowed` is a bool mask of length len(self) or an integer array
         of global ids (`allowed_bitmap`'s rules)."""
         q = _as_points(queries)
-        bits = allowed_bitmap(allowed, len(self)).reshape(1, -1)
+        bits = allowed_bitmap(allowed, len(self)).reshape(1, -1)    # (whatever it is: no ready bitmaps here)
         return self.search_allowed_sets(q, bits, np.zeros(q.shape[0], dtype=np.uint32), k, max_rungs=max_rungs, counters=counters)
 
     def search_one_allowed(self, point, allowed, k: int) -> list[Item]:
         """One query: its min(k, allowed points) nearest allowed items, nearest first; `Item.pid` is the global id."""
-        r = self.search_allowed(np.asarray(point, dtype=np.float32).reshape(1, -1), allowed, k)
-        return [Item(float(r.distance[0, i]), int(r.pid[0, i]), self[int(r.pid[0, i])]) for i in range(int(r.count[0]))]
+        return _rows(self.search_allowed(np.asarray(point, dtype=np.float32).reshape(1, -1), allowed, k), self._item)[0]
 
     def last_allowed_slice_ms(self) -> float:
         """Host time the last restricted search spent on the bitmaps (the parts' strided uploads + slice kernels), milliseconds;
@@ -236,49 +220,7 @@ class PartitionedHnsw:
         the metric's report applied once, after the merge.  `radius`, `max_rungs` and `max_total` as in `Hnsw.search_range`;
         `max_total` bounds the merged total.  `RangeResult.pid` holds GLOBAL ids, `RangeResult.rung` has shape (nq, n_parts)
         (RUNG_NONE for an empty part), the counters are summed over the parts."""
-        q = _as_points(queries)
-        info = self.info()
-        P = int(info.n_parts)
-        if q.shape[0] and len(self) and q.shape[1] != info.dim:
-            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
-        nq = q.shape[0]
-        rad = np.ascontiguousarray(np.asarray(radius, dtype=np.float32).reshape(-1))
-        if rad.size != 1 and rad.size != nq:
-            raise ValueError(f"`radius` is one float or an array of nq = {nq}, got {rad.size}")
-        lims = np.zeros(nq + 1, dtype=np.uint64)
-        rung = np.full((nq, P), RUNG_NONE, dtype=np.uint32)
-        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
-        L = _lib()
-        L.check(L.idist_partitioned_search_batch_range(self._h, _capi.f32p(q), nq, _capi.f32p(rad), int(rad.size), int(max_rungs),
-                                                       int(max_total), _capi.u64p(lims), _capi.u32p(rung),
-                                                       _capi.u32p(ctr) if counters else None))
-        total = int(lims[nq])
-        pid = np.zeros(total, dtype=np.uint32)
-        dist = np.zeros(total, dtype=np.float32)
-        L.check(L.idist_partitioned_range_fetch(self._h, _capi.u32p(pid), _capi.f32p(dist)))
-        return RangeResult(lims, pid, dist, rung, ctr)
-
-    def _range_outputs(self, queries, radius, counters: bool):
-        q = _as_points(queries)
-        info = self.info()
-        if q.shape[0] and len(self) and q.shape[1] != info.dim:
-            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
-        nq = q.shape[0]
-        rad = np.ascontiguousarray(np.asarray(radius, dtype=np.float32).reshape(-1))
-        if rad.size != 1 and rad.size != nq:
-            raise ValueError(f"`radius` is one float or an array of nq = {nq}, got {rad.size}")
-        lims = np.zeros(nq + 1, dtype=np.uint64)
-        rung = np.full((nq, int(info.n_parts)), RUNG_NONE, dtype=np.uint32)
-        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
-        return q, rad, lims, rung, ctr
-
-    def _range_fetch(self, lims, rung, ctr) -> RangeResult:
-        total = int(lims[-1])
-        pid = np.zeros(total, dtype=np.uint32)
-        dist = np.zeros(total, dtype=np.float32)
-        L = _lib()
-        L.check(L.idist_partitioned_range_fetch(self._h, _capi.u32p(pid), _capi.f32p(dist)))
-        return RangeResult(lims, pid, dist, rung, ctr)
+        return self._range(queries, radius, _Everything(), max_rungs, max_total, counters)
 
     def search_range_allowed_sets(self, queries, radius, sets, set_of, max_rungs: int = -1, max_total: int = 64 * 2**20,
                                   counters: bool = False) -> RangeResult:
@@ -288,26 +230,14 @@ class PartitionedHnsw:
         metric's report applied once, after the merge.  `sets` / `set_of` name GLOBAL ids as in `search_allowed_sets`; `radius`,
         `max_rungs`, `max_total` as in `search_range`, `max_total` bounding the merged restricted total.  `RangeResult.rung` has
         shape (nq, n_parts): RUNG_NONE for an empty part or an empty slice."""
-        q, rad, lims, rung, ctr = self._range_outputs(queries, radius, counters)
-        nq = q.shape[0]
-        bits = allowed_bitmaps(sets, len(self))
-        so = _set_of(set_of, bits.shape[0], nq)
-        if bits.shape[0] == 0 and nq == 0:
-            return RangeResult(lims, np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.float32), rung, ctr)
-        L = _lib()
-        L.check(L.idist_partitioned_search_batch_range_allowed_sets(self._h, _capi.f32p(q), nq, _capi.f32p(rad), int(rad.size),
-                                                                    _capi.u32p(bits), bits.shape[0],
-                                                                    _capi.u32p(so) if so is not None else None, int(max_rungs),
-                                                                    int(max_total), _capi.u64p(lims), _capi.u32p(rung),
-                                                                    _capi.u32p(ctr) if counters else None))
-        return self._range_fetch(lims, rung, ctr)
+        return self._range(queries, radius, _Sets(sets, set_of), max_rungs, max_total, counters)
 
     def search_range_allowed(self, queries, radius, allowed, max_rungs: int = -1, max_total: int = 64 * 2**20,
                              counters: bool = False) -> RangeResult:
         """`search_range_allowed_sets` with ONE set shared by the batch: `allowed` is a bool mask of length len(self) or an integer
         array of global ids (`allowed_bitmap`'s rules)."""
         q = _as_points(queries)
-        bits = allowed_bitmap(allowed, len(self)).reshape(1, -1)
+        bits = allowed_bitmap(allowed, len(self)).reshape(1, -1)    # (whatever it is: no ready bitmaps here)
         return self.search_range_allowed_sets(q, radius, bits, np.zeros(q.shape[0], dtype=np.uint32), max_rungs, max_total, counters)
 
     # -- attribute filters --
@@ -325,37 +255,13 @@ class PartitionedHnsw:
         (idist_partitioned_search_batch_attr): row q is exactly what `search_allowed_sets` returns for the mask
         `(attr.values >= lo[q]) & (attr.values <= hi[q])` over the global ids; every part makes its bitmaps from its own slice of the
         values on its own device.  `lo` / `hi`: one integer for the batch or an array of one per query; hi=None means equality."""
-        q = _as_points(queries)
-        info = self.info()
-        n, P = int(info.n), int(info.n_parts)
-        if q.shape[0] and n and q.shape[1] != info.dim:
-            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
-        nq, k = q.shape[0], int(k)
-        lo_a, hi_a, n_cond = _conditions(lo, hi, nq)
-        kk = max(k, 0)
-        pid = np.full((nq, kk), INVALID, dtype=np.uint32)
-        dist = np.full((nq, kk), np.inf, dtype=np.float32)
-        cnt = np.zeros(nq, dtype=np.uint32)
-        rung = np.full((nq, P), RUNG_NONE, dtype=np.uint32)
-        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
-        L = _lib()
-        L.check(L.idist_partitioned_search_batch_attr(self._h, attr._h, _capi.f32p(q), nq, _capi.u32p(lo_a), _capi.u32p(hi_a), n_cond, kk,
-                                                      int(max_rungs), _capi.u32p(pid), _capi.f32p(dist), _capi.u32p(cnt), _capi.u32p(rung),
-                                                      _capi.u32p(ctr) if counters else None))
-        return AllowedResult(pid, dist, cnt, rung, ctr)
+        return self._topk(queries, _Where(attr, lo, hi), k, max_rungs, counters)
 
     def search_range_where(self, queries, radius, attr: Attr, lo, hi=None, max_rungs: int = -1, max_total: int = 64 * 2**20,
                            counters: bool = False) -> RangeResult:
         """Every point within `radius` whose attribute lies in the query's interval (idist_partitioned_search_batch_range_attr): row q
         is exactly what `search_range_allowed_sets` returns for the mask of `search_where`."""
-        q, rad, lims, rung, ctr = self._range_outputs(queries, radius, counters)
-        nq = q.shape[0]
-        lo_a, hi_a, n_cond = _conditions(lo, hi, nq)
-        L = _lib()
-        L.check(L.idist_partitioned_search_batch_range_attr(self._h, attr._h, _capi.f32p(q), nq, _capi.f32p(rad), int(rad.size),
-                                                            _capi.u32p(lo_a), _capi.u32p(hi_a), n_cond, int(max_rungs), int(max_total),
-                                                            _capi.u64p(lims), _capi.u32p(rung), _capi.u32p(ctr) if counters else None))
-        return self._range_fetch(lims, rung, ctr)
+        return self._range(queries, radius, _Where(attr, lo, hi), max_rungs, max_total, counters)
 
     # -- attribute tables --
     def attribute_table(self, columns) -> AttrTable:
@@ -372,42 +278,17 @@ class PartitionedHnsw:
         (idist_partitioned_search_batch_match): row q is exactly what `search_allowed_sets` returns for the mask of its condition over
         the global ids; every part evaluates the conditions over its own slice of the columns on its own device.  `conds` as in
         `Hnsw.search_match`."""
-        q = _as_points(queries)
-        info = self.info()
-        n, P = int(info.n), int(info.n_parts)
-        if q.shape[0] and n and q.shape[1] != info.dim:
-            raise TypeError(f"query dim {q.shape[1]} != index dim {info.dim}")
-        nq, k = q.shape[0], int(k)
-        cs, _keep = _conds_arg(table, conds, nq)
-        kk = max(k, 0)
-        pid = np.full((nq, kk), INVALID, dtype=np.uint32)
-        dist = np.full((nq, kk), np.inf, dtype=np.float32)
-        cnt = np.zeros(nq, dtype=np.uint32)
-        rung = np.full((nq, P), RUNG_NONE, dtype=np.uint32)
-        ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
-        L = _lib()
-        L.check(L.idist_partitioned_search_batch_match(self._h, table._h, _capi.f32p(q), nq, C.byref(cs), kk, int(max_rungs), _capi.u32p(pid),
-                                                       _capi.f32p(dist), _capi.u32p(cnt), _capi.u32p(rung),
-                                                       _capi.u32p(ctr) if counters else None))
-        return AllowedResult(pid, dist, cnt, rung, ctr)
+        return self._topk(queries, _Match(table, conds), k, max_rungs, counters)
 
     def search_range_match(self, queries, radius, table: AttrTable, conds, max_rungs: int = -1, max_total: int = 64 * 2**20,
                            counters: bool = False) -> RangeResult:
         """Every point within `radius` that satisfies the query's condition (idist_partitioned_search_batch_range_match): row q is
         exactly what `search_range_allowed_sets` returns for the mask of its condition."""
-        q, rad, lims, rung, ctr = self._range_outputs(queries, radius, counters)
-        nq = q.shape[0]
-        cs, _keep = _conds_arg(table, conds, nq)
-        L = _lib()
-        L.check(L.idist_partitioned_search_batch_range_match(self._h, table._h, _capi.f32p(q), nq, _capi.f32p(rad), int(rad.size), C.byref(cs),
-                                                             int(max_rungs), int(max_total), _capi.u64p(lims), _capi.u32p(rung),
-                                                             _capi.u32p(ctr) if counters else None))
-        return self._range_fetch(lims, rung, ctr)
+        return self._range(queries, radius, _Match(table, conds), max_rungs, max_total, counters)
 
     def search_one_range(self, point, radius) -> list[Item]:
         """One query: every item within `radius`, nearest first; `Item.pid` is the global id."""
-        r = self.search_range(np.asarray(point, dtype=np.float32).reshape(1, -1), float(radius))
-        return [Item(float(r.distance[i]), int(r.pid[i]), self[int(r.pid[i])]) for i in range(int(r.lims[1]))]
+        return _range_rows(self.search_range(np.asarray(point, dtype=np.float32).reshape(1, -1), float(radius)), self._item)[0]
 
     def last_range_merge_ms(self) -> float:
         """HIP-event duration of the last range search's counts, prefix-sum and merge kernels, milliseconds."""
