@@ -850,6 +850,63 @@ idist_status idist_attr_match_bitmaps_device(const void* d_values, uint32_t n, u
                                              const void* d_clauses, const void* d_and_lims, const void* d_or_lims, uint32_t n_sets,
                                              void* d_out, int32_t device, void* hip_stream);
 
+/* ---- grouped search: the nearest point of each of the k nearest groups --------------------------------------- */
+/* Rows are often chunks of documents, frames of videos, offers of one product: the caller wants the k nearest DOCUMENTS, each
+ * represented by its nearest chunk ("collapse" / "group_by").  The group of a point is one column of an attribute table:
+ *   attr        a table bound to idx (as for idist_search_batch_match); group_col < n_cols, anything else is IDIST_ERR_INVALID_ARG
+ *               and the message names the column count.  g(i) = values[group_col][i].  All 2^32 values are legal groups, 0 and
+ *               0xFFFFFFFF included.
+ *   conds       NULL: no restriction, A is every point.  Otherwise exactly the argument of idist_search_batch_match: the same
+ *               checks, the same grouping into distinct conditions, the same bitmap kernel; A is the query's own set.
+ *   k, max_rungs, null pointers: the error cases of idist_search_batch_allowed_sets (1 <= k <= ef_search).  nq == 0 is no error.
+ * DEFINITION.  The ladder is E[0] = ef_search, E[r + 1] = min(4 E[r], IDIST_MAX_EF).  collapse(L) of a list L ordered by (raw distance
+ * bits, id): walk L in order, keep an entry iff it is in A and no earlier KEPT entry has its group, stop after k kept entries.  For
+ * one query:
+ *   1. n == 0, ef_search == 0 or |A| == 0: count 0, rung IDIST_RUNG_NONE.
+ *   2. the start rule of idist_search_batch_allowed_sets, unchanged: |A| <= k goes to the exact step; otherwise r0 is the first
+ *      permitted r with E[r] |A| >= k n (64-bit integers); none: the exact step.
+ *   3. for r = r0, r0 + 1, ... among the permitted rungs: L = the result of Hnsw::search at ef_search = E[r], raw distances; if
+ *      collapse(L) has k entries it is the answer, the rung is r, the query stops.
+ *   4. exact: T = all of A ordered by (raw canonical distance bits, id); the answer is collapse(T), the rung IDIST_RUNG_EXACT, the
+ *      count min(k, number of distinct groups in A).
+ *   5. distances go through the metric's report once, at the end, on the [nq][k] result.  Padding: IDIST_INVALID / +inf, 0 in
+ *      out_group.  out_group[q][i] is the group of result i.  out_counters sums {n_dist, n_exp0, n_expU} over the rungs the query
+ *      ran; the exact step adds nothing.
+ * As in the several-sets call: a later rung that does not fit a wave's LDS ends the ladder (rung 0: the failure is returned); strict
+ * ties are retried inside; every row is what the call returns for that query alone; host pointers, the call blocks until done;
+ * ctx is the `&mut Search`, idx is never mutated.
+ * Two consequences the tests rest on:
+ *   - every result row has pairwise distinct groups, and with max_rungs == 0 it is the TRUE answer: the k groups whose nearest
+ *     allowed member is nearest, each represented by that member;
+ *   - IDENTITY: when every point is its own group (g(i) = i), every output — ids, order, distances, count, rung, counters — equals
+ *     that of idist_search_batch_match with the same conds, bit for bit; with conds == NULL that of idist_search_batch_allowed with
+ *     every bit set.
+ * The rungs launch the search kernels of the several-sets call; one kernel collapses a rung's lists (a set of seen groups in LDS,
+ * sized by k); the exact step runs in rounds of the restricted search's scan over A minus the groups found so far, at most k of
+ * them (idist_search_ctx_allowed_kernel_ms: the collapse under select_ms, the rounds under exact_ms).  An unrestricted call
+ * uploads no bitmap.
+ * Out of scope: more than one member per group, the partitioned index, device-pointer / stream variants,
+ * idist_search_batch_sharded. */
+idist_status idist_search_batch_grouped(const idist_index* idx, idist_search_ctx* ctx, const idist_attr* attr, uint32_t group_col,
+                                        const float* queries, uint32_t nq,
+                                        const idist_attr_conds* conds,           /* NULL: no restriction */
+                                        uint32_t k, int32_t max_rungs,
+                                        uint32_t* out_pid, float* out_dist,      /* nq*k */
+                                        uint32_t* out_group,                     /* nq*k or NULL */
+                                        uint32_t* out_count, uint32_t* out_rung, /* nq; out_rung may be NULL */
+                                        uint32_t* out_counters);                 /* nq*3 or NULL */
+/* The collapse kernel on its own (the role idist_attr_bitmaps_device plays for the bitmap kernel): d_pid / d_dist [nq][width] (u32 ids,
+ * f32 bit patterns), d_count [nq], d_groups [n] u32, d_bits [nq][(n + 31) / 32] or NULL (everything allowed), all in the memory of
+ * `device`; 1 <= k <= IDIST_MAX_EF.  Row q of d_out_pid / d_out_dist / d_out_group [nq][k] is collapse of the first min(count,
+ * width) entries of list q with A = the bits of row q of d_bits, padded as above; d_out_count[q] is the number kept.  Every output
+ * word is written exactly once; nothing beyond a list's count is read; ids >= n are never dereferenced and count as not allowed.
+ * nq == 0: nothing is done.  Enqueued on `hip_stream` (a hipStream_t, may be NULL) without synchronising. */
+idist_status idist_grouped_collapse_device(const void* d_pid, const void* d_dist, const void* d_count, uint32_t nq, uint32_t width,
+                                           const void* d_groups /* u32 [n] */, uint32_t n,
+                                           const void* d_bits /* [nq][(n+31)/32] or NULL: everything allowed */,
+                                           uint32_t k, void* d_out_pid, void* d_out_dist, void* d_out_group, void* d_out_count,
+                                           int32_t device, void* hip_stream);
+
 /* Point::distance for id lists (core/lib.rs:780-782 as used at :709-710): out[q][i] =
  * distance(queries[q], points[ids[q][i]]) for i < n_ids; IDIST_INVALID ids give +inf.
  * Host pointers. The batched gather-L2 kernel on its own. */

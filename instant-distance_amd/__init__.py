@@ -11,8 +11,8 @@ The directory name is fixed by the repo contract; import it as
 # it imports torch).
 from ._capi import (INVALID, M, M2, METRIC_COSINE, METRIC_DOT, METRIC_L2, METRIC_L2SQ, MAX_EF, RUNG_EXACT, RUNG_NONE, TIES_DROP, TIES_STRICT, IdistError,
                     LIB_PATH)
-from .api import (AllowedResult, AnyOf, Attr, AttrTable, BatchResult, Builder, Heuristic, Hnsw, HnswMap, Item, MapItem, PointId, RangeResult, Search, augment_dot, normalize)
+from .api import (AllowedResult, AnyOf, Attr, AttrTable, BatchResult, Builder, GroupedResult, Heuristic, Hnsw, HnswMap, Item, MapItem, PointId, RangeResult, Search, augment_dot, normalize)
 from .partition import PartitionedHnsw
 
-__all__ = ["Builder", "Heuristic", "Hnsw", "HnswMap", "PartitionedHnsw", "Search", "Item", "MapItem", "PointId", "BatchResult", "AllowedResult", "RangeResult", "Attr", "AttrTable", "AnyOf", "RUNG_EXACT", "RUNG_NONE",
+__all__ = ["Builder", "Heuristic", "Hnsw", "HnswMap", "PartitionedHnsw", "Search", "Item", "MapItem", "PointId", "BatchResult", "AllowedResult", "GroupedResult", "RangeResult", "Attr", "AttrTable", "AnyOf", "RUNG_EXACT", "RUNG_NONE",
            "normalize", "augment_dot", "IdistError", "INVALID", "M", "M2", "METRIC_COSINE", "METRIC_DOT", "METRIC_L2", "METRIC_L2SQ", "MAX_EF", "TIES_DROP", "TIES_STRICT", "LIB_PATH"]

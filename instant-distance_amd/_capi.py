@@ -6,6 +6,7 @@ MI355X is visible, every compute call raises.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 
@@ -201,6 +202,10 @@ SYMBOLS = {
     "idist_partitioned_search_batch_range_match": (C.c_int32, [_vp, _vp, _f32p, C.c_uint32, _f32p, C.c_uint32, _condsp, C.c_int32, C.c_uint64,
                                                                _u64p, _u32p, _u32p]),
     "idist_attr_match_bitmaps_device": (C.c_int32, [_vp, C.c_uint32, C.c_uint32, C.c_uint64, _vp, _vp, _vp, C.c_uint32, _vp, C.c_int32, _vp]),
+    "idist_search_batch_grouped": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, _f32p, C.c_uint32, _condsp, C.c_uint32, C.c_int32, _u32p, _f32p,
+                                               _u32p, _u32p, _u32p, _u32p]),
+    "idist_grouped_collapse_device": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp, _vp,
+                                                  C.c_int32, _vp]),
     "idist_distance_batch": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, _f32p]),
     "idist_filter_bound_batch": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, _f32p]),
     "idist_bruteforce": (C.c_int32, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),
@@ -212,7 +217,9 @@ SYMBOLS = {
 class Lib:
     """A loaded libidist with typed entry points and status checking."""
 
-    def __init__(self, path: str = LIB_PATH):
+    def __init__(self, path: str = LIB_PATH, without=()):
+        """`without` (a measurement aid for scripts/, not for users of the package) names symbols not to resolve: an older build of
+        the library, loaded to measure against, lacks the newest"""
         if not os.path.exists(path):
             raise ImportError(
                 f"{path} is missing: build it with `make -C instant-distance_amd/csrc` "
@@ -231,6 +238,8 @@ class Lib:
                 pass
         self.cdll = C.CDLL(path)
         for name, (res, args) in SYMBOLS.items():
+            if name in without:
+                continue
             fn = getattr(self.cdll, name)   # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
@@ -259,6 +268,19 @@ def lib() -> Lib:
     if _singleton is None:
         _singleton = Lib()
     return _singleton
+
+
+@contextlib.contextmanager
+def _using(other: Lib):
+    """A measurement aid for scripts/ (an A/B against another build of the library in one process), not for users of the package:
+    the package bound to `other` inside the block.  Not thread-safe — it swaps the module's one library — and objects made inside
+    belong to `other`, so every call on them, their release included, has to be made inside such a block too."""
+    global _singleton
+    old, _singleton = _singleton, other
+    try:
+        yield other
+    finally:
+        _singleton = old
 
 
 def f32p(a: np.ndarray):

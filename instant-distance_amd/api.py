@@ -372,6 +372,12 @@ class AllowedResult:
 
 
 @dataclass
+class GroupedResult(AllowedResult):
+    """`Hnsw.search_grouped`: an `AllowedResult` whose rows hold pairwise distinct groups, each represented by its nearest member."""
+    group: np.ndarray     # [nq, k] uint32, the group of every result; 0 padded
+
+
+@dataclass
 class RangeResult:
     """`Hnsw.search_range`: query q owns the entries [lims[q], lims[q + 1]) of `pid` and `distance`, nearest first."""
     lims: np.ndarray      # [nq + 1] uint64, lims[0] = 0
@@ -632,6 +638,21 @@ def _conds_arg(table: "AttrTable", conds, nq: int):
     return _capi.AttrConds(_capi.u32p(clauses), _capi.u32p(and_lims), _capi.u32p(or_lims), n_cond), keep
 
 
+def _group_column(table: "Attr", by) -> int:
+    """The column of `table` a `search_grouped` call collapses by: `by` names a column of an `AttrTable`; by=None takes the only
+    column of a one-column `Attr`."""
+    if not isinstance(table, Attr):
+        raise TypeError("`table` is an AttrTable (attribute_table) or a one-column Attr (attributes)")
+    names = table.names if isinstance(table, AttrTable) else None
+    if by is None:
+        if names is not None and len(names) != 1:
+            raise ValueError(f"by=None needs a one-column attribute; name one of the table's columns: {names}")
+        return 0
+    if names is None or by not in names:
+        raise KeyError(f"no column {by!r}: the table has {names if names is not None else 'one unnamed column (by=None)'}")
+    return names.index(by)
+
+
 def normalize(points, device: int = 0, return_norm2: bool = False):
     """x / sqrt(s(x)) per row, s = the canonical squared-L2 distance of the row to the origin (idist_normalize_batch): the rows a
     METRIC_COSINE index holds for `points`, bit for bit — an METRIC_L2SQ index over `normalize(points)` searched with
@@ -815,6 +836,23 @@ class _RestrictedSearch:
                                                                   int(max_rungs), int(max_total), _capi.u64p(lims), _capi.u32p(rung),
                                                                   _capi.u32p(ctr) if counters else None))
         return _range_fetch(getattr(L, self._FETCH), lead[-1], lims, rung, ctr)
+
+    def _grouped(self, queries, table, by, conds, k: int, max_rungs: int, counters: bool, search=None) -> GroupedResult:
+        """`_topk` collapsed by a column (`_GROUPED`: leading handles, attr, group_col, queries, nq, conds or NULL, k, max_rungs,
+        the outputs of `_topk` with the groups behind the distances).  Arguments are judged in the order queries, by, conds."""
+        info = self.info()
+        q = _queries(queries, info)
+        nq, k = q.shape[0], max(int(k), 0)
+        col = _group_column(table, by)
+        match = None if conds is None else _Match(table, conds)      # (lives through the call: it owns what its argument points into)
+        rargs = (None,) if match is None else match.args(int(info.n), nq)
+        pid, dist, cnt, rung, ctr = _topk_outputs(nq, k, self._rung_shape(nq, info), counters)
+        group = np.zeros((nq, k), dtype=np.uint32)
+        L = _lib()
+        L.check(getattr(L, self._GROUPED)(*self._lead(search), table._h, col, _capi.f32p(q), nq, *rargs, k, int(max_rungs), _capi.u32p(pid),
+                                          _capi.f32p(dist), _capi.u32p(group), _capi.u32p(cnt), _capi.u32p(rung),
+                                          _capi.u32p(ctr) if ctr is not None else None))
+        return GroupedResult(pid, dist, cnt, rung, ctr, group)
 
 
 def _or_fresh(search: "Search | None") -> "Search":
@@ -1079,6 +1117,19 @@ class Hnsw(_RestrictedSearch):
         `conds` as in `search_match`."""
         return self._range(queries, radius, _Match(table, conds), max_rungs, max_total, counters, _or_fresh(search))
 
+    _GROUPED = "idist_search_batch_grouped"
+
+    def search_grouped(self, queries, table: Attr, by, k: int = 10, conds=None, search: Search | None = None, max_rungs: int = -1,
+                       counters: bool = False) -> GroupedResult:
+        """The nearest point of each of the k nearest groups (idist_search_batch_grouped): rows are chunks of documents, the answer
+        is the k nearest documents, each represented by its nearest chunk.  `by`: the column of the `AttrTable` that holds a point's
+        group — every uint32 is a legal group — or None for a one-column `Attr`.  `conds`: None, or a `search_match` condition
+        over the same table ("tenant = 7, one hit per document").  The rungs are `search_match`'s, each list collapsed to the first
+        allowed entry of every group; the first rung that holds k groups answers, and where the ladder ends an exact step does —
+        `max_rungs=0` is the ground truth.  `.group[q, i]` is the group of result i; when every point is its own group the result
+        is `search_match`'s."""
+        return self._grouped(queries, table, by, conds, k, max_rungs, counters, _or_fresh(search))
+
     def search_batch_device(self, search: Search, d_queries: int, nq: int, d_pid: int, d_dist: int, d_count: int,
                             d_counters: int = 0, stream: int = 0):
         """Device-pointer variant: inputs/outputs stay in HBM, enqueued on `stream` without a sync."""
@@ -1251,6 +1302,11 @@ class HnswMap:
                            max_total: int = 64 * 2**20) -> list[list[MapItem]]:
         """`Hnsw.search_range_match` with the values: per query every result of its condition within its radius as `MapItem`s."""
         return self._range_items(self.hnsw.search_range_match(queries, radius, table, conds, search, max_rungs, max_total))
+
+    def search_grouped(self, queries, table: Attr, by, k: int = 10, conds=None, search: Search | None = None,
+                       max_rungs: int = -1) -> list[list[MapItem]]:
+        """`Hnsw.search_grouped` with the values: per query the nearest member of each of its groups as `MapItem`s, nearest first."""
+        return self._items(self.hnsw.search_grouped(queries, table, by, k, conds, search, max_rungs))
 
     def iter(self):
         return self.hnsw.iter()

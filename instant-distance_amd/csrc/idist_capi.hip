@@ -15,6 +15,7 @@
 #include "idist_range_allowed.hpp"
 #include "idist_range_merge.hpp"
 #include "idist_attr.hpp"
+#include "idist_grouped.hpp"
 #include "idist_basis.hpp"
 
 #ifndef IDIST_EMU
@@ -304,6 +305,7 @@ inline Knobs knobs_from_env() {
     if (const char* e = test_env("IDIST_W2_EF")) k.w2_ef = (uint32_t)strtoul(e, nullptr, 10);
     if (const char* e = test_env("IDIST_ALLOWED_SEGMENTS")) k.allowed_segments = std::min(64u, (uint32_t)std::max(0, atoi(e)));
     if (const char* e = test_env("IDIST_RANGE_SEGMENTS")) k.range_segments = std::min(64u, (uint32_t)std::max(0, atoi(e)));
+    if (const char* e = test_env("IDIST_GROUPED_STAGE")) k.grouped_stage = (uint64_t)strtoull(e, nullptr, 10);
     if (const char* e = test_env("IDIST_RANGE_SORT_CHUNK")) {
         const uint32_t c = (uint32_t)std::max(0, atoi(e));
         if (c >= 128u && c <= 4096u && (c & (c - 1u)) == 0u) k.range_sort_chunk = c;
@@ -397,11 +399,15 @@ struct idist_search_ctx {
     DevBuf<float> al_pq;
     DevBuf<uint32_t> al_bits, al_ids, al_opid, al_ocnt, al_mpid, al_mcnt, al_setof, al_size, al_start, al_first, al_raw;
     DevBuf<> al_odist, al_mdist;   // distances: f32 to the report pass, their bits to the ranking kernels
+    //  * The grouped search's, on top of the restricted search's: the groups of the [nq][k] result (gr_ogroup), the
+    //    bitmaps of an exact round's chunk of pending queries and the identity that names them (gr_bits, gr_ident).
+    DevBuf<uint32_t> gr_ogroup, gr_bits, gr_ident;
     // The passes a call times (ladder_timed): a pair of events each, created on first use, resolved when the call has synchronised its
     // stream.  A restricted search: a pair per select and pending pass of at most seven rungs + the exact step's two; several sets: + the
     // count pass and a pending pass in front of every launch.  A range search: three pairs per rung (select, pending, copy) + five
-    // (init, the exact step's three, lims).  Pairs beyond kAllowedEvents are not timed.
-    static constexpr uint32_t kAllowedEvents = 64;
+    // (init, the exact step's three, lims).  A grouped search: the several-sets call's, + four pairs per round of its exact step
+    // (exclude, scan + merge, select, pending).  Pairs beyond kAllowedEvents are not timed.
+    static constexpr uint32_t kAllowedEvents = 256;
     hipEvent_t al_ev[kAllowedEvents] = {nullptr};
     uint8_t al_ev_which[kAllowedEvents / 2] = {0};   // the slot of al_ms a pair adds to
     uint32_t al_ev_used = 0;
@@ -3731,11 +3737,11 @@ idist_status allowed_select(idist_search_ctx* ctx, const AllowedOut& o, uint32_t
     return ladder_timed(ctx, 0, select_pass);
 }
 
-// Step 5 of the restricted search, exact, around either scan kernel: launch_scan enqueues one wave per (pending query, segment),
-// each writing its segment's top-k as list s of the merge by (distance bits, id); the k best are selected as rung IDIST_RUNG_EXACT
+// The scan and merge half of an exact step, around either scan kernel: launch_scan enqueues one wave per (pending query, segment),
+// each writing its segment's top-k as list s of the merge by (distance bits, id); the k best of every pending query end up in
+// ctx->al_mpid / al_mdist [np][k], al_mcnt [np]
 template <typename F>
-idist_status allowed_exact_step(const idist_index* idx, idist_search_ctx* ctx, const AllowedOut& o, uint32_t np, uint32_t k, uint32_t S,
-                                const uint32_t* d_list, const uint32_t* d_setof, uint32_t words, F launch_scan) {
+idist_status exact_scan_merge(const idist_index* idx, idist_search_ctx* ctx, uint32_t np, uint32_t k, uint32_t S, F launch_scan) {
     const size_t sb = (size_t)S * np * k * 4, mb = (size_t)np * k * 4;
     CHK(ctx->d_pid.grow(sb));
     CHK(ctx->d_dist.grow(sb));
@@ -3758,7 +3764,14 @@ idist_status allowed_exact_step(const idist_index* idx, idist_search_ctx* ctx, c
         a.out_counters = nullptr;
         return launch_merge(a, ctx->stream);
     };
-    CHK(ladder_timed(ctx, 2, scan_and_merge));
+    return ladder_timed(ctx, 2, scan_and_merge);
+}
+
+// Step 5 of the restricted search, exact: the k best of the scan are selected as rung IDIST_RUNG_EXACT
+template <typename F>
+idist_status allowed_exact_step(const idist_index* idx, idist_search_ctx* ctx, const AllowedOut& o, uint32_t np, uint32_t k, uint32_t S,
+                                const uint32_t* d_list, const uint32_t* d_setof, uint32_t words, F launch_scan) {
+    CHK(exact_scan_merge(idx, ctx, np, k, S, launch_scan));
     return allowed_select(ctx, o, idx->n, ctx->al_mpid, ctx->al_mdist.as<float>(), ctx->al_mcnt, nullptr, k,
                           d_list, np, IDIST_RUNG_EXACT, true, d_setof, words);
 }
@@ -3893,9 +3906,17 @@ namespace {
 // [nq][k] result goes, RAW distances — the caller reports; o.pending is set here.  n > 0, ef_search > 0, nq > 0 and the arguments
 // checked.  Blocks on ctx->stream once per rung; on return the last passes are enqueued there, not waited for: the caller
 // synchronises the stream and calls ladder_times_resolve.
-idist_status allowed_sets_device(const idist_index* idx, idist_search_ctx* ctx, const float* d_qk, uint32_t nq, const uint32_t* d_bits,
-                                 uint32_t n_sets, const uint32_t* d_setof, const uint32_t* set_of, uint32_t k, int32_t max_rungs,
-                                 AllowedOut o) {
+// What is done with a rung's lists and what the exact step is are the caller's (the restricted search filters and scans, the grouped
+// search collapses and scans in rounds):
+//   select_rung(o, ef, d_list, np, r)           the np lists of rung r in ctx->d_pid / d_dist [np][ef], d_cnt, d_ctr; d_list: the
+//                                               query of every list (nullptr: the identity)
+//   exact_step(o, d_list, d_pq, np, gather)     the np queries still pending, their rows in d_pq; gather(kRungExact) makes the three
+//                                               anew from o.pending
+// known_start [n_sets] (host; nullptr: counted here): the first step of every set by the start rule, where the caller knows |A_s|.
+template <typename Select, typename Exact>
+idist_status sets_ladder_device(const idist_index* idx, idist_search_ctx* ctx, const float* d_qk, uint32_t nq, const uint32_t* d_bits,
+                                uint32_t n_sets, const uint32_t* d_setof, const uint32_t* set_of, uint32_t k, int32_t max_rungs,
+                                AllowedOut o, Select select_rung, Exact exact_step, const uint32_t* known_start = nullptr) {
     const uint32_t n = idx->n;
     // the permitted rungs, as idist_search_batch_allowed has them; every set's size and start rung come from the device
     const uint32_t words = (n + 31u) / 32u;
@@ -3922,9 +3943,14 @@ idist_status allowed_sets_device(const idist_index* idx, idist_search_ctx* ctx, 
         HIPCHK(hipGetLastError());
         return IDIST_OK;
     };
-    CHK(ladder_timed(ctx, 0, count_pass));
     std::vector<uint32_t> start(n_sets);
-    HIPCHK(hipMemcpyAsync(start.data(), ctx->al_start.p, (size_t)n_sets * 4, hipMemcpyDeviceToHost, stream));
+    if (known_start) {                                   // the caller knows every set's first step (d_bits may be null): no count pass
+        start.assign(known_start, known_start + n_sets);
+        HIPCHK(hipMemcpyAsync(ctx->al_start.p, start.data(), (size_t)n_sets * 4, hipMemcpyHostToDevice, stream));
+    } else {
+        CHK(ladder_timed(ctx, 0, count_pass));
+        HIPCHK(hipMemcpyAsync(start.data(), ctx->al_start.p, (size_t)n_sets * 4, hipMemcpyDeviceToHost, stream));
+    }
     {
         const uint32_t grid = (uint32_t)std::min<size_t>(((size_t)nq * k + 255) / 256, (size_t)std::max(ctx->n_cu, 1) * 8u);
         IDIST_LAUNCH(allowed_init_kernel, grid, 256, 0, stream, o, ctx->al_start, d_setof, ctx->al_first);
@@ -3978,26 +4004,128 @@ idist_status allowed_sets_device(const idist_index* idx, idist_search_ctx* ctx, 
         bool ended = false;
         CHK(ladder_rung(idx, ctx, d_pq, np, ef, r, counters, &ended));
         if (ended) break;
-        CHK(allowed_select(ctx, o, n, ctx->d_pid, ctx->d_dist, ctx->d_cnt, counters ? ctx->d_ctr.p : nullptr, ef, d_list, np, r, false,
-                           d_setof, words));
+        CHK(select_rung(o, ef, d_list, np, r));
         r++;
     }
     if (!all_done && !in_place) CHK(gather(kRungExact));
-    if (!all_done && np) {
-        // step 5, exact, straight from the bitmaps: the 64-id windows of [0, n) cut into S segments, never narrower than one window
+    if (!all_done && np) CHK(exact_step(o, d_list, d_pq, np, gather));
+    return IDIST_OK;
+}
+
+// an exact scan straight from bitmaps: the pending rows d_pq [np][kdim] of the queries list [np] (nullptr: the identity), query q
+// reading d_bits + set_of[q] * words — what exact_scan_merge takes as launch_scan
+auto scan_bits_launcher(const idist_index* idx, hipStream_t stream, const float* d_pq, uint32_t np, const uint32_t* d_bits, uint32_t words,
+                        const uint32_t* d_list, const uint32_t* d_setof, uint32_t k) {
+    return [=](uint32_t grid, size_t smem, uint32_t S, uint32_t wcap, uint32_t* s_pid, uint32_t* s_dist, uint32_t* s_cnt) {
         const IndexView view = idx->view();
-        auto scan_bits = [&](uint32_t grid, size_t smem, uint32_t S, uint32_t wcap, uint32_t* s_pid, uint32_t* s_dist, uint32_t* s_cnt) {
+        const uint32_t n = idx->n;
 #define LAUNCH_AS(NB_, RS_, TAIL_)                                                                                                 \
     {                                                                                                                              \
         auto kA = allowed_scan_bits_kernel<NB_, RS_, TAIL_>;                                                                       \
         IDIST_LAUNCH(kA, grid, 64, smem, stream, view, d_pq, np, d_bits, n, words, d_list, d_setof, S, k, wcap, s_pid, s_dist, s_cnt); \
     }
-            IDIST_DISPATCH(idx->L, LAUNCH_AS);
+        IDIST_DISPATCH(idx->L, LAUNCH_AS);
 #undef LAUNCH_AS
-        };
-        CHK(allowed_exact_step(idx, ctx, o, np, k, exact_segments(ctx, np, n, ctx->knobs.allowed_segments), d_list, d_setof, words, scan_bits));
+    };
+}
+
+// The several-sets call: a rung's lists filtered by the query's set; step 5, exact, straight from the bitmaps — the 64-id windows of
+// [0, n) cut into S segments, never narrower than one window
+idist_status allowed_sets_device(const idist_index* idx, idist_search_ctx* ctx, const float* d_qk, uint32_t nq, const uint32_t* d_bits,
+                                 uint32_t n_sets, const uint32_t* d_setof, const uint32_t* set_of, uint32_t k, int32_t max_rungs,
+                                 AllowedOut o) {
+    const uint32_t n = idx->n, words = (n + 31u) / 32u;
+    auto select_rung = [&](const AllowedOut& out, uint32_t ef, const uint32_t* d_list, uint32_t np, uint32_t r) {
+        return allowed_select(ctx, out, n, ctx->d_pid, ctx->d_dist, ctx->d_cnt, out.counters ? ctx->d_ctr.p : nullptr, ef, d_list, np, r, false,
+                              d_setof, words);
+    };
+    auto exact_step = [&](const AllowedOut& out, const uint32_t*& d_list, const float*& d_pq, uint32_t& np, auto&) {
+        return allowed_exact_step(idx, ctx, out, np, k, exact_segments(ctx, np, n, ctx->knobs.allowed_segments), d_list, d_setof, words,
+                                  scan_bits_launcher(idx, ctx->stream, d_pq, np, d_bits, words, d_list, d_setof, k));
+    };
+    return sets_ladder_device(idx, ctx, d_qk, nq, d_bits, n_sets, d_setof, set_of, k, max_rungs, o, select_rung, exact_step);
+}
+
+// ---- grouped search: the ladder collapsed by a column, exact rounds ----
+// grouped_select_kernel on `stream` over np lists of `width`; d_bits null: every id < n is allowed
+idist_status launch_grouped_select(const GroupedOut& g, const uint32_t* d_groups, uint32_t n, const uint32_t* d_bits, uint32_t words,
+                                   const uint32_t* d_setof, const uint32_t* r_pid, const uint32_t* r_dist, const uint32_t* r_cnt,
+                                   const uint32_t* r_ctr, uint32_t width, const uint32_t* d_list, uint32_t np, uint32_t rung, uint32_t mode,
+                                   hipStream_t stream) {
+    const uint32_t tab_log2 = grouped_tab_log2(g.k);
+    const uint32_t grid = std::min<uint32_t>(np, 65536u);                     // one wave per list; the kernel strides over the rest
+    IDIST_LAUNCH(grouped_select_kernel, grid, 64, (size_t)8u << tab_log2, stream, g, d_groups, n, d_bits, words, d_setof, r_pid, r_dist, r_cnt,
+                 r_ctr, width, d_list, np, rung, mode, tab_log2);
+    HIPCHK(hipGetLastError());
+    return IDIST_OK;
+}
+
+// The exact step of the grouped search, in rounds: for the pending queries one bitmap each, A and "group not found yet"; the scan and
+// merge of the restricted search give the k nearest remaining points; the collapse appends their new groups.  A query closes when
+// its count reaches k or its list came back shorter than k.  Every remaining point nearer than a kept entry is in the list in front
+// of it, so the found groups are a prefix of the true group order after every round: the result depends neither on the width of a
+// round nor on S nor on the chunks, and a round adds at least one group to every query it leaves pending — at most k rounds.  The
+// bitmaps of a chunk of pending queries stay under a fixed staging bound.
+template <typename Gather>
+idist_status grouped_exact_rounds(const idist_index* idx, idist_search_ctx* ctx, const GroupedOut& g, const uint32_t* d_groups,
+                                  const uint32_t* d_bits, const uint32_t* d_setof, const uint32_t*& d_list, const float*& d_pq, uint32_t& np,
+                                  Gather& gather) {
+    const uint32_t n = idx->n, k = g.k, kdim = idx->kdim, words = (n + 31u) / 32u;
+    const uint32_t tab_log2 = grouped_tab_log2(k);
+    hipStream_t stream = ctx->stream;
+    if (!d_list) CHK(gather(kRungExact));                                     // a chunk names its queries through the list
+    const uint64_t bound = ctx->knobs.grouped_stage ? ctx->knobs.grouped_stage : (uint64_t)256u << 20;
+    const uint32_t chunk = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(bound / ((uint64_t)words * 4u), 1u), np);
+    CHK(ctx->gr_bits.grow((size_t)chunk * words * 4));
+    CHK(ctx->gr_ident.grow((size_t)chunk * 4));
+    for (uint32_t round = 0; np; round++) {
+        if (round > k) return fail(IDIST_ERR_INTERNAL, "grouped search: %u queries still pending after %u exact rounds", np, round);
+        for (uint32_t c0 = 0; c0 < np; c0 += chunk) {
+            const uint32_t npc = std::min(chunk, np - c0);
+            const uint32_t* lst = d_list + c0;
+            auto exclude_pass = [&]() -> idist_status {
+                const uint32_t S = exact_segments(ctx, npc, n, ctx->knobs.allowed_segments);    // (rows: at most one segment per window)
+                const uint32_t grid = (uint32_t)std::min<uint64_t>((uint64_t)npc * S, (uint64_t)std::max(ctx->n_cu, 1) * 64u);
+                IDIST_LAUNCH(grouped_exclude_kernel, grid, 64, (size_t)8u << tab_log2, stream, d_bits, n, words, d_setof, lst, npc, d_groups,
+                             g.group, g.count, k, S, tab_log2, ctx->gr_bits, ctx->gr_ident);
+                HIPCHK(hipGetLastError());
+                return IDIST_OK;
+            };
+            CHK(ladder_timed(ctx, 2, exclude_pass));
+            CHK(exact_scan_merge(idx, ctx, npc, k, exact_segments(ctx, npc, n, ctx->knobs.allowed_segments),
+                                 scan_bits_launcher(idx, stream, d_pq + (size_t)c0 * kdim, npc, ctx->gr_bits, words, nullptr, ctx->gr_ident, k)));
+            auto select_pass = [&]() -> idist_status {
+                return launch_grouped_select(g, d_groups, n, nullptr, words, nullptr, ctx->al_mpid, ctx->al_mdist.as<uint32_t>(), ctx->al_mcnt,
+                                             nullptr, k, lst, npc, IDIST_RUNG_EXACT, kGroupedRound, stream);
+            };
+            CHK(ladder_timed(ctx, 0, select_pass));
+        }
+        CHK(gather(kRungExact));
     }
     return IDIST_OK;
+}
+
+// The grouped call between its uploads and its report, as allowed_sets_device: the same count pass, init, pending pass and rungs;
+// d_groups [n]: the group column; d_ogroup [nq][k]: the groups of the result, zero on entry.  d_bits null: one set, every point,
+// its first step in known_start[0] — no bitmap exists and none is read.
+idist_status grouped_device(const idist_index* idx, idist_search_ctx* ctx, const float* d_qk, uint32_t nq, const uint32_t* d_bits,
+                            uint32_t n_sets, const uint32_t* d_setof, const uint32_t* set_of, const uint32_t* d_groups, uint32_t k,
+                            int32_t max_rungs, AllowedOut o, uint32_t* d_ogroup, const uint32_t* known_start) {
+    const uint32_t n = idx->n, words = (n + 31u) / 32u;
+    auto grouped_out = [&](const AllowedOut& out) {
+        return GroupedOut{out.pid, out.dist, d_ogroup, out.count, out.rung, out.counters, out.pending, k};
+    };
+    auto select_rung = [&](const AllowedOut& out, uint32_t ef, const uint32_t* d_list, uint32_t np, uint32_t r) {
+        auto select_pass = [&]() -> idist_status {
+            return launch_grouped_select(grouped_out(out), d_groups, n, d_bits, words, d_setof, ctx->d_pid, reinterpret_cast<const uint32_t*>(ctx->d_dist.p), ctx->d_cnt,
+                                         out.counters ? ctx->d_ctr.p : nullptr, ef, d_list, np, r, kGroupedRung, ctx->stream);
+        };
+        return ladder_timed(ctx, 0, select_pass);
+    };
+    auto exact_step = [&](const AllowedOut& out, const uint32_t*& d_list, const float*& d_pq, uint32_t& np, auto& gather) {
+        return grouped_exact_rounds(idx, ctx, grouped_out(out), d_groups, d_bits, d_setof, d_list, d_pq, np, gather);
+    };
+    return sets_ladder_device(idx, ctx, d_qk, nq, d_bits, n_sets, d_setof, set_of, k, max_rungs, o, select_rung, exact_step, known_start);
 }
 
 }  // namespace
@@ -4167,6 +4295,78 @@ idist_status idist_search_batch_match(const idist_index* idx, idist_search_ctx* 
     MatchConds g;
     match_group(conds, conds->n_cond, nq, &g);
     return allowed_sets_call(idx, ctx, queries, nq, g.source(attr), k, max_rungs, out_pid, out_dist, out_count, out_rung, out_counters);
+}
+
+// ---- grouped search ----
+idist_status idist_search_batch_grouped(const idist_index* idx, idist_search_ctx* ctx, const idist_attr* attr, uint32_t group_col,
+                                        const float* queries, uint32_t nq, const idist_attr_conds* conds, uint32_t k, int32_t max_rungs,
+                                        uint32_t* out_pid, float* out_dist, uint32_t* out_group, uint32_t* out_count, uint32_t* out_rung,
+                                        uint32_t* out_counters) {
+    CHK(check_ctx(idx, ctx));
+    CHK(check_attr(attr, idx->uid, false));
+    if (group_col >= attr->n_cols)
+        return fail(IDIST_ERR_INVALID_ARG, "group_col %u, but the table has %u column%s", group_col, attr->n_cols, attr->n_cols == 1 ? "" : "s");
+    ctx->at_ms = 0.0f;
+    CHK(check_ladder_args(max_rungs, k, idx->cfg.ef_search));
+    if (conds) CHK(check_match_args(conds, nq, attr->n_cols));
+    if (nq == 0) return IDIST_OK;
+    if (!queries || !out_pid || !out_dist || !out_count) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    const uint32_t n = idx->n;
+    if (n == 0 || idx->cfg.ef_search == 0) {                                 // step 1: nothing to find
+        fill_nothing_found(nq, k, out_pid, out_dist, out_count, out_rung, out_counters);
+        if (out_group) memset(out_group, 0, (size_t)nq * k * 4);
+        return IDIST_OK;
+    }
+    // A: the query's condition, grouped and staged as idist_search_batch_match does — or every point: one set that needs no bitmap
+    // and no count, |A| = n being known (the start rule on the host: rung 0 when a rung is permitted and n > k, else exact)
+    MatchConds g;
+    std::vector<uint32_t> one_set;
+    uint32_t first_step = kRungExact;
+    if (conds) match_group(conds, conds->n_cond, nq, &g);
+    else {
+        one_set.assign(nq, 0u);
+        if (n > k && make_ladder(idx->cfg.ef_search, max_rungs).n_rungs) first_step = 0u;   // (E[0] n >= k n: k <= ef_search was checked)
+    }
+    HIPCHK(hipSetDevice(idx->device));
+    hipStream_t stream = ctx->stream;
+    const MetricPasses metric(idx);
+    const size_t ob = (size_t)nq * k * 4;
+    AllowedOut o{};
+    CHK(allowed_out_in_ctx(ctx, nq, k, out_counters != nullptr, &o));
+    CHK(ctx->gr_ogroup.grow(ob));
+    HIPCHK(hipMemsetAsync(ctx->gr_ogroup.p, 0, ob, stream));
+    if (conds) {
+        CHK(stage_sets(ctx, n, nq, g.source(attr)));
+    } else {
+        CHK(ctx->al_setof.grow((size_t)nq * 4));
+        HIPCHK(hipMemsetAsync(ctx->al_setof.p, 0, (size_t)nq * 4, stream));
+    }
+    const float* d_qk = nullptr;
+    CHK(ladder_upload_queries(idx, ctx, metric, queries, nq, &d_qk));
+    CHK(grouped_device(idx, ctx, d_qk, nq, conds ? ctx->al_bits.p : nullptr, conds ? g.n_sets : 1u, ctx->al_setof,
+                       conds ? g.set_of.data() : one_set.data(), attr->parts[0].v.p + (size_t)group_col * n, k, max_rungs, o, ctx->gr_ogroup,
+                       conds ? nullptr : &first_step));
+    CHK(metric.report(ctx->al_odist.as<float>(), ctx->d_sq, nq, k, stream));
+    CHK(allowed_download(ctx, nq, k, out_pid, out_dist, out_count, out_rung, out_counters));
+    if (out_group) HIPCHK(hipMemcpyAsync(out_group, ctx->gr_ogroup.p, ob, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    CHK(attr_time_resolve(ctx));
+    return ladder_times_resolve(ctx);
+}
+
+idist_status idist_grouped_collapse_device(const void* d_pid, const void* d_dist, const void* d_count, uint32_t nq, uint32_t width,
+                                           const void* d_groups, uint32_t n, const void* d_bits, uint32_t k, void* d_out_pid,
+                                           void* d_out_dist, void* d_out_group, void* d_out_count, int32_t device, void* hip_stream) {
+    if (k == 0 || k > IDIST_MAX_EF) return fail(IDIST_ERR_INVALID_ARG, "k %u out of [1,%u]", k, IDIST_MAX_EF);
+    if (nq == 0) return IDIST_OK;
+    if (!d_count || !d_out_pid || !d_out_dist || !d_out_group || !d_out_count || (width && (!d_pid || !d_dist)) || (n && !d_groups))
+        return fail(IDIST_ERR_INVALID_ARG, "null device pointer");
+    CHK(check_device(device));
+    HIPCHK(hipSetDevice(device));
+    const GroupedOut g{(uint32_t*)d_out_pid, (uint32_t*)d_out_dist, (uint32_t*)d_out_group, (uint32_t*)d_out_count, nullptr, nullptr, nullptr, k};
+    return launch_grouped_select(g, (const uint32_t*)d_groups, n, (const uint32_t*)d_bits, (n + 31u) / 32u, nullptr, (const uint32_t*)d_pid,
+                                 (const uint32_t*)d_dist, (const uint32_t*)d_count, nullptr, width, nullptr, nq, 0u, kGroupedWhole,
+                                 (hipStream_t)hip_stream);
 }
 
 idist_status idist_search_ctx_attr_bitmap_ms(idist_search_ctx* ctx, float* ms) {

@@ -90,6 +90,8 @@ struct Knobs {
     uint32_t allowed_segments = 0;    // IDIST_ALLOWED_SEGMENTS=<1..64>: segments of the exact step of a restricted search (test knob: the result
                                       // must not depend on it; default: by the number of pending queries)
     uint32_t range_segments = 0;      // IDIST_RANGE_SEGMENTS=<1..64>: segments of the exact step of a range search (test knob, as allowed_segments)
+    uint64_t grouped_stage = 0;       // IDIST_GROUPED_STAGE=<bytes>: staging bound of the bitmaps of an exact round of a grouped search (test
+                                      // knob: small bounds cut the pending queries into chunks; the result must not depend on it; default 256 MiB)
     uint32_t range_sort_chunk = 0;    // IDIST_RANGE_SORT_CHUNK=<128..4096, a power of two>: keys a wave of the range search's sort holds in
                                       // LDS (test knob: small chunks send short lists through the global-memory strides; default 2048)
     uint32_t quad_nq = 0xFFFFFFFFu;   // IDIST_QUAD_NQ: batches up to this many queries run four waves per query (default: two
