@@ -80,7 +80,22 @@ inline void warn_ignored_knobs() {
 }
 #endif
 
-char g_err_anchor;                                       // (its address identifies this loaded library, see fresh_uid)
+// The CU count the search side and the helper kernels size their grids by: the device's, or IDIST_CUS=<1..1024> (test knob: a small
+// count makes small batches run the grid-stride loops' later trips, a large one the many short segments of a full chip; the results
+// must not depend on it).  It reaches everything sized by idist_index::n_cu / idist_search_ctx::n_cu: the searches and their
+// helper kernels, and also the row passes of load_points (normalise, augment), the filter tables' kernels (filter_rows_principal,
+// filter_inline), bruteforce with its rerank and row-norm kernels, and the stand-alone device entry points.  Every one of these
+// launches strides over its work or pulls it from a queue, and none waits for another workgroup, so any count is a legal geometry.
+// plan_build alone keeps the device's count (idist_index::n_cu_build): the insertion schedule is not this knob's business.
+inline int launch_cus(int device_cus) {
+    if (const char* e = test_env("IDIST_CUS")) {
+        const int v = atoi(e);
+        if (v >= 1 && v <= 1024) return v;
+    }
+    return device_cus;
+}
+
+char g_err_anchor;                                      // (its address identifies this loaded library, see fresh_uid)
 thread_local std::string g_err;
 // The identity of an index or a partitioned index, never reused.  uids are unique across the libraries of one process too
 // (libidist.so and the test build libidist_variants.so share handles in tests/): the counter starts at a value derived from where
@@ -253,7 +268,8 @@ struct idist_index {
     uint32_t* d_zero = nullptr;
     uint32_t* d_upper = nullptr;
     uint64_t* d_layer_off = nullptr;
-    int n_cu = 256;
+    int n_cu = 256;          // launch_cus(): what searches and helper kernels size their grids by
+    int n_cu_build = 256;    // the device's own count: plan_build's fact
     idist_build_stats stats{};
     // the walk's reject filter (FilterView, idist_device.hpp): a compact copy of the rows, made once — after a build / an import, or
     // on the first search of an index whose buffers were filled from outside (idist_index_alloc + a broadcast) — see filter_ensure
@@ -568,7 +584,10 @@ idist_status index_alloc(uint32_t n, uint32_t dim, const idist_config* cfg, cons
     ix->L = make_layout(ix->kdim);
     ix->n_upper = n_upper;
     hipDeviceProp_t p;
-    if (hipGetDeviceProperties(&p, device) == hipSuccess) ix->n_cu = p.multiProcessorCount;
+    if (hipGetDeviceProperties(&p, device) == hipSuccess) {
+        ix->n_cu_build = p.multiProcessorCount;
+        ix->n_cu = launch_cus(p.multiProcessorCount);
+    }
     size_t rows = 0;
     for (uint32_t l = 0; l < n_upper; l++) {
         if (layer_len[l] > n) { delete ix; return fail(IDIST_ERR_INVALID_ARG, "layer_len[%u] = %u > n", l, layer_len[l]); }
@@ -934,7 +953,7 @@ idist_status run_build(idist_index* ix, idist_progress* prog, bool tie_spill) {
     BuildFacts f;
     f.n = n;
     f.L = ix->L;
-    f.n_cu = ix->n_cu;
+    f.n_cu = ix->n_cu_build;
     f.ef_construction = cfg.ef_construction;
     f.max_batch = cfg.max_batch;
     f.has_heuristic = cfg.has_heuristic;
@@ -4249,7 +4268,7 @@ idist_status idist_attr_bitmaps_device(const void* d_values, uint32_t n, const v
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
     return launch_attr_bitmaps((const uint32_t*)d_values, n, (const uint32_t*)d_lo, (const uint32_t*)d_hi, n_sets, (uint32_t*)d_out,
-                               prop.multiProcessorCount, (hipStream_t)hip_stream);
+                               launch_cus(prop.multiProcessorCount), (hipStream_t)hip_stream);
 }
 
 idist_status idist_attr_match_bitmaps_device(const void* d_values, uint32_t n, uint32_t n_cols, uint64_t col_pitch, const void* d_clauses,
@@ -4264,7 +4283,7 @@ idist_status idist_attr_match_bitmaps_device(const void* d_values, uint32_t n, u
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, device));
     return launch_attr_match((const uint32_t*)d_values, n, n_cols, col_pitch, (const AttrClause*)d_clauses, (const uint32_t*)d_and_lims,
-                             (const uint32_t*)d_or_lims, n_sets, (uint32_t*)d_out, prop.multiProcessorCount, (hipStream_t)hip_stream);
+                             (const uint32_t*)d_or_lims, n_sets, (uint32_t*)d_out, launch_cus(prop.multiProcessorCount), (hipStream_t)hip_stream);
 }
 
 idist_status idist_search_batch_attr(const idist_index* idx, idist_search_ctx* ctx, const idist_attr* attr, const float* queries, uint32_t nq,
@@ -5106,7 +5125,7 @@ idist_status idist_range_merge_device(const void* const* d_keys, const void* con
     uint64_t* chunks = nullptr;
     CHK(mem.alloc(&c, nq));
     CHK(mem.alloc(&chunks, ((size_t)nq + 63u) / 64u));
-    CHK(launch_range_merge_counts(L, c, nullptr, chunks, (uint64_t*)d_lims, prop.multiProcessorCount, stream));
+    CHK(launch_range_merge_counts(L, c, nullptr, chunks, (uint64_t*)d_lims, launch_cus(prop.multiProcessorCount), stream));
     uint64_t total = 0;                                          // the one read-back: it checks the capacity
     HIPCHK(hipMemcpyAsync(&total, (const uint64_t*)d_lims + nq, 8, hipMemcpyDeviceToHost, stream));
     HIPCHK(hipStreamSynchronize(stream));
@@ -5117,7 +5136,7 @@ idist_status idist_range_merge_device(const void* const* d_keys, const void* con
     if (total == 0) return IDIST_OK;
     if (!d_out_pid || !d_out_dist) return fail(IDIST_ERR_INVALID_ARG, "null device pointer");
     return launch_range_merge(L, (const uint64_t*)d_lims, total, metric, (const float*)d_sq, dot_bound, (uint32_t*)d_out_pid,
-                              (float*)d_out_dist, prop.multiProcessorCount, stream);
+                              (float*)d_out_dist, launch_cus(prop.multiProcessorCount), stream);
 }
 
 // The range search over the parts behind its argument checks (p->rg_valid is false already).  src == nullptr: the plain call, which
@@ -5331,7 +5350,7 @@ idist_status idist_normalize_batch(const float* rows, uint32_t n, uint32_t dim, 
     CHK(mem.alloc(&d_x, xb / 4));
     if (out_norm2) CHK(mem.alloc(&d_s, n));
     HIPCHK(hipMemcpy(d_x, rows, xb, hipMemcpyHostToDevice));
-    CHK(launch_normalize(d_x, d_x, n, dim, dim, 0u, d_s, prop.multiProcessorCount, nullptr));
+    CHK(launch_normalize(d_x, d_x, n, dim, dim, 0u, d_s, launch_cus(prop.multiProcessorCount), nullptr));
     HIPCHK(hipMemcpy(out_rows, d_x, xb, hipMemcpyDeviceToHost));
     if (out_norm2) HIPCHK(hipMemcpy(out_norm2, d_s, (size_t)n * 4, hipMemcpyDeviceToHost));
     return IDIST_OK;
@@ -5355,7 +5374,7 @@ idist_status idist_dot_augment_batch(const float* rows, uint32_t n, uint32_t dim
     if (out_rows) CHK(mem.alloc(&d_a, ab / 4));
     HIPCHK(hipMemcpy(d_x, rows, xb, hipMemcpyHostToDevice));
     float S = bound_in;
-    CHK(dot_augment_device(d_x, d_a, n, dim, kdim, 0u, &S, d_s, prop.multiProcessorCount));   // (natural x~ rows: stride kdim, no blocks)
+    CHK(dot_augment_device(d_x, d_a, n, dim, kdim, 0u, &S, d_s, launch_cus(prop.multiProcessorCount)));   // (natural x~ rows: stride kdim, no blocks)
     if (out_rows) HIPCHK(hipMemcpy(out_rows, d_a, ab, hipMemcpyDeviceToHost));
     if (out_norm2) HIPCHK(hipMemcpy(out_norm2, d_s, (size_t)n * 4, hipMemcpyDeviceToHost));
     if (out_bound) *out_bound = S;

@@ -8,6 +8,7 @@
 """
 import os
 import subprocess
+import sys
 
 import pytest
 
@@ -17,6 +18,22 @@ EMU_SO = os.path.join(ROOT, "tests", "simt", "_build", "libidist_emu.so")
 
 def engine_params():
     return [pytest.param("emu", id="emu"), pytest.param("gpu", id="gpu", marks=pytest.mark.gpu)]
+
+
+_CUS = {}
+
+
+def cu_count(kind):
+    """The CU count the engine sizes its grids by: 1 under the emulator (its multiProcessorCount); on the GPU device 0's, asked of
+    torch in a child process, once — torch brings a HIP runtime of its own, which must not be initialised next to the library's."""
+    if kind != "gpu":
+        return 1
+    if "gpu" not in _CUS:
+        out = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.get_device_properties(0).multi_processor_count)"],
+                             capture_output=True, text=True, timeout=300, check=True).stdout
+        _CUS["gpu"] = int(out.split()[-1])
+        assert 1 <= _CUS["gpu"] <= 1024
+    return _CUS["gpu"]
 
 
 def build_emu():

@@ -118,7 +118,7 @@ def search_variant(env):
             swapped = None
     keys = ("IDIST_LATENCY_NQ", "IDIST_WALK", "IDIST_VISITED", "IDIST_TAB_LOG2", "IDIST_QUAD_NQ", "IDIST_BUILD_A2",
             "IDIST_TAB_FORMAT", "IDIST_BUILD_NO_FAST", "IDIST_BUILD_QUAD", "IDIST_BUILD_A_REGS", "IDIST_W2_EF", "IDIST_FILTER",
-            "IDIST_BUILD_FILTER")
+            "IDIST_BUILD_FILTER", "IDIST_CUS")
     old = {k: os.environ.get(k) for k in keys}
     for k in keys:
         os.environ.pop(k, None)

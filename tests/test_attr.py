@@ -128,6 +128,34 @@ def test_bitmap_kernel(eng, n_sets):
         mem.free()
 
 
+def test_bitmap_kernel_past_the_grid(eng):
+    """more work items than workgroups.  attr_grid never cuts the sets into more chunks than the CUs want waves, so its cap binds only
+    once the TILES alone exceed it: n > 4096 x 32 x the CU count (33.5M points on 256 CUs, 131,072 under the emulator's one) — a
+    workgroup then takes tile t and tile t + grid.  n ends 37 points into a tile: no multiple of 64."""
+    # cap: min(items, n_cu * 32) workgroups of one (tile, chunk of sets) each, attr_grid (idist_capi.hip)
+    from engines import cu_count
+    ida, kind = eng
+    from instant_distance_amd import _capi
+
+    L = _capi.lib()
+    n = (cu_count(kind) * 32 + 1) * 4096 + 37
+    words = (n + 31) // 32
+    rng = np.random.default_rng(250)
+    lo, hi = np.array([3, TOP], np.uint32), np.array([5, FULL], np.uint32)
+    v = rng.choice(np.array([0, 1, 2, 3, 4, 5, 6, 7, 0, TOP, FULL], np.uint32), n)
+    v[-1] = 3
+    mem = DeviceMem(kind)
+    try:
+        out = np.full(2 * words + 5, FILL, np.uint32)
+        d_out = mem.up(out)
+        L.check(L.idist_attr_bitmaps_device(mem.up(v), n, mem.up(lo), mem.up(hi), 2, d_out, 0, None))
+        got = mem.down(d_out, out)
+        assert np.array_equal(got[: 2 * words].reshape(2, words), bitmap_model(v, lo, hi))
+        assert np.all(got[2 * words:] == FILL)
+    finally:
+        mem.free()
+
+
 # ---- the attribute and the conditions of the parity tests ------------------------------------------------------------------------------
 def attribute(n, seed, groups=100):
     """a uniform category in [0, groups) per point; one point alone in its category far above 2^31; a few points at 0xFFFFFFFF"""

@@ -179,6 +179,37 @@ def test_match_kernel(eng, n_sets, n_cols):
         mem.free()
 
 
+def test_match_kernel_past_the_grid(eng):
+    """tests/test_attr.py's test_bitmap_kernel_past_the_grid for attr_match_kernel: two columns, col_pitch = n + 5, more tiles than
+    workgroups (the grid is attr_grid's), n no multiple of 64; a workgroup keeps a loaded tile while consecutive clauses name its
+    column — condition 0 ends and condition 1 starts on column 1, so the kept tile must not outlive the work item"""
+    # cap: min(items, n_cu * 32) workgroups of one (tile, chunk of sets) each, attr_grid (idist_capi.hip)
+    from engines import cu_count
+    ida, kind = eng
+    from instant_distance_amd import _capi
+
+    L = _capi.lib()
+    n = (cu_count(kind) * 32 + 1) * 4096 + 37
+    words, pitch = (n + 31) // 32, n + 5
+    rng = np.random.default_rng(350)
+    conds = [[[(0, 1, 6), (1, 2, TOP)]], [[(1, 3, 3)], [(0, TOP, FULL)]]]
+    clauses, and_lims, or_lims = flat(conds)
+    vals = rng.choice(np.array([0, 1, 2, 3, 4, 5, 6, 7, 0, TOP, FULL], np.uint32), (2, n))
+    vals[:, -1] = (3, 3)
+    table = np.full(pitch + n, 0xDEADBEEF, np.uint32)
+    table[:n], table[pitch:] = vals[0], vals[1]
+    mem = DeviceMem(kind)
+    try:
+        out = np.full(2 * words + 5, FILL, np.uint32)
+        d_out = mem.up(out)
+        L.check(L.idist_attr_match_bitmaps_device(mem.up(table), n, 2, pitch, mem.up(clauses), mem.up(and_lims), mem.up(or_lims), 2, d_out, 0, None))
+        got = mem.down(d_out, out)
+        assert np.array_equal(got[: 2 * words].reshape(2, words), program_model(list(vals), clauses, and_lims, or_lims))
+        assert np.all(got[2 * words:] == FILL)
+    finally:
+        mem.free()
+
+
 # ---- the table and the conditions of the parity tests -------------------------------------------------------------------------------------
 def table_of(n, seed):
     """two columns: "a", tests/test_attr.py's attribute (a uniform category in [0, 100), one point alone at TOP + 5, a few at

@@ -125,6 +125,27 @@ def test_normalize_kernel(eng, oracle, dim):
     assert np.array_equal(pc.bits(ida.normalize(np.ldexp(x, k).astype(np.float32))), pc.bits(want))
 
 
+@pytest.mark.parametrize("dim", [5, 300])
+def test_normalize_kernel_past_the_grid(eng, oracle, dim):
+    """more rows than the grid's waves take in one trip (eight each): a wave normalises rows r .. r + 7, then the eight rows a grid
+    further.  1009 distinct rows, row i of the batch = row i % 1009 (the trip length is no multiple of 1009), the model over the 1009;
+    the bit rule of test_normalize_kernel"""
+    # cap: min(ceil(n / 8), n_cu * 32) waves of eight rows, launch_normalize (idist_capi.hip)
+    from engines import cu_count
+    ida, kind = eng
+    m = 1009
+    n = 8 * cu_count(kind) * 32 + 37
+    assert n > m or kind == "emu"
+    rng = np.random.default_rng(150 + dim)
+    base = scaled_rows(rng, m, dim)
+    rows = np.arange(n) % m
+    x = np.ascontiguousarray(base[rows])
+    want, want_s = np_normalize(oracle, base)
+    got, s = ida.normalize(x, return_norm2=True)
+    assert np.array_equal(pc.bits(s), pc.bits(want_s[rows]))
+    assert np.array_equal(pc.bits(got), pc.bits(want[rows]))
+
+
 @pytest.mark.parametrize("dim", [1, 5, 12, 300])
 def test_normalize_special_rows(eng, oracle, dim):
     """zero, NaN, inf, an s that overflows and denormals whose s underflows: all come back unchanged"""

@@ -130,6 +130,30 @@ def test_augment_kernel(eng, oracle, dim):
     assert np.array_equal(x, keep)
 
 
+@pytest.mark.parametrize("dim", [5, 300])
+def test_augment_kernel_past_the_grid(eng, oracle, dim):
+    """more rows than the waves of dot_norms_kernel take in one trip (eight each); at dim 300 on the GPU also more elements than the
+    lanes of dot_augment_rows_kernel's grid.  1009 distinct rows, row i of the batch = row i % 1009, the model over the 1009 (the
+    bound S is the maximum over them); the bit rule of test_augment_kernel"""
+    # caps: min(ceil(n / 8), n_cu * 32) waves of eight rows, launch_dot_norms; min(ceil(n * stride / 256), 65536) workgroups of 256
+    # elements, dot_augment_device (idist_capi.hip)
+    from engines import cu_count
+    ida, kind = eng
+    m = 1009
+    n = 8 * cu_count(kind) * 32 + 37
+    rng = np.random.default_rng(250 + dim)
+    base = scaled_rows(rng, m, dim)
+    rows = np.arange(n) % m
+    if kind == "emu":                           # (fewer rows than the 1009: the model over the rows that are there)
+        base, rows = np.ascontiguousarray(base[:n]), np.arange(n)
+    x = np.ascontiguousarray(base[rows])
+    want, want_S, want_s = np_augment(oracle, base)
+    got, got_S, s = ida.augment_dot(x, return_norm2=True)
+    assert got.shape == (n, dim + 1) and f32_bits(got_S) == f32_bits(want_S)
+    assert np.array_equal(pc.bits(s), pc.bits(want_s[rows]))
+    assert np.array_equal(pc.bits(got), pc.bits(want[rows]))
+
+
 @pytest.mark.parametrize("dim", [1, 5, 12, 300])
 def test_augment_special_rows(eng, oracle, dim):
     """a zero row, a NaN row, inf rows, a row whose s overflows, denormals whose s underflows, and the maximal row"""

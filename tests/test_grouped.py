@@ -441,6 +441,77 @@ def test_collapse_kernel(eng, width):
         mem.free()
 
 
+def collapse_model_flat(pid, dist, count, groups, n, allowed, k):
+    """kernel_model without a Python loop over the lists: an entry is kept when it lies below the count, names a point, is allowed and
+    no kept-or-not valid entry in front of it has its group; the first k kept entries, in order.  allowed: bool [nq][n]"""
+    nq, width = pid.shape
+    ok = (np.arange(width)[None, :] < count[:, None]) & (pid < n)
+    safe = np.where(ok, pid, 0)
+    ok &= allowed[np.arange(nq)[:, None], safe]
+    g = groups[safe]
+    keep = ok.copy()
+    for j in range(1, width):
+        keep[:, j] &= ~np.any(ok[:, :j] & (g[:, :j] == g[:, j: j + 1]), axis=1)
+    rank = np.cumsum(keep, axis=1) - 1
+    keep &= rank < k
+    o_pid, o_dist = np.full((nq, k), INVALID, np.uint32), np.full((nq, k), INF_BITS, np.uint32)
+    o_group = np.zeros((nq, k), np.uint32)
+    rows, cols = np.nonzero(keep)
+    o_pid[rows, rank[rows, cols]], o_dist[rows, rank[rows, cols]], o_group[rows, rank[rows, cols]] = pid[rows, cols], dist[rows, cols], g[rows, cols]
+    return o_pid, o_dist, o_group, keep.sum(axis=1).astype(np.uint32)
+
+
+def test_collapse_kernel_past_the_grid(eng):
+    """65,536 + 37 lists of width 3, k = 2: the first run in which grouped_select_kernel's workgroups take a second list.  List j and
+    list j + 65,536 — the two lists of one workgroup — hold other points of other groups under complementary bitmaps, so a group set
+    left in LDS by the first list, or the first list's bitmap row, changes the second list's answer."""
+    # cap: min(np, 65536) workgroups of one list each, launch_grouped_select (idist_capi.hip)
+    ida, kind = eng
+    from instant_distance_amd import _capi
+
+    L = _capi.lib()
+    grid, width, k, n = 65536, 3, 2, 61
+    nq = grid + 37
+    rng = np.random.default_rng(4242)
+    groups = (np.arange(n) % 5).astype(np.uint32) * np.uint32(0x33333333)            # (0 and 0xCCCCCCCC among them; neighbours differ)
+    pid = rng.integers(0, n, (nq, width)).astype(np.uint32)
+    pid[rng.random((nq, width)) < 0.05] = INVALID
+    pid[grid:] = np.where(pid[:37] < n, (pid[:37] + 1) % n, pid[:37])                # the second list of a workgroup: other groups
+    count = rng.integers(0, width + 1, nq).astype(np.uint32)
+    count[:37] = count[grid:] = width
+    allowed = rng.random((nq, n)) < 0.6
+    allowed[grid:] = ~allowed[:37]
+    dist = rng.integers(0, 0x7F000000, (nq, width)).astype(np.uint32)
+    words = (n + 31) // 32
+    padded = np.zeros((nq, words * 32), np.uint8)
+    padded[:, :n] = allowed
+    bits = np.packbits(padded, axis=1, bitorder="little").view("<u4")
+    every = np.ones((nq, n), bool)
+    # the vectorised model is the module's kernel_model, held on the rows that share a workgroup and a sample of the others
+    rows = np.concatenate([np.arange(37), np.arange(grid, nq), rng.choice(nq, 200)])
+    for a in (allowed, every):
+        flat, slow = collapse_model_flat(pid[rows], dist[rows], count[rows], groups, n, a[rows], k), kernel_model(pid[rows], dist[rows], count[rows], groups, n, a[rows], k)
+        assert all(np.array_equal(x, y) for x, y in zip(flat, slow))
+    mem = DeviceMem(kind)
+    try:
+        d_pid, d_dist, d_count, d_groups, d_bits = mem.up(pid), mem.up(dist), mem.up(count), mem.up(groups), mem.up(bits)
+        for what, a, d_b in (("bitmap", allowed, d_bits), ("no bitmap", every, None)):
+            want = collapse_model_flat(pid, dist, count, groups, n, a, k)
+            if what == "bitmap":           # the complementary bitmaps do change the answers of the rows that share a workgroup
+                assert np.any(want[0][:37] != collapse_model_flat(pid[:37], dist[:37], count[:37], groups, n, a[grid:], k)[0])
+            outs = [np.full(nq * k + 5, FILL, np.uint32) for _ in range(3)] + [np.full(nq + 5, FILL, np.uint32)]
+            d_outs = [mem.up(o) for o in outs]
+            L.check(L.idist_grouped_collapse_device(d_pid, d_dist, d_count, nq, width, d_groups, n, d_b, k, *d_outs, 0, None))
+            got = [mem.down(d, o) for d, o in zip(d_outs, outs)]
+            for i, name in enumerate(("ids", "distance bits", "groups")):
+                assert np.array_equal(got[i][: nq * k].reshape(nq, k), want[i]), (what, name)
+                assert np.all(got[i][nq * k:] == FILL), (what, name)
+            assert np.array_equal(got[3][:nq], want[3]) and np.all(got[3][nq:] == FILL), what
+            assert want[3].max() == k and want[3].min() == 0
+    finally:
+        mem.free()
+
+
 # ---- 5. arguments and trivial cases -----------------------------------------------------------------------------------------------------
 def test_argument_errors(eng):
     ida, kind = eng

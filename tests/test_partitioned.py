@@ -67,6 +67,22 @@ class DeviceMem:
         assert self.hip.hipMemcpy(out.ctypes.data, C.c_void_p(ptr), out.nbytes, 2) == 0   # hipMemcpyDeviceToHost
         return out
 
+    def up_tiled(self, block, nq):
+        """block [P][m][...] -> the device array [P][nq][...] whose row q is block row q % m, without making it on the host"""
+        block = np.ascontiguousarray(block)
+        if self.hip is None:
+            return self.up(block[:, np.arange(nq) % block.shape[1]])
+        P, m = block.shape[:2]
+        row = block[0, 0].nbytes
+        p = C.c_void_p()
+        assert self.hip.hipMalloc(C.byref(p), P * nq * row) == 0
+        self.keep.append(p)
+        for l in range(P):
+            for q0 in range(0, nq, m):
+                rows = min(m, nq - q0)
+                assert self.hip.hipMemcpy(C.c_void_p(p.value + (l * nq + q0) * row), block[l].ctypes.data, rows * row, 1) == 0
+        return p.value
+
     def free(self):
         if self.hip is not None:
             for p in self.keep:
@@ -74,12 +90,18 @@ class DeviceMem:
         self.keep = []
 
 
-def run_merge(kind, pid, dist_bits, count, counters, base, out_width):
-    """idist_merge_topk_device on [P][nq][w] lists; returns (pid, dist bits, count, counters) of the merged result."""
+def run_merge(kind, pid, dist_bits, count, counters, base, out_width, nq=None):
+    """idist_merge_topk_device on [P][nq][w] lists; returns (pid, dist bits, count, counters) of the merged result.
+    nq: the lists are [P][m][w] and row q of the batch is their row q % m (tiled on the device: the wide batches of the grid tests)"""
     from instant_distance_amd import _capi
 
-    P, nq, w = pid.shape
+    P, m, w = pid.shape
     mem = DeviceMem(kind)
+    if nq is not None:
+        up = mem.up
+        mem.up = lambda x: mem.up_tiled(x, nq) if (x.ndim >= 2 and x.shape[:2] == (P, m)) else up(x)
+    else:
+        nq = m
     try:
         # outputs start as a pattern no result can hold: every element must be written (results and padding alike)
         o_pid = np.full((nq, out_width), 0xABABABAB, np.uint32)
@@ -188,6 +210,28 @@ def test_merge_kernel_beyond_lds(eng):
     lists = random_lists(rng, 64, S(kind, 2, 24), 1024)
     check_merge(kind, lists, 100)
     check_merge(kind, lists, 4096, with_counters=False)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("form, w, m", [("lds", 7, 521), ("beyond lds", 2710, 17)])
+def test_merge_kernel_past_the_grid_gpu(engine_loader, form, w, m):
+    """more queries than workgroups: a workgroup merges query q, then q + 16,384 with the same LDS head (len_s, base_s) and, in the LDS
+    form, the same key region.  m distinct rows of random_lists, row q of the batch = row q % m (16,384 % m != 0: the two queries of a
+    workgroup differ), the expected rows from merge_reference over the m.  P = 3; w = 2710: 3 x 2710 keys do not fit the LDS budget."""
+    # cap: min(nq, 16384) workgroups of one query each, launch_merge (idist_capi.hip)
+    engine_loader("gpu")
+    P, nq = 3, 16384 + 37
+    assert (P * w * 8 + 512 > 64 * 1024) == (form == "beyond lds") and 16384 % m
+    rng = np.random.default_rng(600 + w)
+    pid, bits, count, counters, base = random_lists(rng, P, m, w)
+    rows = np.arange(nq) % m
+    ow = 7 if form == "lds" else 100
+    got = run_merge("gpu", pid, bits, count, counters, base, ow, nq=nq)          # (1.07 GB of lists on the device in the beyond-LDS form:
+    #  nq > 16,384 rows of more than 8,128 keys is what that form past the grid takes; they are tiled there, never made on the host)
+    want = merge_reference(pid, bits, count, counters, base, ow)
+    assert not np.array_equal(want[0][0], want[0][16384 % m])                        # the two queries of workgroup 0 differ
+    for g, x, name in zip(got, want, ("global ids", "distance bits", "count", "counters")):
+        assert np.array_equal(g, x[rows]), (form, name)
 
 
 def test_merge_kernel_rejects_bad_shapes(eng):

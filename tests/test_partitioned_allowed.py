@@ -202,6 +202,34 @@ def test_slice_kernel(eng, n_sets):
         mem.free()
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("bit_offset", [1, 31, 33])
+def test_slice_kernel_past_the_grid_gpu(engine_loader, bit_offset):
+    """more output words than lanes in the grid: 3 rows of 350,001 words, a lane writes word i and word i + 256 x 4096; the last word
+    of a row holds 5 bits; random bits all around the range, the source ends at the last word that may be read"""
+    # cap: min(ceil(total / 256), 4096) workgroups of 256 lanes, one output word per lane, idist_allowed_slice_device (idist_capi.hip)
+    engine_loader("gpu")
+    from instant_distance_amd import _capi
+
+    L = _capi.lib()
+    n_sets, n_out = 3, 32 * 350000 + 5
+    words_out = (n_out + 31) // 32
+    assert n_sets * words_out > 256 * 4096
+    w_end = (bit_offset + n_out + 31) // 32
+    pitch = w_end + 3
+    rng = np.random.default_rng(170 + bit_offset)
+    src = rng.integers(0, 2**32, (n_sets - 1) * pitch + w_end, dtype=np.uint64).astype(np.uint32)
+    rows = [src[s * pitch: s * pitch + w_end] for s in range(n_sets)]
+    mem = DeviceMem("gpu")
+    try:
+        out = np.full((n_sets, words_out), 0xABABABAB, np.uint32)
+        d_out = mem.up(out)
+        L.check(L.idist_allowed_slice_device(mem.up(src), n_sets, pitch, bit_offset, n_out, d_out, 0, None))
+        assert np.array_equal(mem.down(d_out, out), slice_model(rows, bit_offset, n_out))
+    finally:
+        mem.free()
+
+
 # ---- 2. composition parity: every path of every part in one call --------------------------------------------------------------------
 @pytest.mark.parametrize("P", [1, 2, 3, 5])
 def test_composition_parity(eng, oracle, P):

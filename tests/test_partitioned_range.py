@@ -287,6 +287,95 @@ def test_merge_kernels_all_lists_empty(eng):
     assert st == 0 and total == 0 and np.all(lims == 0) and np.all(pid == FILL) and np.all(dist == FILL)
 
 
+def synthetic_lists_flat(rng, P, nq, lens):
+    """synthetic_lists without a Python loop over the queries, for batches of thousands to millions: the same key buffers (ascending
+    segments in a random completion order, zero keys between them, distance bits from a small pool so that the global id decides)
+    -> (key buffers, offsets [P][nq] u64, base [P], the expected flat global ids, the expected flat distance bits)"""
+    sizes = np.maximum(lens.max(axis=1), 1) + rng.integers(1, 9, size=P)
+    base = np.concatenate([[0], np.cumsum(sizes)[:-1]]).astype(np.uint32)
+    pool = np.sort(rng.random(48, dtype=np.float32)).view(np.uint32)
+    pool = np.concatenate([pool, np.full(2, 0x7F800000, np.uint32)])
+    bufs, offs = [], np.zeros((P, nq), np.uint64)
+    all_q, all_g, all_d = [], [], []
+    for l in range(P):
+        c = lens[l].astype(np.int64)
+        qidx = np.repeat(np.arange(nq), c)
+        first = np.concatenate([[0], np.cumsum(c)[:-1]])
+        j = np.arange(len(qidx)) - first[qidx]
+        ids = ((rng.integers(0, int(sizes[l]), size=nq)[qidx] + j) % int(sizes[l])).astype(np.uint64)   # distinct within a segment: c <= sizes[l]
+        key = (rng.choice(pool, size=len(qidx)).astype(np.uint64) << np.uint64(32)) | ids
+        key = key[np.lexsort((key, qidx))]                                          # every segment ascending
+        perm = rng.permutation(nq)
+        gap = rng.integers(0, 4, size=nq)
+        start = np.zeros(nq, np.int64)
+        start[perm] = np.cumsum(gap + c[perm]) - c[perm]
+        buf = np.zeros(int(c.sum() + gap.sum()) + 2, np.uint64)
+        buf[start[qidx] + j] = key
+        offs[l] = start.astype(np.uint64)
+        bufs.append(buf)
+        all_q.append(qidx)
+        all_g.append((key & np.uint64(0xFFFFFFFF)) + np.uint64(base[l]))
+        all_d.append((key >> np.uint64(32)).astype(np.uint32))
+    qs, g, d = np.concatenate(all_q), np.concatenate(all_g), np.concatenate(all_d)
+    order = np.lexsort((g, d, qs))
+    return bufs, offs, base, g[order].astype(np.uint32), d[order]
+
+
+def check_range_merge_flat(kind, rng, lens):
+    """check_range_merge's assertions on a wide batch"""
+    bufs, offs, base, w_pid, w_bits = synthetic_lists_flat(rng, *lens.shape, lens)
+    total = int(lens.sum())
+    st, lims, pid, dist, got_total = run_range_merge(kind, bufs, offs, lens, base, total)
+    assert st == 0 and got_total == total
+    assert np.array_equal(lims, np.concatenate([[0], np.cumsum(lens.sum(axis=0))]).astype(np.uint64)), "lims"
+    assert np.array_equal(pid[:total], w_pid), "global ids"
+    assert np.array_equal(dist[:total], w_bits), "distance bits"
+    assert np.all(pid[total:] == FILL) and np.all(dist[total:] == FILL)
+
+
+def test_synthetic_lists_flat_rows_are_the_merge_of_its_buffers():
+    """the vectorised model's expected rows, derived again query by query from the buffers, offsets and bases it returned"""
+    rng = np.random.default_rng(77)
+    lens = rng.choice([0, 1, 2, 65], size=(3, 40))
+    bufs, offs, base, w_pid, w_bits = synthetic_lists_flat(rng, 3, 40, lens)
+    g, d = [], []
+    for q in range(40):
+        keys = [bufs[l][int(offs[l, q]): int(offs[l, q]) + int(lens[l, q])] for l in range(3)]
+        assert all(np.all(k[:-1] < k[1:]) for k in keys)                            # ascending, no id twice
+        gq = np.concatenate([(k & np.uint64(0xFFFFFFFF)) + np.uint64(base[l]) for l, k in enumerate(keys)])
+        dq = np.concatenate([(k >> np.uint64(32)).astype(np.uint32) for k in keys])
+        order = np.lexsort((gq, dq))
+        g.append(gq[order].astype(np.uint32))
+        d.append(dq[order])
+    assert np.array_equal(np.concatenate(g), w_pid) and np.array_equal(np.concatenate(d), w_bits)
+
+
+@pytest.mark.parametrize("nq", [4095, 4096, 4097, 8193])
+@pytest.mark.parametrize("P", [1, 3])
+def test_merge_kernels_second_level_of_the_prefix_sum(eng, P, nq):
+    """range_offsets_kernel sums the chunk sums in front of its chunk with `for (c = lane; c < b; c += 64)`: chunk b has b chunks in
+    front of it, so the loop's second trip needs a chunk b > 64, that is nq > 65 x 64 = 4,160 — of these shapes 8193 alone (129
+    chunks); 4095, 4096 and 4097 stand on both sides of the last full first trip.  Lengths from {0, 1, 2, 65}."""
+    # cap: 64 lanes, one chunk of 64 items each, per trip of the chunk loop in range_offsets_kernel (idist_range.hpp), launched by range_prefix_on
+    ida, kind = eng
+    rng = np.random.default_rng(8000 + 10 * nq + P)
+    lens = rng.choice([0, 1, 2, 65], size=(P, nq), p=[0.4, 0.3, 0.2, 0.1])
+    assert {0, 1, 2, 65} <= set(lens.ravel().tolist())
+    check_range_merge_flat(kind, rng, lens)
+
+
+@pytest.mark.gpu
+def test_merge_kernels_past_the_prefix_sum_grid_gpu(engine_loader):
+    """the first batch at which range_prefix_on's grid strides: more than 65,536 chunks of 64 queries; lengths 0 / 1"""
+    # cap: min(chunks, 65536) workgroups of 64 items, range_prefix_on (idist_capi.hip); range_merge_counts_kernel (n_cu * 8 x 256 rows,
+    # launch_range_merge_counts) and range_merge_kernel (n_cu * 32 tiles, launch_range_merge) stride at this size too
+    engine_loader("gpu")
+    nq = 64 * 65536 + 37
+    rng = np.random.default_rng(8100)
+    lens = rng.integers(0, 2, size=(2, nq))
+    check_range_merge_flat("gpu", rng, lens)
+
+
 def test_merge_kernels_report(eng):
     """the report runs in the merge kernel: cosine halves, DOT subtracts the query's own term s(q) + S"""
     ida, kind = eng
