@@ -885,8 +885,8 @@ idist_status idist_attr_match_bitmaps_device(const void* d_values, uint32_t n, u
  * sized by k); the exact step runs in rounds of the restricted search's scan over A minus the groups found so far, at most k of
  * them (idist_search_ctx_allowed_kernel_ms: the collapse under select_ms, the rounds under exact_ms).  An unrestricted call
  * uploads no bitmap.
- * Out of scope: more than one member per group, the partitioned index, device-pointer / stream variants,
- * idist_search_batch_sharded. */
+ * Out of scope: more than one member per group, device-pointer / stream variants, idist_search_batch_sharded (the partitioned
+ * index: idist_partitioned_search_batch_grouped below). */
 idist_status idist_search_batch_grouped(const idist_index* idx, idist_search_ctx* ctx, const idist_attr* attr, uint32_t group_col,
                                         const float* queries, uint32_t nq,
                                         const idist_attr_conds* conds,           /* NULL: no restriction */
@@ -906,6 +906,53 @@ idist_status idist_grouped_collapse_device(const void* d_pid, const void* d_dist
                                            const void* d_bits /* [nq][(n+31)/32] or NULL: everything allowed */,
                                            uint32_t k, void* d_out_pid, void* d_out_dist, void* d_out_group, void* d_out_count,
                                            int32_t device, void* hip_stream);
+
+/* Grouped search over a partitioned index.  attr is a table made for p (idist_partitioned_attr_new_columns);
+ * g(i) is column group_col at GLOBAL id i.  DEFINITION.  For query q let L_p be what idist_search_batch_grouped returns on part p
+ * with the part's slice of the table, the part's slice of q's condition, the same k and max_rungs, raw distances, ids shifted by
+ * base[p].  Row q is collapse of the merge of the L_p by the u64 key  raw distance bits << 32 | global id:  walk the merged order,
+ * keep an entry iff no earlier kept entry has its group, stop after k.
+ *   count, padding   count = min(k, distinct groups among the L_p); padding IDIST_INVALID / +inf / group 0.
+ *   rungs, counters  out_rung[q * n_parts + p] is part p's rung (IDIST_RUNG_NONE for an empty part or an empty slice); the counters
+ *                    are the parts' counters summed.
+ *   report           the metric's report runs once, after the merge, on the [nq][k] result.
+ *   retries          strict-tie retries stay inside the parts; a part's failure on rung 0 is returned with the
+ *                    "part <p> (device <d>): " prefix.
+ *   errors           IDIST_ERR_INVALID_ARG: the cases of idist_search_batch_grouped (group_col >= n_cols names the column count; k
+ *                    outside 1..ef_search; max_rungs < -1; null pointers) and those of idist_partitioned_search_batch_match,
+ *                    an attr not made for p included.  nq == 0 is no error.  N == 0 or ef_search == 0: every count 0, every rung
+ *                    IDIST_RUNG_NONE, every counter 0.
+ * Three consequences the tests rest on:
+ *   1. EXACTNESS at max_rungs == 0: the row is the true answer over the whole set — the k groups whose nearest allowed member is
+ *      nearest, each by that member — bit for bit what idist_search_batch_grouped at max_rungs == 0 gives on one index over the
+ *      concatenated points.  Let group G be in the global top k, its nearest member in part p.  Every group nearer than G inside
+ *      part p is nearer than G globally (a part's minimum is never below the global one), so fewer than k groups precede G in L_p
+ *      and G's true representative is in L_p; a farther copy of G in another list has a larger key and is dropped by the collapse.
+ *   2. ONE PART is the identity: every output equals idist_search_batch_grouped on that part.
+ *   3. g(i) = global id is the identity: every output equals idist_partitioned_search_batch_match with the same conds; with
+ *      conds == NULL idist_partitioned_search_batch_allowed_sets with one all-ones set.
+ * idist_partitioned_last_merge_ms reports the grouped merge kernel after this call.  Out of scope as for idist_search_batch_grouped. */
+idist_status idist_partitioned_search_batch_grouped(idist_partitioned* p, const idist_attr* attr, uint32_t group_col,
+                                                    const float* queries, uint32_t nq,
+                                                    const idist_attr_conds* conds,       /* NULL: no restriction */
+                                                    uint32_t k, int32_t max_rungs,
+                                                    uint32_t* out_pid, float* out_dist,  /* nq*k, global ids */
+                                                    uint32_t* out_group,                 /* nq*k or NULL */
+                                                    uint32_t* out_count,                 /* nq */
+                                                    uint32_t* out_rung,                  /* [nq][n_parts] or NULL */
+                                                    uint32_t* out_counters);             /* nq*3 or NULL */
+/* The union kernel of that call on its own (as idist_merge_topk_device and idist_grouped_collapse_device are): d_pid / d_dist /
+ * d_group [n_lists][nq][width], d_count [n_lists][nq], d_counters [n_lists][nq][3] or NULL, in the memory of `device`; base [n_lists]
+ * on the host; 1 <= n_lists <= 64, 1 <= width, k <= IDIST_MAX_EF.  Each list is ascending in the key  distance bits << 32 | base[l] +
+ * pid  and holds pairwise distinct groups; only the first min(count, width) entries of a list are read.  Row q of d_out_pid /
+ * d_out_dist / d_out_group [nq][k] is the collapse of the merged lists of query q, padded as above; d_out_count [nq]; d_out_counters
+ * [nq][3] (the lists' counters summed) is written iff d_counters is given.  Every output word is written exactly once, no global
+ * atomics, the same bytes whatever the grid; one path for every size — the lists are never staged.  nq == 0: nothing is done.
+ * Enqueued on `hip_stream` without synchronising. */
+idist_status idist_grouped_merge_device(const void* d_pid, const void* d_dist, const void* d_group, const void* d_count,
+                                        const void* d_counters /* or NULL */, uint32_t n_lists, uint32_t nq, uint32_t width,
+                                        const uint32_t* base /* host */, uint32_t k, void* d_out_pid, void* d_out_dist,
+                                        void* d_out_group, void* d_out_count, void* d_out_counters, int32_t device, void* hip_stream);
 
 /* Point::distance for id lists (core/lib.rs:780-782 as used at :709-710): out[q][i] =
  * distance(queries[q], points[ids[q][i]]) for i < n_ids; IDIST_INVALID ids give +inf.

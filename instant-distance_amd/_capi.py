@@ -206,6 +206,10 @@ SYMBOLS = {
                                                _u32p, _u32p, _u32p, _u32p]),
     "idist_grouped_collapse_device": (C.c_int32, [_vp, _vp, _vp, C.c_uint32, C.c_uint32, _vp, C.c_uint32, _vp, C.c_uint32, _vp, _vp, _vp, _vp,
                                                   C.c_int32, _vp]),
+    "idist_partitioned_search_batch_grouped": (C.c_int32, [_vp, _vp, C.c_uint32, _f32p, C.c_uint32, _condsp, C.c_uint32, C.c_int32, _u32p,
+                                                           _f32p, _u32p, _u32p, _u32p, _u32p]),
+    "idist_grouped_merge_device": (C.c_int32, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, _vp, _vp, _vp,
+                                               _vp, _vp, C.c_int32, _vp]),
     "idist_distance_batch": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, _f32p]),
     "idist_filter_bound_batch": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, _f32p]),
     "idist_bruteforce": (C.c_int32, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),

@@ -16,6 +16,7 @@
 #include "idist_range_merge.hpp"
 #include "idist_attr.hpp"
 #include "idist_grouped.hpp"
+#include "idist_grouped_merge.hpp"
 #include "idist_basis.hpp"
 
 #ifndef IDIST_EMU
@@ -494,6 +495,7 @@ struct idist_partitioned {
     DevBuf<uint32_t> s_pid, s_cnt, s_ctr, o_pid, o_cnt, o_ctr;
     DevBuf<float> s_dist, o_dist;
     DevBuf<uint32_t> s_rung;                 // restricted search: the parts' rungs [P][nq]
+    DevBuf<uint32_t> s_grp, o_grp;           // grouped search: the groups of the parts' lists [P][nq][k] and of the result [nq][k]
     float al_slice_ms = 0.0f;                // ... and the host time its last call spent on the bitmaps: upload + slice, every part
                                              // (an attribute call: the parts' bitmap kernels, HIP events, summed)
     // range search, on the merge device: the merged counts, lims and the chunk sums of their prefix sum; the merged result, which no
@@ -2981,10 +2983,10 @@ static idist_status partitioned_upload_queries(idist_partitioned* p, const float
     });
 }
 
-// A part away from the merge device: its (pid, dist, count[, rung][, counters]) arrays, [nq] rows of `width`, to slice i of the
-// staging memory on the merge device, one peer copy per array on the part's stream (the part's device is current)
+// A part away from the merge device: its (pid, dist, count[, rung][, counters][, groups]) arrays, [nq] rows of `width`, to slice i of
+// the staging memory on the merge device, one peer copy per array on the part's stream (the part's device is current)
 static idist_status partitioned_send(idist_partitioned* p, size_t i, uint32_t nq, uint32_t width, const uint32_t* pid, const void* dist,
-                                     const uint32_t* cnt, const uint32_t* rung, const uint32_t* ctr) {
+                                     const uint32_t* cnt, const uint32_t* rung, const uint32_t* ctr, const uint32_t* grp = nullptr) {
     const int32_t dev = part_device(p, i), to = p->merge_device;
     hipStream_t stream = p->parts[i].ctx->stream;
     const size_t row = (size_t)nq * width;
@@ -2993,6 +2995,7 @@ static idist_status partitioned_send(idist_partitioned* p, size_t i, uint32_t nq
     HIPCHK(hipMemcpyPeerAsync(p->s_cnt + i * nq, to, cnt, dev, (size_t)nq * 4, stream));
     if (rung) HIPCHK(hipMemcpyPeerAsync(p->s_rung + i * nq, to, rung, dev, (size_t)nq * 4, stream));
     if (ctr) HIPCHK(hipMemcpyPeerAsync(p->s_ctr + i * nq * 3, to, ctr, dev, (size_t)nq * 12, stream));
+    if (grp) HIPCHK(hipMemcpyPeerAsync(p->s_grp + i * row, to, grp, dev, row * 4, stream));
     return IDIST_OK;
 }
 
@@ -4594,6 +4597,159 @@ idist_status idist_partitioned_search_batch_match(idist_partitioned* p, const id
     MatchConds g;
     match_group(conds, conds->n_cond, nq, &g);
     return partitioned_allowed_sets_call(p, ef, queries, nq, g.source(attr), k, max_rungs, out_pid, out_dist, out_count, out_rung, out_counters);
+}
+
+// ---- grouped search over the parts: the parts' collapsed lists, merged and collapsed again ----
+// grouped_merge_kernel on `stream`: one wave per query, the grid striding over the rest
+static idist_status launch_grouped_merge(GroupedMergeArgs a, int cus, hipStream_t stream) {
+    a.tab_log2 = grouped_tab_log2(a.k);
+    const uint32_t grid = std::min<uint32_t>(a.nq, (uint32_t)std::max(cus, 1) * 32u);
+    IDIST_LAUNCH(grouped_merge_kernel, grid, 64, ((size_t)8u << a.tab_log2) + kGroupedMergeTileBytes, stream, a);
+    HIPCHK(hipGetLastError());
+    return IDIST_OK;
+}
+
+idist_status idist_grouped_merge_device(const void* d_pid, const void* d_dist, const void* d_group, const void* d_count,
+                                        const void* d_counters, uint32_t n_lists, uint32_t nq, uint32_t width, const uint32_t* base,
+                                        uint32_t k, void* d_out_pid, void* d_out_dist, void* d_out_group, void* d_out_count,
+                                        void* d_out_counters, int32_t device, void* hip_stream) {
+    const uint32_t max_w = IDIST_MAX_EF;
+    if (n_lists == 0 || n_lists > kMergeMaxLists) return fail(IDIST_ERR_INVALID_ARG, "n_lists %u out of [1,%u]", n_lists, kMergeMaxLists);
+    if (width == 0 || width > max_w || k == 0 || k > max_w) return fail(IDIST_ERR_INVALID_ARG, "width %u / k %u out of [1,%u]", width, k, max_w);
+    if (!base) return fail(IDIST_ERR_INVALID_ARG, "base is null");
+    if (nq == 0) return IDIST_OK;
+    if (!d_pid || !d_dist || !d_group || !d_count || !d_out_pid || !d_out_dist || !d_out_group || !d_out_count || (d_counters && !d_out_counters))
+        return fail(IDIST_ERR_INVALID_ARG, "null device pointer");
+    CHK(check_device(device));
+    HIPCHK(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    GroupedMergeArgs a{};
+    a.pid = (const uint32_t*)d_pid; a.dist = (const uint32_t*)d_dist; a.group = (const uint32_t*)d_group; a.count = (const uint32_t*)d_count;
+    a.counters = (const uint32_t*)d_counters;
+    a.n_lists = n_lists; a.nq = nq; a.width = width; a.k = k;
+    a.out_pid = (uint32_t*)d_out_pid; a.out_dist = (uint32_t*)d_out_dist; a.out_group = (uint32_t*)d_out_group;
+    a.out_count = (uint32_t*)d_out_count; a.out_counters = d_counters ? (uint32_t*)d_out_counters : nullptr;
+    for (uint32_t l = 0; l < n_lists; l++) a.base[l] = base[l];
+    return launch_grouped_merge(a, launch_cus(prop.multiProcessorCount), (hipStream_t)hip_stream);
+}
+
+// The grouped search over the parts behind its argument checks.  nq > 0, N > 0, ef > 0.  conds null: every point, no bitmap anywhere.
+static idist_status partitioned_grouped_call(idist_partitioned* p, const idist_attr* attr, uint32_t group_col, const float* queries, uint32_t nq,
+                                             const idist_attr_conds* conds, uint32_t k, int32_t max_rungs, uint32_t* out_pid, float* out_dist,
+                                             uint32_t* out_group, uint32_t* out_count, uint32_t* out_rung, uint32_t* out_counters) {
+    const size_t P = p->parts.size();
+    const bool counters = out_counters != nullptr;
+    const size_t row = (size_t)nq * k;
+    p->al_slice_ms = 0.0f;
+    HIPCHK(hipSetDevice(p->merge_device));
+    CHK(partitioned_reserve(p, nq, k, k));
+    CHK(p->s_rung.grow(P * nq * 4));
+    CHK(p->s_grp.grow(P * row * 4));
+    CHK(p->o_grp.grow(row * 4));
+    CHK(partitioned_prepare_report(p, queries, nq));
+    // 1. the queries, once per device; 2. the conditions as the match call stages them: the set of every query once per device, every
+    //    part's bitmaps from its own slice of the table — or one set of every point, which needs neither a bitmap nor a count
+    CHK(partitioned_upload_queries(p, queries, nq));
+    MatchConds g;
+    SetsSource src;
+    std::vector<uint32_t> one_set;
+    if (conds) {
+        match_group(conds, conds->n_cond, nq, &g);
+        src = g.source(attr);
+        CHK(partitioned_stage_sets(p, nq, src));
+    } else {
+        one_set.assign(nq, 0u);
+        CHK(for_each_used_device(p, [&](idist_partitioned::Dev& dv) -> idist_status {
+            CHK(dv.d_setof.grow((size_t)nq * 4));
+            HIPCHK(hipMemset(dv.d_setof.p, 0, (size_t)nq * 4));
+            return IDIST_OK;
+        }));
+    }
+    // 3. every non-empty part's grouped search on its own context, over its own slice of the group column: on the merge device
+    //    straight into the part's slice of the staging memory, elsewhere into the context's memory followed by one peer copy per array
+    CHK(partitioned_fan_out(p, [&](size_t i) -> idist_status {
+        idist_partitioned::Part& pt = p->parts[i];
+        idist_search_ctx* ctx = pt.ctx;
+        const idist_partitioned::Dev& dv = p->devs[pt.dev_slot];
+        const int32_t dev = dv.device;
+        const uint32_t n_p = pt.idx->n;
+        HIPCHK(hipSetDevice(dev));
+        AllowedOut o{};
+        uint32_t* d_ogroup = p->s_grp + i * row;
+        if (dev == p->merge_device) {
+            o.pid = p->s_pid + i * row; o.dist = reinterpret_cast<uint32_t*>(p->s_dist + i * row); o.count = p->s_cnt + i * nq;
+            o.rung = p->s_rung + i * nq; o.counters = counters ? p->s_ctr + i * nq * 3 : nullptr;
+        } else {
+            CHK(allowed_out_in_ctx(ctx, nq, k, counters, &o));
+            CHK(ctx->gr_ogroup.grow(row * 4));
+            d_ogroup = ctx->gr_ogroup;
+        }
+        HIPCHK(hipMemsetAsync(d_ogroup, 0, row * 4, ctx->stream));
+        uint32_t first_step = kRungExact;                 // no condition: |A| = n_p is known, the start rule runs on the host
+        if (!conds && n_p > k && make_ladder(pt.idx->cfg.ef_search, max_rungs).n_rungs) first_step = 0u;
+        if (!conds) ctx->at_ms = 0.0f;
+        CHK(grouped_device(pt.idx, ctx, dv.d_q, nq, conds ? ctx->al_bits.p : nullptr, conds ? g.n_sets : 1u, dv.d_setof,
+                           conds ? g.set_of.data() : one_set.data(), attr->parts[i].v.p + (size_t)group_col * n_p, k, max_rungs, o, d_ogroup,
+                           conds ? nullptr : &first_step));
+        if (dev != p->merge_device) CHK(partitioned_send(p, i, nq, k, o.pid, o.dist, o.count, o.rung, counters ? o.counters : nullptr, d_ogroup));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        CHK(attr_time_resolve(ctx));
+        return ladder_times_resolve(ctx);
+    }));
+    if (conds) partitioned_attr_times(p, src);
+    // 4. the union: empty parts hand in lists of length 0; the grouped merge between the two events; the report on the [nq][k] result
+    HIPCHK(hipSetDevice(p->merge_device));
+    CHK(partitioned_zero_empty_parts(p, nq, counters));
+    std::vector<uint32_t> rungs;
+    if (out_rung) {
+        rungs.resize(P * nq);
+        HIPCHK(hipMemcpyAsync(rungs.data(), p->s_rung, P * nq * 4, hipMemcpyDeviceToHost, p->stream));
+    }
+    GroupedMergeArgs a{};
+    a.pid = p->s_pid; a.dist = (const uint32_t*)p->s_dist.p; a.group = p->s_grp; a.count = p->s_cnt; a.counters = counters ? p->s_ctr.p : nullptr;
+    a.n_lists = (uint32_t)P; a.nq = nq; a.width = k; a.k = k;
+    a.out_pid = p->o_pid; a.out_dist = (uint32_t*)p->o_dist.p; a.out_group = p->o_grp; a.out_count = p->o_cnt;
+    a.out_counters = counters ? p->o_ctr.p : nullptr;
+    for (uint32_t l = 0; l < a.n_lists; l++) a.base[l] = p->base[l];
+    HIPCHK(hipEventRecord(p->ev0, p->stream));
+    CHK(launch_grouped_merge(a, p->parts[0].idx->n_cu, p->stream));
+    HIPCHK(hipEventRecord(p->ev1, p->stream));
+    p->timed = true;
+    CHK(MetricPasses(p).report(p->o_dist, p->d_sq, nq, k, p->stream));
+    HIPCHK(hipMemcpyAsync(out_pid, p->o_pid, row * 4, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipMemcpyAsync(out_dist, p->o_dist, row * 4, hipMemcpyDeviceToHost, p->stream));
+    if (out_group) HIPCHK(hipMemcpyAsync(out_group, p->o_grp, row * 4, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipMemcpyAsync(out_count, p->o_cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, p->stream));
+    if (counters) HIPCHK(hipMemcpyAsync(out_counters, p->o_ctr, (size_t)nq * 12, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    partitioned_transpose_rungs(p, rungs, nq, out_rung);
+    return IDIST_OK;
+}
+
+idist_status idist_partitioned_search_batch_grouped(idist_partitioned* p, const idist_attr* attr, uint32_t group_col, const float* queries,
+                                                    uint32_t nq, const idist_attr_conds* conds, uint32_t k, int32_t max_rungs,
+                                                    uint32_t* out_pid, float* out_dist, uint32_t* out_group, uint32_t* out_count,
+                                                    uint32_t* out_rung, uint32_t* out_counters) {
+    if (!p) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    uint32_t ef = 0;
+    CHK(partitioned_check(p, &ef));
+    CHK(check_partitioned_attr(p, attr));
+    if (group_col >= attr->n_cols)
+        return fail(IDIST_ERR_INVALID_ARG, "group_col %u, but the table has %u column%s", group_col, attr->n_cols, attr->n_cols == 1 ? "" : "s");
+    CHK(check_ladder_args(max_rungs, k, ef));
+    if (conds) CHK(check_match_args(conds, nq, attr->n_cols));
+    if (nq == 0) return IDIST_OK;
+    if (!queries || !out_pid || !out_dist || !out_count) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    const size_t P = p->parts.size();
+    if (out_rung) std::fill(out_rung, out_rung + (size_t)nq * P, (uint32_t)IDIST_RUNG_NONE);   // (empty parts keep it)
+    if (p->base[P] == 0 || ef == 0) {                                        // nothing to find
+        fill_nothing_found(nq, k, out_pid, out_dist, out_count, nullptr, out_counters);
+        if (out_group) memset(out_group, 0, (size_t)nq * k * 4);
+        return IDIST_OK;
+    }
+    return partitioned_grouped_call(p, attr, group_col, queries, nq, conds, k, max_rungs, out_pid, out_dist, out_group, out_count, out_rung,
+                                    out_counters);
 }
 
 idist_status idist_partitioned_last_allowed_slice_ms(idist_partitioned* p, float* ms) {

@@ -20,7 +20,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import INVALID, METRIC_DOT
-from .api import (AllowedResult, Attr, AttrTable, BatchResult, Builder, Hnsw, Item, RangeResult, _as_points, _attr_values, _Everything, _Match,
+from .api import (AllowedResult, Attr, AttrTable, BatchResult, Builder, GroupedResult, Hnsw, Item, RangeResult, _as_points, _attr_values, _Everything, _Match,
                   _range_rows, _RestrictedSearch, _rows, _Sets, _table_columns, _Where, allowed_bitmap)
 from .dist import shard_range
 
@@ -285,6 +285,17 @@ class PartitionedHnsw(_RestrictedSearch):
         """Every point within `radius` that satisfies the query's condition (idist_partitioned_search_batch_range_match): row q is
         exactly what `search_range_allowed_sets` returns for the mask of its condition."""
         return self._range(queries, radius, _Match(table, conds), max_rungs, max_total, counters)
+
+    _GROUPED = "idist_partitioned_search_batch_grouped"
+
+    def search_grouped(self, queries, table: Attr, by, k: int = 10, conds=None, max_rungs: int = -1, counters: bool = False) -> GroupedResult:
+        """The nearest point of each of the k nearest groups over the whole set (idist_partitioned_search_batch_grouped):
+        `Hnsw.search_grouped` on every part with its own slice of the table — a group may have members in several parts — then the
+        parts' lists merged on the GPU by (raw distance bits, global id) and collapsed again, a group's farther copies dropped.
+        `table` is an `attribute_table` (or `attributes`) of THIS index, `by`, `conds`, `k`, `max_rungs` as in `Hnsw.search_grouped`;
+        `max_rungs=0` is the true answer over all parts.  `.pid` holds GLOBAL ids, `.rung` has shape (nq, n_parts), the counters are
+        summed over the parts; one part, or every point its own group, give `Hnsw.search_grouped` / `search_match` bit for bit."""
+        return self._grouped(queries, table, by, conds, k, max_rungs, counters)
 
     def search_one_range(self, point, radius) -> list[Item]:
         """One query: every item within `radius`, nearest first; `Item.pid` is the global id."""
