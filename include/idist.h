@@ -48,6 +48,7 @@ extern "C" {
 #define IDIST_INVALID 0xFFFFFFFFu   /* PointId INVALID, core/types.rs:293 */
 #define IDIST_MAX_LAYERS 64u
 #define IDIST_MAX_EF 4096u
+#define IDIST_KMEANS_CHUNK 1024u    /* rows per partial sum of idist_kmeans_update: part of its definition */
 
 typedef int32_t idist_status;
 enum {
@@ -987,6 +988,48 @@ idist_status idist_normalize_batch(const float* rows, uint32_t n, uint32_t dim, 
  * to reproduce a DOT index with an L2SQ one bit for bit, and to find the common bound of the parts of a partitioned index. */
 idist_status idist_dot_augment_batch(const float* rows, uint32_t n, uint32_t dim, float bound_in, float* out_rows,
                                      float* out_norm2, float* out_bound, int32_t device);
+
+/* ---- k-means for at most 64 clusters (idist_kmeans.hpp): what cuts the points of a partitioned index into parts with centroids ----
+ * Host pointers, blocking, like idist_normalize_batch.  rows: n x dim, row-major.  1 <= k <= 64 (the limit on parts), k <= n,
+ * 1 <= dim <= 65536: IDIST_ERR_INVALID_ARG otherwise.
+ *
+ * ASSIGN.  d~(x, c) = |x|^2 + |c|^2 - 2 x.c, every term an f32 fma chain (the product form of the MFMA filters, on the matrix cores);
+ * out_assign[i] = the j with the smallest d~(x_i, c_j) under a strict `<` scan from j = 0: ties and NaN fall to the lower index.  A
+ * row whose computed |x|^2 is NaN or inf gets i mod k.  out_counts[j] (may be NULL) = the rows assigned to j. */
+idist_status idist_kmeans_assign(const float* rows, uint32_t n, uint32_t dim, const float* centroids /* k x dim */, uint32_t k,
+                                 uint32_t* out_assign /* n */, uint32_t* out_counts /* k or NULL */, int32_t device);
+/* UPDATE.  centroids_inout[j] = s_j / count_j, one f32 division per coordinate, where s_j is the f32 sum of the rows with
+ * assign[i] == j: partial sums over FIXED chunks of IDIST_KMEANS_CHUNK rows, in row order inside a chunk, the chunks added in chunk
+ * order — no float atomics, the same bytes on every launch geometry.  A row whose computed |x|^2 is not finite is a member
+ * (out_counts counts it) but is left out of s_j and of the divisor; a cluster without members, or with such rows only, keeps its
+ * centroid.  assign[i] >= k: IDIST_ERR_INVALID_ARG. */
+idist_status idist_kmeans_update(const float* rows, uint32_t n, uint32_t dim, const uint32_t* assign /* n */, uint32_t k,
+                                 float* centroids_inout /* k x dim */, uint32_t* out_counts /* k */, int32_t device);
+/* Lloyd's iteration with those two steps, bit for bit the loop a caller would write with them:
+ *     centroid j = row floor(j * n / k) (64-bit arithmetic);
+ *     for t in 0 .. iters-1: { assign; if t > 0 and no row changed its cluster: stop; update }      (*out_iters_run = updates made)
+ *     assign once more against the final centroids: out_assign and out_counts belong to out_centroids.
+ * The rows cross the host boundary once.  out_iters_run may be NULL. */
+idist_status idist_kmeans(const float* rows, uint32_t n, uint32_t dim, uint32_t k, uint32_t iters, float* out_centroids /* k x dim */,
+                          uint32_t* out_assign /* n */, uint32_t* out_counts /* k */, uint32_t* out_iters_run, int32_t device);
+
+/* ---- routed search over a partitioned index (idist_route.hpp) ----
+ * One centroid per part, n_parts x kdim floats on the host, IN THE SPACE THE PARTS SEARCH: kdim = dim for L2SQ and L2, the normalised
+ * rows' space for COSINE (idist_normalize_batch), kdim = dim + 1 augmented rows for DOT (idist_dot_augment_batch).  Copied. */
+idist_status idist_partitioned_set_centroids(idist_partitioned* p, const float* centroids);
+/* idist_partitioned_search_batch over the parts of route(q) only.  route(q) = the `nprobe` NON-EMPTY parts with the smallest canonical
+ * L2SQ distance (what idist_distance_batch computes) between the prepared query — what the parts search, after the metric's query
+ * preparation — and the part's centroid, in the reference's `Candidate` order: distance, NaN greatest, then the part's index.
+ * Row q is the merge idist_partitioned_search_batch performs, taken over those parts: count = min(ef_search, the sum of their counts),
+ * the counters theirs summed, report and padding unchanged.  With nprobe = n_parts every output equals that call's bit for bit.
+ * out_route (may be NULL): [nq][nprobe] the parts, nearest centroid first, padded with IDIST_INVALID when fewer non-empty parts exist.
+ * IDIST_ERR_INVALID_ARG when no centroids are set, nprobe is outside 1 .. n_parts, or a pointer is null.  Strict-tie retries stay
+ * inside, as in the unrouted call.  Each routed part searches only its own queries, packed densely, on its own stream. */
+idist_status idist_partitioned_search_batch_routed(idist_partitioned* p, const float* queries, uint32_t nq, uint32_t nprobe,
+                                                   uint32_t* out_pid, float* out_dist, uint32_t* out_count,
+                                                   uint32_t* out_counters /* nq*3 or NULL */, uint32_t* out_route /* nq*nprobe or NULL */);
+/* HIP-event time of the last routed call's route, gather and scatter kernels, summed, milliseconds. */
+idist_status idist_partitioned_last_route_ms(idist_partitioned* p, float* ms);
 
 #ifdef __cplusplus
 }

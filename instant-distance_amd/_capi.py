@@ -20,6 +20,7 @@ M2 = 64
 INVALID = 0xFFFFFFFF
 MAX_LAYERS = 64
 MAX_EF = 4096
+KMEANS_CHUNK = 1024   # rows per partial sum of idist_kmeans_update
 METRIC_L2SQ = 0
 METRIC_L2 = 1
 METRIC_COSINE = 2
@@ -215,6 +216,12 @@ SYMBOLS = {
     "idist_bruteforce": (C.c_int32, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),
     "idist_normalize_batch": (C.c_int32, [_f32p, C.c_uint32, C.c_uint32, _f32p, _f32p, C.c_int32]),
     "idist_dot_augment_batch": (C.c_int32, [_f32p, C.c_uint32, C.c_uint32, C.c_float, _f32p, _f32p, _f32p, C.c_int32]),
+    "idist_kmeans_assign": (C.c_int32, [_f32p, C.c_uint32, C.c_uint32, _f32p, C.c_uint32, _u32p, _u32p, C.c_int32]),
+    "idist_kmeans_update": (C.c_int32, [_f32p, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, _f32p, _u32p, C.c_int32]),
+    "idist_kmeans": (C.c_int32, [_f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _f32p, _u32p, _u32p, _u32p, C.c_int32]),
+    "idist_partitioned_set_centroids": (C.c_int32, [_vp, _f32p]),
+    "idist_partitioned_search_batch_routed": (C.c_int32, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p, _u32p, _u32p, _u32p]),
+    "idist_partitioned_last_route_ms": (C.c_int32, [_vp, C.POINTER(C.c_float)]),
 }
 
 

@@ -359,6 +359,7 @@ class BatchResult:
     distance: np.ndarray  # [nq, ef_search] float32, +inf padded
     count: np.ndarray     # [nq]
     counters: np.ndarray | None  # [nq, 3] {n_dist, n_exp0, n_expU}
+    route: np.ndarray | None = None  # [nq, nprobe] `PartitionedHnsw.search_batch(nprobe=, routes=True)`: the parts searched, INVALID padded
 
 
 @dataclass
@@ -683,6 +684,50 @@ def augment_dot(points, bound: float = 0.0, device: int = 0, return_norm2: bool 
                                       C.byref(S), int(device)))
     S = np.float32(S.value)
     return (out, S, s) if return_norm2 else (out, S)
+
+
+def kmeans_assign(points, centroids, device: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """(assign [n] uint32, counts [k] uint32): row i goes to the centroid with the smallest product-form squared distance
+    |x|^2 + |c|^2 - 2 x.c in f32, ties to the lower index (idist_kmeans_assign, on the matrix cores); a row whose |x|^2 is not finite
+    gets i mod k.  1 <= k <= 64, k <= n."""
+    pts, cen = _as_points(points), _as_points(centroids)
+    if pts.shape[1] != cen.shape[1]:
+        raise TypeError(f"centroid dim {cen.shape[1]} != point dim {pts.shape[1]}")
+    assign, counts = np.zeros(pts.shape[0], dtype=np.uint32), np.zeros(cen.shape[0], dtype=np.uint32)
+    L = _lib()
+    L.check(L.idist_kmeans_assign(_capi.f32p(pts), pts.shape[0], pts.shape[1], _capi.f32p(cen), cen.shape[0], _capi.u32p(assign),
+                                  _capi.u32p(counts), int(device)))
+    return assign, counts
+
+
+def kmeans_update(points, assign, centroids, device: int = 0) -> tuple[np.ndarray, np.ndarray]:
+    """(centroids [k, dim], counts [k]): every centroid the f32 mean of its member rows, summed in a fixed order — chunks of
+    `_capi.KMEANS_CHUNK` rows in row order, the chunks in chunk order (idist_kmeans_update); a cluster without members keeps the
+    centroid given.  Rows with a non-finite |x|^2 are counted but not summed."""
+    pts, cen = _as_points(points), _as_points(centroids).copy()
+    a = np.ascontiguousarray(assign, dtype=np.uint32)
+    if a.shape != (pts.shape[0],) or pts.shape[1] != cen.shape[1]:
+        raise TypeError("assign must hold one cluster per row, the centroids the rows' dim")
+    counts = np.zeros(cen.shape[0], dtype=np.uint32)
+    L = _lib()
+    L.check(L.idist_kmeans_update(_capi.f32p(pts), pts.shape[0], pts.shape[1], _capi.u32p(a), cen.shape[0], _capi.f32p(cen),
+                                  _capi.u32p(counts), int(device)))
+    return cen, counts
+
+
+def kmeans(points, k: int, iters: int = 10, device: int = 0, return_iters: bool = False):
+    """Lloyd's k-means on the GPU (idist_kmeans): centroid j starts as row floor(j * n / k); at most `iters` rounds of
+    {kmeans_assign; stop if nothing changed; kmeans_update}, then one more assign.  Returns (centroids [k, dim], assign [n],
+    counts [k]) — assign and counts belong to the centroids returned — and with `return_iters` the number of updates made."""
+    pts = _as_points(points)
+    k = int(k)
+    cen = np.zeros((max(k, 0), pts.shape[1]), dtype=np.float32)
+    assign, counts = np.zeros(pts.shape[0], dtype=np.uint32), np.zeros(max(k, 0), dtype=np.uint32)
+    run = C.c_uint32(0)
+    L = _lib()
+    L.check(L.idist_kmeans(_capi.f32p(pts), pts.shape[0], pts.shape[1], k, int(iters), _capi.f32p(cen), _capi.u32p(assign), _capi.u32p(counts),
+                           C.byref(run), int(device)))
+    return (cen, assign, counts, int(run.value)) if return_iters else (cen, assign, counts)
 
 
 def _as_points(points) -> np.ndarray:

@@ -18,6 +18,8 @@
 #include "idist_grouped.hpp"
 #include "idist_grouped_merge.hpp"
 #include "idist_basis.hpp"
+#include "idist_kmeans.hpp"
+#include "idist_route.hpp"
 
 #ifndef IDIST_EMU
 #include <hip/hip_runtime.h>
@@ -477,6 +479,12 @@ struct idist_partitioned {
         // the part's stream; grown with the merge device current); a part on the merge device is read where its context holds them
         DevBuf<uint64_t> m_keys, m_off;
         DevBuf<uint32_t> m_cnt, m_ctr;
+        // routed search, on the part's device: its queries' indices (a part away from the merge device) and their rows packed densely;
+        // the events around its gather kernel (made at the first routed call)
+        DevBuf<uint32_t> q_list;
+        DevBuf<float> q_dense;
+        hipEvent_t gev0 = nullptr, gev1 = nullptr;
+        bool gathered = false;
     };
     struct Dev {
         int32_t device = 0;
@@ -496,6 +504,13 @@ struct idist_partitioned {
     DevBuf<float> s_dist, o_dist;
     DevBuf<uint32_t> s_rung;                 // restricted search: the parts' rungs [P][nq]
     DevBuf<uint32_t> s_grp, o_grp;           // grouped search: the groups of the parts' lists [P][nq][k] and of the result [nq][k]
+    // routed search (idist_route.hpp), on the merge device: one centroid per part in the space the parts search; the route [nq][nprobe],
+    // the (part, query) flags and the parts' query lists [P][nq] with their lengths [P]; the parts' dense results [sum m_p][ef]
+    DevBuf<float> d_cent, g_dist;
+    bool has_cent = false;
+    DevBuf<uint32_t> r_route, r_sel, r_list, r_lens, g_pid, g_cnt, g_ctr;
+    hipEvent_t rev[4] = {nullptr, nullptr, nullptr, nullptr};   // around the route kernels and around the scatter kernel
+    float route_ms = -1.0f;                  // the last routed call's route, gather and scatter kernels (-1: none has run)
     float al_slice_ms = 0.0f;                // ... and the host time its last call spent on the bitmaps: upload + slice, every part
                                              // (an attribute call: the parts' bitmap kernels, HIP events, summed)
     // range search, on the merge device: the merged counts, lims and the chunk sums of their prefix sum; the merged result, which no
@@ -2857,7 +2872,12 @@ idist_status idist_partitioned_new(const idist_index* const* parts, uint32_t n_p
 void idist_partitioned_free(idist_partitioned* p) {
     if (!p) return;
     // (the parts are borrowed and may already be gone: nothing of them is touched here)
-    for (auto& pt : p->parts) idist_search_ctx_free(pt.ctx);
+    for (auto& pt : p->parts) {
+        idist_search_ctx_free(pt.ctx);
+        if (pt.gev0) hipEventDestroy(pt.gev0);
+        if (pt.gev1) hipEventDestroy(pt.gev1);
+    }
+    for (hipEvent_t e : p->rev) if (e) hipEventDestroy(e);
     if (p->ev0) hipEventDestroy(p->ev0);
     if (p->ev1) hipEventDestroy(p->ev1);
     if (p->stream) hipStreamDestroy(p->stream);
@@ -2967,20 +2987,21 @@ template <typename Fn> idist_status for_each_used_device(idist_partitioned* p, F
 // The batch's queries, once per distinct device that has something to search, as the parts' launches read them (prepared = true):
 // Dev::d_q holds the [nq][kdim] rows in front (a metric whose prepare cannot run in place: followed by the queries as uploaded).
 // Leaves another device current.  with_sq: a metric with a report term also leaves s(q) in Dev::d_sq (the range search's limits).
-static idist_status partitioned_upload_queries(idist_partitioned* p, const float* queries, uint32_t nq, bool with_sq = false) {
+static idist_status partitioned_upload_to(idist_partitioned* p, idist_partitioned::Dev& dv, const float* queries, uint32_t nq, bool with_sq) {
     const MetricPasses metric(p);
     const size_t qb = (size_t)nq * p->dim * 4, qa = metric.in_place() ? 0 : metric.qk_floats(nq) * 4;
-    return for_each_used_device(p, [&](idist_partitioned::Dev& dv) -> idist_status {
-        CHK(dv.d_q.grow(qa + qb));
-        HIPCHK(hipMemcpy(dv.d_q + qa / 4, queries, qb, hipMemcpyHostToDevice));
-        const bool sq = with_sq && metric.sq_floats(nq) != 0;
-        if (sq) CHK(dv.d_sq.grow(metric.sq_floats(nq) * 4));
-        if (metric.any()) {                              // prepared once per device; the parts' launches take them as they are
-            CHK(metric.prepare(dv.d_q + qa / 4, dv.d_q, sq ? dv.d_sq.p : nullptr, nq, nullptr, nullptr));
-            HIPCHK(hipStreamSynchronize(nullptr));
-        }
-        return IDIST_OK;
-    });
+    CHK(dv.d_q.grow(qa + qb));
+    HIPCHK(hipMemcpy(dv.d_q + qa / 4, queries, qb, hipMemcpyHostToDevice));
+    const bool sq = with_sq && metric.sq_floats(nq) != 0;
+    if (sq) CHK(dv.d_sq.grow(metric.sq_floats(nq) * 4));
+    if (metric.any()) {                                  // prepared once per device; the parts' launches take them as they are
+        CHK(metric.prepare(dv.d_q + qa / 4, dv.d_q, sq ? dv.d_sq.p : nullptr, nq, nullptr, nullptr));
+        HIPCHK(hipStreamSynchronize(nullptr));
+    }
+    return IDIST_OK;
+}
+static idist_status partitioned_upload_queries(idist_partitioned* p, const float* queries, uint32_t nq, bool with_sq = false) {
+    return for_each_used_device(p, [&](idist_partitioned::Dev& dv) -> idist_status { return partitioned_upload_to(p, dv, queries, nq, with_sq); });
 }
 
 // A part away from the merge device: its (pid, dist, count[, rung][, counters][, groups]) arrays, [nq] rows of `width`, to slice i of
@@ -3131,6 +3152,174 @@ idist_status idist_partitioned_last_merge_ms(idist_partitioned* p, float* ms) {
     if (!p->timed) return fail(IDIST_ERR_INVALID_ARG, "no merge kernel has run through this object yet");
     HIPCHK(hipEventSynchronize(p->ev1));
     HIPCHK(hipEventElapsedTime(ms, p->ev0, p->ev1));
+    return IDIST_OK;
+}
+
+// ---- routed search: every query to the nprobe parts with the nearest centroids (idist_route.hpp) ----
+idist_status idist_partitioned_set_centroids(idist_partitioned* p, const float* centroids) {
+    if (!p || !centroids) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    CHK(partitioned_check(p, nullptr));
+    const size_t bytes = p->parts.size() * (size_t)p->parts[0].idx->kdim * 4;
+    HIPCHK(hipSetDevice(p->merge_device));
+    CHK(p->d_cent.grow(bytes));
+    HIPCHK(hipMemcpy(p->d_cent, centroids, bytes, hipMemcpyHostToDevice));
+    p->has_cent = true;
+    return IDIST_OK;
+}
+
+idist_status idist_partitioned_search_batch_routed(idist_partitioned* p, const float* queries, uint32_t nq, uint32_t nprobe,
+                                                   uint32_t* out_pid, float* out_dist, uint32_t* out_count, uint32_t* out_counters,
+                                                   uint32_t* out_route) {
+    if (!p) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    uint32_t ef = 0;
+    CHK(partitioned_check(p, &ef));
+    const size_t P = p->parts.size();
+    if (!p->has_cent) return fail(IDIST_ERR_INVALID_ARG, "no centroids are set: call idist_partitioned_set_centroids first");
+    if (nprobe == 0 || nprobe > P) return fail(IDIST_ERR_INVALID_ARG, "nprobe %u out of [1,%zu]", nprobe, P);
+    if (nq == 0) return IDIST_OK;
+    if (!queries || !out_count) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    if (p->base[P] == 0 || ef == 0) {                    // core/lib.rs:359-361
+        memset(out_count, 0, (size_t)nq * 4);
+        if (out_counters) memset(out_counters, 0, (size_t)nq * 12);
+        if (out_route) memset(out_route, 0xFF, (size_t)nq * nprobe * 4);
+        return IDIST_OK;
+    }
+    if (!out_pid || !out_dist) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    const bool counters = out_counters != nullptr;
+    const uint32_t kdim = p->parts[0].idx->kdim;
+    const int cus = p->parts[0].idx->n_cu;
+    HIPCHK(hipSetDevice(p->merge_device));
+    for (hipEvent_t& e : p->rev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    CHK(partitioned_reserve(p, nq, ef, ef));
+    CHK(partitioned_prepare_report(p, queries, nq));
+    // 1. the queries, once per distinct device that has something to search — and on the merge device, where the route is made
+    CHK(partitioned_upload_queries(p, queries, nq));
+    idist_partitioned::Dev& mdv = p->devs[p->parts[0].dev_slot];
+    bool merge_used = false;
+    for (auto& pt : p->parts) merge_used |= pt.ctx && pt.dev_slot == p->parts[0].dev_slot;
+    HIPCHK(hipSetDevice(p->merge_device));
+    if (!merge_used) CHK(partitioned_upload_to(p, mdv, queries, nq, false));
+    // 2. the route, the parts' query lists and their lengths; the staging counts of every (part, query) pair cleared
+    CHK(p->r_route.grow((size_t)nq * nprobe * 4));
+    CHK(p->r_sel.grow(P * nq * 4));
+    CHK(p->r_list.grow(P * nq * 4));
+    CHK(p->r_lens.grow(P * 4));
+    RouteArgs ra{};
+    ra.Q = mdv.d_q; ra.cent = p->d_cent; ra.nq = nq; ra.kdim = kdim; ra.P = (uint32_t)P; ra.nprobe = nprobe;
+    for (size_t i = 0; i < P; i++) if (p->parts[i].ctx) ra.nonempty |= 1ull << i;
+    ra.route = p->r_route; ra.sel = p->r_sel; ra.s_cnt = p->s_cnt; ra.s_ctr = counters ? p->s_ctr.p : nullptr;
+    HIPCHK(hipEventRecord(p->rev[0], p->stream));
+    IDIST_LAUNCH(route_kernel, std::min<uint32_t>(nq, (uint32_t)std::max(cus, 1) * 32u), 64, (size_t)((kdim + 3u) & ~3u) * 4 + 256, p->stream, ra);
+    IDIST_LAUNCH(route_lists_kernel, std::min<uint32_t>((uint32_t)P, (uint32_t)std::max(cus, 1) * 32u), 64, 0, p->stream,
+                 (const uint32_t*)p->r_sel.p, (uint32_t)P, nq, p->r_list.p, p->r_lens.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(p->rev[1], p->stream));
+    std::vector<uint32_t> lens(P);
+    HIPCHK(hipMemcpyAsync(lens.data(), p->r_lens, P * 4, hipMemcpyDeviceToHost, p->stream));
+    if (out_route) HIPCHK(hipMemcpyAsync(out_route, p->r_route, (size_t)nq * nprobe * 4, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    ScatterArgs sa{};
+    for (size_t i = 0; i < P; i++) sa.off[i + 1] = sa.off[i] + lens[i];
+    const size_t total = sa.off[P];
+    CHK(p->g_pid.grow(total * ef * 4));
+    CHK(p->g_dist.grow(total * ef * 4));
+    CHK(p->g_cnt.grow(total * 4));
+    CHK(p->g_ctr.grow(total * 12));
+    // 3. every routed part on its own stream: its queries packed densely on its device, searched, the dense rows on the merge device
+    auto search_part = [&](size_t i) -> idist_status {
+        idist_partitioned::Part& pt = p->parts[i];
+        const int32_t dev = p->devs[pt.dev_slot].device;
+        const uint32_t m = lens[i];
+        const size_t o = sa.off[i], row = (size_t)m * ef;
+        HIPCHK(hipSetDevice(dev));
+        if (dev == p->merge_device)
+            return search_batch_device_impl(pt.idx, pt.ctx, pt.q_dense, m, p->g_pid + o * ef, p->g_dist + o * ef, p->g_cnt + o,
+                                            counters ? p->g_ctr + o * 3 : nullptr, pt.ctx->stream, true);
+        CHK(pt.r_pid.grow(row * 4));
+        CHK(pt.r_dist.grow(row * 4));
+        CHK(pt.r_cnt.grow((size_t)m * 4));
+        CHK(pt.r_ctr.grow((size_t)m * 12));
+        CHK(search_batch_device_impl(pt.idx, pt.ctx, pt.q_dense, m, pt.r_pid, pt.r_dist, pt.r_cnt, counters ? pt.r_ctr.p : nullptr, pt.ctx->stream, true));
+        const int32_t to = p->merge_device;
+        HIPCHK(hipMemcpyPeerAsync(p->g_pid + o * ef, to, pt.r_pid, dev, row * 4, pt.ctx->stream));
+        HIPCHK(hipMemcpyPeerAsync(p->g_dist + o * ef, to, pt.r_dist, dev, row * 4, pt.ctx->stream));
+        HIPCHK(hipMemcpyPeerAsync(p->g_cnt + o, to, pt.r_cnt, dev, (size_t)m * 4, pt.ctx->stream));
+        if (counters) HIPCHK(hipMemcpyPeerAsync(p->g_ctr + o * 3, to, pt.r_ctr, dev, (size_t)m * 12, pt.ctx->stream));
+        return IDIST_OK;
+    };
+    for (size_t i = 0; i < P; i++) {
+        idist_partitioned::Part& pt = p->parts[i];
+        pt.gathered = false;
+        if (!pt.ctx || !lens[i]) continue;
+        const int32_t dev = p->devs[pt.dev_slot].device;
+        const uint32_t m = lens[i];
+        HIPCHK(hipSetDevice(dev));
+        if (!pt.gev0) { HIPCHK(hipEventCreate(&pt.gev0)); HIPCHK(hipEventCreate(&pt.gev1)); }
+        const uint32_t* d_list = p->r_list + i * nq;
+        if (dev != p->merge_device) {
+            CHK(pt.q_list.grow((size_t)m * 4));
+            HIPCHK(hipMemcpyPeerAsync(pt.q_list, dev, d_list, p->merge_device, (size_t)m * 4, pt.ctx->stream));
+            d_list = pt.q_list;
+        }
+        CHK(pt.q_dense.grow((size_t)m * kdim * 4));
+        HIPCHK(hipEventRecord(pt.gev0, pt.ctx->stream));
+        const float* d_all = p->devs[pt.dev_slot].d_q;
+        float* d_dense = pt.q_dense;
+        hipStream_t part_stream = pt.ctx->stream;
+        IDIST_LAUNCH(route_gather_kernel, std::min<uint32_t>(m, (uint32_t)std::max(cus, 1) * 32u), 64, 0, part_stream, d_all, d_list, m, kdim, d_dense);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(pt.gev1, pt.ctx->stream));
+        pt.gathered = true;
+    }
+    for (size_t i = 0; i < P; i++)                       // (every gather is enqueued before the first walk: parts that share a device
+        if (p->parts[i].gathered) CHK(search_part(i));   //  would otherwise time their gather behind another part's walk)
+    // 4. wait for every routed part; strict ties: searched again while the escalation makes progress (idist_partitioned_search_batch)
+    for (size_t i = 0; i < P; i++) {
+        idist_partitioned::Part& pt = p->parts[i];
+        if (!pt.gathered) continue;
+        for (;;) {
+            HIPCHK(hipSetDevice(p->devs[pt.dev_slot].device));
+            HIPCHK(hipStreamSynchronize(pt.ctx->stream));
+            idist_status s;
+            if (status_asks_retry(pt.idx, pt.ctx, &s)) {
+                CHK(search_part(i));
+                continue;
+            }
+            if (s == IDIST_OK) break;
+            return part_failed(p, i, s, g_err);
+        }
+    }
+    // 5. the dense rows to their queries' rows of the staging memory, then the union as ever
+    HIPCHK(hipSetDevice(p->merge_device));
+    sa.g_pid = p->g_pid; sa.g_dist = (const uint32_t*)p->g_dist.p; sa.g_cnt = p->g_cnt; sa.g_ctr = counters ? p->g_ctr.p : nullptr;
+    sa.list = p->r_list; sa.P = (uint32_t)P; sa.nq = nq; sa.ef = ef;
+    sa.s_pid = p->s_pid; sa.s_dist = (uint32_t*)p->s_dist.p; sa.s_cnt = p->s_cnt; sa.s_ctr = p->s_ctr;
+    HIPCHK(hipEventRecord(p->rev[2], p->stream));
+    if (total) {
+        IDIST_LAUNCH(route_scatter_kernel, (uint32_t)std::min<size_t>(total, (size_t)std::max(cus, 1) * 32u), 64, 0, p->stream, sa);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(p->rev[3], p->stream));
+    CHK(partitioned_merge(p, nq, ef, ef, counters, out_pid, out_dist, out_count, out_counters));
+    float ms = 0.0f, sum = 0.0f;
+    HIPCHK(hipEventElapsedTime(&ms, p->rev[0], p->rev[1]));
+    sum += ms;
+    HIPCHK(hipEventElapsedTime(&ms, p->rev[2], p->rev[3]));
+    sum += ms;
+    for (auto& pt : p->parts) {
+        if (!pt.gathered) continue;
+        HIPCHK(hipEventElapsedTime(&ms, pt.gev0, pt.gev1));
+        sum += ms;
+    }
+    p->route_ms = sum;
+    return IDIST_OK;
+}
+
+idist_status idist_partitioned_last_route_ms(idist_partitioned* p, float* ms) {
+    if (!p || !ms) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    if (p->route_ms < 0.0f) return fail(IDIST_ERR_INVALID_ARG, "no routed search has run through this object yet");
+    *ms = p->route_ms;
     return IDIST_OK;
 }
 
@@ -5534,6 +5723,137 @@ idist_status idist_dot_augment_batch(const float* rows, uint32_t n, uint32_t dim
     if (out_rows) HIPCHK(hipMemcpy(out_rows, d_a, ab, hipMemcpyDeviceToHost));
     if (out_norm2) HIPCHK(hipMemcpy(out_norm2, d_s, (size_t)n * 4, hipMemcpyDeviceToHost));
     if (out_bound) *out_bound = S;
+    return IDIST_OK;
+}
+
+// ---- k-means (idist_kmeans.hpp): the device-pointer steps, enqueued on `stream`, and the host-pointer entry points over them ----
+// d_cn: 64 floats of scratch.  d_prev / d_changed, d_counts, d_bad: each may be null.
+static idist_status kmeans_assign_device(const float* d_x, uint32_t n, uint32_t dim, const float* d_c, uint32_t k, float* d_cn, uint32_t* d_assign,
+                                         const uint32_t* d_prev, uint32_t* d_changed, uint32_t* d_counts, uint32_t* d_bad, int cus, hipStream_t stream) {
+    IDIST_LAUNCH(kmeans_prep_kernel, 1, 64, 0, stream, d_c, k, dim, d_cn, d_counts, d_changed);
+    KmAssignArgs a{};
+    a.X = d_x; a.C = d_c; a.cn = d_cn; a.n = n; a.dim = dim; a.k = k;
+    a.vec4 = (dim % 4u == 0u && ((uintptr_t)d_x % 16u) == 0 && ((uintptr_t)d_c % 16u) == 0) ? 1u : 0u;
+    a.assign = d_assign; a.prev = d_prev; a.changed = d_changed; a.counts = d_counts; a.bad = d_bad;
+    const uint32_t tiles = (n + (uint32_t)kKmRows - 1u) / (uint32_t)kKmRows;
+    IDIST_LAUNCH(kmeans_assign_kernel, std::min<uint32_t>(tiles, (uint32_t)std::max(cus, 1) * 8u), 256, km_assign_smem(dim), stream, a);
+    HIPCHK(hipGetLastError());
+    return IDIST_OK;
+}
+static size_t kmeans_chunks(uint32_t n) { return ((size_t)n + IDIST_KMEANS_CHUNK - 1) / IDIST_KMEANS_CHUNK; }
+// d_part: kmeans_chunks(n) * k * dim floats, d_cpart: kmeans_chunks(n) * k * 2 u32 of scratch
+static idist_status kmeans_update_device(const float* d_x, uint32_t n, uint32_t dim, const uint32_t* d_assign, const uint32_t* d_bad, uint32_t k,
+                                         float* d_c, uint32_t* d_counts, float* d_part, uint32_t* d_cpart, int cus, hipStream_t stream) {
+    KmUpdateArgs a{};
+    a.X = d_x; a.assign = d_assign; a.bad = d_bad; a.n = n; a.dim = dim; a.k = k; a.chunk = IDIST_KMEANS_CHUNK;
+    a.part = d_part; a.cpart = d_cpart;
+    const size_t nch = kmeans_chunks(n), items = nch * ((dim + 63u) / 64u);
+    IDIST_LAUNCH(kmeans_partial_kernel, (uint32_t)std::min<size_t>(items, (size_t)std::max(cus, 1) * 32u), 64, (size_t)k * 64 * 4 + (size_t)k * 8, stream, a);
+    const size_t cells = (size_t)k * dim;
+    IDIST_LAUNCH(kmeans_reduce_kernel, (uint32_t)std::min<size_t>((cells + 255) / 256, (size_t)std::max(cus, 1) * 8u), 256, 0, stream,
+                 (const float*)d_part, (const uint32_t*)d_cpart, (uint32_t)nch, k, dim, d_c, d_counts);
+    HIPCHK(hipGetLastError());
+    return IDIST_OK;
+}
+static idist_status kmeans_check(uint32_t n, uint32_t dim, uint32_t k, int32_t device, int* cus) {
+    if (dim == 0 || dim > 65536) return fail(IDIST_ERR_INVALID_ARG, "dim %u out of [1,65536]", dim);
+    if (k == 0 || k > (uint32_t)kKmCols) return fail(IDIST_ERR_INVALID_ARG, "k %u out of [1,%d]", k, kKmCols);
+    if (k > n) return fail(IDIST_ERR_INVALID_ARG, "k %u exceeds the %u rows", k, n);
+    CHK(check_device(device));
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    *cus = launch_cus(prop.multiProcessorCount);
+    return IDIST_OK;
+}
+
+idist_status idist_kmeans_assign(const float* rows, uint32_t n, uint32_t dim, const float* centroids, uint32_t k, uint32_t* out_assign,
+                                 uint32_t* out_counts, int32_t device) {
+    if (!rows || !centroids || !out_assign) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    int cus = 1;
+    CHK(kmeans_check(n, dim, k, device, &cus));
+    Scratch mem;
+    float *d_x = nullptr, *d_c = nullptr, *d_cn = nullptr;
+    uint32_t *d_a = nullptr, *d_cnt = nullptr;
+    CHK(mem.alloc(&d_x, (size_t)n * dim));
+    CHK(mem.alloc(&d_c, (size_t)k * dim));
+    CHK(mem.alloc(&d_cn, 64));
+    CHK(mem.alloc(&d_a, n));
+    CHK(mem.alloc(&d_cnt, 64));
+    HIPCHK(hipMemcpy(d_x, rows, (size_t)n * dim * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_c, centroids, (size_t)k * dim * 4, hipMemcpyHostToDevice));
+    CHK(kmeans_assign_device(d_x, n, dim, d_c, k, d_cn, d_a, nullptr, nullptr, out_counts ? d_cnt : nullptr, nullptr, cus, nullptr));
+    HIPCHK(hipMemcpy(out_assign, d_a, (size_t)n * 4, hipMemcpyDeviceToHost));
+    if (out_counts) HIPCHK(hipMemcpy(out_counts, d_cnt, (size_t)k * 4, hipMemcpyDeviceToHost));
+    return IDIST_OK;
+}
+
+idist_status idist_kmeans_update(const float* rows, uint32_t n, uint32_t dim, const uint32_t* assign, uint32_t k, float* centroids_inout,
+                                 uint32_t* out_counts, int32_t device) {
+    if (!rows || !assign || !centroids_inout || !out_counts) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    int cus = 1;
+    CHK(kmeans_check(n, dim, k, device, &cus));
+    for (uint32_t i = 0; i < n; i++)
+        if (assign[i] >= k) return fail(IDIST_ERR_INVALID_ARG, "assign[%u] = %u is not a cluster below k = %u", i, assign[i], k);
+    Scratch mem;
+    float *d_x = nullptr, *d_c = nullptr, *d_part = nullptr;
+    uint32_t *d_a = nullptr, *d_bad = nullptr, *d_cnt = nullptr, *d_cpart = nullptr;
+    const size_t nch = kmeans_chunks(n);
+    CHK(mem.alloc(&d_x, (size_t)n * dim));
+    CHK(mem.alloc(&d_c, (size_t)k * dim));
+    CHK(mem.alloc(&d_a, n));
+    CHK(mem.alloc(&d_bad, n));
+    CHK(mem.alloc(&d_cnt, 64));
+    CHK(mem.alloc(&d_part, nch * k * dim));
+    CHK(mem.alloc(&d_cpart, nch * k * 2));
+    HIPCHK(hipMemcpy(d_x, rows, (size_t)n * dim * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_c, centroids_inout, (size_t)k * dim * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_a, assign, (size_t)n * 4, hipMemcpyHostToDevice));
+    IDIST_LAUNCH(kmeans_rowflags_kernel, std::min<uint32_t>((n + 31u) / 32u, (uint32_t)std::max(cus, 1) * 32u), 64, 0, (hipStream_t) nullptr,
+                 (const float*)d_x, n, dim, d_bad);
+    CHK(kmeans_update_device(d_x, n, dim, d_a, d_bad, k, d_c, d_cnt, d_part, d_cpart, cus, nullptr));
+    HIPCHK(hipMemcpy(centroids_inout, d_c, (size_t)k * dim * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_counts, d_cnt, (size_t)k * 4, hipMemcpyDeviceToHost));
+    return IDIST_OK;
+}
+
+idist_status idist_kmeans(const float* rows, uint32_t n, uint32_t dim, uint32_t k, uint32_t iters, float* out_centroids, uint32_t* out_assign,
+                          uint32_t* out_counts, uint32_t* out_iters_run, int32_t device) {
+    if (!rows || !out_centroids || !out_assign || !out_counts) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    int cus = 1;
+    CHK(kmeans_check(n, dim, k, device, &cus));
+    Scratch mem;
+    float *d_x = nullptr, *d_c = nullptr, *d_cn = nullptr, *d_part = nullptr;
+    uint32_t *d_a[2] = {nullptr, nullptr}, *d_bad = nullptr, *d_cnt = nullptr, *d_cpart = nullptr, *d_chg = nullptr;
+    const size_t nch = kmeans_chunks(n);
+    CHK(mem.alloc(&d_x, (size_t)n * dim));
+    CHK(mem.alloc(&d_c, (size_t)k * dim));
+    CHK(mem.alloc(&d_cn, 64));
+    CHK(mem.alloc(&d_a[0], n));
+    CHK(mem.alloc(&d_a[1], n));
+    CHK(mem.alloc(&d_bad, n));
+    CHK(mem.alloc(&d_cnt, 64));
+    CHK(mem.alloc(&d_chg, 1));
+    CHK(mem.alloc(&d_part, nch * k * dim));
+    CHK(mem.alloc(&d_cpart, nch * k * 2));
+    HIPCHK(hipMemcpy(d_x, rows, (size_t)n * dim * 4, hipMemcpyHostToDevice));
+    for (uint32_t j = 0; j < k; j++)
+        HIPCHK(hipMemcpy(d_c + (size_t)j * dim, d_x + (size_t)((uint64_t)j * n / k) * dim, (size_t)dim * 4, hipMemcpyDeviceToDevice));
+    uint32_t run = 0;
+    int cur = 0;                                             // d_a[cur] takes the next assignment, d_a[cur ^ 1] holds the one before
+    for (uint32_t t = 0; t < iters; t++) {
+        CHK(kmeans_assign_device(d_x, n, dim, d_c, k, d_cn, d_a[cur], t ? d_a[cur ^ 1] : nullptr, d_chg, nullptr, d_bad, cus, nullptr));
+        uint32_t changed = 1;
+        if (t) HIPCHK(hipMemcpy(&changed, d_chg, 4, hipMemcpyDeviceToHost));
+        if (!changed) break;
+        CHK(kmeans_update_device(d_x, n, dim, d_a[cur], d_bad, k, d_c, d_cnt, d_part, d_cpart, cus, nullptr));
+        run++;
+        cur ^= 1;
+    }
+    CHK(kmeans_assign_device(d_x, n, dim, d_c, k, d_cn, d_a[cur], nullptr, nullptr, d_cnt, nullptr, cus, nullptr));
+    HIPCHK(hipMemcpy(out_centroids, d_c, (size_t)k * dim * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_assign, d_a[cur], (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_counts, d_cnt, (size_t)k * 4, hipMemcpyDeviceToHost));
+    if (out_iters_run) *out_iters_run = run;
     return IDIST_OK;
 }
 

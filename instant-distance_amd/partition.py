@@ -19,9 +19,9 @@ from typing import Sequence
 import numpy as np
 
 from . import _capi
-from ._capi import INVALID, METRIC_DOT
+from ._capi import INVALID, METRIC_COSINE, METRIC_DOT
 from .api import (AllowedResult, Attr, AttrTable, BatchResult, Builder, GroupedResult, Hnsw, Item, RangeResult, _as_points, _attr_values, _Everything, _Match,
-                  _range_rows, _RestrictedSearch, _rows, _Sets, _table_columns, _Where, allowed_bitmap)
+                  _range_rows, _RestrictedSearch, _rows, _Sets, _table_columns, _Where, allowed_bitmap, augment_dot, kmeans, normalize)
 from .dist import shard_range
 
 
@@ -36,6 +36,7 @@ class PartitionedHnsw(_RestrictedSearch):
     def __init__(self, handle, hnsws: Sequence[Hnsw]):
         self._h = handle
         self.parts = list(hnsws)      # kept alive for as long as the C handle exists (it borrows them)
+        self.centroids = None         # [n_parts, kdim] once `set_centroids` has run
         info = self.info()
         self._base = np.array(info.base[: info.n_parts + 1], dtype=np.int64)
 
@@ -60,16 +61,23 @@ class PartitionedHnsw(_RestrictedSearch):
         return cls(out, hnsws)
 
     @classmethod
-    def build(cls, points, builder: Builder | None = None, parts: int = 2,
-              devices: Sequence[int] | None = None) -> tuple["PartitionedHnsw", list[int]]:
-        """Cut `points` into `parts` contiguous ranges (dist.shard_range), build an ordinary `Hnsw` of each with `builder`
-        (its seed drives every part's own shuffle) on devices[p % len(devices)] (default: all on the builder's device).
-        Parts on different devices build side by side, one host thread per distinct device; parts that share a device
-        one after the other.  Returns (index, caller's row index -> global id), as `Builder.build_hnsw` does for PointIds."""
+    def build(cls, points, builder: Builder | None = None, parts: int = 2, devices: Sequence[int] | None = None,
+              partition: str = "ranges", kmeans_iters: int = 10) -> tuple["PartitionedHnsw", list[int]]:
+        """Cut `points` into `parts` parts, build an ordinary `Hnsw` of each with `builder` (its seed drives every part's own
+        shuffle) on devices[p % len(devices)] (default: all on the builder's device).  Parts on different devices build side by
+        side, one host thread per distinct device; parts that share a device one after the other.  Returns (index, caller's row
+        index -> global id), as `Builder.build_hnsw` does for PointIds.
+
+        partition="ranges": contiguous ranges of the rows (dist.shard_range).  partition="kmeans": the rows are taken into the space
+        the builder's metric searches (`normalize` for METRIC_COSINE, `augment_dot` for METRIC_DOT), clustered there by `kmeans`
+        with at most `kmeans_iters` rounds, and part p holds the rows of cluster p in their original order — a part may be small
+        or empty; the clusters' centroids are set (`set_centroids`), so `search_batch(nprobe=...)` can route."""
         builder = builder or Builder()
         pts = _as_points(points)
         n = pts.shape[0]
         P = int(parts)
+        if partition not in ("ranges", "kmeans"):
+            raise ValueError(f"partition {partition!r}: 'ranges' or 'kmeans'")
         if builder._metric == METRIC_DOT and builder._dot_bound == 0.0 and n:
             # one query augmentation and one report serve all parts: every part is built with the bound of the WHOLE set
             S = C.c_float(0.0)
@@ -77,6 +85,19 @@ class PartitionedHnsw(_RestrictedSearch):
             L.check(L.idist_dot_augment_batch(_capi.f32p(pts), n, max(pts.shape[1], 1), 0.0, None, None, C.byref(S), builder._device))
             builder = copy.copy(builder).dot_bound(S.value)
         devs = [int(d) for d in devices] if devices else [builder._device]
+        centroids = None
+        if partition == "kmeans":
+            space = pts
+            if builder._metric == METRIC_COSINE:
+                space = normalize(pts, builder._device)
+            elif builder._metric == METRIC_DOT:
+                space = augment_dot(pts, builder._dot_bound, builder._device)[0]
+            centroids, assign, _ = kmeans(space, P, kmeans_iters, builder._device)
+            order = np.argsort(assign, kind="stable")
+            cuts = np.searchsorted(assign[order], np.arange(P + 1))
+            rows = [order[cuts[p]:cuts[p + 1]] for p in range(P)]
+        else:
+            rows = [np.arange(*shard_range(n, p, P)) for p in range(P)]
         hnsws: list = [None] * P
         local: list = [None] * P
         errors: list = []
@@ -86,8 +107,8 @@ class PartitionedHnsw(_RestrictedSearch):
                 b = copy.copy(builder)
                 b._device = device
                 for p in mine:
-                    lo, hi = shard_range(n, p, P)
-                    hnsws[p], local[p] = Hnsw._new(pts[lo:hi], b)
+                    lo, hi = (int(rows[p][0]), int(rows[p][-1]) + 1) if len(rows[p]) else (0, 0)
+                    hnsws[p], local[p] = Hnsw._new(pts[lo:hi] if partition == "ranges" else np.ascontiguousarray(pts[rows[p]]), b)
             except BaseException as e:  # noqa: BLE001 - handed to the calling thread
                 errors.append(e)
 
@@ -107,9 +128,28 @@ class PartitionedHnsw(_RestrictedSearch):
         self = cls.from_hnsws(hnsws)
         ids = np.zeros(n, dtype=np.int64)
         for p in range(P):
-            lo, hi = shard_range(n, p, P)
-            ids[lo:hi] = self._base[p] + np.asarray(local[p], dtype=np.int64)
+            ids[rows[p]] = self._base[p] + np.asarray(local[p], dtype=np.int64)
+        if centroids is not None:
+            self.set_centroids(centroids)
         return self, [int(x) for x in ids]
+
+    def set_centroids(self, centroids) -> None:
+        """One centroid per part, [n_parts, kdim], in the space the parts search (idist_partitioned_set_centroids): the rows' own
+        for METRIC_L2SQ / METRIC_L2, `normalize`d rows' for METRIC_COSINE, the kdim = dim + 1 `augment_dot` rows' for METRIC_DOT.
+        What `search_batch(nprobe=...)` ranks the parts of a query by."""
+        cen = _as_points(centroids)
+        info = self.info()
+        kdim = int(info.dim) + (1 if info.metric == METRIC_DOT else 0)
+        if cen.shape != (int(info.n_parts), kdim):
+            raise TypeError(f"centroids of shape {cen.shape}, expected ({int(info.n_parts)}, {kdim})")
+        _lib().check(_lib().idist_partitioned_set_centroids(self._h, _capi.f32p(cen)))
+        self.centroids = cen.copy()
+
+    def last_route_ms(self) -> float:
+        """HIP-event duration of the last routed search's route, gather and scatter kernels, summed, milliseconds."""
+        ms = C.c_float(0.0)
+        _lib().check(_lib().idist_partitioned_last_route_ms(self._h, C.byref(ms)))
+        return float(ms.value)
 
     # -- introspection --
     def info(self) -> _capi.PartitionedInfo:
@@ -146,8 +186,12 @@ class PartitionedHnsw(_RestrictedSearch):
         return self.parts[p].points[pid]
 
     # -- search --
-    def search_batch(self, queries, counters: bool = False) -> BatchResult:
-        """Hnsw::search on every part, merged: <= ef_search (global id, distance) pairs per query, nearest first."""
+    def search_batch(self, queries, counters: bool = False, nprobe: int | None = None, routes: bool = False) -> BatchResult:
+        """Hnsw::search on every part, merged: <= ef_search (global id, distance) pairs per query, nearest first.
+
+        nprobe=k (1 <= k <= n_parts; needs `set_centroids` or `build(partition="kmeans")`): every query searches only the k non-empty
+        parts whose centroids are nearest to it (idist_partitioned_search_batch_routed) and row q is the merge over those;
+        nprobe = n_parts gives nprobe=None's arrays bit for bit.  `routes`: `BatchResult.route` [nq, nprobe] names the parts."""
         q = _as_points(queries)
         info = self.info()
         if q.shape[0] and len(self) and q.shape[1] != info.dim:
@@ -157,8 +201,13 @@ class PartitionedHnsw(_RestrictedSearch):
         dist = np.full((nq, ef), np.inf, dtype=np.float32)
         cnt = np.zeros(nq, dtype=np.uint32)
         ctr = np.zeros((nq, 3), dtype=np.uint32) if counters else None
+        L = _lib()
+        if nprobe is not None:
+            route = np.full((nq, int(nprobe)), INVALID, dtype=np.uint32) if routes else None
+            L.check(L.idist_partitioned_search_batch_routed(self._h, _capi.f32p(q), nq, int(nprobe), _capi.u32p(pid), _capi.f32p(dist), _capi.u32p(cnt),
+                                                            _capi.u32p(ctr) if counters else None, _capi.u32p(route) if routes else None))
+            return BatchResult(pid, dist, cnt, ctr, route)
         if nq:
-            L = _lib()
             L.check(L.idist_partitioned_search_batch(self._h, _capi.f32p(q), nq, _capi.u32p(pid), _capi.f32p(dist),
                                                      _capi.u32p(cnt), _capi.u32p(ctr) if counters else None))
         return BatchResult(pid, dist, cnt, ctr)
