@@ -955,6 +955,45 @@ idist_status idist_grouped_merge_device(const void* d_pid, const void* d_dist, c
                                         const uint32_t* base /* host */, uint32_t k, void* d_out_pid, void* d_out_dist,
                                         void* d_out_group, void* d_out_count, void* d_out_counters, int32_t device, void* hip_stream);
 
+/* ---- diverse search: MMR re-ranking of a search's candidates ------------------------------------------------ */
+/* k results that are near the query and not near each other (maximal marginal relevance, the fetch_k / lambda search of retrieval
+ * stacks), selected on the device from the list Hnsw::search left there.  DEFINITION, for one query:
+ *   1. L = the result of Hnsw::search at the index's ef_search: ids p_0..p_{c-1}, RAW distances d_0..d_{c-1} — what idist_search_batch
+ *      holds before its report pass (L2: the square root; COSINE: the L2SQ of the normalised rows).  The pool is the first
+ *      m = min(c, fetch) entries; fetch == 0 means ef_search.  1 <= k <= fetch <= ef_search.
+ *   2. D(i, j) = the raw canonical distance between the STORED rows p_i and p_j: what idist_distance_batch computes, before the
+ *      report, for the stored row p_i as the query and the id p_j.  Symmetric bit for bit ((a-b)^2 and (b-a)^2 are the same float).
+ *   3. step 0 selects position 0.
+ *   4. step t >= 1: m_i = min over the selected s of D(i, s), updated after each selection as  m_i = D < m_i ? D : m_i  from +inf (a
+ *      NaN never lowers it);  score_i = (lambda * d_i) - ((1.0f - lambda) * m_i):  four f32 operations, each rounded on its own, never
+ *      fused, 1.0f - lambda computed once; with lambda == 1.0f the second term is not computed and score_i = lambda * d_i.  The
+ *      unselected position with the smallest score is selected; scores compare as OrderedFloat does (NaN greatest, all NaNs equal),
+ *      ties go to the lower list position.
+ *   5. results come in selection order: out_pid the ids, out_rank (optional) their positions in L, out_dist = report(d_i) — the
+ *      metric's report runs once, on the [nq][k] result; out_count = min(k, m); padding IDIST_INVALID / +inf / IDIST_INVALID;
+ *      out_counters (optional, nq*3) are the search's.
+ * Two consequences:
+ *   - lambda == 1 returns the first k entries of idist_search_batch bit for bit;
+ *   - COSINE: scoring on raw distances orders as scoring on 1 - cos does — both terms carry the same factor 2.
+ * IDIST_ERR_INVALID_ARG: lambda NaN or outside [0, 1]; k or fetch out of range; a null pointer.  IDIST_ERR_UNSUPPORTED: a DOT index
+ * (the relevance there is an inner product, the pair term over the augmented rows is not one).  Strict-tie retries stay inside the
+ * call, as in idist_search_batch.  n == 0 or ef_search == 0: every count is 0, every row padding (k is not checked).  nq == 0 is
+ * no error.  Host pointers; the call blocks until done; ctx is the `&mut Search`, idx is never mutated.
+ * One search launch, then one selection kernel: rows of the compile-time geometries are read from HBM once and held in registers
+ * for all k steps while fetch fits that tile and is large enough for it to pay (DESIGN.md 4.14 has the measured thresholds),
+ * otherwise (any geometry, any fetch) each step reads the unselected rows again.
+ * Out of scope: the partitioned index, device-pointer / stream variants, idist_search_batch_sharded, MMR over the restricted, range
+ * or grouped lists. */
+idist_status idist_search_batch_mmr(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
+                                    uint32_t k, uint32_t fetch, float lambda,
+                                    uint32_t* out_pid, float* out_dist,   /* nq*k */
+                                    uint32_t* out_rank,                   /* nq*k or NULL */
+                                    uint32_t* out_count,                  /* nq */
+                                    uint32_t* out_counters);              /* nq*3 or NULL */
+/* HIP-event time (ms) of the selection kernel of the last idist_search_batch_mmr through ctx (the search kernel's own time is in
+ * idist_search_ctx_kernel_times).  IDIST_ERR_INVALID_ARG before the first such call, or with IDIST_KERNEL_EVENTS=0. */
+idist_status idist_search_ctx_mmr_kernel_ms(idist_search_ctx* ctx, float* ms);
+
 /* Point::distance for id lists (core/lib.rs:780-782 as used at :709-710): out[q][i] =
  * distance(queries[q], points[ids[q][i]]) for i < n_ids; IDIST_INVALID ids give +inf.
  * Host pointers. The batched gather-L2 kernel on its own. */

@@ -211,6 +211,8 @@ SYMBOLS = {
                                                            _f32p, _u32p, _u32p, _u32p, _u32p]),
     "idist_grouped_merge_device": (C.c_int32, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _u32p, C.c_uint32, _vp, _vp, _vp,
                                                _vp, _vp, C.c_int32, _vp]),
+    "idist_search_batch_mmr": (C.c_int32, [_vp, _vp, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _u32p, _f32p, _u32p, _u32p, _u32p]),
+    "idist_search_ctx_mmr_kernel_ms": (C.c_int32, [_vp, C.POINTER(C.c_float)]),
     "idist_distance_batch": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, _f32p]),
     "idist_filter_bound_batch": (C.c_int32, [_vp, _f32p, C.c_uint32, _u32p, C.c_uint32, _f32p]),
     "idist_bruteforce": (C.c_int32, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p]),

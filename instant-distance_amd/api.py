@@ -265,6 +265,13 @@ class Search:
         _lib().check(_lib().idist_search_ctx_allowed_kernel_ms(self._ctx, C.byref(a), C.byref(b), C.byref(c)))
         return float(a.value), float(b.value), float(c.value)
 
+    def mmr_kernel_ms(self) -> float:
+        """HIP-event time (ms) of the selection kernel of the last `search_mmr` through this Search; the search kernel's own time is
+        in `kernel_times_ms`."""
+        ms = C.c_float(0)
+        _lib().check(_lib().idist_search_ctx_mmr_kernel_ms(self._ctx, C.byref(ms)))
+        return float(ms.value)
+
     def attr_bitmap_ms(self) -> float:
         """HIP-event time (ms) of the bitmap kernel of the last `search_where` / `search_range_where` through this Search."""
         ms = C.c_float(0)
@@ -376,6 +383,16 @@ class AllowedResult:
 class GroupedResult(AllowedResult):
     """`Hnsw.search_grouped`: an `AllowedResult` whose rows hold pairwise distinct groups, each represented by its nearest member."""
     group: np.ndarray     # [nq, k] uint32, the group of every result; 0 padded
+
+
+@dataclass
+class MmrResult:
+    """`Hnsw.search_mmr`: every query holds min(k, fetch, found) results in selection order."""
+    pids: np.ndarray      # [nq, k] uint32, INVALID padded
+    distances: np.ndarray  # [nq, k] float32 to the query, as the metric reports them; +inf padded
+    ranks: np.ndarray     # [nq, k] uint32, the position of every result in `search_batch`'s list; INVALID padded
+    counts: np.ndarray    # [nq]
+    counters: np.ndarray | None  # [nq, 3] {n_dist, n_exp0, n_expU} of the search
 
 
 @dataclass
@@ -1175,6 +1192,25 @@ class Hnsw(_RestrictedSearch):
         is `search_match`'s."""
         return self._grouped(queries, table, by, conds, k, max_rungs, counters, _or_fresh(search))
 
+    def search_mmr(self, queries, k: int = 10, lam: float = 0.5, fetch: int | None = None, search: Search | None = None,
+                   counters: bool = False) -> MmrResult:
+        """k results that are near the query and not near each other (idist_search_batch_mmr): maximal marginal relevance over the
+        first `fetch` entries of `Hnsw::search`'s list (None: all ef_search of them), selected on the device from the rows the
+        index already holds.  Position 0 first; then, k - 1 times, the unselected candidate with the smallest
+        `lam * d(query, i) - (1 - lam) * min over the selected s of d(i, s)` in f32 on the raw distances, ties to the nearer
+        candidate.  `lam=1` is the first k columns of `search_batch`; 1 <= k <= fetch <= ef_search.  METRIC_DOT is refused."""
+        info = self.info()
+        q = _queries(queries, info)
+        nq, k = q.shape[0], max(int(k), 0)
+        pid, dist, cnt, _, ctr = _topk_outputs(nq, k, (nq,), counters)
+        rank = np.full((nq, k), INVALID, dtype=np.uint32)
+        L = _lib()
+        search = _or_fresh(search)                      # (held until the call returns: the context dies with its Search)
+        L.check(L.idist_search_batch_mmr(self._h, search._bind(self), _capi.f32p(q), nq, k, int(fetch or 0), float(lam),
+                                         _capi.u32p(pid), _capi.f32p(dist), _capi.u32p(rank), _capi.u32p(cnt),
+                                         _capi.u32p(ctr) if counters else None))
+        return MmrResult(pid, dist, rank, cnt, ctr)
+
     def search_batch_device(self, search: Search, d_queries: int, nq: int, d_pid: int, d_dist: int, d_count: int,
                             d_counters: int = 0, stream: int = 0):
         """Device-pointer variant: inputs/outputs stay in HBM, enqueued on `stream` without a sync."""
@@ -1352,6 +1388,11 @@ class HnswMap:
                        max_rungs: int = -1) -> list[list[MapItem]]:
         """`Hnsw.search_grouped` with the values: per query the nearest member of each of its groups as `MapItem`s, nearest first."""
         return self._items(self.hnsw.search_grouped(queries, table, by, k, conds, search, max_rungs))
+
+    def search_mmr(self, queries, k: int = 10, lam: float = 0.5, fetch: int | None = None, search: Search | None = None) -> list[list[MapItem]]:
+        """`Hnsw.search_mmr` with the values: per query its results as `MapItem`s, in selection order."""
+        r = self.hnsw.search_mmr(queries, k, lam, fetch, search)
+        return [[self._item(float(r.distances[i, j]), int(r.pids[i, j])) for j in range(int(r.counts[i]))] for i in range(r.pids.shape[0])]
 
     def iter(self):
         return self.hnsw.iter()

@@ -20,6 +20,7 @@
 #include "idist_basis.hpp"
 #include "idist_kmeans.hpp"
 #include "idist_route.hpp"
+#include "idist_mmr.hpp"
 
 #ifndef IDIST_EMU
 #include <hip/hip_runtime.h>
@@ -325,6 +326,7 @@ inline Knobs knobs_from_env() {
     if (const char* e = test_env("IDIST_ALLOWED_SEGMENTS")) k.allowed_segments = std::min(64u, (uint32_t)std::max(0, atoi(e)));
     if (const char* e = test_env("IDIST_RANGE_SEGMENTS")) k.range_segments = std::min(64u, (uint32_t)std::max(0, atoi(e)));
     if (const char* e = test_env("IDIST_GROUPED_STAGE")) k.grouped_stage = (uint64_t)strtoull(e, nullptr, 10);
+    if (const char* e = test_env("IDIST_MMR")) k.mmr = e[0] == 'g' ? 1 : (e[0] == 't' ? 2 : 0);
     if (const char* e = test_env("IDIST_RANGE_SORT_CHUNK")) {
         const uint32_t c = (uint32_t)std::max(0, atoi(e));
         if (c >= 128u && c <= 4096u && (c & (c - 1u)) == 0u) k.range_sort_chunk = c;
@@ -443,6 +445,12 @@ struct idist_search_ctx {
     hipEvent_t at_ev[2] = {nullptr, nullptr};
     bool at_timed = false;
     float at_ms = 0.0f;
+    // The diverse search's: the [nq][k] selection (ids, raw distances, list positions) and its counts; the pair of
+    // events around its kernel (created on first use) and the time they gave (idist_search_ctx_mmr_kernel_ms; < 0: none yet)
+    DevBuf<uint32_t> mm_opid, mm_orank, mm_ocnt;
+    DevBuf<float> mm_odist;
+    hipEvent_t mm_ev[2] = {nullptr, nullptr};
+    float mm_ms = -1.0f;
     DevBuf<float> rg_radius, rg_term, rg_odist;
     DevBuf<uint32_t> rg_lim, rg_cnt, rg_stepcnt, rg_exlen, rg_opid, rg_list;
     DevBuf<uint64_t> rg_off, rg_stepoff, rg_chunks, rg_keys, rg_exoff, rg_lims;
@@ -569,6 +577,16 @@ template <int NB, int RS, int TAIL, bool ON> struct BoundLaunch {       // filte
 };
 template <int NB, int RS, int TAIL> struct BoundLaunch<NB, RS, TAIL, false> {
     static bool go(uint32_t, size_t, const IndexView&, const float*, uint32_t, const uint32_t*, uint32_t, float*) { return false; }
+};
+template <int NB, int RS, int TAIL, bool ON> struct MmrTileLaunch {     // mmr_tile_kernel: the compile-time geometries (MmrTile<NB>)
+    static bool go(uint32_t grid, size_t smem, hipStream_t stream, const IndexView& view, const MmrArgs& a) {
+        auto kT = mmr_tile_kernel<NB, RS, TAIL, MmrTile<NB>::rpg, MmrTile<NB>::waves>;
+        IDIST_LAUNCH(kT, grid, 256, smem, stream, view, a);
+        return true;
+    }
+};
+template <int NB, int RS, int TAIL> struct MmrTileLaunch<NB, RS, TAIL, false> {
+    static bool go(uint32_t, size_t, hipStream_t, const IndexView&, const MmrArgs&) { return false; }
 };
 template <int NB, int RS, int TAIL, int WALK, bool ON> struct DescentLaunch {
     static bool go(uint32_t grid, size_t smem, hipStream_t stream, const IndexView& view, const BuildArgs& a) {
@@ -2207,6 +2225,8 @@ void idist_search_ctx_free(idist_search_ctx* c) {
         if (e) hipEventDestroy(e);
     for (hipEvent_t e : c->at_ev)
         if (e) hipEventDestroy(e);
+    for (hipEvent_t e : c->mm_ev)
+        if (e) hipEventDestroy(e);
     for (uint32_t i = 0; i < IDIST_EVENT_RING; i++) {
         if (c->ev0[i]) hipEventDestroy(c->ev0[i]);
         if (c->ev1[i]) hipEventDestroy(c->ev1[i]);
@@ -2512,6 +2532,119 @@ static idist_status search_batch_impl(const idist_index* idx, idist_search_ctx* 
         idist_status s;
         if (!status_asks_retry(idx, ctx, &s)) return s;
     }
+}
+
+// ---- diverse search: MMR re-ranking of a search's candidates (idist_mmr.hpp) ----
+idist_status idist_search_batch_mmr(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq, uint32_t k,
+                                    uint32_t fetch, float lambda, uint32_t* out_pid, float* out_dist, uint32_t* out_rank,
+                                    uint32_t* out_count, uint32_t* out_counters) {
+    CHK(check_ctx(idx, ctx));
+    if (!(lambda >= 0.0f && lambda <= 1.0f)) return fail(IDIST_ERR_INVALID_ARG, "lambda %g is not in [0, 1]", (double)lambda);
+    if (idx->cfg.metric == IDIST_METRIC_DOT)
+        return fail(IDIST_ERR_UNSUPPORTED, "diverse search on a DOT index: the relevance there is an inner product, and the pair term over "
+                                           "the augmented rows is not one");
+    if (nq == 0) return IDIST_OK;
+    if (!queries || !out_pid || !out_dist || !out_count) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    const uint32_t ef = idx->cfg.ef_search;
+    if (idx->n == 0 || ef == 0) {                                  // nothing to select from: every count 0, every row padding
+        for (size_t i = 0; i < (size_t)nq * k; i++) {
+            out_pid[i] = IDIST_INVALID;
+            out_dist[i] = INFINITY;
+            if (out_rank) out_rank[i] = IDIST_INVALID;
+        }
+        memset(out_count, 0, (size_t)nq * 4);
+        if (out_counters) memset(out_counters, 0, (size_t)nq * 12);
+        return IDIST_OK;
+    }
+    if (fetch == 0) fetch = ef;
+    if (k == 0 || k > fetch || fetch > ef)
+        return fail(IDIST_ERR_INVALID_ARG, "k %u, fetch %u, ef_search %u: 1 <= k <= fetch <= ef_search", k, fetch, ef);
+    const MmrPlan plan = plan_mmr(idx->L, fetch, ctx->knobs.mmr);
+    if (!plan.ok) return fail(IDIST_ERR_INVALID_ARG, "the tile kernel was asked for (test knob), but there is none for this row geometry (stride %u) at fetch %u", idx->L.stride, fetch);
+    const size_t smem = plan.tile ? mmr_tile_smem(idx->L.stride) : mmr_global_smem(idx->L.stride, fetch);
+    if (smem > 64 * 1024) return fail(IDIST_ERR_INVALID_ARG, "dim/fetch need %zu B of LDS per %s (> 64 KiB)", smem, plan.tile ? "workgroup" : "wave");
+    HIPCHK(hipSetDevice(idx->device));
+    hipStream_t stream = ctx->stream;
+    const size_t qb = (size_t)nq * idx->dim * 4, lb = (size_t)nq * ef * 4, ob = (size_t)nq * k * 4;
+    CHK(ctx->d_q.grow(qb));
+    CHK(ctx->d_pid.grow(lb));
+    CHK(ctx->d_dist.grow(lb));
+    CHK(ctx->d_cnt.grow((size_t)nq * 4));
+    CHK(ctx->d_ctr.grow((size_t)nq * 12));
+    CHK(ctx->mm_opid.grow(ob));
+    CHK(ctx->mm_odist.grow(ob));
+    CHK(ctx->mm_orank.grow(ob));
+    CHK(ctx->mm_ocnt.grow((size_t)nq * 4));
+    HIPCHK(hipMemcpyAsync(ctx->d_q, queries, qb, hipMemcpyHostToDevice, stream));
+    // the lists stay raw: the queries are prepared here, the report runs once, behind the selection, on [nq][k]
+    const MetricPasses metric(idx);
+    const float* d_qk = ctx->d_q;
+    if (metric.any()) {
+        CHK(ctx->d_qn.grow(doubled_from(4096, metric.qk_floats(nq) * 4)));
+        CHK(metric.prepare(ctx->d_q, ctx->d_qn, nullptr, nq, stream, &d_qk));
+    }
+    SearchOpts opts;
+    opts.prepared = true;
+    for (;;) {
+        CHK(launch_search(idx, ctx, d_qk, nq, ctx->d_pid, ctx->d_dist, ctx->d_cnt, out_counters ? ctx->d_ctr.p : nullptr, stream, opts));
+        HIPCHK(hipStreamSynchronize(stream));
+        idist_status s;
+        if (status_asks_retry(idx, ctx, &s)) continue;
+        if (s != IDIST_OK) return s;
+        break;
+    }
+    MmrArgs a{};
+    a.r_pid = ctx->d_pid;
+    a.r_dist = reinterpret_cast<const uint32_t*>(ctx->d_dist.p);
+    a.r_count = ctx->d_cnt;
+    a.nq = nq;
+    a.width = ef;
+    a.k = k;
+    a.fetch = fetch;
+    a.lambda = lambda;
+    a.mu = 1.0f - lambda;
+    a.lam1 = lambda == 1.0f ? 1u : 0u;
+    a.o_pid = ctx->mm_opid;
+    a.o_dist = reinterpret_cast<uint32_t*>(ctx->mm_odist.p);
+    a.o_rank = ctx->mm_orank;
+    a.o_count = ctx->mm_ocnt;
+    const IndexView view = idx->view();
+    const uint32_t grid = std::min<uint32_t>(nq, (uint32_t)std::max(idx->n_cu, 1) * (plan.tile ? plan.waves : 16u));
+    ctx->mm_ms = -1.0f;
+    if (ctx->knobs.events) {
+        for (hipEvent_t& e : ctx->mm_ev)
+            if (!e) HIPCHK(hipEventCreate(&e));
+        HIPCHK(hipEventRecord(ctx->mm_ev[0], stream));
+    }
+    bool launched = true;
+#define LAUNCH_MMR(NB_, RS_, TAIL_)                                                                              \
+    if (plan.tile) {                                                                                             \
+        launched = MmrTileLaunch<NB_, RS_, TAIL_, (MmrTile<NB_>::rpg > 0)>::go(grid, smem, stream, view, a);     \
+    } else {                                                                                                     \
+        auto kG = mmr_global_kernel<NB_, RS_, TAIL_>;                                                            \
+        IDIST_LAUNCH(kG, grid, 64, smem, stream, view, a);                                                       \
+    }
+    IDIST_DISPATCH(idx->L, LAUNCH_MMR);
+#undef LAUNCH_MMR
+    if (!launched) return fail(IDIST_ERR_INTERNAL, "no tile kernel for this row geometry (stride %u)", idx->L.stride);
+    HIPCHK(hipGetLastError());
+    if (ctx->knobs.events) HIPCHK(hipEventRecord(ctx->mm_ev[1], stream));
+    CHK(metric.report(ctx->mm_odist, nullptr, nq, k, stream));
+    HIPCHK(hipMemcpyAsync(out_pid, ctx->mm_opid, ob, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(out_dist, ctx->mm_odist, ob, hipMemcpyDeviceToHost, stream));
+    if (out_rank) HIPCHK(hipMemcpyAsync(out_rank, ctx->mm_orank, ob, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(out_count, ctx->mm_ocnt, (size_t)nq * 4, hipMemcpyDeviceToHost, stream));
+    if (out_counters) HIPCHK(hipMemcpyAsync(out_counters, ctx->d_ctr, (size_t)nq * 12, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (ctx->knobs.events) HIPCHK(hipEventElapsedTime(&ctx->mm_ms, ctx->mm_ev[0], ctx->mm_ev[1]));
+    return IDIST_OK;
+}
+
+idist_status idist_search_ctx_mmr_kernel_ms(idist_search_ctx* ctx, float* ms) {
+    if (!ctx || !ms) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    if (ctx->mm_ms < 0.0f) return fail(IDIST_ERR_INVALID_ARG, "no diverse search has been timed for this ctx (IDIST_KERNEL_EVENTS=0, or no call yet)");
+    *ms = ctx->mm_ms;
+    return IDIST_OK;
 }
 
 // ---- several GPUs of one node: replicate once, shard the queries ----
