@@ -37,6 +37,11 @@ def d64(x, c):
 ASSIGN_SHAPES = [(1, 1, 1), (127, 31, 2), (128, 32, 33), (129, 33, 64), (257, 100, 33), (257, 1, 64), (129, 100, 2), (130, 170, 40)]
 
 
+# centroids staged per chunk (dim > 160) with both accumulators over six row tiles; both sides of the staging boundary (dim 160 with
+# its 64 centroids resident, 161 not); k = 32 exactly (the second accumulator skipped) and k = 33, 17 beyond the boundary; one tiny
+ASSIGN_SHAPES += [(700, 200, 64), (385, 161, 33), (300, 160, 64), (513, 192, 17), (260, 164, 32), (5, 5, 5)]
+
+
 @pytest.mark.parametrize("n,dim,k", ASSIGN_SHAPES)
 def test_assign_exact(eng, n, dim, k):
     ida, _ = eng
@@ -65,19 +70,83 @@ def test_assign_float(eng):
     assert np.all(got <= d.min(axis=1) + 2 * E)
 
 
-@pytest.mark.parametrize("n,dim,k", [(129, 33, 5), (1025, 3, 4), (2100, 70, 64)])
+def scan64(x, c):
+    """include/idist.h's definition written out in f64 with IEEE inf and NaN: d~ = (|x|^2 + |c|^2) - 2 x.c, then the strict `<` scan
+    from j = 0 — a NaN at j = 0 is never beaten, a NaN elsewhere never taken.  On the lattice every finite term is exact in f32 too."""
+    x, c = x.astype(np.float64), c.astype(np.float64)
+    with np.errstate(all="ignore"):
+        d = ((x ** 2).sum(axis=1)[:, None] + (c ** 2).sum(axis=1)[None, :]) - 2.0 * (x[:, None, :] * c[None, :, :]).sum(axis=2)
+    a, best = np.zeros(len(x), np.int64), d[:, 0].copy()
+    for j in range(1, len(c)):
+        m = d[:, j] < best
+        a[m], best[m] = j, d[m, j]
+    return a
+
+
+@pytest.mark.parametrize("dim,k,j,value", [(40, 9, 0, np.nan), (40, 9, 3, np.nan), (40, 40, 35, np.nan), (200, 9, 3, np.inf),
+                                           (40, 9, 0, np.inf), (40, 9, 0, -np.inf)])
+def test_assign_nonfinite_centroid(eng, dim, k, j, value):
+    """one coordinate of centroid j is NaN or infinite: its d~ is NaN wherever 0 * inf or inf - inf occurs and +inf elsewhere, the
+    other centroids' are untouched.  At j = 0 the NaN rows stay with it; at j > 0 it receives nothing."""
+    ida, _ = eng
+    x, c = lattice(200, dim, k)
+    if j:
+        c[j] = x[7]                                       # while it is finite the centroid has a row of its own
+    clean = scan64(x, c)
+    assert np.array_equal(ida.kmeans_assign(x, c)[0], clean)
+    c[j, 2] = value
+    want = scan64(x, c)
+    if j == 0:
+        assert np.any(want != clean) and np.any(want == 0)
+    else:
+        assert not np.any(want == j) and np.any(clean == j)
+    assign, counts = ida.kmeans_assign(x, c)
+    assert np.array_equal(assign, want), (dim, k, j, value)
+    assert np.array_equal(counts, np.bincount(want, minlength=k))
+
+
+def test_overflowing_rows(eng):
+    """a row whose |x|^2 overflows although every element is finite, and a row with -inf: both get i mod k, and the update counts
+    them as members without summing them — the rest stays within test_update_float's bound (one chunk) and test_assign_float's"""
+    ida, _ = eng
+    n, dim, k = 130, 12, 7
+    rng = np.random.default_rng(21)
+    x, c = rng.standard_normal((n, dim)).astype(np.float32), rng.standard_normal((k, dim)).astype(np.float32)
+    x[5] *= np.float32(1e20)
+    x[77, 4] = -np.inf
+    assert np.all(np.isfinite(x[5])) and (x[5].astype(np.float64) ** 2).sum() > 2 * float(np.finfo(np.float32).max)
+    assign, counts = ida.kmeans_assign(x, c)
+    assert assign[5] == 5 % k and assign[77] == 77 % k
+    assert counts.sum() == n and np.array_equal(counts, np.bincount(assign, minlength=k))
+    ok = ~np.isin(np.arange(n), (5, 77))
+    d = d64(x[ok], c)
+    E = 4 * U * 32 * ((x[ok].astype(np.float64) ** 2).sum(axis=1) + (c.astype(np.float64) ** 2).sum(axis=1).max())
+    assert np.all(d[np.arange(ok.sum()), assign[ok]] <= d.min(axis=1) + 2 * E)
+    got, ucounts = ida.kmeans_update(x, assign, np.zeros((k, dim), np.float32))
+    assert np.array_equal(ucounts, counts)
+    for j in range(k):
+        m = (assign == j) & ok
+        assert m.any() and m.sum() == counts[j] - (j == 5 % k) - (j == 77 % k)
+        xs = x[m].astype(np.float64)
+        bound = (1024 + 1 + 2) * U * np.abs(xs).sum(axis=0) / m.sum()
+        assert np.all(np.abs(got[j] - xs.sum(axis=0) / m.sum()) <= bound)
+
+
+# ... and a column tile of 64 exactly full and one column over (dim 64, 65, 128, 129), n exactly one and two chunks, one row
+@pytest.mark.parametrize("n,dim,k", [(129, 33, 5), (1025, 3, 4), (2100, 70, 64),
+                                     (1024, 64, 64), (1025, 65, 64), (2048, 128, 7), (2049, 129, 33), (3, 1, 1)])
 def test_update_exact(eng, n, dim, k):
     """lattice rows: the sums are exact, so the centroid is the one rounded division; n = chunk + 1 and three chunks; cluster k - 1 is
-    empty and keeps its centroid"""
+    empty (where k > 1) and keeps its centroid"""
     ida, _ = eng
     from instant_distance_amd import _capi
 
     assert _capi.KMEANS_CHUNK == 1024
     x, c = lattice(n, dim, k)
-    assign = np.random.default_rng(n).integers(0, k - 1, n).astype(np.uint32)
+    assign = np.random.default_rng(n).integers(0, max(k - 1, 1), n).astype(np.uint32)
     got, counts = ida.kmeans_update(x, assign, c)
     want = c.copy()
-    for j in range(k - 1):
+    for j in range(max(k - 1, 1)):
         m = assign == j
         if m.any():
             want[j] = np.float32(x[m].astype(np.float64).sum(axis=0) / m.sum())
@@ -150,7 +219,16 @@ def test_grid_independence(eng, monkeypatch):
             monkeypatch.setenv("IDIST_CUS", cus)
         cen, assign, counts = ida.kmeans(x, 9, 4)
         results.append(pc.bits(cen).tobytes() + assign.tobytes() + counts.tobytes())
+        if cus is None:
+            first = cen, assign, counts
     assert all(r == results[0] for r in results)
+    # ... and the runs are anchored to a model: the assignment belongs to the centroids returned, within test_assign_float's bound
+    cen, assign, counts = first
+    again, acounts = ida.kmeans_assign(x, cen)
+    assert np.array_equal(assign, again) and np.array_equal(counts, acounts) and np.array_equal(counts, np.bincount(assign, minlength=9))
+    d = d64(x, cen)
+    E = 4 * U * 96 * ((x.astype(np.float64) ** 2).sum(axis=1) + (cen.astype(np.float64) ** 2).sum(axis=1).max())
+    assert np.all(d[np.arange(len(x)), assign] <= d.min(axis=1) + 2 * E)
 
 
 def test_argument_errors(eng):

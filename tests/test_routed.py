@@ -137,7 +137,7 @@ def test_grid_independence(eng, oracle, monkeypatch):
     assert all(r == results[0] for r in results)
 
 
-@pytest.mark.parametrize("metric", [L2SQ, DOT])
+@pytest.mark.parametrize("metric", [L2SQ, COSINE, DOT])
 def test_build_kmeans(eng, metric):
     """the ids are a bijection, index[ids[i]] is points[i], and every part's members are nearest to their part's stored centroid
     within the product-form bound of tests/test_kmeans.py::test_assign_float"""
@@ -148,7 +148,7 @@ def test_build_kmeans(eng, metric):
     ph, ids = ida.PartitionedHnsw.build(pts, ida.Builder().metric(metric).max_batch(1).ef_search(20), parts=P, partition="kmeans", kmeans_iters=5)
     assert sorted(ids) == list(range(n)) and len(ph) == n
     assert all(np.array_equal(ph[ids[i]], pts[i]) for i in range(n))
-    space = (ida.augment_dot(pts)[0] if metric == DOT else pts).astype(np.float64)
+    space = {L2SQ: lambda: pts, COSINE: lambda: ida.normalize(pts), DOT: lambda: ida.augment_dot(pts)[0]}[metric]().astype(np.float64)
     c = ph.centroids.astype(np.float64)
     assert c.shape == (P, dim + (metric == DOT))
     d = ((space[:, None, :] - c[None]) ** 2).sum(axis=2)
@@ -157,3 +157,23 @@ def test_build_kmeans(eng, metric):
     assert np.all(d[np.arange(n), part] <= d.min(axis=1) + 2 * E)
     r = ph.search_batch(pts[:9], nprobe=1, routes=True)
     assert np.array_equal(r.route[:, 0], part[:9]) or np.all(r.count > 0)
+
+
+def test_build_kmeans_mostly_empty(eng):
+    """64 parts of 100 rows with 5 distinct values: most clusters, so most parts, are empty — the ids are still a bijection, all parts
+    routed is the unrouted call, and a query that equals a stored row finds its part"""
+    ida, _ = eng
+    n, P = 100, 64
+    pts = np.ascontiguousarray(np.random.default_rng(4).standard_normal((5, 8)).astype(np.float32)[np.arange(n) % 5])
+    ph, ids = ida.PartitionedHnsw.build(pts, ida.Builder().max_batch(1).ef_search(20), parts=P, partition="kmeans", kmeans_iters=5)
+    assert sorted(ids) == list(range(n)) and len(ph) == n
+    assert all(np.array_equal(ph[ids[i]], pts[i]) for i in range(n))
+    sizes = np.diff(ph._base)
+    assert len(sizes) == P and 1 <= np.count_nonzero(sizes) <= 5 and ph.centroids.shape == (P, 8)
+    full = ph.search_batch(pts, counters=True)
+    got = ph.search_batch(pts, counters=True, nprobe=P, routes=True)
+    assert np.array_equal(got.pid, full.pid) and np.array_equal(pc.bits(got.distance), pc.bits(full.distance))
+    assert np.array_equal(got.count, full.count) and np.array_equal(got.counters, full.counters)
+    assert np.all((got.route != INVALID).sum(axis=1) == np.count_nonzero(sizes))
+    r = ph.search_batch(pts, nprobe=1, routes=True)
+    assert np.all(r.count > 0) and np.all(sizes[r.route[:, 0]] > 0)
