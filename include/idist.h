@@ -982,7 +982,7 @@ idist_status idist_grouped_merge_device(const void* d_pid, const void* d_dist, c
  * One search launch, then one selection kernel: rows of the compile-time geometries are read from HBM once and held in registers
  * for all k steps while fetch fits that tile and is large enough for it to pay (DESIGN.md 4.14 has the measured thresholds),
  * otherwise (any geometry, any fetch) each step reads the unselected rows again.
- * Out of scope: the partitioned index, device-pointer / stream variants, idist_search_batch_sharded, MMR over the restricted, range
+ * Out of scope: device-pointer / stream variants, idist_search_batch_sharded, MMR over the restricted, range
  * or grouped lists. */
 idist_status idist_search_batch_mmr(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq,
                                     uint32_t k, uint32_t fetch, float lambda,
@@ -1069,6 +1069,36 @@ idist_status idist_partitioned_search_batch_routed(idist_partitioned* p, const f
                                                    uint32_t* out_counters /* nq*3 or NULL */, uint32_t* out_route /* nq*nprobe or NULL */);
 /* HIP-event time of the last routed call's route, gather and scatter kernels, summed, milliseconds. */
 idist_status idist_partitioned_last_route_ms(idist_partitioned* p, float* ms);
+
+/* ---- diverse search over a partitioned index (idist_mmr_pool.hpp) ----
+ * Row q is the DEFINITION of idist_search_batch_mmr, steps 1-5, word for word, with two substitutions:
+ *   - L is the merged list of idist_partitioned_search_batch for q before its report pass: GLOBAL ids, raw distances, `Candidate`
+ *     order; out_count and out_counters come from that call's count and counters;
+ *   - D(i, j) is the raw canonical distance between the stored rows of the global ids p_i and p_j, each row taken from the part that
+ *     holds it (all parts share dim and metric, and with them the row layout; COSINE rows are normalised per row, whatever the part).
+ * The rest is unchanged: 1 <= k <= fetch <= ef_search, fetch == 0 means ef_search; out_rank is the position in the merged list; the
+ * report runs once on the [nq][k] result; padding IDIST_INVALID / +inf / IDIST_INVALID; the same argument errors;
+ * IDIST_ERR_UNSUPPORTED on DOT parts.  Strict-tie retries stay inside the parts, a part's failure carries the "part <p> (device <d>): "
+ * prefix, the parts' dim / metric / ef_search are compared again at every call.  N == 0 or ef_search == 0: every count is 0, every
+ * row padding.  nq == 0 is no error.  Host pointers; the call blocks until done.
+ * Three consequences:
+ *   - one part: every output equals idist_search_batch_mmr on that part;
+ *   - lambda == 1 returns the first k entries of idist_partitioned_search_batch bit for bit;
+ *   - P parts over concatenated points: the outputs are the plain greedy loop over idist_partitioned_search_batch's list and the
+ *     caller's own rows.
+ * The rows behind a query's pool are copied from their parts (each on its own device and stream, one peer copy per part away from
+ * the merge device) into one dense pool on the merge device, and the selection kernels of idist_search_batch_mmr read them from
+ * there; the call runs in chunks of queries whose pool stays within 1 GiB. */
+idist_status idist_partitioned_search_batch_mmr(idist_partitioned* p, const float* queries, uint32_t nq, uint32_t k, uint32_t fetch,
+                                                float lambda,
+                                                uint32_t* out_pid, float* out_dist,   /* nq*k */
+                                                uint32_t* out_rank,                   /* nq*k or NULL */
+                                                uint32_t* out_count,                  /* nq */
+                                                uint32_t* out_counters);              /* nq*3 or NULL */
+/* HIP-event times (ms) of the last idist_partitioned_search_batch_mmr, summed over its chunks: gather_ms the pool kernels (lists and
+ * the parts' row gathers), select_ms the selection kernel.  IDIST_ERR_INVALID_ARG before the first such call, or with
+ * IDIST_KERNEL_EVENTS=0. */
+idist_status idist_partitioned_last_mmr_ms(idist_partitioned* p, float* gather_ms, float* select_ms);
 
 #ifdef __cplusplus
 }

@@ -224,6 +224,8 @@ SYMBOLS = {
     "idist_partitioned_set_centroids": (C.c_int32, [_vp, _f32p]),
     "idist_partitioned_search_batch_routed": (C.c_int32, [_vp, _f32p, C.c_uint32, C.c_uint32, _u32p, _f32p, _u32p, _u32p, _u32p]),
     "idist_partitioned_last_route_ms": (C.c_int32, [_vp, C.POINTER(C.c_float)]),
+    "idist_partitioned_search_batch_mmr": (C.c_int32, [_vp, _f32p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, _u32p, _f32p, _u32p, _u32p, _u32p]),
+    "idist_partitioned_last_mmr_ms": (C.c_int32, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
 }
 
 

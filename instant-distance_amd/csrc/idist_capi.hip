@@ -21,6 +21,7 @@
 #include "idist_kmeans.hpp"
 #include "idist_route.hpp"
 #include "idist_mmr.hpp"
+#include "idist_mmr_pool.hpp"
 
 #ifndef IDIST_EMU
 #include <hip/hip_runtime.h>
@@ -493,6 +494,10 @@ struct idist_partitioned {
         DevBuf<float> q_dense;
         hipEvent_t gev0 = nullptr, gev1 = nullptr;
         bool gathered = false;
+        // diverse search, a part away from the merge device: its slice of the pool lists and its rows packed densely, on its device
+        // (the gather there is timed with gev0 / gev1 as well)
+        DevBuf<uint32_t> mp_list;
+        DevBuf<float> mp_rows;
     };
     struct Dev {
         int32_t device = 0;
@@ -519,6 +524,16 @@ struct idist_partitioned {
     DevBuf<uint32_t> r_route, r_sel, r_list, r_lens, g_pid, g_cnt, g_ctr;
     hipEvent_t rev[4] = {nullptr, nullptr, nullptr, nullptr};   // around the route kernels and around the scatter kernel
     float route_ms = -1.0f;                  // the last routed call's route, gather and scatter kernels (-1: none has run)
+    // diverse search (idist_mmr_pool.hpp), on the merge device, sized for one chunk of queries: the (part, query) counts, their prefix
+    // sum with its chunk sums, the parts' first slots; the local id of every slot, the slot of every pool position, the pool itself;
+    // then the [nq][k] selection of the whole batch (ids, raw distances, list positions) and its counts
+    DevBuf<uint32_t> mp_cnt, mp_lid, mp_row;
+    DevBuf<uint64_t> mp_off, mp_chunks, mp_bounds;
+    DevBuf<float> mp_pool;
+    DevBuf<uint32_t> mo_pid, mo_rank, mo_cnt;
+    DevBuf<float> mo_dist;
+    hipEvent_t mev[4] = {nullptr, nullptr, nullptr, nullptr};   // around a chunk's list kernels and around its selection kernel
+    float mmr_gather_ms = -1.0f, mmr_select_ms = -1.0f;          // the last diverse search's pool kernels / selection kernels (-1: none timed)
     float al_slice_ms = 0.0f;                // ... and the host time its last call spent on the bitmaps: upload + slice, every part
                                              // (an attribute call: the parts' bitmap kernels, HIP events, summed)
     // range search, on the merge device: the merged counts, lims and the chunk sums of their prefix sum; the merged result, which no
@@ -578,14 +593,14 @@ template <int NB, int RS, int TAIL, bool ON> struct BoundLaunch {       // filte
 template <int NB, int RS, int TAIL> struct BoundLaunch<NB, RS, TAIL, false> {
     static bool go(uint32_t, size_t, const IndexView&, const float*, uint32_t, const uint32_t*, uint32_t, float*) { return false; }
 };
-template <int NB, int RS, int TAIL, bool ON> struct MmrTileLaunch {     // mmr_tile_kernel: the compile-time geometries (MmrTile<NB>)
+template <int NB, int RS, int TAIL, bool POOL, bool ON> struct MmrTileLaunch {     // mmr_tile_kernel: the compile-time geometries (MmrTile<NB>)
     static bool go(uint32_t grid, size_t smem, hipStream_t stream, const IndexView& view, const MmrArgs& a) {
-        auto kT = mmr_tile_kernel<NB, RS, TAIL, MmrTile<NB>::rpg, MmrTile<NB>::waves>;
+        auto kT = mmr_tile_kernel<NB, RS, TAIL, MmrTile<NB>::rpg, MmrTile<NB>::waves, POOL>;
         IDIST_LAUNCH(kT, grid, 256, smem, stream, view, a);
         return true;
     }
 };
-template <int NB, int RS, int TAIL> struct MmrTileLaunch<NB, RS, TAIL, false> {
+template <int NB, int RS, int TAIL, bool POOL> struct MmrTileLaunch<NB, RS, TAIL, POOL, false> {
     static bool go(uint32_t, size_t, hipStream_t, const IndexView&, const MmrArgs&) { return false; }
 };
 template <int NB, int RS, int TAIL, int WALK, bool ON> struct DescentLaunch {
@@ -2535,6 +2550,28 @@ static idist_status search_batch_impl(const idist_index* idx, idist_search_ctx* 
 }
 
 // ---- diverse search: MMR re-ranking of a search's candidates (idist_mmr.hpp) ----
+// the selection kernel `plan` names for rows of layout L, enqueued on `stream`.  POOL: `view` is a row pool and a.r_row names the rows
+// (the partitioned call); otherwise the rows are the index's own
+extern "C++" {
+namespace {
+template <bool POOL> idist_status launch_mmr(const Layout& L, const MmrPlan& plan, uint32_t grid, size_t smem, hipStream_t stream,
+                                             const IndexView& view, const MmrArgs& a) {
+    bool launched = true;
+#define LAUNCH_MMR(NB_, RS_, TAIL_)                                                                                    \
+    if (plan.tile) {                                                                                                   \
+        launched = MmrTileLaunch<NB_, RS_, TAIL_, POOL, (MmrTile<NB_>::rpg > 0)>::go(grid, smem, stream, view, a);     \
+    } else {                                                                                                           \
+        auto kG = mmr_global_kernel<NB_, RS_, TAIL_, POOL>;                                                            \
+        IDIST_LAUNCH(kG, grid, 64, smem, stream, view, a);                                                             \
+    }
+    IDIST_DISPATCH(L, LAUNCH_MMR);
+#undef LAUNCH_MMR
+    if (!launched) return fail(IDIST_ERR_INTERNAL, "no tile kernel for this row geometry (stride %u)", L.stride);
+    HIPCHK(hipGetLastError());
+    return IDIST_OK;
+}
+}  // namespace
+}  // extern "C++"
 idist_status idist_search_batch_mmr(const idist_index* idx, idist_search_ctx* ctx, const float* queries, uint32_t nq, uint32_t k,
                                     uint32_t fetch, float lambda, uint32_t* out_pid, float* out_dist, uint32_t* out_rank,
                                     uint32_t* out_count, uint32_t* out_counters) {
@@ -2616,18 +2653,7 @@ idist_status idist_search_batch_mmr(const idist_index* idx, idist_search_ctx* ct
             if (!e) HIPCHK(hipEventCreate(&e));
         HIPCHK(hipEventRecord(ctx->mm_ev[0], stream));
     }
-    bool launched = true;
-#define LAUNCH_MMR(NB_, RS_, TAIL_)                                                                              \
-    if (plan.tile) {                                                                                             \
-        launched = MmrTileLaunch<NB_, RS_, TAIL_, (MmrTile<NB_>::rpg > 0)>::go(grid, smem, stream, view, a);     \
-    } else {                                                                                                     \
-        auto kG = mmr_global_kernel<NB_, RS_, TAIL_>;                                                            \
-        IDIST_LAUNCH(kG, grid, 64, smem, stream, view, a);                                                       \
-    }
-    IDIST_DISPATCH(idx->L, LAUNCH_MMR);
-#undef LAUNCH_MMR
-    if (!launched) return fail(IDIST_ERR_INTERNAL, "no tile kernel for this row geometry (stride %u)", idx->L.stride);
-    HIPCHK(hipGetLastError());
+    CHK(launch_mmr<false>(idx->L, plan, grid, smem, stream, view, a));
     if (ctx->knobs.events) HIPCHK(hipEventRecord(ctx->mm_ev[1], stream));
     CHK(metric.report(ctx->mm_odist, nullptr, nq, k, stream));
     HIPCHK(hipMemcpyAsync(out_pid, ctx->mm_opid, ob, hipMemcpyDeviceToHost, stream));
@@ -3011,6 +3037,7 @@ void idist_partitioned_free(idist_partitioned* p) {
         if (pt.gev1) hipEventDestroy(pt.gev1);
     }
     for (hipEvent_t e : p->rev) if (e) hipEventDestroy(e);
+    for (hipEvent_t e : p->mev) if (e) hipEventDestroy(e);
     if (p->ev0) hipEventDestroy(p->ev0);
     if (p->ev1) hipEventDestroy(p->ev1);
     if (p->stream) hipStreamDestroy(p->stream);
@@ -3048,6 +3075,7 @@ static idist_status partitioned_reserve(idist_partitioned* p, uint32_t nq, uint3
 
 static idist_status bruteforce_impl(const idist_index* idx, const float* queries, uint32_t nq, uint32_t k, uint32_t* out_pid,
                                     float* out_dist, bool raw);
+static idist_status partitioned_search_parts(idist_partitioned* p, const float* queries, uint32_t nq, uint32_t ef, bool counters);
 
 // What the report behind the merge needs of the batch's queries — s(q), for a metric that has one — on the merge device (which is
 // current); enqueued on p->stream
@@ -3061,12 +3089,12 @@ static idist_status partitioned_prepare_report(idist_partitioned* p, const float
     return metric.prepare(p->d_qm, nullptr, p->d_sq, nq, p->stream, nullptr);
 }
 
-// the merge kernel between two events + its result to the host; every part's list is complete in the staging memory.  The parts
+// the merge kernel between two events (partitioned_merge_lists: the merged lists stay on the device, raw) + its result to the host
+// (partitioned_merge); every part's list is complete in the staging memory.  The parts
 // hand in the index's raw squared-L2 distances: the metric's report runs HERE, after the merge (partitioned_prepare_report ran on
 // this stream before) — the merge relies on every list being strictly ordered by (distance bits, id) with non-negative keys, which
 // halving can break for denormal distances.
-static idist_status partitioned_merge(idist_partitioned* p, uint32_t nq, uint32_t width, uint32_t out_width, bool counters,
-                                      uint32_t* out_pid, float* out_dist, uint32_t* out_count, uint32_t* out_counters) {
+static idist_status partitioned_merge_lists(idist_partitioned* p, uint32_t nq, uint32_t width, uint32_t out_width, bool counters) {
     MergeArgs a{};
     a.pid = p->s_pid; a.dist = (const uint32_t*)p->s_dist.p; a.count = p->s_cnt; a.counters = counters ? p->s_ctr.p : nullptr;
     a.n_lists = (uint32_t)p->parts.size(); a.nq = nq; a.width = width; a.out_width = out_width;
@@ -3076,6 +3104,11 @@ static idist_status partitioned_merge(idist_partitioned* p, uint32_t nq, uint32_
     CHK(launch_merge(a, p->stream));
     HIPCHK(hipEventRecord(p->ev1, p->stream));
     p->timed = true;
+    return IDIST_OK;                                     // (the diverse search selects from the raw lists before any report)
+}
+static idist_status partitioned_merge(idist_partitioned* p, uint32_t nq, uint32_t width, uint32_t out_width, bool counters,
+                                      uint32_t* out_pid, float* out_dist, uint32_t* out_count, uint32_t* out_counters) {
+    CHK(partitioned_merge_lists(p, nq, width, out_width, counters));
     CHK(MetricPasses(p).report(p->o_dist, p->d_sq, nq, out_width, p->stream));
     const size_t ob = (size_t)nq * out_width * 4;
     HIPCHK(hipMemcpyAsync(out_pid, p->o_pid, ob, hipMemcpyDeviceToHost, p->stream));
@@ -3188,7 +3221,16 @@ idist_status idist_partitioned_search_batch(idist_partitioned* p, const float* q
     }
     if (!out_pid || !out_dist) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
     const bool counters = out_counters != nullptr;
-    const size_t row = (size_t)nq * ef;
+    CHK(partitioned_search_parts(p, queries, nq, ef, counters));
+    // 4. the union
+    HIPCHK(hipSetDevice(p->merge_device));
+    return partitioned_merge(p, nq, ef, ef, counters, out_pid, out_dist, out_count, out_counters);
+}
+
+// Steps 1-3 of idist_partitioned_search_batch: every part's list of `ef` per query, complete in the staging memory of the merge device
+// (reserved here), the report's query term prepared on p->stream.  Leaves another device current.
+static idist_status partitioned_search_parts(idist_partitioned* p, const float* queries, uint32_t nq, uint32_t ef, bool counters) {
+    const size_t P = p->parts.size(), row = (size_t)nq * ef;
     HIPCHK(hipSetDevice(p->merge_device));
     CHK(partitioned_reserve(p, nq, ef, ef));
     CHK(partitioned_prepare_report(p, queries, nq));
@@ -3234,9 +3276,7 @@ idist_status idist_partitioned_search_batch(idist_partitioned* p, const float* q
             return part_failed(p, i, s, g_err);
         }
     }
-    // 4. the union
-    HIPCHK(hipSetDevice(p->merge_device));
-    return partitioned_merge(p, nq, ef, ef, counters, out_pid, out_dist, out_count, out_counters);
+    return IDIST_OK;
 }
 
 idist_status idist_partitioned_bruteforce(idist_partitioned* p, const float* queries, uint32_t nq, uint32_t k,
@@ -5812,6 +5852,194 @@ idist_status idist_partitioned_last_range_merge_ms(idist_partitioned* p, float* 
     if (!p || !ms) return fail(IDIST_ERR_INVALID_ARG, "null argument");
     if (p->rg_merge_ms < 0.0f) return fail(IDIST_ERR_INVALID_ARG, "no range search has run through this object yet");
     *ms = p->rg_merge_ms;
+    return IDIST_OK;
+}
+
+// ---- diverse search over a partitioned index: the merged lists, a row pool on the merge device, the selection (idist_mmr_pool.hpp) ----
+// One chunk of `cq` queries from q0: the pool lists on p->stream, every part's rows gathered on its own device and stream, then the
+// selection from the pool into rows q0.. of mo_*.  The merge device is current on entry and on return.
+static idist_status partitioned_mmr_chunk(idist_partitioned* p, const idist_index* first, const MmrPlan& plan, size_t smem, MmrArgs a,
+                                          uint32_t ef, uint32_t q0, uint32_t cq, bool events) {
+    const size_t P = p->parts.size();
+    const uint32_t stride = first->L.stride, fetch = a.fetch;
+    const int cus = std::max(first->n_cu, 1);
+    float ms = 0.0f;
+    // 1. counts, offsets, lists: which part holds every pool position, and where its row will sit
+    PoolArgs pa{};
+    pa.r_pid = p->o_pid + (size_t)q0 * ef; pa.r_count = p->o_cnt + q0;
+    pa.nq = cq; pa.width = ef; pa.fetch = fetch; pa.P = (uint32_t)P;
+    pa.cnt = p->mp_cnt; pa.off = p->mp_off; pa.lid = p->mp_lid; pa.row_of = p->mp_row; pa.bounds = p->mp_bounds;
+    for (size_t i = 0; i <= P; i++) pa.base[i] = p->base[i];
+    const uint32_t lgrid = std::min<uint32_t>(cq, (uint32_t)cus * 32u);
+    if (events) HIPCHK(hipEventRecord(p->mev[0], p->stream));
+    IDIST_LAUNCH(mmr_pool_lists_kernel<false>, lgrid, 64, kPoolListsSmem, p->stream, pa);
+    CHK(range_prefix_on(p->stream, p->mp_chunks, p->mp_cnt, (uint64_t)P * cq, 0, p->mp_off));
+    IDIST_LAUNCH(mmr_pool_lists_kernel<true>, lgrid, 64, kPoolListsSmem, p->stream, pa);
+    HIPCHK(hipGetLastError());
+    if (events) HIPCHK(hipEventRecord(p->mev[1], p->stream));
+    uint64_t bounds[kMergeMaxLists + 1];
+    HIPCHK(hipMemcpyAsync(bounds, p->mp_bounds, (P + 1) * 8, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));             // (the previous chunk's selection is behind us too: the pool may be replaced)
+    if (events) {
+        if (q0) { HIPCHK(hipEventElapsedTime(&ms, p->mev[2], p->mev[3])); p->mmr_select_ms += ms; }
+        HIPCHK(hipEventElapsedTime(&ms, p->mev[0], p->mev[1]));
+        p->mmr_gather_ms += ms;
+    }
+    const uint64_t slots = bounds[P];                    // <= cq * fetch
+    CHK(p->mp_pool.grow(doubled_from(4096, (size_t)std::max<uint64_t>(slots, 1u) * stride * 4)));   // (a row even for no slot: a lane without a position reads row 0)
+    // 2. every part with rows in this chunk, on its own stream: on the merge device straight into its slot range, elsewhere through a
+    //    packed buffer of its own and one peer copy (partitioned_send's pattern; the list reaches it as q_list does in the routed call)
+    auto hip_failed = [&](size_t i, hipError_t e) { return part_failed(p, i, IDIST_ERR_HIP, std::string("row gather: ") + hipGetErrorString(e)); };
+#define PART_HIP(i_, expr_) do { hipError_t e_ = (expr_); if (e_ != hipSuccess) return hip_failed(i_, e_); } while (0)
+    for (size_t i = 0; i < P; i++) {
+        idist_partitioned::Part& pt = p->parts[i];
+        const uint32_t m = (uint32_t)(bounds[i + 1] - bounds[i]);
+        if (!m) continue;                                // (m > 0: the part holds points, so it has a context and a stream)
+        const int32_t dev = part_device(p, i);
+        PART_HIP(i, hipSetDevice(dev));
+        if (!pt.gev0) { PART_HIP(i, hipEventCreate(&pt.gev0)); PART_HIP(i, hipEventCreate(&pt.gev1)); }
+        const uint32_t* d_list = p->mp_lid + bounds[i];
+        float* d_dst = p->mp_pool + bounds[i] * stride;
+        hipStream_t part_stream = pt.ctx->stream;
+        if (dev != p->merge_device) {
+            CHK(pt.mp_list.grow(doubled_from(4096, (size_t)m * 4)));
+            CHK(pt.mp_rows.grow(doubled_from(4096, (size_t)m * stride * 4)));
+            PART_HIP(i, hipMemcpyPeerAsync(pt.mp_list, dev, d_list, p->merge_device, (size_t)m * 4, part_stream));
+            d_list = pt.mp_list;
+            d_dst = pt.mp_rows;
+        }
+        const IndexView pv = pt.idx->view();
+        if (events) PART_HIP(i, hipEventRecord(pt.gev0, part_stream));
+        IDIST_LAUNCH(mmr_pool_gather_kernel, std::min<uint32_t>((m + 31u) / 32u, (uint32_t)cus * 8u), 256, 0, part_stream, pv, d_list, m, d_dst);
+        PART_HIP(i, hipGetLastError());
+        if (events) PART_HIP(i, hipEventRecord(pt.gev1, part_stream));
+        if (dev != p->merge_device)
+            PART_HIP(i, hipMemcpyPeerAsync(p->mp_pool + bounds[i] * stride, p->merge_device, pt.mp_rows, dev, (size_t)m * stride * 4, part_stream));
+    }
+    for (size_t i = 0; i < P; i++) {                     // the merge stream goes on when every part's rows have arrived
+        if (bounds[i + 1] == bounds[i]) continue;
+        idist_partitioned::Part& pt = p->parts[i];
+        PART_HIP(i, hipSetDevice(part_device(p, i)));
+        PART_HIP(i, hipStreamSynchronize(pt.ctx->stream));
+        if (events) { PART_HIP(i, hipEventElapsedTime(&ms, pt.gev0, pt.gev1)); p->mmr_gather_ms += ms; }
+    }
+#undef PART_HIP
+    // 3. the selection, rows by slot
+    HIPCHK(hipSetDevice(p->merge_device));
+    a.r_pid = p->o_pid + (size_t)q0 * ef;
+    a.r_dist = reinterpret_cast<const uint32_t*>(p->o_dist.p) + (size_t)q0 * ef;
+    a.r_count = p->o_cnt + q0;
+    a.r_row = p->mp_row;
+    a.nq = cq;
+    a.o_pid = p->mo_pid + (size_t)q0 * a.k;
+    a.o_dist = reinterpret_cast<uint32_t*>(p->mo_dist.p) + (size_t)q0 * a.k;
+    a.o_rank = p->mo_rank + (size_t)q0 * a.k;
+    a.o_count = p->mo_cnt + q0;
+    IndexView view = first->view();                      // the parts' stride and metric; the rows are the pool's
+    view.points = p->mp_pool;
+    view.n = (uint32_t)slots;
+    const uint32_t grid = std::min<uint32_t>(cq, (uint32_t)cus * (plan.tile ? plan.waves : 16u));
+    if (events) HIPCHK(hipEventRecord(p->mev[2], p->stream));
+    CHK(launch_mmr<true>(first->L, plan, grid, smem, p->stream, view, a));
+    if (events) HIPCHK(hipEventRecord(p->mev[3], p->stream));
+    return IDIST_OK;
+}
+
+idist_status idist_partitioned_search_batch_mmr(idist_partitioned* p, const float* queries, uint32_t nq, uint32_t k, uint32_t fetch,
+                                                float lambda, uint32_t* out_pid, float* out_dist, uint32_t* out_rank, uint32_t* out_count,
+                                                uint32_t* out_counters) {
+    if (!p) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    uint32_t ef = 0;
+    CHK(partitioned_check(p, &ef));
+    if (!(lambda >= 0.0f && lambda <= 1.0f)) return fail(IDIST_ERR_INVALID_ARG, "lambda %g is not in [0, 1]", (double)lambda);
+    if (p->metric == IDIST_METRIC_DOT)
+        return fail(IDIST_ERR_UNSUPPORTED, "diverse search on a DOT index: the relevance there is an inner product, and the pair term over "
+                                           "the augmented rows is not one");
+    if (nq == 0) return IDIST_OK;
+    if (!queries || !out_pid || !out_dist || !out_count) return fail(IDIST_ERR_INVALID_ARG, "null pointer");
+    const size_t P = p->parts.size();
+    if (p->base[P] == 0 || ef == 0) {                    // nothing to select from: every count 0, every row padding
+        for (size_t i = 0; i < (size_t)nq * k; i++) {
+            out_pid[i] = IDIST_INVALID;
+            out_dist[i] = INFINITY;
+            if (out_rank) out_rank[i] = IDIST_INVALID;
+        }
+        memset(out_count, 0, (size_t)nq * 4);
+        if (out_counters) memset(out_counters, 0, (size_t)nq * 12);
+        return IDIST_OK;
+    }
+    if (fetch == 0) fetch = ef;
+    if (k == 0 || k > fetch || fetch > ef)
+        return fail(IDIST_ERR_INVALID_ARG, "k %u, fetch %u, ef_search %u: 1 <= k <= fetch <= ef_search", k, fetch, ef);
+    const idist_index* first = nullptr;                  // a part that holds points: the parts' row layout, the knobs of its context
+    const idist_search_ctx* fctx = nullptr;
+    for (auto& pt : p->parts)
+        if (pt.ctx && !first) { first = pt.idx; fctx = pt.ctx; }
+    const uint32_t stride = first->L.stride;
+    const MmrPlan plan = plan_mmr(first->L, fetch, fctx->knobs.mmr);
+    if (!plan.ok) return fail(IDIST_ERR_INVALID_ARG, "the tile kernel was asked for (test knob), but there is none for this row geometry (stride %u) at fetch %u", stride, fetch);
+    const size_t smem = plan.tile ? mmr_tile_smem(stride) : mmr_global_smem(stride, fetch);
+    if (smem > 64 * 1024) return fail(IDIST_ERR_INVALID_ARG, "dim/fetch need %zu B of LDS per %s (> 64 KiB)", smem, plan.tile ? "workgroup" : "wave");
+    const bool counters = out_counters != nullptr, events = fctx->knobs.events;
+    // 1. idist_partitioned_search_batch up to its merge: the merged lists stay on the merge device, raw
+    CHK(partitioned_search_parts(p, queries, nq, ef, counters));
+    HIPCHK(hipSetDevice(p->merge_device));
+    CHK(partitioned_merge_lists(p, nq, ef, ef, counters));
+    // 2. chunks of queries whose pool stays within 1 GiB (the bound of the HBM tie bags), at least one query each
+    uint32_t chunk = (uint32_t)std::min<size_t>(nq, std::max<size_t>(1, ((size_t)1 << 30) / ((size_t)fetch * stride * 4)));
+    if (const char* e = test_env("IDIST_MMR_CHUNK")) chunk = std::min(chunk, (uint32_t)std::max(1, atoi(e)));   // test knob: the result must not depend on it
+    const size_t ob = (size_t)nq * k * 4, pc = P * chunk;
+    CHK(p->mp_cnt.grow(pc * 4));
+    CHK(p->mp_off.grow((pc + 1) * 8));
+    CHK(p->mp_chunks.grow((pc + 63) / 64 * 8));
+    CHK(p->mp_bounds.grow((P + 1) * 8));
+    CHK(p->mp_lid.grow((size_t)chunk * fetch * 4));
+    CHK(p->mp_row.grow((size_t)chunk * fetch * 4));
+    CHK(p->mo_pid.grow(ob));
+    CHK(p->mo_dist.grow(ob));
+    CHK(p->mo_rank.grow(ob));
+    CHK(p->mo_cnt.grow((size_t)nq * 4));
+    p->mmr_gather_ms = p->mmr_select_ms = -1.0f;
+    if (events) {
+        for (hipEvent_t& e : p->mev)
+            if (!e) HIPCHK(hipEventCreate(&e));
+        p->mmr_gather_ms = p->mmr_select_ms = 0.0f;
+    }
+    MmrArgs a{};
+    a.width = ef;
+    a.k = k;
+    a.fetch = fetch;
+    a.lambda = lambda;
+    a.mu = 1.0f - lambda;
+    a.lam1 = lambda == 1.0f ? 1u : 0u;
+    for (uint32_t q0 = 0; q0 < nq; q0 += chunk) {
+        const idist_status s = partitioned_mmr_chunk(p, first, plan, smem, a, ef, q0, std::min(chunk, nq - q0), events);
+        if (s != IDIST_OK) {
+            p->mmr_gather_ms = p->mmr_select_ms = -1.0f;
+            return s;
+        }
+    }
+    // 3. the report, once, on the [nq][k] selection; the copies out
+    CHK(MetricPasses(p).report(p->mo_dist, p->d_sq, nq, k, p->stream));
+    HIPCHK(hipMemcpyAsync(out_pid, p->mo_pid, ob, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipMemcpyAsync(out_dist, p->mo_dist, ob, hipMemcpyDeviceToHost, p->stream));
+    if (out_rank) HIPCHK(hipMemcpyAsync(out_rank, p->mo_rank, ob, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipMemcpyAsync(out_count, p->mo_cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, p->stream));
+    if (counters) HIPCHK(hipMemcpyAsync(out_counters, p->o_ctr, (size_t)nq * 12, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipStreamSynchronize(p->stream));
+    if (events) {
+        float ms = 0.0f;
+        HIPCHK(hipEventElapsedTime(&ms, p->mev[2], p->mev[3]));
+        p->mmr_select_ms += ms;
+    }
+    return IDIST_OK;
+}
+
+idist_status idist_partitioned_last_mmr_ms(idist_partitioned* p, float* gather_ms, float* select_ms) {
+    if (!p || !gather_ms || !select_ms) return fail(IDIST_ERR_INVALID_ARG, "null argument");
+    if (p->mmr_select_ms < 0.0f) return fail(IDIST_ERR_INVALID_ARG, "no diverse search has been timed for this object (IDIST_KERNEL_EVENTS=0, or no call yet)");
+    *gather_ms = p->mmr_gather_ms;
+    *select_ms = p->mmr_select_ms;
     return IDIST_OK;
 }
 

@@ -33,6 +33,10 @@
 //                           of runtime geometries and of pools above the tile's cap.
 //
 // plan_mmr() chooses between them: a pure host function of the row geometry and the pool size.
+//
+// POOL = true (idist_partitioned_search_batch_mmr): the candidates' rows live in different parts of a partitioned index, so they were
+// gathered into one dense pool first (idist_mmr_pool.hpp) and MmrArgs::r_row names every position's row there.  Both kernels are
+// otherwise the same code; with POOL = false nothing of it is compiled in.
 #pragma once
 #include "idist_grouped_merge.hpp"   // wave_min_u64
 #include "idist_search_plan.hpp"
@@ -50,6 +54,7 @@ struct MmrArgs {
     uint32_t* o_dist;         // [nq][k] raw d of the selected, f32 bit patterns (the metric's report runs behind the kernel)
     uint32_t* o_rank;         // [nq][k] or nullptr
     uint32_t* o_count;        // [nq]
+    const uint32_t* r_row;    // [nq][fetch] POOL kernels: the row of `ix.points` behind every pool position (idist_mmr_pool.hpp); else nullptr
 };
 
 // the key of a candidate in the arg-min: OrderedFloat's order of the score as an unsigned order (NaN above +inf, -0 == +0)
@@ -101,7 +106,7 @@ __device__ __forceinline__ float mmr_chain_step(float w, float p, float acc) {
 #endif
 }
 
-template <int NB, int RS, int TAIL, int RPG, int WAVES>
+template <int NB, int RS, int TAIL, int RPG, int WAVES, bool POOL = false>
 __global__ __launch_bounds__(256) IDIST_MMR_WAVES(WAVES) void mmr_tile_kernel(IndexView ix, MmrArgs a) {
     static_assert(NB >= 0 && RS >= 0 && TAIL >= 0 && RPG >= 1 && RPG <= 32, "compile-time layout only");
     IDIST_DYN_SMEM(smem_raw);
@@ -136,7 +141,9 @@ __global__ __launch_bounds__(256) IDIST_MMR_WAVES(WAVES) void mmr_tile_kernel(In
             // one row pointer, immediate offsets, no branch per load.  A slot no group fills (32 r >= m: workgroup-uniform) is
             // skipped; in the last filled slot the groups beyond the pool re-read row 0, never used (n > 0: the row exists; an id
             // outside the index is never dereferenced)
-            const float* row = ix.points + (size_t)(on && pid[r] < ix.n ? pid[r] : 0u) * ix.stride + j * 4;
+            // (POOL: ix is a view over the row pool of a partitioned index and the row is named by its slot there; the id stays global)
+            const uint32_t rw = POOL ? (on ? a.r_row[(size_t)q * a.fetch + i] : kInvalid) : pid[r];
+            const float* row = ix.points + (size_t)(on && rw < ix.n ? rw : 0u) * ix.stride + j * 4;
             if (32u * (uint32_t)r < m) {
 #pragma unroll
                 for (int u = 0; u < NB; u++) p[r][u] = ldg_row4(row + u * 32);
@@ -229,7 +236,7 @@ __global__ __launch_bounds__(256) IDIST_MMR_WAVES(WAVES) void mmr_tile_kernel(In
 // ---------------------------------------------------------------------------------------------------------------------------------
 inline size_t mmr_global_smem(uint32_t stride, uint32_t fetch) { return smem_bytes(stride, 0, false, 0, 0, false) + (size_t)fetch * 12; }
 
-template <int NB, int RS, int TAIL>
+template <int NB, int RS, int TAIL, bool POOL = false>
 __global__ __launch_bounds__(64) void mmr_global_kernel(IndexView ix, MmrArgs a) {
     IDIST_DYN_SMEM(smem_raw);
     const Smem sm = carve(smem_raw, ix.stride, 0, false, 0, false);
@@ -245,7 +252,8 @@ __global__ __launch_bounds__(64) void mmr_global_kernel(IndexView ix, MmrArgs a)
         const uint32_t kk = a.k < m ? a.k : m;
         wave_sync();                                               // the previous query's reads of the pool are done
         for (uint32_t i = (uint32_t)lane; i < m; i += 64u) {
-            const uint32_t id = a.r_pid[(size_t)q * a.width + i];
+            // (POOL: c_pid holds pool slots — the staged row and dist_rounds' act_pid are slots then; o_pid still comes from r_pid)
+            const uint32_t id = POOL ? a.r_row[(size_t)q * a.fetch + i] : a.r_pid[(size_t)q * a.width + i];
             c_pid[i] = id < ix.n ? id : 0u;                        // (an id outside the index is never dereferenced)
             c_d[i] = __uint_as_float(a.r_dist[(size_t)q * a.width + i]);
             c_m[i] = __uint_as_float(0x7f800000u);

@@ -20,8 +20,8 @@ import numpy as np
 
 from . import _capi
 from ._capi import INVALID, METRIC_COSINE, METRIC_DOT
-from .api import (AllowedResult, Attr, AttrTable, BatchResult, Builder, GroupedResult, Hnsw, Item, RangeResult, _as_points, _attr_values, _Everything, _Match,
-                  _range_rows, _RestrictedSearch, _rows, _Sets, _table_columns, _Where, allowed_bitmap, augment_dot, kmeans, normalize)
+from .api import (AllowedResult, Attr, AttrTable, BatchResult, Builder, GroupedResult, Hnsw, Item, MmrResult, RangeResult, _as_points, _attr_values, _Everything, _Match,
+                  _queries, _range_rows, _RestrictedSearch, _rows, _Sets, _table_columns, _topk_outputs, _Where, allowed_bitmap, augment_dot, kmeans, normalize)
 from .dist import shard_range
 
 
@@ -345,6 +345,28 @@ class PartitionedHnsw(_RestrictedSearch):
         `max_rungs=0` is the true answer over all parts.  `.pid` holds GLOBAL ids, `.rung` has shape (nq, n_parts), the counters are
         summed over the parts; one part, or every point its own group, give `Hnsw.search_grouped` / `search_match` bit for bit."""
         return self._grouped(queries, table, by, conds, k, max_rungs, counters)
+
+    def search_mmr(self, queries, k: int = 10, lam: float = 0.5, fetch: int | None = None, counters: bool = False) -> MmrResult:
+        """k results that are near the query and not near each other, over the whole set (idist_partitioned_search_batch_mmr):
+        `Hnsw.search_mmr`'s selection over the first `fetch` entries of `search_batch`'s merged list, the pair distances between
+        the stored rows of the parts that hold them — gathered on the GPU into one pool on the merge device, selected there.
+        `.pids` holds GLOBAL ids, `.ranks` positions in the merged list, the counters are summed over the parts.  One part gives
+        `Hnsw.search_mmr` bit for bit, `lam=1` the first k columns of `search_batch`.  METRIC_DOT is refused."""
+        q = _queries(queries, self.info())
+        nq, k = q.shape[0], max(int(k), 0)
+        pid, dist, cnt, _, ctr = _topk_outputs(nq, k, (nq,), counters)
+        rank = np.full((nq, k), INVALID, dtype=np.uint32)
+        L = _lib()
+        L.check(L.idist_partitioned_search_batch_mmr(self._h, _capi.f32p(q), nq, k, int(fetch or 0), float(lam), _capi.u32p(pid),
+                                                     _capi.f32p(dist), _capi.u32p(rank), _capi.u32p(cnt), _capi.u32p(ctr) if counters else None))
+        return MmrResult(pid, dist, rank, cnt, ctr)
+
+    def last_mmr_ms(self) -> tuple[float, float]:
+        """HIP-event durations of the last `search_mmr`, milliseconds: (the pool's list and row-gather kernels, the selection kernel),
+        each summed over the call's chunks of queries."""
+        g, s = C.c_float(0.0), C.c_float(0.0)
+        _lib().check(_lib().idist_partitioned_last_mmr_ms(self._h, C.byref(g), C.byref(s)))
+        return float(g.value), float(s.value)
 
     def search_one_range(self, point, radius) -> list[Item]:
         """One query: every item within `radius`, nearest first; `Item.pid` is the global id."""
